@@ -1,14 +1,18 @@
 #!/usr/bin/env python3
 """Benchmark of the field-solve hot path: Jacobi-PCG iterations/s on the (synthetic) 40 nm
-crossbar K matrix, row-partitioned over N GPUs, plus the CSR-SpMV roofline line and a CPU
-baseline.  Contract: see the task description / DESIGN.md "Measurement".
+crossbar K matrix, row-partitioned over N GPUs.  Contract: DESIGN.md "Measurement".
 
     python bench.py --gpus 1 --steps 300 --warmup 30
+    python bench.py --gpus 1 --steps 300 --warmup 30 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 A "step" is one PCG iteration (1 SpMV with fused p.Ap, the x/r/z update with fused r.z, the
-p update) on the assembled K matrix with the matrix and all vectors resident in HBM.
+p update) on the assembled K matrix with the matrix and all vectors resident in HBM.  A plain run
+sets up, warms up, times ONE solve of --steps iterations and prints the line.  --full adds what
+takes runs of its own: the median of 5 timed solves, the SpMV roofline lines (the CSR and f64
+re-plans, the beyond-cache probe), the multi-rank per-piece timings and the CPU baseline.
+--dump-outputs DIR writes what the last timed solve hands its caller (x, r, the solve's scalars).
 """
 import argparse
 import json
@@ -79,12 +83,18 @@ def main():
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--workload", default="40nm", choices=["40nm", "5nm", "small"])
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: median of 5 solves, SpMV roofline lines, "
+                         "multi-rank per-piece timings, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed solves: write x, r and the scalars of the last one as DIR/<name>.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-iters", type=int, default=0, help="CPU baseline iterations (0 = auto, ~10-30 s)")
-    ap.add_argument("--spmv-reps", type=int, default=50)
-    ap.add_argument("--repeats", type=int, default=5, help="timed solves of --steps iterations each; the line reports their median "
-                                                           "(the authors' protocol: median of 5 after warm-up, main_test_cg.cpp:209-211)")
-    ap.add_argument("--no-hbm-probe", action="store_true", help="skip the beyond-cache SpMV measurement (roofline_hbm)")
+    ap.add_argument("--cpu-iters", type=int, default=0, help="CPU baseline iterations (0 = auto, ~10-30 s; --full)")
+    ap.add_argument("--spmv-reps", type=int, default=50, help="launches per SpMV roofline measurement (--full)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed solves of --steps iterations each; the line reports their median (default 1, with --full 5: "
+                         "the authors' protocol, median of 5 after warm-up, main_test_cg.cpp:209-211)")
+    ap.add_argument("--no-hbm-probe", action="store_true", help="skip the beyond-cache SpMV measurement (roofline_hbm; --full)")
     ap.add_argument("--diag-solves", type=int, default=0, help="after the timed region: time N more solves piecewise (stderr)")
     ap.add_argument("--transport", default="auto", choices=["auto", "rccl", "p2p", "p2p-only"],
                     help="multi-rank data path: auto = peer-to-peer windows if they come up, else RCCL; p2p-only = no RCCL at "
@@ -92,6 +102,8 @@ def main():
     ap.add_argument("--launch-timeout", type=float, default=1500.0,
                     help="--gpus N > 1 without WORLD_SIZE: seconds the self-launched ranks may take before they are ended")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` as one plain command: this process becomes the launcher.  It touches no GPU
@@ -153,7 +165,7 @@ def main():
     S.k_assemble(buf, d["Vd"], d["high_G"], d["low_G"])
     mat = S.Distributed_matrix.from_handle(km.lib.load().kmcf_kstate_matrix(buf.K_distributed))
     info = mat.info()
-    vec = S.k_vectors(buf) if (rank == 0 and world == 1 and not args.no_cpu_baseline) else None
+    vec = S.k_vectors(buf) if (args.full and rank == 0 and world == 1 and not args.no_cpu_baseline) else None
     t_setup = time.time() - t_gen
     n_loc = info["rows_this_rank"]
     nnz_loc = info["nnz"]
@@ -191,6 +203,7 @@ def main():
 
     # ---- warmup + timed CG iterations -----------------------------------------------------
     tol = 1e-14 * n_if
+    last = {}           # what the latest timed solve handed back: --dump-outputs writes it
 
     def timed_solve(steps, warmup):
         r, x, dinv = fresh_vectors()
@@ -204,6 +217,7 @@ def main():
         barrier()
         el = torch.tensor([time.perf_counter() - t0], dtype=torch.float64)
         assert st["iterations"] == steps, st
+        last.update(r=r, x=x, st=st)
         if world > 1:
             dist.all_reduce(el, op=dist.ReduceOp.MAX)
         return float(el.item()), st
@@ -273,6 +287,24 @@ def main():
     order = sorted(range(len(runs)), key=lambda i: runs[i][0])
     elapsed, st = runs[order[len(runs) // 2]]
     all_ms = [round(r[0] * 1e3 / args.steps, 5) for r in runs]
+    if args.dump_outputs:
+        # the last timed solve's x (solution) and r (residual), gathered to rank 0 in row order (the ranks own consecutive
+        # row blocks), and its scalars.  At 40 nm the two vectors are 12.8 MB each; one beyond 32 MB would be written as a
+        # fixed stride sample, so that the files stay within 64 MB
+        vecs = {"x": last["x"].cpu().numpy(), "r": last["r"].cpu().numpy()}
+        if world > 1:
+            got = [None] * world if rank == 0 else None
+            dist.gather_object(vecs, got, dst=0)
+            if rank == 0:
+                vecs = {k: np.concatenate([g[k] for g in got]) for k in vecs}
+        if rank == 0:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            cap = 4 * 2 ** 20
+            for k, v in vecs.items():
+                np.save(os.path.join(args.dump_outputs, k + ".npy"), v[::max(1, -(-v.size // cap))].astype(np.float64))
+            s = last["st"]
+            np.save(os.path.join(args.dump_outputs, "solve_stats.npy"),      # iterations, converged, relres, b.b, r.z
+                    np.array([s["iterations"], s["converged"], s["relres"], s["bb"], s["rz"]], dtype=np.float64))
     for _ in range(args.diag_solves):           # tuning aid: where a solve's wall time goes
         r, x, dinv = fresh_vectors()
         barrier()
@@ -284,56 +316,58 @@ def main():
         sys.stderr.write("diag solve: call %.1f us, trailing barrier %.1f us, device %.1f us\n"
                          % ((tb - ta) * 1e6, (tc - tb) * 1e6, st2["ms_solve"] * 1e3))
 
-    # ---- roofline of the dominant kernel: CSR SpMV (+ fused p.Ap) -------------------------
-    # HIP events on the library's compute stream (kmcf_spmv_bench), this rank's rows
-    mat.spmv_bench(5, True)
-    ms = mat.spmv_bench(args.spmv_reps, True)
-    spmv_us = ms * 1e3 / args.spmv_reps
-    # Algorithmic bytes of one launch = what the kernel's matrix format makes it read and write once
-    # (DESIGN.md 3.1): CSR 12 B/nnz + 20 B/row; window format 10 B/nnz (f64 value + 16-bit
-    # slot) + 4 B per window column + 20 B/row; dictionary-coded window format 2 B/nnz + 4 B per window column
-    # + 28 B/row (row_ptr, diagonal, x, y); row-per-lane coded format below.  csr_equivalent prices the same launch at the CSR figure.
-    minfo = mat.info()
-    csr_bytes = 12.0 * nnz_loc + 20.0 * n_loc
-    if minfo["spmv_kind"] == 2 and minfo["spmv_coded"] == 2:
-        # row-per-lane coded format: 2 B per streamed entry (off-diagonals + padding to the wave's longest row) +
-        # 4 B per window column + 28 B/row (lane row, diagonal, x, y) + 48 B of descriptors per tile
-        kname = "spmv_sell_kernel (row-per-lane window SpMV, dictionary-coded values, fused p.Ap)"
-        alg_bytes = (2.0 * minfo["spmv_stream_entries"] + 4.0 * minfo["spmv_window_cols"] + 28.0 * n_loc
-                     + 48.0 * minfo["spmv_tiles"])
-    elif minfo["spmv_kind"] == 2 and minfo["spmv_coded"]:
-        kname = "spmv_wcode_kernel (window SpMV, dictionary-coded values, fused p.Ap)"
-        alg_bytes = 2.0 * nnz_loc + 4.0 * minfo["spmv_window_cols"] + 28.0 * n_loc
-    elif minfo["spmv_kind"] == 2:
-        kname = "spmv_window_kernel (window SpMV, f64 values, fused p.Ap)"
-        alg_bytes = 10.0 * nnz_loc + 4.0 * minfo["spmv_window_cols"] + 20.0 * n_loc
-    else:
-        kname = "%s (CSR SpMV, fused p.Ap)" % ("spmv_stream_kernel" if minfo["spmv_kind"] == 1 else "spmv_vec_kernel")
-        alg_bytes = csr_bytes
-    achieved = alg_bytes / (spmv_us * 1e-6) / 1e9
-    csr_eq = csr_bytes / (spmv_us * 1e-6) / 1e9
-    # what one launch streams: its matrix format + the vectors it touches (x gathered, y written, row data)
-    vec_bytes = 8.0 * n_loc * 2
-    working_set = alg_bytes + vec_bytes
-    mall = 256 * 2 ** 20
-    roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None,
-                "kernel": kname, "us_per_launch": round(spmv_us, 2),
-                "algorithmic_bytes_per_launch": int(alg_bytes),
-                "working_set_bytes": int(working_set), "fits_infinity_cache": bool(working_set < mall),
-                "note": "frac = format bytes / launch time / 8 TB/s.  With the 2 B/nnz format the launch's working set "
-                        "fits the 256 MiB Infinity Cache and FETCH_SIZE counts its hits, so this is an effective "
-                        "bandwidth against the HBM peak, not a measured HBM fraction; the CSR kernel's figure on "
-                        "SURVEY 8d's bytes is in roofline_csr",
-                "csr_equivalent": {"bytes_per_launch": int(csr_bytes), "achieved": round(csr_eq, 1),
-                                   "frac": round(csr_eq / HBM_PEAK_GBS, 4)}}
+    roofline = None
+    if args.full:
+        # ---- roofline of the dominant kernel: CSR SpMV (+ fused p.Ap) -------------------------
+        # HIP events on the library's compute stream (kmcf_spmv_bench), this rank's rows
+        mat.spmv_bench(5, True)
+        ms = mat.spmv_bench(args.spmv_reps, True)
+        spmv_us = ms * 1e3 / args.spmv_reps
+        # Algorithmic bytes of one launch = what the kernel's matrix format makes it read and write once
+        # (DESIGN.md 3.1): CSR 12 B/nnz + 20 B/row; window format 10 B/nnz (f64 value + 16-bit
+        # slot) + 4 B per window column + 20 B/row; dictionary-coded window format 2 B/nnz + 4 B per window column
+        # + 28 B/row (row_ptr, diagonal, x, y); row-per-lane coded format below.  csr_equivalent prices the same launch at the CSR figure.
+        minfo = mat.info()
+        csr_bytes = 12.0 * nnz_loc + 20.0 * n_loc
+        if minfo["spmv_kind"] == 2 and minfo["spmv_coded"] == 2:
+            # row-per-lane coded format: 2 B per streamed entry (off-diagonals + padding to the wave's longest row) +
+            # 4 B per window column + 28 B/row (lane row, diagonal, x, y) + 48 B of descriptors per tile
+            kname = "spmv_sell_kernel (row-per-lane window SpMV, dictionary-coded values, fused p.Ap)"
+            alg_bytes = (2.0 * minfo["spmv_stream_entries"] + 4.0 * minfo["spmv_window_cols"] + 28.0 * n_loc
+                         + 48.0 * minfo["spmv_tiles"])
+        elif minfo["spmv_kind"] == 2 and minfo["spmv_coded"]:
+            kname = "spmv_wcode_kernel (window SpMV, dictionary-coded values, fused p.Ap)"
+            alg_bytes = 2.0 * nnz_loc + 4.0 * minfo["spmv_window_cols"] + 28.0 * n_loc
+        elif minfo["spmv_kind"] == 2:
+            kname = "spmv_window_kernel (window SpMV, f64 values, fused p.Ap)"
+            alg_bytes = 10.0 * nnz_loc + 4.0 * minfo["spmv_window_cols"] + 20.0 * n_loc
+        else:
+            kname = "%s (CSR SpMV, fused p.Ap)" % ("spmv_stream_kernel" if minfo["spmv_kind"] == 1 else "spmv_vec_kernel")
+            alg_bytes = csr_bytes
+        achieved = alg_bytes / (spmv_us * 1e-6) / 1e9
+        csr_eq = csr_bytes / (spmv_us * 1e-6) / 1e9
+        # what one launch streams: its matrix format + the vectors it touches (x gathered, y written, row data)
+        vec_bytes = 8.0 * n_loc * 2
+        working_set = alg_bytes + vec_bytes
+        mall = 256 * 2 ** 20
+        roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None,
+                    "kernel": kname, "us_per_launch": round(spmv_us, 2),
+                    "algorithmic_bytes_per_launch": int(alg_bytes),
+                    "working_set_bytes": int(working_set), "fits_infinity_cache": bool(working_set < mall),
+                    "note": "frac = format bytes / launch time / 8 TB/s.  With the 2 B/nnz format the launch's working set "
+                            "fits the 256 MiB Infinity Cache and FETCH_SIZE counts its hits, so this is an effective "
+                            "bandwidth against the HBM peak, not a measured HBM fraction; the CSR kernel's figure on "
+                            "SURVEY 8d's bytes is in roofline_csr",
+                    "csr_equivalent": {"bytes_per_launch": int(csr_bytes), "achieved": round(csr_eq, 1),
+                                       "frac": round(csr_eq / HBM_PEAK_GBS, 4)}}
 
     # ---- the CSR SpMV the roofline target is written for (12 B/nnz + 20 B/row) ----------------------
     # the same matrix re-planned onto the CSR stream kernel (f64 values + i32 columns), timed the same way, then
     # the default plan is restored
     roofline_csr = None
     roofline_f64 = None
-    if world == 1 and minfo["spmv_kind"] == 2:
+    if args.full and world == 1 and minfo["spmv_kind"] == 2:
         saved = {k: os.environ.get(k) for k in ("KMCF_SPMV_KIND", "KMCF_SPMV_CODED")}
         try:
             # what the planner gives a matrix WITHOUT a small value dictionary (general f64 values): the row-per-lane
@@ -383,7 +417,7 @@ def main():
     # cells (3.6 M rows, ~350 MB of format: larger than the 256 MiB Infinity Cache), where its bytes really come from
     # HBM.  Generated and measured here, after the timed region; this is the HBM fraction of the kernel `value` runs on.
     roofline_hbm = None
-    if world == 1 and args.workload == "40nm" and not args.no_hbm_probe and minfo["spmv_coded"] == 2:
+    if args.full and world == 1 and args.workload == "40nm" and not args.no_hbm_probe and minfo["spmv_coded"] == 2:
         try:
             d2 = km.structure.synth_crossbar_40nm(tiles=12)
             NL2 = d2["N_contact"]
@@ -425,29 +459,30 @@ def main():
                 "ranks_per_device": int(os.environ.get("KMCF_DEVICE_SHARE", "1"))}
         if transports is not None:
             diag["transports"] = transports
-        used_p2p = comm.transport().startswith("p2p")
-        has_rccl = transports is not None and "rccl" in transports
-        for name, use in ((("rccl", 0), ("p2p", 1)) if has_rccl else ((comm.transport(), None),)):
-            if transports is not None and "error" in transports.get(name, {}):
-                continue
-            try:
-                if use is not None:
-                    comm.select_transport(use)
-                d_t = {}
-                for kind, key in ((0, "allreduce3_us"), (1, "halo_exchange_us"), (2, "spmv_kernels_us")):
-                    mat.comm_bench(kind, 10)
-                    d_t[key] = round(mat.comm_bench(kind, reps) * 1e3 / reps, 2)
-                diag[name] = d_t
-            except km.lib.KmcfError as e:
-                diag[name] = {"error": str(e)[:200]}
-        if has_rccl:
-            comm.select_transport(1 if used_p2p else 0)
+        if args.full:                               # per-piece timings of one distributed iteration
+            used_p2p = comm.transport().startswith("p2p")
+            has_rccl = transports is not None and "rccl" in transports
+            for name, use in ((("rccl", 0), ("p2p", 1)) if has_rccl else ((comm.transport(), None),)):
+                if transports is not None and "error" in transports.get(name, {}):
+                    continue
+                try:
+                    if use is not None:
+                        comm.select_transport(use)
+                    d_t = {}
+                    for kind, key in ((0, "allreduce3_us"), (1, "halo_exchange_us"), (2, "spmv_kernels_us")):
+                        mat.comm_bench(kind, 10)
+                        d_t[key] = round(mat.comm_bench(kind, reps) * 1e3 / reps, 2)
+                    diag[name] = d_t
+                except km.lib.KmcfError as e:
+                    diag[name] = {"error": str(e)[:200]}
+            if has_rccl:
+                comm.select_transport(1 if used_p2p else 0)
 
     # HBM traffic of that kernel from rocprofv3 PMC runs (separate FETCH_SIZE / WRITE_SIZE passes, gfx950
     # corrections applied by tools/pmc_summary.py); measured offline on this workload, committed under
     # profiles/, and only reported when it was taken on the same matrix
     tpath = os.path.join(ROOT, "profiles", "spmv_traffic.json")
-    if world == 1 and os.path.exists(tpath):
+    if args.full and world == 1 and os.path.exists(tpath):
         tj = json.load(open(tpath))
         entries = tj["kernels"] if "kernels" in tj else [tj]
         # a committed figure is only reported for the kernel source it was measured on (tools/pmc_summary.py stamps

@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_line_contract():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "small", "--steps", "40",
-                          "--warmup", "4", "--cpu-iters", "20", "--spmv-reps", "20"],
+                          "--warmup", "4", "--cpu-iters", "20", "--spmv-reps", "20", "--full"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -36,6 +36,33 @@ def test_bench_line_contract():
     assert abs(r["achieved"] - r["algorithmic_bytes_per_launch"] / (r["us_per_launch"] * 1e-6) / 1e9) <= 0.01 * r["achieved"] + 0.1
     c = j["cpu_baseline"]
     assert c["kind"] == "port" and c["unit"] == "iterations/s" and c["value"] > 0 and 1 <= c["cores"] <= 16
+
+
+def test_plain_bench_times_one_solve_and_dumps_its_outputs(tmp_path):
+    """Without --full: ONE timed solve of --steps iterations, none of the extra measurements; --dump-outputs writes the
+    last timed solve's x, r and scalars, the same on a second run with the same arguments."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        d = tmp_path / ("run%d" % i)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "small", "--steps", "40",
+                              "--warmup", "4", "--dump-outputs", str(d)],
+                             capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out.stdout[-2000:]
+        j = json.loads(lines[0])
+        assert j["steps"] == 40 and j["warmup"] == 4 and j["repeats"] == 1 and len(j["ms_per_step_all"]) == 1
+        assert j["value"] > 0 and abs(j["value"] * j["ms_per_step"] / 1e3 - 1.0) < 1e-3
+        assert j["roofline"] is None and j["roofline_hbm"] is None and j["cpu_baseline"] is None
+        got = {k: np.load(d / (k + ".npy")) for k in ("x", "r", "solve_stats")}
+        assert sorted(os.listdir(d)) == ["r.npy", "solve_stats.npy", "x.npy"]
+        assert all(v.dtype == np.float64 for v in got.values())
+        assert got["x"].shape == got["r"].shape == (j["config"]["rows"],)
+        assert got["solve_stats"][0] == 40 and np.isfinite(got["x"]).all() and np.abs(got["x"]).max() > 0
+        dumps.append(got)
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
 
 
 def test_bench_self_launches_two_ranks():

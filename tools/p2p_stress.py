@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Stress: in-process p2p groups set up and run repeatedly (intermittent set-up time-outs)."""
 import os, sys, threading, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "24")
+if not os.environ.get("GPU_MAX_HW_QUEUES", "").isdigit() or int(os.environ["GPU_MAX_HW_QUEUES"]) < 24:
+    os.environ["GPU_MAX_HW_QUEUES"] = "24"      # in-process groups: every stream its own hardware queue (tests/conftest.py)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np, torch

@@ -11,11 +11,11 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 echo "== kernel trace + stats"
 rocprofv3 --kernel-trace --stats -d $OUT/stats -o b --output-format csv -- \
-    python3 $R/bench.py --no-cpu-baseline --steps 20 --warmup 3 > $OUT/bench_line.json 2> $OUT/stats.log
+    python3 $R/bench.py --full --no-cpu-baseline --steps 20 --warmup 3 > $OUT/bench_line.json 2> $OUT/stats.log
 tail -1 $OUT/bench_line.json
 for c in FETCH_SIZE WRITE_SIZE; do
   echo "== pmc $c"
   rocprofv3 --kernel-trace --pmc $c -d $OUT/pmc_$c -o x --output-format csv -- \
-      python3 $R/bench.py --no-cpu-baseline --steps 30 --warmup 2 --spmv-reps 5 > $OUT/pmc_$c.json 2> $OUT/pmc_$c.log
+      python3 $R/bench.py --full --no-cpu-baseline --steps 30 --warmup 2 --spmv-reps 5 > $OUT/pmc_$c.json 2> $OUT/pmc_$c.log
 done
 python3 $R/tools/pmc_summary.py $OUT/pmc_FETCH_SIZE $OUT/pmc_WRITE_SIZE $OUT/pmc_spmv

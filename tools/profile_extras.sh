@@ -16,7 +16,7 @@ echo "== KMC loop, 40 nm, 77 K"
 python3 $R/tools/kmc_loop.py --workload 40nm --T 77 --steps 3 > $OUT/kmc_loop_40nm.txt 2>&1 || true
 python3 $R/tools/kmc_loop.py --workload 5nm --steps 6 > $OUT/kmc_loop_5nm.txt 2>&1 || true
 echo "== a rank's share of the 40 nm matrix (1/8) and the 5 nm device on one GPU"
-python3 $R/bench.py --workload small --no-cpu-baseline --steps 100 2>/dev/null | tail -1 > $OUT/bench_small.json
-python3 $R/bench.py --workload 5nm --no-cpu-baseline --steps 100 2>/dev/null | tail -1 > $OUT/bench_5nm.json
-python3 $R/bench.py --no-cpu-baseline --steps 20 --warmup 3 2>/dev/null | tail -1 > $OUT/bench_steps20.json
+python3 $R/bench.py --full --workload small --no-cpu-baseline --steps 100 2>/dev/null | tail -1 > $OUT/bench_small.json
+python3 $R/bench.py --full --workload 5nm --no-cpu-baseline --steps 100 2>/dev/null | tail -1 > $OUT/bench_5nm.json
+python3 $R/bench.py --full --no-cpu-baseline --steps 20 --warmup 3 2>/dev/null | tail -1 > $OUT/bench_steps20.json
 echo done

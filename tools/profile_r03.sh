@@ -7,12 +7,12 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 echo "== bench: kernel trace + stats (the driver's command line)"
 rocprofv3 --kernel-trace --stats -d $OUT/stats -o b --output-format csv -- \
-    python3 $R/bench.py --steps 20 --warmup 5 --no-hbm-probe > $OUT/bench_line.json 2> $OUT/stats.log   # (the probe launches the SAME kernel on a larger matrix: profiled separately below, so that this summary's average is the 40 nm launch)
+    python3 $R/bench.py --full --steps 20 --warmup 5 --no-hbm-probe > $OUT/bench_line.json 2> $OUT/stats.log   # (the probe launches the SAME kernel on a larger matrix: profiled separately below, so that this summary's average is the 40 nm launch)
 tail -c 400 $OUT/bench_line.json; echo
 for c in FETCH_SIZE WRITE_SIZE; do
   echo "== pmc $c: 40 nm matrix (coded row-per-lane kernel, CSR stream kernel)"
   rocprofv3 --kernel-trace --pmc $c -d $OUT/pmc_$c -o x --output-format csv -- \
-      python3 $R/bench.py --no-cpu-baseline --no-hbm-probe --steps 30 --warmup 2 --repeats 1 --spmv-reps 5 > $OUT/pmc_$c.json 2> $OUT/pmc_$c.log
+      python3 $R/bench.py --full --no-cpu-baseline --no-hbm-probe --steps 30 --warmup 2 --repeats 1 --spmv-reps 5 > $OUT/pmc_$c.json 2> $OUT/pmc_$c.log
   echo "== pmc $c: 12 x 12 device (3.6 M rows, beyond the Infinity Cache)"
   LAB_TILES=12 rocprofv3 --kernel-trace --pmc $c -d $OUT/pmcbig_$c -o x --output-format csv -- \
       python3 $R/tools/spmv_lab.py "SELL=1" > $OUT/pmcbig_$c.txt 2> $OUT/pmcbig_$c.log
@@ -32,14 +32,14 @@ KMCF_EVENTS_PERSISTENT=0 python3 $R/tools/kmc_loop.py --workload 40nm --T 77 --s
 python3 $R/tools/kmc_loop.py --workload 5nm --steps 6 > $E/kmc_loop_5nm.txt 2>&1
 rocprofv3 --kernel-trace --stats -d $E/events -o e --output-format csv -- python3 $R/tools/kmc_loop.py --workload 40nm --T 77 --steps 1 > $E/events.log 2>&1
 for v in classic cg1r; do
-  KMCF_CG_VARIANT=$v python3 $R/bench.py --workload small --no-cpu-baseline --no-hbm-probe --steps 300 --warmup 30 2>/dev/null | tail -1 > $E/bench_small_$v.json
+  KMCF_CG_VARIANT=$v python3 $R/bench.py --full --workload small --no-cpu-baseline --no-hbm-probe --steps 300 --warmup 30 2>/dev/null | tail -1 > $E/bench_small_$v.json
 done
 KMCF_CG_VARIANT=cg1r rocprofv3 --kernel-trace --stats -d $E/small_cg1r -o s --output-format csv -- \
-    python3 $R/bench.py --workload small --no-cpu-baseline --no-hbm-probe --steps 300 --warmup 30 --repeats 2 > /dev/null 2>&1
+    python3 $R/bench.py --full --workload small --no-cpu-baseline --no-hbm-probe --steps 300 --warmup 30 --repeats 2 > /dev/null 2>&1
 rocprofv3 --kernel-trace --stats -d $E/small_classic -o s --output-format csv -- \
-    python3 $R/bench.py --workload small --no-cpu-baseline --no-hbm-probe --steps 300 --warmup 30 --repeats 2 > /dev/null 2>&1
-python3 $R/bench.py --workload 5nm --no-cpu-baseline --steps 100 2>/dev/null | tail -1 > $E/bench_5nm.json
-python3 $R/bench.py --no-cpu-baseline --no-hbm-probe --steps 300 --warmup 30 2>/dev/null | tail -1 > $E/bench_steps300.json
+    python3 $R/bench.py --full --workload small --no-cpu-baseline --no-hbm-probe --steps 300 --warmup 30 --repeats 2 > /dev/null 2>&1
+python3 $R/bench.py --full --workload 5nm --no-cpu-baseline --steps 100 2>/dev/null | tail -1 > $E/bench_5nm.json
+python3 $R/bench.py --full --no-cpu-baseline --no-hbm-probe --steps 300 --warmup 30 2>/dev/null | tail -1 > $E/bench_steps300.json
 cd $R && timeout -k 10 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 \
-    bench.py --gpus 2 --steps 100 --warmup 10 --transport p2p-only --no-cpu-baseline --no-hbm-probe 2>/dev/null | tail -1 > $E/bench_2ranks_one_gpu.json
+    bench.py --full --gpus 2 --steps 100 --warmup 10 --transport p2p-only --no-cpu-baseline --no-hbm-probe 2>/dev/null | tail -1 > $E/bench_2ranks_one_gpu.json
 echo done

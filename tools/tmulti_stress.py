@@ -2,7 +2,8 @@
 """Stress: tests/test_gpu_tpath.py::test_small_device_multirank, its four variants in the suite's order, cycle after cycle
 in ONE process (the history a full-suite run has when the open build flake of DESIGN 11 shows)."""
 import os, sys
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "24")      # in-process groups: every stream its own hardware queue (tests/conftest.py)
+if not os.environ.get("GPU_MAX_HW_QUEUES", "").isdigit() or int(os.environ["GPU_MAX_HW_QUEUES"]) < 24:
+    os.environ["GPU_MAX_HW_QUEUES"] = "24"      # in-process groups: every stream its own hardware queue (tests/conftest.py)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import torch
