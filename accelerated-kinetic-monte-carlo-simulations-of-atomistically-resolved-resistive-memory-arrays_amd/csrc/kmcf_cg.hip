@@ -288,7 +288,7 @@ int vec_grid(int n) { return kmcf_vec_grid(n); }
 // chunk's last kernel): {done, iterations, this check's number} -- and the host polls the number instead of sleeping in
 // hipStreamSynchronize, whose wake-up costs more than the ten iterations a small system runs meanwhile (5 nm device:
 // 13 checks per cold solve).  After 3 ms without an answer it sleeps in
-// hipStreamSynchronize after all; KMCF_CG_SYNC=stream: always.
+// hipStreamSynchronize after all.
 __global__ void cg_mark_kernel(const kmcf_scalars *__restrict__ S, int *__restrict__ host3, int number)
 {
     if (threadIdx.x != 0) return;
@@ -299,13 +299,6 @@ __global__ void cg_mark_kernel(const kmcf_scalars *__restrict__ S, int *__restri
 }
 int cg_chunk_check(kmcf_comm *c, const kmcf_scalars *S, hipStream_t st, bool *done)
 {
-    static const bool use_stream = getenv("KMCF_CG_SYNC") && strcmp(getenv("KMCF_CG_SYNC"), "stream") == 0;
-    if (use_stream) {
-        KMCF_HIP(hipMemcpyAsync(c->h_pinned, &S->done, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
-        KMCF_HIP(hipStreamSynchronize(st));
-        *done = c->h_pinned[0] != 0;
-        return KMCF_OK;
-    }
     if (c->mark_seq == 0x7fffffff) c->mark_seq = 0;
     const int number = ++c->mark_seq;
     // the word the host polls must differ from the number waited for BEFORE the kernel that writes it is enqueued
@@ -707,7 +700,8 @@ int pcg1_loop(kmcf_matrix *m, double tol, int max_it, int fixed_iters, kmcf_solv
     // where the all-reduce of a fused iteration runs: inside the update kernel (every block waits for the P flags: one
     // kernel fewer; right when every rank has a GPU of its own) or in a 1-block kernel in front of it (KMCF_P2P_AR=split:
     // ranks SHARING a GPU -- rehearsals -- otherwise fill it with waiting blocks); bench.py times both and keeps the faster
-    const bool ar_inside = !(getenv("KMCF_P2P_AR") && strcmp(getenv("KMCF_P2P_AR"), "split") == 0);
+    const char *ar = kmcf_knob(KNOB_P2P_AR);
+    const bool ar_inside = !(ar && strcmp(ar, "split") == 0);
     const bool p2p_red = multi && c->nranks > 1 && c->p2p_active;
     const u64 red0 = p2p_red ? kmcf_p2p_red_seq(c) : 0, halo0 = fused ? *kmcf_p2p_halo_seq(m, 0) : 0;
 
@@ -1025,7 +1019,7 @@ extern "C" int kmcf_pcg_jacobi(kmcf_matrix *m, double *d_r, double *d_x, const d
     KMCF_CHECK(max_iterations >= 0 && fixed_iters >= 0, KMCF_ERR_ARG, "kmcf_pcg_jacobi: negative iteration count");
     kmcf_comm *c = m->comm;
     KMCF_CHECK(c->connected, KMCF_ERR_COMM, "kmcf_pcg_jacobi: communicator not connected");
-    const bool trace = getenv("KMCF_TRACE") != nullptr;
+    const bool trace = kmcf_trace();
     auto now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t_0 = trace ? now() : 0.0;
     KMCF_TRY(kmcf_enter(c));

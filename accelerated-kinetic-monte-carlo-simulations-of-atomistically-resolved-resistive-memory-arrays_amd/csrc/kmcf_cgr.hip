@@ -90,7 +90,7 @@ struct cgr_args {
     // also fail for skew between blocks, which no delay cures, and a coarse delay creeps up; the best fixed pair per size reads
     // 10.1 / 5.6).
     int gather_delay, reduce_delay, adapt_delay;
-    int sibling_lds;                 // 1: window columns owned by a sibling tile of the block come out of LDS (KMCF_CGR_SIB=0: through the granules)
+    int sibling_lds;                 // 1: window columns owned by a sibling tile of the block come out of LDS (0: through the granules; the host passes 1)
     // groups of ranks (peer-to-peer transport; kmcf_p2p_dev.hpp): nranks == 1 -> everything below unused
     int nranks, rank, n_loc;
     const int *put_row, *putr_ptr;             // per internal row: its entry list (-1: not sent) | entries of a sent row
@@ -684,10 +684,21 @@ int cgr_run_any(const kmcf_matrix *m, int tpb, const cgr_args &A, bool launch, h
     }
 }
 
+// Bound of the resident launch's device-side waits in wall-clock ticks: KMCF_CGR_TIMEOUT_MS if set, else a group's
+// transport bound (KMCF_P2P_TIMEOUT_MS), else 4 s.
+int cgr_timeout_ticks(const kmcf_comm *c, long long *ticks)
+{
+    const char *e = kmcf_knob(KNOB_CGR_TIMEOUT_MS);
+    if (!e && c->nranks > 1 && c->p2p) { *ticks = c->p2p->timeout_ticks; return KMCF_OK; }
+    int rate_khz = 0;
+    KMCF_HIP(hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, c->device));
+    *ticks = (long long)rate_khz * (e ? atoll(e) : 4000);
+    return KMCF_OK;
+}
+
 int cgr_mode()
 {
-    const char *e = getenv("KMCF_CG_RESIDENT");
-    return e ? atoi(e) : 1;                  // 0 off, 1 where a matrix qualifies
+    return kmcf_knob_int(KNOB_CG_RESIDENT, 1);      // 0 off, 1 where a matrix qualifies
 }
 
 }  // namespace
@@ -732,7 +743,7 @@ static int cgr_plan(kmcf_matrix *m)
     const int share = std::max(kmcf_device_share(), c->group ? c->nranks : 1);
     cgr_args A{};
     int pick = 0;
-    const int forced = getenv("KMCF_CGR_TPB") ? atoi(getenv("KMCF_CGR_TPB")) : 0;
+    const int forced = kmcf_knob_int(KNOB_CGR_TPB, 0);
     // Tiles per block: the smallest that keeps the grid within 256 blocks -- the flat one-hop reduction needs that, and
     // more blocks mean more CUs whose LDS pipes share the row sums (measured, us per iteration at 1 / 2 / 4 tiles per
     // block: 5 nm device, 286 tiles: 8.1 / 6.8 / 8.3; a rank's eighth of the 40 nm matrix, 881 tiles: 14.5 / 14.5 / 11.4);
@@ -760,13 +771,13 @@ static int cgr_plan(kmcf_matrix *m)
         KMCF_HIP(hipMemcpy(&all, d_v, sizeof(double), hipMemcpyDeviceToHost));
         if (all != (double)c->nranks) pick = 0;
     }
-    if (getenv("KMCF_TRACE")) fprintf(stderr, "cgr_plan rank %d: ok %d tiles %d forced %d pick %d share %d\n", c->rank, (int)ok, m->n_sell_tiles, forced, pick, share);
+    if (kmcf_trace()) fprintf(stderr, "cgr_plan rank %d: ok %d tiles %d forced %d pick %d share %d\n", c->rank, (int)ok, m->n_sell_tiles, forced, pick, share);
     if (!pick) return KMCF_OK;
     g->tpb = pick;
     g->nblocks = (m->n_sell_tiles + pick - 1) / pick;
     // reduction: flat (g1 = 0: every block reads every block's sums itself, one hop) up to 256 blocks, else by groups of
     // g1 blocks (two hops); KMCF_CGR_G1 = n forces groups of n
-    int g1 = getenv("KMCF_CGR_G1") ? atoi(getenv("KMCF_CGR_G1")) : (g->nblocks <= 256 ? 0 : 16);
+    int g1 = kmcf_knob_int(KNOB_CGR_G1, g->nblocks <= 256 ? 0 : 16);
     if (g1 != 0 || g->nblocks > 256) {
         g1 = std::max(2, std::min(64, g1));
         while ((g->nblocks + g1 - 1) / g1 > 64) g1 *= 2;            // one lane per group in the second stage
@@ -849,9 +860,6 @@ int kmcf_cgr_solve(kmcf_matrix *m, bool precond, double tol, int max_it, int fix
         g->seq_bound = 0;
     }
     g->seq_bound += 3ull * (unsigned long long)limit + 16;          // (publications + reductions: at most three numbers per iteration)
-    static const long long timeout_ms = getenv("KMCF_CGR_TIMEOUT_MS") ? atoll(getenv("KMCF_CGR_TIMEOUT_MS")) : 4000;
-    int rate_khz = 0;
-    KMCF_HIP(hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, c->device));
     cgr_args A{};
     A.n_tiles = m->n_sell_tiles; A.nblocks = g->nblocks; A.g1 = g->g1; A.ngroups = g->ngroups;
     A.tile4 = m->d_sell_tile; A.swave = m->d_sell_wave; A.wcol = m->d_sell_wcol;
@@ -865,17 +873,13 @@ int kmcf_cgr_solve(kmcf_matrix *m, bool precond, double tol, int max_it, int fix
     A.zll = g->d_zll; A.zwords = (long long)g->zwords;
     A.slot = g->d_slot; A.gslot = g->d_gslot; A.seq = g->d_seq;
     A.d_err = g->d_err; A.h_err = g->h_err;
-    A.timeout = (long long)rate_khz * timeout_ms;
-    if (c->nranks > 1 && c->p2p && !getenv("KMCF_CGR_TIMEOUT_MS")) A.timeout = c->p2p->timeout_ticks;      // (a group: the transport's bound, KMCF_P2P_TIMEOUT_MS)
+    KMCF_TRY(cgr_timeout_ticks(c, &A.timeout));
     A.limit = limit; A.check_tol = fixed_iters > 0 ? 0 : 1; A.tol2 = tol * tol;
-    {
-        static const int gd = getenv("KMCF_CGR_DELAY") ? atoi(getenv("KMCF_CGR_DELAY")) : 6;
-        static const int rd = getenv("KMCF_CGR_RDELAY") ? atoi(getenv("KMCF_CGR_RDELAY")) : 6;
-        static const int ad = getenv("KMCF_CGR_ADAPT") ? atoi(getenv("KMCF_CGR_ADAPT")) : 16;
-        A.gather_delay = gd; A.reduce_delay = rd; A.adapt_delay = ad;
-    }
+    A.gather_delay = kmcf_knob_int(KNOB_CGR_DELAY, 6);
+    A.reduce_delay = kmcf_knob_int(KNOB_CGR_RDELAY, 6);
+    A.adapt_delay = kmcf_knob_int(KNOB_CGR_ADAPT, 16);
     A.classic = classic ? 1 : 0;
-    A.sibling_lds = !(getenv("KMCF_CGR_SIB") && atoi(getenv("KMCF_CGR_SIB")) == 0);
+    A.sibling_lds = 1;
     A.nranks = c->nranks; A.rank = c->rank; A.n_loc = m->n_loc;
     if (c->nranks > 1) {
         const kmcf_p2p_halo *h = m->p2p;

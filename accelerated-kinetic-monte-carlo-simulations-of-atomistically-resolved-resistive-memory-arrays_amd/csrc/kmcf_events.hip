@@ -1023,7 +1023,7 @@ extern "C" int kmcf_execute_kmc_step(kmcf_comm *c, int N, const int *h_count, co
     // lists are gathered once, the generators are in the same state by contract, and the ranks execute the same
     // events with no collective and no extra synchronisation at all.  KMCF_EVENTS_PARTITIONED=1 keeps the
     // reference's scheme.
-    const bool replicate = c->nranks > 1 && !getenv("KMCF_EVENTS_PARTITIONED");
+    const bool replicate = c->nranks > 1 && !kmcf_knob(KNOB_EVENTS_PARTITIONED);
     const int P = replicate ? 1 : c->nranks, rank = replicate ? 0 : c->rank;
     const int count = replicate ? N : h_count[rank], start_i = replicate ? 0 : h_displs[rank];
     const size_t M = (size_t)count * nn;
@@ -1093,7 +1093,7 @@ extern "C" int kmcf_execute_kmc_step(kmcf_comm *c, int N, const int *h_count, co
                                                                d_x, d_y, d_z, d_site_potential_charge, d_site_element,
                                                                d_site_charge, E, d_type, d_prob);
         zero_and_sum_kernel<<<nb, KMCF_BLOCK, 0, st>>>(M, start_i, nn, d_neigh_idx, d_type, d_prob, -1, -1, d_tsum);
-        if (P == 1 && count == N && !getenv("KMCF_EVENTS_FULLSCAN")) {
+        if (P == 1 && count == N && !kmcf_knob(KNOB_EVENTS_FULLSCAN)) {
             // the neighbour lists are built once per run (kmc_main.cpp:199): the verdict on their symmetry is
             // kept with the workspace, keyed by the list's address and shape
             if (w->sym_key != d_neigh_idx || w->sym_N != N) {
@@ -1122,7 +1122,7 @@ extern "C" int kmcf_execute_kmc_step(kmcf_comm *c, int N, const int *h_count, co
         // exactly as by the reference (two draws per executed event); a foreign callback cannot be rewound,
         // so it gets batches of one.
         // persistent batch kernel (default; KMCF_EVENTS_PERSISTENT=0: three launches per event) with its row-aligned sums
-        const bool persistent = !(getenv("KMCF_EVENTS_PERSISTENT") && atoi(getenv("KMCF_EVENTS_PERSISTENT")) == 0) && nn <= 63;
+        const bool persistent = kmcf_knob_int(KNOB_EVENTS_PERSISTENT, 1) != 0 && nn <= 63;
         const long long n_tiles2 = ((long long)count + EV_RT - 1) / EV_RT, n_groups2 = (n_tiles2 + EV_GROUP - 1) / EV_GROUP;
         if (persistent) {
             if (!w->d_rsum &&
@@ -1140,7 +1140,7 @@ extern "C" int kmcf_execute_kmc_step(kmcf_comm *c, int N, const int *h_count, co
         }
         const int BMAX = persistent ? EV_BMAX : 128;
         // (KMCF_EV_TREL: tests shrink the claim range to drive the kernel's out-of-range path)
-        const int trel_max = getenv("KMCF_EV_TREL") ? std::min(std::max(atoi(getenv("KMCF_EV_TREL")), 1), EV_TREL) : EV_TREL;
+        const int trel_max = std::min(std::max(kmcf_knob_int(KNOB_EV_TREL, EV_TREL), 1), EV_TREL);
         const bool own_rng = (next_random == kmcf_rng_next);
         if (!w->d_u &&
             (hipMalloc(reinterpret_cast<void **>(&w->d_u), 2 * 512 * sizeof(double)) != hipSuccess ||
@@ -1152,8 +1152,8 @@ extern "C" int kmcf_execute_kmc_step(kmcf_comm *c, int N, const int *h_count, co
         event_batch_state *d_state = static_cast<event_batch_state *>(w->d_state);
         // Persistent batches hand their results over in pinned host memory, which the kernel writes itself and the host
         // polls (state.seq): no copies in either direction, no sleep in hipStreamSynchronize per batch (a one-event step
-        // of the 5 nm device: 0.15 -> see DESIGN 8).  KMCF_EVENTS_PINNED=0: device buffers and copies.
-        const bool pinned = persistent && !(getenv("KMCF_EVENTS_PINNED") && atoi(getenv("KMCF_EVENTS_PINNED")) == 0);
+        // of the 5 nm device: 0.15 -> see DESIGN 8).  Three launches per event, or no pinned block: device buffers and copies.
+        const bool pinned = persistent;
         constexpr size_t PIN_LOG = 64, PIN_TOT = PIN_LOG + 3 * EV_BMAX * sizeof(int), PIN_U = PIN_TOT + 2 * EV_BMAX * sizeof(double),
                          PIN_END = PIN_U + 2 * EV_BMAX * sizeof(double);
         if (pinned && !w->h_pin) {
@@ -1187,14 +1187,13 @@ extern "C" int kmcf_execute_kmc_step(kmcf_comm *c, int N, const int *h_count, co
                 event_batch_args A;
                 A.count = count; A.nn = nn; A.nbatch = nbatch; A.trel_max = trel_max; A.n_tiles = n_tiles2; A.n_groups = n_groups2; A.inv_freq = 1 / freq;
                 A.number = pin_ok ? ++w->batch_number : 0;
-                // the supertile sums in LDS where they fit beside the kernel's own arrays (KMCF_EVENTS_ST=0: the round-3 walk)
+                // the supertile sums in LDS where they fit beside the kernel's own arrays (else: the round-3 walk)
                 A.n_st = 0;
                 size_t dyn = 0;
                 {
-                    static const bool st_on = !(getenv("KMCF_EVENTS_ST") && atoi(getenv("KMCF_EVENTS_ST")) == 0);
                     const long long n_st = (n_tiles2 + EV_ST - 1) / EV_ST;
                     hipFuncAttributes fa;
-                    if (st_on && n_groups2 <= EV_GLDS && n_st <= EV_STMAX &&
+                    if (n_groups2 <= EV_GLDS && n_st <= EV_STMAX &&
                         hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(event_batch_kernel)) == hipSuccess &&
                         fa.sharedSizeBytes + (size_t)n_st * sizeof(double) <= (size_t)160 * 1024 &&
                         hipFuncSetAttribute(reinterpret_cast<const void *>(event_batch_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "kmcfield.h"
+#include "kmcf_knobs.hpp"
 
 // ---------------------------------------------------------------- errors
 void kmcf_set_error(const char *fmt, ...);
@@ -76,6 +77,7 @@ struct kmcf_group {
     int arrived = 0;
     long generation = 0;
     bool broken = false;               // a barrier timed out: the group is unusable
+    int timeout_s = 120;               // how long a barrier waits for the last rank (KMCF_LOOPBACK_TIMEOUT_S)
     std::vector<void *> slot;            // per-rank published pointer
     std::vector<kmcf_matrix *> mat;      // per-rank matrix taking part in the current halo exchange
     int refs = 0;
@@ -198,10 +200,9 @@ struct kmcf_matrix {
     int spmv_lpr = 16;                 // lanes per row (vec kernel)
     bool stream_nt = false;            // the f64-value kernels mark their matrix loads nontemporal (matrix larger than the caches)
     int spmv_kind = 0;                 // 0: vec<LPR>, 1: stream (nnz-chunked, LDS row reduction), 2: window
-    // window kernel (kind 2): tiles of whole rows whose distinct columns (<= spmv_wmax) are staged in LDS
+    // window kernel (kind 2): tiles of whole rows whose distinct columns (at most 512) are staged in LDS
     int n_tiles = 0;
     int64_t n_wcols = 0;               // sum of the tiles' window sizes
-    int spmv_wmax = 0;
     int2 *d_tile = nullptr;            // (first row, first window slot) per tile, n_tiles + 1
     int4 *d_tile4 = nullptr;           // (first row, rows, first window slot, window size) per tile: the coded kernel's view
     int *d_tbase = nullptr;            // first entry of each tile
@@ -248,8 +249,6 @@ struct kmcf_matrix {
     double *d_sellv = nullptr;
     bool sellv_dirty = true;
     int sellv_grid = 0;
-    int spmv_u = 8;                    // stream: nnz per thread per chunk
-    int spmv_lpr2 = 4;                 // stream: lanes per row in the LDS reduction
     int n_chunks = 0;
     int *d_chunk_row = nullptr;        // stream: first row of each chunk (n_chunks + 1)
     std::vector<int> h_row_ptr;        // host copy of row_ptr (launch planning)
@@ -278,22 +277,25 @@ void kmcf_sell_free(kmcf_matrix *m);       // frees the row-per-lane layout (kmc
 void kmcf_sell_refine_order(int n_short, int n_cols, const int *rp, const int *col, std::vector<int> &perm, std::vector<int> &cuts);
 
 // grid of the CG's vector kernels (= r.z / b.b partials): 8 blocks per CU at most, one partial per block.  One step of
-// two rows per lane where that fits (KMCF_VEC_ROWS rows per lane, default 2): the kernels request a block's first
+// two rows per lane where that fits: the kernels request a block's first
 // step together with its scalars, so with a single step a block's life is ONE memory round trip (a rank's eighth of
 // the 40 nm matrix: update kernel 7.2 us with two steps per lane).
 // KMCF_DEVICE_SHARE = s: s ranks share this GPU (rehearsals of an N-rank run on fewer GPUs): every grid that is sized to
 // fill the chip takes 1/s of it, so that the ranks' kernels -- which wait for each other on the device -- are resident
-// together (two whole-chip grids of waiting blocks on one GPU starve each other: seen as all-reduce time-outs at 40 nm)
+// together (two whole-chip grids of waiting blocks on one GPU starve each other: seen as all-reduce time-outs at 40 nm).
+// Read once per process (kmcf_knobs.hpp).
 inline int kmcf_device_share()
 {
-    static const int s = getenv("KMCF_DEVICE_SHARE") ? std::max(1, atoi(getenv("KMCF_DEVICE_SHARE"))) : 1;
+    static const int s = std::max(1, kmcf_knob_int(KNOB_DEVICE_SHARE, 1));
     return s;
 }
 
+// edge of the bricks of the internal row order of K (kmcf_kstate.hip) and T (kmcf_tstate.hip), in Å; 0: the caller's order
+inline double kmcf_brick_edge() { return kmcf_knob_f64(KNOB_BRICK, 7.7); }
+
 inline int kmcf_vec_grid(int n)
 {
-    static const int rows = getenv("KMCF_VEC_ROWS") ? std::max(2, atoi(getenv("KMCF_VEC_ROWS"))) : 2;
-    int64_t g = ((int64_t)n + KMCF_BLOCK * rows - 1) / (KMCF_BLOCK * rows);
+    int64_t g = ((int64_t)n + KMCF_BLOCK * 2 - 1) / (KMCF_BLOCK * 2);
     if (g < 1) g = 1;
     if (g > KMCF_MAX_PARTIALS / kmcf_device_share()) g = KMCF_MAX_PARTIALS / kmcf_device_share();
     return (int)g;
@@ -319,7 +321,7 @@ inline int kmcf_interior_grid(const kmcf_matrix *m)
 inline bool kmcf_cg_single_reduction(const kmcf_matrix *m)
 {
     bool cg1r = m->comm->nranks > 1;
-    if (const char *e = getenv("KMCF_CG_VARIANT")) cg1r = (e[0] == 'c' && e[1] == 'g');
+    if (const char *e = kmcf_knob(KNOB_CG_VARIANT)) cg1r = (e[0] == 'c' && e[1] == 'g');
     return cg1r;
 }
 
@@ -455,8 +457,7 @@ void kmcf_cgr_free(kmcf_matrix *m);
 // pcg_workspace_run; KMCF_CGR_CLASSIC_TILES lowers the limit)
 inline bool kmcf_cgr_classic_applies(const kmcf_matrix *m)
 {
-    static const int classic_tiles = getenv("KMCF_CGR_CLASSIC_TILES") ? atoi(getenv("KMCF_CGR_CLASSIC_TILES")) : 1024;
-    return m->comm->nranks == 1 && !m->comm->force_collectives && m->n_sell_tiles <= classic_tiles;
+    return m->comm->nranks == 1 && !m->comm->force_collectives && m->n_sell_tiles <= kmcf_knob_int(KNOB_CGR_CLASSIC_TILES, 1024);
 }
 // matrix.hip
 int kmcf_matrix_build(kmcf_comm *c, int matrix_size, const int *counts, const int *displs,

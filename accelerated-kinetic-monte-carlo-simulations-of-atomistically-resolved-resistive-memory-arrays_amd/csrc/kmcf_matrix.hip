@@ -178,8 +178,7 @@ int kmcf_matrix_build(kmcf_comm *c, int matrix_size, const int *counts, const in
     if (h_val) val_int.assign(h_val, h_val + nnz);
     std::vector<int> perm_eff;
     if (h_perm && n_loc > 0) perm_eff.assign(h_perm, h_perm + n_loc);
-    int long_thr = 384;
-    if (const char *e = getenv("KMCF_LONG_ROW")) long_thr = atoi(e);
+    const int long_thr = kmcf_knob_int(KNOB_LONG_ROW, 384);
     int n_long = 0;
     if (long_thr > 0)
         for (int r = 0; r < n_loc; ++r) n_long += (rp[r + 1] - rp[r] > long_thr);

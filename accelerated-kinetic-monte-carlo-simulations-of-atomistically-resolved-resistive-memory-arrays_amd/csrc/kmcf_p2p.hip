@@ -246,9 +246,7 @@ int kmcf_p2p_create(kmcf_comm *c)
     c->p2p = w;
     w->nranks = c->nranks;
     w->rank = c->rank;
-    size_t mb = 96;
-    if (const char *e = getenv("KMCF_P2P_WINDOW_MB")) mb = (size_t)std::max(8, atoi(e));
-    w->win_bytes = mb << 20;
+    w->win_bytes = (size_t)std::max(8, kmcf_knob_int(KNOB_P2P_WINDOW_MB, 96)) << 20;
     // fine-grained device memory: stores arriving over xGMI are coherent with the owner's reads; a plain
     // allocation serves where the runtime refuses (same-device tests)
     if (hipExtMallocWithFlags(reinterpret_cast<void **>(&w->win), w->win_bytes, hipDeviceMallocFinegrained) == hipSuccess) {
@@ -257,7 +255,7 @@ int kmcf_p2p_create(kmcf_comm *c)
         (void)hipGetLastError();
         KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&w->win), w->win_bytes));
     }
-    if (getenv("KMCF_P2P_VERBOSE")) fprintf(stderr, "kmcfield p2p: rank %d window %zu MB at %p, %s\n", c->rank, w->win_bytes >> 20, (void *)w->win,
+    if (kmcf_trace()) fprintf(stderr, "kmcfield p2p: rank %d window %zu MB at %p, %s\n", c->rank, w->win_bytes >> 20, (void *)w->win,
                                             w->fine_grained ? "fine-grained" : "COARSE-grained (hipExtMallocWithFlags refused)");
     KMCF_HIP(hipMemset(w->win, 0, P2P_OFF_BUMP));
     w->stage_half = align_up((w->win_bytes - P2P_OFF_BUMP) / 4, 4096);       // half of the window for the two staging halves
@@ -273,8 +271,7 @@ int kmcf_p2p_create(kmcf_comm *c)
     KMCF_HIP(hipMemset(w->d_ctr, 0, 4 * sizeof(unsigned int)));
     KMCF_HIP(hipHostMalloc(reinterpret_cast<void **>(&w->h_err), sizeof(int), hipHostMallocDefault));
     *w->h_err = 0;
-    double ms = 10000.0;                               // (ranks may enter a solve seconds apart: set-up, IO)
-    if (const char *e = getenv("KMCF_P2P_TIMEOUT_MS")) ms = atof(e);
+    const double ms = kmcf_knob_f64(KNOB_P2P_TIMEOUT_MS, 10000.0);        // (ranks may enter a solve seconds apart: set-up, IO)
     int khz = 0;                                       // wall_clock64() tick rate of this device
     if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, c->device) != hipSuccess || khz <= 0) khz = 100000;
     w->timeout_ticks = (long long)(ms * khz);
@@ -511,8 +508,7 @@ int kmcf_p2p_matrix_connect(kmcf_matrix *m, const std::vector<long long> &r_land
 
 bool kmcf_p2p_direct(const kmcf_matrix *m)
 {
-    const char *e = getenv("KMCF_P2P_DIRECT");              // (read per call: bench.py times the protocols against each other)
-    const bool off = e && atoi(e) == 0;
+    const bool off = kmcf_knob_int(KNOB_P2P_DIRECT, 1) == 0;     // (read per call: bench.py times the protocols against each other)
     const kmcf_comm *c = m->comm;
     // long rows and the tunnel sub-block read the halo behind p_local: they keep the copying protocol
     return !off && c->p2p_active && c->nranks > 1 && m->p2p && m->p2p->d_put_row && m->n_long_items == 0 && !m->sub;

@@ -902,6 +902,10 @@ void launch_vec_halo_any(kmcf_matrix *m, bool with_dot, bool skip_if_done, u64 s
     }
 }
 
+// The shapes the planner uses: window tiles of at most 256 * WIN_U entries and 256 * WIN_WQ distinct columns (K tiles
+// need ~300: measured best), stream chunks of at most 256 * STREAM_U entries reduced by STREAM_LPR2 lanes per row.
+constexpr int WIN_U = 8, WIN_WQ = 2, STREAM_U = 8, STREAM_LPR2 = 4;
+
 #define KMCF_STREAM_ARGS(isb, part) \
     m->n_chunks, m->d_chunk_row, m->d_row_ptr, m->d_col, m->d_val, m->d_p, m->d_Ap, isb, part, m->d_S, chk
 
@@ -1108,18 +1112,6 @@ int sell_refresh(kmcf_matrix *m)
     return KMCF_OK;
 }
 
-int window_dispatch_any(kmcf_matrix *m, int which, bool launch, bool with_dot, bool skip_if_done)
-{
-    switch (m->spmv_u * 100 + m->spmv_wmax / KMCF_BLOCK) {
-        case 402: return window_dispatch<4, 2>(m, which, launch, with_dot, skip_if_done);
-        case 802: return window_dispatch<8, 2>(m, which, launch, with_dot, skip_if_done);
-        case 804: return window_dispatch<8, 4>(m, which, launch, with_dot, skip_if_done);
-        case 1603: return window_dispatch<16, 3>(m, which, launch, with_dot, skip_if_done);
-        case 1604: return window_dispatch<16, 4>(m, which, launch, with_dot, skip_if_done);
-        default: return window_dispatch<8, 3>(m, which, launch, with_dot, skip_if_done);
-    }
-}
-
 // The window kernels walk their tiles in a static loop, so the grid must be exactly what the chip holds at
 // once: with more blocks than resident slots the surplus ones start only after a first-wave block has
 // finished its whole loop (measured 116 us at 2048 blocks vs 102 us at 7 blocks x 256 CUs; 108 vs 72 us
@@ -1127,7 +1119,7 @@ int window_dispatch_any(kmcf_matrix *m, int which, bool launch, bool with_dot, b
 int window_grid(kmcf_matrix *m, int which)
 {
     int cus = 0;
-    const int per_cu = window_dispatch_any(m, which, false, true, false);
+    const int per_cu = window_dispatch<WIN_U, WIN_WQ>(m, which, false, true, false);
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, m->comm->device) != hipSuccess) cus = 0;
     const int resident = per_cu * cus / kmcf_device_share();
     int g = grid_for(m->n_tiles, 1);
@@ -1155,37 +1147,28 @@ void launch_interior(kmcf_matrix *m, bool with_dot, bool skip_if_done)
         if (sellv_prepare(m) != KMCF_OK) return;
         sellv_dispatch(m, true, with_dot, skip_if_done);
     } else if (m->spmv_kind == 2) {
-        window_dispatch_any(m, m->coded ? 1 : 0, true, with_dot, skip_if_done);
+        window_dispatch<WIN_U, WIN_WQ>(m, m->coded ? 1 : 0, true, with_dot, skip_if_done);
     } else if (m->spmv_kind == 1) {
-        const int key = m->spmv_u * 100 + m->spmv_lpr2;
-        switch (key) {
-            case 401: launch_stream<4, 1>(m, with_dot, skip_if_done); break;
-            case 404: launch_stream<4, 4>(m, with_dot, skip_if_done); break;
-            case 801: launch_stream<8, 1>(m, with_dot, skip_if_done); break;
-            case 808: launch_stream<8, 8>(m, with_dot, skip_if_done); break;
-            case 1604: launch_stream<16, 4>(m, with_dot, skip_if_done); break;
-            default: launch_stream<8, 4>(m, with_dot, skip_if_done); break;
-        }
+        launch_stream<STREAM_U, STREAM_LPR2>(m, with_dot, skip_if_done);
     } else {
         launch_vec_any(m, with_dot, skip_if_done, false);
     }
 }
 
-int env_int(const char *name, int dflt)
-{
-    const char *e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
+// KMCF_SPMV_CODED=0: no dictionary-coded kernels (tiles cut for the plain kernel, values streamed as f64)
+bool coding_allowed() { return kmcf_knob_int(KNOB_SPMV_CODED, 1) != 0; }
+// KMCF_SPMV_SELL=0: no row-per-lane layout (plan and row order)
+bool sell_allowed() { return kmcf_knob_int(KNOB_SPMV_SELL, 1) != 0; }
 
-// Cuts the rows into tiles for the window kernels: whole rows, at most 256*u entries, 8*u rows (u/8 full
-// passes of the 4-lanes-per-row reduction) and 256*wq distinct columns per tile (compact-halo column ids, so
+// Cuts the rows into tiles for the window kernels: whole rows, at most 256*WIN_U entries, 8*WIN_U rows (one full
+// pass of the 4-lanes-per-row reduction) and 256*WIN_WQ distinct columns per tile (compact-halo column ids, so
 // halo slots are window columns like any other).  *ok stays false (nothing allocated) if a row does not fit
 // a tile or, with `judge`, if a window column is used by fewer than two entries on average: columns too
 // scattered for a window to pay off, the stream kernel's direct gathers serve those better (K: ~5 entries
 // per window column).
 int plan_sell(kmcf_matrix *m, const std::vector<int> &col);
 
-int plan_window(kmcf_matrix *m, int u, int wq, bool judge, bool *ok)
+int plan_window(kmcf_matrix *m, bool judge, bool *ok)
 {
     *ok = false;
     const int n = m->n_short;                        // long rows have their own kernel
@@ -1193,10 +1176,9 @@ int plan_window(kmcf_matrix *m, int u, int wq, bool judge, bool *ok)
     if (n == 0 || rp[n] == 0) return KMCF_OK;
     // the row limit serves the coded kernel (full passes of its row lanes); the plain kernel, whose cost is
     // the value stream, prefers tiles filled to the entry limit
-    const char *ce = getenv("KMCF_SPMV_CODED");
-    const bool for_coded = m->expect_coded && !(ce && atoi(ce) == 0);
-    // (the coded kernel reads a tile's slot stream from an aligned start up to u - 1 entries early: spmv_wcode_kernel)
-    const int cap = KMCF_BLOCK * u - (for_coded ? u : 0), wmax = KMCF_BLOCK * wq, row_cap = for_coded ? 8 * u : n;
+    const bool for_coded = m->expect_coded && coding_allowed();
+    // (the coded kernel reads a tile's slot stream from an aligned start up to WIN_U - 1 entries early: spmv_wcode_kernel)
+    const int cap = KMCF_BLOCK * WIN_U - (for_coded ? WIN_U : 0), wmax = KMCF_BLOCK * WIN_WQ, row_cap = for_coded ? 8 * WIN_U : n;
     m->tiles_for_coded = for_coded;
     std::vector<int> col((size_t)m->nnz);
     KMCF_HIP(hipMemcpy(col.data(), m->d_col, col.size() * sizeof(int), hipMemcpyDeviceToHost));
@@ -1231,7 +1213,7 @@ int plan_window(kmcf_matrix *m, int u, int wq, bool judge, bool *ok)
     tiles.push_back(make_int2(n, (int)wcol.size()));
     const int nt = (int)tiles.size() - 1;
     if (judge && double(rp[n]) < 2.0 * double(wcol.size())) return KMCF_OK;
-    if (getenv("KMCF_SPMV_VERBOSE"))
+    if (kmcf_trace())
         fprintf(stderr, "kmcf window plan: %d tiles, %.1f rows, %.1f nnz, %.1f window columns per tile\n", nt, double(n) / nt,
                 double(rp[n]) / nt, double(wcol.size()) / nt);
     KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&m->d_tile), tiles.size() * sizeof(int2)));
@@ -1258,7 +1240,6 @@ int plan_window(kmcf_matrix *m, int u, int wq, bool judge, bool *ok)
     KMCF_HIP(hipMemcpy(m->d_idx16, idx.data(), idx.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
     m->n_tiles = nt;
     m->n_wcols = (int64_t)wcol.size() - 1;              // without the spare element
-    m->spmv_wmax = wmax;
     // diagonal positions and the buffers of the dictionary-coded variant (codes are written later, by
     // kmcf_matrix_encode_values or by the K assembly)
     m->h_diag_pos.assign((size_t)n, -1);
@@ -1275,7 +1256,7 @@ int plan_window(kmcf_matrix *m, int u, int wq, bool judge, bool *ok)
     *ok = true;
     KMCF_TRY(plan_sell(m, col));                        // (the coded kernel when the values get a dictionary, the f64 one otherwise)
     m->sellv_grid = 0;
-    if (m->sell_ok && m->sell_ident && m->sell_lw == 10 && env_int("KMCF_SPMV_SELLV", 1) != 0) {
+    if (m->sell_ok && m->sell_ident && m->sell_lw == 10 && kmcf_knob_int(KNOB_SPMV_SELLV, 1) != 0) {
         int cus = 0;
         const int per_cu = sellv_dispatch(m, false, true, false);
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, m->comm->device) != hipSuccess) cus = 0;
@@ -1302,7 +1283,7 @@ sell_params sell_plan_params(int n)
     // 128, 13.8 with 64 -- large tiles win as long as every CU gets one)
     int row_cap = KMCF_BLOCK;
     while (row_cap > 64 && n / row_cap < 256) row_cap /= 2;
-    p.row_cap = std::min(KMCF_BLOCK, std::max(64, env_int("KMCF_SPMV_SELL_ROWS", row_cap) / 64 * 64));
+    p.row_cap = std::min(KMCF_BLOCK, std::max(64, kmcf_knob_int(KNOB_SPMV_SELL_ROWS, row_cap) / 64 * 64));
     return p;
 }
 
@@ -1357,7 +1338,7 @@ int sell_cut_tile(int start, int e_max, int row_cap, int ecap, RowId row_id, Col
 int plan_sell(kmcf_matrix *m, const std::vector<int> &col)
 {
     m->sell_ok = false;
-    if (env_int("KMCF_SPMV_SELL", 1) == 0) return KMCF_OK;
+    if (!sell_allowed()) return KMCF_OK;
     const int n = m->n_short;
     const std::vector<int> &rp = m->h_row_ptr;
     const std::vector<int> &dpos = m->h_diag_pos;
@@ -1440,10 +1421,11 @@ int plan_sell(kmcf_matrix *m, const std::vector<int> &col)
     }
     if (st.size() / 4 > (size_t)0x7fffff00 || (double)st.size() > 1.5 * (double)real + 4096.0 * tiles.size()) return KMCF_OK;
     const int nt = (int)tiles.size();
-    if (getenv("KMCF_SPMV_VERBOSE"))
+    const bool trace = kmcf_trace();
+    if (trace)
         fprintf(stderr, "kmcf row-per-lane plan: %d tiles of <= %d rows%s, %.1f rows, %.1f window columns per tile, %lld entries + %.1f %% padding, %d steps\n",
                 nt, row_cap, ident ? " (sorted in place)" : "", double(n) / nt, double(wcol.size()) / nt, (long long)real, 100.0 * (double(st.size()) / double(std::max<int64_t>(real, 1)) - 1.0), nq);
-    if (getenv("KMCF_SPMV_VERBOSE")) {
+    if (trace) {
         std::vector<long long> hist(20, 0), rows(20, 0);
         for (const int2 &w : waves) ++hist[std::min(w.y, 19)];
         for (int i = 0; i < n; ++i) ++rows[std::min((len_of(i) + 3) / 4, 19)];
@@ -1485,7 +1467,7 @@ int plan_sell(kmcf_matrix *m, const std::vector<int> &col)
     // beyond the Infinity Cache (256 MiB; 10 x 10 cells = 243 MB of format still run 40.2 us plain against 51.9
     // nontemporal) the entry stream is loaded nontemporal; KMCF_SELL_NT overrides
     m->sell_nt = 2.0 * (double)st.size() + 4.0 * (double)wcol.size() + 28.0 * (double)n > 300e6;
-    if (const char *e = getenv("KMCF_SELL_NT")) m->sell_nt = atoi(e) != 0;
+    m->sell_nt = kmcf_knob_int(KNOB_SELL_NT, m->sell_nt) != 0;
     return KMCF_OK;
 }
 
@@ -1527,37 +1509,22 @@ int kmcf_spmv_plan(kmcf_matrix *m)
     // f64-value kernels: nontemporal matrix loads once the CSR stream alone is beyond what the caches can keep
     // between two launches (stream_load; KMCF_SPMV_NT = 0 / 1 overrides)
     m->stream_nt = 12.0 * (double)m->nnz > 192e6;
-    if (const char *e = getenv("KMCF_SPMV_NT")) m->stream_nt = atoi(e) != 0;
+    m->stream_nt = kmcf_knob_int(KNOB_SPMV_NT, m->stream_nt) != 0;
     // vec kernel: lanes per row from the mean row length (K rows hold 4..53 entries, mean 25.8)
     const double mean = m->n_short > 0 ? double(m->h_row_ptr[m->n_short]) / m->n_short : 0.0;
     int lpr = 4;
     while (lpr < 64 && lpr * 2 <= mean) lpr *= 2;  // 25.8 -> 16
-    {
-        int v = env_int("KMCF_SPMV_LPR", 0);
-        if (v == 4 || v == 8 || v == 16 || v == 32 || v == 64) lpr = v;
-    }
     m->spmv_lpr = lpr;
     m->spmv_grid_b = m->n_boundary_rows > 0 ? grid_for(m->n_boundary_rows, KMCF_BLOCK / lpr) : 0;
 
-    // stream kernel: chunks of whole rows with at most 256*U nnz
-    int u = env_int("KMCF_SPMV_U", 8);
-    if (u != 4 && u != 8 && u != 16) u = 8;
-    m->spmv_u = u;
-    m->spmv_lpr2 = env_int("KMCF_SPMV_LPR2", 4);
-    const int cap = KMCF_BLOCK * u;
     // kind: window kernel unless the plan declines (scattered columns, very long rows), then stream, then vec
-    int kind = env_int("KMCF_SPMV_KIND", -1);
+    int kind = kmcf_knob_int(KNOB_SPMV_KIND, -1);
     const bool judge = kind < 0;
     if (kind < 0 || kind > 2) kind = 2;
     if (kind == 2) {
-        int wq = env_int("KMCF_SPMV_WQ", 2);             // 512 window columns: K tiles need ~300 (measured best)
-        if (wq != 2 && wq != 3 && wq != 4) wq = 2;
-        // instantiated (U, WQ) pairs: window_dispatch_any
-        const int uw = (u == 4 && wq == 2) ? 4 : ((u == 16 && wq >= 3) ? 16 : 8);
         bool ok = false;
-        KMCF_TRY(plan_window(m, uw, wq, judge, &ok));
+        KMCF_TRY(plan_window(m, judge, &ok));
         if (ok) {
-            m->spmv_u = uw;
             m->spmv_kind = 2;
             m->spmv_grid = window_grid(m, 0);
             m->spmv_grid_coded = 0;                  // set with the dictionary (kmcf_matrix_set_dictionary)
@@ -1573,7 +1540,7 @@ int kmcf_spmv_plan(kmcf_matrix *m)
         while (r < m->n_short) {
             const int start = rp[r];
             int e = r;
-            while (e < m->n_short && rp[e + 1] - start <= cap) ++e;
+            while (e < m->n_short && rp[e + 1] - start <= KMCF_BLOCK * STREAM_U) ++e;     // (chunks of whole rows)
             if (e == r) { kind = 0; break; }   // a single row exceeds a chunk: vector kernel
             chunk_row.push_back(e);
             r = e;
@@ -1594,9 +1561,7 @@ int kmcf_spmv_plan(kmcf_matrix *m)
 
 static bool coding_enabled(const kmcf_matrix *m)
 {
-    if (m->spmv_kind != 2 || !m->d_idx16 || !m->tiles_for_coded) return false;
-    const char *e = getenv("KMCF_SPMV_CODED");
-    return !(e && atoi(e) == 0);
+    return m->spmv_kind == 2 && m->d_idx16 && m->tiles_for_coded && coding_allowed();
 }
 
 int kmcf_matrix_set_dictionary(kmcf_matrix *m, const double *h_dict, int nd)
@@ -1618,7 +1583,7 @@ int kmcf_matrix_set_dictionary(kmcf_matrix *m, const double *h_dict, int nd)
     if (m->sell_ok && (m->sell_grid <= 0 || (m->dict_n <= 2) != (nd <= 2))) {
         m->dict_n = nd;
         m->sell_grid = sell_grid(m);
-        if (getenv("KMCF_SPMV_VERBOSE")) fprintf(stderr, "kmcf row-per-lane kernel: grid %d for %d tiles\n", m->sell_grid, m->n_sell_tiles);
+        if (kmcf_trace()) fprintf(stderr, "kmcf row-per-lane kernel: grid %d for %d tiles\n", m->sell_grid, m->n_sell_tiles);
     }
     m->dict_n = nd;
     m->sell_dirty = true;                               // the caller is about to write (or has just written) the codes
@@ -1897,7 +1862,7 @@ extern "C" int kmcf_comm_bench(kmcf_matrix *m, int kind, int reps, float *ms_tot
 void kmcf_sell_refine_order(int n_short, int n_cols, const int *rp, const int *col, std::vector<int> &perm, std::vector<int> &cuts)
 {
     cuts.clear();
-    if (env_int("KMCF_SPMV_SELL", 1) == 0 || env_int("KMCF_SPMV_SELL_SORT", 1) == 0 || n_short < 2) return;
+    if (!sell_allowed() || kmcf_knob_int(KNOB_SPMV_SELL_SORT, 1) == 0 || n_short < 2) return;
     const sell_params sp = sell_plan_params(n_short);
     std::vector<unsigned char> mark((size_t)n_cols, 0);
     std::vector<int> touched, len((size_t)n_short);

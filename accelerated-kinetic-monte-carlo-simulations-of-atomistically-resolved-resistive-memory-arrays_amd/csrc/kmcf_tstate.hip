@@ -1319,8 +1319,7 @@ extern "C" int kmcf_initialize_sparsity_T(kmcf_comm *c, const double *d_site_x, 
     // behind by the matrix builder
     std::vector<int> perm;
     {
-        double edge = 7.7;
-        if (const char *e = getenv("KMCF_BRICK")) edge = atof(e);
+        const double edge = kmcf_brick_edge();
         if (edge > 0 && n_loc > 1) {
             std::vector<int64_t> key((size_t)n_loc);
             for (int r = 0; r < n_loc; ++r) {
@@ -1475,8 +1474,7 @@ static int symm_setup(kmcf_tstate *t)
     sb.nb = nb;
     sb.n_tiles_glob = (long long)nb * (nb + 1) / 2;
     KMCF_CHECK(sb.n_tiles_glob < (long long)INT32_MAX, KMCF_ERR_ARG, "tunnel block of %d points: tile index exceeds int32", n_t);
-    int strip_len = 16;
-    if (const char *e = getenv("KMCF_SUB_STRIP")) strip_len = std::max(1, atoi(e));
+    const int strip_len = std::max(1, kmcf_knob_int(KNOB_SUB_STRIP, 16));
     std::vector<int4> strips;
     std::vector<int> first((size_t)nb + 1, 0), tile_local;
     if (sb.spread) tile_local.assign((size_t)sb.n_tiles_glob, -1);
@@ -1655,7 +1653,7 @@ static int t_assemble_async(kmcf_tstate *t, const int *d_site_element, const int
     if (n_t > 0) {
         const long long nbl = (n_t + 63) / 64, all_tiles = nbl * (nbl + 1) / 2;
         const double nn2 = (double)n_t * (double)n_t, nbt = nn2 / 8192;
-        const char *env = getenv("KMCF_SUB_DENSE");
+        const char *env = kmcf_knob(KNOB_SUB_DENSE);
         if (P == 1) {
             sb.dense = n_t >= 2048 && 4.0 * (double)sb.nnz > nn2;
             if (sb.dense && sb.cap_tiles < (size_t)all_tiles * 4096) {
@@ -1724,8 +1722,7 @@ int kmcf_subop_begin(kmcf_matrix *m, bool skip_if_done)
         KMCF_HIP(hipGetLastError());
     }
     if (c->nranks == 1 && !c->force_collectives) return KMCF_OK;
-    static const bool no_overlap = getenv("KMCF_SUB_OVERLAP") && atoi(getenv("KMCF_SUB_OVERLAP")) == 0;
-    if (!no_overlap && (c->p2p_active || (!c->group && c->nccl))) {
+    if (c->p2p_active || (!c->group && c->nccl)) {
         KMCF_HIP(hipEventRecord(c->ev_subpack, st));
         KMCF_HIP(hipStreamWaitEvent(c->comm_stream, c->ev_subpack, 0));
         const int rc = kmcf_comm_allgatherv_double_comm_stream(c, sb->d_xsub, sb->counts.data(), sb->displs.data());

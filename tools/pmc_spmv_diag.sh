@@ -1,10 +1,10 @@
 #!/bin/bash
 # GPU box: hardware counters of the SpMV kernel (one rocprofv3 --pmc pass per counter group; never combined
 # with sys/hip/hsa traces).  Output: gpurun_out/pmcdiag/<group>/...counter_collection.csv + a summary.
-#   bash tools/pmc_spmv_diag.sh ["KIND=1,U=8,LPR2=4"]
+#   bash tools/pmc_spmv_diag.sh ["KIND=1"]
 set -e
 R=${GRAFT_REPO_ROOT:-/root/repo}
-SPEC=${1:-KIND=1,U=8,LPR2=4}
+SPEC=${1:-KIND=1}
 cd /tmp && export TMPDIR=/tmp
 mkdir -p $R/gpurun_out/pmcdiag
 rocprofv3 -L > $R/gpurun_out/pmcdiag/counters.txt 2>&1 || true

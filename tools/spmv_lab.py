@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Tuning aid (GPU box): time SpMV kernel variants of libkmcfield on the synthetic 40 nm K matrix.
 
-    python tools/spmv_lab.py [--workload 40nm|small] "KIND=0,LPR=16" "KIND=1,U=8,LPR2=4" ...
+    python tools/spmv_lab.py [--workload 40nm|small] "KIND=0" "KIND=1" "KIND=2,SELL=0" ...
 Each spec sets KMCF_SPMV_<key> env vars, re-plans the matrix, checks the result against the first
 variant and prints us/launch and GB/s on the algorithmic bytes (12 nnz + 20 n)."""
 import ctypes as C
@@ -22,7 +22,7 @@ def main():
     if args and args[0] == "--workload":
         workload = args[1]
         args = args[2:]
-    specs = args or ["KIND=0,LPR=16", "KIND=1,U=8,LPR2=4"]
+    specs = args or ["KIND=0", "KIND=1"]
     S = km.solvers
     order = os.environ.get("LAB_ORDER", "bwmin")
     d = km.structure.synth_crossbar_40nm(order=order, tiles=int(os.environ.get("LAB_TILES", "8"))) if workload == "40nm" else km.structure.synth_small(tiles=2, order=order)
