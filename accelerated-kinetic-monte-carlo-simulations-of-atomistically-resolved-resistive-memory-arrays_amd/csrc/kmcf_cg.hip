@@ -700,7 +700,7 @@ int pcg1_loop(kmcf_matrix *m, double tol, int max_it, int fixed_iters, kmcf_solv
     // where the all-reduce of a fused iteration runs: inside the update kernel (every block waits for the P flags: one
     // kernel fewer; right when every rank has a GPU of its own) or in a 1-block kernel in front of it (KMCF_P2P_AR=split:
     // ranks SHARING a GPU -- rehearsals -- otherwise fill it with waiting blocks); bench.py times both and keeps the faster
-    const char *ar = kmcf_knob(KNOB_P2P_AR);
+    const char *ar = kmcf_opt(c, KNOB_P2P_AR);
     const bool ar_inside = !(ar && strcmp(ar, "split") == 0);
     const bool p2p_red = multi && c->nranks > 1 && c->p2p_active;
     const u64 red0 = p2p_red ? kmcf_p2p_red_seq(c) : 0, halo0 = fused ? *kmcf_p2p_halo_seq(m, 0) : 0;
@@ -830,7 +830,9 @@ static int pcg_workspace_run(kmcf_matrix *m, bool precond, double tol, int max_i
     // classic = the reference's recurrence and operation order (default for one rank);
     // cg1r = single-reduction variant (default for multi-rank groups)
     if (kmcf_cg_single_reduction(m)) {
-        if (kmcf_cgr_usable(m) && (fixed_iters > 0 || max_it > 0)) return pcg_resident(m, precond, tol, max_it, fixed_iters, stats, flags, false);
+        const bool resident = kmcf_cgr_usable(m);
+        KMCF_TRY(kmcf_cgr_agreed(m));
+        if (resident && (fixed_iters > 0 || max_it > 0)) return pcg_resident(m, precond, tol, max_it, fixed_iters, stats, flags, false);
         KMCF_CHECK(!m->solve_x_user && !m->solve_b_src, KMCF_ERR_STATE, "solve set up for a resident launch that does not apply");
         if (precond) return pcg1_loop<true>(m, tol, max_it, fixed_iters, stats, flags);
         return pcg1_loop<false>(m, tol, max_it, fixed_iters, stats, flags);
@@ -1019,7 +1021,7 @@ extern "C" int kmcf_pcg_jacobi(kmcf_matrix *m, double *d_r, double *d_x, const d
     KMCF_CHECK(max_iterations >= 0 && fixed_iters >= 0, KMCF_ERR_ARG, "kmcf_pcg_jacobi: negative iteration count");
     kmcf_comm *c = m->comm;
     KMCF_CHECK(c->connected, KMCF_ERR_COMM, "kmcf_pcg_jacobi: communicator not connected");
-    const bool trace = kmcf_trace();
+    const bool trace = kmcf_trace(c);
     auto now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t_0 = trace ? now() : 0.0;
     KMCF_TRY(kmcf_enter(c));

@@ -55,6 +55,7 @@ struct kmcf_cgr {
     int *d_err = nullptr, *h_err = nullptr;
     unsigned long long seq_bound = 1;   // host's upper bound of *d_seq (wrap protection)
     size_t zwords = 0;
+    bool disagree = false;              // the group's ranks see different group knobs (cgr_plan): every solve is refused
 };
 
 namespace {
@@ -688,7 +689,7 @@ int cgr_run_any(const kmcf_matrix *m, int tpb, const cgr_args &A, bool launch, h
 // transport bound (KMCF_P2P_TIMEOUT_MS), else 4 s.
 int cgr_timeout_ticks(const kmcf_comm *c, long long *ticks)
 {
-    const char *e = kmcf_knob(KNOB_CGR_TIMEOUT_MS);
+    const char *e = kmcf_opt(c, KNOB_CGR_TIMEOUT_MS);
     if (!e && c->nranks > 1 && c->p2p) { *ticks = c->p2p->timeout_ticks; return KMCF_OK; }
     int rate_khz = 0;
     KMCF_HIP(hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, c->device));
@@ -696,9 +697,9 @@ int cgr_timeout_ticks(const kmcf_comm *c, long long *ticks)
     return KMCF_OK;
 }
 
-int cgr_mode()
+int cgr_mode(const kmcf_comm *c)
 {
-    return kmcf_knob_int(KNOB_CG_RESIDENT, 1);      // 0 off, 1 where a matrix qualifies
+    return kmcf_opt_int(c, KNOB_CG_RESIDENT, 1);      // 0 off, 1 where a matrix qualifies
 }
 
 }  // namespace
@@ -743,7 +744,7 @@ static int cgr_plan(kmcf_matrix *m)
     const int share = std::max(kmcf_device_share(), c->group ? c->nranks : 1);
     cgr_args A{};
     int pick = 0;
-    const int forced = kmcf_knob_int(KNOB_CGR_TPB, 0);
+    const int forced = kmcf_opt_int(c, KNOB_CGR_TPB, 0);
     // Tiles per block: the smallest that keeps the grid within 256 blocks -- the flat one-hop reduction needs that, and
     // more blocks mean more CUs whose LDS pipes share the row sums (measured, us per iteration at 1 / 2 / 4 tiles per
     // block: 5 nm device, 286 tiles: 8.1 / 6.8 / 8.3; a rank's eighth of the 40 nm matrix, 881 tiles: 14.5 / 14.5 / 11.4);
@@ -759,25 +760,35 @@ static int cgr_plan(kmcf_matrix *m)
             if (info.per_cu >= 1 && nb <= (long long)info.per_cu * cus / share) { pick = tpb; break; }
         }
     if (group) {
-        // every rank runs the resident launch or none does (the launches wait for each other): the ranks that could, counted
+        // every rank runs the resident launch or none does (the launches wait for each other): the ranks that could, counted.
+        // With them a 20-bit digest d of the group knobs (kmcf_knobs.hpp) as d and d^2: all ranks agree iff
+        // (sum d)^2 == P sum d^2, exact in doubles for P <= 64 -- the knobs read at solve time may have changed since the
+        // matrix was built and compared them
+        uint32_t h = 0;
+        for (int k = 0; k < KNOB_COUNT; ++k)
+            if (kmcf_knobs[k].group) h = h * 31u + kmcf_group_knob_hash(c, (kmcf_knob_id)k);
+        const double dg = (double)((h ^ (h >> 20)) & 0xfffffu);
         double *d_v = c->d_scratch;
-        const double mine = pick ? 1.0 : 0.0;
-        double all = 0.0;
-        KMCF_HIP(hipMemcpyAsync(d_v, &mine, sizeof(double), hipMemcpyHostToDevice, c->stream));
+        double mine[3] = {pick ? 1.0 : 0.0, dg, dg * dg}, all[3] = {0.0, 0.0, 0.0};
+        KMCF_HIP(hipMemcpyAsync(d_v, mine, sizeof(mine), hipMemcpyHostToDevice, c->stream));
         KMCF_HIP(hipStreamSynchronize(c->stream));
-        KMCF_TRY(kmcf_comm_allreduce_sum(const_cast<kmcf_comm *>(c), d_v, 1));
+        KMCF_TRY(kmcf_comm_allreduce_sum(const_cast<kmcf_comm *>(c), d_v, 3));
         KMCF_HIP(hipStreamSynchronize(c->stream));
         KMCF_TRY(kmcf_p2p_check(const_cast<kmcf_comm *>(c)));
-        KMCF_HIP(hipMemcpy(&all, d_v, sizeof(double), hipMemcpyDeviceToHost));
-        if (all != (double)c->nranks) pick = 0;
+        KMCF_HIP(hipMemcpy(all, d_v, sizeof(all), hipMemcpyDeviceToHost));
+        if (all[0] != (double)c->nranks) pick = 0;
+        if (all[1] * all[1] != (double)c->nranks * all[2]) {
+            g->disagree = true;
+            return kmcf_cgr_agreed(m);
+        }
     }
-    if (kmcf_trace()) fprintf(stderr, "cgr_plan rank %d: ok %d tiles %d forced %d pick %d share %d\n", c->rank, (int)ok, m->n_sell_tiles, forced, pick, share);
+    if (kmcf_trace(c)) fprintf(stderr, "cgr_plan rank %d: ok %d tiles %d forced %d pick %d share %d\n", c->rank, (int)ok, m->n_sell_tiles, forced, pick, share);
     if (!pick) return KMCF_OK;
     g->tpb = pick;
     g->nblocks = (m->n_sell_tiles + pick - 1) / pick;
     // reduction: flat (g1 = 0: every block reads every block's sums itself, one hop) up to 256 blocks, else by groups of
     // g1 blocks (two hops); KMCF_CGR_G1 = n forces groups of n
-    int g1 = kmcf_knob_int(KNOB_CGR_G1, g->nblocks <= 256 ? 0 : 16);
+    int g1 = kmcf_opt_int(c, KNOB_CGR_G1, g->nblocks <= 256 ? 0 : 16);
     if (g1 != 0 || g->nblocks > 256) {
         g1 = std::max(2, std::min(64, g1));
         while ((g->nblocks + g1 - 1) / g1 > 64) g1 *= 2;            // one lane per group in the second stage
@@ -804,9 +815,23 @@ static int cgr_plan(kmcf_matrix *m)
     return KMCF_OK;
 }
 
+int kmcf_cgr_agreed(const kmcf_matrix *m)
+{
+    if (!m->cgr || !m->cgr->disagree) return KMCF_OK;
+    std::string mine;
+    for (int k = 0; k < KNOB_COUNT; ++k)
+        if (kmcf_knobs[k].group) {
+            const char *v = kmcf_opt(m->comm, (kmcf_knob_id)k);
+            if (v) mine += std::string(" ") + kmcf_knobs[k].name + "=" + v;
+        }
+    kmcf_set_error("resident plan: the ranks of the group disagree on a group option read at solve time (rank %d has:%s); "
+                   "every rank must set them alike (kmcf_set_option or the environment)", m->comm->rank, mine.empty() ? " none set" : mine.c_str());
+    return KMCF_ERR_STATE;
+}
+
 bool kmcf_cgr_usable(kmcf_matrix *m)
 {
-    if (cgr_mode() == 0) return false;
+    if (cgr_mode(m->comm) == 0) return false;
     // a group agrees on the launch inside cgr_plan (a collective): every rank must get there or none -- so what decides
     // here is the same on every rank (the transport); what differs from rank to rank is weighed inside
     if (m->comm->nranks > 1 ? !m->comm->p2p_active : !kmcf_sell_coded_active(m)) return false;
@@ -875,9 +900,9 @@ int kmcf_cgr_solve(kmcf_matrix *m, bool precond, double tol, int max_it, int fix
     A.d_err = g->d_err; A.h_err = g->h_err;
     KMCF_TRY(cgr_timeout_ticks(c, &A.timeout));
     A.limit = limit; A.check_tol = fixed_iters > 0 ? 0 : 1; A.tol2 = tol * tol;
-    A.gather_delay = kmcf_knob_int(KNOB_CGR_DELAY, 6);
-    A.reduce_delay = kmcf_knob_int(KNOB_CGR_RDELAY, 6);
-    A.adapt_delay = kmcf_knob_int(KNOB_CGR_ADAPT, 16);
+    A.gather_delay = kmcf_opt_int(c, KNOB_CGR_DELAY, 6);
+    A.reduce_delay = kmcf_opt_int(c, KNOB_CGR_RDELAY, 6);
+    A.adapt_delay = kmcf_opt_int(c, KNOB_CGR_ADAPT, 16);
     A.classic = classic ? 1 : 0;
     A.sibling_lds = 1;
     A.nranks = c->nranks; A.rank = c->rank; A.n_loc = m->n_loc;

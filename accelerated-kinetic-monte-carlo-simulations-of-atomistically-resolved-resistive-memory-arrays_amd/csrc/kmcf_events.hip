@@ -1023,7 +1023,7 @@ extern "C" int kmcf_execute_kmc_step(kmcf_comm *c, int N, const int *h_count, co
     // lists are gathered once, the generators are in the same state by contract, and the ranks execute the same
     // events with no collective and no extra synchronisation at all.  KMCF_EVENTS_PARTITIONED=1 keeps the
     // reference's scheme.
-    const bool replicate = c->nranks > 1 && !kmcf_knob(KNOB_EVENTS_PARTITIONED);
+    const bool replicate = c->nranks > 1 && !kmcf_opt_set(c, KNOB_EVENTS_PARTITIONED);
     const int P = replicate ? 1 : c->nranks, rank = replicate ? 0 : c->rank;
     const int count = replicate ? N : h_count[rank], start_i = replicate ? 0 : h_displs[rank];
     const size_t M = (size_t)count * nn;
@@ -1093,7 +1093,7 @@ extern "C" int kmcf_execute_kmc_step(kmcf_comm *c, int N, const int *h_count, co
                                                                d_x, d_y, d_z, d_site_potential_charge, d_site_element,
                                                                d_site_charge, E, d_type, d_prob);
         zero_and_sum_kernel<<<nb, KMCF_BLOCK, 0, st>>>(M, start_i, nn, d_neigh_idx, d_type, d_prob, -1, -1, d_tsum);
-        if (P == 1 && count == N && !kmcf_knob(KNOB_EVENTS_FULLSCAN)) {
+        if (P == 1 && count == N && !kmcf_opt_set(c, KNOB_EVENTS_FULLSCAN)) {
             // the neighbour lists are built once per run (kmc_main.cpp:199): the verdict on their symmetry is
             // kept with the workspace, keyed by the list's address and shape
             if (w->sym_key != d_neigh_idx || w->sym_N != N) {
@@ -1122,7 +1122,7 @@ extern "C" int kmcf_execute_kmc_step(kmcf_comm *c, int N, const int *h_count, co
         // exactly as by the reference (two draws per executed event); a foreign callback cannot be rewound,
         // so it gets batches of one.
         // persistent batch kernel (default; KMCF_EVENTS_PERSISTENT=0: three launches per event) with its row-aligned sums
-        const bool persistent = kmcf_knob_int(KNOB_EVENTS_PERSISTENT, 1) != 0 && nn <= 63;
+        const bool persistent = kmcf_opt_int(c, KNOB_EVENTS_PERSISTENT, 1) != 0 && nn <= 63;
         const long long n_tiles2 = ((long long)count + EV_RT - 1) / EV_RT, n_groups2 = (n_tiles2 + EV_GROUP - 1) / EV_GROUP;
         if (persistent) {
             if (!w->d_rsum &&
@@ -1140,7 +1140,7 @@ extern "C" int kmcf_execute_kmc_step(kmcf_comm *c, int N, const int *h_count, co
         }
         const int BMAX = persistent ? EV_BMAX : 128;
         // (KMCF_EV_TREL: tests shrink the claim range to drive the kernel's out-of-range path)
-        const int trel_max = std::min(std::max(kmcf_knob_int(KNOB_EV_TREL, EV_TREL), 1), EV_TREL);
+        const int trel_max = std::min(std::max(kmcf_opt_int(c, KNOB_EV_TREL, EV_TREL), 1), EV_TREL);
         const bool own_rng = (next_random == kmcf_rng_next);
         if (!w->d_u &&
             (hipMalloc(reinterpret_cast<void **>(&w->d_u), 2 * 512 * sizeof(double)) != hipSuccess ||

@@ -114,7 +114,28 @@ struct kmcf_comm {
     kmcf_scalars *h_scal = nullptr;     // pinned host copy of a solve's scalars (read after the call's one sync)
     // event-step workspace kept between KMC steps (kmcf_execute_kmc_step, kmcf_events.hip)
     struct kmcf_event_cache *ev_cache = nullptr;
+    kmcf_knob_overrides opts;           // kmcf_set_option: this communicator's knob values (kmcf_opt*)
+    bool connect_begun = false;         // kmcf_comm_connect / kmcf_comm_p2p_export ran (or a loopback group was created):
+                                        // connect-scope knobs are refused from here on
 };
+
+// The knobs as this communicator sees them: its override (kmcf_set_option), else the environment.  Read at the same
+// points as the environment was (plan, solve, wait, set-up), never per iteration.
+inline const char *kmcf_opt(const kmcf_comm *c, kmcf_knob_id k) { return kmcf_knob_effective(c->opts, k); }
+inline int kmcf_opt_int(const kmcf_comm *c, kmcf_knob_id k, int dflt)
+{
+    const char *e = kmcf_opt(c, k);
+    return e ? atoi(e) : dflt;
+}
+inline double kmcf_opt_f64(const kmcf_comm *c, kmcf_knob_id k, double dflt)
+{
+    const char *e = kmcf_opt(c, k);
+    return e ? atof(e) : dflt;
+}
+inline bool kmcf_opt_set(const kmcf_comm *c, kmcf_knob_id k) { return kmcf_opt(c, k) != nullptr; }
+inline bool kmcf_trace(const kmcf_comm *c) { return kmcf_opt_set(c, KNOB_TRACE); }
+// digest of the group knobs' effective values on c (kmcf_matrix_build and the resident plan compare it across ranks)
+uint32_t kmcf_group_knob_hash(const kmcf_comm *c, kmcf_knob_id k);
 void kmcf_event_cache_free(kmcf_comm *c);
 
 struct kmcf_subop;   // sub-block operator of the split T matrix (kmcf_tstate.hip)
@@ -274,7 +295,8 @@ struct kmcf_kstate {
 };
 
 void kmcf_sell_free(kmcf_matrix *m);       // frees the row-per-lane layout (kmcf_spmv.hip)
-void kmcf_sell_refine_order(int n_short, int n_cols, const int *rp, const int *col, std::vector<int> &perm, std::vector<int> &cuts);
+void kmcf_sell_refine_order(const kmcf_comm *c, int n_short, int n_cols, const int *rp, const int *col, std::vector<int> &perm,
+                            std::vector<int> &cuts);
 
 // grid of the CG's vector kernels (= r.z / b.b partials): 8 blocks per CU at most, one partial per block.  One step of
 // two rows per lane where that fits: the kernels request a block's first
@@ -291,7 +313,7 @@ inline int kmcf_device_share()
 }
 
 // edge of the bricks of the internal row order of K (kmcf_kstate.hip) and T (kmcf_tstate.hip), in Å; 0: the caller's order
-inline double kmcf_brick_edge() { return kmcf_knob_f64(KNOB_BRICK, 7.7); }
+inline double kmcf_brick_edge(const kmcf_comm *c) { return kmcf_opt_f64(c, KNOB_BRICK, 7.7); }
 
 inline int kmcf_vec_grid(int n)
 {
@@ -321,7 +343,7 @@ inline int kmcf_interior_grid(const kmcf_matrix *m)
 inline bool kmcf_cg_single_reduction(const kmcf_matrix *m)
 {
     bool cg1r = m->comm->nranks > 1;
-    if (const char *e = kmcf_knob(KNOB_CG_VARIANT)) cg1r = (e[0] == 'c' && e[1] == 'g');
+    if (const char *e = kmcf_opt(m->comm, KNOB_CG_VARIANT)) cg1r = (e[0] == 'c' && e[1] == 'g');
     return cg1r;
 }
 
@@ -448,6 +470,7 @@ int kmcf_p2p_direct_put(kmcf_matrix *m, unsigned long long seq, bool skip_if_don
 int kmcf_p2p_direct_ack(kmcf_matrix *m, unsigned long long seq, bool skip_if_done);      // standalone acknowledgement (compute stream)
 // cgr.hip: register-resident PCG (one launch per solve) for matrices whose tiles are all resident at once
 bool kmcf_cgr_usable(kmcf_matrix *m);
+int kmcf_cgr_agreed(const kmcf_matrix *m);        // KMCF_ERR_STATE if the resident plan found the ranks' group knobs differing
 int kmcf_cgr_solve(kmcf_matrix *m, bool precond, double tol, int max_it, int fixed_iters, bool classic);
 bool kmcf_pcg_resident_applies(kmcf_matrix *m);      // kmcf_cg.hip: the next kmcf_pcg_workspace call on m runs as a resident launch
 int kmcf_cgr_check(kmcf_matrix *m);           // after the synchronisation: KMCF_ERR_STATE if a bounded wait expired
@@ -457,7 +480,7 @@ void kmcf_cgr_free(kmcf_matrix *m);
 // pcg_workspace_run; KMCF_CGR_CLASSIC_TILES lowers the limit)
 inline bool kmcf_cgr_classic_applies(const kmcf_matrix *m)
 {
-    return m->comm->nranks == 1 && !m->comm->force_collectives && m->n_sell_tiles <= kmcf_knob_int(KNOB_CGR_CLASSIC_TILES, 1024);
+    return m->comm->nranks == 1 && !m->comm->force_collectives && m->n_sell_tiles <= kmcf_opt_int(m->comm, KNOB_CGR_CLASSIC_TILES, 1024);
 }
 // matrix.hip
 int kmcf_matrix_build(kmcf_comm *c, int matrix_size, const int *counts, const int *displs,

@@ -392,7 +392,7 @@ extern "C" int kmcf_initialize_sparsity_K(kmcf_comm *c, const double *d_x, const
     // 161 -> 135 us for the 40 nm SpMV.  The caller never sees this order (vectors are permuted at the ABI).
     std::vector<int> perm;
     {
-        const double edge = kmcf_brick_edge();
+        const double edge = kmcf_brick_edge(c);
         if (edge > 0 && n_loc > 1) {
             std::vector<double> sx(n_loc), sy(n_loc), sz(n_loc);
             const size_t off = (size_t)N_left + disp, bytes = (size_t)n_loc * sizeof(double);
@@ -575,7 +575,7 @@ extern "C" int kmcf_update_CB_edge_sparse(kmcf_kstate *k, const int *d_site_elem
     // solve_sparse_CG_Jacobi's iteration in its Jacobi-PCG form (kmcf_cg.hip): the CB system is private to this call
     // (the reference builds and frees its own copy, :700-770), so nobody sees A scaled in place, and left unscaled it
     // keeps the two-conductance value codes the coded SpMV runs on.  KMCF_CB_SCALED=1: the literal scaled form.
-    if (m->coded && kmcf_knob_int(KNOB_CB_SCALED, 0) == 0)
+    if (m->coded && kmcf_opt_int(c, KNOB_CB_SCALED, 0) == 0)
         KMCF_TRY(kmcf_jacobi_cg_workspace_absolute(m, 1e-14 /* :719 */, 50000 /* warning threshold :860 */, stats));
     else
         KMCF_TRY(kmcf_scaled_cg_workspace(m, 1e-14 /* :719 */, 50000 /* warning threshold :860 */, nullptr, stats));

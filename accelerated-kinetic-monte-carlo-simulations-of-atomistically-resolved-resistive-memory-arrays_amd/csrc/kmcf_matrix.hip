@@ -178,7 +178,7 @@ int kmcf_matrix_build(kmcf_comm *c, int matrix_size, const int *counts, const in
     if (h_val) val_int.assign(h_val, h_val + nnz);
     std::vector<int> perm_eff;
     if (h_perm && n_loc > 0) perm_eff.assign(h_perm, h_perm + n_loc);
-    const int long_thr = kmcf_knob_int(KNOB_LONG_ROW, 384);
+    const int long_thr = kmcf_opt_int(c, KNOB_LONG_ROW, 384);
     int n_long = 0;
     if (long_thr > 0)
         for (int r = 0; r < n_loc; ++r) n_long += (rp[r + 1] - rp[r] > long_thr);
@@ -204,7 +204,7 @@ int kmcf_matrix_build(kmcf_comm *c, int matrix_size, const int *counts, const in
                 if (valid) seen[r] = 1;
             }
         }
-        if (valid) kmcf_sell_refine_order(m->n_short, n_loc + m->n_halo, rp.data(), col_local.data(), perm_eff, m->h_sell_cuts);
+        if (valid) kmcf_sell_refine_order(c, m->n_short, n_loc + m->n_halo, rp.data(), col_local.data(), perm_eff, m->h_sell_cuts);
     }
     if (!perm_eff.empty()) {
         const int *hp = perm_eff.data();
@@ -319,12 +319,18 @@ int kmcf_matrix_build(kmcf_comm *c, int matrix_size, const int *counts, const in
         // per rank: sent to q | expected from q | landing offset | flag offset | acknowledgement offset (8-byte units, in
         // this rank's window, for what q sends) | this rank's halo size (= distance between its two landing buffers)
         // | first granule of q's values in this rank's granule zone | this rank's reduction zone (register-resident solve)
-        const int W = 8 * P;
+        // | a hash of each group knob's value on this rank (kmcf_knobs.hpp: ranks that disagree would enter different
+        // collectives or device-side protocols, and wait for each other until a time-out)
+        std::vector<kmcf_knob_id> gk;
+        for (int k = 0; k < KNOB_COUNT; ++k)
+            if (kmcf_knobs[k].group) gk.push_back((kmcf_knob_id)k);
+        const int G = (int)gk.size(), W = 8 * P + G;
         std::vector<int> tab((size_t)W * P, 0), cnt(P, W), dsp(P);
         for (int q = 0; q < P; ++q) dsp[q] = W * q;
         int land8 = 0, flag8 = 0, ack8 = 0, ll8 = 0, red8 = 0;
         if (c->p2p_active) KMCF_TRY(kmcf_p2p_matrix_alloc(m, &land8, &flag8, &ack8, &ll8, &red8));
         for (int q = 0; q < P; ++q) tab[(size_t)W * rank + 7 * P + q] = red8;
+        for (int i = 0; i < G; ++i) tab[(size_t)W * rank + 8 * P + i] = (int)(kmcf_group_knob_hash(c, gk[i]) & 0x7fffffffu);
         for (int k = 1; k < nnb; ++k) {
             const int q = m->neighbours[k];
             tab[(size_t)W * rank + q] = (int)m->rows_per_neighbour[k].size();
@@ -344,6 +350,16 @@ int kmcf_matrix_build(kmcf_comm *c, int matrix_size, const int *counts, const in
         if (rc == KMCF_OK && c->p2p_active) rc = kmcf_p2p_check(c);
         if (rc == KMCF_OK && hipMemcpy(tab.data(), d_tab, tab.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) rc = KMCF_ERR_HIP;
         if (rc != KMCF_OK) return rc;
+        // the group knobs first: the same verdict on every rank, before any solve waits on the device
+        for (int i = 0; i < G; ++i)
+            for (int q = 1; q < P; ++q) {
+                if (tab[(size_t)W * q + 8 * P + i] == tab[(size_t)8 * P + i]) continue;
+                const char *v = kmcf_opt(c, gk[i]);
+                KMCF_CHECK(false, KMCF_ERR_STATE,
+                           "kmcf_matrix_build: the ranks of the group disagree on %s (ranks 0 and %d differ; rank %d has %s%s%s); "
+                           "every rank must set it alike (kmcf_set_option or the environment)",
+                           kmcf_knobs[gk[i]].name, q, rank, v ? "\"" : "", v ? v : "it unset", v ? "\"" : "");
+            }
         for (int a = 0; a < P; ++a)
             for (int b = 0; b < P; ++b) {
                 if (tab[(size_t)W * a + b] == tab[(size_t)W * b + P + a]) continue;

@@ -246,7 +246,7 @@ int kmcf_p2p_create(kmcf_comm *c)
     c->p2p = w;
     w->nranks = c->nranks;
     w->rank = c->rank;
-    w->win_bytes = (size_t)std::max(8, kmcf_knob_int(KNOB_P2P_WINDOW_MB, 96)) << 20;
+    w->win_bytes = (size_t)std::max(8, kmcf_opt_int(c, KNOB_P2P_WINDOW_MB, 96)) << 20;
     // fine-grained device memory: stores arriving over xGMI are coherent with the owner's reads; a plain
     // allocation serves where the runtime refuses (same-device tests)
     if (hipExtMallocWithFlags(reinterpret_cast<void **>(&w->win), w->win_bytes, hipDeviceMallocFinegrained) == hipSuccess) {
@@ -255,7 +255,7 @@ int kmcf_p2p_create(kmcf_comm *c)
         (void)hipGetLastError();
         KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&w->win), w->win_bytes));
     }
-    if (kmcf_trace()) fprintf(stderr, "kmcfield p2p: rank %d window %zu MB at %p, %s\n", c->rank, w->win_bytes >> 20, (void *)w->win,
+    if (kmcf_trace(c)) fprintf(stderr, "kmcfield p2p: rank %d window %zu MB at %p, %s\n", c->rank, w->win_bytes >> 20, (void *)w->win,
                                             w->fine_grained ? "fine-grained" : "COARSE-grained (hipExtMallocWithFlags refused)");
     KMCF_HIP(hipMemset(w->win, 0, P2P_OFF_BUMP));
     w->stage_half = align_up((w->win_bytes - P2P_OFF_BUMP) / 4, 4096);       // half of the window for the two staging halves
@@ -271,7 +271,7 @@ int kmcf_p2p_create(kmcf_comm *c)
     KMCF_HIP(hipMemset(w->d_ctr, 0, 4 * sizeof(unsigned int)));
     KMCF_HIP(hipHostMalloc(reinterpret_cast<void **>(&w->h_err), sizeof(int), hipHostMallocDefault));
     *w->h_err = 0;
-    const double ms = kmcf_knob_f64(KNOB_P2P_TIMEOUT_MS, 10000.0);        // (ranks may enter a solve seconds apart: set-up, IO)
+    const double ms = kmcf_opt_f64(c, KNOB_P2P_TIMEOUT_MS, 10000.0);        // (ranks may enter a solve seconds apart: set-up, IO)
     int khz = 0;                                       // wall_clock64() tick rate of this device
     if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, c->device) != hipSuccess || khz <= 0) khz = 100000;
     w->timeout_ticks = (long long)(ms * khz);
@@ -301,6 +301,7 @@ extern "C" int kmcf_comm_p2p_export(kmcf_comm *c, void *h_handle)
 {
     KMCF_CHECK(c && h_handle, KMCF_ERR_ARG, "kmcf_comm_p2p_export: null argument");
     KMCF_CHECK(c->device >= 0, KMCF_ERR_STATE, "kmcf_comm_p2p_export: host-only communicator");
+    c->connect_begun = true;
     static_assert(sizeof(hipIpcMemHandle_t) == KMCF_P2P_HANDLE_BYTES, "IPC handle size");
     KMCF_TRY(kmcf_p2p_create(c));
     hipIpcMemHandle_t h;
@@ -508,8 +509,8 @@ int kmcf_p2p_matrix_connect(kmcf_matrix *m, const std::vector<long long> &r_land
 
 bool kmcf_p2p_direct(const kmcf_matrix *m)
 {
-    const bool off = kmcf_knob_int(KNOB_P2P_DIRECT, 1) == 0;     // (read per call: bench.py times the protocols against each other)
     const kmcf_comm *c = m->comm;
+    const bool off = kmcf_opt_int(c, KNOB_P2P_DIRECT, 1) == 0;     // (read per call: bench.py times the protocols against each other)
     // long rows and the tunnel sub-block read the halo behind p_local: they keep the copying protocol
     return !off && c->p2p_active && c->nranks > 1 && m->p2p && m->p2p->d_put_row && m->n_long_items == 0 && !m->sub;
 }

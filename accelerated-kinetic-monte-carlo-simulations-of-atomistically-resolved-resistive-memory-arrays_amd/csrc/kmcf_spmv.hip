@@ -1156,9 +1156,9 @@ void launch_interior(kmcf_matrix *m, bool with_dot, bool skip_if_done)
 }
 
 // KMCF_SPMV_CODED=0: no dictionary-coded kernels (tiles cut for the plain kernel, values streamed as f64)
-bool coding_allowed() { return kmcf_knob_int(KNOB_SPMV_CODED, 1) != 0; }
+bool coding_allowed(const kmcf_comm *c) { return kmcf_opt_int(c, KNOB_SPMV_CODED, 1) != 0; }
 // KMCF_SPMV_SELL=0: no row-per-lane layout (plan and row order)
-bool sell_allowed() { return kmcf_knob_int(KNOB_SPMV_SELL, 1) != 0; }
+bool sell_allowed(const kmcf_comm *c) { return kmcf_opt_int(c, KNOB_SPMV_SELL, 1) != 0; }
 
 // Cuts the rows into tiles for the window kernels: whole rows, at most 256*WIN_U entries, 8*WIN_U rows (one full
 // pass of the 4-lanes-per-row reduction) and 256*WIN_WQ distinct columns per tile (compact-halo column ids, so
@@ -1176,7 +1176,7 @@ int plan_window(kmcf_matrix *m, bool judge, bool *ok)
     if (n == 0 || rp[n] == 0) return KMCF_OK;
     // the row limit serves the coded kernel (full passes of its row lanes); the plain kernel, whose cost is
     // the value stream, prefers tiles filled to the entry limit
-    const bool for_coded = m->expect_coded && coding_allowed();
+    const bool for_coded = m->expect_coded && coding_allowed(m->comm);
     // (the coded kernel reads a tile's slot stream from an aligned start up to WIN_U - 1 entries early: spmv_wcode_kernel)
     const int cap = KMCF_BLOCK * WIN_U - (for_coded ? WIN_U : 0), wmax = KMCF_BLOCK * WIN_WQ, row_cap = for_coded ? 8 * WIN_U : n;
     m->tiles_for_coded = for_coded;
@@ -1213,7 +1213,7 @@ int plan_window(kmcf_matrix *m, bool judge, bool *ok)
     tiles.push_back(make_int2(n, (int)wcol.size()));
     const int nt = (int)tiles.size() - 1;
     if (judge && double(rp[n]) < 2.0 * double(wcol.size())) return KMCF_OK;
-    if (kmcf_trace())
+    if (kmcf_trace(m->comm))
         fprintf(stderr, "kmcf window plan: %d tiles, %.1f rows, %.1f nnz, %.1f window columns per tile\n", nt, double(n) / nt,
                 double(rp[n]) / nt, double(wcol.size()) / nt);
     KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&m->d_tile), tiles.size() * sizeof(int2)));
@@ -1256,7 +1256,7 @@ int plan_window(kmcf_matrix *m, bool judge, bool *ok)
     *ok = true;
     KMCF_TRY(plan_sell(m, col));                        // (the coded kernel when the values get a dictionary, the f64 one otherwise)
     m->sellv_grid = 0;
-    if (m->sell_ok && m->sell_ident && m->sell_lw == 10 && kmcf_knob_int(KNOB_SPMV_SELLV, 1) != 0) {
+    if (m->sell_ok && m->sell_ident && m->sell_lw == 10 && kmcf_opt_int(m->comm, KNOB_SPMV_SELLV, 1) != 0) {
         int cus = 0;
         const int per_cu = sellv_dispatch(m, false, true, false);
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, m->comm->device) != hipSuccess) cus = 0;
@@ -1274,7 +1274,7 @@ int plan_window(kmcf_matrix *m, bool judge, bool *ok)
 // Tile limits of the row-per-lane layout: window slots per class (the first 256 are the tile's own rows, slot
 // W - 1 stays empty: the padding entries' target) and rows per tile -- 256 where that still gives every CU a tile, fewer on small matrices.
 struct sell_params { int lw, ecap, row_cap; };
-sell_params sell_plan_params(int n)
+sell_params sell_plan_params(const kmcf_comm *c, int n)
 {
     sell_params p;
     p.lw = 10;
@@ -1283,7 +1283,7 @@ sell_params sell_plan_params(int n)
     // 128, 13.8 with 64 -- large tiles win as long as every CU gets one)
     int row_cap = KMCF_BLOCK;
     while (row_cap > 64 && n / row_cap < 256) row_cap /= 2;
-    p.row_cap = std::min(KMCF_BLOCK, std::max(64, kmcf_knob_int(KNOB_SPMV_SELL_ROWS, row_cap) / 64 * 64));
+    p.row_cap = std::min(KMCF_BLOCK, std::max(64, kmcf_opt_int(c, KNOB_SPMV_SELL_ROWS, row_cap) / 64 * 64));
     return p;
 }
 
@@ -1338,11 +1338,11 @@ int sell_cut_tile(int start, int e_max, int row_cap, int ecap, RowId row_id, Col
 int plan_sell(kmcf_matrix *m, const std::vector<int> &col)
 {
     m->sell_ok = false;
-    if (!sell_allowed()) return KMCF_OK;
+    if (!sell_allowed(m->comm)) return KMCF_OK;
     const int n = m->n_short;
     const std::vector<int> &rp = m->h_row_ptr;
     const std::vector<int> &dpos = m->h_diag_pos;
-    const sell_params sp = sell_plan_params(n);
+    const sell_params sp = sell_plan_params(m->comm, n);
     const int lw = sp.lw, W = 1 << lw, row_cap = sp.row_cap;
     int maxlen = 0;
     for (int i = 0; i < n; ++i) maxlen = std::max(maxlen, rp[i + 1] - rp[i] - (dpos[i] >= 0 ? 1 : 0));
@@ -1421,7 +1421,7 @@ int plan_sell(kmcf_matrix *m, const std::vector<int> &col)
     }
     if (st.size() / 4 > (size_t)0x7fffff00 || (double)st.size() > 1.5 * (double)real + 4096.0 * tiles.size()) return KMCF_OK;
     const int nt = (int)tiles.size();
-    const bool trace = kmcf_trace();
+    const bool trace = kmcf_trace(m->comm);
     if (trace)
         fprintf(stderr, "kmcf row-per-lane plan: %d tiles of <= %d rows%s, %.1f rows, %.1f window columns per tile, %lld entries + %.1f %% padding, %d steps\n",
                 nt, row_cap, ident ? " (sorted in place)" : "", double(n) / nt, double(wcol.size()) / nt, (long long)real, 100.0 * (double(st.size()) / double(std::max<int64_t>(real, 1)) - 1.0), nq);
@@ -1467,7 +1467,7 @@ int plan_sell(kmcf_matrix *m, const std::vector<int> &col)
     // beyond the Infinity Cache (256 MiB; 10 x 10 cells = 243 MB of format still run 40.2 us plain against 51.9
     // nontemporal) the entry stream is loaded nontemporal; KMCF_SELL_NT overrides
     m->sell_nt = 2.0 * (double)st.size() + 4.0 * (double)wcol.size() + 28.0 * (double)n > 300e6;
-    m->sell_nt = kmcf_knob_int(KNOB_SELL_NT, m->sell_nt) != 0;
+    m->sell_nt = kmcf_opt_int(m->comm, KNOB_SELL_NT, m->sell_nt) != 0;
     return KMCF_OK;
 }
 
@@ -1509,7 +1509,7 @@ int kmcf_spmv_plan(kmcf_matrix *m)
     // f64-value kernels: nontemporal matrix loads once the CSR stream alone is beyond what the caches can keep
     // between two launches (stream_load; KMCF_SPMV_NT = 0 / 1 overrides)
     m->stream_nt = 12.0 * (double)m->nnz > 192e6;
-    m->stream_nt = kmcf_knob_int(KNOB_SPMV_NT, m->stream_nt) != 0;
+    m->stream_nt = kmcf_opt_int(m->comm, KNOB_SPMV_NT, m->stream_nt) != 0;
     // vec kernel: lanes per row from the mean row length (K rows hold 4..53 entries, mean 25.8)
     const double mean = m->n_short > 0 ? double(m->h_row_ptr[m->n_short]) / m->n_short : 0.0;
     int lpr = 4;
@@ -1518,7 +1518,7 @@ int kmcf_spmv_plan(kmcf_matrix *m)
     m->spmv_grid_b = m->n_boundary_rows > 0 ? grid_for(m->n_boundary_rows, KMCF_BLOCK / lpr) : 0;
 
     // kind: window kernel unless the plan declines (scattered columns, very long rows), then stream, then vec
-    int kind = kmcf_knob_int(KNOB_SPMV_KIND, -1);
+    int kind = kmcf_opt_int(m->comm, KNOB_SPMV_KIND, -1);
     const bool judge = kind < 0;
     if (kind < 0 || kind > 2) kind = 2;
     if (kind == 2) {
@@ -1561,7 +1561,7 @@ int kmcf_spmv_plan(kmcf_matrix *m)
 
 static bool coding_enabled(const kmcf_matrix *m)
 {
-    return m->spmv_kind == 2 && m->d_idx16 && m->tiles_for_coded && coding_allowed();
+    return m->spmv_kind == 2 && m->d_idx16 && m->tiles_for_coded && coding_allowed(m->comm);
 }
 
 int kmcf_matrix_set_dictionary(kmcf_matrix *m, const double *h_dict, int nd)
@@ -1583,7 +1583,7 @@ int kmcf_matrix_set_dictionary(kmcf_matrix *m, const double *h_dict, int nd)
     if (m->sell_ok && (m->sell_grid <= 0 || (m->dict_n <= 2) != (nd <= 2))) {
         m->dict_n = nd;
         m->sell_grid = sell_grid(m);
-        if (kmcf_trace()) fprintf(stderr, "kmcf row-per-lane kernel: grid %d for %d tiles\n", m->sell_grid, m->n_sell_tiles);
+        if (kmcf_trace(m->comm)) fprintf(stderr, "kmcf row-per-lane kernel: grid %d for %d tiles\n", m->sell_grid, m->n_sell_tiles);
     }
     m->dict_n = nd;
     m->sell_dirty = true;                               // the caller is about to write (or has just written) the codes
@@ -1859,11 +1859,12 @@ extern "C" int kmcf_comm_bench(kmcf_matrix *m, int kind, int reps, float *ms_tot
 // tile are contiguous for the kernel.  cuts receives the end row of every tile: plan_sell must cut there (its
 // own greedy cut would try a DIFFERENT next row after a window-limited tile, the next tile's longest).  rp / col: the caller-ordered local pattern (own columns < n_loc, halo
 // slots above); perm[i] = caller row of internal row i; only the first n_short entries are touched.
-void kmcf_sell_refine_order(int n_short, int n_cols, const int *rp, const int *col, std::vector<int> &perm, std::vector<int> &cuts)
+void kmcf_sell_refine_order(const kmcf_comm *c, int n_short, int n_cols, const int *rp, const int *col, std::vector<int> &perm,
+                            std::vector<int> &cuts)
 {
     cuts.clear();
-    if (!sell_allowed() || kmcf_knob_int(KNOB_SPMV_SELL_SORT, 1) == 0 || n_short < 2) return;
-    const sell_params sp = sell_plan_params(n_short);
+    if (!sell_allowed(c) || kmcf_opt_int(c, KNOB_SPMV_SELL_SORT, 1) == 0 || n_short < 2) return;
+    const sell_params sp = sell_plan_params(c, n_short);
     std::vector<unsigned char> mark((size_t)n_cols, 0);
     std::vector<int> touched, len((size_t)n_short);
     for (int i = 0; i < n_short; ++i) {

@@ -1319,7 +1319,7 @@ extern "C" int kmcf_initialize_sparsity_T(kmcf_comm *c, const double *d_site_x, 
     // behind by the matrix builder
     std::vector<int> perm;
     {
-        const double edge = kmcf_brick_edge();
+        const double edge = kmcf_brick_edge(c);
         if (edge > 0 && n_loc > 1) {
             std::vector<int64_t> key((size_t)n_loc);
             for (int r = 0; r < n_loc; ++r) {
@@ -1474,7 +1474,7 @@ static int symm_setup(kmcf_tstate *t)
     sb.nb = nb;
     sb.n_tiles_glob = (long long)nb * (nb + 1) / 2;
     KMCF_CHECK(sb.n_tiles_glob < (long long)INT32_MAX, KMCF_ERR_ARG, "tunnel block of %d points: tile index exceeds int32", n_t);
-    const int strip_len = std::max(1, kmcf_knob_int(KNOB_SUB_STRIP, 16));
+    const int strip_len = std::max(1, kmcf_opt_int(c, KNOB_SUB_STRIP, 16));
     std::vector<int4> strips;
     std::vector<int> first((size_t)nb + 1, 0), tile_local;
     if (sb.spread) tile_local.assign((size_t)sb.n_tiles_glob, -1);
@@ -1653,7 +1653,7 @@ static int t_assemble_async(kmcf_tstate *t, const int *d_site_element, const int
     if (n_t > 0) {
         const long long nbl = (n_t + 63) / 64, all_tiles = nbl * (nbl + 1) / 2;
         const double nn2 = (double)n_t * (double)n_t, nbt = nn2 / 8192;
-        const char *env = kmcf_knob(KNOB_SUB_DENSE);
+        const char *env = kmcf_opt(c, KNOB_SUB_DENSE);
         if (P == 1) {
             sb.dense = n_t >= 2048 && 4.0 * (double)sb.nnz > nn2;
             if (sb.dense && sb.cap_tiles < (size_t)all_tiles * 4096) {

@@ -77,6 +77,9 @@ SIGNATURES = {
     "kmcf_comm_transport": (C.c_char_p, [_P]),
     "kmcf_comm_select_transport": (C.c_int, [_P, C.c_int]),
     "kmcf_comm_rccl_ranks": (C.c_int, [_P]),
+    "kmcf_set_option": (C.c_int, [_P, C.c_char_p, C.c_char_p]),
+    "kmcf_get_option": (C.c_int, [_P, C.c_char_p, C.c_char_p, C.c_int]),
+    "kmcf_option_info": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), _IP, _IP]),
     "kmcf_partition": (C.c_int, [C.c_int, C.c_int, _IP, _IP]),
     "kmcf_matrix_create_csr": (C.c_int, [_P, C.c_int, _IP, _IP, _IP, _IP, _DP, C.POINTER(_P)]),
     "kmcf_matrix_destroy": (C.c_int, [_P]),

@@ -36,7 +36,8 @@ class KMC_comm:
     """Partition tables of src/KMC_comm.h:225-289 (split=false: every module uses
     all ranks) plus this rank's libkmcfield communicator."""
 
-    def __init__(self, nrows_K, nrows_T, nrows_pairwise, nrows_events, rank=0, size=1, device=0, _handle=None):
+    def __init__(self, nrows_K, nrows_T, nrows_pairwise, nrows_events, rank=0, size=1, device=0, _handle=None,
+                 options=None):
         self.lib = _L.load()
         self.rank_K = self.rank_events = self.rank_pairwise = rank
         self.size_K = self.size_events = self.size_pairwise = size
@@ -52,16 +53,49 @@ class KMC_comm:
             _L.check(self.lib.kmcf_comm_create(C.byref(h), device, size, rank), "kmcf_comm_create")
             _handle = h
         self.handle = _handle
+        for key, value in (options or {}).items():       # (before connect(): connect-scope knobs apply)
+            self.set_option(key, value)
 
     @classmethod
-    def loopback_group(cls, nrows_K, nrows_T, nrows_pairwise, nrows_events, size, device=0):
+    def loopback_group(cls, nrows_K, nrows_T, nrows_pairwise, nrows_events, size, device=0, options=None):
         """All `size` ranks of an in-process test group on one GPU (kmcf_comm_create_loopback); each
-        returned KMC_comm must be driven by its own host thread."""
+        returned KMC_comm must be driven by its own host thread.  options: one dict for every rank, or a list of
+        per-rank dicts (KMC_comm.set_option).  The group is connected at creation, so its connect-scope knobs
+        (KMCF_TRANSPORT, ...) come from the environment."""
+        if options is None or isinstance(options, dict):
+            options = [options] * size
+        assert len(options) == size, "options: one dict, or one per rank"
         lib = _L.load()
         arr = (C.c_void_p * size)()
         _L.check(lib.kmcf_comm_create_loopback(arr, device, size), "kmcf_comm_create_loopback")
         return [cls(nrows_K, nrows_T, nrows_pairwise, nrows_events, rank=r, size=size, device=device,
-                    _handle=C.c_void_p(arr[r])) for r in range(size)]
+                    _handle=C.c_void_p(arr[r]), options=options[r]) for r in range(size)]
+
+    def set_option(self, key, value):
+        """kmcf_set_option: a KMCF_* knob on this communicator only (value None: back to the environment).
+        Flags take "1" / "0"; numbers may be given as int or float."""
+        v = None if value is None else str(value).encode()
+        _L.check(self.lib.kmcf_set_option(self.handle, key.encode(), v), "kmcf_set_option(%s)" % key)
+
+    def get_option(self, key):
+        """(effective value or None if the library decides, source): 0 default, 1 environment, 2 set here."""
+        buf = C.create_string_buffer(256)
+        src = self.lib.kmcf_get_option(self.handle, key.encode(), buf, len(buf))
+        if src < 0:
+            _L.check(src, "kmcf_get_option(%s)" % key)
+        v = buf.value.decode()
+        return (v if src else None), src
+
+    @staticmethod
+    def option_table():
+        """kmcf_option_info: [(name, values, scope 0 comm / 1 connect / 2 process, group)] in the library's order."""
+        lib = _L.load()
+        out, i = [], 0
+        name, values, scope, group = C.c_char_p(), C.c_char_p(), C.c_int(), C.c_int()
+        while lib.kmcf_option_info(i, C.byref(name), C.byref(values), C.byref(scope), C.byref(group)) == 0:
+            out.append((name.value.decode(), values.value.decode(), scope.value, bool(group.value)))
+            i += 1
+        return out
 
     @staticmethod
     def partition(nrows, size):
@@ -625,7 +659,8 @@ class Distributed_matrix:
         _L.check(self.lib.kmcf_spmv(self.handle, _ptr(p), _ptr(Ap)), "kmcf_spmv")
 
     def replan(self):
-        """kmcf_spmv_replan: re-plan the SpMV from the KMCF_SPMV_* environment (measurement aid)."""
+        """kmcf_spmv_replan: re-plan the SpMV from the effective KMCF_SPMV_* values -- the communicator's options, else
+        the environment (measurement aid)."""
         _L.check(self.lib.kmcf_spmv_replan(self.handle), "kmcf_spmv_replan")
         return self.info()
 

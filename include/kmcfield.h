@@ -24,6 +24,10 @@
  * (the reference's contract, hipDeviceSynchronize at dist_conjugate_gradient.cpp:271).
  * Work queued on OTHER streams than the declared one must be synchronised by the caller.
  *
+ * Threads: calls on different communicators may run concurrently (the members of an
+ * in-process group are driven by one thread each); calls on ONE communicator, including
+ * kmcf_set_option and kmcf_get_option, must not overlap.
+ *
  * Process model: one process per GPU.  A kmcf_comm is this process's member of
  * the solver group (the reference's MPI communicator comm_K, src/KMC_comm.h:
  * 132-289).  Multi-rank groups exchange halos and dot products with RCCL.
@@ -93,6 +97,23 @@ void *kmcf_comm_stream(kmcf_comm *c);        /* hipStream_t of the compute strea
 /* Declares the hipStream_t the caller queues its own device work on (NULL = legacy null
  * stream, the default); see "Stream ordering contract" above. */
 int kmcf_comm_set_caller_stream(kmcf_comm *c, void *hip_stream);
+
+/* Options per communicator: the KMCF_* knobs of INTEGRATION.md set on one communicator instead of the process's
+ * environment.  A value set here wins over the environment on this communicator only and takes effect where the
+ * environment would: at the next plan, solve, wait or set-up (matrices already planned keep their plan).  Connect-scope
+ * knobs (KMCF_TRANSPORT, KMCF_FORCE_COMM, KMCF_P2P_WINDOW_MB, KMCF_P2P_TIMEOUT_MS, KMCF_LOOPBACK_TIMEOUT_S) are
+ * settable until kmcf_comm_connect / kmcf_comm_p2p_export; in-process groups are connected at creation, so theirs come
+ * from the environment.  Group knobs must be set alike on every rank: kmcf_matrix_build and a group's resident plan
+ * compare them and refuse with KMCF_ERR_STATE.  Host-only communicators (device -1) accept options too.
+ * key: the environment name ("KMCF_SPMV_KIND").  Flags ("set" in the table): "1" sets, "0" masks the environment.
+ * value NULL: drop this communicator's override (back to the environment / the library's default).
+ * KMCF_ERR_ARG: unknown key, value outside the knob's spec, or a process-wide knob (kmcf_last_error says which
+ * and lists the accepted values).  KMCF_ERR_STATE: a connect-time knob on a connected communicator. */
+int kmcf_set_option(kmcf_comm *c, const char *key, const char *value);
+/* Effective value into buf (empty: the library decides).  Returns 0 default, 1 environment, 2 set on c, <0 error. */
+int kmcf_get_option(const kmcf_comm *c, const char *key, char *buf, int buflen);
+/* Enumerate the table: name, accepted values, scope (0 comm, 1 connect, 2 process), group flag. */
+int kmcf_option_info(int index, const char **name, const char **values, int *scope, int *group);
 
 /* Block-row partition rule of the reference (src/KMC_comm.h:249-263,
  * dist_iterative_test/utils.cpp:3-23). */
@@ -198,8 +219,9 @@ int kmcf_spmv(kmcf_matrix *m, const double *d_p, double *d_Ap);
  * events on that stream; *ms_total receives the elapsed time. */
 int kmcf_spmv_bench(kmcf_matrix *m, int reps, int with_dot, float *ms_total);
 
-/* Re-plans the SpMV of an existing matrix from the KMCF_SPMV_* environment (KIND 0 vec / 1 stream (CSR) /
- * 2 window, CODED 0/1, U, WQ, LPR, LPR2) and re-codes its current values.  Measurement aid: bench.py times
+/* Re-plans the SpMV of an existing matrix from the effective KMCF_SPMV_* values -- its communicator's options
+ * (kmcf_set_option), else the environment -- (KIND 0 vec / 1 stream (CSR) / 2 window, CODED 0/1, SELL ...) and
+ * re-codes its current values.  Measurement aid: bench.py times
  * the CSR kernel on the same matrix with it (the `roofline_csr` block); tests compare the kernels. */
 int kmcf_spmv_replan(kmcf_matrix *m);
 
