@@ -674,15 +674,7 @@ int cgr_run_tpb(int tpb, const cgr_args &A, bool launch, hipStream_t st, cgr_lau
 
 int cgr_run_any(const kmcf_matrix *m, int tpb, const cgr_args &A, bool launch, hipStream_t st, cgr_launch_info *info)
 {
-    const int nd = m->dict_n <= 2 ? 2 : 3;
-    switch (m->sell_nq * 10 + nd) {          // the instantiated (steps, dictionary size) pairs of the row-per-lane kernel
-        case 82: return cgr_run_tpb<8, 2>(tpb, A, launch, st, info);
-        case 83: return cgr_run_tpb<8, 3>(tpb, A, launch, st, info);
-        case 132: return cgr_run_tpb<13, 2>(tpb, A, launch, st, info);
-        case 133: return cgr_run_tpb<13, 3>(tpb, A, launch, st, info);
-        case 162: return cgr_run_tpb<16, 2>(tpb, A, launch, st, info);
-        default: return cgr_run_tpb<16, 3>(tpb, A, launch, st, info);
-    }
+    return kmcf_sell_instance(m, [&](auto nq, auto nd) { return cgr_run_tpb<nq, nd>(tpb, A, launch, st, info); });
 }
 
 // Bound of the resident launch's device-side waits in wall-clock ticks: KMCF_CGR_TIMEOUT_MS if set, else a group's
@@ -703,9 +695,6 @@ int cgr_mode(const kmcf_comm *c)
 }
 
 }  // namespace
-
-bool kmcf_sell_coded_active(const kmcf_matrix *m);   // kmcf_spmv.hip
-int kmcf_sell_ready(kmcf_matrix *m);                  // ... its stream holds the current value codes
 
 void kmcf_cgr_free(kmcf_matrix *m)
 {
@@ -732,8 +721,8 @@ static int cgr_plan(kmcf_matrix *m)
     // short rows only, no tunnel block, coded row-per-lane stream with lane t = row r0 + t; one rank, or a group on the
     // peer-to-peer transport whose every rank qualifies (agreed below)
     const bool group = c->nranks > 1;
-    bool ok = !(c->force_collectives || m->sub || m->n_short != m->n_loc || m->n_loc == 0 || !m->sell_ok || !m->sell_ident ||
-                m->n_sell_tiles <= 0 || m->sell_lw != KMCF_SLOT_BITS || !kmcf_sell_coded_active(m));
+    bool ok = !(c->force_collectives || m->sub || m->n_short != m->n_loc || m->n_loc == 0 || !m->sell_ident ||
+                m->n_sell_tiles <= 0 || m->sell_lw != KMCF_SLOT_BITS || kmcf_interior_path(m) != KMCF_PATH_SELL);
     if (group) ok = ok && c->p2p_active && m->p2p && m->p2p->d_putr_ll && m->n_long_items == 0;
     else ok = ok && m->n_halo == 0;
     if (!ok && !group) return KMCF_OK;
@@ -834,7 +823,7 @@ bool kmcf_cgr_usable(kmcf_matrix *m)
     if (cgr_mode(m->comm) == 0) return false;
     // a group agrees on the launch inside cgr_plan (a collective): every rank must get there or none -- so what decides
     // here is the same on every rank (the transport); what differs from rank to rank is weighed inside
-    if (m->comm->nranks > 1 ? !m->comm->p2p_active : !kmcf_sell_coded_active(m)) return false;
+    if (m->comm->nranks > 1 ? !m->comm->p2p_active : kmcf_interior_path(m) != KMCF_PATH_SELL) return false;
     if (cgr_plan(m) != KMCF_OK) return false;
     return m->cgr && m->cgr->tpb > 0;
 }

@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "kmcfield.h"
@@ -220,8 +221,10 @@ struct kmcf_matrix {
     int spmv_grid_b = 0;               // boundary pass grid
     int spmv_lpr = 16;                 // lanes per row (vec kernel)
     bool stream_nt = false;            // the f64-value kernels mark their matrix loads nontemporal (matrix larger than the caches)
-    int spmv_kind = 0;                 // 0: vec<LPR>, 1: stream (nnz-chunked, LDS row reduction), 2: window
-    // window kernel (kind 2): tiles of whole rows whose distinct columns (at most 512) are staged in LDS
+    // format the plan made: 0 none (vec<LPR>), 1 stream chunks, 2 window tiles (+ the row-per-lane layout where sell_ok);
+    // which of the kernels that can read it runs is kmcf_interior_path's choice
+    int spmv_kind = 0;
+    // window kernels (kind 2): tiles of whole rows whose distinct columns (at most 512) are staged in LDS
     int n_tiles = 0;
     int64_t n_wcols = 0;               // sum of the tiles' window sizes
     int2 *d_tile = nullptr;            // (first row, first window slot) per tile, n_tiles + 1
@@ -294,7 +297,7 @@ struct kmcf_kstate {
     double *d_gather = nullptr;
 };
 
-void kmcf_sell_free(kmcf_matrix *m);       // frees the row-per-lane layout (kmcf_spmv.hip)
+void kmcf_spmv_plan_free(kmcf_matrix *m);  // frees the SpMV plan's buffers (kmcf_spmv.hip)
 void kmcf_sell_refine_order(const kmcf_comm *c, int n_short, int n_cols, const int *rp, const int *col, std::vector<int> &perm,
                             std::vector<int> &cuts);
 
@@ -327,17 +330,68 @@ inline int kmcf_vec_grid(int n)
 // true = single-reduction variant (default for multi-rank groups); KMCF_CG_VARIANT=classic|cg1r overrides
 inline bool kmcf_cg_single_reduction(const kmcf_matrix *m);
 
-// grid of the interior SpMV pass = number of p.Ap partials it writes
-inline bool kmcf_sellv_usable(const kmcf_matrix *m)
+// The kernel that computes the interior rows [0, n_short) of an SpMV (kmcf_spmv.hip: launch_interior) and the grid
+// it runs with.  kmcf_interior_path is the one place that decides it, from the plan and the current values.
+enum kmcf_spmv_path {
+    KMCF_PATH_VEC,      // spmv_vec_kernel<LPR>          spmv_grid
+    KMCF_PATH_STREAM,   // spmv_stream_kernel            spmv_grid
+    KMCF_PATH_WINDOW,   // spmv_window_kernel (f64)      spmv_grid
+    KMCF_PATH_WCODE,    // spmv_wcode_kernel (coded)     spmv_grid_coded
+    KMCF_PATH_SELL,     // spmv_sell_kernel (coded)      sell_grid
+    KMCF_PATH_SELLV,    // spmv_sellv_kernel (f64)       sellv_grid
+};
+
+inline kmcf_spmv_path kmcf_interior_path(const kmcf_matrix *m)
 {
-    return m->spmv_kind == 2 && !m->coded && m->sell_ok && m->sell_ident && m->sellv_grid > 0;      // (sellv_grid: 0 with KMCF_SPMV_SELLV=0 at plan time)
+    if (m->spmv_kind == 1) return KMCF_PATH_STREAM;
+    if (m->spmv_kind != 2) return KMCF_PATH_VEC;
+    // row per lane where the plan made that layout: the coded kernel for dictionaries of up to three values, the f64
+    // one where lane t owns row r0 + t (sellv_grid: 0 with KMCF_SPMV_SELLV=0 at plan time)
+    if (m->coded && m->sell_ok && m->dict_n <= 3) return KMCF_PATH_SELL;
+    if (!m->coded && m->sell_ok && m->sell_ident && m->sellv_grid > 0) return KMCF_PATH_SELLV;
+    return m->coded ? KMCF_PATH_WCODE : KMCF_PATH_WINDOW;
 }
 
+// grid of the interior SpMV pass = number of p.Ap partials it writes
 inline int kmcf_interior_grid(const kmcf_matrix *m)
 {
-    if (m->spmv_kind == 2 && m->coded) return (m->sell_ok && m->dict_n <= 3) ? m->sell_grid : m->spmv_grid_coded;
-    if (kmcf_sellv_usable(m)) return m->sellv_grid;
-    return m->spmv_grid;
+    switch (kmcf_interior_path(m)) {
+        case KMCF_PATH_WCODE: return m->spmv_grid_coded;
+        case KMCF_PATH_SELL: return m->sell_grid;
+        case KMCF_PATH_SELLV: return m->sellv_grid;
+        default: return m->spmv_grid;
+    }
+}
+
+// The instances of the coded row-per-lane kernels (spmv_sell_kernel, cgr_kernel): steps of 4 entries held in registers
+// (sell_nq, one of KMCF_SELL_NQ) and dictionary class ND (dictionaries of one value run as two, second = 0).  Calls
+// f(NQ, ND), both as std::integral_constant, for the matrix's pair.
+constexpr int KMCF_SELL_NQ[] = {8, 13, 16};
+
+template <class F>
+int kmcf_sell_instance(const kmcf_matrix *m, F &&f)
+{
+    using I8 = std::integral_constant<int, 8>;
+    using I13 = std::integral_constant<int, 13>;
+    using I16 = std::integral_constant<int, 16>;
+    using D2 = std::integral_constant<int, 2>;
+    using D3 = std::integral_constant<int, 3>;
+    switch (m->sell_nq * 10 + (m->dict_n <= 2 ? 2 : 3)) {
+        case 82: return f(I8{}, D2{});
+        case 83: return f(I8{}, D3{});
+        case 132: return f(I13{}, D2{});
+        case 133: return f(I13{}, D3{});
+        case 162: return f(I16{}, D2{});
+        default: return f(I16{}, D3{});
+    }
+}
+
+// d_val has (or is about to get) new values: the value codes no longer match them, and the f64 row-per-lane stream is
+// refreshed from them before its next use
+inline void kmcf_values_changed(kmcf_matrix *m)
+{
+    m->coded = false;
+    m->sellv_dirty = true;
 }
 
 inline bool kmcf_cg_single_reduction(const kmcf_matrix *m)
@@ -412,6 +466,7 @@ int kmcf_spmv_device(kmcf_matrix *m, bool with_dot, bool skip_if_done, int flags
 // rows, sub-block), added in a fixed order by whoever consumes them
 struct kmcf_part4 { const double *p[4]; int n[4]; };
 kmcf_part4 kmcf_spmv_partials(const kmcf_matrix *m);
+int kmcf_sell_ready(kmcf_matrix *m);          // the coded row-per-lane stream holds the current value codes
 // tstate.hip: y[sub rows] += S x_sub (+ dot partials).  begin: pack the local part of x_sub out of m->d_p and start the
 // all-gather of the ranks' parts -- on the comm stream where the transport allows, so that it runs underneath the
 // neighbour part of the SpMV (spmm_split_sparse2/3 post the exchange first and poll it, dist_spmv_split_sparse.cpp:

@@ -463,13 +463,12 @@ extern "C" int kmcf_matrix_destroy(kmcf_matrix *m)
         hipStreamSynchronize(m->comm->stream);
         hipStreamSynchronize(m->comm->comm_stream);
         kmcf_p2p_matrix_free(m);
-        kmcf_sell_free(m);
+        kmcf_spmv_plan_free(m);
         kmcf_cgr_free(m);
         void *ptrs[] = {m->d_row_ptr, m->d_col, m->d_val, m->d_boundary_rows, m->d_is_boundary, m->d_send_idx,
                         m->d_send_buf, m->d_halo_gid, m->d_p, m->d_Ap, m->d_r, m->d_x, m->d_dinv,
-                        m->d_part_a, m->d_part_b, m->d_part_c, m->d_S, m->d_chunk_row, m->d_perm, m->d_pd, m->d_s,
-                        m->d_tile, m->d_wcol, m->d_idx16, m->d_dict, m->d_diagv, m->d_diag_pos, m->d_code_fail,
-                        m->d_long_items, m->d_long_part, m->d_long_ctr, m->d_tile4, m->d_tbase, m->d_build_tab};
+                        m->d_part_a, m->d_part_b, m->d_part_c, m->d_S, m->d_perm, m->d_pd, m->d_s,
+                        m->d_long_items, m->d_long_part, m->d_long_ctr, m->d_build_tab};
         for (void *p : ptrs)
             if (p) hipFree(p);
     }
@@ -500,12 +499,13 @@ extern "C" int kmcf_matrix_info(const kmcf_matrix *m, kmcf_matrix_info_t *info)
     info->send_rows = m->n_send;
     info->boundary_rows = m->n_boundary_rows;
     info->spmv_kind = m->spmv_kind;
-    const bool sellc = m->spmv_kind == 2 && m->coded && m->sell_ok && m->dict_n <= 3;
-    const bool sell = sellc || kmcf_sellv_usable(m);      // either row-per-lane kernel: the lane stream's figures
-    info->spmv_coded = (m->spmv_kind == 2 && m->coded) ? (sellc ? 2 : 1) : 0;
-    info->spmv_tiles = m->spmv_kind == 2 ? (sell ? m->n_sell_tiles : m->n_tiles) : 0;
-    info->spmv_window_cols = m->spmv_kind == 2 ? (sell ? m->n_sell_wcols : m->n_wcols) : 0;
-    info->spmv_stream_entries = sell ? m->n_sell_entries : (info->spmv_coded ? (int64_t)m->h_row_ptr[m->n_short] : 0);
+    const kmcf_spmv_path path = kmcf_interior_path(m);
+    const bool sell = path == KMCF_PATH_SELL || path == KMCF_PATH_SELLV;     // either row-per-lane kernel: the lane stream's figures
+    const bool window = path == KMCF_PATH_WINDOW || path == KMCF_PATH_WCODE;
+    info->spmv_coded = path == KMCF_PATH_SELL ? 2 : path == KMCF_PATH_WCODE ? 1 : 0;
+    info->spmv_tiles = sell ? m->n_sell_tiles : window ? m->n_tiles : 0;
+    info->spmv_window_cols = sell ? m->n_sell_wcols : window ? m->n_wcols : 0;
+    info->spmv_stream_entries = sell ? m->n_sell_entries : path == KMCF_PATH_WCODE ? (int64_t)m->h_row_ptr[m->n_short] : 0;
     return KMCF_OK;
 }
 

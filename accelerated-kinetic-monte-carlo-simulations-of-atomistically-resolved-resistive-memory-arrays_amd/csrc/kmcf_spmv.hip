@@ -4,21 +4,28 @@
 // HBM-bound work: a CSR launch streams 12 B/nnz (f64 value + i32 column) + 20 B/row (row_ptr, x once,
 // y once); x gathers are served by L2/Infinity Cache.  No MFMA: 2 flop per 12 streamed bytes.
 //
-// Four kernels, chosen per matrix in kmcf_spmv_plan() (DESIGN.md 3.1 has the measurements behind each):
+// kmcf_spmv_plan() lays a matrix out once (DESIGN.md 3.1 has the measurements behind each format).  The interior rows
+// [0, n_short) of every SpMV then run in ONE of six kernels.  kmcf_interior_path (kmcf_internal.hpp) is the one place
+// that picks it, from the plan and the current values; launch_interior runs it, on kmcf_interior_grid blocks.
 //
-//  "window" / "window, coded" (default where columns are local, e.g. K in its internal brick order):
-//    tiles of whole rows whose distinct columns are staged once in LDS; entries carry a 16-bit window
-//    slot instead of a column, and -- where the off-diagonal values come from a small dictionary, as K's
-//    two conductances do -- a 6-bit value code instead of an f64 value: 2 B/nnz.  See the kernels below.
-//  "stream" (short rows with scattered columns): the nnz range is cut
-//    into chunks of whole rows (<= 256*U nnz).  A 256-thread block streams a chunk's
-//    values and columns with fully coalesced loads that do not depend on row_ptr (U
-//    independent loads per lane in flight -> memory-level parallelism instead of the
-//    row_ptr -> col -> x dependency chain per row), gathers x, parks the products in
-//    LDS and then reduces them per row out of LDS.
-//  "vec<LPR>": LPR lanes cooperate on one row (64/LPR rows per wavefront), wave-shuffle
-//    reduction.  Used for the boundary-row pass (row list) and for matrices with rows
-//    longer than a chunk.
+//  vec<LPR> (spmv_vec_kernel): LPR lanes cooperate on one row (64/LPR rows per wavefront), wave-shuffle reduction.
+//    Matrices the other layouts decline (a row longer than a chunk).
+//  stream (spmv_stream_kernel; short rows with scattered columns): the nnz range is cut into chunks of whole rows
+//    (<= 256*U nnz).  A block streams a chunk's values and columns with coalesced loads that do not depend on row_ptr
+//    (memory-level parallelism instead of the row_ptr -> col -> x chain per row), gathers x, parks the products in
+//    LDS and reduces them per row out of LDS.
+//  window (spmv_window_kernel; the default where columns are local, e.g. K in its internal brick order): tiles of
+//    whole rows whose distinct columns are staged once in LDS; entries carry a 16-bit window slot instead of a column.
+//  window, coded (spmv_wcode_kernel): the same tiles while the off-diagonal values come from a small dictionary, as
+//    K's two conductances do: a 6-bit value code above the slot instead of an f64 value, 2 B/nnz.
+//  row per lane, coded (spmv_sell_kernel): one row per lane over tiles of <= 256 rows sharing one x window; an entry
+//    is the LDS offset of its premultiplied product.  Dictionaries of up to three values.
+//  row per lane, f64 (spmv_sellv_kernel): the same layout with the f64 values streamed next to the slots, where lane t
+//    of a tile owns row r0 + t.
+//
+// Beside the interior pass: the boundary rows (those that read halo columns) run after the halo exchange in
+// vec<LPR> over a row list (spmv_vec_halo_kernel in the "direct" peer-to-peer protocol: it waits for the halo in
+// place), and rows longer than KMCF_LONG_ROW in spmv_long_kernel (chunks, deterministic two-stage sum).
 //
 // All fuse the p.Ap dot product of CG (one partial per block, reduced in a fixed order
 // by the consumer kernel) and map blocks to rows XCD-aware: blocks with equal
@@ -832,8 +839,17 @@ int grid_for(int64_t work_items, int per_block)
     return (int)((g + 7) / 8 * 8);
 }
 
-#define KMCF_VEC_ARGS(nrows, isb, rl, part) \
-    nrows, m->d_row_ptr, m->d_col, m->d_val, m->d_p, m->d_Ap, isb, rl, part, m->d_S, chk
+// f(b...) with each runtime bool turned into std::true_type / std::false_type, in order: one instance of f per
+// combination, so that a dispatcher names its kernel once.
+template <class F>
+void with_bools(F &&f) { f(); }
+
+template <class F, class... B>
+void with_bools(F &&f, bool b, B... rest)
+{
+    if (b) with_bools([&](auto... t) { f(std::true_type{}, t...); }, rest...);
+    else with_bools([&](auto... t) { f(std::false_type{}, t...); }, rest...);
+}
 
 template <int LPR>
 void launch_vec(kmcf_matrix *m, bool with_dot, bool skip_if_done, bool boundary_pass)
@@ -841,28 +857,21 @@ void launch_vec(kmcf_matrix *m, bool with_dot, bool skip_if_done, bool boundary_
     hipStream_t st = m->comm->stream;
     const int chk = skip_if_done ? 1 : 0;
     if (!boundary_pass) {
-        const int grid = m->spmv_grid;
+        const int grid = kmcf_interior_grid(m);
         const bool skipb = (m->n_halo > 0);
-        if (with_dot) {
-            if (skipb)
-                spmv_vec_kernel<LPR, true, true, false><<<grid, KMCF_BLOCK, 0, st>>>(KMCF_VEC_ARGS(m->n_short, m->d_is_boundary, nullptr, m->d_part_a));
-            else
-                spmv_vec_kernel<LPR, true, false, false><<<grid, KMCF_BLOCK, 0, st>>>(KMCF_VEC_ARGS(m->n_short, nullptr, nullptr, m->d_part_a));
-        } else {
-            if (skipb)
-                spmv_vec_kernel<LPR, false, true, false><<<grid, KMCF_BLOCK, 0, st>>>(KMCF_VEC_ARGS(m->n_short, m->d_is_boundary, nullptr, nullptr));
-            else
-                spmv_vec_kernel<LPR, false, false, false><<<grid, KMCF_BLOCK, 0, st>>>(KMCF_VEC_ARGS(m->n_short, nullptr, nullptr, nullptr));
-        }
+        const unsigned char *isb = skipb ? m->d_is_boundary : nullptr;
+        double *part = with_dot ? m->d_part_a : nullptr;
+        with_bools([&](auto dot, auto skip) {
+            spmv_vec_kernel<LPR, dot, skip, false><<<grid, KMCF_BLOCK, 0, st>>>(m->n_short, m->d_row_ptr, m->d_col, m->d_val, m->d_p, m->d_Ap,
+                                                                                isb, nullptr, part, m->d_S, chk);
+        }, with_dot, skipb);
     } else {
-        const int grid = m->spmv_grid_b;
         // partials of the boundary pass live behind the interior ones
-        if (with_dot)
-            spmv_vec_kernel<LPR, true, false, true><<<grid, KMCF_BLOCK, 0, st>>>(
-                KMCF_VEC_ARGS(m->n_boundary_rows, nullptr, m->d_boundary_rows, m->d_part_a + KMCF_MAX_PARTIALS));
-        else
-            spmv_vec_kernel<LPR, false, false, true><<<grid, KMCF_BLOCK, 0, st>>>(
-                KMCF_VEC_ARGS(m->n_boundary_rows, nullptr, m->d_boundary_rows, nullptr));
+        double *part = with_dot ? m->d_part_a + KMCF_MAX_PARTIALS : nullptr;
+        with_bools([&](auto dot) {
+            spmv_vec_kernel<LPR, dot, false, true><<<m->spmv_grid_b, KMCF_BLOCK, 0, st>>>(m->n_boundary_rows, m->d_row_ptr, m->d_col, m->d_val, m->d_p,
+                                                                                         m->d_Ap, nullptr, m->d_boundary_rows, part, m->d_S, chk);
+        }, with_dot);
     }
 }
 
@@ -882,13 +891,11 @@ void launch_vec_halo(kmcf_matrix *m, bool with_dot, bool skip_if_done, u64 seq)
 {
     const kmcf_p2p_dev pd = kmcf_p2p_dev_of(m);
     const int chk = skip_if_done ? 1 : 0;
-    if (with_dot)
-        spmv_vec_halo_kernel<LPR, true><<<m->spmv_grid_b, KMCF_BLOCK, 0, m->comm->stream>>>(
-            m->n_boundary_rows, m->d_row_ptr, m->d_col, m->d_val, m->d_p, m->d_Ap, m->d_boundary_rows, m->d_part_a + KMCF_MAX_PARTIALS,
-            m->d_S, chk, m->n_loc, pd, seq);
-    else
-        spmv_vec_halo_kernel<LPR, false><<<m->spmv_grid_b, KMCF_BLOCK, 0, m->comm->stream>>>(
-            m->n_boundary_rows, m->d_row_ptr, m->d_col, m->d_val, m->d_p, m->d_Ap, m->d_boundary_rows, nullptr, m->d_S, chk, m->n_loc, pd, seq);
+    double *part = with_dot ? m->d_part_a + KMCF_MAX_PARTIALS : nullptr;
+    with_bools([&](auto dot) {
+        spmv_vec_halo_kernel<LPR, dot><<<m->spmv_grid_b, KMCF_BLOCK, 0, m->comm->stream>>>(
+            m->n_boundary_rows, m->d_row_ptr, m->d_col, m->d_val, m->d_p, m->d_Ap, m->d_boundary_rows, part, m->d_S, chk, m->n_loc, pd, seq);
+    }, with_dot);
 }
 
 void launch_vec_halo_any(kmcf_matrix *m, bool with_dot, bool skip_if_done, u64 seq)
@@ -906,33 +913,6 @@ void launch_vec_halo_any(kmcf_matrix *m, bool with_dot, bool skip_if_done, u64 s
 // need ~300: measured best), stream chunks of at most 256 * STREAM_U entries reduced by STREAM_LPR2 lanes per row.
 constexpr int WIN_U = 8, WIN_WQ = 2, STREAM_U = 8, STREAM_LPR2 = 4;
 
-#define KMCF_STREAM_ARGS(isb, part) \
-    m->n_chunks, m->d_chunk_row, m->d_row_ptr, m->d_col, m->d_val, m->d_p, m->d_Ap, isb, part, m->d_S, chk
-
-template <int U, int LPR2>
-void launch_stream(kmcf_matrix *m, bool with_dot, bool skip_if_done)
-{
-    hipStream_t st = m->comm->stream;
-    const int chk = skip_if_done ? 1 : 0;
-    const int grid = kmcf_interior_grid(m);
-    const bool skipb = (m->n_halo > 0);
-#define KMCF_STREAM_LAUNCH(NT)                                                                                                       \
-    if (with_dot) {                                                                                                                  \
-        if (skipb) spmv_stream_kernel<U, LPR2, true, true, NT><<<grid, KMCF_BLOCK, 0, st>>>(KMCF_STREAM_ARGS(m->d_is_boundary, m->d_part_a)); \
-        else spmv_stream_kernel<U, LPR2, true, false, NT><<<grid, KMCF_BLOCK, 0, st>>>(KMCF_STREAM_ARGS(nullptr, m->d_part_a));  \
-    } else {                                                                                                                         \
-        if (skipb) spmv_stream_kernel<U, LPR2, false, true, NT><<<grid, KMCF_BLOCK, 0, st>>>(KMCF_STREAM_ARGS(m->d_is_boundary, nullptr)); \
-        else spmv_stream_kernel<U, LPR2, false, false, NT><<<grid, KMCF_BLOCK, 0, st>>>(KMCF_STREAM_ARGS(nullptr, nullptr));      \
-    }
-    if (m->stream_nt) { KMCF_STREAM_LAUNCH(true) } else { KMCF_STREAM_LAUNCH(false) }
-#undef KMCF_STREAM_LAUNCH
-}
-
-#define KMCF_WINDOW_ARGS(isb, part) \
-    m->n_tiles, m->d_tile, m->d_row_ptr, m->d_wcol, m->d_idx16, m->d_val, m->d_p, m->d_Ap, isb, part, m->d_S, chk
-#define KMCF_WCODE_ARGS(isb, part) \
-    m->n_tiles, m->d_tile4, m->d_tbase, m->d_row_ptr, m->d_wcol, m->d_idx16, m->d_p, m->d_Ap, isb, part, m->d_S, chk, m->d_dict, m->d_diagv
-
 template <typename K, typename... A>
 void run_or_query(K kernel, bool launch, int *per_cu, int grid, hipStream_t st, A... args)
 {
@@ -940,119 +920,92 @@ void run_or_query(K kernel, bool launch, int *per_cu, int grid, hipStream_t st, 
     else if (hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, kernel, KMCF_BLOCK, 0) != hipSuccess) *per_cu = 0;
 }
 
-// One place that names every window-kernel instance.  which: 0 plain (values streamed), 1 dictionary-coded.
-// launch = false: return the resident blocks per CU of that instance instead of launching it.
-template <int U, int WQ>
-int window_dispatch(kmcf_matrix *m, int which, bool launch, bool with_dot, bool skip_if_done)
+// One dispatcher per interior kernel, each naming its kernel once.  launch = true: run it on the interior grid;
+// launch = false: return the resident blocks per CU of the instance that would run instead (resident_grid).
+void stream_dispatch(kmcf_matrix *m, bool with_dot, bool skip_if_done)
 {
     hipStream_t st = m->comm->stream;
-    const int chk = skip_if_done ? 1 : 0;
+    const int chk = skip_if_done ? 1 : 0, grid = kmcf_interior_grid(m);
     const bool skipb = (m->n_halo > 0);
     const unsigned char *isb = skipb ? m->d_is_boundary : nullptr;
     double *part = with_dot ? m->d_part_a : nullptr;
-    const int grid = launch ? kmcf_interior_grid(m) : 0;
-    int pc = 0;
-    if (which == 0) {
-#define KMCF_WINDOW_LAUNCH(NT)                                                                                                            \
-        if (with_dot) {                                                                                                                   \
-            if (skipb) run_or_query(spmv_window_kernel<U, WQ, 4, true, true, NT>, launch, &pc, grid, st, KMCF_WINDOW_ARGS(isb, part));    \
-            else run_or_query(spmv_window_kernel<U, WQ, 4, true, false, NT>, launch, &pc, grid, st, KMCF_WINDOW_ARGS(isb, part));          \
-        } else {                                                                                                                          \
-            if (skipb) run_or_query(spmv_window_kernel<U, WQ, 4, false, true, NT>, launch, &pc, grid, st, KMCF_WINDOW_ARGS(isb, part));   \
-            else run_or_query(spmv_window_kernel<U, WQ, 4, false, false, NT>, launch, &pc, grid, st, KMCF_WINDOW_ARGS(isb, part));         \
-        }
-        if (m->stream_nt) { KMCF_WINDOW_LAUNCH(true) } else { KMCF_WINDOW_LAUNCH(false) }
-#undef KMCF_WINDOW_LAUNCH
-    } else {
-        if (with_dot) {
-            if (skipb) run_or_query(spmv_wcode_kernel<U, WQ, true, true>, launch, &pc, grid, st, KMCF_WCODE_ARGS(isb, part));
-            else run_or_query(spmv_wcode_kernel<U, WQ, true, false>, launch, &pc, grid, st, KMCF_WCODE_ARGS(isb, part));
-        } else {
-            if (skipb) run_or_query(spmv_wcode_kernel<U, WQ, false, true>, launch, &pc, grid, st, KMCF_WCODE_ARGS(isb, part));
-            else run_or_query(spmv_wcode_kernel<U, WQ, false, false>, launch, &pc, grid, st, KMCF_WCODE_ARGS(isb, part));
-        }
-    }
-    return pc;
+    with_bools([&](auto dot, auto skip, auto nt) {
+        spmv_stream_kernel<STREAM_U, STREAM_LPR2, dot, skip, nt><<<grid, KMCF_BLOCK, 0, st>>>(
+            m->n_chunks, m->d_chunk_row, m->d_row_ptr, m->d_col, m->d_val, m->d_p, m->d_Ap, isb, part, m->d_S, chk);
+    }, with_dot, skipb, m->stream_nt);
 }
 
-#define KMCF_SELL_ARGS(isb, part) \
-    m->n_sell_tiles, m->d_sell_tile, m->d_sell_wave, m->d_sell_lrow, m->d_sell_wcol, reinterpret_cast<const sell_pair *>(m->d_sell), \
-        m->d_p, m->d_Ap, isb, part, m->d_S, chk, m->d_dict, m->d_diagv
-
-template <int NQ, int LW, int ND, bool IDENT>
-int sell_dispatch1(kmcf_matrix *m, bool launch, bool with_dot, bool skip_if_done)
+int window_dispatch(kmcf_matrix *m, bool launch, bool with_dot, bool skip_if_done)
 {
     hipStream_t st = m->comm->stream;
-    const int chk = skip_if_done ? 1 : 0;
+    const int chk = skip_if_done ? 1 : 0, grid = launch ? kmcf_interior_grid(m) : 0;
     const bool skipb = (m->n_halo > 0);
     const unsigned char *isb = skipb ? m->d_is_boundary : nullptr;
     double *part = with_dot ? m->d_part_a : nullptr;
-    const int grid = launch ? m->sell_grid : 0;
     int pc = 0;
-    if constexpr (IDENT) {
-        if (!skipb && m->sell_nt && launch) {            // (same registers and LDS: the occupancy query of the plain instance holds)
-            if (with_dot) run_or_query(spmv_sell_kernel<NQ, LW, ND, true, false, true, true>, launch, &pc, grid, st, KMCF_SELL_ARGS(isb, part));
-            else run_or_query(spmv_sell_kernel<NQ, LW, ND, false, false, true, true>, launch, &pc, grid, st, KMCF_SELL_ARGS(isb, part));
-            return pc;
-        }
-    }
-    if (with_dot) {
-        if (skipb) run_or_query(spmv_sell_kernel<NQ, LW, ND, true, true, IDENT>, launch, &pc, grid, st, KMCF_SELL_ARGS(isb, part));
-        else run_or_query(spmv_sell_kernel<NQ, LW, ND, true, false, IDENT>, launch, &pc, grid, st, KMCF_SELL_ARGS(isb, part));
-    } else {
-        if (skipb) run_or_query(spmv_sell_kernel<NQ, LW, ND, false, true, IDENT>, launch, &pc, grid, st, KMCF_SELL_ARGS(isb, part));
-        else run_or_query(spmv_sell_kernel<NQ, LW, ND, false, false, IDENT>, launch, &pc, grid, st, KMCF_SELL_ARGS(isb, part));
-    }
+    with_bools([&](auto dot, auto skip, auto nt) {
+        run_or_query(spmv_window_kernel<WIN_U, WIN_WQ, 4, dot, skip, nt>, launch, &pc, grid, st, m->n_tiles, m->d_tile, m->d_row_ptr,
+                     m->d_wcol, m->d_idx16, m->d_val, m->d_p, m->d_Ap, isb, part, m->d_S, chk);
+    }, with_dot, skipb, m->stream_nt);
     return pc;
 }
 
-template <int NQ, int LW, int ND>
+int wcode_dispatch(kmcf_matrix *m, bool launch, bool with_dot, bool skip_if_done)
+{
+    hipStream_t st = m->comm->stream;
+    const int chk = skip_if_done ? 1 : 0, grid = launch ? kmcf_interior_grid(m) : 0;
+    const bool skipb = (m->n_halo > 0);
+    const unsigned char *isb = skipb ? m->d_is_boundary : nullptr;
+    double *part = with_dot ? m->d_part_a : nullptr;
+    int pc = 0;
+    with_bools([&](auto dot, auto skip) {
+        run_or_query(spmv_wcode_kernel<WIN_U, WIN_WQ, dot, skip>, launch, &pc, grid, st, m->n_tiles, m->d_tile4, m->d_tbase, m->d_row_ptr,
+                     m->d_wcol, m->d_idx16, m->d_p, m->d_Ap, isb, part, m->d_S, chk, m->d_dict, m->d_diagv);
+    }, with_dot, skipb);
+    return pc;
+}
+
 int sell_dispatch(kmcf_matrix *m, bool launch, bool with_dot, bool skip_if_done)
 {
-    return m->sell_ident ? sell_dispatch1<NQ, LW, ND, true>(m, launch, with_dot, skip_if_done)
-                         : sell_dispatch1<NQ, LW, ND, false>(m, launch, with_dot, skip_if_done);
-}
-
-// instantiated (steps, log2 window, dictionary size) triples; dictionaries of one value run as two (second = 0)
-constexpr int KMCF_SELL_NQ[] = {8, 13, 16};
-
-int sell_dispatch_any(kmcf_matrix *m, bool launch, bool with_dot, bool skip_if_done)
-{
     constexpr int LW = 10;
-    const int nd = m->dict_n <= 2 ? 2 : 3;
-    switch (m->sell_nq * 10 + nd) {
-        case 82: return sell_dispatch<8, LW, 2>(m, launch, with_dot, skip_if_done);
-        case 83: return sell_dispatch<8, LW, 3>(m, launch, with_dot, skip_if_done);
-        case 132: return sell_dispatch<13, LW, 2>(m, launch, with_dot, skip_if_done);
-        case 133: return sell_dispatch<13, LW, 3>(m, launch, with_dot, skip_if_done);
-        case 162: return sell_dispatch<16, LW, 2>(m, launch, with_dot, skip_if_done);
-        default: return sell_dispatch<16, LW, 3>(m, launch, with_dot, skip_if_done);
-    }
+    hipStream_t st = m->comm->stream;
+    const int chk = skip_if_done ? 1 : 0, grid = launch ? kmcf_interior_grid(m) : 0;
+    const bool skipb = (m->n_halo > 0);
+    const unsigned char *isb = skipb ? m->d_is_boundary : nullptr;
+    double *part = with_dot ? m->d_part_a : nullptr;
+    const sell_pair *stream = reinterpret_cast<const sell_pair *>(m->d_sell);
+    int pc = 0;
+    kmcf_sell_instance(m, [&](auto nq, auto nd) {
+        with_bools([&](auto dot, auto skip, auto ident) {
+            auto run = [&](auto kernel) {
+                run_or_query(kernel, launch, &pc, grid, st, m->n_sell_tiles, m->d_sell_tile, m->d_sell_wave, m->d_sell_lrow, m->d_sell_wcol,
+                             stream, m->d_p, m->d_Ap, isb, part, m->d_S, chk, m->d_dict, m->d_diagv);
+            };
+            // the nontemporal instance exists only for IDENT without a boundary skip (same registers and LDS: the
+            // occupancy query of the plain instance holds)
+            if constexpr (ident && !skip) {
+                if (m->sell_nt && launch) return run(spmv_sell_kernel<nq, LW, nd, dot, false, true, true>);
+            }
+            run(spmv_sell_kernel<nq, LW, nd, dot, skip, ident>);
+        }, with_dot, skipb, m->sell_ident);
+        return 0;
+    });
+    return pc;
 }
-
-inline bool sell_active(const kmcf_matrix *m) { return m->spmv_kind == 2 && m->coded && m->sell_ok && m->dict_n <= 3; }
-
-#define KMCF_SELLV_ARGS(isb, part) \
-    m->n_sell_tiles, m->d_sell_tile, m->d_sell_wave, m->d_sell_wcol, reinterpret_cast<const sell_pair *>(m->d_sell), m->d_sellv, m->d_p, m->d_Ap, \
-        isb, part, m->d_S, chk, m->d_diagv
 
 int sellv_dispatch(kmcf_matrix *m, bool launch, bool with_dot, bool skip_if_done)
 {
     constexpr int LW = 10;
     hipStream_t st = m->comm->stream;
-    const int chk = skip_if_done ? 1 : 0;
+    const int chk = skip_if_done ? 1 : 0, grid = launch ? kmcf_interior_grid(m) : 0;
     const bool skipb = (m->n_halo > 0);
     const unsigned char *isb = skipb ? m->d_is_boundary : nullptr;
     double *part = with_dot ? m->d_part_a : nullptr;
-    const int grid = launch ? m->sellv_grid : 0;
     int pc = 0;
-    if (with_dot) {
-        if (skipb) run_or_query(spmv_sellv_kernel<LW, true, true>, launch, &pc, grid, st, KMCF_SELLV_ARGS(isb, part));
-        else run_or_query(spmv_sellv_kernel<LW, true, false>, launch, &pc, grid, st, KMCF_SELLV_ARGS(isb, part));
-    } else {
-        if (skipb) run_or_query(spmv_sellv_kernel<LW, false, true>, launch, &pc, grid, st, KMCF_SELLV_ARGS(isb, part));
-        else run_or_query(spmv_sellv_kernel<LW, false, false>, launch, &pc, grid, st, KMCF_SELLV_ARGS(isb, part));
-    }
+    with_bools([&](auto dot, auto skip) {
+        run_or_query(spmv_sellv_kernel<LW, dot, skip>, launch, &pc, grid, st, m->n_sell_tiles, m->d_sell_tile, m->d_sell_wave, m->d_sell_wcol,
+                     reinterpret_cast<const sell_pair *>(m->d_sell), m->d_sellv, m->d_p, m->d_Ap, isb, part, m->d_S, chk, m->d_diagv);
+    }, with_dot, skipb);
     return pc;
 }
 
@@ -1112,46 +1065,35 @@ int sell_refresh(kmcf_matrix *m)
     return KMCF_OK;
 }
 
-// The window kernels walk their tiles in a static loop, so the grid must be exactly what the chip holds at
-// once: with more blocks than resident slots the surplus ones start only after a first-wave block has
-// finished its whole loop (measured 116 us at 2048 blocks vs 102 us at 7 blocks x 256 CUs; 108 vs 72 us
-// for the coded kernel when 512 B more LDS dropped it from 7 to 6 blocks per CU under an unchanged grid).
-int window_grid(kmcf_matrix *m, int which)
+// The tiled kernels walk their tiles in a static loop, so the grid must be exactly what the chip holds at once: with
+// more blocks than resident slots the surplus ones start only after a first-wave block has finished its whole loop
+// (measured 116 us at 2048 blocks vs 102 us at 7 blocks x 256 CUs; 108 vs 72 us for the coded kernel when 512 B more
+// LDS dropped it from 7 to 6 blocks per CU under an unchanged grid).  per_cu: resident blocks per CU of the instance
+// (its dispatcher's query).
+int resident_grid(const kmcf_matrix *m, int per_cu, int n_tiles)
 {
     int cus = 0;
-    const int per_cu = window_dispatch<WIN_U, WIN_WQ>(m, which, false, true, false);
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, m->comm->device) != hipSuccess) cus = 0;
     const int resident = per_cu * cus / kmcf_device_share();
-    int g = grid_for(m->n_tiles, 1);
+    int g = grid_for(n_tiles, 1);
     if (resident >= 8 && g > resident) g = resident / 8 * 8;
     return g;
 }
 
-int sell_grid(kmcf_matrix *m)
-{
-    int cus = 0;
-    const int per_cu = sell_dispatch_any(m, false, true, false);
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, m->comm->device) != hipSuccess) cus = 0;
-    const int resident = per_cu * cus / kmcf_device_share();
-    int g = grid_for(m->n_sell_tiles, 1);
-    if (resident >= 8 && g > resident) g = resident / 8 * 8;
-    return g;
-}
-
+// The interior rows' kernel, as kmcf_interior_path picks it, after its preparation.
 void launch_interior(kmcf_matrix *m, bool with_dot, bool skip_if_done)
 {
-    if (sell_active(m)) {
-        if (sell_refresh(m) != KMCF_OK) return;
-        sell_dispatch_any(m, true, with_dot, skip_if_done);
-    } else if (kmcf_sellv_usable(m)) {
-        if (sellv_prepare(m) != KMCF_OK) return;
-        sellv_dispatch(m, true, with_dot, skip_if_done);
-    } else if (m->spmv_kind == 2) {
-        window_dispatch<WIN_U, WIN_WQ>(m, m->coded ? 1 : 0, true, with_dot, skip_if_done);
-    } else if (m->spmv_kind == 1) {
-        launch_stream<STREAM_U, STREAM_LPR2>(m, with_dot, skip_if_done);
-    } else {
-        launch_vec_any(m, with_dot, skip_if_done, false);
+    switch (kmcf_interior_path(m)) {
+        case KMCF_PATH_SELL:
+            if (sell_refresh(m) == KMCF_OK) sell_dispatch(m, true, with_dot, skip_if_done);
+            break;
+        case KMCF_PATH_SELLV:
+            if (sellv_prepare(m) == KMCF_OK) sellv_dispatch(m, true, with_dot, skip_if_done);
+            break;
+        case KMCF_PATH_WCODE: wcode_dispatch(m, true, with_dot, skip_if_done); break;
+        case KMCF_PATH_WINDOW: window_dispatch(m, true, with_dot, skip_if_done); break;
+        case KMCF_PATH_STREAM: stream_dispatch(m, with_dot, skip_if_done); break;
+        case KMCF_PATH_VEC: launch_vec_any(m, with_dot, skip_if_done, false); break;
     }
 }
 
@@ -1256,15 +1198,8 @@ int plan_window(kmcf_matrix *m, bool judge, bool *ok)
     *ok = true;
     KMCF_TRY(plan_sell(m, col));                        // (the coded kernel when the values get a dictionary, the f64 one otherwise)
     m->sellv_grid = 0;
-    if (m->sell_ok && m->sell_ident && m->sell_lw == 10 && kmcf_opt_int(m->comm, KNOB_SPMV_SELLV, 1) != 0) {
-        int cus = 0;
-        const int per_cu = sellv_dispatch(m, false, true, false);
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, m->comm->device) != hipSuccess) cus = 0;
-        const int resident = per_cu * cus / kmcf_device_share();
-        int g = grid_for(m->n_sell_tiles, 1);
-        if (resident >= 8 && g > resident) g = resident / 8 * 8;
-        m->sellv_grid = g;
-    }
+    if (m->sell_ok && m->sell_ident && m->sell_lw == 10 && kmcf_opt_int(m->comm, KNOB_SPMV_SELLV, 1) != 0)
+        m->sellv_grid = resident_grid(m, sellv_dispatch(m, false, true, false), m->n_sell_tiles);
     return KMCF_OK;
 }
 
@@ -1526,7 +1461,7 @@ int kmcf_spmv_plan(kmcf_matrix *m)
         KMCF_TRY(plan_window(m, judge, &ok));
         if (ok) {
             m->spmv_kind = 2;
-            m->spmv_grid = window_grid(m, 0);
+            m->spmv_grid = resident_grid(m, window_dispatch(m, false, true, false), m->n_tiles);
             m->spmv_grid_coded = 0;                  // set with the dictionary (kmcf_matrix_set_dictionary)
             return KMCF_OK;
         }
@@ -1566,8 +1501,7 @@ static bool coding_enabled(const kmcf_matrix *m)
 
 int kmcf_matrix_set_dictionary(kmcf_matrix *m, const double *h_dict, int nd)
 {
-    m->coded = false;
-    m->sellv_dirty = true;                               // (the caller is about to write new values)
+    kmcf_values_changed(m);                              // (the caller is about to write new values)
     if (!coding_enabled(m)) return KMCF_OK;
     KMCF_CHECK(nd >= 0 && nd <= KMCF_DICT_MAX, KMCF_ERR_ARG, "value dictionary of %d entries", nd);
     bool same = true;
@@ -1579,10 +1513,10 @@ int kmcf_matrix_set_dictionary(kmcf_matrix *m, const double *h_dict, int nd)
         KMCF_HIP(hipMemcpyAsync(m->d_dict, m->h_dict, sizeof(m->h_dict), hipMemcpyHostToDevice, m->comm->stream));
         m->dict_uploaded = true;
     }
-    if (m->spmv_grid_coded <= 0) m->spmv_grid_coded = window_grid(m, 1);
+    if (m->spmv_grid_coded <= 0) m->spmv_grid_coded = resident_grid(m, wcode_dispatch(m, false, true, false), m->n_tiles);
     if (m->sell_ok && (m->sell_grid <= 0 || (m->dict_n <= 2) != (nd <= 2))) {
         m->dict_n = nd;
-        m->sell_grid = sell_grid(m);
+        m->sell_grid = resident_grid(m, sell_dispatch(m, false, true, false), m->n_sell_tiles);
         if (kmcf_trace(m->comm)) fprintf(stderr, "kmcf row-per-lane kernel: grid %d for %d tiles\n", m->sell_grid, m->n_sell_tiles);
     }
     m->dict_n = nd;
@@ -1593,8 +1527,7 @@ int kmcf_matrix_set_dictionary(kmcf_matrix *m, const double *h_dict, int nd)
 
 int kmcf_matrix_encode_values(kmcf_matrix *m, const double *h_dict, int nd)
 {
-    m->coded = false;
-    m->sellv_dirty = true;                               // d_val holds new values
+    kmcf_values_changed(m);                              // d_val holds new values
     if (!coding_enabled(m) || m->n_short == 0) return KMCF_OK;
     hipStream_t st = m->comm->stream;
     KMCF_TRY(kmcf_matrix_set_dictionary(m, h_dict, nd));
@@ -1613,8 +1546,7 @@ int kmcf_matrix_encode_values(kmcf_matrix *m, const double *h_dict, int nd)
 
 int kmcf_matrix_encode_from_host(kmcf_matrix *m, const double *h_val_internal)
 {
-    m->coded = false;
-    m->sellv_dirty = true;
+    kmcf_values_changed(m);
     if (!coding_enabled(m) || m->n_short == 0) return KMCF_OK;
     // distinct off-diagonal values (bit patterns); give up at the first one beyond the dictionary size
     long long dict[KMCF_DICT_MAX];
@@ -1709,19 +1641,16 @@ int kmcf_spmv_device(kmcf_matrix *m, bool with_dot, bool skip_if_done, int flags
         hipStream_t st = m->comm->stream;
         const int chk = skip_if_done ? 1 : 0;
         double *part = m->d_part_a + 2 * KMCF_MAX_PARTIALS;
-        if (with_dot)
-            spmv_long_kernel<true><<<m->n_long_items, KMCF_BLOCK, 0, st>>>(m->n_long_items, m->d_long_items, m->d_col, m->d_val, m->d_p,
-                                                                          m->d_Ap, m->d_long_part, m->d_long_ctr, part, m->d_S, chk);
-        else
-            spmv_long_kernel<false><<<m->n_long_items, KMCF_BLOCK, 0, st>>>(m->n_long_items, m->d_long_items, m->d_col, m->d_val, m->d_p,
-                                                                           m->d_Ap, m->d_long_part, m->d_long_ctr, part, m->d_S, chk);
+        with_bools([&](auto dot) {
+            spmv_long_kernel<dot><<<m->n_long_items, KMCF_BLOCK, 0, st>>>(m->n_long_items, m->d_long_items, m->d_col, m->d_val, m->d_p,
+                                                                         m->d_Ap, m->d_long_part, m->d_long_ctr, part, m->d_S, chk);
+        }, with_dot);
         KMCF_HIP(hipGetLastError());
     }
     if (m->sub) KMCF_TRY(kmcf_subop_finish(m, with_dot, skip_if_done));
     return KMCF_OK;
 }
 
-bool kmcf_sell_coded_active(const kmcf_matrix *m) { return sell_active(m); }
 int kmcf_sell_ready(kmcf_matrix *m) { return sell_refresh(m); }
 
 kmcf_part4 kmcf_spmv_partials(const kmcf_matrix *m)
@@ -1739,7 +1668,8 @@ extern "C" int kmcf_matrix_sum_plan(const kmcf_matrix *m, kmcf_sum_plan_t *plan,
 {
     KMCF_CHECK(m, KMCF_ERR_ARG, "kmcf_matrix_sum_plan: null matrix");
     KMCF_CHECK(m->d_val, KMCF_ERR_STATE, "kmcf_matrix_sum_plan: host-only matrix");
-    const bool sell = sell_active(m) || kmcf_sellv_usable(m);
+    const kmcf_spmv_path path = kmcf_interior_path(m);
+    const bool sell = path == KMCF_PATH_SELL || path == KMCF_PATH_SELLV;
     if (plan) {
         memset(plan, 0, sizeof(*plan));
         plan->rows = m->n_loc;
@@ -1852,7 +1782,6 @@ extern "C" int kmcf_comm_bench(kmcf_matrix *m, int kind, int reps, float *ms_tot
     return KMCF_OK;
 }
 
-// Re-plan the SpMV of an existing matrix from the KMCF_SPMV_* environment (tuning aid).
 // Refines an internal row order for the row-per-lane layout: the rows of each of its tiles (cut exactly as
 // plan_sell will cut them: the cut depends on the rows' column SETS, not on their order inside a tile) are
 // put into lane order (sell_lane_order: waves of similar length).  Lane t of a tile then owns row r0 + t: x, diagonal and y of a
@@ -1901,38 +1830,30 @@ void kmcf_sell_refine_order(const kmcf_comm *c, int n_short, int n_cols, const i
     }
 }
 
-void kmcf_sell_free(kmcf_matrix *m)
+void kmcf_spmv_plan_free(kmcf_matrix *m)
 {
-    void *ptrs[] = {m->d_sell_tile, m->d_sell_wave, m->d_sell_lrow, m->d_sell_wcol, m->d_sell, m->d_sell_pos, m->d_sellv};
+    void *ptrs[] = {m->d_chunk_row, m->d_tile, m->d_tile4, m->d_tbase, m->d_wcol, m->d_idx16, m->d_dict, m->d_diagv,
+                    m->d_diag_pos, m->d_code_fail, m->d_sell_tile, m->d_sell_wave, m->d_sell_lrow, m->d_sell_wcol,
+                    m->d_sell, m->d_sell_pos, m->d_sellv};
     for (void *p : ptrs)
         if (p) hipFree(p);
-    m->d_sell_tile = nullptr; m->d_sell_wave = nullptr; m->d_sell_lrow = nullptr;
-    m->d_sell_wcol = nullptr; m->d_sell = nullptr; m->d_sell_pos = nullptr; m->d_sellv = nullptr;
-    m->sellv_dirty = true; m->sellv_grid = 0;
-    m->sell_ok = false;
-    m->n_sell_tiles = 0;
+    m->d_chunk_row = nullptr; m->d_tile = nullptr; m->d_tile4 = nullptr; m->d_tbase = nullptr; m->d_wcol = nullptr;
+    m->d_idx16 = nullptr; m->d_dict = nullptr; m->d_diagv = nullptr; m->d_diag_pos = nullptr; m->d_code_fail = nullptr;
+    m->d_sell_tile = nullptr; m->d_sell_wave = nullptr; m->d_sell_lrow = nullptr; m->d_sell_wcol = nullptr;
+    m->d_sell = nullptr; m->d_sell_pos = nullptr; m->d_sellv = nullptr;
+    m->n_chunks = 0; m->n_tiles = 0; m->n_sell_tiles = 0; m->sellv_grid = 0;
+    m->sell_ok = false; m->dict_uploaded = false;
+    kmcf_values_changed(m);
 }
 
+// Re-plan the SpMV of an existing matrix from the KMCF_SPMV_* environment (tuning aid).
 extern "C" int kmcf_spmv_replan(kmcf_matrix *m)
 {
     KMCF_CHECK(m && m->d_val, KMCF_ERR_ARG, "kmcf_spmv_replan: bad matrix");
     KMCF_TRY(kmcf_enter(m->comm));
     KMCF_HIP(hipStreamSynchronize(m->comm->stream));
-    if (m->d_chunk_row) { hipFree(m->d_chunk_row); m->d_chunk_row = nullptr; }
-    if (m->d_tile) { hipFree(m->d_tile); m->d_tile = nullptr; }
-    if (m->d_tile4) { hipFree(m->d_tile4); m->d_tile4 = nullptr; }
-    if (m->d_tbase) { hipFree(m->d_tbase); m->d_tbase = nullptr; }
-    if (m->d_wcol) { hipFree(m->d_wcol); m->d_wcol = nullptr; }
-    if (m->d_idx16) { hipFree(m->d_idx16); m->d_idx16 = nullptr; }
-    if (m->d_dict) { hipFree(m->d_dict); m->d_dict = nullptr; }
-    if (m->d_diagv) { hipFree(m->d_diagv); m->d_diagv = nullptr; }
-    if (m->d_diag_pos) { hipFree(m->d_diag_pos); m->d_diag_pos = nullptr; }
-    if (m->d_code_fail) { hipFree(m->d_code_fail); m->d_code_fail = nullptr; }
-    kmcf_sell_free(m);
+    kmcf_spmv_plan_free(m);
     kmcf_cgr_free(m);                 // (the resident solve's plan follows the row-per-lane layout)
-    m->n_tiles = 0;
-    m->coded = false;
-    m->dict_uploaded = false;
     KMCF_TRY(kmcf_spmv_plan(m));
     // re-code the values now in d_val (tuning aid: a host round trip is fine here)
     std::vector<double> v((size_t)m->nnz);
