@@ -926,6 +926,17 @@ int kmcf_jacobi_cg_workspace_absolute(kmcf_matrix *m, double tol, int max_iterat
     return pcg_loop<true>(m, tol, max_iterations, 0, 1, stats);
 }
 
+int kmcf_pcg_workspace_loop(kmcf_matrix *m, double tol, int max_it, kmcf_solve_stats_t *stats)
+{
+    kmcf_comm *c = m->comm;
+    KMCF_TRY(kmcf_group_rendezvous(c));                   // (in-process test groups: see kmcf_internal.hpp)
+    c->in_solve = true;
+    m->last_solve_resident = false;
+    const int rc = kmcf_cg_single_reduction(m) ? pcg1_loop<true>(m, tol, max_it, 0, stats) : pcg_loop<true>(m, tol, max_it, 0, 0, stats);
+    c->in_solve = false;
+    return rc;
+}
+
 extern "C" int kmcf_solve_sparse_CG_Jacobi(kmcf_matrix *m, double *d_rhs, double *d_x, double tol, int max_iterations,
                                            kmcf_solve_stats_t *stats)
 {

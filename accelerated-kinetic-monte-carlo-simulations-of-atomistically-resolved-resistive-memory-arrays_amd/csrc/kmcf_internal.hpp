@@ -297,6 +297,13 @@ struct kmcf_kstate {
     double *d_gather = nullptr;
 };
 
+// kstate.hip: site classes (d_cls) and their copy per internal column (d_cls_col) for the current elements and charges
+int kmcf_k_classes_async(kmcf_kstate *k, const int *d_site_element, const int *d_site_charge, const int *d_metals,
+                         int num_metals);
+// cg.hip: Jacobi-PCG on the workspace (m->d_r = b, m->d_x = start guess, m->d_dinv) as a loop of kernels, never as the
+// resident launch: for systems other than the one m's resident plan was made for.  The rank group's recurrence.
+int kmcf_pcg_workspace_loop(kmcf_matrix *m, double tol, int max_it, kmcf_solve_stats_t *stats);
+
 void kmcf_spmv_plan_free(kmcf_matrix *m);  // frees the SpMV plan's buffers (kmcf_spmv.hip)
 void kmcf_sell_refine_order(const kmcf_comm *c, int n_short, int n_cols, const int *rp, const int *col, std::vector<int> &perm,
                             std::vector<int> &cuts);

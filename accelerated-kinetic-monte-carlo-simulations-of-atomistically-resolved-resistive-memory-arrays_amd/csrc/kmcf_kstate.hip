@@ -495,20 +495,32 @@ extern "C" int kmcf_update_charge(kmcf_comm *c, const int *d_site_element, int *
         m->d_halo_gid, m->d_perm, k->d_left_row_ptr, k->d_left_col, k->d_right_row_ptr, k->d_right_col, k->d_cls,      \
         high_G, low_G, VL, VR, k->d_diag, k->d_left, k->d_right, m->d_dinv, k->d_rhs, code_idx, code_diag, k->d_cls_col
 
-static int k_assemble_async(kmcf_kstate *k, const int *d_site_element, const int *d_site_charge,
-                            const int *d_metals, int num_metals, double Vd, double high_G, double low_G,
-                            bool cb_rule = false)
+int kmcf_k_classes_async(kmcf_kstate *k, const int *d_site_element, const int *d_site_charge, const int *d_metals,
+                         int num_metals)
 {
     kmcf_comm *c = k->comm;
     kmcf_matrix *m = k->K;
     site_class_kernel<<<grid1d(k->N), KMCF_BLOCK, 0, c->stream>>>(d_site_element, d_site_charge, d_metals, num_metals, k->N, k->d_cls);
     KMCF_HIP(hipGetLastError());
     if (m->n_loc > 0) {
-        constexpr int LPR = 16;
-        const int grid = grid1d((int64_t)m->n_loc * LPR);
         const int n_cols = m->n_loc + m->n_halo;
         cls_col_kernel<<<grid1d(n_cols), KMCF_BLOCK, 0, c->stream>>>(n_cols, m->n_loc, k->N_left + m->row0, k->N_left, m->d_perm,
                                                                     m->d_halo_gid, k->d_cls, k->d_cls_col);
+        KMCF_HIP(hipGetLastError());
+    }
+    return KMCF_OK;
+}
+
+static int k_assemble_async(kmcf_kstate *k, const int *d_site_element, const int *d_site_charge,
+                            const int *d_metals, int num_metals, double Vd, double high_G, double low_G,
+                            bool cb_rule = false)
+{
+    kmcf_comm *c = k->comm;
+    kmcf_matrix *m = k->K;
+    KMCF_TRY(kmcf_k_classes_async(k, d_site_element, d_site_charge, d_metals, num_metals));
+    if (m->n_loc > 0) {
+        constexpr int LPR = 16;
+        const int grid = grid1d((int64_t)m->n_loc * LPR);
         // window SpMV: the off-diagonals are -high_G / -low_G, so the assembly writes their dictionary codes
         // next to the values and the CG's SpMV streams 2 B/nnz (kmcf_internal.hpp, kmcf_matrix::coded)
         const double dict[2] = {-high_G, -low_G};

@@ -48,6 +48,14 @@ class CurrentParams(C.Structure):
                 ("cg_tolerance", C.c_double), ("cg_max_iterations", C.c_int), ("solve_heating", C.c_int)]
 
 
+class HeatParams(C.Structure):
+    """kmcf_heat_params_t"""
+    _fields_ = [("background_temp", C.c_double), ("k_th_metal", C.c_double), ("k_th_vacancies", C.c_double),
+                ("k_th_non_vacancy", C.c_double), ("L_char", C.c_double), ("c_p", C.c_double), ("A", C.c_double),
+                ("t_ox", C.c_double), ("delta_t", C.c_double), ("cg_tolerance", C.c_double),
+                ("cg_max_iterations", C.c_int)]
+
+
 class SolveStats(C.Structure):
     _fields_ = [("iterations", C.c_int), ("converged", C.c_int), ("relres", C.c_double), ("bb", C.c_double),
                 ("rz", C.c_double), ("ms_solve", C.c_float), ("ms_assembly", C.c_float)]
@@ -132,6 +140,8 @@ SIGNATURES = {
                                            C.POINTER(C.c_double), C.POINTER(SolveStats)]),
     "kmcf_update_temperature_global": (C.c_int, [_P, _P, _P, C.c_int, C.c_double, C.c_double, C.c_double,
                                                  C.c_double, C.c_double]),
+    "kmcf_update_temperature_local": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_double,
+                                                C.POINTER(HeatParams), C.POINTER(C.c_double), _IP, C.POINTER(SolveStats)]),
     "kmcf_rng_create": (C.c_int, [C.c_uint, C.POINTER(_P)]),
     "kmcf_rng_next": (C.c_double, [_P]),
     "kmcf_rng_destroy": (C.c_int, [_P]),

@@ -186,6 +186,7 @@ class GPUBuffers:
         self.K_distributed = None      # kmcf_kstate* (K_distributed + K_p_distributed + contact patterns)
         self.T_distributed = None      # kmcf_tstate* (T_distributed + T_p_distributed + atom_* arrays)
         self.site_CB_edge = None
+        self.site_temperature = None   # kmcf_update_temperature_local (created on first use)
         self.atom_virtual_potentials = None   # N_atom + 2 doubles, allocated by initialize_sparsity_T
         self.N_atom_ = 0
 
@@ -432,6 +433,38 @@ def update_temperatureglobal_gpu(site_power, T_bg, N, a_coeff, b_coeff, number_s
                                                 float(a_coeff), float(b_coeff), float(number_steps),
                                                 float(C_thermal), float(small_step)),
              "kmcf_update_temperature_global")
+
+
+def heat_params(background_temp=300.0, k_th_metal=29.0, k_th_vacancies=5.0, k_th_non_vacancy=0.5, L_char=3.5e-10,
+                c_p=1.92, A=51.15e-10 * 51.15e-10, t_ox=52.6838e-10, delta_t=1e-13, cg_tolerance=1e-12,
+                cg_max_iterations=20000):
+    """kmcf_heat_params_t.  Defaults = the "Local thermal model" block of the 5 nm device's parameters.txt; the
+    stopping rule (cg_tolerance, cg_max_iterations) is the library's own (local heat solve)."""
+    return _L.HeatParams(float(background_temp), float(k_th_metal), float(k_th_vacancies), float(k_th_non_vacancy),
+                         float(L_char), float(c_p), float(A), float(t_ox), float(delta_t), float(cg_tolerance),
+                         int(cg_max_iterations))
+
+
+def update_temperature_local_gpu(gpubuf, N, N_left_tot, N_right_tot, step_time, params, num_metals=None):
+    """The solve_heating_local branch of Device::updateTemperature (src/heat_solver.cpp:76-98) as a sparse solve
+    (kmcf_update_temperature_local): gpubuf.site_temperature (N doubles, created at background_temp on first use) is
+    the previous field on entry and the new one, replicated on every rank, on return; gpubuf.site_power is the source.
+    Returns {"Global temperature [K]": T_bg, "steady": bool, "stats": solve statistics}."""
+    lib = _L.load()
+    if getattr(gpubuf, "site_temperature", None) is None:
+        gpubuf.site_temperature = torch.full((gpubuf.N_,), float(params.background_temp), dtype=torch.float64,
+                                             device=gpubuf.device)
+    nm = gpubuf.num_metal_types_ if num_metals is None else int(num_metals)
+    st = _L.SolveStats()
+    T_bg = C.c_double(0.0)
+    steady = C.c_int(0)
+    _L.check(lib.kmcf_update_temperature_local(gpubuf.K_distributed, _ptr(gpubuf.site_element), _ptr(gpubuf.site_charge),
+                                               _ptr(gpubuf.metal_types), nm, _ptr(gpubuf.site_power),
+                                               _ptr(gpubuf.site_temperature), int(N), int(N_left_tot), int(N_right_tot),
+                                               float(step_time), C.byref(params), C.byref(T_bg), C.byref(steady),
+                                               C.byref(st)), "kmcf_update_temperature_local")
+    gpubuf.T_bg.fill_(T_bg.value)
+    return {"Global temperature [K]": T_bg.value, "steady": bool(steady.value), "stats": st.as_dict()}
 
 
 class RandomNumberGenerator:

@@ -475,6 +475,39 @@ int kmcf_update_temperature_global(kmcf_comm *c, const double *d_site_power, dou
                                    double a_coeff, double b_coeff, double number_steps,
                                    double C_thermal, double small_step);
 
+/* Local thermal model: the "Local thermal model" block of the reference's parameters.txt
+ * plus the solver's stopping rule. */
+typedef struct {
+    double background_temp;        /* [K] temperature of the contact sites                         */
+    double k_th_metal;             /* [W/mK] pair of metal sites                                   */
+    double k_th_vacancies;         /* [W/mK] pair of uncharged vacancies (class 2 of K's rule)     */
+    double k_th_non_vacancy;       /* [W/mK] every other pair                                      */
+    double L_char;                 /* [m] pair conductance g = k_th * L_char [W/K]                 */
+    double c_p;                    /* [J/Kcm^3] heat capacity = c_p * 1e6 * A * t_ox, shared       */
+    double A;                      /* [m^2]     equally by the interface sites                     */
+    double t_ox;                   /* [m]                                                          */
+    double delta_t;                /* [s] step_time > 1e3 * delta_t selects the steady state       */
+    double cg_tolerance;           /* sqrt(r.D^-1 r / b.b) <= cg_tolerance, conductances in units  */
+                                   /* of the largest pair conductance (local heat)      */
+    int cg_max_iterations;
+} kmcf_heat_params_t;
+
+/* Local heat solve (the solve_heating_local branch of Device::updateTemperature,
+ * src/heat_solver.cpp:76-98, with a sparse operator: DESIGN.md, "Local heat solve").
+ * Graph Laplacian of pair conductances on K's pattern, contact sites held at
+ * background_temp, source d_site_power [W] (N doubles); one backward-Euler step of
+ * step_time, or the steady state when step_time > 1e3 * delta_t (*h_steady = 1).
+ * d_site_temperature: N doubles in/out.  Its interface slice is T_old and the start guess;
+ * on return every rank holds the whole field (interface solved, contacts = background_temp).
+ * *h_T_bg = mean over the interface sites.  h_T_bg, h_steady and stats may be NULL.
+ * Runs on one rank and on rank groups; overwrites the K values of the state (the next
+ * kmcf_k_assemble refills them) and never uses K's resident solve plan. */
+int kmcf_update_temperature_local(kmcf_kstate *k, const int *d_site_element, const int *d_site_charge,
+                                  const int *d_metals, int num_metals, const double *d_site_power,
+                                  double *d_site_temperature, int N, int N_left_tot, int N_right_tot,
+                                  double step_time, const kmcf_heat_params_t *p,
+                                  double *h_T_bg, int *h_steady, kmcf_solve_stats_t *stats);
+
 /* Site neighbour index list (compute_neighbor_list, src/neighbor_lists_gpu.cu:
  * 55-77, 252-292): nn slots per site, -1 padded, ascending j.  Cell list
  * instead of the O(N^2) scan.  d_neigh_idx: count*nn ints. */
