@@ -442,7 +442,8 @@ int pcg_loop(kmcf_matrix *m, double tol, int max_it, int fixed_iters, int absolu
 // inner products of an iteration -- gamma = (r,z) and delta = (Az,z) -- are available at the same
 // point, so a multi-rank group pays ONE all-reduce (of 3 doubles) per iteration instead of two, and an
 // iteration is 2 kernels (SpMV with fused delta | fused vector update) instead of 3.  The matrix is
-// applied to z = M^-1 r; s = A p is carried by recurrence.  Same stopping rule on gamma / (b.b).
+// applied to z = M^-1 r; s = A p is carried by recurrence.  Same stopping rules on gamma: relative to b.b, or the
+// absolute one of solve_sparse_CG_Jacobi (the band-edge solve of a group).
 // Default for groups of more than one rank (latency-bound there); KMCF_CG_VARIANT=classic|cg1r overrides.
 //
 //   init : r = b - A x0 ; z = r.*dinv ; gamma = (r,z)
@@ -584,7 +585,13 @@ __global__ __launch_bounds__(KMCF_BLOCK) void cg1_update_kernel(
         gamma = red[0]; delta = red[1]; bsum = red[2];
     }
     const double bb = first ? bsum : bb_saved;
-    const bool go = check_tol ? (gamma / bb > tol2) : true;
+    // check_tol as in cg_p_kernel: 0 fixed iteration count; 1 relative rule gamma / b.b > tol^2; 2 absolute rule of
+    // solve_sparse_CG_Jacobi (first test on sqrt(r.z), later ones on r.z).  gamma is the group's sum here -- reduced by
+    // the transport (P2P = false), by the exchange above or by the kernel in front (P2P = true) -- the same bits on every
+    // rank and in every block: all of them stop at the same iteration.
+    bool go = true;
+    if (check_tol == 1) go = gamma / bb > tol2;
+    else if (check_tol == 2) go = (first ? sqrt(gamma) : gamma) > tol2;
     double beta = 0.0, alpha;
     if (first) {
         alpha = gamma / delta;
@@ -665,7 +672,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void cg1_finalize_kernel(part_ref pg, p
 }
 
 template <bool PRECOND>
-int pcg1_loop(kmcf_matrix *m, double tol, int max_it, int fixed_iters, kmcf_solve_stats_t *stats, int flags = 0)
+int pcg1_loop(kmcf_matrix *m, double tol, int max_it, int fixed_iters, int absolute, kmcf_solve_stats_t *stats, int flags = 0)
 {
     kmcf_comm *c = m->comm;
     hipStream_t st = c->stream;
@@ -674,7 +681,7 @@ int pcg1_loop(kmcf_matrix *m, double tol, int max_it, int fixed_iters, kmcf_solv
     const bool multi = c->nranks > 1 || c->force_collectives;
     kmcf_scalars *S = m->d_S;
     const double tol2 = tol * tol;
-    const int check_tol = fixed_iters > 0 ? 0 : 1;
+    const int check_tol = fixed_iters > 0 ? 0 : (absolute ? 2 : 1);
     const int limit = fixed_iters > 0 ? fixed_iters : max_it;
     if (!m->d_pd) {
         KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&m->d_pd), ((size_t)n + 2) * sizeof(double)));
@@ -785,7 +792,7 @@ int pcg1_loop(kmcf_matrix *m, double tol, int max_it, int fixed_iters, kmcf_solv
     KMCF_HIP(hipEventRecord(c->ev_t1, st));
     if (flags & 2) return KMCF_OK;
     KMCF_HIP(hipMemcpyAsync(c->h_scal, S, sizeof(kmcf_scalars), hipMemcpyDeviceToHost, st));
-    return pcg_collect(m, tol2, 0, stats);
+    return pcg_collect(m, tol2, absolute, stats);
 }
 
 }  // namespace
@@ -834,8 +841,8 @@ static int pcg_workspace_run(kmcf_matrix *m, bool precond, double tol, int max_i
         KMCF_TRY(kmcf_cgr_agreed(m));
         if (resident && (fixed_iters > 0 || max_it > 0)) return pcg_resident(m, precond, tol, max_it, fixed_iters, stats, flags, false);
         KMCF_CHECK(!m->solve_x_user && !m->solve_b_src, KMCF_ERR_STATE, "solve set up for a resident launch that does not apply");
-        if (precond) return pcg1_loop<true>(m, tol, max_it, fixed_iters, stats, flags);
-        return pcg1_loop<false>(m, tol, max_it, fixed_iters, stats, flags);
+        if (precond) return pcg1_loop<true>(m, tol, max_it, fixed_iters, 0, stats, flags);
+        return pcg1_loop<false>(m, tol, max_it, fixed_iters, 0, stats, flags);
     }
     // the reference's recurrence as ONE register-resident launch, one rank: two reduction points per iteration, i.e. two
     // waits for everybody's sums against three kernel boundaries (us per iteration, resident / loop: 5 nm device, 286 tiles:
@@ -880,6 +887,25 @@ __global__ __launch_bounds__(KMCF_BLOCK) void scale_matrix_kernel(int n, const i
         for (int j = row_ptr[r] + lane; j < row_ptr[r + 1]; j += LPR) val[j] = val[j] * dis[r] * dis[col[j]];
 }
 
+// The same scaling for the rows of one rank of a group: a_ij * s_i * s_j with s_j the rank's own 1/sqrt(diag) for an own
+// column and the neighbour's -- landed in the halo slot by the matrix's halo exchange -- for a halo column.  16 lanes per
+// row like the other row walks; every entry is written by exactly one lane.
+__global__ __launch_bounds__(KMCF_BLOCK) void scale_matrix_halo_kernel(int n, const int *__restrict__ row_ptr,
+                                                                       const int *__restrict__ col, double *__restrict__ val,
+                                                                       const double *__restrict__ dis,
+                                                                       const double *__restrict__ dis_halo)
+{
+    constexpr int LPR = 16, RPB = KMCF_BLOCK / LPR;
+    const int lane = threadIdx.x % LPR;
+    for (int r = blockIdx.x * RPB + threadIdx.x / LPR; r < n; r += gridDim.x * RPB) {
+        const double si = dis[r];
+        for (int j = row_ptr[r] + lane; j < row_ptr[r + 1]; j += LPR) {
+            const int cj = col[j];
+            val[j] = val[j] * si * (cj < n ? dis[cj] : dis_halo[cj - n]);
+        }
+    }
+}
+
 // jacobi_precondition_array :654-664 (mode 0) / jacobi_unprecondition_array :682-692 (mode 1)
 __global__ __launch_bounds__(KMCF_BLOCK) void scale_vector_kernel(int n, double *__restrict__ a, const double *__restrict__ dis, int mode)
 {
@@ -889,9 +915,32 @@ __global__ __launch_bounds__(KMCF_BLOCK) void scale_vector_kernel(int n, double 
 
 }  // namespace
 
+// CG with the absolute stopping rule of solve_sparse_CG_Jacobi on the workspace, as a loop of kernels.  One rank: the
+// reference's recurrence (whatever KMCF_CG_VARIANT says: the one-rank band-edge solve is what it always was).  A rank
+// group: the group's recurrence, chosen as for K.  Never the resident launch: the system in the matrix is not the one a
+// resident plan of m was made for, and that plan and its buffers are not touched.
+static int cg_absolute_loop(kmcf_matrix *m, bool precond, double tol, int max_it, kmcf_solve_stats_t *stats)
+{
+    kmcf_comm *c = m->comm;
+    if (!(c->nranks > 1 || c->force_collectives))
+        return precond ? pcg_loop<true>(m, tol, max_it, 0, 1, stats) : pcg_loop<false>(m, tol, max_it, 0, 1, stats);
+    KMCF_TRY(kmcf_group_rendezvous(c));                   // (in-process test groups: see kmcf_internal.hpp)
+    c->in_solve = true;
+    m->last_solve_resident = false;
+    int rc;
+    if (kmcf_cg_single_reduction(m))
+        rc = precond ? pcg1_loop<true>(m, tol, max_it, 0, 1, stats) : pcg1_loop<false>(m, tol, max_it, 0, 1, stats);
+    else
+        rc = precond ? pcg_loop<true>(m, tol, max_it, 0, 1, stats) : pcg_loop<false>(m, tol, max_it, 0, 1, stats);
+    c->in_solve = false;
+    return rc;
+}
+
 // solve_sparse_CG_Jacobi on the workspace: m->d_r = rhs, m->d_x = start guess (internal order).
 // Scales A (in place), rhs and the guess, solves, un-scales the solution into m->d_x.  If d_rhs_user is
 // given, the scaled rhs is written back to it (the reference scales the caller's rhs in place, :740).
+// A rank group: every rank scales its own rows; the column scale of a halo entry is the neighbour's 1/sqrt(diag), fetched
+// by ONE halo exchange of that vector (through d_p, like the halo of an SpMV) before the values are touched.
 int kmcf_scaled_cg_workspace(kmcf_matrix *m, double tol, int max_iterations, double *d_rhs_user, kmcf_solve_stats_t *stats)
 {
     kmcf_comm *c = m->comm;
@@ -900,7 +949,15 @@ int kmcf_scaled_cg_workspace(kmcf_matrix *m, double tol, int max_iterations, dou
     double *dis = m->d_dinv;  // workspace: 1/sqrt(diag)
     diag_inv_sqrt_kernel<<<g, KMCF_BLOCK, 0, c->stream>>>(n, m->d_row_ptr, m->d_col, m->d_val, dis);
     scale_vector_kernel<<<g, KMCF_BLOCK, 0, c->stream>>>(n, m->d_r, dis, 0);      // rhs scaled (:740)
-    scale_matrix_kernel<<<g * 4, KMCF_BLOCK, 0, c->stream>>>(n, m->d_row_ptr, m->d_col, m->d_val, dis);  // :745
+    if (c->nranks > 1 || c->force_collectives) {
+        KMCF_HIP(hipGetLastError());
+        KMCF_HIP(hipMemcpyAsync(m->d_p, dis, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        KMCF_TRY(kmcf_group_rendezvous(c));
+        KMCF_TRY(kmcf_halo_exchange_begin(m));
+        if (m->n_halo > 0 || m->n_send > 0) KMCF_TRY(kmcf_halo_exchange_end(m));
+        scale_matrix_halo_kernel<<<g * 4, KMCF_BLOCK, 0, c->stream>>>(n, m->d_row_ptr, m->d_col, m->d_val, dis, m->d_p + n);
+    } else
+        scale_matrix_kernel<<<g * 4, KMCF_BLOCK, 0, c->stream>>>(n, m->d_row_ptr, m->d_col, m->d_val, dis);  // :745
     scale_vector_kernel<<<g, KMCF_BLOCK, 0, c->stream>>>(n, m->d_x, dis, 1);      // start guess (:751)
     KMCF_HIP(hipGetLastError());
     kmcf_values_changed(m);       // the SpMV reads d_val from here on (or the f64 row-per-lane stream refreshed from it)
@@ -908,7 +965,7 @@ int kmcf_scaled_cg_workspace(kmcf_matrix *m, double tol, int max_iterations, dou
     // plain CG on the scaled system; the reference carries r = A y - b and p = -r (:826-836),
     // the same iterates as r = b - A y, p = r used here.  The unpreconditioned loop never
     // touches d_dinv, so `dis` stays intact.
-    KMCF_TRY((pcg_loop<false>(m, std::sqrt(tol * tol), max_iterations, 0, 1, stats)));
+    KMCF_TRY(cg_absolute_loop(m, false, std::sqrt(tol * tol), max_iterations, stats));
     scale_vector_kernel<<<g, KMCF_BLOCK, 0, c->stream>>>(n, m->d_x, dis, 0);      // y = D^-1/2 y' (:864)
     KMCF_HIP(hipGetLastError());
     return KMCF_OK;
@@ -923,7 +980,7 @@ int kmcf_scaled_cg_workspace(kmcf_matrix *m, double tol, int max_iterations, dou
 // m->d_dinv = 1/diag on entry.
 int kmcf_jacobi_cg_workspace_absolute(kmcf_matrix *m, double tol, int max_iterations, kmcf_solve_stats_t *stats)
 {
-    return pcg_loop<true>(m, tol, max_iterations, 0, 1, stats);
+    return cg_absolute_loop(m, true, tol, max_iterations, stats);
 }
 
 int kmcf_pcg_workspace_loop(kmcf_matrix *m, double tol, int max_it, kmcf_solve_stats_t *stats)
@@ -932,7 +989,7 @@ int kmcf_pcg_workspace_loop(kmcf_matrix *m, double tol, int max_it, kmcf_solve_s
     KMCF_TRY(kmcf_group_rendezvous(c));                   // (in-process test groups: see kmcf_internal.hpp)
     c->in_solve = true;
     m->last_solve_resident = false;
-    const int rc = kmcf_cg_single_reduction(m) ? pcg1_loop<true>(m, tol, max_it, 0, stats) : pcg_loop<true>(m, tol, max_it, 0, 0, stats);
+    const int rc = kmcf_cg_single_reduction(m) ? pcg1_loop<true>(m, tol, max_it, 0, 0, stats) : pcg_loop<true>(m, tol, max_it, 0, 0, stats);
     c->in_solve = false;
     return rc;
 }
@@ -942,15 +999,15 @@ extern "C" int kmcf_solve_sparse_CG_Jacobi(kmcf_matrix *m, double *d_rhs, double
 {
     KMCF_CHECK(m && d_rhs && d_x, KMCF_ERR_ARG, "kmcf_solve_sparse_CG_Jacobi: null argument");
     KMCF_CHECK(m->d_val, KMCF_ERR_STATE, "kmcf_solve_sparse_CG_Jacobi: host-only matrix");
-    KMCF_CHECK(m->comm->nranks == 1, KMCF_ERR_ARG, "kmcf_solve_sparse_CG_Jacobi: single-rank solver (reference: one GPU)");
     kmcf_comm *c = m->comm;
+    KMCF_CHECK(c->nranks == 1 || c->connected, KMCF_ERR_COMM, "kmcf_solve_sparse_CG_Jacobi: communicator not connected");
     KMCF_TRY(kmcf_enter(c));
     KMCF_TRY(kmcf_vec_in(m, m->d_r, d_rhs));
     KMCF_TRY(kmcf_vec_in(m, m->d_x, d_x));
     KMCF_TRY(kmcf_scaled_cg_workspace(m, tol, max_iterations, d_rhs, stats));
     KMCF_TRY(kmcf_vec_out(m, d_x, m->d_x));
     KMCF_HIP(hipStreamSynchronize(c->stream));
-    return KMCF_OK;
+    return kmcf_p2p_check(c);
 }
 
 namespace {

@@ -845,6 +845,13 @@ int kmcf_cgr_solve(kmcf_matrix *m, bool precond, double tol, int max_it, int fix
     kmcf_cgr *g = m->cgr;
     KMCF_CHECK(g && g->tpb > 0, KMCF_ERR_STATE, "kmcf_cgr_solve: the matrix has no resident plan");
     kmcf_comm *c = m->comm;
+    // A group's plan is cached (kmcf_cgr_usable re-checks only its transport: asking more would send a subset of ranks
+    // into the planning collective).  The launch reads the coded row-per-lane stream: if the values have left the
+    // dictionary since the plan was made -- the scaled band-edge form or kmcf_matrix_set_values without a new assembly,
+    // on every rank alike -- refuse here, loudly, instead of solving with the codes of the system before.
+    KMCF_CHECK(kmcf_interior_path(m) == KMCF_PATH_SELL && !m->sub, KMCF_ERR_STATE,
+               "kmcf_cgr_solve: the matrix no longer holds the dictionary-coded values its resident plan was made for "
+               "(assemble it again, or set KMCF_CG_RESIDENT=0)");
     hipStream_t st = c->stream;
     KMCF_TRY(kmcf_sell_ready(m));
     const int limit = fixed_iters > 0 ? fixed_iters : max_it;

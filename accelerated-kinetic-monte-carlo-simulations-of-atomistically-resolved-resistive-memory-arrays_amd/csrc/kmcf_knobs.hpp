@@ -67,8 +67,8 @@ inline constexpr kmcf_knob_def kmcf_knobs[] = {
      KNOB_COMM, false, kv_enum("0|1")},
     {KNOB_LONG_ROW, "KMCF_LONG_ROW", "384", "entries; <= 0: none", "rows longer than this go to the long-row kernel",
      KNOB_COMM, false, kv_int(-1000000000, 1000000000)},
-    {KNOB_CB_SCALED, "KMCF_CB_SCALED", "0", "0 / 1", "1: the CB-edge solve in the literal scaled form",
-     KNOB_COMM, false, kv_enum("0|1")},
+    {KNOB_CB_SCALED, "KMCF_CB_SCALED", "0", "0 / 1", "1: the CB-edge solve in the literal scaled form (a group: one more halo exchange)",
+     KNOB_COMM, true, kv_enum("0|1")},
     {KNOB_SUB_DENSE, "KMCF_SUB_DENSE", "dense from a quarter full", "0 bitmap / 1 dense / 2 jagged",
      "tunnel block as bitmap / dense symmetric tiles / jagged tiles (one rank); all ranks of a group must agree",
      KNOB_COMM, true, kv_enum("0|1|2")},

@@ -566,7 +566,12 @@ int kmcf_jacobi_cg_workspace_absolute(kmcf_matrix *m, double tol, int max_iterat
 // update_CB_edge_gpu_sparse (src/potential_solver_gpu.cu:673-772): Laplace solve for the conduction-band
 // edge on the K pattern (the reference rebuilds an identical single-GPU pattern, initialize_sparsity_CB),
 // "either site metal" conductances, contacts at +Vd/2 / -Vd/2, solve_sparse_CG_Jacobi (tol 1e-14),
-// result x eV_to_J.  Start guess = current content of site_CB_edge (:732).  Single rank, like the reference.
+// result x eV_to_J.  Start guess = current content of site_CB_edge (:732).
+// One rank: as the reference runs it.  A rank group (the reference has every rank solve a whole-device copy redundantly;
+// a group's K state holds its own rows only): every rank assembles its rows with the halo columns' classes, the group
+// solves with its recurrence under the same absolute rule, and the interface slices are all-gathered, so that every rank
+// leaves with the whole array -- contacts filled and scaled -- as the T assembly needs it.  The solve is the kernel
+// loop: K's resident plan and its buffers are not touched.
 extern "C" int kmcf_update_CB_edge_sparse(kmcf_kstate *k, const int *d_site_element, const int *d_site_charge,
                                           const int *d_metals, int num_metals, double *d_site_CB_edge, int N,
                                           int N_left_tot, int N_right_tot, double Vd, double high_G, double low_G,
@@ -577,25 +582,31 @@ extern "C" int kmcf_update_CB_edge_sparse(kmcf_kstate *k, const int *d_site_elem
                "kmcf_update_CB_edge_sparse: N/N_left/N_right differ from the pattern's");
     kmcf_comm *c = k->comm;
     kmcf_matrix *m = k->K;
-    KMCF_CHECK(c->nranks == 1, KMCF_ERR_ARG, "kmcf_update_CB_edge_sparse: single-rank solve (the reference runs it on one GPU)");
+    const bool multi = c->nranks > 1 || c->force_collectives;
+    KMCF_CHECK(c->nranks == 1 || c->connected, KMCF_ERR_COMM, "kmcf_update_CB_edge_sparse: communicator not connected");
     KMCF_TRY(kmcf_enter(c));
     KMCF_TRY(k_assemble_async(k, d_site_element, d_site_charge, d_metals, num_metals, Vd, high_G, low_G, true));
     // (the matrix now holds the CB system: values, diag, rhs; the next kmcf_k_assemble refills K)
     KMCF_HIP(hipMemcpyAsync(m->d_r, k->d_rhs, (size_t)m->n_loc * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    double *v_soln = d_site_CB_edge + N_left_tot;
+    double *v_soln = d_site_CB_edge + N_left_tot + m->row0;      // this rank's interface rows, caller's order
     KMCF_TRY(kmcf_vec_in(m, m->d_x, v_soln));
     // solve_sparse_CG_Jacobi's iteration in its Jacobi-PCG form (kmcf_cg.hip): the CB system is private to this call
     // (the reference builds and frees its own copy, :700-770), so nobody sees A scaled in place, and left unscaled it
     // keeps the two-conductance value codes the coded SpMV runs on.  KMCF_CB_SCALED=1: the literal scaled form.
-    if (m->coded && kmcf_opt_int(c, KNOB_CB_SCALED, 0) == 0)
+    // (A group takes the form from the knob alone -- a group knob: the scaled form enters one more halo exchange -- never
+    // from what a single rank's plan made of its rows.)
+    const bool scaled_knob = kmcf_opt_int(c, KNOB_CB_SCALED, 0) != 0;
+    if (multi ? !scaled_knob : (m->coded && !scaled_knob))
         KMCF_TRY(kmcf_jacobi_cg_workspace_absolute(m, 1e-14 /* :719 */, 50000 /* warning threshold :860 */, stats));
     else
         KMCF_TRY(kmcf_scaled_cg_workspace(m, 1e-14 /* :719 */, 50000 /* warning threshold :860 */, nullptr, stats));
     KMCF_TRY(kmcf_vec_out(m, v_soln, m->d_x));
+    // replicated on every rank (as kmcf_sum_and_gather_potential replicates the potential); contacts and units after that
+    if (multi) KMCF_TRY(kmcf_comm_allgatherv_double(c, d_site_CB_edge + N_left_tot, m->counts.data(), m->displs.data()));
     cb_finish_kernel<<<grid1d(N), KMCF_BLOCK, 0, c->stream>>>(d_site_CB_edge, N, N_left_tot, k->N_interface, Vd, 1.60217663e-19);
     KMCF_HIP(hipGetLastError());
     KMCF_HIP(hipStreamSynchronize(c->stream));
-    return KMCF_OK;
+    return kmcf_p2p_check(c);
 }
 
 extern "C" int kmcf_k_assemble(kmcf_kstate *k, const int *d_site_element, const int *d_site_charge,

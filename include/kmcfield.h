@@ -253,10 +253,17 @@ int kmcf_pcg_jacobi(kmcf_matrix *m, double *d_r, double *d_x, const double *d_di
                     double relative_tolerance, int max_iterations, int fixed_iters,
                     kmcf_solve_stats_t *stats);
 
-/* Single-GPU symmetric-scaled CG (solve_sparse_CG_Jacobi, src/
+/* Symmetric-scaled CG (solve_sparse_CG_Jacobi, src/
  * iterative_solvers_gpu.cu:716-887): solves D^-1/2 A D^-1/2 y = D^-1/2 b with
  * an absolute stop ||r||^2 <= tol^2 (tol 1e-14, max 50000 there); A values and
- * rhs are scaled IN PLACE like the reference.  Requires a 1-rank matrix. */
+ * rhs are scaled IN PLACE like the reference.  On a rank group (every rank
+ * calls it, d_rhs / d_x being its rows): 1/sqrt(diag) of the neighbours' rows
+ * comes in by one halo exchange, every rank scales its own rows a_ij s_i s_j
+ * and its slice of rhs and guess, the group runs plain CG with its recurrence
+ * (KMCF_CG_VARIANT) under the same rule.  Afterwards kmcf_matrix_get_values
+ * returns this rank's rows of the scaled matrix, d_rhs holds its scaled rows,
+ * d_x its rows of the solution; `stats` are the group's (the time is the
+ * rank's own). */
 int kmcf_solve_sparse_CG_Jacobi(kmcf_matrix *m, double *d_rhs, double *d_x,
                                 double tol, int max_iterations, kmcf_solve_stats_t *stats);
 
@@ -316,8 +323,14 @@ int kmcf_background_potential_sparse(kmcf_kstate *k, const int *d_site_element, 
  * conduction-band edge on the K pattern: G = high_G if EITHER site is a metal (:289-319),
  * contacts at +Vd/2 (left) / -Vd/2 (right), solve_sparse_CG_Jacobi (tol 1e-14), boundary
  * fill and scaling by eV_to_J = 1.60217663e-19.  d_site_CB_edge: N doubles, in/out (its
- * interface slice is the start guess, :732).  Single-rank, like the reference.  Overwrites
- * the K values of the state (the next kmcf_k_assemble refills them). */
+ * interface slice is the start guess, :732).  Overwrites the K values of the state (the
+ * next kmcf_k_assemble refills them).  On a rank group (every rank calls it with its own
+ * whole-device array): each rank assembles and solves its rows of the K partition, the
+ * stopping rule is read on the group's all-reduced r.z, the interface slices are
+ * all-gathered, and every rank returns with the complete array, contacts filled and in J;
+ * `stats` are the group's (the time is the rank's own).  The solve is a loop of kernels:
+ * a register-resident plan of K and its buffers are not touched.  KMCF_CB_SCALED (a group
+ * knob) chooses the literal scaled form. */
 int kmcf_update_CB_edge_sparse(kmcf_kstate *k, const int *d_site_element, const int *d_site_charge,
                                const int *d_metals, int num_metals, double *d_site_CB_edge, int N,
                                int N_left_tot, int N_right_tot, double Vd, double high_G, double low_G,

@@ -113,7 +113,8 @@ void initialize_sparsity_K(GPUBuffers &gpubuf, int pbc, const double nn_dist, in
 }
 
 // src/iterative_solvers_gpu.cu:199-260: the reference builds a second, single-GPU copy of the K pattern for the
-// conduction-band-edge solve; update_CB_edge_gpu_sparse below works on the K state's own pattern instead.
+// conduction-band-edge solve; update_CB_edge_gpu_sparse below works on the K state's own pattern instead: with several
+// ranks the solve is distributed over comm_K like the K solve, and every rank ends up with the whole band edge.
 void initialize_sparsity_CB(GPUBuffers &gpubuf, int pbc, const double nn_dist, int num_atoms_contact)
 {
     (void)pbc; (void)nn_dist; (void)num_atoms_contact;
@@ -204,7 +205,8 @@ void background_potential_gpu_sparse(hipblasHandle_t, hipsolverDnHandle_t, GPUBu
         std::printf("iteration K = %d, relative residual = %g\n", st.iterations + 1, st.relres);
 }
 
-// src/potential_solver_gpu.cu:673-772 (single GPU; needs initialize_sparsity_K to have run)
+// src/potential_solver_gpu.cu:673-772 (the reference: redundantly on every rank's GPU; here: distributed over comm_K, the
+// result all-gathered into every rank's site_CB_edge; needs initialize_sparsity_K to have run)
 void update_CB_edge_gpu_sparse(hipblasHandle_t, hipsolverDnHandle_t, GPUBuffers &gpubuf, const int N,
                                const int N_left_tot, const int N_right_tot, const double d_Vd, const int pbc,
                                const double d_high_G, const double d_low_G, const double nn_dist, const int num_metals)
@@ -216,7 +218,9 @@ void update_CB_edge_gpu_sparse(hipblasHandle_t, hipsolverDnHandle_t, GPUBuffers 
                                                   reinterpret_cast<const int *>(gpubuf.metal_types), num_metals,
                                                   gpubuf.site_CB_edge, N, N_left_tot, N_right_tot, d_Vd, d_high_G, d_low_G,
                                                   &st), "kmcf_update_CB_edge_sparse");
-    std::printf("# CG steps: %d\n", st.iterations);   // src/iterative_solvers_gpu.cu:862
+    int rank = 0;
+    MPI_Comm_rank(MPI_COMM_WORLD, &rank);
+    if (rank == 0) std::printf("# CG steps: %d\n", st.iterations);   // src/iterative_solvers_gpu.cu:862
 }
 
 // src/potential_solver_gpu.cu:1130-1151.  NB: the reference's main gathers the solution to rank 0
