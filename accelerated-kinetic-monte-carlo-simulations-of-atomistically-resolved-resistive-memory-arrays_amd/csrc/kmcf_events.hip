@@ -16,6 +16,8 @@
 // same loop (events are drawn until the LAST drawn residence time reaches 1/freq; that last draw is the
 // returned time).  Ranks own contiguous site ranges; the partial totals are all-gathered and the rank
 // whose range holds the drawn number selects (MPI_Allgather + MPI_Bcast in the reference, :423-470).
+#include <cfloat>
+#include <algorithm>
 #include <climits>
 #include <cstring>
 #include <chrono>
@@ -37,6 +39,7 @@ struct kmcf_event_cache {
     unsigned char *d_type = nullptr;
     double *d_prob = nullptr, *d_tsum = nullptr, *d_gsum = nullptr, *d_tot = nullptr;
     int *d_ij = nullptr, *d_aff = nullptr, *d_asym = nullptr;
+    int *d_tbad = nullptr;              // thermal rate modes: one word per rank, the first site with an unusable temperature
     double *d_u = nullptr, *d_totlog = nullptr;     // batch: uniforms in, totals out
     int *d_evlog = nullptr;
     void *d_state = nullptr;
@@ -58,7 +61,7 @@ void kmcf_event_cache_free(kmcf_comm *c)
 {
     if (!c || !c->ev_cache) return;
     kmcf_event_cache *w = c->ev_cache;
-    void *ptrs[] = {w->d_type, w->d_prob, w->d_tsum, w->d_gsum, w->d_tot, w->d_ij, w->d_aff, w->d_asym,
+    void *ptrs[] = {w->d_type, w->d_prob, w->d_tsum, w->d_gsum, w->d_tot, w->d_ij, w->d_aff, w->d_asym, w->d_tbad,
                     w->d_u, w->d_totlog, w->d_evlog, w->d_state, w->d_neigh_full, w->d_rsum, w->d_tsum2, w->d_gsum2};
     for (void *p : ptrs)
         if (p) hipFree(p);
@@ -107,15 +110,32 @@ __device__ __forceinline__ double block_sum_ev(double v, double *lds4)
     return t;
 }
 
-// build_event_list_split, src/kmc_events.cu:128-207
+// The site temperatures of the thermal rate modes (KMCF_RATE_EKIN, KMCF_RATE_T_SITE): the whole-device field and the
+// word that receives the smallest site id whose temperature is unusable (atomicMin; the host presets INT_MAX-like).
+struct thermal_field { const double *__restrict__ T; int *__restrict__ bad; };
+__device__ __forceinline__ const double *ev_T(thermal_field th) { return th.T; }
+__device__ __forceinline__ const double *ev_T() { return nullptr; }
+__device__ __forceinline__ int *ev_bad(thermal_field th) { return th.bad; }
+__device__ __forceinline__ int *ev_bad() { return nullptr; }
+
+// build_event_list_split, src/kmc_events.cu:128-207.  MODE = the rate mode (include/kmcfield.h).  KMCF_RATE_T_BG is
+// instantiated with an empty pack: the parameter list and the arithmetic of the kernel before the thermal modes.
+// The thermal modes take one thermal_field behind it and read T[i] once per slot (the same address over a row's nn
+// slots) and T[j] on the generation branch only: the temperature that counts is site s = j for generation, i for
+// recombination and the two diffusions (the first comment on the reference's Ekin lines :81-220; :65 names j for
+// recombination too -- here i, like src/KMCProcess.cpp:462-511).
+template <int MODE, class... TH>
 __global__ __launch_bounds__(KMCF_BLOCK) void build_event_list_kernel(
     int N, int size_i, int start_i, int nn, const int *__restrict__ neigh_idx, const int *__restrict__ layer,
     double T_bg, double freq, double sigma, double k, const double *__restrict__ x, const double *__restrict__ y,
     const double *__restrict__ z, const double *__restrict__ pot, const int *__restrict__ element,
     const int *__restrict__ charge, layer_energies E, unsigned char *__restrict__ event_type,
-    double *__restrict__ event_prob)
+    double *__restrict__ event_prob, TH... th)
 {
+    static_assert(MODE == KMCF_RATE_T_BG ? sizeof...(TH) == 0 : sizeof...(TH) == 1, "thermal modes take one thermal_field");
     const double kB = 8.617333262e-5, epsilon = 1e-200;
+    const double *__restrict__ T = ev_T(th...);
+    int *__restrict__ bad = ev_bad(th...);
     const size_t M = (size_t)size_i * nn;
     for (size_t id = (size_t)blockIdx.x * blockDim.x + threadIdx.x; id < M; id += (size_t)gridDim.x * blockDim.x) {
         int et = EV_NULL;
@@ -128,10 +148,14 @@ __global__ __launch_bounds__(KMCF_BLOCK) void build_event_list_kernel(
             const int ei = element[i], ej = element[j];
             const double dpot = pot[i] - pot[j];
             double EA = 0.0;
+            int s = i;                                          // the site whose temperature counts
+            double Ts = 0.0;
+            if (MODE != KMCF_RATE_T_BG) Ts = T[i];
             if (ei == EL_DEFECT && ej == EL_O) {
                 const double Eg = 2 * dpot;
                 EA = E.gen[layer[j]] - Eg - 0;
                 et = EV_GEN;
+                if (MODE != KMCF_RATE_T_BG) { s = j; Ts = T[j]; }
             }
             if (ei == EL_OXYGEN_DEFECT && ej == EL_VACANCY) {
                 const double self_int_V = v_solve_dev(dist, 2, sigma, k);
@@ -154,7 +178,19 @@ __global__ __launch_bounds__(KMCF_BLOCK) void build_event_list_kernel(
                 EA = E.odiff[layer[j]] - Eo - 0;
                 et = EV_ODIFF;
             }
-            if (et != EV_NULL) P = freq * (1 / (exp(EA / (kB * T_bg)) + epsilon));
+            if (MODE == KMCF_RATE_T_BG) {
+                if (et != EV_NULL) P = freq * (1 / (exp(EA / (kB * T_bg)) + epsilon));
+            } else if (et != EV_NULL) {
+                if (!(Ts > 0.0 && Ts <= DBL_MAX)) {             // zero, negative, inf, NaN: the step refuses the field
+                    atomicMin(bad, s);
+                } else if (MODE == KMCF_RATE_EKIN) {
+                    // Ekin = kB (T[s] - T_bg) (src/KMCProcess.cpp:462); T[s] == T_bg: EA - 0.0, the bits of KMCF_RATE_T_BG
+                    const double EAk = EA - kB * (Ts - T_bg);
+                    P = freq * (1 / (exp(EAk / (kB * T_bg)) + epsilon));
+                } else {
+                    P = freq * (1 / (exp(EA / (kB * Ts)) + epsilon));
+                }
+            }
         }
         event_type[id] = (unsigned char)et;
         event_prob[id] = P;
@@ -999,22 +1035,72 @@ __global__ __launch_bounds__(KMCF_BLOCK) void check_symmetry_kernel(int N, int n
     }
 }
 
-}  // namespace
+constexpr int EV_NO_BAD_SITE = 0x7f7f7f7f;                  // (what hipMemset 0x7f leaves: above every site id)
 
-extern "C" int kmcf_execute_kmc_step(kmcf_comm *c, int N, const int *h_count, const int *h_displs, int nn,
-                                     const int *d_neigh_idx, const int *d_site_layer, double T_bg, double freq,
-                                     double sigma, double k, const double *d_x, const double *d_y, const double *d_z,
-                                     const double *d_site_potential_charge, int *d_site_element, int *d_site_charge,
-                                     int num_layers, const double *h_E_gen, const double *h_E_rec,
-                                     const double *h_E_Vdiff, const double *h_E_Odiff,
-                                     double (*next_random)(void *), void *rng_user, int max_events,
-                                     double *event_time, int *n_events, int *h_event_log)
+// the one pass over the count * nn slots, in the instantiation of the rate mode
+void launch_build_event_list(int rate_mode, int grid, hipStream_t st, int N, int count, int start_i, int nn, const int *d_neigh_idx,
+                             const int *d_site_layer, double T_bg, double freq, double sigma, double k, const double *d_x,
+                             const double *d_y, const double *d_z, const double *d_pot, const int *d_site_element,
+                             const int *d_site_charge, const layer_energies &E, unsigned char *d_type, double *d_prob,
+                             const double *d_site_temperature, int *d_bad)
+{
+    const thermal_field th = {d_site_temperature, d_bad};
+    if (rate_mode == KMCF_RATE_EKIN)
+        build_event_list_kernel<KMCF_RATE_EKIN><<<grid, KMCF_BLOCK, 0, st>>>(N, count, start_i, nn, d_neigh_idx, d_site_layer, T_bg, freq,
+                                                                             sigma, k, d_x, d_y, d_z, d_pot, d_site_element,
+                                                                             d_site_charge, E, d_type, d_prob, th);
+    else if (rate_mode == KMCF_RATE_T_SITE)
+        build_event_list_kernel<KMCF_RATE_T_SITE><<<grid, KMCF_BLOCK, 0, st>>>(N, count, start_i, nn, d_neigh_idx, d_site_layer, T_bg, freq,
+                                                                               sigma, k, d_x, d_y, d_z, d_pot, d_site_element,
+                                                                               d_site_charge, E, d_type, d_prob, th);
+    else
+        build_event_list_kernel<KMCF_RATE_T_BG><<<grid, KMCF_BLOCK, 0, st>>>(N, count, start_i, nn, d_neigh_idx, d_site_layer, T_bg, freq,
+                                                                             sigma, k, d_x, d_y, d_z, d_pot, d_site_element,
+                                                                             d_site_charge, E, d_type, d_prob);
+}
+
+int build_grid(size_t M)
+{
+    int64_t g = ((int64_t)M + KMCF_BLOCK * 4 - 1) / (KMCF_BLOCK * 4);
+    return (int)std::min<int64_t>(g, 16384);
+}
+
+void fill_layer_energies(layer_energies &E, int num_layers, const double *h_E_gen, const double *h_E_rec, const double *h_E_Vdiff,
+                         const double *h_E_Odiff)
+{
+    for (int l = 0; l < MAX_LAYERS; ++l) {
+        E.gen[l] = l < num_layers ? h_E_gen[l] : 0.0; E.rec[l] = l < num_layers ? h_E_rec[l] : 0.0;
+        E.vdiff[l] = l < num_layers ? h_E_Vdiff[l] : 0.0; E.odiff[l] = l < num_layers ? h_E_Odiff[l] : 0.0;
+    }
+}
+
+// what the thermal entry points check on top of the step's own checks; before anything that needs a device
+int check_thermal_args(const char *what, int rate_mode, const double *d_site_temperature, double T_bg)
+{
+    KMCF_CHECK(rate_mode == KMCF_RATE_T_BG || rate_mode == KMCF_RATE_EKIN || rate_mode == KMCF_RATE_T_SITE, KMCF_ERR_ARG,
+               "%s: rate_mode %d (0 KMCF_RATE_T_BG, 1 KMCF_RATE_EKIN, 2 KMCF_RATE_T_SITE)", what, rate_mode);
+    KMCF_CHECK(rate_mode == KMCF_RATE_T_BG || d_site_temperature, KMCF_ERR_ARG, "%s: rate_mode %d needs d_site_temperature", what, rate_mode);
+    KMCF_CHECK(T_bg > 0, KMCF_ERR_ARG, "%s: T_bg %g is not > 0", what, T_bg);
+    return KMCF_OK;
+}
+
+// kmcf_execute_kmc_step (rate_mode KMCF_RATE_T_BG, no field) and kmcf_execute_kmc_step_thermal
+int execute_kmc_step_impl(const char *what, kmcf_comm *c, int N, const int *h_count, const int *h_displs, int nn,
+                          const int *d_neigh_idx, const int *d_site_layer, double T_bg, double freq,
+                          double sigma, double k, const double *d_x, const double *d_y, const double *d_z,
+                          const double *d_site_potential_charge, int *d_site_element, int *d_site_charge,
+                          int num_layers, const double *h_E_gen, const double *h_E_rec,
+                          const double *h_E_Vdiff, const double *h_E_Odiff,
+                          double (*next_random)(void *), void *rng_user, int max_events,
+                          double *event_time, int *n_events, int *h_event_log,
+                          const double *d_site_temperature, int rate_mode)
 {
     KMCF_CHECK(c && h_count && h_displs && d_neigh_idx && d_site_layer && d_x && d_y && d_z && d_site_potential_charge &&
                    d_site_element && d_site_charge && h_E_gen && h_E_rec && h_E_Vdiff && h_E_Odiff && next_random && event_time,
-               KMCF_ERR_ARG, "kmcf_execute_kmc_step: null argument");
-    KMCF_CHECK(c->device >= 0, KMCF_ERR_STATE, "kmcf_execute_kmc_step: host-only communicator");
-    KMCF_CHECK(num_layers > 0 && num_layers <= MAX_LAYERS && nn > 0 && freq > 0, KMCF_ERR_ARG, "kmcf_execute_kmc_step: bad sizes");
+               KMCF_ERR_ARG, "%s: null argument", what);
+    KMCF_CHECK(c->device >= 0, KMCF_ERR_STATE, "%s: host-only communicator", what);
+    KMCF_CHECK(num_layers > 0 && num_layers <= MAX_LAYERS && nn > 0 && freq > 0, KMCF_ERR_ARG, "%s: bad sizes", what);
+    const bool thermal = rate_mode != KMCF_RATE_T_BG;
     KMCF_TRY(kmcf_enter(c));
     hipStream_t st = c->stream;
     // Multi-rank groups: the reference partitions the event list and pays a zero-out pass, an MPI_Allgather, an
@@ -1030,10 +1116,7 @@ extern "C" int kmcf_execute_kmc_step(kmcf_comm *c, int N, const int *h_count, co
     const int nb = (int)((M + EV_TILE - 1) / EV_TILE);
     const int ng = std::max((nb + EV_GROUP - 1) / EV_GROUP, 1);
     layer_energies E;
-    for (int l = 0; l < MAX_LAYERS; ++l) {
-        E.gen[l] = l < num_layers ? h_E_gen[l] : 0.0; E.rec[l] = l < num_layers ? h_E_rec[l] : 0.0;
-        E.vdiff[l] = l < num_layers ? h_E_Vdiff[l] : 0.0; E.odiff[l] = l < num_layers ? h_E_Odiff[l] : 0.0;
-    }
+    fill_layer_energies(E, num_layers, h_E_gen, h_E_rec, h_E_Vdiff, h_E_Odiff);
     const int n_aff = 4 * nn + 4;
     // workspace kept on the communicator between steps: the reference allocates and frees its event arrays on
     // every call (:352-361); at 40 nm that is 0.8 GB per step
@@ -1051,11 +1134,12 @@ extern "C" int kmcf_execute_kmc_step(kmcf_comm *c, int N, const int *h_count, co
             hipMalloc(reinterpret_cast<void **>(&w->d_aff), (size_t)n_aff * sizeof(int)) != hipSuccess ||
             hipMalloc(reinterpret_cast<void **>(&w->d_asym), sizeof(int)) != hipSuccess) {
             kmcf_event_cache_free(c);
-            kmcf_set_error("kmcf_execute_kmc_step: out of device memory for %zu event slots", M);
+            kmcf_set_error("%s: out of device memory for %zu event slots", what, M);
             return KMCF_ERR_HIP;
         }
     }
     kmcf_event_cache *w = c->ev_cache;
+    if (thermal && !w->d_tbad) KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&w->d_tbad), (size_t)P * sizeof(int)));
     if (replicate) {
         if (w->full_key != d_neigh_idx || w->full_N != N) {     // the lists are built once per run (kmc_main.cpp:199)
             if (w->d_neigh_full) { hipFree(w->d_neigh_full); w->d_neigh_full = nullptr; }
@@ -1064,7 +1148,7 @@ extern "C" int kmcf_execute_kmc_step(kmcf_comm *c, int N, const int *h_count, co
             std::vector<int> cn(R), dn(R);
             for (int q = 0; q < R; ++q) {
                 KMCF_CHECK((int64_t)h_count[q] * nn < INT32_MAX && (int64_t)h_displs[q] * nn < INT32_MAX, KMCF_ERR_ARG,
-                           "kmcf_execute_kmc_step: neighbour list too large for the int32 gather");
+                           "%s: neighbour list too large for the int32 gather", what);
                 cn[q] = h_count[q] * nn; dn[q] = h_displs[q] * nn;
             }
             if (h_count[c->rank] > 0)
@@ -1086,19 +1170,32 @@ extern "C" int kmcf_execute_kmc_step(kmcf_comm *c, int N, const int *h_count, co
     int rc = KMCF_OK;
     auto fail = [&](int code) { rc = code; };
     bool fast = false;   // neighbour-list zero-out + one host sync per event
+    // Thermal modes: the build kernel leaves the first site with an unusable temperature in d_tbad[rank]; the word comes
+    // back with the step's first host round trip, before any event executes.  A partitioned group agrees on it first
+    // (every rank saw only its own slots, and all must leave the step together).
+    std::vector<int> h_bad(P, EV_NO_BAD_SITE);
+    if (thermal) KMCF_HIP(hipMemsetAsync(w->d_tbad, 0x7f, (size_t)P * sizeof(int), st));
+    bool bad_read = false;
+    auto read_bad = [&]() {       // enqueue the read of the verdict (the caller synchronises)
+        if (!thermal || bad_read) return true;
+        bad_read = true;
+        if (P > 1 && kmcf_comm_allgatherv_int(c, w->d_tbad, ones.data(), iota.data()) != KMCF_OK) { fail(KMCF_ERR_COMM); return false; }
+        if (hipMemcpyAsync(h_bad.data(), w->d_tbad, (size_t)P * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess) { fail(KMCF_ERR_HIP); return false; }
+        return true;
+    };
     if (M > 0) {
-        int64_t g = ((int64_t)M + KMCF_BLOCK * 4 - 1) / (KMCF_BLOCK * 4);
-        if (g > 16384) g = 16384;
-        build_event_list_kernel<<<(int)g, KMCF_BLOCK, 0, st>>>(N, count, start_i, nn, d_neigh_idx, d_site_layer, T_bg, freq, sigma, k,
-                                                               d_x, d_y, d_z, d_site_potential_charge, d_site_element,
-                                                               d_site_charge, E, d_type, d_prob);
+        const int g = build_grid(M);
+        launch_build_event_list(rate_mode, g, st, N, count, start_i, nn, d_neigh_idx, d_site_layer, T_bg, freq, sigma, k, d_x, d_y, d_z,
+                                d_site_potential_charge, d_site_element, d_site_charge, E, d_type, d_prob, d_site_temperature,
+                                thermal ? w->d_tbad + rank : nullptr);
         zero_and_sum_kernel<<<nb, KMCF_BLOCK, 0, st>>>(M, start_i, nn, d_neigh_idx, d_type, d_prob, -1, -1, d_tsum);
         if (P == 1 && count == N && !kmcf_opt_set(c, KNOB_EVENTS_FULLSCAN)) {
             // the neighbour lists are built once per run (kmc_main.cpp:199): the verdict on their symmetry is
             // kept with the workspace, keyed by the list's address and shape
             if (w->sym_key != d_neigh_idx || w->sym_N != N) {
-                check_symmetry_kernel<<<(int)g, KMCF_BLOCK, 0, st>>>(N, nn, d_neigh_idx, d_asym);
+                check_symmetry_kernel<<<g, KMCF_BLOCK, 0, st>>>(N, nn, d_neigh_idx, d_asym);
                 int asym = 1;
+                read_bad();
                 if (hipMemcpyAsync(&asym, d_asym, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
                     hipStreamSynchronize(st) != hipSuccess) fail(KMCF_ERR_HIP);
                 w->sym_key = d_neigh_idx;
@@ -1106,6 +1203,17 @@ extern "C" int kmcf_execute_kmc_step(kmcf_comm *c, int N, const int *h_count, co
                 w->symmetric = (asym == 0);
             }
             fast = w->symmetric;
+        }
+    }
+    if (thermal) {
+        // (whatever this rank's rc: a partitioned group's ranks all enter the all-gather of the word)
+        if (!bad_read && read_bad() && hipStreamSynchronize(st) != hipSuccess) fail(KMCF_ERR_HIP);
+        const int bad_site = *std::min_element(h_bad.begin(), h_bad.end());
+        if (rc == KMCF_OK && bad_site != EV_NO_BAD_SITE) {
+            kmcf_set_error("%s: the temperature of site %d is not finite or not > 0 (it owns an event)", what, bad_site);
+            *event_time = 0.0;
+            if (n_events) *n_events = 0;
+            return KMCF_ERR_ARG;
         }
     }
     double t = 0.0;
@@ -1245,7 +1353,7 @@ extern "C" int kmcf_execute_kmc_step(kmcf_comm *c, int N, const int *h_count, co
             if (own_rng) for (int q = 0; q < 2 * n; ++q) next_random(rng_user);           // consume what was used
             nev += n;
             if (rc == KMCF_OK && (hs.done == 2 || n == 0)) {
-                kmcf_set_error("kmcf_execute_kmc_step: no event could be selected (total rate %g)", n < nbatch ? h_tot[2 * n] : 0.0);
+                kmcf_set_error("%s: no event could be selected (total rate %g)", what, n < nbatch ? h_tot[2 * n] : 0.0);
                 fail(KMCF_ERR_STATE);
             }
             if (own_rng && n == nbatch && hs.done == 0 && B < BMAX) B *= 2;
@@ -1284,7 +1392,7 @@ extern "C" int kmcf_execute_kmc_step(kmcf_comm *c, int N, const int *h_count, co
             }
         }
         if (ij[0] < 0 || ij[0] >= N || ij[1] < 0 || ij[1] >= N) {
-            kmcf_set_error("kmcf_execute_kmc_step: no event could be selected (total rate %g)", total);
+            kmcf_set_error("%s: no event could be selected (total rate %g)", what, total);
             fail(KMCF_ERR_STATE);
             break;
         }
@@ -1293,8 +1401,96 @@ extern "C" int kmcf_execute_kmc_step(kmcf_comm *c, int N, const int *h_count, co
         ++nev;
     }
     if (rc == KMCF_OK && hipStreamSynchronize(st) != hipSuccess) rc = KMCF_ERR_HIP;
-    if (rc == KMCF_ERR_HIP) kmcf_set_error("kmcf_execute_kmc_step: HIP failure: %s", hipGetErrorString(hipGetLastError()));
+    if (rc == KMCF_ERR_HIP) kmcf_set_error("%s: HIP failure: %s", what, hipGetErrorString(hipGetLastError()));
     *event_time = t;
     if (n_events) *n_events = nev;
     return rc;
+}
+
+}  // namespace
+
+extern "C" int kmcf_execute_kmc_step(kmcf_comm *c, int N, const int *h_count, const int *h_displs, int nn,
+                                     const int *d_neigh_idx, const int *d_site_layer, double T_bg, double freq,
+                                     double sigma, double k, const double *d_x, const double *d_y, const double *d_z,
+                                     const double *d_site_potential_charge, int *d_site_element, int *d_site_charge,
+                                     int num_layers, const double *h_E_gen, const double *h_E_rec,
+                                     const double *h_E_Vdiff, const double *h_E_Odiff,
+                                     double (*next_random)(void *), void *rng_user, int max_events,
+                                     double *event_time, int *n_events, int *h_event_log)
+{
+    return execute_kmc_step_impl("kmcf_execute_kmc_step", c, N, h_count, h_displs, nn, d_neigh_idx, d_site_layer, T_bg, freq, sigma, k,
+                                 d_x, d_y, d_z, d_site_potential_charge, d_site_element, d_site_charge, num_layers, h_E_gen, h_E_rec,
+                                 h_E_Vdiff, h_E_Odiff, next_random, rng_user, max_events, event_time, n_events, h_event_log,
+                                 nullptr, KMCF_RATE_T_BG);
+}
+
+extern "C" int kmcf_execute_kmc_step_thermal(kmcf_comm *c, int N, const int *h_count, const int *h_displs, int nn,
+                                             const int *d_neigh_idx, const int *d_site_layer, double T_bg, double freq,
+                                             double sigma, double k, const double *d_x, const double *d_y, const double *d_z,
+                                             const double *d_site_potential_charge, int *d_site_element, int *d_site_charge,
+                                             int num_layers, const double *h_E_gen, const double *h_E_rec,
+                                             const double *h_E_Vdiff, const double *h_E_Odiff,
+                                             double (*next_random)(void *), void *rng_user, int max_events,
+                                             double *event_time, int *n_events, int *h_event_log,
+                                             const double *d_site_temperature, int rate_mode)
+{
+    KMCF_TRY(check_thermal_args("kmcf_execute_kmc_step_thermal", rate_mode, d_site_temperature, T_bg));
+    return execute_kmc_step_impl("kmcf_execute_kmc_step_thermal", c, N, h_count, h_displs, nn, d_neigh_idx, d_site_layer, T_bg, freq,
+                                 sigma, k, d_x, d_y, d_z, d_site_potential_charge, d_site_element, d_site_charge, num_layers, h_E_gen,
+                                 h_E_rec, h_E_Vdiff, h_E_Odiff, next_random, rng_user, max_events, event_time, n_events, h_event_log,
+                                 d_site_temperature, rate_mode);
+}
+
+extern "C" int kmcf_event_rates(kmcf_comm *c, int N, const int *h_count, const int *h_displs, int nn,
+                                const int *d_neigh_idx, const int *d_site_layer, double T_bg, double freq,
+                                double sigma, double k, const double *d_x, const double *d_y, const double *d_z,
+                                const double *d_site_potential_charge, const int *d_site_element,
+                                const int *d_site_charge, int num_layers, const double *h_E_gen,
+                                const double *h_E_rec, const double *h_E_Vdiff, const double *h_E_Odiff,
+                                const double *d_site_temperature, int rate_mode,
+                                unsigned char *h_type, double *h_prob)
+{
+    const char *what = "kmcf_event_rates";
+    KMCF_TRY(check_thermal_args(what, rate_mode, d_site_temperature, T_bg));
+    KMCF_CHECK(c && h_count && h_displs && d_neigh_idx && d_site_layer && d_x && d_y && d_z && d_site_potential_charge &&
+                   d_site_element && d_site_charge && h_E_gen && h_E_rec && h_E_Vdiff && h_E_Odiff,
+               KMCF_ERR_ARG, "%s: null argument", what);
+    KMCF_CHECK(c->device >= 0, KMCF_ERR_STATE, "%s: host-only communicator", what);
+    KMCF_CHECK(num_layers > 0 && num_layers <= MAX_LAYERS && nn > 0 && freq > 0, KMCF_ERR_ARG, "%s: bad sizes", what);
+    KMCF_TRY(kmcf_enter(c));
+    hipStream_t st = c->stream;
+    // this rank's own rows, whatever the group's event step does with them (replicated or partitioned): the caller's
+    // d_neigh_idx holds exactly these count * nn slots
+    const int count = h_count[c->rank], start_i = h_displs[c->rank];
+    const size_t M = (size_t)count * nn;
+    if (M == 0) return KMCF_OK;
+    layer_energies E;
+    fill_layer_energies(E, num_layers, h_E_gen, h_E_rec, h_E_Vdiff, h_E_Odiff);
+    const bool thermal = rate_mode != KMCF_RATE_T_BG;
+    unsigned char *d_type = nullptr;
+    double *d_prob = nullptr;
+    int *d_bad = nullptr;
+    int bad_site = EV_NO_BAD_SITE;
+    bool ok = hipMalloc(reinterpret_cast<void **>(&d_type), M) == hipSuccess &&
+              hipMalloc(reinterpret_cast<void **>(&d_prob), M * sizeof(double)) == hipSuccess &&
+              hipMalloc(reinterpret_cast<void **>(&d_bad), sizeof(int)) == hipSuccess &&
+              hipMemsetAsync(d_bad, 0x7f, sizeof(int), st) == hipSuccess;
+    if (ok) {
+        launch_build_event_list(rate_mode, build_grid(M), st, N, count, start_i, nn, d_neigh_idx, d_site_layer, T_bg, freq, sigma, k,
+                                d_x, d_y, d_z, d_site_potential_charge, d_site_element, d_site_charge, E, d_type, d_prob,
+                                d_site_temperature, thermal ? d_bad : nullptr);
+        ok = hipGetLastError() == hipSuccess &&
+             hipMemcpyAsync(&bad_site, d_bad, sizeof(int), hipMemcpyDeviceToHost, st) == hipSuccess &&
+             (!h_type || hipMemcpyAsync(h_type, d_type, M, hipMemcpyDeviceToHost, st) == hipSuccess) &&
+             (!h_prob || hipMemcpyAsync(h_prob, d_prob, M * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess) &&
+             hipStreamSynchronize(st) == hipSuccess;
+    }
+    if (!ok) kmcf_set_error("%s: HIP failure: %s", what, hipGetErrorString(hipGetLastError()));
+    if (d_type) hipFree(d_type);
+    if (d_prob) hipFree(d_prob);
+    if (d_bad) hipFree(d_bad);
+    if (!ok) return KMCF_ERR_HIP;
+    KMCF_CHECK(bad_site == EV_NO_BAD_SITE, KMCF_ERR_ARG, "%s: the temperature of site %d is not finite or not > 0 (it owns an event)",
+               what, bad_site);
+    return KMCF_OK;
 }

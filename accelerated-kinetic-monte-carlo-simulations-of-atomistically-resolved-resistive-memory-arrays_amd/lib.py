@@ -148,6 +148,12 @@ SIGNATURES = {
     "kmcf_execute_kmc_step": (C.c_int, [_P, C.c_int, _IP, _IP, C.c_int, _P, _P, C.c_double, C.c_double, C.c_double,
                                         C.c_double, _P, _P, _P, _P, _P, _P, C.c_int, _DP, _DP, _DP, _DP, _P, _P,
                                         C.c_int, _DP, _IP, _IP]),
+    "kmcf_execute_kmc_step_thermal": (C.c_int, [_P, C.c_int, _IP, _IP, C.c_int, _P, _P, C.c_double, C.c_double,
+                                                C.c_double, C.c_double, _P, _P, _P, _P, _P, _P, C.c_int, _DP, _DP, _DP,
+                                                _DP, _P, _P, C.c_int, _DP, _IP, _IP, _P, C.c_int]),
+    "kmcf_event_rates": (C.c_int, [_P, C.c_int, _IP, _IP, C.c_int, _P, _P, C.c_double, C.c_double, C.c_double,
+                                   C.c_double, _P, _P, _P, _P, _P, _P, C.c_int, _DP, _DP, _DP, _DP, _P, C.c_int,
+                                   C.POINTER(C.c_ubyte), _DP]),
     "kmcf_neighbor_list":(C.c_int, [_P, _P, _P, _P, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _P]),
 }
 

@@ -497,19 +497,35 @@ def site_layers(site_x, layers):
     return lay
 
 
+RATE_MODES = {"bg": 0, "ekin": 1, "site": 2}     # KMCF_RATE_T_BG, KMCF_RATE_EKIN, KMCF_RATE_T_SITE
+
+
+def _rate_mode(rate_mode):
+    if isinstance(rate_mode, str):
+        if rate_mode not in RATE_MODES:
+            raise ValueError("rate_mode %r: one of %s or 0 / 1 / 2" % (rate_mode, " | ".join(RATE_MODES)))
+        return RATE_MODES[rate_mode]
+    return int(rate_mode)
+
+
+def _layer_energies(layers):
+    return [_da([l[key] for l in layers]) for key in ("E_gen_0", "E_rec_1", "E_diff_2", "E_diff_3")]
+
+
 def execute_kmc_step_mpi(kmc_comm, N, count, displs, nn, neigh_idx, site_layer, T_bg, freq, sigma, k, posx, posy, posz,
                          site_potential_charge, site_element, site_charge, rng, layers, max_events=1 << 20,
-                         return_log=False):
+                         return_log=False, site_temperature=None, rate_mode="bg"):
     """execute_kmc_step_mpi (gpu_solvers.h:250; src/kmc_events.cu:333-563).  T_bg, freq, sigma, k are host
     scalars here.  layers: list of dicts with E_gen_0, E_rec_1, E_diff_2, E_diff_3 (copytoConstMemory).
-    Returns the event time (and, with return_log, the number of events and their (i, j, type) rows)."""
+    Returns the event time (and, with return_log, the number of events and their (i, j, type) rows).
+    site_temperature (N doubles on the device, e.g. gpubuf.site_temperature after update_temperature_local_gpu) with
+    rate_mode "ekin" | "site" (or 1 | 2): thermally coupled rates, kmcf_execute_kmc_step_thermal.  The defaults
+    ("bg", no field) are kmcf_execute_kmc_step."""
     lib = _L.load()
+    mode = _rate_mode(rate_mode)
     cnt, cntp = _ia(count)
     dsp, dspp = _ia(displs)
-    eg, egp = _da([l["E_gen_0"] for l in layers])
-    er, erp = _da([l["E_rec_1"] for l in layers])
-    ev, evp = _da([l["E_diff_2"] for l in layers])
-    eo, eop = _da([l["E_diff_3"] for l in layers])
+    (eg, egp), (er, erp), (ev, evp), (eo, eop) = _layer_energies(layers)
     t = C.c_double()
     nev = C.c_int()
     cap = min(int(max_events), 1 << 16) if return_log else 0
@@ -521,16 +537,39 @@ def execute_kmc_step_mpi(kmc_comm, N, count, displs, nn, neigh_idx, site_layer, 
         fn, user = C.cast(keep, C.c_void_p), None
     else:
         fn, user = C.cast(lib.kmcf_rng_next, C.c_void_p), rng.handle
-    _L.check(lib.kmcf_execute_kmc_step(kmc_comm.handle, int(N), cntp, dspp, int(nn), _ptr(neigh_idx), _ptr(site_layer),
-                                       float(T_bg), float(freq), float(sigma), float(k), _ptr(posx), _ptr(posy),
-                                       _ptr(posz), _ptr(site_potential_charge), _ptr(site_element), _ptr(site_charge),
-                                       len(layers), egp, erp, evp, eop, fn, user,
-                                       cap if return_log else int(max_events), C.byref(t), C.byref(nev),
-                                       log.ctypes.data_as(C.POINTER(C.c_int)) if return_log else None),
-             "kmcf_execute_kmc_step")
+    args = (kmc_comm.handle, int(N), cntp, dspp, int(nn), _ptr(neigh_idx), _ptr(site_layer),
+            float(T_bg), float(freq), float(sigma), float(k), _ptr(posx), _ptr(posy),
+            _ptr(posz), _ptr(site_potential_charge), _ptr(site_element), _ptr(site_charge),
+            len(layers), egp, erp, evp, eop, fn, user,
+            cap if return_log else int(max_events), C.byref(t), C.byref(nev),
+            log.ctypes.data_as(C.POINTER(C.c_int)) if return_log else None)
+    if mode == 0 and site_temperature is None:
+        _L.check(lib.kmcf_execute_kmc_step(*args), "kmcf_execute_kmc_step")
+    else:
+        _L.check(lib.kmcf_execute_kmc_step_thermal(*args, _ptr(site_temperature), mode), "kmcf_execute_kmc_step_thermal")
     if return_log:
         return t.value, nev.value, log[:3 * nev.value].reshape(-1, 3).copy()
     return t.value
+
+
+def event_rates(kmc_comm, N, count, displs, nn, neigh_idx, site_layer, T_bg, freq, sigma, k, posx, posy, posz,
+                site_potential_charge, site_element, site_charge, layers, site_temperature=None, rate_mode="bg"):
+    """kmcf_event_rates: the event list the step would build for this rank's rows, nothing executed.  Returns (type, prob): uint8 EVENTTYPE codes and float64 rates,
+    both of shape (count[rank], nn)."""
+    lib = _L.load()
+    cnt, cntp = _ia(count)
+    dsp, dspp = _ia(displs)
+    (eg, egp), (er, erp), (ev, evp), (eo, eop) = _layer_energies(layers)
+    rows = int(cnt[kmc_comm.rank_events])
+    typ = np.zeros((rows, int(nn)), np.uint8)
+    prob = np.zeros((rows, int(nn)), np.float64)
+    _L.check(lib.kmcf_event_rates(kmc_comm.handle, int(N), cntp, dspp, int(nn), _ptr(neigh_idx), _ptr(site_layer),
+                                  float(T_bg), float(freq), float(sigma), float(k), _ptr(posx), _ptr(posy), _ptr(posz),
+                                  _ptr(site_potential_charge), _ptr(site_element), _ptr(site_charge), len(layers),
+                                  egp, erp, evp, eop, _ptr(site_temperature), _rate_mode(rate_mode),
+                                  typ.ctypes.data_as(C.POINTER(C.c_ubyte)), prob.ctypes.data_as(C.POINTER(C.c_double))),
+             "kmcf_event_rates")
+    return typ, prob
 
 
 # K-state inspection helpers used by the parity tests --------------------------------

@@ -3,6 +3,8 @@
 //
 //     update_charge_gpu -> background_potential_gpu_sparse -> poisson_gridless_gpu -> sum_and_gather_potential
 //     [-> update_power_gpu_sparse_dist with --current] -> execute_kmc_step_mpi
+//     [--current --thermal: the power with heating -> kmcf_update_temperature_local -> the event rates read the site
+//      temperatures, kmcf_execute_kmc_step_thermal in KMCF_RATE_T_SITE]
 //
 // on the reference's shipped 5 nm device (tests/golden/device_5nm.bin: site count, coordinates, elements after
 // makeSubstoichiometric -- data extracted from structures/5nm_device/, see tests/golden/make_golden_5nm.py) with
@@ -13,7 +15,7 @@
 //
 //   hipcc -O2 -std=c++17 --offload-arch=gfx950 -Iinclude examples/kmc_loop.cpp -L<package dir> -lkmcfield \
 //         -Wl,-rpath,<package dir> -o examples/kmc_loop
-//   examples/kmc_loop tests/golden/device_5nm.bin [--current]
+//   examples/kmc_loop tests/golden/device_5nm.bin [--current [--thermal]]
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -45,8 +47,11 @@ static T *to_device(const std::vector<T> &h)
 
 int main(int argc, char **argv)
 {
-    if (argc < 2) { std::fprintf(stderr, "usage: %s device_5nm.bin [--current]\n", argv[0]); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: %s device_5nm.bin [--current [--thermal]]\n", argv[0]); return 2; }
     const bool solve_current = argc > 2 && std::strcmp(argv[2], "--current") == 0;
+    bool thermal = false;
+    for (int q = 2; q < argc; ++q) thermal |= std::strcmp(argv[q], "--thermal") == 0;
+    if (thermal && !solve_current) { std::fprintf(stderr, "--thermal needs --current (the heat solve's source)\n"); return 2; }
     // ---- fixture: int32 N | N x (x, y, z) f64 | N x int32 ELEMENT --------------------------------------------
     FILE *f = std::fopen(argv[1], "rb");
     if (!f) { std::perror(argv[1]); return 2; }
@@ -83,6 +88,7 @@ int main(int argc, char **argv)
     int *d_element = to_device(element), *d_metals = to_device(metals), *d_layer = to_device(layer);
     int *d_charge = nullptr, *d_neigh = nullptr;
     double *d_pot_boundary = nullptr, *d_pot_charge = nullptr, *d_power = nullptr, *d_cb = nullptr, *d_avp = nullptr;
+    double *d_temperature = nullptr;
     HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_charge), (size_t)N * sizeof(int)));
     HIP_OK(hipMemset(d_charge, 0, (size_t)N * sizeof(int)));
     HIP_OK(hipMalloc(reinterpret_cast<void **>(&d_neigh), (size_t)N * nn * sizeof(int)));
@@ -121,7 +127,14 @@ int main(int argc, char **argv)
         cp.tol = 1.60217663e-19 * 0.01; cp.m_e = 0.85 * 9.11e-31; cp.V0 = 1.6; cp.alpha_disp = 1.0;
         cp.contact_x_lo = -4.2; cp.contact_x_hi = 52.65;
         cp.cg_tolerance = 1e-15 * n_atom; cp.cg_max_iterations = 2000;   // the reference's commented-out setting (:1454)
-        cp.solve_heating = 0;
+        cp.solve_heating = thermal ? 1 : 0;
+    }
+    kmcf_heat_params_t hp;                                      // "Local thermal model", structures/5nm_device/parameters.txt
+    if (thermal) {
+        hp.background_temp = T_bg; hp.k_th_metal = 29.0; hp.k_th_vacancies = 5.0; hp.k_th_non_vacancy = 0.5; hp.L_char = 3.5e-10;
+        hp.c_p = 1.92; hp.A = 51.15e-10 * 51.15e-10; hp.t_ox = 52.6838e-10; hp.delta_t = 1e-13;
+        hp.cg_tolerance = 1e-12; hp.cg_max_iterations = 20000;
+        d_temperature = to_device(std::vector<double>((size_t)N, T_bg));
     }
 
     // ---- the KMC loop (src/kmc_main.cpp:328-527) ------------------------------------------------------------------
@@ -142,6 +155,19 @@ int main(int argc, char **argv)
         KMCF(kmcf_sum_and_gather_potential(K, d_pot_boundary, d_pot_charge, N, NL, nullptr, nullptr));
         double event_time = 0.0;
         int n_events = 0;
+        if (thermal) {
+            // steady state of the dissipated power (step_time > 1e3 delta_t), then rates at the sites' own temperatures
+            double T_global = 0.0;
+            int steady = 0;
+            kmcf_solve_stats_t hs;
+            KMCF(kmcf_update_temperature_local(K, d_element, d_charge, d_metals, (int)metals.size(), d_power, d_temperature, N, NL, NL,
+                                               1e-6, &hp, &T_global, &steady, &hs));
+            std::printf("iteration (heat) = %d, relative residual = %g\n", hs.iterations + 1, hs.relres);
+            KMCF(kmcf_execute_kmc_step_thermal(comm, N, counts_N, displs_N, nn, d_neigh, d_layer, T_bg, freq, sigma, k_coulomb, d_x,
+                                               d_y, d_z, d_pot_charge, d_element, d_charge, num_layers, E_gen, E_rec, E_vd, E_od,
+                                               kmcf_rng_next, rng, 1 << 20, &event_time, &n_events, nullptr, d_temperature,
+                                               KMCF_RATE_T_SITE));
+        } else
         KMCF(kmcf_execute_kmc_step(comm, N, counts_N, displs_N, nn, d_neigh, d_layer, T_bg, freq, sigma, k_coulomb, d_x, d_y, d_z,
                                    d_pot_charge, d_element, d_charge, num_layers, E_gen, E_rec, E_vd, E_od, kmcf_rng_next, rng,
                                    1 << 20, &event_time, &n_events, nullptr));

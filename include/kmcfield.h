@@ -395,6 +395,44 @@ int kmcf_execute_kmc_step(kmcf_comm *c, int N, const int *h_count, const int *h_
                           double (*next_random)(void *), void *rng_user, int max_events,
                           double *event_time, int *n_events, int *h_event_log);
 
+/* Rate modes of the thermal step.  EA: the activation energy kmcf_execute_kmc_step forms; s: the site whose
+ * temperature counts -- j for generation, i for recombination, vacancy diffusion and ion diffusion. */
+#define KMCF_RATE_T_BG   0   /* P = freq / (exp(EA / (kB T_bg)) + 1e-200): kmcf_execute_kmc_step's rates          */
+#define KMCF_RATE_EKIN   1   /* the reference's commented term: EA -= kB (T[s] - T_bg), then as KMCF_RATE_T_BG    */
+#define KMCF_RATE_T_SITE 2   /* Boltzmann factor at the site's own temperature: exp(EA / (kB T[s]))              */
+
+/* kmcf_execute_kmc_step with event rates that read the site temperatures (the field
+ * kmcf_update_temperature_local leaves on every rank): d_site_temperature, N doubles, whole device (a
+ * partitioned group's ranks read it at global site ids, like the potential).  A field equal to T_bg
+ * everywhere gives, in both thermal modes, the bits of KMCF_RATE_T_BG.  Rates are fixed for the step.
+ * rate_mode KMCF_RATE_T_BG: d_site_temperature may be NULL and is never read; the call is kmcf_execute_kmc_step.
+ * KMCF_ERR_ARG (checked before anything needs a device): rate_mode outside 0..2, NULL field in mode 1 or 2,
+ * T_bg <= 0.  KMCF_ERR_ARG before any event executes (site arrays and generator untouched, *n_events 0):
+ * a temperature that is not finite or not > 0 at the site s of a non-null event slot; kmcf_last_error
+ * names the first such site. */
+int kmcf_execute_kmc_step_thermal(kmcf_comm *c, int N, const int *h_count, const int *h_displs, int nn,
+                                  const int *d_neigh_idx, const int *d_site_layer, double T_bg, double freq,
+                                  double sigma, double k, const double *d_x, const double *d_y, const double *d_z,
+                                  const double *d_site_potential_charge, int *d_site_element, int *d_site_charge,
+                                  int num_layers, const double *h_E_gen, const double *h_E_rec,
+                                  const double *h_E_Vdiff, const double *h_E_Odiff,
+                                  double (*next_random)(void *), void *rng_user, int max_events,
+                                  double *event_time, int *n_events, int *h_event_log,
+                                  const double *d_site_temperature, int rate_mode);
+
+/* Inspection, like kmcf_kstate_pattern: builds the event list of this rank's rows [displs[rank], +count[rank])
+ * in the given rate mode and copies it out; executes nothing, draws nothing, keeps nothing.
+ * h_type: count*nn bytes (EVENTTYPE codes), h_prob: count*nn doubles; either may be NULL.
+ * Errors as kmcf_execute_kmc_step_thermal. */
+int kmcf_event_rates(kmcf_comm *c, int N, const int *h_count, const int *h_displs, int nn,
+                     const int *d_neigh_idx, const int *d_site_layer, double T_bg, double freq,
+                     double sigma, double k, const double *d_x, const double *d_y, const double *d_z,
+                     const double *d_site_potential_charge, const int *d_site_element,
+                     const int *d_site_charge, int num_layers, const double *h_E_gen,
+                     const double *h_E_rec, const double *h_E_Vdiff, const double *h_E_Odiff,
+                     const double *d_site_temperature, int rate_mode,
+                     unsigned char *h_type, double *h_prob);
+
 /* ---------------------------------------------------------------------- */
 /* T path: current solve (Kirchhoff matrix with two virtual nodes + WKB       */
 /* tunnelling sub-block), SURVEY 8 rows a14 / f3.  PARITY UNPINNED: no         */

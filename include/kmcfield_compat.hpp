@@ -303,6 +303,37 @@ double execute_kmc_step_mpi(MPI_Comm comm, const int N, const int *count, const 
     return event_time;
 }
 
+// The same call with thermally coupled event rates: the reference's signature, site_temperature passed through
+// (kmcf_execute_kmc_step_thermal), plus the rate mode -- KMCF_RATE_EKIN is the reference's commented-out Ekin term
+// (src/kmc_events.cu:81-220), KMCF_RATE_T_SITE the Boltzmann factor at the site's own temperature.  Not a reference
+// entry point: a host program changes this one call.
+namespace kmcf_compat {
+inline double execute_kmc_step_mpi_thermal(MPI_Comm comm, const int N, const int *count, const int *displs, const int nn,
+                                           const int *neigh_idx, const int *site_layer, const double *lattice, const int pbc,
+                                           const double *T_bg, const double *freq, const double *sigma, const double *k,
+                                           const double *posx, const double *posy, const double *posz,
+                                           const double *site_potential_charge, const double *site_temperature,
+                                           ELEMENT *site_element, int *site_charge, RandomNumberGenerator &rng, int rate_mode)
+{
+    (void)lattice; (void)pbc;
+    double h[4];
+    const double *d[4] = {T_bg, freq, sigma, k};
+    for (int i = 0; i < 4; ++i)
+        if (hipMemcpy(&h[i], d[i], sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) std::exit(1);
+    double event_time = 0.0;
+    int n_events = 0;
+    check(kmcf_execute_kmc_step_thermal(comm_of(comm), N, count, displs, nn, neigh_idx, site_layer, h[0], h[1], h[2], h[3], posx,
+                                        posy, posz, site_potential_charge, reinterpret_cast<int *>(site_element), site_charge,
+                                        (int)layer_E(0).size(), layer_E(0).data(), layer_E(1).data(), layer_E(2).data(),
+                                        layer_E(3).data(), next_random_cb, &rng, 1 << 30, &event_time, &n_events, nullptr,
+                                        site_temperature, rate_mode), "kmcf_execute_kmc_step_thermal");
+    int rank = 0;
+    MPI_Comm_rank(comm, &rank);
+    if (rank == 0) std::printf("Number of KMC events: %d\nEvent time: %g\n", n_events, event_time);
+    return event_time;
+}
+}  // namespace kmcf_compat
+
 // src/heat_solver_gpu.cu:53-70
 void update_temperatureglobal_gpu(const double *site_power, double *T_bg, const int N, const double a_coeff,
                                          const double b_coeff, const double number_steps, const double C_thermal,

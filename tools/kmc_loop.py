@@ -3,7 +3,12 @@
 boundary (K) solve, pairwise term, sum/gather, KMC events -- with the per-module wall times the reference
 prints into output<size>_<rank>.txt ("Z - calculation time - ...").
 
-    python tools/kmc_loop.py [--workload 5nm|40nm] [--steps 6] [--T 300]
+    python tools/kmc_loop.py [--workload 5nm|40nm|conducting] [--steps 6] [--T 300] [--current] [--rate-mode bg|ekin|site]
+
+--current adds the electro-thermal stages after the potential and before the events: conduction-band edge, current
+solve with heating (site_power), local heat solve (site_temperature); --rate-mode ekin | site lets the event rates read
+that field (kmcf_execute_kmc_step_thermal).  Workload `conducting`: the 4 x 4 crossbar with a vacancy filament of
+tests/test_gpu_conducting.py, whose current is a property of the device.
 """
 import argparse
 import os
@@ -20,14 +25,24 @@ import kmcfield_amd as km  # noqa: E402
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", default="5nm")
+    ap.add_argument("--workload", default="5nm", choices=["5nm", "40nm", "conducting"])
     ap.add_argument("--steps", type=int, default=6)
     ap.add_argument("--T", type=float, default=300.0)
     ap.add_argument("--max-events", type=int, default=100000)
     ap.add_argument("--event-stats", action="store_true", help="locality of the selected rows (supertiles of 128 rows)")
+    ap.add_argument("--current", action="store_true", help="CB edge, current solve with heating and local heat solve in every step")
+    ap.add_argument("--rate-mode", default="bg", choices=["bg", "ekin", "site"],
+                    help="event rates: T_bg only | the reference's Ekin term | Boltzmann factor at the site's temperature")
     a = ap.parse_args()
+    if a.rate_mode != "bg" and not a.current:
+        ap.error("--rate-mode %s needs --current (the heat solve provides the site temperatures)" % a.rate_mode)
     S = km.solvers
-    d = km.structure.load_device_5nm("init") if a.workload == "5nm" else km.structure.synth_crossbar_40nm()
+    if a.workload == "5nm":
+        d = km.structure.load_device_5nm("init")
+    elif a.workload == "conducting":
+        d = km.structure.synth_crossbar_40nm(tiles=4, filament=4.0)
+    else:
+        d = km.structure.synth_crossbar_40nm()
     N, NL = d["N"], d["N_contact"]
     t0 = time.perf_counter()
     comm = S.KMC_comm(N - 2 * NL, N + 1, N, N)
@@ -43,6 +58,15 @@ def main():
         xs = np.clip(xs, layers[0]["start_x"], layers[-1]["end_x"])
     lay = torch.as_tensor(S.site_layers(xs, layers), device="cuda")
     rng = S.RandomNumberGenerator(km.structure.RND_SEED_KMC)
+    if a.current:
+        # the atoms of the current solve are invariant under KMC events: one pattern per run (src/kmc_main.cpp:273)
+        N_atom = int(((d["element"] != 0) & (d["element"] != 1)).sum())
+        comm.counts_T, comm.displs_T = comm.partition(N_atom + 1, comm.size_T)
+        S.initialize_sparsity_T(buf, d["pbc"], d["nn_dist"], NL, NL, 10, comm)
+        q_e = 1.60217663e-19
+        high_G_T, loop_G, G0 = 1e5 * d["high_G"], 1e7 * d["high_G"], 2 * 3.8612e-5 * 1e-5
+        side = float(d["lattice"][1]) * 1e-10
+        heat = S.heat_params(background_temp=a.T, A=side * side, cg_tolerance=1e-12, cg_max_iterations=50000)
     comm.sync()
     print("init [s] %.3f  (sites %d)" % (time.perf_counter() - t0, N))
     kmc_time = 0.0
@@ -62,11 +86,21 @@ def main():
                                                                  d["low_G"], d["nn_dist"], len(d["metals"]), step))
         tp, _ = timed(lambda: S.poisson_gridless_gpu(buf, comm))
         tg, _ = timed(lambda: S.sum_and_gather_potential(buf, NL, comm))
+        thermal = {}
+        if a.current:
+            tcb, st_cb = timed(lambda: S.update_CB_edge_gpu_sparse(buf, N, NL, NL, d["Vd"], d["pbc"], d["high_G"], d["low_G"],
+                                                                   d["nn_dist"], len(d["metals"])))
+            tpw, (imacro, st_t) = timed(lambda: S.update_power_gpu_sparse_dist(
+                buf, NL, NL, 10, d["Vd"], high_G_T, d["low_G"], loop_G, G0, q_e * 0.01, d["nn_dist"], 0.85 * 9.11e-31, 1.6,
+                len(d["metals"]), True, False, 1.0, cg_tolerance=1e-15 * N_atom, cg_max_iterations=40000))
+            th, ht = timed(lambda: S.update_temperature_local_gpu(buf, N, NL, NL, 1e-6, heat))      # steady state
+            if a.rate_mode != "bg":
+                thermal = dict(site_temperature=buf.site_temperature, rate_mode=a.rate_mode)
         te, ev = timed(lambda: S.execute_kmc_step_mpi(comm, N, comm.counts_events, comm.displs_events, 52, buf.neigh_idx,
                                                       lay, a.T, freq, d["sigma"], d["k"], buf.site_x, buf.site_y,
                                                       buf.site_z, buf.site_potential_charge, buf.site_element,
                                                       buf.site_charge, rng, layers, max_events=a.max_events,
-                                                      return_log=True))
+                                                      return_log=True, **thermal))
         kmc_time += ev[0]
         if a.event_stats and ev[1] > 0:
             # where the selection walk lands: how often a recently used supertile (128 consecutive rows of the event list)
@@ -86,6 +120,14 @@ def main():
                             lru.popitem(last=False)
                 line += ", LRU-%d hit rate %.2f" % (cap, hits / len(st_))
             print(line, flush=True)
+        if a.current:
+            print("step %d: charge %.6f | boundary %.6f (%d it) | pairwise %.6f | gather %.6f | CB edge %.6f (%d it) | "
+                  "power %.6f (%d it, I_macro %.4e) | heat %.6f (%d it, max T %.2f K) | events[%s] %.6f (%d ev) | "
+                  "superstep %.6f | KMC time %.5e" % (step + 1, tc, tb, st["iterations"], tp, tg, tcb, st_cb["iterations"], tpw,
+                                                       st_t["iterations"], imacro, th, ht["stats"]["iterations"],
+                                                       float(buf.site_temperature.max()), a.rate_mode, te, ev[1],
+                                                       tc + tb + tp + tg + tcb + tpw + th + te, kmc_time), flush=True)
+            continue
         print("step %d: charge %.6f | boundary %.6f (%d it) | pairwise %.6f | gather %.6f | events %.6f (%d ev) | "
               "superstep %.6f | KMC time %.5e" % (step + 1, tc, tb, st["iterations"], tp, tg, te, ev[1],
                                                    tc + tb + tp + tg + te, kmc_time), flush=True)
