@@ -90,6 +90,14 @@ def test_generic_csr_spmv_and_cg(km, oracle, torch, long_row):
         assert np.abs(M @ xs.cpu().numpy() - b).max() <= 1e-9
         # r holds the final residual b - A x (in/out like the reference's r_local_d)
         np.testing.assert_allclose(r.cpu().numpy(), b - M @ xs.cpu().numpy(), atol=1e-9)
+    # the iteration count of the plain reference (tests/cg_ref.py; tests/test_cg_ref.py holds the tolerance a factor
+    # >= 2 away from the reference's residuals on both sides)
+    import cg_ref
+    cref, ctol, cstop = cg_ref.count_case(M)
+    r = torch.as_tensor(cref["b"].copy(), device="cuda")
+    xs = torch.zeros(n, dtype=torch.float64, device="cuda")
+    st = S.conjugate_gradient_jacobi(mat, r, xs, torch.as_tensor(1.0 / M.diagonal(), device="cuda"), ctol, 2000)
+    assert st["iterations"] == cstop, (st, cstop)
     # values can be replaced in place (creation order)
     mat.set_values(2.0 * M.data)
     np.testing.assert_allclose(mat.get_values(), 2.0 * M.data)

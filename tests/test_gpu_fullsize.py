@@ -155,8 +155,8 @@ def test_full_size_event_step_bookkeeping(full, km):
 
 def test_full_size_event_paths_agree(full, km, monkeypatch):
     """The persistent batch kernel (row-aligned sums, changed sums patched through LDS, hundreds of groups and tens of
-    thousands of tiles here -- the 5 nm tests have one group) against the three-launch path (slot-aligned sums, every
-    touched tile re-added from memory): the same 300 events, residence times to rounding, the same final state."""
+    thousands of tiles here -- the 5 nm device's 37 650 sites make 5 groups) against the three-launch path (slot-aligned
+    sums, every touched tile re-added from memory): the same 300 events, residence times to rounding, the same final state."""
     S, d, buf, comm, t = full["S"], full["d"], full["buf"], full["comm"], full["torch"]
     layers = km.structure.LAYERS
     xs = np.clip(d["xyz"][:, 0], layers[0]["start_x"], layers[-1]["end_x"])

@@ -236,18 +236,25 @@ def test_resident_group_solve_matches_its_oracle_bit_for_bit(km, oracle, dev5, r
     assert np.linalg.norm(res) / np.linalg.norm(A["rhs"]) <= TRUE_RESIDUAL_BAR
 
 
-@pytest.mark.parametrize("n,P", [(10, 4), (3, 4), (2000, 3)])
-def test_multirank_generic_matrix_small_and_empty_ranks(km, n, P):
-    """Caller-supplied CSR over P loopback ranks: fewer rows than ranks (a rank owns nothing), a handful of
-    rows per rank, and an uneven partition; distributed SpMV and Jacobi-PCG against the assembled matrix."""
+def _tridiagonal(n):
     import scipy.sparse as sp
-    import torch
-    S = km.solvers
     M = sp.diags([np.full(n - 1, -1.0), np.full(n, 2.5) + 0.01 * np.arange(n), np.full(n - 1, -1.0)], [-1, 0, 1],
                  format="csr")
     if n > 100:
         M = (M + sp.diags([np.full(n - 37, -0.25)] * 2, [-37, 37])).tocsr()
     M.sort_indices()
+    return M
+
+
+@pytest.mark.parametrize("n,P", [(10, 4), (3, 4), (2000, 3)])
+def test_multirank_generic_matrix_small_and_empty_ranks(km, n, P):
+    """Caller-supplied CSR over P loopback ranks: fewer rows than ranks (a rank owns nothing), a handful of
+    rows per rank, and an uneven partition; distributed SpMV and Jacobi-PCG against the assembled matrix."""
+    import torch
+    import cg_ref
+    S = km.solvers
+    M = _tridiagonal(n)
+    cref, ctol, cstop = cg_ref.count_case(M)         # a right-hand side whose iteration count is decided by a wide margin
     counts, displs = S.KMC_comm.partition(n, P)
     comms = S.KMC_comm.loopback_group(n, n, n, n, size=P, device=0)
     x = np.cos(np.arange(n) * 0.7) + 2.0
@@ -270,7 +277,10 @@ def test_multirank_generic_matrix_small_and_empty_ranks(km, n, P):
             xs = torch.zeros(nr, dtype=torch.float64, device="cuda")
             dinv = torch.as_tensor(1.0 / M.diagonal()[r0:r0 + nr], device="cuda")
             st = S.conjugate_gradient_jacobi(mat, rr, xs, dinv, 1e-12, 500)
-            out[r] = dict(Ap=Ap.cpu().numpy(), x=xs.cpu().numpy(), st=st, r0=r0, nr=nr)
+            rc = torch.as_tensor(cref["b"][r0:r0 + nr].copy(), device="cuda")
+            xc = torch.zeros(nr, dtype=torch.float64, device="cuda")
+            stc = S.conjugate_gradient_jacobi(mat, rc, xc, dinv, ctol, 500)
+            out[r] = dict(Ap=Ap.cpu().numpy(), x=xs.cpu().numpy(), st=st, stc=stc, r0=r0, nr=nr)
             mat.close()
         except Exception as e:  # pragma: no cover
             import traceback
@@ -291,6 +301,9 @@ def test_multirank_generic_matrix_small_and_empty_ranks(km, n, P):
         np.testing.assert_allclose(o["Ap"], y[o["r0"]:o["r0"] + o["nr"]], rtol=1e-13, atol=1e-13)
         assert o["st"]["converged"] == 1 and o["st"]["iterations"] == out[0]["st"]["iterations"]
     assert np.abs(M @ sol - b).max() <= 1e-9
+    # the iteration count of the plain reference (tests/cg_ref.py), on every rank; tests/test_cg_ref.py holds the
+    # tolerance a factor >= 2 away from the reference's residuals on both sides
+    assert [o["stc"]["iterations"] for o in out] == [cstop] * P, ([o["stc"] for o in out], cstop)
 
 
 def test_p2p_slow_rank_cannot_have_its_halo_overwritten(km, oracle, dev5, ref5, monkeypatch):

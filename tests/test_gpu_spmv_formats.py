@@ -178,6 +178,14 @@ def test_generic_matrix_value_coding(km, torch):
     st = S.conjugate_gradient_jacobi(mat, r, xs, torch.as_tensor(1.0 / M3.diagonal(), device="cuda"), 1e-12, 5000)
     assert st["converged"] == 1
     assert np.abs(M3 @ xs.cpu().numpy() - b).max() <= 1e-9
+    # the iteration count of the plain reference (tests/cg_ref.py; tests/test_cg_ref.py holds the tolerance a factor
+    # >= 2 away from the reference's residuals on both sides)
+    import cg_ref
+    cref, ctol, cstop = cg_ref.count_case(M3)
+    r = torch.as_tensor(cref["b"].copy(), device="cuda")
+    xs.zero_()
+    st = S.conjugate_gradient_jacobi(mat, r, xs, torch.as_tensor(1.0 / M3.diagonal(), device="cuda"), ctol, 5000)
+    assert st["iterations"] == cstop, (st, cstop)
     mat.close()
     comm.close()
 
