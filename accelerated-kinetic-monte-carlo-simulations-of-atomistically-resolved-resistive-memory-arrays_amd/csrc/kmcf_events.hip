@@ -425,10 +425,11 @@ __global__ __launch_bounds__(KMCF_BLOCK) void select_event_kernel(
         const size_t id0 = (size_t)b * EV_TILE;
         const int L = (int)(id0 + EV_TILE < M ? (size_t)EV_TILE : M - id0);
         int k = wave_search<EV_TILE / 64>(event_prob + id0, L, number, &acc);
-        if (k < 0) k = 0;
+        const bool none = k < 0;                               // no slot of the tile holds a rate: only when no slot does at all
+        if (none) k = 0;
         const size_t id = id0 + k;
         if (lane == 0) {
-            const int i = (int)(id / nn) + start_i, j = neigh_idx[id], et = (int)event_type[id];
+            const int i = (int)(id / nn) + start_i, j = none ? -1 : neigh_idx[id], et = (int)event_type[id];
             ijevent[0] = s_ij[0] = i;
             ijevent[1] = s_ij[1] = j;
             ijevent[2] = s_ij[2] = et;
@@ -718,9 +719,10 @@ __global__ __launch_bounds__(EV_PB) void event_batch_kernel(
             const double pv_l = prob[sl];
             const int nj_l = neigh[sl], ty_l = (int)type[sl];
             int k = wave_search_f<1>([pv_l](int) { return pv_l; }, nn, number, &acc);
-            if (k < 0) k = 0;
+            const bool none = k < 0;                           // no slot of the row holds a rate: only when no slot does at all
+            if (none) k = 0;
             const int ks = __builtin_amdgcn_readfirstlane(k);
-            const int j = __builtin_amdgcn_readlane(nj_l, ks), et = __builtin_amdgcn_readlane(ty_l, ks);
+            const int j = none ? -1 : __builtin_amdgcn_readlane(nj_l, ks), et = __builtin_amdgcn_readlane(ty_l, ks);
             const double t_res = s_nlog[ev] / total;                                  // :479; the device decides whether the step goes on
             const bool last = !(t_res < A.inv_freq);                                  // this event is the step's last
             if (j >= 0 && !last) {
@@ -1422,6 +1424,17 @@ extern "C" int kmcf_execute_kmc_step(kmcf_comm *c, int N, const int *h_count, co
                                  d_x, d_y, d_z, d_site_potential_charge, d_site_element, d_site_charge, num_layers, h_E_gen, h_E_rec,
                                  h_E_Vdiff, h_E_Odiff, next_random, rng_user, max_events, event_time, n_events, h_event_log,
                                  nullptr, KMCF_RATE_T_BG);
+}
+
+extern "C" int kmcf_events_reset(kmcf_comm *c)
+{
+    KMCF_CHECK(c, KMCF_ERR_ARG, "kmcf_events_reset: null argument");
+    if (c->ev_cache && c->device >= 0) {
+        KMCF_TRY(kmcf_enter(c));
+        KMCF_HIP(hipStreamSynchronize(c->stream));              // (nothing of a step is in flight when its buffers go)
+    }
+    kmcf_event_cache_free(c);
+    return KMCF_OK;
 }
 
 extern "C" int kmcf_execute_kmc_step_thermal(kmcf_comm *c, int N, const int *h_count, const int *h_displs, int nn,

@@ -148,6 +148,7 @@ SIGNATURES = {
     "kmcf_execute_kmc_step": (C.c_int, [_P, C.c_int, _IP, _IP, C.c_int, _P, _P, C.c_double, C.c_double, C.c_double,
                                         C.c_double, _P, _P, _P, _P, _P, _P, C.c_int, _DP, _DP, _DP, _DP, _P, _P,
                                         C.c_int, _DP, _IP, _IP]),
+    "kmcf_events_reset": (C.c_int, [_P]),
     "kmcf_execute_kmc_step_thermal": (C.c_int, [_P, C.c_int, _IP, _IP, C.c_int, _P, _P, C.c_double, C.c_double,
                                                 C.c_double, C.c_double, _P, _P, _P, _P, _P, _P, C.c_int, _DP, _DP, _DP,
                                                 _DP, _P, _P, C.c_int, _DP, _IP, _IP, _P, C.c_int]),

@@ -520,7 +520,9 @@ def execute_kmc_step_mpi(kmc_comm, N, count, displs, nn, neigh_idx, site_layer, 
     Returns the event time (and, with return_log, the number of events and their (i, j, type) rows).
     site_temperature (N doubles on the device, e.g. gpubuf.site_temperature after update_temperature_local_gpu) with
     rate_mode "ekin" | "site" (or 1 | 2): thermally coupled rates, kmcf_execute_kmc_step_thermal.  The defaults
-    ("bg", no field) are kmcf_execute_kmc_step."""
+    ("bg", no field) are kmcf_execute_kmc_step.
+    The library keeps its verdict on a neighbour list per address: after writing into neigh_idx in place, or when a new list
+    may sit where torch's caching allocator freed an old one, call events_reset(kmc_comm) before the next step."""
     lib = _L.load()
     mode = _rate_mode(rate_mode)
     cnt, cntp = _ia(count)
@@ -550,6 +552,12 @@ def execute_kmc_step_mpi(kmc_comm, N, count, displs, nn, neigh_idx, site_layer, 
     if return_log:
         return t.value, nev.value, log[:3 * nev.value].reshape(-1, 3).copy()
     return t.value
+
+
+def events_reset(kmc_comm):
+    """kmcf_events_reset: drop the event step's workspace, the symmetry verdict of the neighbour list and a replicated
+    group's gathered lists; the next step works them out again.  In a group: every rank, between the same two steps."""
+    _L.check(_L.load().kmcf_events_reset(kmc_comm.handle), "kmcf_events_reset")
 
 
 def event_rates(kmc_comm, N, count, displs, nn, neigh_idx, site_layer, T_bg, freq, sigma, k, posx, posy, posz,

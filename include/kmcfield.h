@@ -385,7 +385,15 @@ int kmcf_rng_destroy(kmcf_rng *r);
  * number of executed events, h_event_log (may be NULL; 3*max_events ints) the (i, j, type) triples.
  * d_neigh_idx: this rank's count*nn neighbour slots.  Layer energies: copytoConstMemory
  * (src/kmc_events.cu:565-571).  T_bg, freq, sigma, k: host scalars (device scalars in the reference).
- * ELEMENT / EVENTTYPE codes: src/utils.h:37-60.  Every rank must pass a generator in the same state. */
+ * ELEMENT / EVENTTYPE codes: src/utils.h:37-60.  Every rank must pass a generator in the same state.
+ * The neighbour list is read as a constant of the run: the communicator keeps, per address d_neigh_idx and N, what
+ * it has worked out about the list (whether it is symmetric, which decides how an event's slots are zeroed; a
+ * replicated group's gathered copy of all ranks' lists).  While the communicator lives, the CONTENTS of a list at a
+ * given address must not change without a call of kmcf_events_reset -- a list rewritten in place, or another list
+ * that an allocator places at a freed list's address, is otherwise stepped with the old list's verdict and copy.
+ * KMCF_ERR_STATE, "no event could be selected": no slot holds a rate (e.g. every site is O_EL) when an event is due.
+ * The events executed before are counted and logged; the generator's position is unspecified after this error (the
+ * paths draw a different number of uniforms before they give up). */
 int kmcf_execute_kmc_step(kmcf_comm *c, int N, const int *h_count, const int *h_displs, int nn,
                           const int *d_neigh_idx, const int *d_site_layer, double T_bg, double freq,
                           double sigma, double k, const double *d_x, const double *d_y, const double *d_z,
@@ -394,6 +402,12 @@ int kmcf_execute_kmc_step(kmcf_comm *c, int N, const int *h_count, const int *h_
                           const double *h_E_Vdiff, const double *h_E_Odiff,
                           double (*next_random)(void *), void *rng_user, int max_events,
                           double *event_time, int *n_events, int *h_event_log);
+
+/* Drops what the communicator keeps for the event step between calls (workspace, the symmetry verdict of the
+ * neighbour list, a replicated group's gathered lists): the next step works everything out again from the list it
+ * is given.  For callers that change a neighbour list in place or reuse its memory; in a group, every rank calls it
+ * between the same two steps.  Costs one symmetry pass and the allocations on the next step, nothing per step. */
+int kmcf_events_reset(kmcf_comm *c);
 
 /* Rate modes of the thermal step.  EA: the activation energy kmcf_execute_kmc_step forms; s: the site whose
  * temperature counts -- j for generation, i for recombination, vacancy diffusion and ion diffusion. */

@@ -332,6 +332,10 @@ inline double execute_kmc_step_mpi_thermal(MPI_Comm comm, const int N, const int
     if (rank == 0) std::printf("Number of KMC events: %d\nEvent time: %g\n", n_events, event_time);
     return event_time;
 }
+
+// For a host program that rewrites a neighbour list in place or reuses its memory (the reference builds its lists once
+// per run, kmc_main.cpp:199, and needs no such call): kmcf_events_reset, between two event steps.
+inline void events_reset(MPI_Comm comm) { check(kmcf_events_reset(comm_of(comm)), "kmcf_events_reset"); }
 }  // namespace kmcf_compat
 
 // src/heat_solver_gpu.cu:53-70

@@ -30,8 +30,22 @@ def event_list(xyz, neigh, layer, T_bg, freq, sigma, k, pot, element, charge, la
     neigh = np.asarray(neigh)
     N, nn = neigh.shape
     layer, pot, element, charge = np.asarray(layer), np.asarray(pot, np.float64), np.asarray(element), np.asarray(charge)
+    # every event needs element[i] != O_EL: only those rows are evaluated (the same arithmetic per slot; lists of millions
+    # of rows with a few hundred live ones would otherwise spend seconds in erfc), the others are null
+    rows = np.flatnonzero(element != O_EL)
+    if len(rows) < N:
+        t, p, s = _event_list_rows(rows, xyz, neigh[rows], layer, T_bg, freq, sigma, k, pot, element, charge, layers, T, mode)
+        typ, prob, site = np.full((N, nn), EV_NULL, np.uint8), np.zeros((N, nn)), np.full((N, nn), -1, np.int32)
+        typ[rows], prob[rows], site[rows] = t, p, s
+        return typ, prob, site
+    return _event_list_rows(np.arange(N), xyz, neigh, layer, T_bg, freq, sigma, k, pot, element, charge, layers, T, mode)
+
+
+def _event_list_rows(rows, xyz, neigh, layer, T_bg, freq, sigma, k, pot, element, charge, layers, T, mode):
+    """event_list for the rows `rows` of the list; neigh holds these rows only, its entries are site ids"""
+    N, nn = len(element), neigh.shape[1]
     E = [np.array([l[key] for l in layers], np.float64) for key in ("E_gen_0", "E_rec_1", "E_diff_2", "E_diff_3")]
-    i = np.repeat(np.arange(N), nn).reshape(N, nn)
+    i = np.repeat(rows, nn).reshape(len(rows), nn)
     valid = (neigh >= 0) & (neigh < N)
     j = np.where(valid, neigh, 0)
     d = xyz[j] - xyz[i]
@@ -40,8 +54,8 @@ def event_list(xyz, neigh, layer, T_bg, freq, sigma, k, pot, element, charge, la
     ei, ej, ci, cj = element[i], element[j], charge[i].astype(np.int64), charge[j].astype(np.int64)
     dpot = pot[i] - pot[j]
     lj = layer[j]
-    typ = np.full((N, nn), EV_NULL, np.uint8)
-    EA = np.zeros((N, nn))
+    typ = np.full(neigh.shape, EV_NULL, np.uint8)
+    EA = np.zeros(neigh.shape)
     # generation
     m = valid & (ei == DEFECT) & (ej == O_EL)
     EA = np.where(m, E[0][lj] - 2 * dpot - 0, EA)

@@ -43,6 +43,18 @@ def test_error_convention(km):
         km.lib.check(-1, "x")
 
 
+def test_events_reset_on_a_communicator_without_workspace(km):
+    """kmcf_events_reset: nothing to drop is no error (a host-only communicator never steps), NULL is KMCF_ERR_ARG."""
+    lib = km.lib.load()
+    h = C.c_void_p()
+    km.lib.check(lib.kmcf_comm_create(C.byref(h), -1, 1, 0), "comm")
+    try:
+        assert lib.kmcf_events_reset(h) == 0 and lib.kmcf_events_reset(h) == 0
+        assert lib.kmcf_events_reset(None) == -1 and b"kmcf_events_reset" in lib.kmcf_last_error()
+    finally:
+        lib.kmcf_comm_destroy(h)
+
+
 def test_partition_matches_reference_rule(km, oracle):
     for n, P in ((36498, 8), (1597080, 8), (5, 8), (7, 1), (0, 3)):
         c, d = km.solvers.KMC_comm.partition(n, P)

@@ -35,3 +35,5 @@ def test_compat_shim_compiles_against_reference_headers(tmp_path):
                  "poisson_gridless_gpu", "sum_and_gather_potential", "update_power_gpu_sparse_dist",
                  "update_temperatureglobal_gpu", "execute_kmc_step_mpi", "copytoConstMemory"):
         assert ("\n%s(" % name) in shim.replace("void ", "\n").replace("double ", "\n"), name
+    # not a reference entry point: the reset a host program calls when it changes a neighbour list in place
+    assert "kmcf_events_reset(comm_of(comm))" in shim
