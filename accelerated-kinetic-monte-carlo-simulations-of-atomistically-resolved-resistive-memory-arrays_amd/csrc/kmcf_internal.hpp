@@ -115,6 +115,8 @@ struct kmcf_comm {
     kmcf_scalars *h_scal = nullptr;     // pinned host copy of a solve's scalars (read after the call's one sync)
     // event-step workspace kept between KMC steps (kmcf_execute_kmc_step, kmcf_events.hip)
     struct kmcf_event_cache *ev_cache = nullptr;
+    // workspace of kmcf_conductive_clusters (kmcf_clusters.hip): buffers only, no result outlives a call
+    struct kmcf_cluster_ws *cl_ws = nullptr;
     kmcf_knob_overrides opts;           // kmcf_set_option: this communicator's knob values (kmcf_opt*)
     bool connect_begun = false;         // kmcf_comm_connect / kmcf_comm_p2p_export ran (or a loopback group was created):
                                         // connect-scope knobs are refused from here on
@@ -138,6 +140,7 @@ inline bool kmcf_trace(const kmcf_comm *c) { return kmcf_opt_set(c, KNOB_TRACE);
 // digest of the group knobs' effective values on c (kmcf_matrix_build and the resident plan compare it across ranks)
 uint32_t kmcf_group_knob_hash(const kmcf_comm *c, kmcf_knob_id k);
 void kmcf_event_cache_free(kmcf_comm *c);
+void kmcf_cluster_ws_free(kmcf_comm *c);
 
 struct kmcf_subop;   // sub-block operator of the split T matrix (kmcf_tstate.hip)
 

@@ -64,6 +64,22 @@ class SolveStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class Cluster(C.Structure):
+    """kmcf_cluster_t"""
+    _fields_ = [("root", C.c_int), ("kind", C.c_int), ("size", C.c_int), ("touch", C.c_int),
+                ("x_min", C.c_double), ("x_max", C.c_double)]
+
+
+class ClusterStats(C.Structure):
+    """kmcf_cluster_stats_t"""
+    _fields_ = [("members", C.c_int), ("n_clusters", C.c_int), ("n_metal_clusters", C.c_int),
+                ("n_vacancy_clusters", C.c_int), ("n_bridging", C.c_int), ("largest_vacancy", C.c_int),
+                ("largest_bridging", C.c_int), ("passes", C.c_int), ("ms", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 _P = C.c_void_p          # device or opaque pointer
 _IP = C.POINTER(C.c_int)
 _DP = C.POINTER(C.c_double)
@@ -155,6 +171,8 @@ SIGNATURES = {
     "kmcf_event_rates": (C.c_int, [_P, C.c_int, _IP, _IP, C.c_int, _P, _P, C.c_double, C.c_double, C.c_double,
                                    C.c_double, _P, _P, _P, _P, _P, _P, C.c_int, _DP, _DP, _DP, _DP, _P, C.c_int,
                                    C.POINTER(C.c_ubyte), _DP]),
+    "kmcf_conductive_clusters": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, C.c_int, C.c_int, _P,
+                                           C.POINTER(Cluster), C.c_int, C.POINTER(ClusterStats)]),
     "kmcf_neighbor_list":(C.c_int, [_P, _P, _P, _P, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _P]),
 }
 

@@ -582,6 +582,35 @@ def event_rates(kmc_comm, N, count, displs, nn, neigh_idx, site_layer, T_bg, fre
 
 # K-state inspection helpers used by the parity tests --------------------------------
 
+CLUSTER_DTYPE = np.dtype([("root", np.int32), ("kind", np.int32), ("size", np.int32), ("touch", np.int32),
+                          ("x_min", np.float64), ("x_max", np.float64)])      # kmcf_cluster_t
+
+
+def conductive_clusters(kmc_comm, gpubuf, N_left_tot, N_right_tot, labels=True):
+    """kmcf_conductive_clusters on the buffers' whole-device neighbour list: connected components of the metal sites and
+    of the uncharged vacancies under the high_G rule (definitions: include/kmcfield.h).  Call it after
+    update_charge_gpu.  Returns dict(label: int32 device tensor of N entries (-1: no member) or None, clusters: numpy
+    structured array (root, kind, size, touch, x_min, x_max) sorted by root, stats: dict).  Two calls: the count, then
+    the table."""
+    lib = _L.load()
+    N = gpubuf.N_
+    assert gpubuf.neigh_idx is not None and gpubuf.neigh_idx.numel() == N * gpubuf.nn_, \
+        "conductive_clusters needs the neighbour list of the whole device"
+    label = torch.empty(N, dtype=torch.int32, device=gpubuf.device) if labels else None
+    st = _L.ClusterStats()
+    head = (kmc_comm.handle, N, gpubuf.nn_, _ptr(gpubuf.neigh_idx), _ptr(gpubuf.site_element), _ptr(gpubuf.site_charge),
+            _ptr(gpubuf.metal_types), gpubuf.num_metal_types_, _ptr(gpubuf.site_x), int(N_left_tot), int(N_right_tot))
+    _L.check(lib.kmcf_conductive_clusters(*head, _ptr(label), None, 0, C.byref(st)), "kmcf_conductive_clusters")
+    table = np.zeros(st.n_clusters, CLUSTER_DTYPE)
+    if st.n_clusters:
+        ms_count = st.ms
+        _L.check(lib.kmcf_conductive_clusters(*head, _ptr(label), table.ctypes.data_as(C.POINTER(_L.Cluster)), len(table),
+                                              C.byref(st)), "kmcf_conductive_clusters")
+        assert st.n_clusters == len(table)
+        st.ms += ms_count
+    return dict(label=label, clusters=table, stats=st.as_dict())
+
+
 def k_assemble(gpubuf, Vd, high_G, low_G):
     lib = _L.load()
     _L.check(lib.kmcf_k_assemble(gpubuf.K_distributed, _ptr(gpubuf.site_element), _ptr(gpubuf.site_charge),

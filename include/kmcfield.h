@@ -448,6 +448,54 @@ int kmcf_event_rates(kmcf_comm *c, int N, const int *h_count, const int *h_displ
                      unsigned char *h_type, double *h_prob);
 
 /* ---------------------------------------------------------------------- */
+/* Conductive clusters: the filament as a graph (no reference counterpart)   */
+/* ---------------------------------------------------------------------- */
+/* Connected components of the sites that conduct, by the reference's own high_G rule (populate_T_dist,
+ * src/current_solver_gpu.cu:1227-1241; class 1 / class 2 of the K rule).
+ * Members: site i is METAL if site_element[i] is in the metal list, a CONDUCTIVE VACANCY if site_element[i] == VACANCY
+ * (2) and site_charge[i] == 0; no other site is a member.
+ * Conductive edge (i, j): j appears in row i of the neighbour list OR i appears in row j (rows truncated at nn make
+ * lists one-sided), and both sites are metal or both are conductive vacancies (a metal-vacancy pair gets low_G).
+ * Cluster: a connected component of the members under conductive edges.  Its label and `root` is its smallest site id;
+ * non-members get label -1; a member without a conductive edge is a cluster of size 1.  kind: 1 metal, 2 vacancy.
+ * touch: a metal cluster has bit 0 (left) if it holds a site id < N_left_tot, bit 1 (right) if it holds a site id
+ * >= N - N_right_tot; a vacancy cluster has a bit if one of its sites shares a neighbour-list entry (either direction)
+ * with a metal site whose cluster has that bit.  A vacancy cluster with touch == 3 is a bridging filament.
+ * x_min / x_max: over the cluster's sites, from d_x, exact.  Every output is independent of the execution order: two
+ * calls on the same input return the same bytes. */
+#define KMCF_CLUSTER_METAL   1
+#define KMCF_CLUSTER_VACANCY 2
+typedef struct { int root, kind, size, touch; double x_min, x_max; } kmcf_cluster_t;   /* 32 bytes */
+typedef struct {
+    int members, n_clusters, n_metal_clusters, n_vacancy_clusters;
+    int n_bridging;             /* vacancy clusters with touch == 3                         */
+    int largest_vacancy;        /* size of the largest vacancy cluster (0: none)            */
+    int largest_bridging;       /* size of the largest bridging filament (0: none)          */
+    int passes;                 /* kernel launches that walk neighbour rows: a constant of the implementation */
+    float ms;                   /* device time of everything the call enqueued (HIP events) */
+} kmcf_cluster_stats_t;
+
+/* A LOCAL operation on the WHOLE-device list (N rows, -1 padded; an entry >= N or < -1 is ignored as padding): no
+ * collectives.  In a rank group every rank that wants the result calls it on its own copy of the whole list;
+ * partitioned lists are out of scope.  Nothing is kept between calls but buffers on the communicator (freed by
+ * kmcf_comm_destroy); no verdict about the list is cached, so the list and the site arrays may change between calls.
+ * Call it after kmcf_update_charge: the classes read the charges.
+ * d_site_label: N ints out, may be NULL.  h_clusters: the table sorted by root ascending, may be NULL; when
+ * n_clusters > max_clusters the first max_clusters entries are written and stats->n_clusters still reports the true
+ * count (query with h_clusters == NULL, then size the buffer).  stats may be NULL.
+ * KMCF_ERR_ARG (before anything needs a device; kmcf_last_error names the argument): NULL c, list, element, charge or
+ * d_x; N <= 0; nn <= 0; num_metals < 0, or num_metals > 0 with NULL d_metals; N_left_tot < 0, N_right_tot < 0 or
+ * N_left_tot + N_right_tot > N; max_clusters < 0, or h_clusters set with max_clusters == 0.
+ * KMCF_ERR_STATE: host-only communicator. */
+int kmcf_conductive_clusters(kmcf_comm *c, int N, int nn, const int *d_neigh_idx /* N*nn, -1 padded */,
+                             const int *d_site_element, const int *d_site_charge,
+                             const int *d_metals, int num_metals, const double *d_x,
+                             int N_left_tot, int N_right_tot,
+                             int *d_site_label /* N ints out; may be NULL */,
+                             kmcf_cluster_t *h_clusters /* may be NULL */, int max_clusters,
+                             kmcf_cluster_stats_t *stats /* may be NULL */);
+
+/* ---------------------------------------------------------------------- */
 /* T path: current solve (Kirchhoff matrix with two virtual nodes + WKB       */
 /* tunnelling sub-block), SURVEY 8 rows a14 / f3.  PARITY UNPINNED: no         */
 /* reference fixture exercises it (src/KMC_comm.h:243 disables it from main).  */

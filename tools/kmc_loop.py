@@ -4,11 +4,15 @@ boundary (K) solve, pairwise term, sum/gather, KMC events -- with the per-module
 prints into output<size>_<rank>.txt ("Z - calculation time - ...").
 
     python tools/kmc_loop.py [--workload 5nm|40nm|conducting] [--steps 6] [--T 300] [--current] [--rate-mode bg|ekin|site]
+                             [--clusters]
 
 --current adds the electro-thermal stages after the potential and before the events: conduction-band edge, current
 solve with heating (site_power), local heat solve (site_temperature); --rate-mode ekin | site lets the event rates read
 that field (kmcf_execute_kmc_step_thermal).  Workload `conducting`: the 4 x 4 crossbar with a vacancy filament of
-tests/test_gpu_conducting.py, whose current is a property of the device.
+tests/test_gpu_conducting.py, whose current is a property of the device.  --clusters runs the conductive cluster analysis
+(kmcf_conductive_clusters) after the charge update of every step: whether a filament bridges the electrodes, without a
+current solve; the step line gains `clusters <ms> (<vacancy clusters> vac, largest <sites>, bridging <filaments>)`, the
+time in milliseconds of device time.
 """
 import argparse
 import os
@@ -33,6 +37,8 @@ def main():
     ap.add_argument("--current", action="store_true", help="CB edge, current solve with heating and local heat solve in every step")
     ap.add_argument("--rate-mode", default="bg", choices=["bg", "ekin", "site"],
                     help="event rates: T_bg only | the reference's Ekin term | Boltzmann factor at the site's temperature")
+    ap.add_argument("--clusters", action="store_true",
+                    help="conductive cluster analysis after every charge update: vacancy clusters, the largest, bridging filaments")
     a = ap.parse_args()
     if a.rate_mode != "bg" and not a.current:
         ap.error("--rate-mode %s needs --current (the heat solve provides the site temperatures)" % a.rate_mode)
@@ -82,6 +88,11 @@ def main():
         tc, _ = timed(lambda: S.update_charge_gpu(buf.site_element, buf.site_charge, buf.neigh_idx, buf.N_, buf.nn_,
                                                   buf.metal_types, buf.num_metal_types_, comm.counts_events,
                                                   comm.displs_events, comm))
+        clusters = ""
+        if a.clusters:
+            cs = S.conductive_clusters(comm, buf, NL, NL, labels=False)["stats"]
+            clusters = " | clusters %.3f (%d vac, largest %d, bridging %d)" % (cs["ms"], cs["n_vacancy_clusters"],
+                                                                                  cs["largest_vacancy"], cs["n_bridging"])
         tb, st = timed(lambda: S.background_potential_gpu_sparse(buf, N, NL, NL, d["Vd"], d["pbc"], d["high_G"],
                                                                  d["low_G"], d["nn_dist"], len(d["metals"]), step))
         tp, _ = timed(lambda: S.poisson_gridless_gpu(buf, comm))
@@ -123,14 +134,14 @@ def main():
         if a.current:
             print("step %d: charge %.6f | boundary %.6f (%d it) | pairwise %.6f | gather %.6f | CB edge %.6f (%d it) | "
                   "power %.6f (%d it, I_macro %.4e) | heat %.6f (%d it, max T %.2f K) | events[%s] %.6f (%d ev) | "
-                  "superstep %.6f | KMC time %.5e" % (step + 1, tc, tb, st["iterations"], tp, tg, tcb, st_cb["iterations"], tpw,
-                                                       st_t["iterations"], imacro, th, ht["stats"]["iterations"],
-                                                       float(buf.site_temperature.max()), a.rate_mode, te, ev[1],
-                                                       tc + tb + tp + tg + tcb + tpw + th + te, kmc_time), flush=True)
+                  "superstep %.6f | KMC time %.5e%s" % (step + 1, tc, tb, st["iterations"], tp, tg, tcb, st_cb["iterations"], tpw,
+                                                         st_t["iterations"], imacro, th, ht["stats"]["iterations"],
+                                                         float(buf.site_temperature.max()), a.rate_mode, te, ev[1],
+                                                         tc + tb + tp + tg + tcb + tpw + th + te, kmc_time, clusters), flush=True)
             continue
         print("step %d: charge %.6f | boundary %.6f (%d it) | pairwise %.6f | gather %.6f | events %.6f (%d ev) | "
-              "superstep %.6f | KMC time %.5e" % (step + 1, tc, tb, st["iterations"], tp, tg, te, ev[1],
-                                                   tc + tb + tp + tg + te, kmc_time), flush=True)
+              "superstep %.6f | KMC time %.5e%s" % (step + 1, tc, tb, st["iterations"], tp, tg, te, ev[1],
+                                                     tc + tb + tp + tg + te, kmc_time, clusters), flush=True)
     buf.freeGPUmemory()
     comm.close()
 
