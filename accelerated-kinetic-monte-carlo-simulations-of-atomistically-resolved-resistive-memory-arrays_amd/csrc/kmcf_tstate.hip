@@ -67,6 +67,10 @@ struct kmcf_tstate {
     double *d_agree = nullptr, *h_agree = nullptr; // storage vote of a rank group: 2 P on the device; pinned 2 + 2 P
     bool assembled = false;
     kmcf_current_params_t par{};
+    // kmcf_current_map: scratch only (allocated with the state; nothing in it outlives a call)
+    double *d_cmap = nullptr;                      // 3 (Nsub + 2): per node sum |I|, tunnel sum |I|, sum I, interleaved
+    double *d_cmstat = nullptr, *h_cmstat = nullptr;   // 8 doubles on the device / pinned: the statistics
+    std::vector<int> cm_counts, cm_displs;         // 3 x the matrix's row partition (the all-gather of d_cmap)
 };
 
 namespace {
@@ -1169,6 +1173,138 @@ __global__ __launch_bounds__(KMCF_BLOCK) void gather_tunnel_pot_kernel(int n_glo
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_glob; i += gridDim.x * blockDim.x) out[i] = m[tidx[i] + 2];
 }
 
+// ---------------------------------------------------------------- current map (kmcf_current_map)
+// Per node r of the T matrix three sums over the stored off-diagonals (r, c) of its row, I_rc = g (m_r - m_c) with
+// g = -A_rc: sum |I_rc|, the same over tunnel pairs only, and sum I_rc; kept interleaved in cm[3 node + 0 / 1 / 2] so that
+// one all-gather moves them.  The virtual-virtual entry (0, 1) / (1, 0) -- the loop_G driver -- is no pair.
+// Neighbour part: LPR lanes per internal row (power_neighbour_kernel's walk), virtual rows included; sets all three.
+template <int LPR>
+__global__ __launch_bounds__(KMCF_BLOCK) void current_neighbour_kernel(int n_loc, const int *__restrict__ row_ptr, const int *__restrict__ col,
+                                                                       const double *__restrict__ val, const int *__restrict__ diag_pos,
+                                                                       const int *__restrict__ col_node, const double *__restrict__ m,
+                                                                       double *__restrict__ cm)
+{
+    constexpr int RPB = KMCF_BLOCK / LPR;
+    const int lane = threadIdx.x % LPR;
+    const int groups = (n_loc + RPB - 1) / RPB;
+    for (int grp = blockIdx.x; grp < groups; grp += gridDim.x) {
+        const int r = grp * RPB + threadIdx.x / LPR;
+        const bool valid = r < n_loc;
+        double a = 0.0, b = 0.0;
+        int nr = 0;
+        if (valid) {
+            nr = col_node[r];
+            const double mr = m[nr];
+            const int dpos = diag_pos[r];
+            for (int j = row_ptr[r] + lane; j < row_ptr[r + 1]; j += LPR) {
+                if (j == dpos) continue;
+                const int nc = col_node[col[j]];
+                if (nr < 2 && nc < 2) continue;                        // (0, 1) / (1, 0)
+                const double g = -val[j];
+                const double i_rc = g * (mr - m[nc]);
+                a += fabs(i_rc);
+                b += i_rc;
+            }
+        }
+#pragma unroll
+        for (int off = LPR / 2; off >= 1; off >>= 1) { a += __shfl_xor(a, off, 64); b += __shfl_xor(b, off, 64); }
+        if (valid && lane == 0) { cm[3 * (size_t)nr] = a; cm[3 * (size_t)nr + 1] = 0.0; cm[3 * (size_t)nr + 2] = b; }
+    }
+}
+
+// Tunnel part: a wave per local row of the pair bitmap (tunnel_value_kernel's walk), lane = column of a mask word; the
+// conductance of every set pair is evaluated afresh (one symmetric expression per pair: the same value whatever
+// storage the solve uses), the row's sums go into the slots of its node (after the neighbour part, same stream).
+__global__ __launch_bounds__(KMCF_BLOCK) void current_tunnel_kernel(
+    int n_loc, int s0, int n_groups, const int *__restrict__ tinfo, const double *__restrict__ tx, const double *__restrict__ ty,
+    const double *__restrict__ tz, const double *__restrict__ tcb, double tol, double m_e, double V0,
+    const unsigned long long *__restrict__ mask, const int *__restrict__ tidx, const double *__restrict__ m, double *__restrict__ cm)
+{
+    const int lane = threadIdx.x & 63;
+    const int wpb = KMCF_BLOCK / 64;
+    for (int s = blockIdx.x * wpb + (threadIdx.x >> 6); s < n_loc; s += gridDim.x * wpb) {
+        const int sg = s0 + s;
+        const double xi = tx[sg], yi = ty[sg], zi = tz[sg], cbi = tcb[sg];
+        const int fi = tinfo[sg];
+        const int node = tidx[sg] + 2;
+        const double mr = m[node];
+        double a = 0.0, b = 0.0;
+        for (int g = 0; g < n_groups; ++g) {
+            const unsigned long long mk = mask[(size_t)s * n_groups + g];
+            if (mk == 0ull) continue;                                      // wave-uniform
+            if ((mk >> lane) & 1ull) {
+                const int j = g * 64 + lane;
+                if (j != sg) {
+                    bool c2t;
+                    tunnel_pair(fi, tinfo[j], cbi, tcb[j], tol, &c2t);
+                    const double gc = -wkb_value(dist3(xi, yi, zi, tx[j], ty[j], tz[j]), cbi, tcb[j], c2t, m_e, V0);
+                    const double i_rc = gc * (mr - m[tidx[j] + 2]);
+                    a += fabs(i_rc);
+                    b += i_rc;
+                }
+            }
+        }
+        a = wave_sum(a); b = wave_sum(b);
+        if (lane == 0) { cm[3 * (size_t)node] += a; cm[3 * (size_t)node + 1] = a; cm[3 * (size_t)node + 2] += b; }
+    }
+}
+
+// site arrays (zero-filled before): through = half of sum |I|, tunnel likewise, net; atoms with a row only
+__global__ __launch_bounds__(KMCF_BLOCK) void current_scatter_kernel(int n_rows_atoms, const int *__restrict__ atom_site,
+                                                                     const double *__restrict__ cm, double *__restrict__ site_current,
+                                                                     double *__restrict__ site_tunnel, double *__restrict__ site_net)
+{
+    for (int a = blockIdx.x * blockDim.x + threadIdx.x; a < n_rows_atoms; a += gridDim.x * blockDim.x) {
+        const int s = atom_site[a];
+        const double *v = cm + 3 * ((size_t)a + 2);
+        site_current[s] = 0.5 * v[0];
+        if (site_tunnel) site_tunnel[s] = 0.5 * v[1];
+        if (site_net) site_net[s] = v[2];
+    }
+}
+
+__device__ __forceinline__ double block_max4(double v, double *lds4)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
+    if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const double t = fmax(fmax(lds4[0], lds4[1]), fmax(lds4[2], lds4[3]));
+    __syncthreads();
+    return t;
+}
+
+// One block: thread t adds atoms t, t + 256, ... in ascending order, then the block sum -- an order the input fixes.
+// out: [0] net[1], [1] -net[0], [2] sum through, [3] sum tunnel, [4] max through, [5] its site (lowest among equals; -1)
+__global__ __launch_bounds__(KMCF_BLOCK) void current_stats_kernel(int n_rows_atoms, const int *__restrict__ atom_site,
+                                                                   const double *__restrict__ cm, double *__restrict__ out)
+{
+    __shared__ double lds4[4];
+    double st = 0.0, su = 0.0, mx = -1.0;
+    for (int a = threadIdx.x; a < n_rows_atoms; a += KMCF_BLOCK) {
+        const double th = 0.5 * cm[3 * ((size_t)a + 2)];
+        st += th;
+        su += 0.5 * cm[3 * ((size_t)a + 2) + 1];
+        mx = fmax(mx, th);
+    }
+    st = block_sum4(st, lds4);
+    su = block_sum4(su, lds4);
+    mx = block_max4(mx, lds4);
+    double site = -2147483648.0;                                           // (minus the site: a maximum again)
+    for (int a = threadIdx.x; a < n_rows_atoms; a += KMCF_BLOCK)
+        if (0.5 * cm[3 * ((size_t)a + 2)] == mx) site = fmax(site, -(double)atom_site[a]);
+    site = block_max4(site, lds4);
+    if (threadIdx.x == 0) {
+        const bool found = site > -2147483648.0;
+        out[0] = cm[3 * 1 + 2];
+        out[1] = -cm[2];
+        out[2] = st;
+        out[3] = su;
+        out[4] = found ? mx : 0.0;
+        out[5] = found ? -site : -1.0;
+    }
+}
+
 template <typename T>
 int ensure(T **d, size_t *cap, size_t need)
 {
@@ -1202,11 +1338,13 @@ extern "C" int kmcf_tstate_destroy(kmcf_tstate *t)
                         t->d_tflag, t->d_blk, t->d_tidx, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz, t->d_tcb, t->d_rowcnt, t->d_tdiag,
                         t->sub.d_rows, t->sub.d_mask, t->sub.d_voff, t->sub.d_val, t->sub.d_xsub, t->d_pdisp, t->d_scal, t->d_err,
                         t->sub.d_tiles, t->sub.d_strips, t->sub.d_strip_first, t->sub.d_rowpart, t->sub.d_colpart,
-                        t->sub.d_jmask, t->sub.d_jvoff, t->sub.d_jval, t->sub.d_jcnt, t->sub.d_tile_local, t->sub.d_ypart, t->d_agree};
+                        t->sub.d_jmask, t->sub.d_jvoff, t->sub.d_jval, t->sub.d_jcnt, t->sub.d_tile_local, t->sub.d_ypart, t->d_agree,
+                        t->d_cmap, t->d_cmstat};
         for (void *p : ptrs)
             if (p) hipFree(p);
         if (t->h_pin) hipHostFree(t->h_pin);
         if (t->h_agree) hipHostFree(t->h_agree);
+        if (t->h_cmstat) hipHostFree(t->h_cmstat);
     }
     if (t->T) { t->T->sub = nullptr; kmcf_matrix_destroy(t->T); }
     delete t;
@@ -1378,6 +1516,13 @@ extern "C" int kmcf_initialize_sparsity_T(kmcf_comm *c, const double *d_site_x, 
     memset(t->h_agree, 0, (size_t)(2 + 2 * P) * sizeof(double));
     t->sub.counts.assign(P, 0);
     t->sub.displs.assign(P, 0);
+    // scratch of kmcf_current_map (here, not at its first call: no allocation between the exchanges of a group)
+    KMCF_CHECK((int64_t)3 * (Nsub + 2) < (int64_t)INT32_MAX, KMCF_ERR_ARG, "kmcf_initialize_sparsity_T: %d atoms exceed int32 indexing", Na);
+    KMCF_TRY(dalloc(&t->d_cmap, (size_t)3 * (Nsub + 2))); KMCF_TRY(dalloc(&t->d_cmstat, 8));
+    KMCF_HIP(hipHostMalloc(reinterpret_cast<void **>(&t->h_cmstat), 8 * sizeof(double), hipHostMallocDefault));
+    memset(t->h_cmstat, 0, 8 * sizeof(double));
+    t->cm_counts.resize((size_t)P); t->cm_displs.resize((size_t)P);
+    for (int q = 0; q < P; ++q) { t->cm_counts[q] = 3 * h_counts_T[q]; t->cm_displs[q] = 3 * h_displs_T[q]; }
     guard.t = nullptr;
     *out = t;
     return KMCF_OK;
@@ -1976,6 +2121,63 @@ extern "C" int kmcf_update_power_sparse(kmcf_tstate *t, const int *d_site_elemen
         float ms = 0.f;
         KMCF_HIP(hipEventElapsedTime(&ms, c->ev_a0, c->ev_a1));
         stats->ms_assembly = ms;
+    }
+    return KMCF_OK;
+}
+
+extern "C" int kmcf_current_map(kmcf_tstate *t, const double *d_atom_virtual_potentials, double *d_site_current, double *d_site_tunnel,
+                                double *d_site_net, kmcf_current_map_stats_t *stats)
+{
+    KMCF_CHECK(t, KMCF_ERR_ARG, "kmcf_current_map: null state (t)");
+    KMCF_CHECK(d_atom_virtual_potentials, KMCF_ERR_ARG, "kmcf_current_map: null d_atom_virtual_potentials");
+    KMCF_CHECK(d_site_current, KMCF_ERR_ARG, "kmcf_current_map: null d_site_current");
+    KMCF_CHECK(t->assembled, KMCF_ERR_STATE, "kmcf_current_map: call kmcf_t_assemble or kmcf_update_power_sparse first");
+    kmcf_comm *c = t->comm;
+    kmcf_matrix *m = t->T;
+    KMCF_CHECK(c->connected, KMCF_ERR_COMM, "kmcf_current_map: communicator not connected");
+    KMCF_TRY(kmcf_enter(c));
+    hipStream_t st = c->stream;
+    const kmcf_subop &sb = t->sub;
+    const int n_loc = m->n_loc, Na = t->N_atom, N = t->N;
+    const double *pot = d_atom_virtual_potentials;
+    KMCF_HIP(hipEventRecord(c->ev_a0, st));
+    KMCF_HIP(hipMemsetAsync(d_site_current, 0, (size_t)N * sizeof(double), st));
+    if (d_site_tunnel) KMCF_HIP(hipMemsetAsync(d_site_tunnel, 0, (size_t)N * sizeof(double), st));
+    if (d_site_net) KMCF_HIP(hipMemsetAsync(d_site_net, 0, (size_t)N * sizeof(double), st));
+    // this rank's rows: the neighbour part sets the three sums of a node, the tunnel part adds the row's pairs of the bitmap
+    if (n_loc > 0) {
+        current_neighbour_kernel<16><<<grid1d((int64_t)n_loc * 16), KMCF_BLOCK, 0, st>>>(n_loc, m->d_row_ptr, m->d_col, m->d_val, t->d_diag_pos,
+                                                                                         t->d_col_node, pot, t->d_cmap);
+        KMCF_HIP(hipGetLastError());
+    }
+    if (sb.n_loc > 0) {
+        const int wgrid = std::max(1, std::min((sb.n_loc + KMCF_BLOCK / 64 - 1) / (KMCF_BLOCK / 64), KMCF_MAX_PARTIALS));
+        current_tunnel_kernel<<<wgrid, KMCF_BLOCK, 0, st>>>(sb.n_loc, sb.row0, sb.n_groups, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz, t->d_tcb,
+                                                            t->par.tol, t->par.m_e, t->par.V0, sb.d_mask, t->d_tidx, pot, t->d_cmap);
+        KMCF_HIP(hipGetLastError());
+    }
+    // every rank gets all nodes (as d_pdisp is gathered: the row partition, three doubles a row)
+    KMCF_TRY(kmcf_comm_allgatherv_double(c, t->d_cmap, t->cm_counts.data(), t->cm_displs.data()));
+    current_scatter_kernel<<<grid1d(Na - 1), KMCF_BLOCK, 0, st>>>(Na - 1, t->d_atom_site, t->d_cmap, d_site_current, d_site_tunnel, d_site_net);
+    current_stats_kernel<<<1, KMCF_BLOCK, 0, st>>>(Na - 1, t->d_atom_site, t->d_cmap, t->d_cmstat);
+    KMCF_HIP(hipGetLastError());
+    KMCF_HIP(hipMemcpyAsync(t->h_cmstat, t->d_cmstat, 6 * sizeof(double), hipMemcpyDeviceToHost, st));
+    KMCF_HIP(hipEventRecord(c->ev_a1, st));
+    KMCF_HIP(hipStreamSynchronize(st));
+    KMCF_TRY(kmcf_p2p_check(c));
+    if (stats) {
+        const double *h = t->h_cmstat;
+        stats->i_injection = h[0];
+        stats->i_extraction = h[1];
+        stats->sum_through = h[2];
+        stats->sum_tunnel = h[3];
+        stats->max_through = h[4];
+        stats->max_site = (int)h[5];
+        const long long walked = (long long)sb.nnz - sb.n_loc;               // every row of the bitmap holds its diagonal bit
+        stats->tunnel_pairs_walked = (int)std::min<long long>(std::max<long long>(walked, 0), INT32_MAX);
+        float ms = 0.f;
+        KMCF_HIP(hipEventElapsedTime(&ms, c->ev_a0, c->ev_a1));
+        stats->ms = ms;
     }
     return KMCF_OK;
 }

@@ -80,6 +80,16 @@ class ClusterStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class CurrentMapStats(C.Structure):
+    """kmcf_current_map_stats_t"""
+    _fields_ = [("i_injection", C.c_double), ("i_extraction", C.c_double), ("sum_through", C.c_double),
+                ("sum_tunnel", C.c_double), ("max_through", C.c_double), ("max_site", C.c_int),
+                ("tunnel_pairs_walked", C.c_int), ("ms", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 _P = C.c_void_p          # device or opaque pointer
 _IP = C.POINTER(C.c_int)
 _DP = C.POINTER(C.c_double)
@@ -154,6 +164,7 @@ SIGNATURES = {
     "kmcf_t_assemble": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.POINTER(CurrentParams)]),
     "kmcf_update_power_sparse": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, _P, _P, C.POINTER(CurrentParams),
                                            C.POINTER(C.c_double), C.POINTER(SolveStats)]),
+    "kmcf_current_map": (C.c_int, [_P, _P, _P, _P, _P, C.POINTER(CurrentMapStats)]),
     "kmcf_update_temperature_global": (C.c_int, [_P, _P, _P, C.c_int, C.c_double, C.c_double, C.c_double,
                                                  C.c_double, C.c_double]),
     "kmcf_update_temperature_local": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_double,

@@ -328,6 +328,22 @@ def update_power_gpu_sparse_dist(gpubuf, num_source_inj, num_ground_ext, num_lay
     return im.value, st.as_dict()
 
 
+def current_map(gpubuf, potentials=None, tunnel=True, net=True):
+    """kmcf_current_map: where the current of a potential field flows (definitions: include/kmcfield.h).  Call it after
+    update_power_gpu_sparse_dist (or t_assemble, with potentials of your own: N_atom + 2 doubles on the device; default
+    gpubuf.atom_virtual_potentials).  Returns dict(current: N doubles per site, tunnel / net: the same or None, stats)."""
+    pot = gpubuf.atom_virtual_potentials if potentials is None else potentials
+    assert pot is None or pot.numel() == gpubuf.N_atom_ + 2, "potentials: N_atom + 2 doubles"
+    f64 = dict(dtype=torch.float64, device=gpubuf.device)
+    cur = torch.empty(gpubuf.N_, **f64)
+    tun = torch.empty(gpubuf.N_, **f64) if tunnel else None
+    nt = torch.empty(gpubuf.N_, **f64) if net else None
+    st = _L.CurrentMapStats()
+    _L.check(_L.load().kmcf_current_map(gpubuf.T_distributed, _ptr(pot), _ptr(cur), _ptr(tun), _ptr(nt), C.byref(st)),
+             "kmcf_current_map")
+    return dict(current=cur, tunnel=tun, net=nt, stats=st.as_dict())
+
+
 def t_info(gpubuf):
     info = _L.TStateInfo()
     _L.check(_L.load().kmcf_tstate_info(gpubuf.T_distributed, C.byref(info)), "kmcf_tstate_info")

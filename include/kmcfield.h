@@ -583,6 +583,49 @@ int kmcf_update_power_sparse(kmcf_tstate *t, const int *d_site_element, const in
                              double *d_atom_virtual_potentials, double *d_site_power,
                              const kmcf_current_params_t *p, double *imacro, kmcf_solve_stats_t *stats);
 
+/* Site-resolved current map: where the current of a solved potential field flows.
+ * Nodes are those of the T matrix (0 extraction, 1 injection, a + 2 for atom a); m =
+ * d_atom_virtual_potentials (N_atom + 2 doubles, as kmcf_update_power_sparse leaves them; only
+ * differences of m enter, so the |min| shift made with solve_heating drops out).  A PAIR is a
+ * stored off-diagonal of this rank's rows: an entry (r, c), c != r, of the neighbour matrix, or
+ * a set bit (i, j), j != i, of the tunnel pair bitmap; the virtual-virtual pair (0,1)/(1,0) is
+ * the loop_G driver term, no device current, and is left out.  With g = -A_rc >= 0 the current
+ * from r to c is I_rc = g (m[r] - m[c]), and per node r
+ *     through[r] = 1/2 sum_c |I_rc|        what flows through the node
+ *     tunnel[r]  = the same over tunnel pairs only
+ *     net[r]     = sum_c I_rc              Kirchhoff residual; positive: the node emits.
+ * The diagonal start values are no pairs: +high_G in row 0 and in the rows of atoms within
+ * nn_dist of the last atom (the cut ground node).  net is therefore EXPECTED to be non-zero at
+ * nodes 0 and 1 and at those atoms; everywhere else it measures how far the solve is from
+ * conserving current (100 CG iterations need not get there).
+ * Site outputs: N doubles each, zero-filled, then out[atom_site[a]] = value[a + 2] for every
+ * atom with a row, metal atoms included; the last atom has no row and keeps 0.
+ * The tunnel conductances are evaluated afresh from the pair bitmap every assembly builds,
+ * whatever storage the solve chose for the block (bitmap, dense, jagged or spread tiles): the
+ * call reads the state as the last kmcf_t_assemble / kmcf_update_power_sparse left it, changes
+ * scratch buffers only and never touches site_power, the matrix or a tunnel storage.  Two calls
+ * on the same input return the same bytes (no atomics; every sum is added in an order the
+ * input fixes).  On a rank group every rank calls it: each forms the sums of its own rows, the
+ * per-node sums are all-gathered by the row partition, every rank returns the complete site
+ * arrays and the same statistics except the two marked "this rank".
+ * KMCF_ERR_ARG (before anything needs a device; kmcf_last_error names the argument): NULL t,
+ * potentials or d_site_current.  KMCF_ERR_STATE: nothing assembled yet.  KMCF_ERR_COMM:
+ * communicator not connected. */
+typedef struct {
+    double i_injection;    /* net[1]: equals I_macro as get_imacro_sparse forms it            */
+    double i_extraction;   /* -net[0]: current arriving at the extraction node from atoms      */
+    double sum_through;    /* sum over atoms of through[]                                      */
+    double sum_tunnel;     /* sum over atoms of tunnel[]                                       */
+    double max_through;    /* largest through[] of an atom, and the site that holds it:        */
+    int    max_site;       /* the smallest site id among equals; -1 if there is no atom row   */
+    int    tunnel_pairs_walked; /* set off-diagonal bits of this rank's rows (saturating)      */
+    float  ms;             /* device time of everything the call enqueued (HIP events); this rank */
+} kmcf_current_map_stats_t;
+
+int kmcf_current_map(kmcf_tstate *t, const double *d_atom_virtual_potentials,
+                     double *d_site_current /* N, required */, double *d_site_tunnel /* N or NULL */,
+                     double *d_site_net /* N or NULL */, kmcf_current_map_stats_t *stats /* or NULL */);
+
 /* update_temperatureglobal_gpu (src/heat_solver_gpu.cu:53-70). */
 int kmcf_update_temperature_global(kmcf_comm *c, const double *d_site_power, double *d_T_bg, int N,
                                    double a_coeff, double b_coeff, double number_steps,

@@ -4,7 +4,7 @@ boundary (K) solve, pairwise term, sum/gather, KMC events -- with the per-module
 prints into output<size>_<rank>.txt ("Z - calculation time - ...").
 
     python tools/kmc_loop.py [--workload 5nm|40nm|conducting] [--steps 6] [--T 300] [--current] [--rate-mode bg|ekin|site]
-                             [--clusters]
+                             [--clusters] [--current-map]
 
 --current adds the electro-thermal stages after the potential and before the events: conduction-band edge, current
 solve with heating (site_power), local heat solve (site_temperature); --rate-mode ekin | site lets the event rates read
@@ -12,7 +12,9 @@ that field (kmcf_execute_kmc_step_thermal).  Workload `conducting`: the 4 x 4 cr
 tests/test_gpu_conducting.py, whose current is a property of the device.  --clusters runs the conductive cluster analysis
 (kmcf_conductive_clusters) after the charge update of every step: whether a filament bridges the electrodes, without a
 current solve; the step line gains `clusters <ms> (<vacancy clusters> vac, largest <sites>, bridging <filaments>)`, the
-time in milliseconds of device time.
+time in milliseconds of device time.  --current-map (with --current) runs the site-resolved current map (kmcf_current_map)
+after the power update of every step: the step line gains `current map <ms> (tunnel share <sum_tunnel / sum_through>, max
+<max_through> at site <max_site>)`, the time again in milliseconds of device time.
 """
 import argparse
 import os
@@ -39,7 +41,11 @@ def main():
                     help="event rates: T_bg only | the reference's Ekin term | Boltzmann factor at the site's temperature")
     ap.add_argument("--clusters", action="store_true",
                     help="conductive cluster analysis after every charge update: vacancy clusters, the largest, bridging filaments")
+    ap.add_argument("--current-map", action="store_true",
+                    help="site-resolved current map after every power update (needs --current): tunnel share, the busiest site")
     a = ap.parse_args()
+    if a.current_map and not a.current:
+        ap.error("--current-map needs --current (the map reads the potentials of the current solve)")
     if a.rate_mode != "bg" and not a.current:
         ap.error("--rate-mode %s needs --current (the heat solve provides the site temperatures)" % a.rate_mode)
     S = km.solvers
@@ -104,6 +110,10 @@ def main():
             tpw, (imacro, st_t) = timed(lambda: S.update_power_gpu_sparse_dist(
                 buf, NL, NL, 10, d["Vd"], high_G_T, d["low_G"], loop_G, G0, q_e * 0.01, d["nn_dist"], 0.85 * 9.11e-31, 1.6,
                 len(d["metals"]), True, False, 1.0, cg_tolerance=1e-15 * N_atom, cg_max_iterations=40000))
+            if a.current_map:
+                cm = S.current_map(buf, tunnel=False, net=False)["stats"]
+                clusters += " | current map %.3f (tunnel share %.4f, max %.4e at site %d)" % (
+                    cm["ms"], cm["sum_tunnel"] / cm["sum_through"] if cm["sum_through"] > 0 else 0.0, cm["max_through"], cm["max_site"])
             th, ht = timed(lambda: S.update_temperature_local_gpu(buf, N, NL, NL, 1e-6, heat))      # steady state
             if a.rate_mode != "bg":
                 thermal = dict(site_temperature=buf.site_temperature, rate_mode=a.rate_mode)
