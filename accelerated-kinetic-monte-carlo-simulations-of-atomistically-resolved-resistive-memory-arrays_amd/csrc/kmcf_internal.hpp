@@ -270,6 +270,16 @@ struct kmcf_matrix {
     int *d_sell_wcol = nullptr;        // column of each window slot
     unsigned short *d_sell = nullptr;  // the entry stream
     int *d_sell_pos = nullptr;         // per row: position of its first entry in d_sell
+    // ... and the same stream packed (kmcf_sell_pack.hpp): five 12-bit fields (code << 10) | slot per 8-byte word, same
+    // [tile][wave][step][lane] order, a wave padded to ceil(longest row / 5) steps.  What spmv_sell_kernel reads when
+    // sell_pack; d_sell stays for the readers of 16-bit entries (spmv_sellv_kernel's slots, the resident launch).  Each
+    // stream gets the codes of d_idx16 before its own reader runs (sell_dirty / sell12_dirty).
+    bool sell_pack = false;            // the plan made the packed stream (KMCF_SELL_PACK, and the packed size passes the plan's limits)
+    bool sell12_dirty = true;          // codes in d_idx16 are newer than d_sell12
+    int64_t n_sell12_words = 0;        // 8-byte words of d_sell12 (without the tail that idle waves read)
+    unsigned long long *d_sell12 = nullptr;
+    int2 *d_sell12_wave = nullptr;     // per tile and wave: (first word of its packed stream, steps of 5 entries)
+    int *d_sell12_pos = nullptr;       // per row: its first word in d_sell12
     // ... the same layout with f64 VALUES streamed next to the 16-bit slots (spmv_sellv_kernel: matrices whose values are
     // not dictionary-coded -- general CSR input, the symmetrically scaled CB-edge system): d_sellv[pos] = value of entry pos
     // of d_sell (0.0 in the padding), refreshed from d_val whenever the values changed; allocated on first use
@@ -361,6 +371,9 @@ inline kmcf_spmv_path kmcf_interior_path(const kmcf_matrix *m)
     if (!m->coded && m->sell_ok && m->sell_ident && m->sellv_grid > 0) return KMCF_PATH_SELLV;
     return m->coded ? KMCF_PATH_WCODE : KMCF_PATH_WINDOW;
 }
+
+// ... and whether spmv_sell_kernel reads the packed stream (five 12-bit fields per word) or the 16-bit one
+inline bool kmcf_sell_packed(const kmcf_matrix *m) { return m->sell_pack && m->d_sell12 != nullptr; }
 
 // grid of the interior SpMV pass = number of p.Ap partials it writes
 inline int kmcf_interior_grid(const kmcf_matrix *m)

@@ -12,7 +12,7 @@
 
 enum kmcf_knob_id {
     KNOB_BRICK, KNOB_SPMV_KIND, KNOB_SPMV_CODED, KNOB_SPMV_SELL, KNOB_SPMV_SELLV, KNOB_SPMV_SELL_ROWS,
-    KNOB_SPMV_SELL_SORT, KNOB_SPMV_NT, KNOB_SELL_NT, KNOB_LONG_ROW, KNOB_CB_SCALED, KNOB_SUB_DENSE, KNOB_SUB_STRIP,
+    KNOB_SPMV_SELL_SORT, KNOB_SPMV_NT, KNOB_SELL_NT, KNOB_SELL_PACK, KNOB_LONG_ROW, KNOB_CB_SCALED, KNOB_SUB_DENSE, KNOB_SUB_STRIP,
     KNOB_EVENTS_PERSISTENT, KNOB_EVENTS_FULLSCAN, KNOB_EVENTS_PARTITIONED, KNOB_EV_TREL, KNOB_CG_VARIANT,
     KNOB_CG_RESIDENT, KNOB_CGR_TPB, KNOB_CGR_G1, KNOB_CGR_DELAY, KNOB_CGR_RDELAY, KNOB_CGR_ADAPT, KNOB_CGR_TIMEOUT_MS,
     KNOB_CGR_CLASSIC_TILES, KNOB_TRANSPORT, KNOB_P2P_WINDOW_MB, KNOB_P2P_TIMEOUT_MS, KNOB_P2P_DIRECT, KNOB_P2P_AR,
@@ -64,6 +64,8 @@ inline constexpr kmcf_knob_def kmcf_knobs[] = {
     {KNOB_SPMV_NT, "KMCF_SPMV_NT", "matrices beyond the caches", "0 / 1", "nontemporal matrix loads in the f64-value SpMV kernels",
      KNOB_COMM, false, kv_enum("0|1")},
     {KNOB_SELL_NT, "KMCF_SELL_NT", "beyond the Infinity Cache", "0 / 1", "nontemporal loads of the coded entry stream",
+     KNOB_COMM, false, kv_enum("0|1")},
+    {KNOB_SELL_PACK, "KMCF_SELL_PACK", "1", "0 / 1", "0: the coded entry stream as 16-bit entries, four per 8-byte word, instead of five 12-bit fields",
      KNOB_COMM, false, kv_enum("0|1")},
     {KNOB_LONG_ROW, "KMCF_LONG_ROW", "384", "entries; <= 0: none", "rows longer than this go to the long-row kernel",
      KNOB_COMM, false, kv_int(-1000000000, 1000000000)},

@@ -505,7 +505,8 @@ extern "C" int kmcf_matrix_info(const kmcf_matrix *m, kmcf_matrix_info_t *info)
     info->spmv_coded = path == KMCF_PATH_SELL ? 2 : path == KMCF_PATH_WCODE ? 1 : 0;
     info->spmv_tiles = sell ? m->n_sell_tiles : window ? m->n_tiles : 0;
     info->spmv_window_cols = sell ? m->n_sell_wcols : window ? m->n_wcols : 0;
-    info->spmv_stream_entries = sell ? m->n_sell_entries : path == KMCF_PATH_WCODE ? (int64_t)m->h_row_ptr[m->n_short] : 0;
+    // (the packed stream in 2-byte units: 4 per 8-byte word of five entries)
+    info->spmv_stream_entries = path == KMCF_PATH_SELL && kmcf_sell_packed(m) ? 4 * m->n_sell12_words : sell ? m->n_sell_entries : path == KMCF_PATH_WCODE ? (int64_t)m->h_row_ptr[m->n_short] : 0;
     return KMCF_OK;
 }
 

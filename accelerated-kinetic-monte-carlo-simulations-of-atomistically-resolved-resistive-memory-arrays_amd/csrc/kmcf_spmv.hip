@@ -39,6 +39,7 @@
 #include <climits>
 
 #include "kmcf_p2p_dev.hpp"
+#include "kmcf_sell_pack.hpp"
 
 namespace {
 
@@ -403,7 +404,11 @@ __global__ __launch_bounds__(KMCF_BLOCK) void spmv_wcode_kernel(
 //     the tile, gathered through the window map wcol;
 //   * the register a step frees receives the same step of the next tile at once: one register set holds the
 //     stream of two tiles in flight (with a second set: 106 VGPRs, 4 blocks per CU, 41.9 us; with one: 81,
-//     5 blocks, 37.6 us on the 40 nm K matrix).
+//     5 blocks, 37.6 us on the 40 nm K matrix);
+//   * an entry carries 12 bits of information (10 slot bits, a code < 4), so the stream the kernel reads by default
+//     holds five of them per 8-byte word instead of four 16-bit offsets (PACK, kmcf_sell_pack.hpp; KMCF_SELL_PACK=0:
+//     the 16-bit stream): 0.8 x the stream's bytes and load instructions, two shifts-and-masks per entry instead of
+//     one, the same products added in the same order.
 // Stages per iteration k as in the kernel above: D(k) stage + reduce (+ stream of k+1), C(k+1) gathers and row
 // data, B(k+2) window map (+ lane rows), A(k+3) descriptors.
 typedef unsigned int sell_pair __attribute__((ext_vector_type(2)));   // 4 entries
@@ -423,7 +428,10 @@ struct sell_regs {
     bool valid;
 };
 
-template <int NQ, int LW, int ND, bool DOT, bool SKIP_BOUNDARY, bool IDENT, bool NT = false>
+// PACK: the stream holds five 12-bit fields per 8-byte word (kmcf_sell_pack.hpp) instead of four 16-bit offsets: the
+// same entries in the same order at 0.8 x the bytes, NS = ceil(4 NQ / 5) steps in registers; swave and stream are then
+// the packed stream's (d_sell12_wave, d_sell12).
+template <int NQ, int LW, int ND, bool DOT, bool SKIP_BOUNDARY, bool IDENT, bool NT = false, bool PACK = false>
 __global__ __launch_bounds__(KMCF_BLOCK) void spmv_sell_kernel(
     int n_tiles, const int4 *__restrict__ tile4, const int2 *__restrict__ swave, const int *__restrict__ lrow,
     const int *__restrict__ wcol, const sell_pair *__restrict__ stream, const double *__restrict__ x, double *__restrict__ y,
@@ -433,6 +441,8 @@ __global__ __launch_bounds__(KMCF_BLOCK) void spmv_sell_kernel(
     // window slots [0, 256): the tile's own rows (slot t = x[r0 + t], which the lane loads anyway); the rest:
     // the other columns the tile references, gathered through wcol
     constexpr int W = 1 << LW, WQ = W / KMCF_BLOCK - 1, BUF = ND * W;
+    constexpr int NS = PACK ? (4 * NQ + KMCF_PACK_FIELDS - 1) / KMCF_PACK_FIELDS : NQ;     // steps held in registers
+    static_assert(!PACK || (LW == KMCF_PACK_SLOT_BITS && ND <= 4), "a packed field is 10 slot bits + 2 code bits");
     typedef sell_regs<WQ> regs_t;
     __shared__ double xs[2 * BUF];      // (exactly 32 KB for two values and 1024 slots: five blocks fill a CU's LDS)
     if (check_done && S->done) return;
@@ -486,7 +496,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void spmv_sell_kernel(
         int2 s1 = swave[KMCF_TILE_OF(1) * 4 + wv], s2 = swave[KMCF_TILE_OF(2) * 4 + wv];
         int wca[WQ], wcb[WQ], lra = 0, lrb = 0;
         regs_t ta, tb;
-        sell_pair pk[NQ];
+        sell_pair pk[NS];
         {   // prologue: window maps of tiles 0 and 1, then everything of tile 0 -- the issue order of the loop
             // body (B before C), so that the wait counts the compiler derives for the loop head are the loop's own
             const int4 d0 = tile4[c_first];
@@ -498,7 +508,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void spmv_sell_kernel(
             const sell_pair *sp = stream + s0.x + lane;
             const int last = max(s0.y - 1, 0);
 #pragma unroll
-            for (int q = 0; q < NQ; ++q) pk[q] = KMCF_SELL_LD(sp + min(q, last) * 64);
+            for (int q = 0; q < NS; ++q) pk[q] = KMCF_SELL_LD(sp + min(q, last) * 64);
         }
         // wu / lu: window map and lane rows of tile k+1 (loaded an iteration ago); wl / ll: receive tile k+2's.
         // B is issued before C so that waiting for tile k+1's map next iteration leaves this iteration's later
@@ -528,14 +538,24 @@ __global__ __launch_bounds__(KMCF_BLOCK) void spmv_sell_kernel(
             const char *base = reinterpret_cast<const char *>(xb);
             double s = 0.0;
 #pragma unroll
-            for (int q = 0; q < NQ; ++q) {
+            for (int q = 0; q < NS; ++q) {
                 if (q < cur.nq) {
                     const sell_pair e = pk[q];
-                    const double a0 = *reinterpret_cast<const double *>(base + (e.x & 0xffffu));
-                    const double a1 = *reinterpret_cast<const double *>(base + (e.x >> 16));
-                    const double a2 = *reinterpret_cast<const double *>(base + (e.y & 0xffffu));
-                    const double a3 = *reinterpret_cast<const double *>(base + (e.y >> 16));
-                    s += a0; s += a1; s += a2; s += a3;
+                    if constexpr (PACK) {
+                        uint32_t off[KMCF_PACK_FIELDS];
+                        kmcf_pack_offsets(e.x, e.y, off);
+                        double a[KMCF_PACK_FIELDS];
+#pragma unroll
+                        for (int f = 0; f < KMCF_PACK_FIELDS; ++f) a[f] = *reinterpret_cast<const double *>(base + off[f]);
+#pragma unroll
+                        for (int f = 0; f < KMCF_PACK_FIELDS; ++f) s += a[f];      // entry order
+                    } else {
+                        const double a0 = *reinterpret_cast<const double *>(base + (e.x & 0xffffu));
+                        const double a1 = *reinterpret_cast<const double *>(base + (e.x >> 16));
+                        const double a2 = *reinterpret_cast<const double *>(base + (e.y & 0xffffu));
+                        const double a3 = *reinterpret_cast<const double *>(base + (e.y >> 16));
+                        s += a0; s += a1; s += a2; s += a3;
+                    }
                 }
                 pk[q] = KMCF_SELL_LD(spn + min(q, lastn) * 64);
             }
@@ -973,21 +993,24 @@ int sell_dispatch(kmcf_matrix *m, bool launch, bool with_dot, bool skip_if_done)
     const bool skipb = (m->n_halo > 0);
     const unsigned char *isb = skipb ? m->d_is_boundary : nullptr;
     double *part = with_dot ? m->d_part_a : nullptr;
-    const sell_pair *stream = reinterpret_cast<const sell_pair *>(m->d_sell);
+    // the packed stream (five 12-bit fields per word) with its own wave table, or the 16-bit one
+    const bool packed = kmcf_sell_packed(m);
+    const sell_pair *stream = reinterpret_cast<const sell_pair *>(packed ? static_cast<const void *>(m->d_sell12) : m->d_sell);
+    const int2 *swave = packed ? m->d_sell12_wave : m->d_sell_wave;
     int pc = 0;
     kmcf_sell_instance(m, [&](auto nq, auto nd) {
-        with_bools([&](auto dot, auto skip, auto ident) {
+        with_bools([&](auto dot, auto skip, auto ident, auto pack) {
             auto run = [&](auto kernel) {
-                run_or_query(kernel, launch, &pc, grid, st, m->n_sell_tiles, m->d_sell_tile, m->d_sell_wave, m->d_sell_lrow, m->d_sell_wcol,
+                run_or_query(kernel, launch, &pc, grid, st, m->n_sell_tiles, m->d_sell_tile, swave, m->d_sell_lrow, m->d_sell_wcol,
                              stream, m->d_p, m->d_Ap, isb, part, m->d_S, chk, m->d_dict, m->d_diagv);
             };
             // the nontemporal instance exists only for IDENT without a boundary skip (same registers and LDS: the
             // occupancy query of the plain instance holds)
             if constexpr (ident && !skip) {
-                if (m->sell_nt && launch) return run(spmv_sell_kernel<nq, LW, nd, dot, false, true, true>);
+                if (m->sell_nt && launch) return run(spmv_sell_kernel<nq, LW, nd, dot, false, true, true, pack>);
             }
-            run(spmv_sell_kernel<nq, LW, nd, dot, skip, ident>);
-        }, with_dot, skipb, m->sell_ident);
+            run(spmv_sell_kernel<nq, LW, nd, dot, skip, ident, false, pack>);
+        }, with_dot, skipb, m->sell_ident, packed);
         return 0;
     });
     return pc;
@@ -1054,8 +1077,50 @@ __global__ __launch_bounds__(KMCF_BLOCK) void sell_refresh_kernel(int n, const i
     }
 }
 
-int sell_refresh(kmcf_matrix *m)
+// The same for the packed stream.  A word has one owner: lane l of a row's LPR lanes owns the row's steps l, l + LPR,
+// ..., replaces the codes of a word in a register and writes the word once (no two threads touch one word).
+// Neighbouring rows are neighbouring lanes of the stream, so the words of a step are read and written in runs.
+template <int LPR>
+__global__ __launch_bounds__(KMCF_BLOCK) void sell12_refresh_kernel(int n, const int *__restrict__ row_ptr,
+                                                                    const int *__restrict__ diag_pos,
+                                                                    const unsigned short *__restrict__ idx16,
+                                                                    const int *__restrict__ sell12_pos,
+                                                                    unsigned long long *__restrict__ sell12)
 {
+    constexpr int RPB = KMCF_BLOCK / LPR;
+    const int lane = threadIdx.x % LPR;
+    for (int r = blockIdx.x * RPB + threadIdx.x / LPR; r < n; r += gridDim.x * RPB) {
+        const int b = row_ptr[r], e = row_ptr[r + 1], dp = diag_pos[r];
+        const int len = e - b - (dp >= 0 ? 1 : 0);
+        unsigned long long *wp = sell12 + sell12_pos[r];
+        for (int q = lane; q * KMCF_PACK_FIELDS < len; q += LPR) {
+            uint64_t w = wp[(size_t)q * 64];
+#pragma unroll
+            for (int f = 0; f < KMCF_PACK_FIELDS; ++f) {
+                const int k = q * KMCF_PACK_FIELDS + f;
+                if (k < len) {
+                    const int j = b + k + ((dp >= 0 && b + k >= dp) ? 1 : 0);
+                    w = kmcf_pack_put_code(w, f, (unsigned int)idx16[j] >> KMCF_SLOT_BITS);
+                }
+            }
+            wp[(size_t)q * 64] = w;
+        }
+    }
+}
+
+// the stream that spmv_sell_kernel reads holds the current codes (each stream is refreshed before its own reader
+// runs: an assembly pays for one pass, over the stream in use)
+int sell_refresh(kmcf_matrix *m, bool packed)
+{
+    if (packed) {
+        if (!m->sell12_dirty) return KMCF_OK;
+        constexpr int LPR12 = 4;
+        sell12_refresh_kernel<LPR12><<<grid_for(m->n_short, KMCF_BLOCK / LPR12), KMCF_BLOCK, 0, m->comm->stream>>>(
+            m->n_short, m->d_row_ptr, m->d_diag_pos, m->d_idx16, m->d_sell12_pos, m->d_sell12);
+        KMCF_HIP(hipGetLastError());
+        m->sell12_dirty = false;
+        return KMCF_OK;
+    }
     if (!m->sell_dirty) return KMCF_OK;
     constexpr int LPR = 4;
     sell_refresh_kernel<LPR><<<grid_for(m->n_short, KMCF_BLOCK / LPR), KMCF_BLOCK, 0, m->comm->stream>>>(
@@ -1085,7 +1150,7 @@ void launch_interior(kmcf_matrix *m, bool with_dot, bool skip_if_done)
 {
     switch (kmcf_interior_path(m)) {
         case KMCF_PATH_SELL:
-            if (sell_refresh(m) == KMCF_OK) sell_dispatch(m, true, with_dot, skip_if_done);
+            if (sell_refresh(m, kmcf_sell_packed(m)) == KMCF_OK) sell_dispatch(m, true, with_dot, skip_if_done);
             break;
         case KMCF_PATH_SELLV:
             if (sellv_prepare(m) == KMCF_OK) sellv_dispatch(m, true, with_dot, skip_if_done);
@@ -1292,6 +1357,12 @@ int plan_sell(kmcf_matrix *m, const std::vector<int> &col)
     std::vector<int2> waves;
     std::vector<int> lrow;
     std::vector<unsigned short> st;
+    // the packed stream next to it (five 12-bit fields per word; KMCF_SELL_PACK=0: the 16-bit stream alone, as before)
+    const bool want_pack = lw == KMCF_PACK_SLOT_BITS && kmcf_opt_int(m->comm, KNOB_SELL_PACK, 1) != 0;
+    const uint64_t pad12 = kmcf_pack_fill(kmcf_pack_field(0, (uint32_t)(W - 1)));
+    std::vector<uint64_t> st12;
+    std::vector<int2> waves12;
+    std::vector<int> pos12(want_pack ? (size_t)n : 0, 0);
     int64_t real = 0;
     bool ident = true;                               // rows already sorted inside every tile (kmcf_sell_refine_order)
     auto len_of = [&](int i) { return rp[i + 1] - rp[i] - (dpos[i] >= 0 ? 1 : 0); };
@@ -1338,13 +1409,23 @@ int plan_sell(kmcf_matrix *m, const std::vector<int> &col)
             const size_t base = st.size() / 4;                              // in 8-byte groups
             waves.push_back(make_int2((int)base, wq));
             st.resize(st.size() + (size_t)wq * 256, pad);
+            const size_t base12 = st12.size();                              // in words
+            if (want_pack) {
+                waves12.push_back(make_int2((int)base12, kmcf_pack_steps(wlen)));
+                st12.resize(base12 + (size_t)kmcf_pack_steps(wlen) * 64, pad12);
+            }
             for (int t = t0; t < std::min(t0 + 64, nr); ++t) {
                 const int row = r + ord[t];
                 pos[row] = (int)((base + (t - t0)) * 4);
+                if (want_pack) pos12[row] = (int)(base12 + (t - t0));
                 int k = 0;
                 for (int j = rp[row]; j < rp[row + 1]; ++j) {
                     if (j == dpos[row]) continue;
                     st[(size_t)pos[row] + (size_t)(k >> 2) * 256 + (k & 3)] = (unsigned short)(slot[col[j]] << 3);
+                    if (want_pack) {
+                        uint64_t &w12 = st12[(size_t)pos12[row] + (size_t)(k / KMCF_PACK_FIELDS) * 64];
+                        w12 = kmcf_pack_put(w12, k % KMCF_PACK_FIELDS, kmcf_pack_field(0, (uint32_t)slot[col[j]]));
+                    }
                     ++k;
                 }
                 real += k;
@@ -1357,6 +1438,14 @@ int plan_sell(kmcf_matrix *m, const std::vector<int> &col)
     if (st.size() / 4 > (size_t)0x7fffff00 || (double)st.size() > 1.5 * (double)real + 4096.0 * tiles.size()) return KMCF_OK;
     const int nt = (int)tiles.size();
     const bool trace = kmcf_trace(m->comm);
+    // the same two limits on the packed stream, in its own units (words; 5 entries per word where the 16-bit stream
+    // has 4 per group): where it misses them the 16-bit stream runs
+    const bool pack = want_pack && st12.size() <= (size_t)0x7fffff00 &&
+                      (double)KMCF_PACK_FIELDS * (double)st12.size() <= 1.5 * (double)real + 5120.0 * tiles.size();
+    if (trace && pack)
+        fprintf(stderr, "kmcf row-per-lane plan: packed stream %lld words = %.1f MB (16-bit: %.1f MB), %lld entries + %.1f %% padding, %d steps\n",
+                (long long)st12.size(), 8e-6 * st12.size(), 2e-6 * st.size(), (long long)real,
+                100.0 * (double(KMCF_PACK_FIELDS) * double(st12.size()) / double(std::max<int64_t>(real, 1)) - 1.0), kmcf_pack_steps(4 * nq));
     if (trace)
         fprintf(stderr, "kmcf row-per-lane plan: %d tiles of <= %d rows%s, %.1f rows, %.1f window columns per tile, %lld entries + %.1f %% padding, %d steps\n",
                 nt, row_cap, ident ? " (sorted in place)" : "", double(n) / nt, double(wcol.size()) / nt, (long long)real, 100.0 * (double(st.size()) / double(std::max<int64_t>(real, 1)) - 1.0), nq);
@@ -1392,6 +1481,18 @@ int plan_sell(kmcf_matrix *m, const std::vector<int> &col)
     KMCF_HIP(hipMemcpy(m->d_sell_wcol, wcol.data(), wcol.size() * sizeof(int), hipMemcpyHostToDevice));
     KMCF_HIP(hipMemcpy(m->d_sell, st.data(), st.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
     KMCF_HIP(hipMemcpy(m->d_sell_pos, pos.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+    m->sell_pack = pack;
+    m->n_sell12_words = pack ? (int64_t)st12.size() : 0;
+    if (pack) {
+        st12.resize(st12.size() + 128, pad12);        // (idle waves, as above)
+        KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&m->d_sell12), st12.size() * sizeof(uint64_t)));
+        KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&m->d_sell12_wave), waves12.size() * sizeof(int2)));
+        KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&m->d_sell12_pos), (size_t)n * sizeof(int)));
+        KMCF_HIP(hipMemcpy(m->d_sell12, st12.data(), st12.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+        KMCF_HIP(hipMemcpy(m->d_sell12_wave, waves12.data(), waves12.size() * sizeof(int2), hipMemcpyHostToDevice));
+        KMCF_HIP(hipMemcpy(m->d_sell12_pos, pos12.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+    }
+    m->sell12_dirty = true;
     m->n_sell_tiles = nt;
     m->sell_lw = lw;
     m->sell_nq = nq;
@@ -1401,7 +1502,9 @@ int plan_sell(kmcf_matrix *m, const std::vector<int> &col)
     m->sell_grid = 0;                                 // with the dictionary (its size selects the instance)
     // beyond the Infinity Cache (256 MiB; 10 x 10 cells = 243 MB of format still run 40.2 us plain against 51.9
     // nontemporal) the entry stream is loaded nontemporal; KMCF_SELL_NT overrides
-    m->sell_nt = 2.0 * (double)st.size() + 4.0 * (double)wcol.size() + 28.0 * (double)n > 300e6;
+    // (the bytes of the stream the kernel reads: packed where the plan packed it)
+    const double stream_bytes = pack ? 8.0 * (double)m->n_sell12_words : 2.0 * (double)m->n_sell_entries;
+    m->sell_nt = stream_bytes + 4.0 * (double)m->n_sell_wcols + 28.0 * (double)n > 300e6;
     m->sell_nt = kmcf_opt_int(m->comm, KNOB_SELL_NT, m->sell_nt) != 0;
     return KMCF_OK;
 }
@@ -1520,7 +1623,7 @@ int kmcf_matrix_set_dictionary(kmcf_matrix *m, const double *h_dict, int nd)
         if (kmcf_trace(m->comm)) fprintf(stderr, "kmcf row-per-lane kernel: grid %d for %d tiles\n", m->sell_grid, m->n_sell_tiles);
     }
     m->dict_n = nd;
-    m->sell_dirty = true;                               // the caller is about to write (or has just written) the codes
+    m->sell_dirty = m->sell12_dirty = true;             // the caller is about to write (or has just written) the codes
     m->coded = true;
     return KMCF_OK;
 }
@@ -1651,7 +1754,7 @@ int kmcf_spmv_device(kmcf_matrix *m, bool with_dot, bool skip_if_done, int flags
     return KMCF_OK;
 }
 
-int kmcf_sell_ready(kmcf_matrix *m) { return sell_refresh(m); }
+int kmcf_sell_ready(kmcf_matrix *m) { return sell_refresh(m, false); }     // (the resident launch reads the 16-bit stream)
 
 kmcf_part4 kmcf_spmv_partials(const kmcf_matrix *m)
 {
@@ -1834,13 +1937,14 @@ void kmcf_spmv_plan_free(kmcf_matrix *m)
 {
     void *ptrs[] = {m->d_chunk_row, m->d_tile, m->d_tile4, m->d_tbase, m->d_wcol, m->d_idx16, m->d_dict, m->d_diagv,
                     m->d_diag_pos, m->d_code_fail, m->d_sell_tile, m->d_sell_wave, m->d_sell_lrow, m->d_sell_wcol,
-                    m->d_sell, m->d_sell_pos, m->d_sellv};
+                    m->d_sell, m->d_sell_pos, m->d_sellv, m->d_sell12, m->d_sell12_wave, m->d_sell12_pos};
     for (void *p : ptrs)
         if (p) hipFree(p);
     m->d_chunk_row = nullptr; m->d_tile = nullptr; m->d_tile4 = nullptr; m->d_tbase = nullptr; m->d_wcol = nullptr;
     m->d_idx16 = nullptr; m->d_dict = nullptr; m->d_diagv = nullptr; m->d_diag_pos = nullptr; m->d_code_fail = nullptr;
     m->d_sell_tile = nullptr; m->d_sell_wave = nullptr; m->d_sell_lrow = nullptr; m->d_sell_wcol = nullptr;
     m->d_sell = nullptr; m->d_sell_pos = nullptr; m->d_sellv = nullptr;
+    m->d_sell12 = nullptr; m->d_sell12_wave = nullptr; m->d_sell12_pos = nullptr; m->sell_pack = false; m->n_sell12_words = 0;
     m->n_chunks = 0; m->n_tiles = 0; m->n_sell_tiles = 0; m->sellv_grid = 0;
     m->sell_ok = false; m->dict_uploaded = false;
     kmcf_values_changed(m);

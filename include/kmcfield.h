@@ -158,7 +158,10 @@ typedef struct {
     int spmv_tiles;           /* window / row-per-lane kernel: number of tiles      */
     int64_t spmv_window_cols; /* the same: sum of the tiles' window sizes           */
     int64_t spmv_stream_entries; /* coded kernels: 16-bit entries streamed per launch; row-per-lane kernels (coded, or
-                                    spmv_coded==0 with f64 values): entries per launch, padding included; else 0 */
+                                    spmv_coded==0 with f64 values): entries per launch, padding included; else 0.
+                                    Where the coded row-per-lane kernel streams its entries packed (five 12-bit fields
+                                    per 8-byte word, KMCF_SELL_PACK): the streamed bytes / 2, so that 2 B times this
+                                    field stays the bytes a launch reads */
 } kmcf_matrix_info_t;
 int kmcf_matrix_info(const kmcf_matrix *m, kmcf_matrix_info_t *info);
 
