@@ -142,6 +142,8 @@ extern "C" int kmcf_comm_create(kmcf_comm **out, int device, int nranks, int ran
     // already hold the first number that will be waited for
     memset(c->h_pinned, 0, 16 * sizeof(int));
     memset(c->h_scal, 0, sizeof(kmcf_scalars));
+    KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&c->d_bad_site), sizeof(int)));
+    KMCF_HIP(hipMemset(c->d_bad_site, KMCF_NO_BAD_SITE & 0xff, sizeof(int)));
     c->mark_seq = 0;
     c->connected = (nranks == 1);
     *out = c;
@@ -284,6 +286,7 @@ extern "C" int kmcf_comm_destroy(kmcf_comm *c)
     if (c->ev_call1) hipEventDestroy(c->ev_call1);
     if (c->ev_entry) hipEventDestroy(c->ev_entry);
     if (c->d_scratch) hipFree(c->d_scratch);
+    if (c->d_bad_site) hipFree(c->d_bad_site);
     if (c->stream) hipStreamDestroy(c->stream);
     if (c->comm_stream) hipStreamDestroy(c->comm_stream);
     if (c->h_pinned) hipHostFree(c->h_pinned);

@@ -48,6 +48,8 @@ constexpr int KMCF_CHUNK_ITERS = 32;     // CG iterations enqueued between conve
 constexpr int KMCF_DICT_MAX = 62;        // value dictionary of the coded window SpMV (codes 0..61)
 constexpr int KMCF_CODE_DIAG = 63;       // code of a row's diagonal entry (value in d_diagv)
 constexpr int KMCF_SLOT_BITS = 10;       // window slots < 1024
+constexpr int KMCF_NO_BAD_SITE = 0x7f7f7f7f;   // kmcf_comm::d_bad_site at rest (a byte pattern: set with hipMemset)
+constexpr int KMCF_PINNED_BAD_SITE = 15;       // word of kmcf_comm::h_pinned that receives d_bad_site (0-2: the CG's chunk checks)
 
 // Device-resident CG scalars (never round-trip through the host inside the loop).
 struct kmcf_scalars {
@@ -113,6 +115,8 @@ struct kmcf_comm {
     int mark_seq = 0;                   // number of the last chunk check (cg_chunk_check)
     int *h_pinned = nullptr;            // 16 ints pinned host (done/iters read-back)
     kmcf_scalars *h_scal = nullptr;     // pinned host copy of a solve's scalars (read after the call's one sync)
+    int *d_bad_site = nullptr;          // smallest site id whose contact value is not finite (k_rhs_contacts_kernel, atomicMin);
+                                        // KMCF_NO_BAD_SITE between calls: whoever finds it lowered sets it back
     // event-step workspace kept between KMC steps (kmcf_execute_kmc_step, kmcf_events.hip)
     struct kmcf_event_cache *ev_cache = nullptr;
     // workspace of kmcf_conductive_clusters (kmcf_clusters.hip): buffers only, no result outlives a call
@@ -305,6 +309,10 @@ struct kmcf_kstate {
     unsigned char *d_cls = nullptr;    // per-site class (N): 1 metal, 2 uncharged vacancy, 0 other
     unsigned char *d_cls_col = nullptr;  // the same per internal column (own rows in internal order | halo slots)
     double *d_diag = nullptr, *d_left = nullptr, *d_right = nullptr, *d_rhs = nullptr;
+    // internal rows that have a left or right contact entry, ascending: the only rows whose rhs depends on the contact
+    // values (a shell one neighbour distance thick under each electrode); kmcf_k_assemble_contacts walks this list
+    int *d_crow = nullptr;
+    int n_crow = 0;
     bool assembled = false;
     // replicated interface solution for sum_and_gather
     double *d_gather = nullptr;

@@ -317,6 +317,48 @@ __global__ __launch_bounds__(KMCF_BLOCK) void sum_ab_kernel(double *__restrict__
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < N; i += gridDim.x * blockDim.x) A[i] += B[i];
 }
 
+// Right-hand side for ONE DIRICHLET VALUE PER CONTACT SITE (kmcf_k_assemble_contacts): rhs[i] = sum over the contact
+// sites j of row i's left and right contact patterns of G_ij * V[j], G_ij by the K rule.  The scalar assembly above forms
+// (sum of G) * V from integer counts, which needs every site of a side at one value; here each entry has its own.
+// One lane per row of the compact list `crow` (the rows that have a contact entry at all: a shell one neighbour distance
+// thick, 2.6 % of the rows of a one-tile crossbar, at most a handful of entries each), so the order of addition is fixed
+// by the pattern alone -- one accumulator from 0.0, left entries in pattern order, then right entries, every step one
+// fma -- and a row's result is the same bytes on any rank count and transport.  Rows outside the list keep the 0.0 the
+// assembly with Vd = 0 left.  A value that is not finite enters as 0.0 (the solve that follows must not iterate on NaN
+// to its limit) and its site id is lowered into *bad_site by an integer atomicMin in the second loop, which walks the
+// N_left + N_right contact slots on every rank, whatever rows it owns: the host refuses the call after its one
+// synchronisation.  Nothing here writes V.
+__global__ __launch_bounds__(KMCF_BLOCK) void k_rhs_contacts_kernel(
+    int n_crow, const int *__restrict__ crow, const int *__restrict__ perm /* internal -> caller local row, or nullptr */,
+    const int *__restrict__ left_row_ptr, const int *__restrict__ left_col, const int *__restrict__ right_row_ptr,
+    const int *__restrict__ right_col, const unsigned char *__restrict__ cls, const unsigned char *__restrict__ cls_col,
+    int n_left, int n_interface, int n_right, const double *__restrict__ V /* N doubles, whole device */, double high_G,
+    double low_G, double *__restrict__ rhs_out, int *__restrict__ bad_site)
+{
+    const int tid = blockIdx.x * blockDim.x + threadIdx.x, nthreads = gridDim.x * blockDim.x;
+    for (int t = tid; t < n_crow; t += nthreads) {
+        const int r = crow[t];
+        const int ru = perm ? perm[r] : r;                // caller's local row (contact patterns)
+        const unsigned char ci = cls_col[r];
+        double acc = 0.0;
+        for (int j = left_row_ptr[ru]; j < left_row_ptr[ru + 1]; ++j) {
+            const int s = left_col[j];
+            const double v = V[s];
+            acc = fma(high_rule<false>(ci, cls[s]) ? high_G : low_G, isfinite(v) ? v : 0.0, acc);
+        }
+        for (int j = right_row_ptr[ru]; j < right_row_ptr[ru + 1]; ++j) {
+            const int s = n_left + n_interface + right_col[j];
+            const double v = V[s];
+            acc = fma(high_rule<false>(ci, cls[s]) ? high_G : low_G, isfinite(v) ? v : 0.0, acc);
+        }
+        rhs_out[r] = acc;
+    }
+    for (int t = tid; t < n_left + n_right; t += nthreads) {
+        const int s = t < n_left ? t : n_interface + t;   // right slots: [n_left + n_interface, N)
+        if (!isfinite(V[s])) atomicMin(bad_site, s);
+    }
+}
+
 // ---------------------------------------------------------------- heat
 __device__ __forceinline__ double block_sum_h(double v, double *lds4)
 {
@@ -426,6 +468,16 @@ extern "C" int kmcf_initialize_sparsity_K(kmcf_comm *c, const double *d_x, const
             if (k->h_col[j] == disp + r) { diag_pos[i] = k->K->h_row_ptr[i] + (j - k->h_row_ptr[r]); break; }
     }
     KMCF_TRY(upload(&k->d_diag_pos, diag_pos));
+    // the rows whose rhs depends on the contact values (k_rhs_contacts_kernel), in the internal order
+    {
+        std::vector<int> crow;
+        for (int i = 0; i < n_loc; ++i) {
+            const int r = perm_m.empty() ? i : perm_m[i];
+            if (k->h_left_row_ptr[r + 1] > k->h_left_row_ptr[r] || k->h_right_row_ptr[r + 1] > k->h_right_row_ptr[r]) crow.push_back(i);
+        }
+        k->n_crow = (int)crow.size();
+        KMCF_TRY(upload(&k->d_crow, crow));
+    }
     KMCF_TRY(upload(&k->d_left_row_ptr, k->h_left_row_ptr));
     KMCF_TRY(upload(&k->d_left_col, k->h_left_col));
     KMCF_TRY(upload(&k->d_right_row_ptr, k->h_right_row_ptr));
@@ -447,7 +499,7 @@ extern "C" int kmcf_kstate_destroy(kmcf_kstate *k)
     if (k->comm && k->comm->device >= 0) {
         hipSetDevice(k->comm->device);
         hipStreamSynchronize(k->comm->stream);
-        void *ptrs[] = {k->d_left_row_ptr, k->d_left_col, k->d_right_row_ptr, k->d_right_col, k->d_diag_pos, k->d_cls, k->d_cls_col,
+        void *ptrs[] = {k->d_left_row_ptr, k->d_left_col, k->d_right_row_ptr, k->d_right_col, k->d_diag_pos, k->d_crow, k->d_cls, k->d_cls_col,
                         k->d_diag, k->d_left, k->d_right, k->d_rhs, k->d_gather};
         for (void *p : ptrs)
             if (p) hipFree(p);
@@ -548,6 +600,38 @@ static int k_assemble_async(kmcf_kstate *k, const int *d_site_element, const int
     return KMCF_OK;
 }
 
+// K assembly with the contact values taken per site from d_V (N doubles): the scalar assembly with Vd = 0 -- same
+// launches, same values, diagonal and 1/diag, rhs = 0.0 in every row -- then the rows of the compact list get their sums.
+// The word that names a site whose value is not finite travels to the host behind the kernel, without a synchronisation of
+// its own: k_contacts_verdict reads it after the caller's.
+static int k_assemble_contacts_async(kmcf_kstate *k, const int *d_site_element, const int *d_site_charge,
+                                     const int *d_metals, int num_metals, const double *d_V, double high_G, double low_G)
+{
+    kmcf_comm *c = k->comm;
+    kmcf_matrix *m = k->K;
+    KMCF_TRY(k_assemble_async(k, d_site_element, d_site_charge, d_metals, num_metals, 0.0, high_G, low_G));
+    const int work = std::max(k->n_crow, k->N_left + k->N_right);
+    k_rhs_contacts_kernel<<<grid1d(work), KMCF_BLOCK, 0, c->stream>>>(
+        k->n_crow, k->d_crow, m->d_perm, k->d_left_row_ptr, k->d_left_col, k->d_right_row_ptr, k->d_right_col, k->d_cls,
+        k->d_cls_col, k->N_left, k->N_interface, k->N_right, d_V, high_G, low_G, k->d_rhs, c->d_bad_site);
+    KMCF_HIP(hipGetLastError());
+    KMCF_HIP(hipMemcpyAsync(c->h_pinned + KMCF_PINNED_BAD_SITE, c->d_bad_site, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    return KMCF_OK;
+}
+
+// After the synchronisation that follows k_assemble_contacts_async: KMCF_ERR_ARG if a contact value was not finite.
+static int k_contacts_verdict(kmcf_kstate *k, const char *who)
+{
+    kmcf_comm *c = k->comm;
+    const int bad = c->h_pinned[KMCF_PINNED_BAD_SITE];
+    if (bad == KMCF_NO_BAD_SITE) return KMCF_OK;
+    KMCF_HIP(hipMemset(c->d_bad_site, KMCF_NO_BAD_SITE & 0xff, sizeof(int)));     // (the error path may wait)
+    c->h_pinned[KMCF_PINNED_BAD_SITE] = KMCF_NO_BAD_SITE;
+    KMCF_CHECK(false, KMCF_ERR_ARG, "%s: the contact value of site %d is not finite (%s contact slot %d)", who, bad,
+               bad < k->N_left ? "left" : "right", bad < k->N_left ? bad : bad - k->N_left - k->N_interface);
+    return KMCF_ERR_ARG;
+}
+
 __global__ __launch_bounds__(KMCF_BLOCK) void cb_finish_kernel(double *__restrict__ cb, int N, int n_left, int n_interface,
                                                                double Vd, double eV_to_J)
 {
@@ -619,6 +703,21 @@ extern "C" int kmcf_k_assemble(kmcf_kstate *k, const int *d_site_element, const 
     return KMCF_OK;
 }
 
+extern "C" int kmcf_k_assemble_contacts(kmcf_kstate *k, const int *d_site_element, const int *d_site_charge,
+                                        const int *d_metals, int num_metals, const double *d_site_potential,
+                                        double high_G, double low_G)
+{
+    KMCF_CHECK(k, KMCF_ERR_ARG, "kmcf_k_assemble_contacts: k is NULL");
+    KMCF_CHECK(d_site_element, KMCF_ERR_ARG, "kmcf_k_assemble_contacts: d_site_element is NULL");
+    KMCF_CHECK(d_site_charge, KMCF_ERR_ARG, "kmcf_k_assemble_contacts: d_site_charge is NULL");
+    KMCF_CHECK(d_metals, KMCF_ERR_ARG, "kmcf_k_assemble_contacts: d_metals is NULL");
+    KMCF_CHECK(d_site_potential, KMCF_ERR_ARG, "kmcf_k_assemble_contacts: d_site_potential is NULL");
+    KMCF_TRY(kmcf_enter(k->comm));
+    KMCF_TRY(k_assemble_contacts_async(k, d_site_element, d_site_charge, d_metals, num_metals, d_site_potential, high_G, low_G));
+    KMCF_HIP(hipStreamSynchronize(k->comm->stream));
+    return k_contacts_verdict(k, "kmcf_k_assemble_contacts");
+}
+
 extern "C" int kmcf_k_get_vectors(const kmcf_kstate *k, double *h_diag, double *h_dinv, double *h_rhs,
                                   double *h_left, double *h_right)
 {
@@ -644,23 +743,21 @@ extern "C" int kmcf_k_get_vectors(const kmcf_kstate *k, double *h_diag, double *
     return KMCF_OK;
 }
 
-extern "C" int kmcf_background_potential_sparse(kmcf_kstate *k, const int *d_site_element, const int *d_site_charge,
-                                                const int *d_metals, int num_metals, double *d_site_potential_boundary,
-                                                int N, int N_left_tot, int N_right_tot, double Vd,
-                                                double high_G, double low_G, kmcf_solve_stats_t *stats)
+// The K solve of both entry points.  per_site: the contact slots of d_site_potential_boundary are the boundary condition
+// (kmcf_background_potential_sparse_contacts); otherwise Vd is (kmcf_background_potential_sparse: what it always launched).
+static int k_potential_solve(kmcf_kstate *k, const int *d_site_element, const int *d_site_charge, const int *d_metals,
+                             int num_metals, double *d_site_potential_boundary, int N_left_tot, bool per_site, double Vd,
+                             double high_G, double low_G, kmcf_solve_stats_t *stats, const char *who)
 {
-    KMCF_CHECK(k && d_site_element && d_site_charge && d_metals && d_site_potential_boundary, KMCF_ERR_ARG,
-               "kmcf_background_potential_sparse: null argument");
-    KMCF_CHECK(N == k->N && N_left_tot == k->N_left && N_right_tot == k->N_right, KMCF_ERR_ARG,
-               "kmcf_background_potential_sparse: N/N_left/N_right (%d,%d,%d) differ from the pattern's (%d,%d,%d)",
-               N, N_left_tot, N_right_tot, k->N, k->N_left, k->N_right);
     kmcf_comm *c = k->comm;
     kmcf_matrix *m = k->K;
-    KMCF_CHECK(c->connected, KMCF_ERR_COMM, "kmcf_background_potential_sparse: communicator not connected");
     KMCF_TRY(kmcf_enter(c));
     hipEvent_t a0 = c->ev_a0, a1 = c->ev_a1;   // owned by the communicator: nothing to create or leak per call
     KMCF_HIP(hipEventRecord(a0, c->stream));
-    KMCF_TRY(k_assemble_async(k, d_site_element, d_site_charge, d_metals, num_metals, Vd, high_G, low_G));
+    if (per_site)
+        KMCF_TRY(k_assemble_contacts_async(k, d_site_element, d_site_charge, d_metals, num_metals, d_site_potential_boundary, high_G, low_G));
+    else
+        KMCF_TRY(k_assemble_async(k, d_site_element, d_site_charge, d_metals, num_metals, Vd, high_G, low_G));
     KMCF_HIP(hipEventRecord(a1, c->stream));
     const size_t bytes = (size_t)m->n_loc * sizeof(double);
     // the initial guess is the current potential inside the device, solved in place (:861)
@@ -681,12 +778,47 @@ extern "C" int kmcf_background_potential_sparse(kmcf_kstate *k, const int *d_sit
     KMCF_TRY(rc_solve);
     if (!direct) KMCF_TRY(kmcf_vec_out(m, v_soln, m->d_x));
     KMCF_HIP(hipStreamSynchronize(c->stream));
+    if (per_site) KMCF_TRY(k_contacts_verdict(k, who));          // (the word arrived with the statistics: no wait of its own)
     if (stats) {
         float ms = 0.f;
         KMCF_HIP(hipEventElapsedTime(&ms, a0, a1));
         stats->ms_assembly = ms;
     }
     return KMCF_OK;
+}
+
+extern "C" int kmcf_background_potential_sparse(kmcf_kstate *k, const int *d_site_element, const int *d_site_charge,
+                                                const int *d_metals, int num_metals, double *d_site_potential_boundary,
+                                                int N, int N_left_tot, int N_right_tot, double Vd,
+                                                double high_G, double low_G, kmcf_solve_stats_t *stats)
+{
+    KMCF_CHECK(k && d_site_element && d_site_charge && d_metals && d_site_potential_boundary, KMCF_ERR_ARG,
+               "kmcf_background_potential_sparse: null argument");
+    KMCF_CHECK(N == k->N && N_left_tot == k->N_left && N_right_tot == k->N_right, KMCF_ERR_ARG,
+               "kmcf_background_potential_sparse: N/N_left/N_right (%d,%d,%d) differ from the pattern's (%d,%d,%d)",
+               N, N_left_tot, N_right_tot, k->N, k->N_left, k->N_right);
+    KMCF_CHECK(k->comm->connected, KMCF_ERR_COMM, "kmcf_background_potential_sparse: communicator not connected");
+    return k_potential_solve(k, d_site_element, d_site_charge, d_metals, num_metals, d_site_potential_boundary, N_left_tot, false,
+                             Vd, high_G, low_G, stats, "kmcf_background_potential_sparse");
+}
+
+extern "C" int kmcf_background_potential_sparse_contacts(kmcf_kstate *k, const int *d_site_element, const int *d_site_charge,
+                                                         const int *d_metals, int num_metals, double *d_site_potential_boundary,
+                                                         int N, int N_left_tot, int N_right_tot,
+                                                         double high_G, double low_G, kmcf_solve_stats_t *stats)
+{
+    const char *who = "kmcf_background_potential_sparse_contacts";
+    KMCF_CHECK(k, KMCF_ERR_ARG, "%s: k is NULL", who);
+    KMCF_CHECK(d_site_element, KMCF_ERR_ARG, "%s: d_site_element is NULL", who);
+    KMCF_CHECK(d_site_charge, KMCF_ERR_ARG, "%s: d_site_charge is NULL", who);
+    KMCF_CHECK(d_metals, KMCF_ERR_ARG, "%s: d_metals is NULL", who);
+    KMCF_CHECK(d_site_potential_boundary, KMCF_ERR_ARG, "%s: d_site_potential_boundary is NULL", who);
+    KMCF_CHECK(N == k->N && N_left_tot == k->N_left && N_right_tot == k->N_right, KMCF_ERR_ARG,
+               "%s: N/N_left_tot/N_right_tot (%d,%d,%d) differ from the pattern's (%d,%d,%d)", who, N, N_left_tot, N_right_tot,
+               k->N, k->N_left, k->N_right);
+    KMCF_CHECK(k->comm->connected, KMCF_ERR_COMM, "%s: communicator not connected", who);
+    return k_potential_solve(k, d_site_element, d_site_charge, d_metals, num_metals, d_site_potential_boundary, N_left_tot, true,
+                             0.0, high_G, low_G, stats, who);
 }
 
 extern "C" int kmcf_sum_and_gather_potential(kmcf_kstate *k, double *d_site_potential_boundary,

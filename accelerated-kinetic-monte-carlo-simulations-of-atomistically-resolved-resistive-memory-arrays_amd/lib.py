@@ -146,6 +146,9 @@ SIGNATURES = {
     "kmcf_k_get_vectors": (C.c_int, [_P, _DP, _DP, _DP, _DP, _DP]),
     "kmcf_background_potential_sparse": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int,
                                                    C.c_double, C.c_double, C.c_double, C.POINTER(SolveStats)]),
+    "kmcf_k_assemble_contacts": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, C.c_double, C.c_double]),
+    "kmcf_background_potential_sparse_contacts": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int,
+                                                            C.c_double, C.c_double, C.POINTER(SolveStats)]),
     "kmcf_sum_and_gather_potential": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _IP, _IP]),
     "kmcf_update_CB_edge_sparse": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int,
                                              C.c_double, C.c_double, C.c_double, C.POINTER(SolveStats)]),

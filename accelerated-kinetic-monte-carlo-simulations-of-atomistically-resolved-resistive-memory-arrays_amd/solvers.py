@@ -255,6 +255,21 @@ def background_potential_gpu_sparse(gpubuf, N, N_left_tot, N_right_tot, Vd, pbc,
     return st.as_dict()
 
 
+def background_potential_gpu_sparse_contacts(gpubuf, N, N_left_tot, N_right_tot, high_G, low_G, num_metals):
+    """kmcf_background_potential_sparse_contacts: the K solve with one Dirichlet value per contact site.  The contact
+    slots [0, N_left_tot) and [N - N_right_tot, N) of gpubuf.site_potential_boundary are the boundary condition (fill
+    them once, e.g. from structure.bias_scheme; they are read, never written), its interface slice is the start guess
+    and receives the solution.  Returns the solve statistics."""
+    lib = _L.load()
+    st = _L.SolveStats()
+    _L.check(lib.kmcf_background_potential_sparse_contacts(gpubuf.K_distributed, _ptr(gpubuf.site_element),
+                                                           _ptr(gpubuf.site_charge), _ptr(gpubuf.metal_types),
+                                                           int(num_metals), _ptr(gpubuf.site_potential_boundary), int(N),
+                                                           int(N_left_tot), int(N_right_tot), float(high_G), float(low_G),
+                                                           C.byref(st)), "kmcf_background_potential_sparse_contacts")
+    return st.as_dict()
+
+
 def update_CB_edge_gpu_sparse(gpubuf, N, N_left_tot, N_right_tot, Vd, pbc, high_G, low_G, nn_dist, num_metals):
     """update_CB_edge_gpu_sparse (gpu_solvers.h:143; src/potential_solver_gpu.cu:673-772): writes
     gpubuf.site_CB_edge [J]."""
@@ -632,6 +647,15 @@ def k_assemble(gpubuf, Vd, high_G, low_G):
     _L.check(lib.kmcf_k_assemble(gpubuf.K_distributed, _ptr(gpubuf.site_element), _ptr(gpubuf.site_charge),
                                  _ptr(gpubuf.metal_types), gpubuf.num_metal_types_, float(Vd), float(high_G),
                                  float(low_G)), "kmcf_k_assemble")
+
+
+def k_assemble_contacts(gpubuf, site_potential, high_G, low_G):
+    """kmcf_k_assemble_contacts: K assembly whose right-hand side takes one Dirichlet value per contact site from the
+    contact slots of site_potential (N doubles on the device, layout of site_potential_boundary)."""
+    lib = _L.load()
+    _L.check(lib.kmcf_k_assemble_contacts(gpubuf.K_distributed, _ptr(gpubuf.site_element), _ptr(gpubuf.site_charge),
+                                          _ptr(gpubuf.metal_types), gpubuf.num_metal_types_, _ptr(site_potential),
+                                          float(high_G), float(low_G)), "kmcf_k_assemble_contacts")
 
 
 def k_pattern(gpubuf, which=0):

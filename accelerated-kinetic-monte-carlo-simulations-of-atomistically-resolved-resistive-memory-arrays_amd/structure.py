@@ -12,6 +12,9 @@
   dist_iterative_test/main_test_cg.cpp:197-201).  Site order "bwmin": contacts'
   outer layers first/last, everything else sorted along y (the reference runs the
   40 nm device from crossbar_40_bwmin.xyz).
+* crossbar_lines() / line_bias() / bias_scheme(): which word line or bit line every contact site of a carved crossbar
+  belongs to, and the per-site contact potentials of the array bias schemes (all cells selected, V/2, V/3) for
+  solvers.background_potential_gpu_sparse_contacts.
 * xyz / parameters.txt readers for users who have their own structure files
   (format of src/utils.cpp:72-97 and src/input_parser.cpp).
 """
@@ -195,3 +198,72 @@ def synth_crossbar_40nm(tiles=8, fill=0.52, n_lines=2, vacancy_fraction=0.05, se
 def synth_small(tiles=1, seed=1, order="bwmin", fill=1.0):
     """Small synthetic device of the same family (for quick tests): `tiles` x `tiles` cells, uncarved."""
     return synth_crossbar_40nm(tiles=tiles, seed=seed, carve=fill < 1.0, fill=fill, order=order)
+
+
+# --------------------------------------------------------------------------
+# per-line bias of a carved crossbar
+# --------------------------------------------------------------------------
+
+def _line_index(coord, length, n_lines):
+    """index of the stripe period (see _stripes) that holds `coord`"""
+    return np.clip(np.floor(np.asarray(coord) / (length / n_lines)), 0, n_lines - 1).astype(np.int32)
+
+
+def crossbar_lines(d, n_lines=2, fill=0.52):
+    """The lines of a crossbar carved by synth_crossbar_40nm(n_lines=n_lines, fill=fill), by the same stripe rule:
+    (word_of_contact[N_contact]: word line (stripe in z) of every left contact site,
+     bit_of_contact[N_contact]: bit line (stripe in y) of every right contact site,
+     cell_of_site[N]: word * n_lines + bit for the sites under a crossing of a word and a bit stripe, -1 elsewhere)."""
+    N, NL = d["N"], d["N_contact"]
+    L = float(d["lattice"][1])
+    y, z = d["xyz"][:, 1], d["xyz"][:, 2]
+    on_word, on_bit = _stripes(z, L, n_lines, fill), _stripes(y, L, n_lines, fill)
+    if not (on_word[:NL].all() and on_bit[N - NL:].all()):
+        raise ValueError("crossbar_lines: a contact site lies between the stripes: the device was not carved with n_lines=%d, "
+                         "fill=%g" % (n_lines, fill))
+    word, bit = _line_index(z, L, n_lines), _line_index(y, L, n_lines)
+    cell = np.where(on_word & on_bit, word * n_lines + bit, -1).astype(np.int32)
+    return word[:NL].copy(), bit[N - NL:].copy(), cell
+
+
+def line_bias(d, word_V, bit_V, fill=0.52):
+    """N-vector for gpubuf.site_potential_boundary: zero in the interface, every left contact slot at its word line's
+    value, every right contact slot at its bit line's (len(word_V) == len(bit_V) == n_lines)."""
+    word_V, bit_V = np.asarray(word_V, np.float64), np.asarray(bit_V, np.float64)
+    if word_V.ndim != 1 or word_V.shape != bit_V.shape:
+        raise ValueError("line_bias: word_V and bit_V hold one value per line each")
+    word, bit, _ = crossbar_lines(d, len(word_V), fill)
+    NL = d["N_contact"]
+    v = np.zeros(d["N"])
+    v[:NL] = word_V[word]
+    v[d["N"] - NL:] = bit_V[bit]
+    return v
+
+
+def scheme_line_voltages(scheme, select, V, n_lines=2):
+    """(word_V, bit_V) of an array bias scheme in K's sign convention (left contact = word lines = -, right = bit lines
+    = +); a cell sees bit - word.
+      "all":   every word line -V/2, every bit line +V/2: every cell at V (the scalar call)
+      "half":  selected word -V/2, selected bit +V/2, unselected lines 0: half-selected cells at V/2
+      "third": selected word -V/2, selected bit +V/2, unselected words +V/6, unselected bits -V/6: every other cell at
+               +-V/3"""
+    w, b = select
+    if not (0 <= w < n_lines and 0 <= b < n_lines):
+        raise ValueError("select=(%d, %d): lines are 0..%d" % (w, b, n_lines - 1))
+    if scheme == "all":
+        return np.full(n_lines, -V / 2), np.full(n_lines, V / 2)
+    if scheme == "half":
+        word_V, bit_V = np.zeros(n_lines), np.zeros(n_lines)
+    elif scheme == "third":
+        word_V, bit_V = np.full(n_lines, V / 6), np.full(n_lines, -V / 6)
+    else:
+        raise ValueError("scheme %r: one of all | half | third" % (scheme,))
+    word_V[w], bit_V[b] = -V / 2, V / 2
+    return word_V, bit_V
+
+
+def bias_scheme(d, scheme, select=(0, 0), V=None, n_lines=2, fill=0.52):
+    """line_bias of scheme_line_voltages(scheme, select, V): the N-vector whose contact slots drive the selected cell at
+    V (default d["Vd"]) and its neighbours by the scheme."""
+    word_V, bit_V = scheme_line_voltages(scheme, select, d["Vd"] if V is None else float(V), n_lines)
+    return line_bias(d, word_V, bit_V, fill)

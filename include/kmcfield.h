@@ -322,6 +322,48 @@ int kmcf_background_potential_sparse(kmcf_kstate *k, const int *d_site_element, 
                                      int N, int N_left_tot, int N_right_tot, double Vd,
                                      double high_G, double low_G, kmcf_solve_stats_t *stats);
 
+/* Per-line bias: one Dirichlet value per contact site instead of one scalar Vd.
+ *
+ * K assembly with one Dirichlet value per contact site.  d_site_potential: N doubles, whole
+ * device, same layout as site_potential_boundary; only its contact slots [0, N_left) and
+ * [N - N_right, N) are read, and nothing is written to it.  Values, diagonal and 1/diag are
+ * those of kmcf_k_assemble (they do not depend on the bias); rhs[i] = sum over the contact
+ * sites j in row i's left and right contact patterns (kmcf_kstate_pattern, which = 1, 2) of
+ * G_ij * V[j], G_ij by the K rule (high_G iff both sites are metals or both uncharged
+ * vacancies).  Order of addition, part of the contract: one accumulator per row starting at
+ * 0.0, left entries in pattern order, then right entries in pattern order, each step one
+ * fused multiply-add.  The result depends on the input alone: two calls give the same bytes,
+ * and a row's rhs is the same bytes whatever the rank count and transport.  A row without
+ * contact entries gets exactly 0.0.  With every left slot at -Vd/2 and every right slot at
+ * +Vd/2 the system is that of kmcf_k_assemble(Vd) up to the rounding of the sums.
+ * KMCF_ERR_ARG before anything needs a device: a NULL argument (kmcf_last_error names it).
+ * KMCF_ERR_ARG after the call's one synchronisation: a contact value is not finite;
+ * kmcf_last_error names the smallest such site id.  The contact slots are untouched then,
+ * and the assembled rhs is unspecified (call again with finite values). */
+int kmcf_k_assemble_contacts(kmcf_kstate *k, const int *d_site_element, const int *d_site_charge,
+                             const int *d_metals, int num_metals, const double *d_site_potential,
+                             double high_G, double low_G);
+
+/* kmcf_background_potential_sparse with the contact values taken from the array itself: the
+ * contact slots of d_site_potential_boundary are the boundary condition (read, never
+ * written), its interface slice is the start guess and receives the solution (this rank's
+ * rows, as in the scalar call; kmcf_sum_and_gather_potential replicates them).  Same
+ * tolerance (1e-14 * N_interface), same max_it, same solver paths (register-resident launch
+ * or kernel loop, either recurrence, one rank or a group).  On a group every rank passes its
+ * own whole-device array with identical contact slots.  Downstream nothing changes:
+ * kmcf_sum_and_gather_potential adds the whole array, contact slots included, into
+ * site_potential_charge.  The band-edge and current solves still take a scalar Vd.
+ * KMCF_ERR_ARG before anything needs a device (kmcf_last_error names the argument): NULL
+ * argument, N / N_left_tot / N_right_tot other than the pattern's.  KMCF_ERR_COMM:
+ * communicator not connected.  KMCF_ERR_ARG at the call's final synchronisation (no extra
+ * host round trip on the good path): a contact value is not finite, kmcf_last_error names
+ * the smallest such site id; the contact slots are untouched and the interface slice is
+ * unspecified.  On a group every rank returns the same verdict. */
+int kmcf_background_potential_sparse_contacts(kmcf_kstate *k, const int *d_site_element, const int *d_site_charge,
+                                              const int *d_metals, int num_metals, double *d_site_potential_boundary,
+                                              int N, int N_left_tot, int N_right_tot,
+                                              double high_G, double low_G, kmcf_solve_stats_t *stats);
+
 /* update_CB_edge_gpu_sparse (src/potential_solver_gpu.cu:575-772): Laplace solve for the
  * conduction-band edge on the K pattern: G = high_G if EITHER site is a metal (:289-319),
  * contacts at +Vd/2 (left) / -Vd/2 (right), solve_sparse_CG_Jacobi (tol 1e-14), boundary

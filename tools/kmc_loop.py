@@ -4,7 +4,7 @@ boundary (K) solve, pairwise term, sum/gather, KMC events -- with the per-module
 prints into output<size>_<rank>.txt ("Z - calculation time - ...").
 
     python tools/kmc_loop.py [--workload 5nm|40nm|conducting] [--steps 6] [--T 300] [--current] [--rate-mode bg|ekin|site]
-                             [--clusters] [--current-map]
+                             [--clusters] [--current-map] [--scheme all|half|third --select W,B]
 
 --current adds the electro-thermal stages after the potential and before the events: conduction-band edge, current
 solve with heating (site_power), local heat solve (site_temperature); --rate-mode ekin | site lets the event rates read
@@ -14,7 +14,12 @@ tests/test_gpu_conducting.py, whose current is a property of the device.  --clus
 current solve; the step line gains `clusters <ms> (<vacancy clusters> vac, largest <sites>, bridging <filaments>)`, the
 time in milliseconds of device time.  --current-map (with --current) runs the site-resolved current map (kmcf_current_map)
 after the power update of every step: the step line gains `current map <ms> (tunnel share <sum_tunnel / sum_through>, max
-<max_through> at site <max_site>)`, the time again in milliseconds of device time.
+<max_through> at site <max_site>)`, the time again in milliseconds of device time.  --scheme all | half | third with --select W,B
+(the synthetic crossbars only) drives the array per line instead of with one scalar Vd: the contact slots of the potential
+array are filled once by structure.bias_scheme (selected word line -Vd/2, selected bit line +Vd/2, the others by the scheme),
+the boundary solve is kmcf_background_potential_sparse_contacts, and the step line gains `events per cell [c0 c1 ...]`: the
+events of the step whose first site lies under crossing word * n_lines + bit.  The band-edge and current stages of --current
+still see the scalar Vd.
 """
 import argparse
 import os
@@ -43,7 +48,12 @@ def main():
                     help="conductive cluster analysis after every charge update: vacancy clusters, the largest, bridging filaments")
     ap.add_argument("--current-map", action="store_true",
                     help="site-resolved current map after every power update (needs --current): tunnel share, the busiest site")
+    ap.add_argument("--scheme", default=None, choices=["all", "half", "third"],
+                    help="per-line bias of the crossbar (synthetic workloads): all cells selected | V/2 scheme | V/3 scheme")
+    ap.add_argument("--select", default="0,0", help="W,B: the selected word line and bit line of --scheme")
     a = ap.parse_args()
+    if a.scheme and a.workload == "5nm":
+        ap.error("--scheme needs a crossbar with lines: --workload 40nm or conducting")
     if a.current_map and not a.current:
         ap.error("--current-map needs --current (the map reads the potentials of the current solve)")
     if a.rate_mode != "bg" and not a.current:
@@ -79,6 +89,16 @@ def main():
         high_G_T, loop_G, G0 = 1e5 * d["high_G"], 1e7 * d["high_G"], 2 * 3.8612e-5 * 1e-5
         side = float(d["lattice"][1]) * 1e-10
         heat = S.heat_params(background_temp=a.T, A=side * side, cg_tolerance=1e-12, cg_max_iterations=50000)
+    cell_of_site = None
+    if a.scheme:
+        try:
+            select = tuple(int(t) for t in a.select.split(","))
+            assert len(select) == 2
+            contacts = km.structure.bias_scheme(d, a.scheme, select=select)
+        except (AssertionError, ValueError) as e:
+            ap.error("--select %s: %s" % (a.select, str(e) or "W,B expected"))
+        cell_of_site = km.structure.crossbar_lines(d)[2]
+        buf.site_potential_boundary.copy_(torch.as_tensor(contacts))      # once: the solve reads the slots, never writes them
     comm.sync()
     print("init [s] %.3f  (sites %d)" % (time.perf_counter() - t0, N))
     kmc_time = 0.0
@@ -99,8 +119,12 @@ def main():
             cs = S.conductive_clusters(comm, buf, NL, NL, labels=False)["stats"]
             clusters = " | clusters %.3f (%d vac, largest %d, bridging %d)" % (cs["ms"], cs["n_vacancy_clusters"],
                                                                                   cs["largest_vacancy"], cs["n_bridging"])
-        tb, st = timed(lambda: S.background_potential_gpu_sparse(buf, N, NL, NL, d["Vd"], d["pbc"], d["high_G"],
-                                                                 d["low_G"], d["nn_dist"], len(d["metals"]), step))
+        if a.scheme:
+            tb, st = timed(lambda: S.background_potential_gpu_sparse_contacts(buf, N, NL, NL, d["high_G"], d["low_G"],
+                                                                              len(d["metals"])))
+        else:
+            tb, st = timed(lambda: S.background_potential_gpu_sparse(buf, N, NL, NL, d["Vd"], d["pbc"], d["high_G"],
+                                                                     d["low_G"], d["nn_dist"], len(d["metals"]), step))
         tp, _ = timed(lambda: S.poisson_gridless_gpu(buf, comm))
         tg, _ = timed(lambda: S.sum_and_gather_potential(buf, NL, comm))
         thermal = {}
@@ -123,6 +147,9 @@ def main():
                                                       buf.site_charge, rng, layers, max_events=a.max_events,
                                                       return_log=True, **thermal))
         kmc_time += ev[0]
+        if a.scheme:
+            cells = cell_of_site[ev[2][:, 0]]
+            clusters += " | events per cell [%s]" % " ".join(str(c) for c in np.bincount(cells[cells >= 0], minlength=cell_of_site.max() + 1))
         if a.event_stats and ev[1] > 0:
             # where the selection walk lands: how often a recently used supertile (128 consecutive rows of the event list)
             # is selected again -- what a small cache of row sums in LDS would hit
