@@ -14,6 +14,8 @@
 //   7    touch bits of the vacancy clusters from the metal clusters next to them (either direction)     [walks rows]
 //   8-10 compact the roots into the table (ascending root = scan order) and count the summaries
 // Two launches walk neighbour rows whatever the input: stats->passes = 2.
+// kmcf_clusters_enqueue is the pass without the read-back: kmcf_conductive_clusters calls it with the summaries, the
+// filament gap analysis (kmcf_gap.hip) without launches 8-10, and reads class, label and touch where they lie.
 //
 // Hooking always puts the LARGER root under the SMALLER: parent[v] <= v at all times, every value ever stored in
 // parent[v] is a site of v's component, every walk strictly decreases, and the final root is the minimum id.
@@ -454,6 +456,51 @@ int cl_workspace(kmcf_comm *c, int N, int table_entries)
 
 }  // namespace
 
+int kmcf_clusters_enqueue(kmcf_comm *c, int N, int nn, const int *d_neigh_idx, const int *d_site_element,
+                          const int *d_site_charge, const int *d_metals, int num_metals, const double *d_x, int N_left_tot,
+                          int N_right_tot, int *d_site_label, bool summaries, int table_cap, kmcf_cluster_dev *out)
+{
+    const int cap = table_cap;
+    KMCF_TRY(cl_workspace(c, N, cap));
+    kmcf_cluster_ws *w = c->cl_ws;
+    hipStream_t st = c->stream;
+    int *label = d_site_label ? d_site_label : w->d_label;
+    const int nb = (N + CL_TILE - 1) / CL_TILE;                   // tiles of the scans
+    const int *n_members = w->d_msum + nb;
+    const bool wide = nn > 8;                                     // 16 lanes per row, 4 for short rows
+    const int per_block = KMCF_BLOCK / (wide ? 16 : 4);
+    int64_t row_grid = ((int64_t)N + per_block - 1) / per_block;  // an upper bound: the kernels stride over the members
+    if (row_grid > 16384) row_grid = 16384;
+    int64_t red_grid = ((int64_t)N + KMCF_BLOCK - 1) / KMCF_BLOCK;
+    const int site_grid = (int)red_grid;
+    if (red_grid > 512) red_grid = 512;                           // two blocks per CU: few sets of atomics per hot label
+
+    cl_classify_kernel<<<nb, KMCF_BLOCK, 0, st>>>(N, d_site_element, d_site_charge, d_metals, num_metals, w->d_cls, w->d_parent,
+                                                 w->d_msum, w->d_stats);
+    cl_scan_kernel<<<1, KMCF_BLOCK, 0, st>>>(nb, w->d_msum);
+    cl_member_scatter_kernel<<<nb, KMCF_BLOCK, 0, st>>>(N, w->d_cls, w->d_msum, w->d_members);
+    if (wide)
+        cl_hook_kernel<16><<<(int)row_grid, KMCF_BLOCK, 0, st>>>(N, nn, d_neigh_idx, w->d_cls, w->d_members, n_members, w->d_parent);
+    else
+        cl_hook_kernel<4><<<(int)row_grid, KMCF_BLOCK, 0, st>>>(N, nn, d_neigh_idx, w->d_cls, w->d_members, n_members, w->d_parent);
+    cl_flatten_kernel<<<site_grid, KMCF_BLOCK, 0, st>>>(N, w->d_cls, w->d_parent, label, w->d_size, w->d_touch, w->d_xmin, w->d_xmax);
+    cl_reduce_kernel<<<(int)red_grid, KMCF_BLOCK, 0, st>>>(N, N_left_tot, N_right_tot, w->d_cls, w->d_members, n_members, label, d_x,
+                                                          w->d_size, w->d_touch, w->d_xmin, w->d_xmax);
+    if (wide)
+        cl_touch_kernel<16><<<(int)row_grid, KMCF_BLOCK, 0, st>>>(N, nn, d_neigh_idx, w->d_cls, w->d_members, n_members, label, w->d_touch);
+    else
+        cl_touch_kernel<4><<<(int)row_grid, KMCF_BLOCK, 0, st>>>(N, nn, d_neigh_idx, w->d_cls, w->d_members, n_members, label, w->d_touch);
+    if (summaries) {
+        cl_root_count_kernel<<<nb, KMCF_BLOCK, 0, st>>>(N, w->d_cls, label, w->d_size, w->d_touch, w->d_rsum, w->d_stats);
+        cl_scan_kernel<<<1, KMCF_BLOCK, 0, st>>>(nb, w->d_rsum);
+        cl_root_scatter_kernel<<<nb, KMCF_BLOCK, 0, st>>>(N, nb, w->d_cls, label, w->d_size, w->d_touch, w->d_xmin, w->d_xmax, w->d_rsum,
+                                                         n_members, w->d_table, cap, w->d_stats);
+    }
+    KMCF_HIP(hipGetLastError());
+    if (out) { out->cls = w->d_cls; out->label = label; out->touch = w->d_touch; }
+    return KMCF_OK;
+}
+
 extern "C" int kmcf_conductive_clusters(kmcf_comm *c, int N, int nn, const int *d_neigh_idx, const int *d_site_element,
                                         const int *d_site_charge, const int *d_metals, int num_metals, const double *d_x,
                                         int N_left_tot, int N_right_tot, int *d_site_label, kmcf_cluster_t *h_clusters,
@@ -478,41 +525,11 @@ extern "C" int kmcf_conductive_clusters(kmcf_comm *c, int N, int nn, const int *
     KMCF_CHECK(c->device >= 0, KMCF_ERR_STATE, "%s: host-only communicator", what);
     KMCF_TRY(kmcf_enter(c));
     const int cap = h_clusters ? (max_clusters < N ? max_clusters : N) : 0;
-    KMCF_TRY(cl_workspace(c, N, cap));
-    kmcf_cluster_ws *w = c->cl_ws;
     hipStream_t st = c->stream;
-    int *label = d_site_label ? d_site_label : w->d_label;
-    const int nb = (N + CL_TILE - 1) / CL_TILE;                   // tiles of the scans
-    const int *n_members = w->d_msum + nb;
-    const bool wide = nn > 8;                                     // 16 lanes per row, 4 for short rows
-    const int per_block = KMCF_BLOCK / (wide ? 16 : 4);
-    int64_t row_grid = ((int64_t)N + per_block - 1) / per_block;  // an upper bound: the kernels stride over the members
-    if (row_grid > 16384) row_grid = 16384;
-    int64_t red_grid = ((int64_t)N + KMCF_BLOCK - 1) / KMCF_BLOCK;
-    const int site_grid = (int)red_grid;
-    if (red_grid > 512) red_grid = 512;                           // two blocks per CU: few sets of atomics per hot label
-
     KMCF_HIP(hipEventRecord(c->ev_t0, st));
-    cl_classify_kernel<<<nb, KMCF_BLOCK, 0, st>>>(N, d_site_element, d_site_charge, d_metals, num_metals, w->d_cls, w->d_parent,
-                                                 w->d_msum, w->d_stats);
-    cl_scan_kernel<<<1, KMCF_BLOCK, 0, st>>>(nb, w->d_msum);
-    cl_member_scatter_kernel<<<nb, KMCF_BLOCK, 0, st>>>(N, w->d_cls, w->d_msum, w->d_members);
-    if (wide)
-        cl_hook_kernel<16><<<(int)row_grid, KMCF_BLOCK, 0, st>>>(N, nn, d_neigh_idx, w->d_cls, w->d_members, n_members, w->d_parent);
-    else
-        cl_hook_kernel<4><<<(int)row_grid, KMCF_BLOCK, 0, st>>>(N, nn, d_neigh_idx, w->d_cls, w->d_members, n_members, w->d_parent);
-    cl_flatten_kernel<<<site_grid, KMCF_BLOCK, 0, st>>>(N, w->d_cls, w->d_parent, label, w->d_size, w->d_touch, w->d_xmin, w->d_xmax);
-    cl_reduce_kernel<<<(int)red_grid, KMCF_BLOCK, 0, st>>>(N, N_left_tot, N_right_tot, w->d_cls, w->d_members, n_members, label, d_x,
-                                                          w->d_size, w->d_touch, w->d_xmin, w->d_xmax);
-    if (wide)
-        cl_touch_kernel<16><<<(int)row_grid, KMCF_BLOCK, 0, st>>>(N, nn, d_neigh_idx, w->d_cls, w->d_members, n_members, label, w->d_touch);
-    else
-        cl_touch_kernel<4><<<(int)row_grid, KMCF_BLOCK, 0, st>>>(N, nn, d_neigh_idx, w->d_cls, w->d_members, n_members, label, w->d_touch);
-    cl_root_count_kernel<<<nb, KMCF_BLOCK, 0, st>>>(N, w->d_cls, label, w->d_size, w->d_touch, w->d_rsum, w->d_stats);
-    cl_scan_kernel<<<1, KMCF_BLOCK, 0, st>>>(nb, w->d_rsum);
-    cl_root_scatter_kernel<<<nb, KMCF_BLOCK, 0, st>>>(N, nb, w->d_cls, label, w->d_size, w->d_touch, w->d_xmin, w->d_xmax, w->d_rsum,
-                                                     n_members, w->d_table, cap, w->d_stats);
-    KMCF_HIP(hipGetLastError());
+    KMCF_TRY(kmcf_clusters_enqueue(c, N, nn, d_neigh_idx, d_site_element, d_site_charge, d_metals, num_metals, d_x, N_left_tot,
+                                   N_right_tot, d_site_label, true, cap, nullptr));
+    kmcf_cluster_ws *w = c->cl_ws;
     int *h = c->h_pinned;
     KMCF_HIP(hipMemcpyAsync(h, w->d_stats, CL_STAT_WORDS * sizeof(int), hipMemcpyDeviceToHost, st));
     KMCF_HIP(hipEventRecord(c->ev_t1, st));

@@ -1,0 +1,612 @@
+// Filament gap analysis: nearest approach of two site sets per gap cell (kmcf_site_set_gap), and the same with the sets
+// derived from the device state -- the conductive matter attached to the left / right electrode (kmcf_filament_gap).
+//
+// The reference has no counterpart.  Definitions (sets, cells, pairs, tie-break, profile): include/kmcfield.h and
+// DESIGN.md, "Filament gap".  The side of a site is the touch word of its conductive cluster (kmcf_clusters.hip).
+//
+// Launches, all on the compute stream (kmcf_filament_gap: behind the cluster pass and one kernel that forms the sides):
+//   1    clear the per-cell words
+//   2    counts of the sides per gap cell and for the device                       [integer atomics, one set per wave and cell]
+//   3-5  compact, per INDEX cell (the cells of kmcf_compute_cutoff_list), the B members with their coordinates and gap
+//        cell, and the A members: flag count / scan / scatter as in kmcf_pairwise.hip, on scratch of this file's own
+//        (kmcf_poisson_gridless keeps its lists)
+//   6    search: 16 lanes per A site walk the contiguous runs of the 27 surrounding index cells (r_max <= cell edge),
+//        every lane keeps its lexicographic minimum (d2, b); the group's minimum is stored per A site and lowers the gap
+//        cell's best d2 with a 64-bit integer atomicMin on the bit pattern (non-negative doubles order as integers)
+//   7    among the A sites that attain their cell's d2, the smallest packed (a << 32 | b) wins (atomicMin again)
+//   8    the records; 9 (kmcf_filament_gap with a profile) the histogram
+//
+// Pruning: before a run of index cells is walked, its distance from the A site (a lower bound, shortened by a margin that
+// covers the rounding of the cell assignment) is compared with the smallest d2 known so far -- r_max^2, the gap cell's
+// current best (read once per A site; whatever value it has is >= the final one) and what the group has found in the runs
+// before.  A run is skipped only if its bound is GREATER: every b at the final minimum of the cell, ties included, lies
+// in a run that is walked, so the A sites that attain the minimum hold their exact (d2, smallest b), and the others --
+// whose stored minimum may be too large or missing -- never enter step 7.  The result does not depend on what was read.
+//
+// Determinism: counts are integer adds, the minimum d2 and the packed pair are integer minima: every output is
+// independent of the execution order.  No thread waits for another.
+#include <cmath>
+#include <limits>
+
+#include "kmcf_internal.hpp"
+
+static_assert(sizeof(kmcf_gap_t) == 56, "kmcf_gap_t is 56 bytes");
+
+struct kmcf_gap_ws {
+    int N = 0;                                   // the index's N: the per-site arrays hold that many
+    int *d_side = nullptr;                       // side per site (kmcf_filament_gap without d_site_side)
+    int *d_bpos = nullptr;                       // N + 1: exclusive scan of the B flags in index-cell order
+    int *d_sum = nullptr;                        // 2 x (tiles + 1): tile counts / offsets of the A and of the B flags
+    int *d_alist = nullptr, *d_acell = nullptr;  // A members (index-cell order) and their gap cells
+    int *d_bsite = nullptr, *d_bcell = nullptr;  // B members (index-cell order), their gap cells ...
+    double *d_bx = nullptr, *d_by = nullptr, *d_bz = nullptr;   // ... and coordinates
+    unsigned long long *d_ad2 = nullptr;         // per A member: bits of its smallest d2 (+inf: none seen)
+    int *d_ab = nullptr;                         // ... and the b that gives it (-1: none)
+    int *d_stats = nullptr;                      // GP_STAT_* words
+    size_t cap_cells = 0;
+    unsigned long long *d_best = nullptr, *d_pair = nullptr;    // per gap cell: bits of the smallest d2, packed pair
+    int *d_cnt = nullptr;                        // per gap cell: n_left, n_right, n_both
+    kmcf_gap_t *d_gaps = nullptr;
+    size_t cap_prof = 0;
+    int *d_prof = nullptr;
+};
+
+void kmcf_gap_ws_free(kmcf_pairwise *p)
+{
+    if (!p || !p->gap_ws) return;
+    kmcf_gap_ws *w = p->gap_ws;
+    void *ptrs[] = {w->d_side, w->d_bpos, w->d_sum, w->d_alist, w->d_acell, w->d_bsite, w->d_bcell, w->d_bx, w->d_by, w->d_bz,
+                    w->d_ad2, w->d_ab, w->d_stats, w->d_best, w->d_pair, w->d_cnt, w->d_gaps, w->d_prof};
+    for (void *q : ptrs)
+        if (q) hipFree(q);
+    delete w;
+    p->gap_ws = nullptr;
+}
+
+namespace {
+
+typedef unsigned long long u64;
+constexpr int GP_ITEMS = 8, GP_TILE = KMCF_BLOCK * GP_ITEMS;      // flags per block of the scans
+constexpr int GP_LPS = 16, GP_SPB = KMCF_BLOCK / GP_LPS;          // lanes per A site, A sites per block
+constexpr u64 GP_INF = 0x7ff0000000000000ull;                    // bits of +infinity
+constexpr u64 GP_NO_PAIR = ~0ull;
+constexpr int GP_KIND_VACANCY = KMCF_CLUSTER_VACANCY;
+enum { GP_STAT_LEFT, GP_STAT_RIGHT, GP_STAT_BOTH, GP_STAT_BRIDGED, GP_STAT_OPEN, GP_STAT_NONE, GP_STAT_WORDS = 8 };
+
+__device__ __forceinline__ int gp_block_excl_scan(int v, int *lds, int *total)
+{
+    // exclusive scan of one int per thread over 256 threads (kmcf_pairwise.hip's)
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int s = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        int t = __shfl_up(s, off, 64);
+        if (lane >= off) s += t;
+    }
+    if (lane == 63) lds[w] = s;
+    __syncthreads();
+    int base = 0;
+    for (int i = 0; i < w; ++i) base += lds[i];
+    if (total) *total = lds[0] + lds[1] + lds[2] + lds[3];
+    __syncthreads();
+    return base + s - v;
+}
+
+// gap cell of a site, -1: none
+__device__ __forceinline__ int gp_cell(const int *__restrict__ site_cell, int n_cells, int i)
+{
+    const int c = site_cell ? site_cell[i] : 0;
+    return (unsigned)c < (unsigned)n_cells ? c : -1;
+}
+
+// the sides: touch word of the site's cluster, 0 for non-members
+__global__ __launch_bounds__(KMCF_BLOCK) void gp_side_kernel(int N, const unsigned char *__restrict__ cls,
+                                                             const int *__restrict__ label, const int *__restrict__ touch,
+                                                             int *__restrict__ side)
+{
+    const int i = blockIdx.x * KMCF_BLOCK + threadIdx.x;
+    if (i < N) side[i] = cls[i] ? (touch[label[i]] & 3) : 0;
+}
+
+// 1
+__global__ __launch_bounds__(KMCF_BLOCK) void gp_clear_kernel(size_t n_cells, u64 *__restrict__ best, u64 *__restrict__ pair,
+                                                              int *__restrict__ cnt, int *__restrict__ stats)
+{
+    const size_t c = (size_t)blockIdx.x * KMCF_BLOCK + threadIdx.x;
+    if (c < n_cells) {
+        best[c] = GP_INF;
+        pair[c] = GP_NO_PAIR;
+        cnt[3 * c] = cnt[3 * c + 1] = cnt[3 * c + 2] = 0;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < GP_STAT_WORDS) stats[threadIdx.x] = 0;
+}
+
+// 2: a wave adds once per gap cell it meets (the sites of one cell lie together in most orders), once for the device
+__global__ __launch_bounds__(KMCF_BLOCK) void gp_count_kernel(int N, const int *__restrict__ side,
+                                                              const int *__restrict__ site_cell, int n_cells, int *cnt, int *stats)
+{
+    const int i = blockIdx.x * KMCF_BLOCK + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const int s = i < N ? (side[i] & 3) : 0;
+    const int c = s ? gp_cell(site_cell, n_cells, i) : -1;
+    const u64 d1 = __ballot(s & 1), d2 = __ballot(s & 2), d3 = __ballot(s == 3);
+    if (lane == 0) {
+        if (d1) atomicAdd(stats + GP_STAT_LEFT, __popcll(d1));
+        if (d2) atomicAdd(stats + GP_STAT_RIGHT, __popcll(d2));
+        if (d3) atomicAdd(stats + GP_STAT_BOTH, __popcll(d3));
+    }
+    bool todo = c >= 0;
+    for (u64 act = __ballot(todo); act; act = __ballot(todo)) {
+        const int leader = __ffsll((long long)act) - 1;
+        const int lc = __shfl(c, leader, 64);
+        const bool mine = todo && c == lc;
+        const u64 a1 = __ballot(mine && (s & 1)), a2 = __ballot(mine && (s & 2)), a3 = __ballot(mine && s == 3);
+        if (lane == leader) {
+            int *q = cnt + 3 * (size_t)lc;
+            if (a1) atomicAdd(q, __popcll(a1));
+            if (a2) atomicAdd(q + 1, __popcll(a2));
+            if (a3) atomicAdd(q + 2, __popcll(a3));
+        }
+        if (mine) todo = false;
+    }
+}
+
+// members of the search: side bits of a site that lies in a gap cell
+__device__ __forceinline__ int gp_flags(const int *__restrict__ side, const int *__restrict__ site_cell, int n_cells, int i)
+{
+    const int s = side[i] & 3;
+    return (s && gp_cell(site_cell, n_cells, i) >= 0) ? s : 0;
+}
+
+// 3: per-tile counts of the A and of the B members (index-cell order)
+__global__ __launch_bounds__(KMCF_BLOCK) void gp_flag_count_kernel(int N, int nb, const int *__restrict__ cell_order,
+                                                                   const int *__restrict__ side, const int *__restrict__ site_cell,
+                                                                   int n_cells, int *__restrict__ sum)
+{
+    __shared__ int lds[4];
+    const int t0 = blockIdx.x * GP_TILE + threadIdx.x * GP_ITEMS;
+    int ca = 0, cb = 0;
+#pragma unroll
+    for (int k = 0; k < GP_ITEMS; ++k) {
+        const int t = t0 + k;
+        if (t < N) {
+            const int f = gp_flags(side, site_cell, n_cells, cell_order[t]);
+            ca += f & 1;
+            cb += (f >> 1) & 1;
+        }
+    }
+    int ta, tb;
+    gp_block_excl_scan(ca, lds, &ta);
+    gp_block_excl_scan(cb, lds, &tb);
+    if (threadIdx.x == 0) {
+        sum[blockIdx.x] = ta;
+        sum[nb + 1 + blockIdx.x] = tb;
+    }
+}
+
+// 4: exclusive scan of the tile counts in place, totals into sum[nb]; block 0 the A counts, block 1 the B counts
+__global__ __launch_bounds__(KMCF_BLOCK) void gp_scan_kernel(int nb, int *__restrict__ sum)
+{
+    __shared__ int lds[4];
+    __shared__ int carry;
+    int *block_sum = sum + (size_t)blockIdx.x * (nb + 1);
+    if (threadIdx.x == 0) carry = 0;
+    __syncthreads();
+    for (int b0 = 0; b0 < nb; b0 += KMCF_BLOCK) {
+        const int b = b0 + threadIdx.x;
+        const int v = b < nb ? block_sum[b] : 0;
+        int total;
+        const int ex = gp_block_excl_scan(v, lds, &total);
+        if (b < nb) block_sum[b] = carry + ex;
+        __syncthreads();
+        if (threadIdx.x == 0) carry += total;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) block_sum[nb] = carry;
+}
+
+// 5: positions of the B flags (every slot of the cell order: the runs of the search start at cell boundaries), the B
+// members with coordinates and gap cell, the A members with gap cell
+__global__ __launch_bounds__(KMCF_BLOCK) void gp_scatter_kernel(int N, int nb, const int *__restrict__ cell_order,
+                                                                const int *__restrict__ side, const int *__restrict__ site_cell,
+                                                                int n_cells, const double *__restrict__ x,
+                                                                const double *__restrict__ y, const double *__restrict__ z,
+                                                                const int *__restrict__ sum, int *__restrict__ bpos,
+                                                                int *__restrict__ alist, int *__restrict__ acell,
+                                                                int *__restrict__ bsite, int *__restrict__ bcell,
+                                                                double *__restrict__ bx, double *__restrict__ by,
+                                                                double *__restrict__ bz)
+{
+    __shared__ int lds[4];
+    const int t0 = blockIdx.x * GP_TILE + threadIdx.x * GP_ITEMS;
+    int f[GP_ITEMS], site[GP_ITEMS], ca = 0, cb = 0;
+#pragma unroll
+    for (int k = 0; k < GP_ITEMS; ++k) {
+        const int t = t0 + k;
+        site[k] = t < N ? cell_order[t] : -1;
+        f[k] = t < N ? gp_flags(side, site_cell, n_cells, site[k]) : 0;
+        ca += f[k] & 1;
+        cb += (f[k] >> 1) & 1;
+    }
+    int pa = sum[blockIdx.x] + gp_block_excl_scan(ca, lds, nullptr);
+    int pb = sum[nb + 1 + blockIdx.x] + gp_block_excl_scan(cb, lds, nullptr);
+#pragma unroll
+    for (int k = 0; k < GP_ITEMS; ++k) {
+        const int t = t0 + k;
+        if (t >= N) break;
+        bpos[t] = pb;
+        if (!f[k]) continue;
+        const int i = site[k];
+        const int c = gp_cell(site_cell, n_cells, i);
+        if (f[k] & 1) {
+            alist[pa] = i;
+            acell[pa] = c;
+            ++pa;
+        }
+        if (f[k] & 2) {
+            bsite[pb] = i;
+            bcell[pb] = c;
+            bx[pb] = x[i];
+            by[pb] = y[i];
+            bz[pb] = z[i];
+            ++pb;
+        }
+    }
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == KMCF_BLOCK - 1) bpos[N] = sum[2 * nb + 1];
+}
+
+struct gp_grid {
+    double x0, y0, z0, inv, edge;
+    int ncx, ncy, ncz;
+};
+
+__device__ __forceinline__ int gp_coord(double v, double v0, double inv, int nc)
+{
+    int c = (int)floor((v - v0) * inv);      // kmcf_pairwise.hip's cell rule
+    return c < 0 ? 0 : (c >= nc ? nc - 1 : c);
+}
+
+// Lower bound of |v_b - v| over the sites b of index cell column `a` next to the column `c` of v (a = c - 1 or c + 1):
+// the distance to the face between them, shortened by far more than the cell rule can misplace a site (relative 1e-9).
+__device__ __forceinline__ double gp_face_dist(double v, double v0, double edge, int c, int a)
+{
+    const double f = v0 + (double)(a > c ? c + 1 : c) * edge;
+    const double d = (a > c ? f - v : v - f) - 1e-9 * (fabs(f) + fabs(v) + edge);
+    return d > 0.0 ? d : 0.0;
+}
+
+__device__ __forceinline__ u64 gp_load(const u64 *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// 6: the search.  A group of GP_LPS lanes per A member; the loop runs over whole blocks of groups, so every lane of a wave
+// reaches the shuffles behind it.
+__global__ __launch_bounds__(KMCF_BLOCK) void gp_search_kernel(gp_grid g, const int *__restrict__ cell_start,
+                                                               const int *__restrict__ bpos, const int *__restrict__ n_a,
+                                                               const int *__restrict__ alist, const int *__restrict__ acell,
+                                                               const int *__restrict__ bsite, const int *__restrict__ bcell,
+                                                               const double *__restrict__ bx, const double *__restrict__ by,
+                                                               const double *__restrict__ bz, const double *__restrict__ x,
+                                                               const double *__restrict__ y, const double *__restrict__ z,
+                                                               double rmax2, u64 *best, u64 *__restrict__ ad2,
+                                                               int *__restrict__ ab)
+{
+    const int nA = *n_a;
+    const int lane = threadIdx.x % GP_LPS;
+    const int rows = (nA + GP_SPB - 1) / GP_SPB * GP_SPB;
+    const double inf = __longlong_as_double((long long)GP_INF);
+    for (int k = blockIdx.x * GP_SPB + threadIdx.x / GP_LPS; k < rows; k += gridDim.x * GP_SPB) {
+        const bool valid = k < nA;
+        double bd = inf;                    // this lane's minimum (d2, b)
+        int bb = 0x7fffffff;
+        int ca = -1;
+        if (valid) {
+            const int a = alist[k];
+            ca = acell[k];
+            const double xa = x[a], ya = y[a], za = z[a];
+            const int cx = gp_coord(xa, g.x0, g.inv, g.ncx), cy = gp_coord(ya, g.y0, g.inv, g.ncy),
+                      cz = gp_coord(za, g.z0, g.inv, g.ncz);
+            double thr = rmax2;             // no pair with a larger d2 can be the result (uniform over the group)
+            // (the group's first lane's read for all of them: the loops below must not part the group's lanes)
+            const double seen = __shfl(__longlong_as_double((long long)gp_load(best + ca)), 0, GP_LPS);
+            if (seen < thr) thr = seen;
+            for (int ax = max(cx - 1, 0); ax <= min(cx + 1, g.ncx - 1); ++ax) {
+                const double lx = ax == cx ? 0.0 : gp_face_dist(xa, g.x0, g.edge, cx, ax);
+                for (int ay = max(cy - 1, 0); ay <= min(cy + 1, g.ncy - 1); ++ay) {
+                    const double ly = ay == cy ? 0.0 : gp_face_dist(ya, g.y0, g.edge, cy, ay);
+                    if (lx * lx + ly * ly > thr) continue;
+                    // cells (ax, ay, cz-1..cz+1) are contiguous in the cell order: one run
+                    const int c_lo = (ax * g.ncy + ay) * g.ncz + max(cz - 1, 0);
+                    const int c_hi = (ax * g.ncy + ay) * g.ncz + min(cz + 1, g.ncz - 1);
+                    const int b = bpos[cell_start[c_lo]], e = bpos[cell_start[c_hi + 1]];
+                    if (b == e) continue;
+                    for (int t = b + lane; t < e; t += GP_LPS) {
+                        if (bcell[t] != ca) continue;
+                        const double dx = xa - bx[t], dy = ya - by[t], dz = za - bz[t];
+                        const double d2 = (dx * dx + dy * dy) + dz * dz;
+                        if (d2 <= rmax2) {
+                            const int j = bsite[t];                  // (j == a is a pair like any other)
+                            if (d2 < bd || (d2 == bd && j < bb)) { bd = d2; bb = j; }
+                        }
+                    }
+                    double m = bd;
+#pragma unroll
+                    for (int off = GP_LPS / 2; off >= 1; off >>= 1) m = fmin(m, __shfl_xor(m, off, 64));
+                    if (m < thr) thr = m;
+                }
+            }
+        }
+#pragma unroll
+        for (int off = GP_LPS / 2; off >= 1; off >>= 1) {
+            const double od = __shfl_xor(bd, off, 64);
+            const int ob = __shfl_xor(bb, off, 64);
+            if (od < bd || (od == bd && ob < bb)) { bd = od; bb = ob; }
+        }
+        if (valid && lane == 0) {
+            const bool found = bb != 0x7fffffff;
+            const u64 bits = (u64)__double_as_longlong(bd);
+            ad2[k] = bits;
+            ab[k] = found ? bb : -1;
+            if (found) atomicMin(best + ca, bits);
+        }
+    }
+}
+
+// 7: best[] is final (earlier launch); few A members attain it
+__global__ __launch_bounds__(KMCF_BLOCK) void gp_pair_kernel(const int *__restrict__ n_a, const int *__restrict__ alist,
+                                                             const int *__restrict__ acell, const u64 *__restrict__ ad2,
+                                                             const int *__restrict__ ab, const u64 *__restrict__ best, u64 *pair)
+{
+    const int nA = *n_a;
+    for (int k = blockIdx.x * KMCF_BLOCK + threadIdx.x; k < nA; k += gridDim.x * KMCF_BLOCK) {
+        const int b = ab[k];
+        if (b < 0) continue;
+        const int c = acell[k];
+        if (ad2[k] == best[c]) atomicMin(pair + c, ((u64)(unsigned)alist[k] << 32) | (unsigned)b);
+    }
+}
+
+// 8: the records (gap is filled in on the host: sqrt of gap2) and the cell counts
+__global__ __launch_bounds__(KMCF_BLOCK) void gp_record_kernel(size_t n_cells, const u64 *__restrict__ best,
+                                                               const u64 *__restrict__ pair, const int *__restrict__ cnt,
+                                                               const double *__restrict__ x, kmcf_gap_t *__restrict__ gaps,
+                                                               int *stats)
+{
+    const size_t c = (size_t)blockIdx.x * KMCF_BLOCK + threadIdx.x;
+    int state = -1;                          // 0 bridged, 1 open, 2 none
+    if (c < n_cells) {
+        kmcf_gap_t r;
+        const u64 pr = pair[c];
+        r.n_left = cnt[3 * c]; r.n_right = cnt[3 * c + 1]; r.n_both = cnt[3 * c + 2];
+        r.bridged = r.n_both > 0;
+        if (pr == GP_NO_PAIR) {
+            r.gap = r.gap2 = __longlong_as_double((long long)GP_INF);
+            r.x_left = r.x_right = 0.0;
+            r.site_left = r.site_right = -1;
+        } else {
+            r.gap2 = __longlong_as_double((long long)best[c]);
+            r.gap = r.gap2;
+            r.site_left = (int)(pr >> 32);
+            r.site_right = (int)(pr & 0xffffffffull);
+            r.x_left = x[r.site_left];
+            r.x_right = x[r.site_right];
+        }
+        gaps[c] = r;
+        state = r.bridged ? 0 : (pr == GP_NO_PAIR ? 2 : 1);
+    }
+    const u64 m0 = __ballot(state == 0), m1 = __ballot(state == 1), m2 = __ballot(state == 2);
+    if ((threadIdx.x & 63) == 0) {
+        if (m0) atomicAdd(stats + GP_STAT_BRIDGED, __popcll(m0));
+        if (m1) atomicAdd(stats + GP_STAT_OPEN, __popcll(m1));
+        if (m2) atomicAdd(stats + GP_STAT_NONE, __popcll(m2));
+    }
+}
+
+// 9: conductive vacancies per gap cell, x bin and side (integer atomics)
+__global__ __launch_bounds__(KMCF_BLOCK) void gp_profile_kernel(int N, const unsigned char *__restrict__ cls,
+                                                                const int *__restrict__ side, const int *__restrict__ site_cell,
+                                                                int n_cells, const double *__restrict__ x, int n_bins, double x_lo,
+                                                                double inv_w, int *prof)
+{
+    const int i = blockIdx.x * KMCF_BLOCK + threadIdx.x;
+    if (i >= N || cls[i] != GP_KIND_VACANCY) return;
+    const int s = side[i] & 3;
+    if (!s) return;
+    const int c = gp_cell(site_cell, n_cells, i);
+    if (c < 0) return;
+    const double t = (x[i] - x_lo) * inv_w;
+    if (t >= 0.0 && t < (double)n_bins) atomicAdd(prof + ((size_t)c * n_bins + (int)t) * 3 + (s - 1), 1);
+}
+
+template <typename T>
+int gp_alloc(T **p, size_t n)
+{
+    KMCF_HIP(hipMalloc(reinterpret_cast<void **>(p), n * sizeof(T)));
+    return KMCF_OK;
+}
+
+template <typename T>
+int gp_grow(T **p, size_t n)
+{
+    if (*p) hipFree(*p);
+    *p = nullptr;
+    return gp_alloc(p, n);
+}
+
+// scratch on the index, grown on demand and freed by kmcf_pairwise_destroy; it holds nothing a later call reads
+int gp_workspace(kmcf_pairwise *p, size_t n_cells, size_t prof_words)
+{
+    if (!p->gap_ws) {
+        kmcf_gap_ws *w = p->gap_ws = new kmcf_gap_ws();
+        const size_t n = (size_t)p->N, nb = (n + GP_TILE - 1) / GP_TILE;
+        w->N = p->N;
+        KMCF_TRY(gp_alloc(&w->d_side, n));
+        KMCF_TRY(gp_alloc(&w->d_bpos, n + 1));
+        KMCF_TRY(gp_alloc(&w->d_sum, 2 * (nb + 1)));
+        KMCF_TRY(gp_alloc(&w->d_alist, n));
+        KMCF_TRY(gp_alloc(&w->d_acell, n));
+        KMCF_TRY(gp_alloc(&w->d_bsite, n));
+        KMCF_TRY(gp_alloc(&w->d_bcell, n));
+        KMCF_TRY(gp_alloc(&w->d_bx, n));
+        KMCF_TRY(gp_alloc(&w->d_by, n));
+        KMCF_TRY(gp_alloc(&w->d_bz, n));
+        KMCF_TRY(gp_alloc(&w->d_ad2, n));
+        KMCF_TRY(gp_alloc(&w->d_ab, n));
+        KMCF_TRY(gp_alloc(&w->d_stats, (size_t)GP_STAT_WORDS));
+    }
+    kmcf_gap_ws *w = p->gap_ws;
+    if (w->cap_cells < n_cells) {
+        w->cap_cells = 0;
+        KMCF_TRY(gp_grow(&w->d_best, n_cells));
+        KMCF_TRY(gp_grow(&w->d_pair, n_cells));
+        KMCF_TRY(gp_grow(&w->d_cnt, 3 * n_cells));
+        KMCF_TRY(gp_grow(&w->d_gaps, n_cells));
+        w->cap_cells = n_cells;
+    }
+    if (w->cap_prof < prof_words) {
+        w->cap_prof = 0;
+        KMCF_TRY(gp_grow(&w->d_prof, prof_words));
+        w->cap_prof = prof_words;
+    }
+    return KMCF_OK;
+}
+
+// the argument checks both entry points share; p comes last: everything before it is checked without an index
+int gp_check_common(const char *what, const kmcf_pairwise *p, const double *d_x, const double *d_y, const double *d_z,
+                    double r_max, const int *d_site_cell, int n_cells, const kmcf_gap_t *h_gaps)
+{
+    KMCF_CHECK(d_x, KMCF_ERR_ARG, "%s: d_x is NULL", what);
+    KMCF_CHECK(d_y, KMCF_ERR_ARG, "%s: d_y is NULL", what);
+    KMCF_CHECK(d_z, KMCF_ERR_ARG, "%s: d_z is NULL", what);
+    KMCF_CHECK(h_gaps, KMCF_ERR_ARG, "%s: h_gaps is NULL", what);
+    KMCF_CHECK(std::isfinite(r_max), KMCF_ERR_ARG, "%s: r_max is not finite", what);
+    KMCF_CHECK(r_max > 0.0, KMCF_ERR_ARG, "%s: r_max = %g is not > 0", what, r_max);
+    KMCF_CHECK(n_cells >= 1, KMCF_ERR_ARG, "%s: n_cells = %d is not >= 1", what, n_cells);
+    KMCF_CHECK(d_site_cell || n_cells == 1, KMCF_ERR_ARG, "%s: d_site_cell is NULL with n_cells = %d", what, n_cells);
+    KMCF_CHECK(p, KMCF_ERR_ARG, "%s: p is NULL", what);
+    KMCF_CHECK(r_max <= p->cutoff, KMCF_ERR_ARG, "%s: r_max = %g exceeds the index's cutoff radius %g", what, r_max, p->cutoff);
+    return KMCF_OK;
+}
+
+// steps 1-8 (and 9 with cls and a profile) enqueued behind whatever produced d_side
+int gp_enqueue(kmcf_pairwise *p, const double *d_x, const double *d_y, const double *d_z, const int *d_side, double r_max,
+               const int *d_site_cell, int n_cells, const unsigned char *d_cls, int n_bins, double x_lo, double x_hi,
+               bool profile)
+{
+    kmcf_gap_ws *w = p->gap_ws;
+    hipStream_t st = p->comm->stream;
+    const int N = p->N;
+    const int nb = (N + GP_TILE - 1) / GP_TILE;
+    const int site_grid = (N + KMCF_BLOCK - 1) / KMCF_BLOCK;
+    const size_t nc = (size_t)n_cells;
+    const int cell_grid = (int)((nc + KMCF_BLOCK - 1) / KMCF_BLOCK);
+    const int *n_a = w->d_sum + nb;
+    int64_t search_grid = ((int64_t)N + GP_SPB - 1) / GP_SPB;      // an upper bound: the kernel strides over the A members
+    if (search_grid > 8192) search_grid = 8192;
+    int64_t pair_grid = site_grid;
+    if (pair_grid > 2048) pair_grid = 2048;
+    gp_grid g{p->x0, p->y0, p->z0, p->inv, p->cutoff, p->ncx, p->ncy, p->ncz};
+
+    gp_clear_kernel<<<cell_grid, KMCF_BLOCK, 0, st>>>(nc, w->d_best, w->d_pair, w->d_cnt, w->d_stats);
+    gp_count_kernel<<<site_grid, KMCF_BLOCK, 0, st>>>(N, d_side, d_site_cell, n_cells, w->d_cnt, w->d_stats);
+    gp_flag_count_kernel<<<nb, KMCF_BLOCK, 0, st>>>(N, nb, p->d_cell_order, d_side, d_site_cell, n_cells, w->d_sum);
+    gp_scan_kernel<<<2, KMCF_BLOCK, 0, st>>>(nb, w->d_sum);
+    gp_scatter_kernel<<<nb, KMCF_BLOCK, 0, st>>>(N, nb, p->d_cell_order, d_side, d_site_cell, n_cells, d_x, d_y, d_z, w->d_sum,
+                                                w->d_bpos, w->d_alist, w->d_acell, w->d_bsite, w->d_bcell, w->d_bx, w->d_by,
+                                                w->d_bz);
+    gp_search_kernel<<<(int)search_grid, KMCF_BLOCK, 0, st>>>(g, p->d_cell_start, w->d_bpos, n_a, w->d_alist, w->d_acell,
+                                                             w->d_bsite, w->d_bcell, w->d_bx, w->d_by, w->d_bz, d_x, d_y, d_z,
+                                                             r_max * r_max, w->d_best, w->d_ad2, w->d_ab);
+    gp_pair_kernel<<<(int)pair_grid, KMCF_BLOCK, 0, st>>>(n_a, w->d_alist, w->d_acell, w->d_ad2, w->d_ab, w->d_best, w->d_pair);
+    gp_record_kernel<<<cell_grid, KMCF_BLOCK, 0, st>>>(nc, w->d_best, w->d_pair, w->d_cnt, d_x, w->d_gaps, w->d_stats);
+    if (profile) {
+        const size_t words = nc * (size_t)n_bins * 3;
+        KMCF_HIP(hipMemsetAsync(w->d_prof, 0, words * sizeof(int), st));
+        gp_profile_kernel<<<site_grid, KMCF_BLOCK, 0, st>>>(N, d_cls, d_side, d_site_cell, n_cells, d_x, n_bins, x_lo,
+                                                           (double)n_bins / (x_hi - x_lo), w->d_prof);
+    }
+    KMCF_HIP(hipGetLastError());
+    return KMCF_OK;
+}
+
+// the copies, the call's one synchronisation, and what the host adds
+int gp_finish(kmcf_pairwise *p, int n_cells, kmcf_gap_t *h_gaps, size_t prof_words, int *h_profile, hipEvent_t ev_mid,
+              kmcf_gap_stats_t *stats)
+{
+    kmcf_comm *c = p->comm;
+    kmcf_gap_ws *w = p->gap_ws;
+    hipStream_t st = c->stream;
+    int *h = c->h_pinned;
+    KMCF_HIP(hipMemcpyAsync(h_gaps, w->d_gaps, (size_t)n_cells * sizeof(kmcf_gap_t), hipMemcpyDeviceToHost, st));
+    if (prof_words) KMCF_HIP(hipMemcpyAsync(h_profile, w->d_prof, prof_words * sizeof(int), hipMemcpyDeviceToHost, st));
+    KMCF_HIP(hipMemcpyAsync(h, w->d_stats, GP_STAT_WORDS * sizeof(int), hipMemcpyDeviceToHost, st));
+    KMCF_HIP(hipEventRecord(c->ev_call1, st));
+    KMCF_HIP(hipStreamSynchronize(st));
+    for (int k = 0; k < n_cells; ++k) h_gaps[k].gap = std::sqrt(h_gaps[k].gap2);
+    if (stats) {
+        stats->n_left = h[GP_STAT_LEFT];
+        stats->n_right = h[GP_STAT_RIGHT];
+        stats->n_both = h[GP_STAT_BOTH];
+        stats->cells_bridged = h[GP_STAT_BRIDGED];
+        stats->cells_open = h[GP_STAT_OPEN];
+        stats->cells_none = h[GP_STAT_NONE];
+        stats->ms_clusters = 0.f;
+        if (ev_mid) KMCF_HIP(hipEventElapsedTime(&stats->ms_clusters, c->ev_t0, ev_mid));
+        KMCF_HIP(hipEventElapsedTime(&stats->ms_search, ev_mid ? ev_mid : c->ev_t0, c->ev_call1));
+    }
+    return KMCF_OK;
+}
+
+}  // namespace
+
+extern "C" int kmcf_site_set_gap(kmcf_pairwise *p, const double *d_x, const double *d_y, const double *d_z,
+                                 const int *d_site_side, double r_max, const int *d_site_cell, int n_cells,
+                                 kmcf_gap_t *h_gaps, kmcf_gap_stats_t *stats)
+{
+    const char *what = "kmcf_site_set_gap";
+    KMCF_CHECK(d_site_side, KMCF_ERR_ARG, "%s: d_site_side is NULL", what);
+    KMCF_TRY(gp_check_common(what, p, d_x, d_y, d_z, r_max, d_site_cell, n_cells, h_gaps));
+    kmcf_comm *c = p->comm;
+    KMCF_TRY(kmcf_enter(c));
+    KMCF_TRY(gp_workspace(p, (size_t)n_cells, 0));
+    KMCF_HIP(hipEventRecord(c->ev_t0, c->stream));
+    KMCF_TRY(gp_enqueue(p, d_x, d_y, d_z, d_site_side, r_max, d_site_cell, n_cells, nullptr, 0, 0.0, 0.0, false));
+    return gp_finish(p, n_cells, h_gaps, 0, nullptr, nullptr, stats);
+}
+
+extern "C" int kmcf_filament_gap(kmcf_pairwise *p, int nn, const int *d_neigh_idx, const int *d_site_element,
+                                 const int *d_site_charge, const int *d_metals, int num_metals, const double *d_x,
+                                 const double *d_y, const double *d_z, int N_left_tot, int N_right_tot, double r_max,
+                                 const int *d_site_cell, int n_cells, kmcf_gap_t *h_gaps, int n_bins, double x_lo, double x_hi,
+                                 int *h_profile, int *d_site_side, kmcf_gap_stats_t *stats)
+{
+    const char *what = "kmcf_filament_gap";
+    KMCF_CHECK(d_neigh_idx, KMCF_ERR_ARG, "%s: d_neigh_idx is NULL", what);
+    KMCF_CHECK(d_site_element, KMCF_ERR_ARG, "%s: d_site_element is NULL", what);
+    KMCF_CHECK(d_site_charge, KMCF_ERR_ARG, "%s: d_site_charge is NULL", what);
+    KMCF_CHECK(nn > 0, KMCF_ERR_ARG, "%s: nn = %d is not > 0", what, nn);
+    KMCF_CHECK(num_metals >= 0, KMCF_ERR_ARG, "%s: num_metals = %d is negative", what, num_metals);
+    KMCF_CHECK(num_metals == 0 || d_metals, KMCF_ERR_ARG, "%s: d_metals is NULL with num_metals = %d", what, num_metals);
+    KMCF_CHECK(N_left_tot >= 0, KMCF_ERR_ARG, "%s: N_left_tot = %d is negative", what, N_left_tot);
+    KMCF_CHECK(N_right_tot >= 0, KMCF_ERR_ARG, "%s: N_right_tot = %d is negative", what, N_right_tot);
+    KMCF_CHECK(n_bins >= 0, KMCF_ERR_ARG, "%s: n_bins = %d is negative", what, n_bins);
+    KMCF_CHECK(!h_profile || n_bins > 0, KMCF_ERR_ARG, "%s: h_profile is set with n_bins = 0", what);
+    KMCF_CHECK(!h_profile || x_hi > x_lo, KMCF_ERR_ARG, "%s: h_profile is set with x_hi = %g not above x_lo = %g", what, x_hi, x_lo);
+    KMCF_TRY(gp_check_common(what, p, d_x, d_y, d_z, r_max, d_site_cell, n_cells, h_gaps));
+    const int N = p->N;
+    KMCF_CHECK((int64_t)N_left_tot + N_right_tot <= N, KMCF_ERR_ARG, "%s: N_left_tot + N_right_tot = %lld exceeds N = %d", what,
+               (long long)N_left_tot + N_right_tot, N);
+    kmcf_comm *c = p->comm;
+    KMCF_TRY(kmcf_enter(c));
+    const size_t prof_words = h_profile ? (size_t)n_cells * (size_t)n_bins * 3 : 0;
+    KMCF_TRY(gp_workspace(p, (size_t)n_cells, prof_words));
+    kmcf_gap_ws *w = p->gap_ws;
+    hipStream_t st = c->stream;
+    int *side = d_site_side ? d_site_side : w->d_side;
+    kmcf_cluster_dev cl;
+    KMCF_HIP(hipEventRecord(c->ev_t0, st));
+    KMCF_TRY(kmcf_clusters_enqueue(c, N, nn, d_neigh_idx, d_site_element, d_site_charge, d_metals, num_metals, d_x, N_left_tot,
+                                   N_right_tot, nullptr, false, 0, &cl));
+    gp_side_kernel<<<(N + KMCF_BLOCK - 1) / KMCF_BLOCK, KMCF_BLOCK, 0, st>>>(N, cl.cls, cl.label, cl.touch, side);
+    KMCF_HIP(hipEventRecord(c->ev_t1, st));
+    KMCF_TRY(gp_enqueue(p, d_x, d_y, d_z, side, r_max, d_site_cell, n_cells, cl.cls, n_bins, x_lo, x_hi, h_profile != nullptr));
+    return gp_finish(p, n_cells, h_gaps, prof_words, h_profile, c->ev_t1, stats);
+}

@@ -146,6 +146,40 @@ uint32_t kmcf_group_knob_hash(const kmcf_comm *c, kmcf_knob_id k);
 void kmcf_event_cache_free(kmcf_comm *c);
 void kmcf_cluster_ws_free(kmcf_comm *c);
 
+// clusters.hip: the cluster pass of kmcf_conductive_clusters (its arguments, already checked; kmcf_enter done) enqueued on
+// the compute stream, nothing waited for and nothing copied.  Hands back where the results lie on the device: the class
+// per site (0 no member, 1 metal, 2 conductive vacancy), the label per site (d_site_label if given, else the workspace's)
+// and the touch bits PER ROOT (touch[label[i]] for a member i).  They live in the communicator's workspace until its next
+// cluster pass.  summaries: also count the clusters into the workspace's summary words and write the first table_cap of
+// them into its table (what kmcf_conductive_clusters copies out).
+struct kmcf_cluster_dev {
+    const unsigned char *cls = nullptr;
+    const int *label = nullptr;
+    const int *touch = nullptr;
+};
+int kmcf_clusters_enqueue(kmcf_comm *c, int N, int nn, const int *d_neigh_idx, const int *d_site_element,
+                          const int *d_site_charge, const int *d_metals, int num_metals, const double *d_x, int N_left_tot,
+                          int N_right_tot, int *d_site_label, bool summaries, int table_cap, kmcf_cluster_dev *out);
+
+// Spatial index of the sites (kmcf_pairwise.hip: kmcf_compute_cutoff_list): cells of edge `cutoff`, cell id
+// (cx * ncy + cy) * ncz + cz, so the cells (cx, cy, cz-1..cz+1) are one contiguous run of d_cell_order.
+struct kmcf_pairwise {
+    kmcf_comm *comm = nullptr;
+    int N = 0;
+    double cutoff = 20.0;
+    double x0 = 0, y0 = 0, z0 = 0, inv = 0;
+    int ncx = 1, ncy = 1, ncz = 1;
+    int ncell = 1;
+    int *d_cell_order = nullptr;   // sites sorted by cell (ascending site id inside a cell), N
+    int *d_cell_start = nullptr;   // ncell + 1 offsets into d_cell_order
+    int *d_flag_pos = nullptr;     // N + 1: exclusive scan of the charged flags (cell order)
+    int *d_block_sum = nullptr;    // scan scratch
+    int *d_clist = nullptr;        // compacted charged sites (cell order), N
+    int n_blocks = 0;
+    struct kmcf_gap_ws *gap_ws = nullptr;   // scratch of kmcf_site_set_gap / kmcf_filament_gap (kmcf_gap.hip): buffers only
+};
+void kmcf_gap_ws_free(kmcf_pairwise *p);
+
 struct kmcf_subop;   // sub-block operator of the split T matrix (kmcf_tstate.hip)
 
 constexpr int KMCF_LONG_CHUNK = 2048;    // entries of a long row handled by one block (spmv_long_kernel)

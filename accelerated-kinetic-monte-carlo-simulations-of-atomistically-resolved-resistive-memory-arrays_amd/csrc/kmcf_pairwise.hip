@@ -17,22 +17,7 @@
 #include <cmath>
 #include <vector>
 
-#include "kmcf_internal.hpp"
-
-struct kmcf_pairwise {
-    kmcf_comm *comm = nullptr;
-    int N = 0;
-    double cutoff = 20.0;
-    double x0 = 0, y0 = 0, z0 = 0, inv = 0;
-    int ncx = 1, ncy = 1, ncz = 1;
-    int ncell = 1;
-    int *d_cell_order = nullptr;   // sites sorted by cell (ascending site id inside a cell), N
-    int *d_cell_start = nullptr;   // ncell + 1 offsets into d_cell_order
-    int *d_flag_pos = nullptr;     // N + 1: exclusive scan of the charged flags (cell order)
-    int *d_block_sum = nullptr;    // scan scratch
-    int *d_clist = nullptr;        // compacted charged sites (cell order), N
-    int n_blocks = 0;
-};
+#include "kmcf_internal.hpp"      // struct kmcf_pairwise
 
 namespace {
 
@@ -233,6 +218,7 @@ extern "C" int kmcf_pairwise_destroy(kmcf_pairwise *p)
     if (!p) return KMCF_OK;
     hipSetDevice(p->comm->device);
     hipStreamSynchronize(p->comm->stream);
+    kmcf_gap_ws_free(p);
     void *ptrs[] = {p->d_cell_order, p->d_cell_start, p->d_flag_pos, p->d_block_sum, p->d_clist};
     for (void *q : ptrs)
         if (q) hipFree(q);

@@ -80,6 +80,22 @@ class ClusterStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class Gap(C.Structure):
+    """kmcf_gap_t"""
+    _fields_ = [("gap", C.c_double), ("gap2", C.c_double), ("x_left", C.c_double), ("x_right", C.c_double),
+                ("site_left", C.c_int), ("site_right", C.c_int), ("n_left", C.c_int), ("n_right", C.c_int),
+                ("n_both", C.c_int), ("bridged", C.c_int)]
+
+
+class GapStats(C.Structure):
+    """kmcf_gap_stats_t"""
+    _fields_ = [("n_left", C.c_int), ("n_right", C.c_int), ("n_both", C.c_int), ("cells_bridged", C.c_int),
+                ("cells_open", C.c_int), ("cells_none", C.c_int), ("ms_clusters", C.c_float), ("ms_search", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class CurrentMapStats(C.Structure):
     """kmcf_current_map_stats_t"""
     _fields_ = [("i_injection", C.c_double), ("i_extraction", C.c_double), ("sum_through", C.c_double),
@@ -187,6 +203,9 @@ SIGNATURES = {
                                    C.POINTER(C.c_ubyte), _DP]),
     "kmcf_conductive_clusters": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, C.c_int, C.c_int, _P,
                                            C.POINTER(Cluster), C.c_int, C.POINTER(ClusterStats)]),
+    "kmcf_site_set_gap": (C.c_int, [_P, _P, _P, _P, _P, C.c_double, _P, C.c_int, C.POINTER(Gap), C.POINTER(GapStats)]),
+    "kmcf_filament_gap": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P,
+                                    C.c_int, C.POINTER(Gap), C.c_int, C.c_double, C.c_double, _IP, _P, C.POINTER(GapStats)]),
     "kmcf_neighbor_list":(C.c_int, [_P, _P, _P, _P, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _P]),
 }
 

@@ -642,6 +642,65 @@ def conductive_clusters(kmc_comm, gpubuf, N_left_tot, N_right_tot, labels=True):
     return dict(label=label, clusters=table, stats=st.as_dict())
 
 
+GAP_DTYPE = np.dtype([("gap", np.float64), ("gap2", np.float64), ("x_left", np.float64), ("x_right", np.float64),
+                      ("site_left", np.int32), ("site_right", np.int32), ("n_left", np.int32), ("n_right", np.int32),
+                      ("n_both", np.int32), ("bridged", np.int32)])           # kmcf_gap_t
+
+
+def _gap_cells(gpubuf, site_cell, n_cells):
+    if site_cell is None:
+        assert n_cells == 1, "n_cells = %d needs site_cell" % n_cells
+        return None
+    if not torch.is_tensor(site_cell):
+        site_cell = torch.as_tensor(np.ascontiguousarray(site_cell, dtype=np.int32), device=gpubuf.device)
+    assert site_cell.dtype == torch.int32 and site_cell.numel() == gpubuf.N_, "site_cell: N int32 entries"
+    return site_cell
+
+
+def site_set_gap(gpubuf, site_side, r_max, site_cell=None, n_cells=1):
+    """kmcf_site_set_gap on the buffers' spatial index (gpubuf.cutoff_idx, compute_cutoff_list): per gap cell the nearest
+    pair (a, b) of the sites with side bit 0 and the sites with side bit 1 within r_max (definitions:
+    include/kmcfield.h).  site_side: int32 device tensor of N entries; site_cell: int32 tensor or array of N entries
+    (values outside [0, n_cells): no cell), or None with n_cells == 1.  Returns dict(gaps: numpy structured array
+    GAP_DTYPE of n_cells records, stats: dict)."""
+    assert gpubuf.cutoff_idx is not None, "site_set_gap needs the spatial index: compute_cutoff_list first"
+    assert site_side.dtype == torch.int32 and site_side.numel() == gpubuf.N_, "site_side: N int32 entries"
+    cell = _gap_cells(gpubuf, site_cell, n_cells)
+    gaps = np.zeros(int(n_cells), GAP_DTYPE)
+    st = _L.GapStats()
+    _L.check(_L.load().kmcf_site_set_gap(gpubuf.cutoff_idx, _ptr(gpubuf.site_x), _ptr(gpubuf.site_y), _ptr(gpubuf.site_z),
+                                         _ptr(site_side), float(r_max), _ptr(cell), int(n_cells),
+                                         gaps.ctypes.data_as(C.POINTER(_L.Gap)), C.byref(st)), "kmcf_site_set_gap")
+    return dict(gaps=gaps, stats=st.as_dict())
+
+
+def filament_gap(kmc_comm, gpubuf, N_left_tot, N_right_tot, r_max, site_cell=None, n_cells=1, bins=None, sides=True):
+    """kmcf_filament_gap: how close the conductive matter attached to the left electrode comes to the matter attached to
+    the right one, per gap cell (definitions: include/kmcfield.h).  Call it after update_charge_gpu and
+    compute_cutoff_list, on the communicator the index was built with.  bins: None or (n_bins, x_lo, x_hi) for the
+    profile of the conductive vacancies along x.  Returns dict(gaps: numpy structured array GAP_DTYPE of n_cells records,
+    profile: int32 array (n_cells, n_bins, 3) -- last axis: side 1, 2, 3 -- or None, side: int32 device tensor of N
+    entries or None, stats: dict)."""
+    N = gpubuf.N_
+    assert gpubuf.cutoff_idx is not None, "filament_gap needs the spatial index: compute_cutoff_list first"
+    assert gpubuf.neigh_idx is not None and gpubuf.neigh_idx.numel() == N * gpubuf.nn_, \
+        "filament_gap needs the neighbour list of the whole device"
+    cell = _gap_cells(gpubuf, site_cell, n_cells)
+    gaps = np.zeros(int(n_cells), GAP_DTYPE)
+    n_bins, x_lo, x_hi = (int(bins[0]), float(bins[1]), float(bins[2])) if bins is not None else (0, 0.0, 0.0)
+    profile = np.zeros((int(n_cells), n_bins, 3), np.int32) if bins is not None else None
+    side = torch.empty(N, dtype=torch.int32, device=gpubuf.device) if sides else None
+    st = _L.GapStats()
+    _L.check(_L.load().kmcf_filament_gap(gpubuf.cutoff_idx, gpubuf.nn_, _ptr(gpubuf.neigh_idx), _ptr(gpubuf.site_element),
+                                         _ptr(gpubuf.site_charge), _ptr(gpubuf.metal_types), gpubuf.num_metal_types_,
+                                         _ptr(gpubuf.site_x), _ptr(gpubuf.site_y), _ptr(gpubuf.site_z), int(N_left_tot),
+                                         int(N_right_tot), float(r_max), _ptr(cell), int(n_cells),
+                                         gaps.ctypes.data_as(C.POINTER(_L.Gap)), n_bins, x_lo, x_hi,
+                                         profile.ctypes.data_as(C.POINTER(C.c_int)) if profile is not None else None,
+                                         _ptr(side), C.byref(st)), "kmcf_filament_gap")
+    return dict(gaps=gaps, profile=profile, side=side, stats=st.as_dict())
+
+
 def k_assemble(gpubuf, Vd, high_G, low_G):
     lib = _L.load()
     _L.check(lib.kmcf_k_assemble(gpubuf.K_distributed, _ptr(gpubuf.site_element), _ptr(gpubuf.site_charge),

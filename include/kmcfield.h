@@ -541,6 +541,67 @@ int kmcf_conductive_clusters(kmcf_comm *c, int N, int nn, const int *d_neigh_idx
                              kmcf_cluster_stats_t *stats /* may be NULL */);
 
 /* ---------------------------------------------------------------------- */
+/* Filament gap: nearest approach of the two electrode sides (no reference   */
+/* counterpart)                                                              */
+/* ---------------------------------------------------------------------- */
+/* In the high-resistance state no filament bridges the device; what then sets the resistance is the tunnelling gap: how
+ * close the conductive matter attached to the left electrode comes to the matter attached to the right one.
+ * Sets: A = sites with side bit 0, B = sites with side bit 1; a site may be in both.  kmcf_site_set_gap takes the sides
+ * as given (d_site_side; bits above 1 are ignored).  kmcf_filament_gap derives them: side[i] = touch of i's cluster,
+ * exactly as kmcf_conductive_clusters defines touch, for members -- metal and vacancy clusters alike -- and 0 for
+ * non-members.
+ * Cell: d_site_cell[i] in [0, n_cells) is the gap cell of site i (for a crossbar: structure.crossbar_lines'
+ * cell_of_site); any other value: the site belongs to no cell and enters no pair.  d_site_cell NULL requires
+ * n_cells == 1 and puts every site in cell 0.
+ * Pair of cell c: (a, b) with a in A, b in B, both in cell c; a == b is allowed.  dx = x[a] - x[b], likewise dy, dz;
+ * d2 = (dx*dx + dy*dy) + dz*dz, every operation rounded to double (no fused multiply-add); the distance is non-periodic.
+ * A pair counts iff d2 <= r_max*r_max, that product formed in double.
+ * Result per cell: the pair with the smallest d2; among equal d2 the smallest a, then the smallest b.  A site in both sets
+ * gives gap2 = 0 through the pair (a, a).  gap2, the two sites, x_left / x_right and the counts are exact; gap =
+ * sqrt(gap2).  Every output is independent of the execution order: two calls on the same input return the same bytes.
+ * Profile (kmcf_filament_gap): inv_w = n_bins / (x_hi - x_lo) is computed once on the host; a conductive vacancy
+ * (cluster kind 2) of cell c with side s in {1, 2, 3} and t = (x[i] - x_lo) * inv_w, 0 <= t < n_bins, adds 1 to
+ * h_profile[(c*n_bins + (int)t)*3 + s-1].  The smallest side-3 count along x is the filament's constriction. */
+typedef struct {            /* 56 bytes */
+    double gap, gap2;       /* gap = sqrt(gap2); +infinity: no pair within r_max           */
+    double x_left, x_right; /* x of site_left / site_right (0.0 when there is no pair)     */
+    int site_left, site_right;   /* the pair, -1 when none                                  */
+    int n_left, n_right, n_both; /* sites of this cell with side bit 0 / bit 1 / both bits  */
+    int bridged;                 /* n_both > 0                                              */
+} kmcf_gap_t;
+typedef struct {
+    int n_left, n_right, n_both;                 /* whole device, cell -1 included */
+    int cells_bridged, cells_open, cells_none;   /* n_both > 0 / not bridged, a pair within r_max / not bridged, no pair */
+    float ms_clusters, ms_search;                /* device time (HIP events): cluster pass and sides / everything behind */
+} kmcf_gap_stats_t;
+
+/* Both are LOCAL operations on WHOLE-device arrays of the index's N sites (kmcf_compute_cutoff_list; the coordinates are
+ * the ones it was built from): no collectives, and nothing is kept between calls but scratch buffers on the index (freed
+ * by kmcf_pairwise_destroy).  kmcf_poisson_gridless's lists are not touched.  r_max is at most the index's cutoff radius:
+ * the 27 index cells around a site then hold every partner.  h_gaps: n_cells records out.  stats may be NULL.
+ * KMCF_ERR_ARG (before anything needs a device; kmcf_last_error names the argument): NULL coordinates, d_site_side
+ * (kmcf_site_set_gap), h_gaps or p; r_max not finite, <= 0, or larger than the index's cutoff radius; n_cells < 1, or
+ * NULL d_site_cell with n_cells != 1. */
+int kmcf_site_set_gap(kmcf_pairwise *p, const double *d_x, const double *d_y, const double *d_z,
+                      const int *d_site_side /* N: bit 0 left set, bit 1 right set */, double r_max,
+                      const int *d_site_cell /* N, or NULL */, int n_cells,
+                      kmcf_gap_t *h_gaps /* n_cells */, kmcf_gap_stats_t *stats /* or NULL */);
+
+/* The cluster pass of kmcf_conductive_clusters on the communicator of the index (call it after kmcf_update_charge),
+ * the sides, then the search.  h_profile: n_cells*n_bins*3 ints out, or NULL (n_bins, x_lo, x_hi are then not used
+ * beyond the check n_bins >= 0).  d_site_side: N ints out, or NULL.
+ * KMCF_ERR_ARG as above, and: NULL list, element or charge; n_bins < 0; h_profile set with n_bins == 0 or with
+ * x_hi <= x_lo; nn <= 0; num_metals < 0, or num_metals > 0 with NULL d_metals; N_left_tot < 0, N_right_tot < 0 or
+ * N_left_tot + N_right_tot > N of the index. */
+int kmcf_filament_gap(kmcf_pairwise *p, int nn, const int *d_neigh_idx, const int *d_site_element,
+                      const int *d_site_charge, const int *d_metals, int num_metals,
+                      const double *d_x, const double *d_y, const double *d_z,
+                      int N_left_tot, int N_right_tot, double r_max,
+                      const int *d_site_cell, int n_cells, kmcf_gap_t *h_gaps,
+                      int n_bins, double x_lo, double x_hi, int *h_profile /* n_cells*n_bins*3, or NULL */,
+                      int *d_site_side /* N out, or NULL */, kmcf_gap_stats_t *stats);
+
+/* ---------------------------------------------------------------------- */
 /* T path: current solve (Kirchhoff matrix with two virtual nodes + WKB       */
 /* tunnelling sub-block), SURVEY 8 rows a14 / f3.  PARITY UNPINNED: no         */
 /* reference fixture exercises it (src/KMC_comm.h:243 disables it from main).  */

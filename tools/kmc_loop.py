@@ -4,7 +4,7 @@ boundary (K) solve, pairwise term, sum/gather, KMC events -- with the per-module
 prints into output<size>_<rank>.txt ("Z - calculation time - ...").
 
     python tools/kmc_loop.py [--workload 5nm|40nm|conducting] [--steps 6] [--T 300] [--current] [--rate-mode bg|ekin|site]
-                             [--clusters] [--current-map] [--scheme all|half|third --select W,B]
+                             [--clusters] [--current-map] [--scheme all|half|third --select W,B] [--gap R]
 
 --current adds the electro-thermal stages after the potential and before the events: conduction-band edge, current
 solve with heating (site_power), local heat solve (site_temperature); --rate-mode ekin | site lets the event rates read
@@ -19,7 +19,12 @@ after the power update of every step: the step line gains `current map <ms> (tun
 array are filled once by structure.bias_scheme (selected word line -Vd/2, selected bit line +Vd/2, the others by the scheme),
 the boundary solve is kmcf_background_potential_sparse_contacts, and the step line gains `events per cell [c0 c1 ...]`: the
 events of the step whose first site lies under crossing word * n_lines + bit.  The band-edge and current stages of --current
-still see the scalar Vd.
+still see the scalar Vd.  --gap R runs the filament gap analysis (kmcf_filament_gap) after the charge update of every step:
+how close the conductive matter attached to the left electrode comes to the matter attached to the right one, searched up
+to R angstrom (at most 20, the cell edge of the spatial index), per cell of structure.crossbar_lines on the crossbar
+workloads.  The step line gains `gap <ms clusters>+<ms search> [<cell>: <gap> A (<site_left>-<site_right>) L <n_left> R
+<n_right> | <cell>: bridged (<n_both> sites) L .. R .. | <cell>: none L .. R ..]`; with --clusters a bridged cell also shows
+`constriction <sites>`: the smallest number of filament vacancies in a slice of 3.2 angstrom along x.
 """
 import argparse
 import os
@@ -51,11 +56,16 @@ def main():
     ap.add_argument("--scheme", default=None, choices=["all", "half", "third"],
                     help="per-line bias of the crossbar (synthetic workloads): all cells selected | V/2 scheme | V/3 scheme")
     ap.add_argument("--select", default="0,0", help="W,B: the selected word line and bit line of --scheme")
+    ap.add_argument("--gap", type=float, default=None, metavar="R",
+                    help="filament gap analysis after every charge update, searched up to R angstrom (<= 20): gap, pair and "
+                         "counts per crossbar cell; with --clusters also the constriction of a bridging filament")
     a = ap.parse_args()
     if a.scheme and a.workload == "5nm":
         ap.error("--scheme needs a crossbar with lines: --workload 40nm or conducting")
     if a.current_map and not a.current:
         ap.error("--current-map needs --current (the map reads the potentials of the current solve)")
+    if a.gap is not None and not 0.0 < a.gap <= 20.0:
+        ap.error("--gap %g: the search radius is > 0 and at most 20 (the cell edge of the spatial index)" % a.gap)
     if a.rate_mode != "bg" and not a.current:
         ap.error("--rate-mode %s needs --current (the heat solve provides the site temperatures)" % a.rate_mode)
     S = km.solvers
@@ -99,6 +109,14 @@ def main():
             ap.error("--select %s: %s" % (a.select, str(e) or "W,B expected"))
         cell_of_site = km.structure.crossbar_lines(d)[2]
         buf.site_potential_boundary.copy_(torch.as_tensor(contacts))      # once: the solve reads the slots, never writes them
+    gap_cells, n_gap_cells, gap_bins = None, 1, None
+    if a.gap is not None:
+        if a.workload != "5nm":
+            cells = km.structure.crossbar_lines(d)[2] if cell_of_site is None else cell_of_site
+            gap_cells, n_gap_cells = torch.as_tensor(cells, device="cuda"), int(cells.max()) + 1
+        if a.clusters:
+            x_lo, x_hi = float(d["xyz"][:, 0].min()), float(d["xyz"][:, 0].max()) + 1e-6
+            gap_bins = (int(np.ceil((x_hi - x_lo) / 3.2)), x_lo, x_hi)
     comm.sync()
     print("init [s] %.3f  (sites %d)" % (time.perf_counter() - t0, N))
     kmc_time = 0.0
@@ -119,6 +137,22 @@ def main():
             cs = S.conductive_clusters(comm, buf, NL, NL, labels=False)["stats"]
             clusters = " | clusters %.3f (%d vac, largest %d, bridging %d)" % (cs["ms"], cs["n_vacancy_clusters"],
                                                                                   cs["largest_vacancy"], cs["n_bridging"])
+        if a.gap is not None:
+            gp = S.filament_gap(comm, buf, NL, NL, a.gap, site_cell=gap_cells, n_cells=n_gap_cells, bins=gap_bins, sides=False)
+            cells = []
+            for c, g in enumerate(gp["gaps"]):
+                if g["bridged"]:
+                    what = "bridged (%d sites)" % g["n_both"]
+                    if gap_bins is not None:
+                        s3 = gp["profile"][c][:, 2]
+                        nz = np.flatnonzero(s3)
+                        what += " constriction %d" % (s3[nz[0]:nz[-1] + 1].min() if len(nz) else 0)
+                elif g["site_left"] >= 0:
+                    what = "%.4f A (%d-%d)" % (g["gap"], g["site_left"], g["site_right"])
+                else:
+                    what = "none"
+                cells.append("%d: %s L %d R %d" % (c, what, g["n_left"], g["n_right"]))
+            clusters += " | gap %.3f+%.3f [%s]" % (gp["stats"]["ms_clusters"], gp["stats"]["ms_search"], " | ".join(cells))
         if a.scheme:
             tb, st = timed(lambda: S.background_potential_gpu_sparse_contacts(buf, N, NL, NL, d["high_G"], d["low_G"],
                                                                               len(d["metals"])))
