@@ -134,14 +134,6 @@ __global__ __launch_bounds__(KMCF_BLOCK) void pattern_brute_kernel(
     }
 }
 
-int grid1d(int64_t n, int cap = 2048)
-{
-    int64_t g = (n + KMCF_BLOCK - 1) / KMCF_BLOCK;
-    if (g < 1) g = 1;
-    if (g > cap) g = cap;
-    return (int)g;
-}
-
 // ---------------------------------------------------------------- host-side cell list
 struct host_cells {
     cell_grid g;
@@ -208,8 +200,8 @@ int build_cells(const double *d_x, const double *d_y, const double *d_z, int N, 
     for (int64_t cidx = 0; cidx < ncell; ++cidx) start[cidx + 1] += start[cidx];
     std::vector<int> fill(start.begin(), start.end() - 1);
     for (int s = 0; s < N; ++s) items[fill[cid[s]]++] = s;
-    KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&hc->d_cell_start), start.size() * sizeof(int)));
-    KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&hc->d_cell_items), items.size() * sizeof(int)));
+    KMCF_TRY(kmcf_dev_alloc(&hc->d_cell_start, start.size(), false));
+    KMCF_TRY(kmcf_dev_alloc(&hc->d_cell_items, items.size(), false));
     KMCF_HIP(hipMemcpy(hc->d_cell_start, start.data(), start.size() * sizeof(int), hipMemcpyHostToDevice));
     KMCF_HIP(hipMemcpy(hc->d_cell_items, items.data(), items.size() * sizeof(int), hipMemcpyHostToDevice));
     return KMCF_OK;
@@ -235,7 +227,7 @@ int coords_seen_by_kernels(const host_cells &hc, const double *d_x, const double
     unsigned long long *d_sum = nullptr, h_sum = 0;
     KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&d_sum), sizeof(unsigned long long)));
     KMCF_HIP(hipMemsetAsync(d_sum, 0, sizeof(unsigned long long), st));
-    coords_sum_kernel<<<grid1d(N, 1024), KMCF_BLOCK, 0, st>>>(N, d_x, d_y, d_z, d_sum);
+    coords_sum_kernel<<<kmcf_grid1d(N, 1024), KMCF_BLOCK, 0, st>>>(N, d_x, d_y, d_z, d_sum);
     KMCF_HIP(hipGetLastError());
     KMCF_HIP(hipMemcpyAsync(&h_sum, d_sum, sizeof(h_sum), hipMemcpyDeviceToHost, st));
     KMCF_HIP(hipStreamSynchronize(st));
@@ -256,8 +248,8 @@ int build_pattern(const host_cells &hc, const double *d_x, const double *d_y, co
     col->clear();
     if (n_rows == 0) return KMCF_OK;
     int *d_cnt = nullptr, *d_rp = nullptr, *d_col = nullptr;
-    KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&d_cnt), (size_t)n_rows * sizeof(int)));
-    const int grid = grid1d(n_rows, 1 << 20);
+    KMCF_TRY(kmcf_dev_alloc(&d_cnt, (size_t)n_rows, false));
+    const int grid = kmcf_grid1d(n_rows, 1 << 20);
     if (hc.usable)
         pattern_count_kernel<<<grid, KMCF_BLOCK, 0, st>>>(hc.g, hc.d_cell_start, hc.d_cell_items, d_x, d_y, d_z, cutoff,
                                                           lattice[1], lattice[2], pbc, row_site0, n_rows, col_lo, col_hi, d_cnt);
@@ -273,8 +265,8 @@ int build_pattern(const host_cells &hc, const double *d_x, const double *d_y, co
     KMCF_CHECK(nnz < (int64_t)INT32_MAX, KMCF_ERR_ARG, "pattern has %lld nnz: exceeds int32 indexing", (long long)nnz);
     col->resize((size_t)nnz);
     if (nnz > 0) {
-        KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&d_rp), ((size_t)n_rows + 1) * sizeof(int)));
-        KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&d_col), (size_t)nnz * sizeof(int)));
+        KMCF_TRY(kmcf_dev_alloc(&d_rp, (size_t)n_rows + 1, false));
+        KMCF_TRY(kmcf_dev_alloc(&d_col, (size_t)nnz, false));
         KMCF_HIP(hipMemcpyAsync(d_rp, row_ptr->data(), ((size_t)n_rows + 1) * sizeof(int), hipMemcpyHostToDevice, st));
         if (hc.usable)
             pattern_fill_kernel<<<grid, KMCF_BLOCK, 0, st>>>(hc.g, hc.d_cell_start, hc.d_cell_items, d_x, d_y, d_z, cutoff,
@@ -295,7 +287,7 @@ int build_pattern(const host_cells &hc, const double *d_x, const double *d_y, co
 template <typename T>
 int upload(T **d, const std::vector<T> &h)
 {
-    KMCF_HIP(hipMalloc(reinterpret_cast<void **>(d), std::max<size_t>(h.size(), 1) * sizeof(T)));
+    KMCF_TRY(kmcf_dev_alloc(d, std::max<size_t>(h.size(), 1), false));
     if (!h.empty()) KMCF_HIP(hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
     return KMCF_OK;
 }

@@ -24,22 +24,6 @@
 
 namespace {
 
-__device__ __forceinline__ double wave_sum64(double v)
-{
-    return kmcf_wave_sum64(v);     // (the xor butterfly 32 ... 1; kmcf_internal.hpp)
-}
-
-__device__ __forceinline__ double block_sum(double v, double *lds4)
-{
-    v = wave_sum64(v);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) lds4[w] = v;
-    __syncthreads();
-    double t = (lds4[0] + lds4[1]) + (lds4[2] + lds4[3]);
-    __syncthreads();
-    return t;
-}
-
 // Up to four partial arrays (an SpMV writes one per pass: interior rows, boundary rows, long rows, sub-block).
 struct part_ref {
     const double *p[4];
@@ -61,7 +45,7 @@ __device__ __forceinline__ double reduce_partials(const part_ref &r, double *lds
 #pragma unroll
     for (int q = 0; q < 4; ++q)
         for (int i = threadIdx.x; i < r.n[q]; i += KMCF_BLOCK) v += r.p[q][i];
-    return block_sum(v, lds4);
+    return kmcf_block_sum(v, lds4);
 }
 
 // r = b - A x0 ; z = r .* dinv ; partial r.z and b.b   (dist_conjugate_gradient.cpp:187, 201-212)
@@ -80,8 +64,8 @@ __global__ __launch_bounds__(KMCF_BLOCK) void cg_init_kernel(int n, double *__re
         double z = PRECOND ? ri * dinv[i] : ri;
         rz += ri * z;
     }
-    double t = block_sum(rz, lds4);
-    double u = block_sum(bb, lds4);
+    double t = kmcf_block_sum(rz, lds4);
+    double u = kmcf_block_sum(bb, lds4);
     if (threadIdx.x == 0) { part_rz[blockIdx.x] = t; part_bb[blockIdx.x] = u; }
 }
 
@@ -257,7 +241,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void cg_xr_kernel(int n, double *__rest
         const double z = PRECOND ? ri * dinv[i] : ri;
         rz += ri * z;
     }
-    double t = block_sum(rz, lds4);
+    double t = kmcf_block_sum(rz, lds4);
     if (threadIdx.x == 0) {
         part_rz[blockIdx.x] = t;
         if (blockIdx.x == 0) { S->pAp = pAp; S->xa = a; S->x_pending = 1; }
@@ -281,8 +265,6 @@ __global__ __launch_bounds__(KMCF_BLOCK) void cg_tail_kernel(part_ref prz, kmcf_
     double t = reduce_partials(prz, lds4);
     if (threadIdx.x == 0) S->rz_last = t;
 }
-
-int vec_grid(int n) { return kmcf_vec_grid(n); }
 
 // End of a chunk of iterations: has the loop stopped?  The device says so in pinned host memory (one thread, behind the
 // chunk's last kernel): {done, iterations, this check's number} -- and the host polls the number instead of sleeping in
@@ -351,7 +333,7 @@ int pcg_loop(kmcf_matrix *m, double tol, int max_it, int fixed_iters, int absolu
     kmcf_comm *c = m->comm;
     hipStream_t st = c->stream;
     const int n = m->n_loc;
-    const int vg = vec_grid(n);
+    const int vg = kmcf_vec_grid(n);
     const bool multi = c->nranks > 1 || c->force_collectives;
     kmcf_scalars *S = m->d_S;
     const double tol2 = tol * tol;
@@ -467,8 +449,8 @@ __global__ __launch_bounds__(KMCF_BLOCK) void cg1_init_kernel(int n, double *__r
         z_out[i] = z;
         rz += ri * z;
     }
-    double t = block_sum(rz, lds4);
-    double u = block_sum(bb, lds4);
+    double t = kmcf_block_sum(rz, lds4);
+    double u = kmcf_block_sum(bb, lds4);
     if (threadIdx.x == 0) { part_rz[blockIdx.x] = t; part_bb[blockIdx.x] = u; }
 }
 
@@ -489,14 +471,14 @@ __device__ __forceinline__ void reduce_partials3(const part_ref &a, const part_r
         for (int q = 0; q < 4; ++q)
             for (int i = threadIdx.x; i < c.n[q]; i += KMCF_BLOCK) vc += c.p[q][i];
     }
-    va = wave_sum64(va); vb = wave_sum64(vb); vc = wave_sum64(vc);
+    va = kmcf_wave_sum64(va); vb = kmcf_wave_sum64(vb); vc = kmcf_wave_sum64(vc);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     if (lane == 0) { lds[0][w] = va; lds[1][w] = vb; lds[2][w] = vc; }
     __syncthreads();
     ra = (lds[0][0] + lds[0][1]) + (lds[0][2] + lds[0][3]);
     rb = (lds[1][0] + lds[1][1]) + (lds[1][2] + lds[1][3]);
     rc = (lds[2][0] + lds[2][1]) + (lds[2][2] + lds[2][3]);
-    __syncthreads();                     // (lds is written again by the caller's block_sum, with no barrier of the caller's in between)
+    __syncthreads();                     // (lds is written again by the caller's kmcf_block_sum, with no barrier of the caller's in between)
 }
 
 // The update of the single-reduction loop, for one rank or a host-synchronous group (P2P = false: gamma, delta, b.b are
@@ -642,7 +624,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void cg1_update_kernel(
         upd(z[i], w[i], pi, si, xi, ri, PRECOND ? dinv[i] : 1.0, zn, P2P ? pd.put_row[i] : -1);
         p[i] = pi; s[i] = si; x[i] = xi; r[i] = ri; z[i] = zn;
     }
-    const double tsum = block_sum(rz, &lds[0][0]);
+    const double tsum = kmcf_block_sum(rz, &lds[0][0]);
     if (t == 0) part_rz[blockIdx.x] = tsum;
     if (P2P) {
         // the last block to finish raises the neighbours' flags
@@ -677,15 +659,15 @@ int pcg1_loop(kmcf_matrix *m, double tol, int max_it, int fixed_iters, int absol
     kmcf_comm *c = m->comm;
     hipStream_t st = c->stream;
     const int n = m->n_loc;
-    const int vg = vec_grid(n);
+    const int vg = kmcf_vec_grid(n);
     const bool multi = c->nranks > 1 || c->force_collectives;
     kmcf_scalars *S = m->d_S;
     const double tol2 = tol * tol;
     const int check_tol = fixed_iters > 0 ? 0 : (absolute ? 2 : 1);
     const int limit = fixed_iters > 0 ? fixed_iters : max_it;
     if (!m->d_pd) {
-        KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&m->d_pd), ((size_t)n + 2) * sizeof(double)));
-        KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&m->d_s), ((size_t)n + 2) * sizeof(double)));
+        KMCF_TRY(kmcf_dev_alloc(&m->d_pd, (size_t)n + 2, false));
+        KMCF_TRY(kmcf_dev_alloc(&m->d_s, (size_t)n + 2, false));
     }
     part_ref pg_loc = pr1(m->d_part_b, vg);
     part_ref pb_loc = pr1(m->d_part_c, vg);
@@ -945,7 +927,7 @@ int kmcf_scaled_cg_workspace(kmcf_matrix *m, double tol, int max_iterations, dou
 {
     kmcf_comm *c = m->comm;
     const int n = m->n_loc;
-    const int g = vec_grid(n);
+    const int g = kmcf_vec_grid(n);
     double *dis = m->d_dinv;  // workspace: 1/sqrt(diag)
     diag_inv_sqrt_kernel<<<g, KMCF_BLOCK, 0, c->stream>>>(n, m->d_row_ptr, m->d_col, m->d_val, dis);
     scale_vector_kernel<<<g, KMCF_BLOCK, 0, c->stream>>>(n, m->d_r, dis, 0);      // rhs scaled (:740)
@@ -1076,7 +1058,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void cg_out_kernel(int n, const int *__
         x_u[s] = xv;
     }
 }
-inline int perm_grid(int n) { return (vec_grid(n) + 7) / 8 * 8; }
+inline int perm_grid(int n) { return (kmcf_vec_grid(n) + 7) / 8 * 8; }
 }  // namespace
 
 extern "C" int kmcf_pcg_jacobi(kmcf_matrix *m, double *d_r, double *d_x, const double *d_diag_inv,
@@ -1108,7 +1090,7 @@ extern "C" int kmcf_pcg_jacobi(kmcf_matrix *m, double *d_r, double *d_x, const d
     const double t_b = trace ? now() : 0.0;
     const bool tail_here = !(c->nranks > 1 || c->force_collectives) && !kmcf_cg_single_reduction(m) && n > 0 && !m->last_solve_resident;
     cg_out_kernel<<<perm_grid(std::max(n, 1)), KMCF_BLOCK, 0, c->stream>>>(n, m->d_perm, m->d_r, m->d_x, m->d_p, d_r, d_x, m->d_S, c->h_scal,
-                                                                           tail_here ? pr1(m->d_part_b, vec_grid(n)) : pr_none());
+                                                                           tail_here ? pr1(m->d_part_b, kmcf_vec_grid(n)) : pr_none());
     KMCF_HIP(hipGetLastError());
     KMCF_HIP(hipEventRecord(c->ev_call1, c->stream));
     // results visible on return (:271 hipDeviceSynchronize)
@@ -1148,7 +1130,7 @@ int kmcf_vec_in(kmcf_matrix *m, double *d_internal, const double *d_user)
     if (!m->d_perm) {
         KMCF_HIP(hipMemcpyAsync(d_internal, d_user, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, m->comm->stream));
     } else {
-        perm_in_kernel<<<vec_grid(n), KMCF_BLOCK, 0, m->comm->stream>>>(n, d_internal, d_user, m->d_perm);
+        perm_in_kernel<<<kmcf_vec_grid(n), KMCF_BLOCK, 0, m->comm->stream>>>(n, d_internal, d_user, m->d_perm);
         KMCF_HIP(hipGetLastError());
     }
     return KMCF_OK;
@@ -1161,7 +1143,7 @@ int kmcf_vec_out(kmcf_matrix *m, double *d_user, const double *d_internal)
     if (!m->d_perm) {
         KMCF_HIP(hipMemcpyAsync(d_user, d_internal, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, m->comm->stream));
     } else {
-        perm_out_kernel<<<vec_grid(n), KMCF_BLOCK, 0, m->comm->stream>>>(n, d_user, d_internal, m->d_perm);
+        perm_out_kernel<<<kmcf_vec_grid(n), KMCF_BLOCK, 0, m->comm->stream>>>(n, d_user, d_internal, m->d_perm);
         KMCF_HIP(hipGetLastError());
     }
     return KMCF_OK;

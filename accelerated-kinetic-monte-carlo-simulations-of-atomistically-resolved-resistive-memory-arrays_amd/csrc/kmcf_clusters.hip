@@ -7,7 +7,7 @@
 //
 // Algorithm: union-find with atomic hooking and path compression (ECL-CC / Afforest style), NOT label propagation: the
 // electrode lines are clusters of 1e5-1e6 sites with diameters of hundreds of hops.  Launches, all on the compute stream:
-//   1-3  classify the sites, compact the member list (flag / scan / scatter as in kmcf_pairwise.hip)
+//   1-3  classify the sites, compact the member list (the tile compaction of kmcf_block.hpp)
 //   4    hook: LPR lanes per member row; every same-class neighbour is united with the row's site      [walks rows]
 //   5    flatten: label[i] = root of i (the smallest id of its component), -1 for non-members
 //   6    sizes, extents, the metal clusters' contact bits: summed per block in an LDS hash table, then atomics
@@ -44,17 +44,15 @@ struct kmcf_cluster_ws {
     int *d_msum = nullptr, *d_rsum = nullptr;   // scan scratch of the member and of the root compaction (tiles + 1)
     int *d_stats = nullptr;              // CL_STAT_* words
     kmcf_cluster_t *d_table = nullptr;
-    int cap_table = 0;
+    size_t cap_table = 0;
 };
 
 void kmcf_cluster_ws_free(kmcf_comm *c)
 {
     if (!c || !c->cl_ws) return;
     kmcf_cluster_ws *w = c->cl_ws;
-    void *ptrs[] = {w->d_cls, w->d_parent, w->d_members, w->d_label, w->d_size, w->d_touch, w->d_xmin, w->d_xmax,
-                    w->d_msum, w->d_rsum, w->d_stats, w->d_table};
-    for (void *p : ptrs)
-        if (p) hipFree(p);
+    kmcf_dev_free_all({w->d_cls, w->d_parent, w->d_members, w->d_label, w->d_size, w->d_touch, w->d_xmin, w->d_xmax, w->d_msum,
+                       w->d_rsum, w->d_stats, w->d_table});
     delete w;
     c->cl_ws = nullptr;
 }
@@ -63,49 +61,9 @@ namespace {
 
 constexpr int EL_VACANCY = 2;                          // src/utils.h:37-44
 constexpr int CL_NONE = 0, CL_METAL = KMCF_CLUSTER_METAL, CL_VACANCY = KMCF_CLUSTER_VACANCY;
-constexpr int CL_ITEMS = 8, CL_TILE = KMCF_BLOCK * CL_ITEMS;     // sites per block of the scans
 constexpr int CL_PASSES = 2;                           // launches that walk neighbour rows: cl_hook_kernel, cl_touch_kernel
 enum { CL_STAT_METAL, CL_STAT_VACANCY, CL_STAT_BRIDGING, CL_STAT_LARGEST_VAC, CL_STAT_LARGEST_BRIDGING, CL_STAT_MEMBERS,
        CL_STAT_CLUSTERS, CL_STAT_WORDS = 8 };
-
-__device__ __forceinline__ int cl_block_excl_scan(int v, int *lds, int *total)
-{
-    // exclusive scan of one int per thread over 256 threads (kmcf_pairwise.hip's)
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int s = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        int t = __shfl_up(s, off, 64);
-        if (lane >= off) s += t;
-    }
-    if (lane == 63) lds[w] = s;
-    __syncthreads();
-    int base = 0;
-    for (int i = 0; i < w; ++i) base += lds[i];
-    if (total) *total = lds[0] + lds[1] + lds[2] + lds[3];
-    __syncthreads();
-    return base + s - v;
-}
-
-// exclusive scan of the tile counts in place, total into block_sum[nb] (one block)
-__global__ __launch_bounds__(KMCF_BLOCK) void cl_scan_kernel(int nb, int *__restrict__ block_sum)
-{
-    __shared__ int lds[4];
-    __shared__ int carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int b0 = 0; b0 < nb; b0 += KMCF_BLOCK) {
-        const int b = b0 + threadIdx.x;
-        const int v = b < nb ? block_sum[b] : 0;
-        int total;
-        const int ex = cl_block_excl_scan(v, lds, &total);
-        if (b < nb) block_sum[b] = carry + ex;
-        __syncthreads();
-        if (threadIdx.x == 0) carry += total;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) block_sum[nb] = carry;
-}
 
 __device__ __forceinline__ int cl_class_of(int el, int q, const int *__restrict__ metals, int num_metals)
 {
@@ -122,20 +80,14 @@ __global__ __launch_bounds__(KMCF_BLOCK) void cl_classify_kernel(int N, const in
                                                                  int *__restrict__ stats)
 {
     __shared__ int lds[4];
-    const int t0 = blockIdx.x * CL_TILE + threadIdx.x * CL_ITEMS;
-    int c = 0;
-#pragma unroll
-    for (int k = 0; k < CL_ITEMS; ++k) {
-        const int i = t0 + k;
-        if (i < N) {
-            const int cl = cl_class_of(element[i], charge[i], metals, num_metals);
-            cls[i] = (unsigned char)cl;
-            parent[i] = i;
-            c += cl != CL_NONE;
-        }
-    }
-    int total;
-    cl_block_excl_scan(c, lds, &total);
+    int f[KMCF_SCAN_ITEMS];
+    kmcf_tile_flags(N, f, [&](int i) {
+        const int cl = cl_class_of(element[i], charge[i], metals, num_metals);
+        cls[i] = (unsigned char)cl;
+        parent[i] = i;
+        return cl != CL_NONE;
+    });
+    const int total = kmcf_tile_count(f, lds);
     if (threadIdx.x == 0) msum[blockIdx.x] = total;
     if (blockIdx.x == 0 && threadIdx.x < CL_STAT_WORDS) stats[threadIdx.x] = 0;
 }
@@ -145,17 +97,12 @@ __global__ __launch_bounds__(KMCF_BLOCK) void cl_member_scatter_kernel(int N, co
                                                                        const int *__restrict__ msum, int *__restrict__ members)
 {
     __shared__ int lds[4];
-    const int t0 = blockIdx.x * CL_TILE + threadIdx.x * CL_ITEMS;
-    int f[CL_ITEMS], c = 0;
+    const int t0 = kmcf_tile_item0();
+    int f[KMCF_SCAN_ITEMS];
+    kmcf_tile_flags(N, f, [&](int i) { return cls[i] != CL_NONE; });
+    int pos = kmcf_tile_pos(f, msum[blockIdx.x], lds);
 #pragma unroll
-    for (int k = 0; k < CL_ITEMS; ++k) {
-        const int i = t0 + k;
-        f[k] = (i < N) ? (cls[i] != CL_NONE) : 0;
-        c += f[k];
-    }
-    int pos = msum[blockIdx.x] + cl_block_excl_scan(c, lds, nullptr);
-#pragma unroll
-    for (int k = 0; k < CL_ITEMS; ++k)
+    for (int k = 0; k < KMCF_SCAN_ITEMS; ++k)
         if (f[k]) members[pos++] = t0 + k;
 }
 
@@ -341,26 +288,22 @@ __global__ __launch_bounds__(KMCF_BLOCK) void cl_root_count_kernel(int N, const 
                                                                    int *stats)
 {
     __shared__ int lds[4];
-    const int t0 = blockIdx.x * CL_TILE + threadIdx.x * CL_ITEMS;
-    int c = 0, v[5] = {0, 0, 0, 0, 0};
-#pragma unroll
-    for (int k = 0; k < CL_ITEMS; ++k) {
-        const int i = t0 + k;
-        if (i < N && label[i] == i) {
-            ++c;
-            if (cls[i] == CL_METAL) {
-                ++v[CL_STAT_METAL];
-            } else {
-                const int sz = size[i];
-                ++v[CL_STAT_VACANCY];
-                v[CL_STAT_LARGEST_VAC] = max(v[CL_STAT_LARGEST_VAC], sz);
-                if (touch[i] == 3) {
-                    ++v[CL_STAT_BRIDGING];
-                    v[CL_STAT_LARGEST_BRIDGING] = max(v[CL_STAT_LARGEST_BRIDGING], sz);
-                }
+    int f[KMCF_SCAN_ITEMS], v[5] = {0, 0, 0, 0, 0};
+    kmcf_tile_flags(N, f, [&](int i) {
+        if (label[i] != i) return false;
+        if (cls[i] == CL_METAL) {
+            ++v[CL_STAT_METAL];
+        } else {
+            const int sz = size[i];
+            ++v[CL_STAT_VACANCY];
+            v[CL_STAT_LARGEST_VAC] = max(v[CL_STAT_LARGEST_VAC], sz);
+            if (touch[i] == 3) {
+                ++v[CL_STAT_BRIDGING];
+                v[CL_STAT_LARGEST_BRIDGING] = max(v[CL_STAT_LARGEST_BRIDGING], sz);
             }
         }
-    }
+        return true;
+    });
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) {
 #pragma unroll
@@ -374,8 +317,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void cl_root_count_kernel(int N, const 
         for (int q = 3; q < 5; ++q)
             if (v[q]) atomicMax(stats + q, v[q]);
     }
-    int total;
-    cl_block_excl_scan(c, lds, &total);
+    const int total = kmcf_tile_count(f, lds);
     if (threadIdx.x == 0) rsum[blockIdx.x] = total;
 }
 
@@ -389,17 +331,12 @@ __global__ __launch_bounds__(KMCF_BLOCK) void cl_root_scatter_kernel(int N, int 
                                                                      kmcf_cluster_t *__restrict__ table, int cap, int *stats)
 {
     __shared__ int lds[4];
-    const int t0 = blockIdx.x * CL_TILE + threadIdx.x * CL_ITEMS;
-    int f[CL_ITEMS], c = 0;
+    const int t0 = kmcf_tile_item0();
+    int f[KMCF_SCAN_ITEMS];
+    kmcf_tile_flags(N, f, [&](int i) { return label[i] == i; });
+    int pos = kmcf_tile_pos(f, rsum[blockIdx.x], lds);
 #pragma unroll
-    for (int k = 0; k < CL_ITEMS; ++k) {
-        const int i = t0 + k;
-        f[k] = (i < N) ? (label[i] == i) : 0;
-        c += f[k];
-    }
-    int pos = rsum[blockIdx.x] + cl_block_excl_scan(c, lds, nullptr);
-#pragma unroll
-    for (int k = 0; k < CL_ITEMS; ++k) {
+    for (int k = 0; k < KMCF_SCAN_ITEMS; ++k) {
         if (!f[k]) continue;
         const int i = t0 + k;
         if (pos < cap) {
@@ -416,41 +353,28 @@ __global__ __launch_bounds__(KMCF_BLOCK) void cl_root_scatter_kernel(int N, int 
     }
 }
 
-template <typename T>
-int cl_alloc(T **p, size_t n)
-{
-    KMCF_HIP(hipMalloc(reinterpret_cast<void **>(p), n * sizeof(T)));
-    return KMCF_OK;
-}
-
 // workspace on the communicator, grown on demand and freed by kmcf_comm_destroy; it holds nothing a later call reads
 int cl_workspace(kmcf_comm *c, int N, int table_entries)
 {
     if (c->cl_ws && c->cl_ws->cap_N < N) kmcf_cluster_ws_free(c);
     if (!c->cl_ws) {
         kmcf_cluster_ws *w = c->cl_ws = new kmcf_cluster_ws();
-        const size_t n = (size_t)N, nb = (n + CL_TILE - 1) / CL_TILE + 1;
-        KMCF_TRY(cl_alloc(&w->d_cls, n));
-        KMCF_TRY(cl_alloc(&w->d_parent, n));
-        KMCF_TRY(cl_alloc(&w->d_members, n));
-        KMCF_TRY(cl_alloc(&w->d_label, n));
-        KMCF_TRY(cl_alloc(&w->d_size, n));
-        KMCF_TRY(cl_alloc(&w->d_touch, n));
-        KMCF_TRY(cl_alloc(&w->d_xmin, n));
-        KMCF_TRY(cl_alloc(&w->d_xmax, n));
-        KMCF_TRY(cl_alloc(&w->d_msum, nb));
-        KMCF_TRY(cl_alloc(&w->d_rsum, nb));
-        KMCF_TRY(cl_alloc(&w->d_stats, (size_t)CL_STAT_WORDS));
+        const size_t n = (size_t)N, nb = (n + KMCF_SCAN_TILE - 1) / KMCF_SCAN_TILE + 1;
+        KMCF_TRY(kmcf_dev_alloc(&w->d_cls, n, false));
+        KMCF_TRY(kmcf_dev_alloc(&w->d_parent, n, false));
+        KMCF_TRY(kmcf_dev_alloc(&w->d_members, n, false));
+        KMCF_TRY(kmcf_dev_alloc(&w->d_label, n, false));
+        KMCF_TRY(kmcf_dev_alloc(&w->d_size, n, false));
+        KMCF_TRY(kmcf_dev_alloc(&w->d_touch, n, false));
+        KMCF_TRY(kmcf_dev_alloc(&w->d_xmin, n, false));
+        KMCF_TRY(kmcf_dev_alloc(&w->d_xmax, n, false));
+        KMCF_TRY(kmcf_dev_alloc(&w->d_msum, nb, false));
+        KMCF_TRY(kmcf_dev_alloc(&w->d_rsum, nb, false));
+        KMCF_TRY(kmcf_dev_alloc(&w->d_stats, (size_t)CL_STAT_WORDS, false));
         w->cap_N = N;
     }
     kmcf_cluster_ws *w = c->cl_ws;
-    if (w->cap_table < table_entries) {
-        if (w->d_table) hipFree(w->d_table);
-        w->d_table = nullptr;
-        w->cap_table = 0;
-        KMCF_TRY(cl_alloc(&w->d_table, (size_t)table_entries));
-        w->cap_table = table_entries;
-    }
+    if (w->cap_table < (size_t)table_entries) KMCF_TRY(kmcf_dev_grow(&w->d_table, &w->cap_table, (size_t)table_entries, 0));
     return KMCF_OK;
 }
 
@@ -465,7 +389,7 @@ int kmcf_clusters_enqueue(kmcf_comm *c, int N, int nn, const int *d_neigh_idx, c
     kmcf_cluster_ws *w = c->cl_ws;
     hipStream_t st = c->stream;
     int *label = d_site_label ? d_site_label : w->d_label;
-    const int nb = (N + CL_TILE - 1) / CL_TILE;                   // tiles of the scans
+    const int nb = (N + KMCF_SCAN_TILE - 1) / KMCF_SCAN_TILE;     // tiles of the scans
     const int *n_members = w->d_msum + nb;
     const bool wide = nn > 8;                                     // 16 lanes per row, 4 for short rows
     const int per_block = KMCF_BLOCK / (wide ? 16 : 4);
@@ -477,7 +401,7 @@ int kmcf_clusters_enqueue(kmcf_comm *c, int N, int nn, const int *d_neigh_idx, c
 
     cl_classify_kernel<<<nb, KMCF_BLOCK, 0, st>>>(N, d_site_element, d_site_charge, d_metals, num_metals, w->d_cls, w->d_parent,
                                                  w->d_msum, w->d_stats);
-    cl_scan_kernel<<<1, KMCF_BLOCK, 0, st>>>(nb, w->d_msum);
+    kmcf_scan_counts_kernel<int><<<1, KMCF_BLOCK, 0, st>>>(nb, w->d_msum, w->d_msum, 0);
     cl_member_scatter_kernel<<<nb, KMCF_BLOCK, 0, st>>>(N, w->d_cls, w->d_msum, w->d_members);
     if (wide)
         cl_hook_kernel<16><<<(int)row_grid, KMCF_BLOCK, 0, st>>>(N, nn, d_neigh_idx, w->d_cls, w->d_members, n_members, w->d_parent);
@@ -492,7 +416,7 @@ int kmcf_clusters_enqueue(kmcf_comm *c, int N, int nn, const int *d_neigh_idx, c
         cl_touch_kernel<4><<<(int)row_grid, KMCF_BLOCK, 0, st>>>(N, nn, d_neigh_idx, w->d_cls, w->d_members, n_members, label, w->d_touch);
     if (summaries) {
         cl_root_count_kernel<<<nb, KMCF_BLOCK, 0, st>>>(N, w->d_cls, label, w->d_size, w->d_touch, w->d_rsum, w->d_stats);
-        cl_scan_kernel<<<1, KMCF_BLOCK, 0, st>>>(nb, w->d_rsum);
+        kmcf_scan_counts_kernel<int><<<1, KMCF_BLOCK, 0, st>>>(nb, w->d_rsum, w->d_rsum, 0);
         cl_root_scatter_kernel<<<nb, KMCF_BLOCK, 0, st>>>(N, nb, w->d_cls, label, w->d_size, w->d_touch, w->d_xmin, w->d_xmax, w->d_rsum,
                                                          n_members, w->d_table, cap, w->d_stats);
     }

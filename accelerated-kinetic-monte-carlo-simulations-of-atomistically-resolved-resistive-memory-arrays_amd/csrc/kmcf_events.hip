@@ -61,10 +61,8 @@ void kmcf_event_cache_free(kmcf_comm *c)
 {
     if (!c || !c->ev_cache) return;
     kmcf_event_cache *w = c->ev_cache;
-    void *ptrs[] = {w->d_type, w->d_prob, w->d_tsum, w->d_gsum, w->d_tot, w->d_ij, w->d_aff, w->d_asym, w->d_tbad,
-                    w->d_u, w->d_totlog, w->d_evlog, w->d_state, w->d_neigh_full, w->d_rsum, w->d_tsum2, w->d_gsum2};
-    for (void *p : ptrs)
-        if (p) hipFree(p);
+    kmcf_dev_free_all({w->d_type, w->d_prob, w->d_tsum, w->d_gsum, w->d_tot, w->d_ij, w->d_aff, w->d_asym, w->d_tbad,
+                       w->d_u, w->d_totlog, w->d_evlog, w->d_state, w->d_neigh_full, w->d_rsum, w->d_tsum2, w->d_gsum2});
     if (w->h_pin) hipHostFree(w->h_pin);
     delete w;
     c->ev_cache = nullptr;
@@ -99,6 +97,8 @@ __device__ __forceinline__ double v_solve_dev(double r_dist, int charge, double 
     return (double)charge * erfc(r_dist / (sigma * sqrt(2.0))) * k * q / r_dist;
 }
 
+// kmcf_block_sum (kmcf_block.hpp) with the wavefront step spelled as the shuffle loop: the same operands in the same order,
+// but other instructions.  Kept so that the kernels of the event step compile to the code they were measured with.
 __device__ __forceinline__ double block_sum_ev(double v, double *lds4)
 {
 #pragma unroll

@@ -8,7 +8,7 @@
 //   1    clear the per-cell words
 //   2    counts of the sides per gap cell and for the device                       [integer atomics, one set per wave and cell]
 //   3-5  compact, per INDEX cell (the cells of kmcf_compute_cutoff_list), the B members with their coordinates and gap
-//        cell, and the A members: flag count / scan / scatter as in kmcf_pairwise.hip, on scratch of this file's own
+//        cell, and the A members: the tile compaction of kmcf_block.hpp (two sets in one pass), on scratch of this file's own
 //        (kmcf_poisson_gridless keeps its lists)
 //   6    search: 16 lanes per A site walk the contiguous runs of the 27 surrounding index cells (r_max <= cell edge),
 //        every lane keeps its lexicographic minimum (d2, b); the group's minimum is stored per A site and lowers the gap
@@ -55,10 +55,8 @@ void kmcf_gap_ws_free(kmcf_pairwise *p)
 {
     if (!p || !p->gap_ws) return;
     kmcf_gap_ws *w = p->gap_ws;
-    void *ptrs[] = {w->d_side, w->d_bpos, w->d_sum, w->d_alist, w->d_acell, w->d_bsite, w->d_bcell, w->d_bx, w->d_by, w->d_bz,
-                    w->d_ad2, w->d_ab, w->d_stats, w->d_best, w->d_pair, w->d_cnt, w->d_gaps, w->d_prof};
-    for (void *q : ptrs)
-        if (q) hipFree(q);
+    kmcf_dev_free_all({w->d_side, w->d_bpos, w->d_sum, w->d_alist, w->d_acell, w->d_bsite, w->d_bcell, w->d_bx, w->d_by, w->d_bz,
+                       w->d_ad2, w->d_ab, w->d_stats, w->d_best, w->d_pair, w->d_cnt, w->d_gaps, w->d_prof});
     delete w;
     p->gap_ws = nullptr;
 }
@@ -66,31 +64,11 @@ void kmcf_gap_ws_free(kmcf_pairwise *p)
 namespace {
 
 typedef unsigned long long u64;
-constexpr int GP_ITEMS = 8, GP_TILE = KMCF_BLOCK * GP_ITEMS;      // flags per block of the scans
 constexpr int GP_LPS = 16, GP_SPB = KMCF_BLOCK / GP_LPS;          // lanes per A site, A sites per block
 constexpr u64 GP_INF = 0x7ff0000000000000ull;                    // bits of +infinity
 constexpr u64 GP_NO_PAIR = ~0ull;
 constexpr int GP_KIND_VACANCY = KMCF_CLUSTER_VACANCY;
 enum { GP_STAT_LEFT, GP_STAT_RIGHT, GP_STAT_BOTH, GP_STAT_BRIDGED, GP_STAT_OPEN, GP_STAT_NONE, GP_STAT_WORDS = 8 };
-
-__device__ __forceinline__ int gp_block_excl_scan(int v, int *lds, int *total)
-{
-    // exclusive scan of one int per thread over 256 threads (kmcf_pairwise.hip's)
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int s = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        int t = __shfl_up(s, off, 64);
-        if (lane >= off) s += t;
-    }
-    if (lane == 63) lds[w] = s;
-    __syncthreads();
-    int base = 0;
-    for (int i = 0; i < w; ++i) base += lds[i];
-    if (total) *total = lds[0] + lds[1] + lds[2] + lds[3];
-    __syncthreads();
-    return base + s - v;
-}
 
 // gap cell of a site, -1: none
 __device__ __forceinline__ int gp_cell(const int *__restrict__ site_cell, int n_cells, int i)
@@ -151,58 +129,28 @@ __global__ __launch_bounds__(KMCF_BLOCK) void gp_count_kernel(int N, const int *
     }
 }
 
-// members of the search: side bits of a site that lies in a gap cell
+// members of the search: side bits (A = 1, B = 2) of a site that lies in a gap cell
+constexpr int GP_A = 1, GP_B = 2;
 __device__ __forceinline__ int gp_flags(const int *__restrict__ side, const int *__restrict__ site_cell, int n_cells, int i)
 {
     const int s = side[i] & 3;
     return (s && gp_cell(site_cell, n_cells, i) >= 0) ? s : 0;
 }
 
-// 3: per-tile counts of the A and of the B members (index-cell order)
+// 3: per-tile counts of the A and of the B members (index-cell order): the A counts in sum[0, nb), the B counts in
+// sum[nb + 1, 2 nb + 1).  4 is kmcf_scan_counts_kernel on the two arrays, in place: totals in sum[nb] and sum[2 nb + 1]
 __global__ __launch_bounds__(KMCF_BLOCK) void gp_flag_count_kernel(int N, int nb, const int *__restrict__ cell_order,
                                                                    const int *__restrict__ side, const int *__restrict__ site_cell,
                                                                    int n_cells, int *__restrict__ sum)
 {
     __shared__ int lds[4];
-    const int t0 = blockIdx.x * GP_TILE + threadIdx.x * GP_ITEMS;
-    int ca = 0, cb = 0;
-#pragma unroll
-    for (int k = 0; k < GP_ITEMS; ++k) {
-        const int t = t0 + k;
-        if (t < N) {
-            const int f = gp_flags(side, site_cell, n_cells, cell_order[t]);
-            ca += f & 1;
-            cb += (f >> 1) & 1;
-        }
-    }
-    int ta, tb;
-    gp_block_excl_scan(ca, lds, &ta);
-    gp_block_excl_scan(cb, lds, &tb);
+    int f[KMCF_SCAN_ITEMS];
+    kmcf_tile_flags(N, f, [&](int t) { return gp_flags(side, site_cell, n_cells, cell_order[t]); });
+    const int ta = kmcf_tile_count(f, lds, GP_A), tb = kmcf_tile_count(f, lds, GP_B);
     if (threadIdx.x == 0) {
         sum[blockIdx.x] = ta;
         sum[nb + 1 + blockIdx.x] = tb;
     }
-}
-
-// 4: exclusive scan of the tile counts in place, totals into sum[nb]; block 0 the A counts, block 1 the B counts
-__global__ __launch_bounds__(KMCF_BLOCK) void gp_scan_kernel(int nb, int *__restrict__ sum)
-{
-    __shared__ int lds[4];
-    __shared__ int carry;
-    int *block_sum = sum + (size_t)blockIdx.x * (nb + 1);
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int b0 = 0; b0 < nb; b0 += KMCF_BLOCK) {
-        const int b = b0 + threadIdx.x;
-        const int v = b < nb ? block_sum[b] : 0;
-        int total;
-        const int ex = gp_block_excl_scan(v, lds, &total);
-        if (b < nb) block_sum[b] = carry + ex;
-        __syncthreads();
-        if (threadIdx.x == 0) carry += total;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) block_sum[nb] = carry;
 }
 
 // 5: positions of the B flags (every slot of the cell order: the runs of the search start at cell boundaries), the B
@@ -218,32 +166,25 @@ __global__ __launch_bounds__(KMCF_BLOCK) void gp_scatter_kernel(int N, int nb, c
                                                                 double *__restrict__ bz)
 {
     __shared__ int lds[4];
-    const int t0 = blockIdx.x * GP_TILE + threadIdx.x * GP_ITEMS;
-    int f[GP_ITEMS], site[GP_ITEMS], ca = 0, cb = 0;
+    const int t0 = kmcf_tile_item0();
+    int f[KMCF_SCAN_ITEMS], site[KMCF_SCAN_ITEMS];
+    kmcf_tile_flags(N, f, [&](int t) { return gp_flags(side, site_cell, n_cells, site[t - t0] = cell_order[t]); });
+    int pa = kmcf_tile_pos(f, sum[blockIdx.x], lds, GP_A);
+    int pb = kmcf_tile_pos(f, sum[nb + 1 + blockIdx.x], lds, GP_B);
 #pragma unroll
-    for (int k = 0; k < GP_ITEMS; ++k) {
-        const int t = t0 + k;
-        site[k] = t < N ? cell_order[t] : -1;
-        f[k] = t < N ? gp_flags(side, site_cell, n_cells, site[k]) : 0;
-        ca += f[k] & 1;
-        cb += (f[k] >> 1) & 1;
-    }
-    int pa = sum[blockIdx.x] + gp_block_excl_scan(ca, lds, nullptr);
-    int pb = sum[nb + 1 + blockIdx.x] + gp_block_excl_scan(cb, lds, nullptr);
-#pragma unroll
-    for (int k = 0; k < GP_ITEMS; ++k) {
+    for (int k = 0; k < KMCF_SCAN_ITEMS; ++k) {
         const int t = t0 + k;
         if (t >= N) break;
         bpos[t] = pb;
         if (!f[k]) continue;
         const int i = site[k];
         const int c = gp_cell(site_cell, n_cells, i);
-        if (f[k] & 1) {
+        if (f[k] & GP_A) {
             alist[pa] = i;
             acell[pa] = c;
             ++pa;
         }
-        if (f[k] & 2) {
+        if (f[k] & GP_B) {
             bsite[pb] = i;
             bcell[pb] = c;
             bx[pb] = x[i];
@@ -253,17 +194,6 @@ __global__ __launch_bounds__(KMCF_BLOCK) void gp_scatter_kernel(int N, int nb, c
         }
     }
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x == KMCF_BLOCK - 1) bpos[N] = sum[2 * nb + 1];
-}
-
-struct gp_grid {
-    double x0, y0, z0, inv, edge;
-    int ncx, ncy, ncz;
-};
-
-__device__ __forceinline__ int gp_coord(double v, double v0, double inv, int nc)
-{
-    int c = (int)floor((v - v0) * inv);      // kmcf_pairwise.hip's cell rule
-    return c < 0 ? 0 : (c >= nc ? nc - 1 : c);
 }
 
 // Lower bound of |v_b - v| over the sites b of index cell column `a` next to the column `c` of v (a = c - 1 or c + 1):
@@ -279,7 +209,7 @@ __device__ __forceinline__ u64 gp_load(const u64 *p) { return __hip_atomic_load(
 
 // 6: the search.  A group of GP_LPS lanes per A member; the loop runs over whole blocks of groups, so every lane of a wave
 // reaches the shuffles behind it.
-__global__ __launch_bounds__(KMCF_BLOCK) void gp_search_kernel(gp_grid g, const int *__restrict__ cell_start,
+__global__ __launch_bounds__(KMCF_BLOCK) void gp_search_kernel(kmcf_cell_grid g, const int *__restrict__ cell_start,
                                                                const int *__restrict__ bpos, const int *__restrict__ n_a,
                                                                const int *__restrict__ alist, const int *__restrict__ acell,
                                                                const int *__restrict__ bsite, const int *__restrict__ bcell,
@@ -302,8 +232,8 @@ __global__ __launch_bounds__(KMCF_BLOCK) void gp_search_kernel(gp_grid g, const 
             const int a = alist[k];
             ca = acell[k];
             const double xa = x[a], ya = y[a], za = z[a];
-            const int cx = gp_coord(xa, g.x0, g.inv, g.ncx), cy = gp_coord(ya, g.y0, g.inv, g.ncy),
-                      cz = gp_coord(za, g.z0, g.inv, g.ncz);
+            const int cx = kmcf_cell_coord(xa, g.x0, g.inv, g.ncx), cy = kmcf_cell_coord(ya, g.y0, g.inv, g.ncy),
+                      cz = kmcf_cell_coord(za, g.z0, g.inv, g.ncz);
             double thr = rmax2;             // no pair with a larger d2 can be the result (uniform over the group)
             // (the group's first lane's read for all of them: the loops below must not part the group's lanes)
             const double seen = __shfl(__longlong_as_double((long long)gp_load(best + ca)), 0, GP_LPS);
@@ -416,56 +346,37 @@ __global__ __launch_bounds__(KMCF_BLOCK) void gp_profile_kernel(int N, const uns
     if (t >= 0.0 && t < (double)n_bins) atomicAdd(prof + ((size_t)c * n_bins + (int)t) * 3 + (s - 1), 1);
 }
 
-template <typename T>
-int gp_alloc(T **p, size_t n)
-{
-    KMCF_HIP(hipMalloc(reinterpret_cast<void **>(p), n * sizeof(T)));
-    return KMCF_OK;
-}
-
-template <typename T>
-int gp_grow(T **p, size_t n)
-{
-    if (*p) hipFree(*p);
-    *p = nullptr;
-    return gp_alloc(p, n);
-}
-
 // scratch on the index, grown on demand and freed by kmcf_pairwise_destroy; it holds nothing a later call reads
 int gp_workspace(kmcf_pairwise *p, size_t n_cells, size_t prof_words)
 {
     if (!p->gap_ws) {
         kmcf_gap_ws *w = p->gap_ws = new kmcf_gap_ws();
-        const size_t n = (size_t)p->N, nb = (n + GP_TILE - 1) / GP_TILE;
+        const size_t n = (size_t)p->N, nb = (n + KMCF_SCAN_TILE - 1) / KMCF_SCAN_TILE;
         w->N = p->N;
-        KMCF_TRY(gp_alloc(&w->d_side, n));
-        KMCF_TRY(gp_alloc(&w->d_bpos, n + 1));
-        KMCF_TRY(gp_alloc(&w->d_sum, 2 * (nb + 1)));
-        KMCF_TRY(gp_alloc(&w->d_alist, n));
-        KMCF_TRY(gp_alloc(&w->d_acell, n));
-        KMCF_TRY(gp_alloc(&w->d_bsite, n));
-        KMCF_TRY(gp_alloc(&w->d_bcell, n));
-        KMCF_TRY(gp_alloc(&w->d_bx, n));
-        KMCF_TRY(gp_alloc(&w->d_by, n));
-        KMCF_TRY(gp_alloc(&w->d_bz, n));
-        KMCF_TRY(gp_alloc(&w->d_ad2, n));
-        KMCF_TRY(gp_alloc(&w->d_ab, n));
-        KMCF_TRY(gp_alloc(&w->d_stats, (size_t)GP_STAT_WORDS));
+        KMCF_TRY(kmcf_dev_alloc(&w->d_side, n, false));
+        KMCF_TRY(kmcf_dev_alloc(&w->d_bpos, n + 1, false));
+        KMCF_TRY(kmcf_dev_alloc(&w->d_sum, 2 * (nb + 1), false));
+        KMCF_TRY(kmcf_dev_alloc(&w->d_alist, n, false));
+        KMCF_TRY(kmcf_dev_alloc(&w->d_acell, n, false));
+        KMCF_TRY(kmcf_dev_alloc(&w->d_bsite, n, false));
+        KMCF_TRY(kmcf_dev_alloc(&w->d_bcell, n, false));
+        KMCF_TRY(kmcf_dev_alloc(&w->d_bx, n, false));
+        KMCF_TRY(kmcf_dev_alloc(&w->d_by, n, false));
+        KMCF_TRY(kmcf_dev_alloc(&w->d_bz, n, false));
+        KMCF_TRY(kmcf_dev_alloc(&w->d_ad2, n, false));
+        KMCF_TRY(kmcf_dev_alloc(&w->d_ab, n, false));
+        KMCF_TRY(kmcf_dev_alloc(&w->d_stats, (size_t)GP_STAT_WORDS, false));
     }
     kmcf_gap_ws *w = p->gap_ws;
-    if (w->cap_cells < n_cells) {
+    if (w->cap_cells < n_cells) {                      // four buffers of one capacity, exact size
         w->cap_cells = 0;
-        KMCF_TRY(gp_grow(&w->d_best, n_cells));
-        KMCF_TRY(gp_grow(&w->d_pair, n_cells));
-        KMCF_TRY(gp_grow(&w->d_cnt, 3 * n_cells));
-        KMCF_TRY(gp_grow(&w->d_gaps, n_cells));
+        KMCF_TRY(kmcf_dev_grow(&w->d_best, nullptr, n_cells, 0));
+        KMCF_TRY(kmcf_dev_grow(&w->d_pair, nullptr, n_cells, 0));
+        KMCF_TRY(kmcf_dev_grow(&w->d_cnt, nullptr, 3 * n_cells, 0));
+        KMCF_TRY(kmcf_dev_grow(&w->d_gaps, nullptr, n_cells, 0));
         w->cap_cells = n_cells;
     }
-    if (w->cap_prof < prof_words) {
-        w->cap_prof = 0;
-        KMCF_TRY(gp_grow(&w->d_prof, prof_words));
-        w->cap_prof = prof_words;
-    }
+    if (w->cap_prof < prof_words) KMCF_TRY(kmcf_dev_grow(&w->d_prof, &w->cap_prof, prof_words, 0));
     return KMCF_OK;
 }
 
@@ -494,7 +405,7 @@ int gp_enqueue(kmcf_pairwise *p, const double *d_x, const double *d_y, const dou
     kmcf_gap_ws *w = p->gap_ws;
     hipStream_t st = p->comm->stream;
     const int N = p->N;
-    const int nb = (N + GP_TILE - 1) / GP_TILE;
+    const int nb = (N + KMCF_SCAN_TILE - 1) / KMCF_SCAN_TILE;
     const int site_grid = (N + KMCF_BLOCK - 1) / KMCF_BLOCK;
     const size_t nc = (size_t)n_cells;
     const int cell_grid = (int)((nc + KMCF_BLOCK - 1) / KMCF_BLOCK);
@@ -503,16 +414,15 @@ int gp_enqueue(kmcf_pairwise *p, const double *d_x, const double *d_y, const dou
     if (search_grid > 8192) search_grid = 8192;
     int64_t pair_grid = site_grid;
     if (pair_grid > 2048) pair_grid = 2048;
-    gp_grid g{p->x0, p->y0, p->z0, p->inv, p->cutoff, p->ncx, p->ncy, p->ncz};
 
     gp_clear_kernel<<<cell_grid, KMCF_BLOCK, 0, st>>>(nc, w->d_best, w->d_pair, w->d_cnt, w->d_stats);
     gp_count_kernel<<<site_grid, KMCF_BLOCK, 0, st>>>(N, d_side, d_site_cell, n_cells, w->d_cnt, w->d_stats);
     gp_flag_count_kernel<<<nb, KMCF_BLOCK, 0, st>>>(N, nb, p->d_cell_order, d_side, d_site_cell, n_cells, w->d_sum);
-    gp_scan_kernel<<<2, KMCF_BLOCK, 0, st>>>(nb, w->d_sum);
+    kmcf_scan_counts_kernel<int><<<2, KMCF_BLOCK, 0, st>>>(nb, w->d_sum, w->d_sum, nb + 1);
     gp_scatter_kernel<<<nb, KMCF_BLOCK, 0, st>>>(N, nb, p->d_cell_order, d_side, d_site_cell, n_cells, d_x, d_y, d_z, w->d_sum,
                                                 w->d_bpos, w->d_alist, w->d_acell, w->d_bsite, w->d_bcell, w->d_bx, w->d_by,
                                                 w->d_bz);
-    gp_search_kernel<<<(int)search_grid, KMCF_BLOCK, 0, st>>>(g, p->d_cell_start, w->d_bpos, n_a, w->d_alist, w->d_acell,
+    gp_search_kernel<<<(int)search_grid, KMCF_BLOCK, 0, st>>>(p->grid(), p->d_cell_start, w->d_bpos, n_a, w->d_alist, w->d_acell,
                                                              w->d_bsite, w->d_bcell, w->d_bx, w->d_by, w->d_bz, d_x, d_y, d_z,
                                                              r_max * r_max, w->d_best, w->d_ad2, w->d_ab);
     gp_pair_kernel<<<(int)pair_grid, KMCF_BLOCK, 0, st>>>(n_a, w->d_alist, w->d_acell, w->d_ad2, w->d_ab, w->d_best, w->d_pair);

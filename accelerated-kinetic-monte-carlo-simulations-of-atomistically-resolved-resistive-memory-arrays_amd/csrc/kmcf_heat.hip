@@ -15,12 +15,6 @@
 
 namespace {
 
-int grid_rows(int64_t n, int cap = 2048)
-{
-    int64_t g = (n + KMCF_BLOCK - 1) / KMCF_BLOCK;
-    return (int)std::max<int64_t>(1, std::min<int64_t>(g, cap));
-}
-
 // pair class: 0 both metal, 1 both uncharged vacancies, 2 any other pair (site classes of site_class_kernel:
 // bit 0 metal, bit 1 uncharged vacancy)
 __device__ __forceinline__ int heat_class(unsigned char ci, unsigned char cj)
@@ -215,23 +209,13 @@ __global__ __launch_bounds__(KMCF_BLOCK) void heat_contacts_kernel(double *__res
         if (i < n_left || i >= n_left + n_interface) T[i] = T0;
 }
 
-__device__ __forceinline__ double block_sum_t(double v, double *lds4)
-{
-    v = kmcf_wave_sum64(v);
-    if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = (lds4[0] + lds4[1]) + (lds4[2] + lds4[3]);
-    __syncthreads();
-    return t;
-}
-
 // sum of T over [first, first + n): per-block partials, then one block adds them into part[0]
 __global__ __launch_bounds__(KMCF_BLOCK) void tsum_partial_kernel(const double *__restrict__ T, int first, int n, double *__restrict__ part)
 {
     __shared__ double lds4[4];
     double s = 0.0;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) s += T[first + i];
-    const double t = block_sum_t(s, lds4);
+    const double t = kmcf_block_sum(s, lds4);
     if (threadIdx.x == 0) part[blockIdx.x] = t;
 }
 
@@ -240,7 +224,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void tsum_final_kernel(double *__restri
     __shared__ double lds4[4];
     double s = 0.0;
     for (int i = threadIdx.x; i < npart; i += KMCF_BLOCK) s += part[i];
-    const double t = block_sum_t(s, lds4);        // (every lane has read its partials before the block's first barrier)
+    const double t = kmcf_block_sum(s, lds4);        // (every lane has read its partials before the block's first barrier)
     if (threadIdx.x == 0) part[0] = t;
 }
 
@@ -324,7 +308,7 @@ extern "C" int kmcf_update_temperature_local(kmcf_kstate *k, const int *d_site_e
             if (m->coded && m->spmv_kind == 2 && m->tiles_for_coded && m->n_short == m->n_loc)
                 heat_assemble_tile_kernel<<<std::min(m->n_tiles, 8 * 256 * 4), KMCF_BLOCK, 0, c->stream>>>(a, m->n_tiles, m->d_tile, m->d_wcol);
             else
-                heat_assemble_kernel<16><<<grid_rows((int64_t)m->n_loc * 16), KMCF_BLOCK, 0, c->stream>>>(a);
+                heat_assemble_kernel<16><<<kmcf_grid1d((int64_t)m->n_loc * 16), KMCF_BLOCK, 0, c->stream>>>(a);
             KMCF_HIP(hipGetLastError());
         }
         KMCF_HIP(hipEventRecord(a1, c->stream));
@@ -342,13 +326,13 @@ extern "C" int kmcf_update_temperature_local(kmcf_kstate *k, const int *d_site_e
         *stats = kmcf_solve_stats_t{};
         stats->converged = 1;
     }
-    heat_contacts_kernel<<<grid_rows(N), KMCF_BLOCK, 0, c->stream>>>(d_site_temperature, N, N_left_tot, k->N_interface, T0);
+    heat_contacts_kernel<<<kmcf_grid1d(N), KMCF_BLOCK, 0, c->stream>>>(d_site_temperature, N, N_left_tot, k->N_interface, T0);
     KMCF_HIP(hipGetLastError());
     // replicated on every rank (as kmcf_sum_and_gather_potential replicates the potential), then the mean of the
     // interface sites, added in the same order on every rank
     KMCF_TRY(kmcf_comm_allgatherv_double(c, d_site_temperature + N_left_tot, m->counts.data(), m->displs.data()));
     double *d_part = c->d_scratch;            // 1024 doubles of persistent scratch
-    const int g = grid_rows(k->N_interface, 1024);
+    const int g = kmcf_grid1d(k->N_interface, 1024);
     tsum_partial_kernel<<<g, KMCF_BLOCK, 0, c->stream>>>(d_site_temperature, N_left_tot, k->N_interface, d_part);
     KMCF_HIP(hipGetLastError());
     tsum_final_kernel<<<1, KMCF_BLOCK, 0, c->stream>>>(d_part, g);

@@ -7,7 +7,9 @@
 #include <cstdint>
 #include <cstdio>
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
+#include <initializer_list>
 #include <mutex>
 #include <type_traits>
 #include <vector>
@@ -161,8 +163,60 @@ int kmcf_clusters_enqueue(kmcf_comm *c, int N, int nn, const int *d_neigh_idx, c
                           const int *d_site_charge, const int *d_metals, int num_metals, const double *d_x, int N_left_tot,
                           int N_right_tot, int *d_site_label, bool summaries, int table_cap, kmcf_cluster_dev *out);
 
+// ---------------------------------------------------------------- device buffers and 1-D grids
+// n elements, zeroed on request.  The one place that calls hipMalloc for a typed buffer.
+template <typename T>
+int kmcf_dev_alloc(T **d, size_t n, bool zero)
+{
+    KMCF_HIP(hipMalloc(reinterpret_cast<void **>(d), n * sizeof(T)));
+    if (zero) KMCF_HIP(hipMemset(*d, 0, n * sizeof(T)));
+    return KMCF_OK;
+}
+
+// *d holds at least `need` elements afterwards.  A buffer that is missing or smaller is freed and replaced by one of
+// need + slack elements (contents are not kept, nothing is zeroed).  cap == nullptr: the caller keeps the capacity
+// itself (several buffers of one size) and the buffer is replaced unconditionally.
+template <typename T>
+int kmcf_dev_grow(T **d, size_t *cap, size_t need, size_t slack)
+{
+    if (cap && *d && need <= *cap) return KMCF_OK;
+    T *old = *d;
+    *d = nullptr;                      // (before the free: a failed free leaves no pointer behind for the destructor)
+    if (cap) *cap = 0;
+    if (old) KMCF_HIP(hipFree(old));
+    KMCF_TRY(kmcf_dev_alloc(d, need + slack, false));
+    if (cap) *cap = need + slack;
+    return KMCF_OK;
+}
+
+inline void kmcf_dev_free_all(std::initializer_list<void *> ptrs)
+{
+    for (void *p : ptrs)
+        if (p) hipFree(p);
+}
+
+// blocks of KMCF_BLOCK threads for n items of a grid-stride kernel: at least 1, at most cap
+inline int kmcf_grid1d(int64_t n, int cap = 2048)
+{
+    const int64_t g = (n + KMCF_BLOCK - 1) / KMCF_BLOCK;
+    return (int)std::max<int64_t>(1, std::min<int64_t>(g, cap));
+}
+
 // Spatial index of the sites (kmcf_pairwise.hip: kmcf_compute_cutoff_list): cells of edge `cutoff`, cell id
 // (cx * ncy + cy) * ncz + cz, so the cells (cx, cy, cz-1..cz+1) are one contiguous run of d_cell_order.
+// kmcf_cell_grid is what the kernels that walk it take (pairwise_kernel, gp_search_kernel): origin, inverse edge, edge,
+// cell counts; kmcf_cell_coord is the cell rule along one axis.
+struct kmcf_cell_grid {
+    double x0, y0, z0, inv, edge;
+    int ncx, ncy, ncz;
+};
+
+__host__ __device__ inline int kmcf_cell_coord(double v, double v0, double inv, int nc)
+{
+    const int c = (int)floor((v - v0) * inv);
+    return c < 0 ? 0 : (c >= nc ? nc - 1 : c);
+}
+
 struct kmcf_pairwise {
     kmcf_comm *comm = nullptr;
     int N = 0;
@@ -177,6 +231,7 @@ struct kmcf_pairwise {
     int *d_clist = nullptr;        // compacted charged sites (cell order), N
     int n_blocks = 0;
     struct kmcf_gap_ws *gap_ws = nullptr;   // scratch of kmcf_site_set_gap / kmcf_filament_gap (kmcf_gap.hip): buffers only
+    kmcf_cell_grid grid() const { return kmcf_cell_grid{x0, y0, z0, inv, cutoff, ncx, ncy, ncz}; }
 };
 void kmcf_gap_ws_free(kmcf_pairwise *p);
 
@@ -663,4 +718,6 @@ __device__ __forceinline__ double kmcf_wave_sum64(double v)
     v += kmcf_dpp_f64<0xB1>(v);       // quad_perm [1,0,3,2] = lane ^ 1
     return v;
 }
+
+#include "kmcf_block.hpp"             // block sum / max / scan and the tile compaction, shared by every pass
 #endif

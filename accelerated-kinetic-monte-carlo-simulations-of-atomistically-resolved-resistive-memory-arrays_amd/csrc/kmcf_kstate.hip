@@ -360,22 +360,12 @@ __global__ __launch_bounds__(KMCF_BLOCK) void k_rhs_contacts_kernel(
 }
 
 // ---------------------------------------------------------------- heat
-__device__ __forceinline__ double block_sum_h(double v, double *lds4)
-{
-    v = kmcf_wave_sum64(v);
-    if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = (lds4[0] + lds4[1]) + (lds4[2] + lds4[3]);
-    __syncthreads();
-    return t;
-}
-
 __global__ __launch_bounds__(KMCF_BLOCK) void power_partial_kernel(const double *__restrict__ p, int N, double *__restrict__ part)
 {
     __shared__ double lds4[4];
     double s = 0.0;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < N; i += gridDim.x * blockDim.x) s += p[i];
-    double t = block_sum_h(s, lds4);
+    double t = kmcf_block_sum(s, lds4);
     if (threadIdx.x == 0) part[blockIdx.x] = t;
 }
 
@@ -387,7 +377,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void temp_update_kernel(const double *_
     __shared__ double lds4[4];
     double s = 0.0;
     for (int i = threadIdx.x; i < npart; i += KMCF_BLOCK) s += part[i];
-    double P_tot = block_sum_h(s, lds4);
+    double P_tot = kmcf_block_sum(s, lds4);
     if (threadIdx.x == 0) {
         double c_coeff = b_coeff + P_tot / C_thermal * small_step;
         double T_intermediate = *T_bg;
@@ -482,13 +472,13 @@ extern "C" int kmcf_initialize_sparsity_K(kmcf_comm *c, const double *d_x, const
     KMCF_TRY(upload(&k->d_left_col, k->h_left_col));
     KMCF_TRY(upload(&k->d_right_row_ptr, k->h_right_row_ptr));
     KMCF_TRY(upload(&k->d_right_col, k->h_right_col));
-    const size_t nb = std::max(n_loc, 1) * sizeof(double);
-    KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&k->d_cls), std::max(N, 1)));
-    KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&k->d_cls_col), (size_t)std::max(n_loc + k->K->n_halo, 1)));
-    KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&k->d_diag), nb));
-    KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&k->d_left), nb));
-    KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&k->d_right), nb));
-    KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&k->d_rhs), nb));
+    const size_t nl1 = (size_t)std::max(n_loc, 1);
+    KMCF_TRY(kmcf_dev_alloc(&k->d_cls, (size_t)std::max(N, 1), false));
+    KMCF_TRY(kmcf_dev_alloc(&k->d_cls_col, (size_t)std::max(n_loc + k->K->n_halo, 1), false));
+    KMCF_TRY(kmcf_dev_alloc(&k->d_diag, nl1, false));
+    KMCF_TRY(kmcf_dev_alloc(&k->d_left, nl1, false));
+    KMCF_TRY(kmcf_dev_alloc(&k->d_right, nl1, false));
+    KMCF_TRY(kmcf_dev_alloc(&k->d_rhs, nl1, false));
     *out = k;
     return KMCF_OK;
 }
@@ -499,10 +489,8 @@ extern "C" int kmcf_kstate_destroy(kmcf_kstate *k)
     if (k->comm && k->comm->device >= 0) {
         hipSetDevice(k->comm->device);
         hipStreamSynchronize(k->comm->stream);
-        void *ptrs[] = {k->d_left_row_ptr, k->d_left_col, k->d_right_row_ptr, k->d_right_col, k->d_diag_pos, k->d_crow, k->d_cls, k->d_cls_col,
-                        k->d_diag, k->d_left, k->d_right, k->d_rhs, k->d_gather};
-        for (void *p : ptrs)
-            if (p) hipFree(p);
+        kmcf_dev_free_all({k->d_left_row_ptr, k->d_left_col, k->d_right_row_ptr, k->d_right_col, k->d_diag_pos, k->d_crow, k->d_cls,
+                           k->d_cls_col, k->d_diag, k->d_left, k->d_right, k->d_rhs, k->d_gather});
     }
     kmcf_matrix_destroy(k->K);
     delete k;
@@ -533,7 +521,7 @@ extern "C" int kmcf_update_charge(kmcf_comm *c, const int *d_site_element, int *
     const int count = h_count[c->rank], displ = h_displ[c->rank];
     KMCF_CHECK(displ >= 0 && displ + count <= N, KMCF_ERR_ARG, "kmcf_update_charge: rows [%d,%d) outside N=%d", displ, displ + count, N);
     if (count > 0) {
-        update_charge_kernel<<<grid1d((int64_t)count * 16), KMCF_BLOCK, 0, c->stream>>>(
+        update_charge_kernel<<<kmcf_grid1d((int64_t)count * 16), KMCF_BLOCK, 0, c->stream>>>(
             d_site_element, d_site_charge, d_neigh_idx, nn, d_metals, num_metals, displ, count);
         KMCF_HIP(hipGetLastError());
     }
@@ -552,11 +540,11 @@ int kmcf_k_classes_async(kmcf_kstate *k, const int *d_site_element, const int *d
 {
     kmcf_comm *c = k->comm;
     kmcf_matrix *m = k->K;
-    site_class_kernel<<<grid1d(k->N), KMCF_BLOCK, 0, c->stream>>>(d_site_element, d_site_charge, d_metals, num_metals, k->N, k->d_cls);
+    site_class_kernel<<<kmcf_grid1d(k->N), KMCF_BLOCK, 0, c->stream>>>(d_site_element, d_site_charge, d_metals, num_metals, k->N, k->d_cls);
     KMCF_HIP(hipGetLastError());
     if (m->n_loc > 0) {
         const int n_cols = m->n_loc + m->n_halo;
-        cls_col_kernel<<<grid1d(n_cols), KMCF_BLOCK, 0, c->stream>>>(n_cols, m->n_loc, k->N_left + m->row0, k->N_left, m->d_perm,
+        cls_col_kernel<<<kmcf_grid1d(n_cols), KMCF_BLOCK, 0, c->stream>>>(n_cols, m->n_loc, k->N_left + m->row0, k->N_left, m->d_perm,
                                                                     m->d_halo_gid, k->d_cls, k->d_cls_col);
         KMCF_HIP(hipGetLastError());
     }
@@ -572,7 +560,7 @@ static int k_assemble_async(kmcf_kstate *k, const int *d_site_element, const int
     KMCF_TRY(kmcf_k_classes_async(k, d_site_element, d_site_charge, d_metals, num_metals));
     if (m->n_loc > 0) {
         constexpr int LPR = 16;
-        const int grid = grid1d((int64_t)m->n_loc * LPR);
+        const int grid = kmcf_grid1d((int64_t)m->n_loc * LPR);
         // window SpMV: the off-diagonals are -high_G / -low_G, so the assembly writes their dictionary codes
         // next to the values and the CG's SpMV streams 2 B/nnz (kmcf_internal.hpp, kmcf_matrix::coded)
         const double dict[2] = {-high_G, -low_G};
@@ -611,7 +599,7 @@ static int k_assemble_contacts_async(kmcf_kstate *k, const int *d_site_element, 
     kmcf_matrix *m = k->K;
     KMCF_TRY(k_assemble_async(k, d_site_element, d_site_charge, d_metals, num_metals, 0.0, high_G, low_G));
     const int work = std::max(k->n_crow, k->N_left + k->N_right);
-    k_rhs_contacts_kernel<<<grid1d(work), KMCF_BLOCK, 0, c->stream>>>(
+    k_rhs_contacts_kernel<<<kmcf_grid1d(work), KMCF_BLOCK, 0, c->stream>>>(
         k->n_crow, k->d_crow, m->d_perm, k->d_left_row_ptr, k->d_left_col, k->d_right_row_ptr, k->d_right_col, k->d_cls,
         k->d_cls_col, k->N_left, k->N_interface, k->N_right, d_V, high_G, low_G, k->d_rhs, c->d_bad_site);
     KMCF_HIP(hipGetLastError());
@@ -687,7 +675,7 @@ extern "C" int kmcf_update_CB_edge_sparse(kmcf_kstate *k, const int *d_site_elem
     KMCF_TRY(kmcf_vec_out(m, v_soln, m->d_x));
     // replicated on every rank (as kmcf_sum_and_gather_potential replicates the potential); contacts and units after that
     if (multi) KMCF_TRY(kmcf_comm_allgatherv_double(c, d_site_CB_edge + N_left_tot, m->counts.data(), m->displs.data()));
-    cb_finish_kernel<<<grid1d(N), KMCF_BLOCK, 0, c->stream>>>(d_site_CB_edge, N, N_left_tot, k->N_interface, Vd, 1.60217663e-19);
+    cb_finish_kernel<<<kmcf_grid1d(N), KMCF_BLOCK, 0, c->stream>>>(d_site_CB_edge, N, N_left_tot, k->N_interface, Vd, 1.60217663e-19);
     KMCF_HIP(hipGetLastError());
     KMCF_HIP(hipStreamSynchronize(c->stream));
     return kmcf_p2p_check(c);
@@ -835,7 +823,7 @@ extern "C" int kmcf_sum_and_gather_potential(kmcf_kstate *k, double *d_site_pote
     // MPI_Gatherv to rank 0 (src/kmc_main.cpp:367-384) + MPI_Bcast (potential_solver_gpu.cu:1133-1136)
     KMCF_TRY(kmcf_comm_allgatherv_double(c, d_site_potential_boundary + num_atoms_first_layer,
                                          k->K->counts.data(), k->K->displs.data()));
-    sum_ab_kernel<<<grid1d(N), KMCF_BLOCK, 0, c->stream>>>(d_site_potential_charge, d_site_potential_boundary, N);
+    sum_ab_kernel<<<kmcf_grid1d(N), KMCF_BLOCK, 0, c->stream>>>(d_site_potential_charge, d_site_potential_boundary, N);
     KMCF_HIP(hipGetLastError());
     KMCF_HIP(hipStreamSynchronize(c->stream));
     return kmcf_p2p_check(c);
@@ -849,7 +837,7 @@ extern "C" int kmcf_update_temperature_global(kmcf_comm *c, const double *d_site
     KMCF_CHECK(c->device >= 0, KMCF_ERR_STATE, "kmcf_update_temperature_global: host-only communicator");
     KMCF_TRY(kmcf_enter(c));
     double *d_part = c->d_scratch;            // persistent: the reference allocates nothing per call either
-    const int g = grid1d(N, 1024);
+    const int g = kmcf_grid1d(N, 1024);
     power_partial_kernel<<<g, KMCF_BLOCK, 0, c->stream>>>(d_site_power, N, d_part);
     KMCF_HIP(hipGetLastError());
     temp_update_kernel<<<1, KMCF_BLOCK, 0, c->stream>>>(d_part, g, d_T_bg, a_coeff, b_coeff, number_steps, C_thermal, small_step);
@@ -877,7 +865,7 @@ extern "C" int kmcf_neighbor_list(kmcf_comm *c, const double *d_x, const double 
     hipStream_t ss = kmcf_setup_stream(c);                       // (the caller's stream: see kmcf_internal.hpp)
     KMCF_HIP(hipMemsetAsync(d_over, 0, sizeof(int), ss));
     if (count > 0) {
-        neighbor_list_kernel<<<grid1d(count, 1 << 20), KMCF_BLOCK, 0, ss>>>(
+        neighbor_list_kernel<<<kmcf_grid1d(count, 1 << 20), KMCF_BLOCK, 0, ss>>>(
             hc.g, hc.d_cell_start, hc.d_cell_items, d_x, d_y, d_z, nn_dist, N, nn, count, displ, d_neigh_idx, d_over);
         KMCF_HIP(hipGetLastError());
     }

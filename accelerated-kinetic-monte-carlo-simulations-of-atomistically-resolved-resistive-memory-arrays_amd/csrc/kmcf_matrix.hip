@@ -23,17 +23,8 @@ namespace {
 template <typename T>
 int dev_upload(T **d, const std::vector<T> &h)
 {
-    size_t bytes = std::max<size_t>(h.size(), 1) * sizeof(T);
-    KMCF_HIP(hipMalloc(reinterpret_cast<void **>(d), bytes));
+    KMCF_TRY(kmcf_dev_alloc(d, std::max<size_t>(h.size(), 1), false));
     if (!h.empty()) KMCF_HIP(hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-    return KMCF_OK;
-}
-
-template <typename T>
-int dev_alloc(T **d, size_t n)
-{
-    KMCF_HIP(hipMalloc(reinterpret_cast<void **>(d), std::max<size_t>(n, 1) * sizeof(T)));
-    KMCF_HIP(hipMemset(*d, 0, std::max<size_t>(n, 1) * sizeof(T)));
     return KMCF_OK;
 }
 
@@ -265,30 +256,30 @@ int kmcf_matrix_build(kmcf_comm *c, int matrix_size, const int *counts, const in
     if (h_val) {
         KMCF_TRY(dev_upload(&m->d_val, val_int));
     } else {
-        KMCF_TRY(dev_alloc(&m->d_val, (size_t)nnz));
+        KMCF_TRY(kmcf_dev_alloc(&m->d_val, std::max<size_t>((size_t)nnz, 1), true));
     }
     if (!m->h_perm.empty()) KMCF_TRY(dev_upload(&m->d_perm, m->h_perm));
     if (m->n_long_items > 0) {
         KMCF_TRY(dev_upload(&m->d_long_items, long_items));
-        KMCF_TRY(dev_alloc(&m->d_long_part, (size_t)m->n_long_items));
-        KMCF_TRY(dev_alloc(&m->d_long_ctr, 1));
+        KMCF_TRY(kmcf_dev_alloc(&m->d_long_part, (size_t)m->n_long_items, true));
+        KMCF_TRY(kmcf_dev_alloc(&m->d_long_ctr, 1, true));
     }
     if (m->n_halo > 0) {
         KMCF_TRY(dev_upload(&m->d_is_boundary, is_boundary));
         KMCF_TRY(dev_upload(&m->d_boundary_rows, boundary_rows));
         KMCF_TRY(dev_upload(&m->d_send_idx, send_idx));
-        KMCF_TRY(dev_alloc(&m->d_send_buf, (size_t)m->n_send));
+        KMCF_TRY(kmcf_dev_alloc(&m->d_send_buf, (size_t)std::max(m->n_send, 1), true));
         KMCF_TRY(dev_upload(&m->d_halo_gid, halo_gid));
     }
-    KMCF_TRY(dev_alloc(&m->d_p, (size_t)n_loc + m->n_halo + 2));
-    KMCF_TRY(dev_alloc(&m->d_Ap, (size_t)n_loc + 2));
-    KMCF_TRY(dev_alloc(&m->d_r, (size_t)n_loc + 2));
-    KMCF_TRY(dev_alloc(&m->d_x, (size_t)n_loc + 2));
-    KMCF_TRY(dev_alloc(&m->d_dinv, (size_t)n_loc + 2));
-    KMCF_TRY(dev_alloc(&m->d_part_a, (size_t)4 * KMCF_MAX_PARTIALS));
-    KMCF_TRY(dev_alloc(&m->d_part_b, (size_t)KMCF_MAX_PARTIALS));
-    KMCF_TRY(dev_alloc(&m->d_part_c, (size_t)KMCF_MAX_PARTIALS));
-    KMCF_TRY(dev_alloc(&m->d_S, 1));
+    KMCF_TRY(kmcf_dev_alloc(&m->d_p, (size_t)n_loc + m->n_halo + 2, true));
+    KMCF_TRY(kmcf_dev_alloc(&m->d_Ap, (size_t)n_loc + 2, true));
+    KMCF_TRY(kmcf_dev_alloc(&m->d_r, (size_t)n_loc + 2, true));
+    KMCF_TRY(kmcf_dev_alloc(&m->d_x, (size_t)n_loc + 2, true));
+    KMCF_TRY(kmcf_dev_alloc(&m->d_dinv, (size_t)n_loc + 2, true));
+    KMCF_TRY(kmcf_dev_alloc(&m->d_part_a, (size_t)4 * KMCF_MAX_PARTIALS, true));
+    KMCF_TRY(kmcf_dev_alloc(&m->d_part_b, (size_t)KMCF_MAX_PARTIALS, true));
+    KMCF_TRY(kmcf_dev_alloc(&m->d_part_c, (size_t)KMCF_MAX_PARTIALS, true));
+    KMCF_TRY(kmcf_dev_alloc(&m->d_S, 1, true));
     // Plan hint: a matrix created without values is filled by the K assembly (two off-diagonal values, always
     // coded); one created with values is coded iff its off-diagonals take few distinct values.
     m->expect_coded = true;
@@ -465,12 +456,10 @@ extern "C" int kmcf_matrix_destroy(kmcf_matrix *m)
         kmcf_p2p_matrix_free(m);
         kmcf_spmv_plan_free(m);
         kmcf_cgr_free(m);
-        void *ptrs[] = {m->d_row_ptr, m->d_col, m->d_val, m->d_boundary_rows, m->d_is_boundary, m->d_send_idx,
-                        m->d_send_buf, m->d_halo_gid, m->d_p, m->d_Ap, m->d_r, m->d_x, m->d_dinv,
-                        m->d_part_a, m->d_part_b, m->d_part_c, m->d_S, m->d_perm, m->d_pd, m->d_s,
-                        m->d_long_items, m->d_long_part, m->d_long_ctr, m->d_build_tab};
-        for (void *p : ptrs)
-            if (p) hipFree(p);
+        kmcf_dev_free_all({m->d_row_ptr, m->d_col, m->d_val, m->d_boundary_rows, m->d_is_boundary, m->d_send_idx,
+                           m->d_send_buf, m->d_halo_gid, m->d_p, m->d_Ap, m->d_r, m->d_x, m->d_dinv,
+                           m->d_part_a, m->d_part_b, m->d_part_c, m->d_S, m->d_perm, m->d_pd, m->d_s,
+                           m->d_long_items, m->d_long_part, m->d_long_ctr, m->d_build_tab});
     }
     delete m;
     return KMCF_OK;

@@ -21,63 +21,15 @@
 
 namespace {
 
-constexpr int SCAN_ITEMS = 8;                         // per thread
-constexpr int SCAN_TILE = KMCF_BLOCK * SCAN_ITEMS;    // 2048 flags per block
-
-__device__ __forceinline__ int block_excl_scan(int v, int *lds, int *total)
-{
-    // exclusive scan of one int per thread over 256 threads
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int s = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        int t = __shfl_up(s, off, 64);
-        if (lane >= off) s += t;
-    }
-    if (lane == 63) lds[w] = s;
-    __syncthreads();
-    int base = 0;
-    for (int i = 0; i < w; ++i) base += lds[i];
-    if (total) *total = lds[0] + lds[1] + lds[2] + lds[3];
-    __syncthreads();
-    return base + s - v;
-}
-
-// phase 1: per-tile counts of charged sites (cell order)
+// phase 1: per-tile counts of charged sites (cell order); phase 2 is kmcf_scan_counts_kernel, in place
 __global__ __launch_bounds__(KMCF_BLOCK) void flag_count_kernel(int N, const int *__restrict__ cell_order,
                                                                 const int *__restrict__ charge, int *__restrict__ block_sum)
 {
     __shared__ int lds[4];
-    const int t0 = blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_ITEMS;
-    int c = 0;
-#pragma unroll
-    for (int i = 0; i < SCAN_ITEMS; ++i) {
-        const int t = t0 + i;
-        if (t < N) c += (charge[cell_order[t]] != 0);
-    }
-    int total;
-    block_excl_scan(c, lds, &total);
+    int f[KMCF_SCAN_ITEMS];
+    kmcf_tile_flags(N, f, [&](int t) { return charge[cell_order[t]] != 0; });
+    const int total = kmcf_tile_count(f, lds);
     if (threadIdx.x == 0) block_sum[blockIdx.x] = total;
-}
-
-// phase 2: exclusive scan of the tile counts (one block; tiles <= 256 * 64)
-__global__ __launch_bounds__(KMCF_BLOCK) void block_sum_scan_kernel(int nb, int *__restrict__ block_sum)
-{
-    __shared__ int lds[4];
-    __shared__ int carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int b0 = 0; b0 < nb; b0 += KMCF_BLOCK) {
-        const int b = b0 + threadIdx.x;
-        const int v = b < nb ? block_sum[b] : 0;
-        int total;
-        const int ex = block_excl_scan(v, lds, &total);
-        if (b < nb) block_sum[b] = carry + ex;
-        __syncthreads();
-        if (threadIdx.x == 0) carry += total;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) block_sum[nb] = carry;   // total number of charged sites
 }
 
 // phase 3: positions + compaction
@@ -87,18 +39,12 @@ __global__ __launch_bounds__(KMCF_BLOCK) void flag_scatter_kernel(int N, const i
                                                                   int *__restrict__ flag_pos, int *__restrict__ clist)
 {
     __shared__ int lds[4];
-    const int t0 = blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_ITEMS;
-    int f[SCAN_ITEMS], site[SCAN_ITEMS], c = 0;
+    const int t0 = kmcf_tile_item0();
+    int f[KMCF_SCAN_ITEMS], site[KMCF_SCAN_ITEMS];
+    kmcf_tile_flags(N, f, [&](int t) { return charge[site[t - t0] = cell_order[t]] != 0; });
+    int pos = kmcf_tile_pos(f, block_sum[blockIdx.x], lds);
 #pragma unroll
-    for (int i = 0; i < SCAN_ITEMS; ++i) {
-        const int t = t0 + i;
-        site[i] = t < N ? cell_order[t] : -1;
-        f[i] = (t < N) ? (charge[site[i]] != 0) : 0;
-        c += f[i];
-    }
-    int pos = block_sum[blockIdx.x] + block_excl_scan(c, lds, nullptr);
-#pragma unroll
-    for (int i = 0; i < SCAN_ITEMS; ++i) {
+    for (int i = 0; i < KMCF_SCAN_ITEMS; ++i) {
         const int t = t0 + i;
         if (t < N) {
             flag_pos[t] = pos;
@@ -109,20 +55,9 @@ __global__ __launch_bounds__(KMCF_BLOCK) void flag_scatter_kernel(int N, const i
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x == KMCF_BLOCK - 1) flag_pos[N] = block_sum[gridDim.x];
 }
 
-struct pw_grid {
-    double x0, y0, z0, inv;
-    int ncx, ncy, ncz;
-};
-
-__device__ __forceinline__ int pw_coord(double v, double v0, double inv, int nc)
-{
-    int c = (int)floor((v - v0) * inv);
-    return c < 0 ? 0 : (c >= nc ? nc - 1 : c);
-}
-
 // calculate_pairwise_interaction_indexed (potential_solver_gpu.cu:1525-1564): potential[i] = sum, written not added
 __global__ __launch_bounds__(KMCF_BLOCK) void pairwise_kernel(
-    pw_grid g, const int *__restrict__ cell_start, const int *__restrict__ flag_pos, const int *__restrict__ clist,
+    kmcf_cell_grid g, const int *__restrict__ cell_start, const int *__restrict__ flag_pos, const int *__restrict__ clist,
     const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ z,
     const int *__restrict__ charge, double sigma, double k, double cutoff, int count, int displ,
     double *__restrict__ potential)
@@ -138,8 +73,8 @@ __global__ __launch_bounds__(KMCF_BLOCK) void pairwise_kernel(
         double acc = 0.0;
         if (valid) {
             const double xi = x[i], yi = y[i], zi = z[i];
-            const int cx = pw_coord(xi, g.x0, g.inv, g.ncx), cy = pw_coord(yi, g.y0, g.inv, g.ncy),
-                      cz = pw_coord(zi, g.z0, g.inv, g.ncz);
+            const int cx = kmcf_cell_coord(xi, g.x0, g.inv, g.ncx), cy = kmcf_cell_coord(yi, g.y0, g.inv, g.ncy),
+                      cz = kmcf_cell_coord(zi, g.z0, g.inv, g.ncz);
             for (int ax = max(cx - 1, 0); ax <= min(cx + 1, g.ncx - 1); ++ax)
                 for (int ay = max(cy - 1, 0); ay <= min(cy + 1, g.ncy - 1); ++ay) {
                     // cells (ax, ay, az-1..az+1) are contiguous in the cell order: one run
@@ -189,24 +124,21 @@ extern "C" int kmcf_compute_cutoff_list(kmcf_comm *c, const double *d_x, const d
     p->ncy = (int)std::floor((hi[1] - lo[1]) * p->inv) + 1;
     p->ncz = (int)std::floor((hi[2] - lo[2]) * p->inv) + 1;
     p->ncell = p->ncx * p->ncy * p->ncz;
-    auto coord = [&](double v, double v0, int nc) {
-        int cc = (int)std::floor((v - v0) * p->inv);
-        return cc < 0 ? 0 : (cc >= nc ? nc - 1 : cc);
-    };
     std::vector<int> start((size_t)p->ncell + 1, 0), cid((size_t)N), order((size_t)N);
     for (int s = 0; s < N; ++s) {
-        cid[s] = (coord(x[s], p->x0, p->ncx) * p->ncy + coord(y[s], p->y0, p->ncy)) * p->ncz + coord(z[s], p->z0, p->ncz);
+        cid[s] = (kmcf_cell_coord(x[s], p->x0, p->inv, p->ncx) * p->ncy + kmcf_cell_coord(y[s], p->y0, p->inv, p->ncy)) * p->ncz +
+                 kmcf_cell_coord(z[s], p->z0, p->inv, p->ncz);
         start[cid[s] + 1]++;
     }
     for (int cc = 0; cc < p->ncell; ++cc) start[cc + 1] += start[cc];
     std::vector<int> fill(start.begin(), start.end() - 1);
     for (int s = 0; s < N; ++s) order[fill[cid[s]]++] = s;
-    p->n_blocks = (N + SCAN_TILE - 1) / SCAN_TILE;
-    KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&p->d_cell_order), (size_t)N * sizeof(int)));
-    KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&p->d_cell_start), ((size_t)p->ncell + 1) * sizeof(int)));
-    KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&p->d_flag_pos), ((size_t)N + 1) * sizeof(int)));
-    KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&p->d_block_sum), ((size_t)p->n_blocks + 1) * sizeof(int)));
-    KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&p->d_clist), (size_t)N * sizeof(int)));
+    p->n_blocks = (N + KMCF_SCAN_TILE - 1) / KMCF_SCAN_TILE;
+    KMCF_TRY(kmcf_dev_alloc(&p->d_cell_order, (size_t)N, false));
+    KMCF_TRY(kmcf_dev_alloc(&p->d_cell_start, (size_t)p->ncell + 1, false));
+    KMCF_TRY(kmcf_dev_alloc(&p->d_flag_pos, (size_t)N + 1, false));
+    KMCF_TRY(kmcf_dev_alloc(&p->d_block_sum, (size_t)p->n_blocks + 1, false));
+    KMCF_TRY(kmcf_dev_alloc(&p->d_clist, (size_t)N, false));
     KMCF_HIP(hipMemcpy(p->d_cell_order, order.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice));
     KMCF_HIP(hipMemcpy(p->d_cell_start, start.data(), start.size() * sizeof(int), hipMemcpyHostToDevice));
     *out = p;
@@ -219,9 +151,7 @@ extern "C" int kmcf_pairwise_destroy(kmcf_pairwise *p)
     hipSetDevice(p->comm->device);
     hipStreamSynchronize(p->comm->stream);
     kmcf_gap_ws_free(p);
-    void *ptrs[] = {p->d_cell_order, p->d_cell_start, p->d_flag_pos, p->d_block_sum, p->d_clist};
-    for (void *q : ptrs)
-        if (q) hipFree(q);
+    kmcf_dev_free_all({p->d_cell_order, p->d_cell_start, p->d_flag_pos, p->d_block_sum, p->d_clist});
     delete p;
     return KMCF_OK;
 }
@@ -237,15 +167,14 @@ extern "C" int kmcf_poisson_gridless(kmcf_pairwise *p, const double *d_x, const 
     KMCF_TRY(kmcf_enter(c));
     hipStream_t st = c->stream;
     flag_count_kernel<<<p->n_blocks, KMCF_BLOCK, 0, st>>>(p->N, p->d_cell_order, d_site_charge, p->d_block_sum);
-    block_sum_scan_kernel<<<1, KMCF_BLOCK, 0, st>>>(p->n_blocks, p->d_block_sum);
+    kmcf_scan_counts_kernel<int><<<1, KMCF_BLOCK, 0, st>>>(p->n_blocks, p->d_block_sum, p->d_block_sum, 0);
     flag_scatter_kernel<<<p->n_blocks, KMCF_BLOCK, 0, st>>>(p->N, p->d_cell_order, d_site_charge, p->d_block_sum,
                                                           p->d_flag_pos, p->d_clist);
     KMCF_HIP(hipGetLastError());
     if (count > 0) {
-        pw_grid g{p->x0, p->y0, p->z0, p->inv, p->ncx, p->ncy, p->ncz};
         int64_t grid = ((int64_t)count * 16 + KMCF_BLOCK - 1) / KMCF_BLOCK;
         if (grid > 8192) grid = 8192;
-        pairwise_kernel<<<(int)grid, KMCF_BLOCK, 0, st>>>(g, p->d_cell_start, p->d_flag_pos, p->d_clist, d_x, d_y, d_z,
+        pairwise_kernel<<<(int)grid, KMCF_BLOCK, 0, st>>>(p->grid(), p->d_cell_start, p->d_flag_pos, p->d_clist, d_x, d_y, d_z,
                                                          d_site_charge, sigma, k, p->cutoff, count, displ,
                                                          d_site_potential_charge);
         KMCF_HIP(hipGetLastError());

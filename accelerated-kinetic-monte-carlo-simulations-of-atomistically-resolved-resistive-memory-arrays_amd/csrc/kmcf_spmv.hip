@@ -51,18 +51,6 @@ __device__ __forceinline__ double wave_sum_width(double v, int width)
     return v;
 }
 
-// Deterministic block sum (256 threads): shuffle inside each wavefront, then LDS.
-__device__ __forceinline__ double block_sum_256(double v, double *lds4)
-{
-    v = kmcf_wave_sum64(v);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) lds4[w] = v;
-    __syncthreads();
-    double t = (lds4[0] + lds4[1]) + (lds4[2] + lds4[3]);
-    __syncthreads();
-    return t;
-}
-
 // Matrix data a kernel reads once per launch.  Marked nontemporal (streaming: do not keep it in the caches) only
 // where the matrix is larger than the caches anyway: measured on the 40 nm K matrix (round 2), 534 MB of CSR
 // stream 141 us nontemporal / 148 us plain, 481 MB of window format 129 / 133 -- but the 2 B/nnz formats, which
@@ -135,7 +123,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void spmv_stream_kernel(
         __syncthreads();
     }
     if (DOT) {
-        double t = block_sum_256(dot, lds4);
+        double t = kmcf_block_sum(dot, lds4);
         if (tid == 0) part[blockIdx.x] = t;
     }
 }
@@ -215,7 +203,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void spmv_window_kernel(
         __syncthreads();
     }
     if (DOT) {
-        double t = block_sum_256(dot, lds4);
+        double t = kmcf_block_sum(dot, lds4);
         if (tid == 0) part[blockIdx.x] = t;
     }
 }
@@ -380,7 +368,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void spmv_wcode_kernel(
 #undef KMCF_TILE_OF
     }
     if (DOT) {
-        double t = block_sum_256(dot, lds4);
+        double t = kmcf_block_sum(dot, lds4);
         if (tid == 0) part[blockIdx.x] = t;
     }
 }
@@ -578,7 +566,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void spmv_sell_kernel(
     }
     if (DOT) {
         __syncthreads();                    // every wave is done with xs
-        double t = block_sum_256(dot, xs);
+        double t = kmcf_block_sum(dot, xs);
         if (tid == 0) part[blockIdx.x] = t;
     }
 }
@@ -664,7 +652,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void spmv_sellv_kernel(
     }
     if (DOT) {
         __syncthreads();
-        double t = block_sum_256(dot, &xs[0][0]);
+        double t = kmcf_block_sum(dot, &xs[0][0]);
         if (tid == 0) part[blockIdx.x] = t;
     }
 }
@@ -725,7 +713,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void spmv_vec_kernel(
         }
     }
     if (DOT) {
-        double t = block_sum_256(dot, lds4);
+        double t = kmcf_block_sum(dot, lds4);
         if (threadIdx.x == 0) part[blockIdx.x] = t;
     }
 }
@@ -774,7 +762,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void spmv_vec_halo_kernel(
         }
     }
     if (DOT) {
-        double t = block_sum_256(dot, lds4);
+        double t = kmcf_block_sum(dot, lds4);
         if (threadIdx.x == 0) part[blockIdx.x] = t;
     }
 }
@@ -795,7 +783,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void spmv_long_kernel(
     const int4 it = items[blockIdx.x];
     double s = 0.0;
     for (int j = it.y + threadIdx.x; j < it.z; j += KMCF_BLOCK) s += val[j] * x[col[j]];
-    s = block_sum_256(s, lds4);
+    s = kmcf_block_sum(s, lds4);
     if (threadIdx.x == 0) {
         lpart[blockIdx.x] = s;
         __threadfence();
@@ -815,7 +803,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void spmv_long_kernel(
         if (DOT) dot += x[a.x] * t;
     }
     if (DOT) {
-        const double t = block_sum_256(dot, lds4);
+        const double t = kmcf_block_sum(dot, lds4);
         if (threadIdx.x == 0) part[0] = t;
     }
     if (threadIdx.x == 0) *ctr = 0u;
@@ -1223,11 +1211,11 @@ int plan_window(kmcf_matrix *m, bool judge, bool *ok)
     if (kmcf_trace(m->comm))
         fprintf(stderr, "kmcf window plan: %d tiles, %.1f rows, %.1f nnz, %.1f window columns per tile\n", nt, double(n) / nt,
                 double(rp[n]) / nt, double(wcol.size()) / nt);
-    KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&m->d_tile), tiles.size() * sizeof(int2)));
+    KMCF_TRY(kmcf_dev_alloc(&m->d_tile, tiles.size(), false));
     wcol.push_back(0);                                    // spare elements: wcode_issue_loads clamps, never branches
     idx.resize(idx.size() + KMCF_BLOCK * 16 + 16, 0);    // the coded kernel's block-wide slot load may run past the last tile
-    KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&m->d_wcol), wcol.size() * sizeof(int)));
-    KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&m->d_idx16), idx.size() * sizeof(unsigned short)));
+    KMCF_TRY(kmcf_dev_alloc(&m->d_wcol, wcol.size(), false));
+    KMCF_TRY(kmcf_dev_alloc(&m->d_idx16, idx.size(), false));
     KMCF_HIP(hipMemcpy(m->d_tile, tiles.data(), tiles.size() * sizeof(int2), hipMemcpyHostToDevice));
     {   // self-contained descriptors for the coded kernel's prefetch pipeline (no dependent loads)
         std::vector<int4> t4((size_t)nt + 1);
@@ -1238,8 +1226,8 @@ int plan_window(kmcf_matrix *m, bool judge, bool *ok)
         }
         t4[nt] = make_int4(n, 1, 0, 0);
         tb[nt] = rp[n];
-        KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&m->d_tile4), t4.size() * sizeof(int4)));
-        KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&m->d_tbase), tb.size() * sizeof(int)));
+        KMCF_TRY(kmcf_dev_alloc(&m->d_tile4, t4.size(), false));
+        KMCF_TRY(kmcf_dev_alloc(&m->d_tbase, tb.size(), false));
         KMCF_HIP(hipMemcpy(m->d_tile4, t4.data(), t4.size() * sizeof(int4), hipMemcpyHostToDevice));
         KMCF_HIP(hipMemcpy(m->d_tbase, tb.data(), tb.size() * sizeof(int), hipMemcpyHostToDevice));
     }
@@ -1253,12 +1241,11 @@ int plan_window(kmcf_matrix *m, bool judge, bool *ok)
     for (int i = 0; i < n; ++i)
         for (int j = rp[i]; j < rp[i + 1]; ++j)
             if (col[j] == i) { m->h_diag_pos[i] = j; break; }
-    KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&m->d_diag_pos), (size_t)n * sizeof(int)));
+    KMCF_TRY(kmcf_dev_alloc(&m->d_diag_pos, (size_t)n, false));
     KMCF_HIP(hipMemcpy(m->d_diag_pos, m->h_diag_pos.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
-    KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&m->d_dict), 64 * sizeof(double)));
-    KMCF_HIP(hipMemset(m->d_dict, 0, 64 * sizeof(double)));
-    KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&m->d_diagv), (size_t)std::max(m->n_loc, 1) * sizeof(double)));   // (every row: the row-wise K assembly writes all of them)
-    KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&m->d_code_fail), sizeof(int)));
+    KMCF_TRY(kmcf_dev_alloc(&m->d_dict, 64, true));
+    KMCF_TRY(kmcf_dev_alloc(&m->d_diagv, (size_t)std::max(m->n_loc, 1), false));   // (every row: the row-wise K assembly writes all of them)
+    KMCF_TRY(kmcf_dev_alloc(&m->d_code_fail, 1, false));
     m->coded = false;
     *ok = true;
     KMCF_TRY(plan_sell(m, col));                        // (the coded kernel when the values get a dictionary, the f64 one otherwise)
@@ -1469,12 +1456,12 @@ int plan_sell(kmcf_matrix *m, const std::vector<int> &col)
     m->n_sell_wcols = (int64_t)wcol.size();
     st.resize(st.size() + 128 * 4, pad);              // idle waves read one group per lane at their (empty) stream's start
     wcol.push_back(0);
-    KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&m->d_sell_tile), tiles.size() * sizeof(int4)));
-    KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&m->d_sell_wave), waves.size() * sizeof(int2)));
-    KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&m->d_sell_lrow), lrow.size() * sizeof(int)));
-    KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&m->d_sell_wcol), wcol.size() * sizeof(int)));
-    KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&m->d_sell), st.size() * sizeof(unsigned short)));
-    KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&m->d_sell_pos), (size_t)n * sizeof(int)));
+    KMCF_TRY(kmcf_dev_alloc(&m->d_sell_tile, tiles.size(), false));
+    KMCF_TRY(kmcf_dev_alloc(&m->d_sell_wave, waves.size(), false));
+    KMCF_TRY(kmcf_dev_alloc(&m->d_sell_lrow, lrow.size(), false));
+    KMCF_TRY(kmcf_dev_alloc(&m->d_sell_wcol, wcol.size(), false));
+    KMCF_TRY(kmcf_dev_alloc(&m->d_sell, st.size(), false));
+    KMCF_TRY(kmcf_dev_alloc(&m->d_sell_pos, (size_t)n, false));
     KMCF_HIP(hipMemcpy(m->d_sell_tile, tiles.data(), tiles.size() * sizeof(int4), hipMemcpyHostToDevice));
     KMCF_HIP(hipMemcpy(m->d_sell_wave, waves.data(), waves.size() * sizeof(int2), hipMemcpyHostToDevice));
     KMCF_HIP(hipMemcpy(m->d_sell_lrow, lrow.data(), lrow.size() * sizeof(int), hipMemcpyHostToDevice));
@@ -1485,9 +1472,9 @@ int plan_sell(kmcf_matrix *m, const std::vector<int> &col)
     m->n_sell12_words = pack ? (int64_t)st12.size() : 0;
     if (pack) {
         st12.resize(st12.size() + 128, pad12);        // (idle waves, as above)
-        KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&m->d_sell12), st12.size() * sizeof(uint64_t)));
-        KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&m->d_sell12_wave), waves12.size() * sizeof(int2)));
-        KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&m->d_sell12_pos), (size_t)n * sizeof(int)));
+        KMCF_TRY(kmcf_dev_alloc(&m->d_sell12, st12.size(), false));
+        KMCF_TRY(kmcf_dev_alloc(&m->d_sell12_wave, waves12.size(), false));
+        KMCF_TRY(kmcf_dev_alloc(&m->d_sell12_pos, (size_t)n, false));
         KMCF_HIP(hipMemcpy(m->d_sell12, st12.data(), st12.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
         KMCF_HIP(hipMemcpy(m->d_sell12_wave, waves12.data(), waves12.size() * sizeof(int2), hipMemcpyHostToDevice));
         KMCF_HIP(hipMemcpy(m->d_sell12_pos, pos12.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
@@ -1935,11 +1922,9 @@ void kmcf_sell_refine_order(const kmcf_comm *c, int n_short, int n_cols, const i
 
 void kmcf_spmv_plan_free(kmcf_matrix *m)
 {
-    void *ptrs[] = {m->d_chunk_row, m->d_tile, m->d_tile4, m->d_tbase, m->d_wcol, m->d_idx16, m->d_dict, m->d_diagv,
-                    m->d_diag_pos, m->d_code_fail, m->d_sell_tile, m->d_sell_wave, m->d_sell_lrow, m->d_sell_wcol,
-                    m->d_sell, m->d_sell_pos, m->d_sellv, m->d_sell12, m->d_sell12_wave, m->d_sell12_pos};
-    for (void *p : ptrs)
-        if (p) hipFree(p);
+    kmcf_dev_free_all({m->d_chunk_row, m->d_tile, m->d_tile4, m->d_tbase, m->d_wcol, m->d_idx16, m->d_dict, m->d_diagv,
+                       m->d_diag_pos, m->d_code_fail, m->d_sell_tile, m->d_sell_wave, m->d_sell_lrow, m->d_sell_wcol,
+                       m->d_sell, m->d_sell_pos, m->d_sellv, m->d_sell12, m->d_sell12_wave, m->d_sell12_pos});
     m->d_chunk_row = nullptr; m->d_tile = nullptr; m->d_tile4 = nullptr; m->d_tbase = nullptr; m->d_wcol = nullptr;
     m->d_idx16 = nullptr; m->d_dict = nullptr; m->d_diagv = nullptr; m->d_diag_pos = nullptr; m->d_code_fail = nullptr;
     m->d_sell_tile = nullptr; m->d_sell_wave = nullptr; m->d_sell_lrow = nullptr; m->d_sell_wcol = nullptr;

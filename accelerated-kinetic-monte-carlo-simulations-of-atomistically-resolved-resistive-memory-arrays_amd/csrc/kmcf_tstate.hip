@@ -93,18 +93,6 @@ __device__ __forceinline__ double dist3(double x1, double y1, double z1, double 
     return sqrt(dx * dx + dy * dy + dz * dz);
 }
 
-__device__ __forceinline__ double wave_sum(double v) { return kmcf_wave_sum64(v); }
-
-__device__ __forceinline__ double block_sum4(double v, double *lds4)
-{
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const double t = (lds4[0] + lds4[1]) + (lds4[2] + lds4[3]);
-    __syncthreads();
-    return t;
-}
-
 // ---------------------------------------------------------------- atoms
 __global__ __launch_bounds__(KMCF_BLOCK) void gather_coords_kernel(int n, const int *__restrict__ site, const double *__restrict__ sx,
                                                                    const double *__restrict__ sy, const double *__restrict__ sz,
@@ -217,8 +205,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void t_assemble_kernel(
 // ---------------------------------------------------------------- tunnel points
 // get_is_tunnel_mpi (src/initialize_sparsity_T.cu:618-654) over the atoms 0 .. N_atom - 2 of all ranks; the
 // reference's yes * idx / copy_if(is_not_zero) drops atom 0, restated as "atom 0 is never a tunnel point".
-constexpr int SCAN_ITEMS = 8;    // per thread: 2048 atoms per block
-
+// The list is compacted with the tiles of kmcf_block.hpp (2048 atoms per block): count, scan, scatter.
 __device__ __forceinline__ int tunnel_flag(int a, int n_scan, const int *__restrict__ ael, const double *__restrict__ ax,
                                            double x_lo, double x_hi)
 {
@@ -231,46 +218,10 @@ __global__ __launch_bounds__(KMCF_BLOCK) void tunnel_count_kernel(int n_scan, co
                                                                   double x_lo, double x_hi, int *__restrict__ blk)
 {
     __shared__ int lds4[4];
-    const int base = blockIdx.x * KMCF_BLOCK * SCAN_ITEMS + threadIdx.x * SCAN_ITEMS;
-    int c = 0;
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; ++k) c += tunnel_flag(base + k, n_scan, ael, ax, x_lo, x_hi);
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) c += __shfl_xor(c, off, 64);
-    if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) blk[blockIdx.x] = lds4[0] + lds4[1] + lds4[2] + lds4[3];
-}
-
-// one block: exclusive scan of up to any number of ints (sequential over 256-wide segments)
-template <typename T>
-__global__ __launch_bounds__(KMCF_BLOCK) void scan_exclusive_kernel(int n, const int *__restrict__ in, T *__restrict__ out /* n + 1 */,
-                                                                    T *__restrict__ total_pinned)
-{
-    __shared__ T sh[KMCF_BLOCK];
-    __shared__ T carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int s0 = 0; s0 < n; s0 += KMCF_BLOCK) {
-        const int i = s0 + threadIdx.x;
-        const T v = i < n ? (T)in[i] : 0;
-        sh[threadIdx.x] = v;
-        __syncthreads();
-        for (int off = 1; off < KMCF_BLOCK; off <<= 1) {          // Hillis-Steele inclusive scan
-            const T t = threadIdx.x >= off ? sh[threadIdx.x - off] : 0;
-            __syncthreads();
-            sh[threadIdx.x] += t;
-            __syncthreads();
-        }
-        if (i < n) out[i] = carry + sh[threadIdx.x] - v;
-        __syncthreads();
-        if (threadIdx.x == 0) carry += sh[KMCF_BLOCK - 1];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        out[n] = carry;
-        if (total_pinned) *total_pinned = carry;
-    }
+    int f[KMCF_SCAN_ITEMS];
+    kmcf_tile_flags(n_scan, f, [&](int a) { return tunnel_flag(a, n_scan, ael, ax, x_lo, x_hi); });
+    const int total = kmcf_tile_count(f, lds4);
+    if (threadIdx.x == 0) blk[blockIdx.x] = total;
 }
 
 // scatter: tunnel point list (ascending atom index) + compact per-point data
@@ -283,22 +234,13 @@ __global__ __launch_bounds__(KMCF_BLOCK) void tunnel_scatter_kernel(
     int *__restrict__ tidx, int *__restrict__ tinfo, double *__restrict__ tx, double *__restrict__ ty,
     double *__restrict__ tz, double *__restrict__ tcb)
 {
-    __shared__ int sh[KMCF_BLOCK];
-    const int base = blockIdx.x * KMCF_BLOCK * SCAN_ITEMS + threadIdx.x * SCAN_ITEMS;
-    int f[SCAN_ITEMS], c = 0;
+    __shared__ int lds4[4];
+    const int base = kmcf_tile_item0();
+    int f[KMCF_SCAN_ITEMS];
+    kmcf_tile_flags(n_scan, f, [&](int a) { return tunnel_flag(a, n_scan, ael, ax, x_lo, x_hi); });
+    int pos = kmcf_tile_pos(f, blk_off[blockIdx.x], lds4);
 #pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; ++k) { f[k] = tunnel_flag(base + k, n_scan, ael, ax, x_lo, x_hi); c += f[k]; }
-    sh[threadIdx.x] = c;
-    __syncthreads();
-    for (int off = 1; off < KMCF_BLOCK; off <<= 1) {
-        const int t = threadIdx.x >= off ? sh[threadIdx.x - off] : 0;
-        __syncthreads();
-        sh[threadIdx.x] += t;
-        __syncthreads();
-    }
-    int pos = blk_off[blockIdx.x] + sh[threadIdx.x] - c;
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; ++k) {
+    for (int k = 0; k < KMCF_SCAN_ITEMS; ++k) {
         if (!f[k]) continue;
         const int a = base + k;
         const int e = ael[a];
@@ -413,7 +355,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void tunnel_value_kernel(
             }
             off += __popcll(mk);
         }
-        rowsum = wave_sum(rowsum);
+        rowsum = kmcf_wave_sum64(rowsum);
         if (dpos >= 0) val[dpos] = -rowsum;                                // :685
         if (lane == 0) tdiag[s] = -rowsum;                                 // :680
     }
@@ -498,7 +440,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void sub_spmv_kernel(
             if ((mk >> lane) & 1ull) acc += val[off + __popcll(mk & lt)] * xsub[g * 64 + lane];
             off += __popcll(mk);
         }
-        acc = wave_sum(acc);
+        acc = kmcf_wave_sum64(acc);
         if (lane == 0) {
             const int r = rows[s];
             y[r] += acc;                                       // unpack_add, dist_spmv_split_sparse.cpp:70-76
@@ -506,7 +448,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void sub_spmv_kernel(
         }
     }
     if (DOT) {
-        const double t = block_sum4(dot, lds4);
+        const double t = kmcf_block_sum(dot, lds4);
         if (threadIdx.x == 0) part[blockIdx.x] = t;
     }
 }
@@ -532,7 +474,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void imacro_kernel(int row, const int *
             if (node >= 2) s += val[j] * (m[node] - m1);
         }
     }
-    const double t = block_sum4(s, lds4);
+    const double t = kmcf_block_sum(s, lds4);
     if (threadIdx.x == 0) *out = t;
 }
 
@@ -629,7 +571,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void power_tunnel_kernel(
             }
             off += __popcll(mk);
         }
-        a = wave_sum(a); b = wave_sum(b);
+        a = kmcf_wave_sum64(a); b = kmcf_wave_sum64(b);
         if (lane == 0) { psum[rows[s]] += a; isum[rows[s]] += b; }
     }
 }
@@ -1111,7 +1053,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void sub_symm_reduce_kernel(int n_glob,
         }
     }
     if (DOT) {
-        const double t = block_sum4(dot, lds4);
+        const double t = kmcf_block_sum(dot, lds4);
         if (threadIdx.x == 0) part[blockIdx.x] = t;
     }
 }
@@ -1142,7 +1084,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void sub_combine_kernel(int ns, int row
         else if (DOT) dot = p[r] * a;
     }
     if (DOT) {
-        const double t = block_sum4(dot, lds4);
+        const double t = kmcf_block_sum(dot, lds4);
         if (threadIdx.x == 0) part[blockIdx.x] = t;
     }
 }
@@ -1244,7 +1186,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void current_tunnel_kernel(
                 }
             }
         }
-        a = wave_sum(a); b = wave_sum(b);
+        a = kmcf_wave_sum64(a); b = kmcf_wave_sum64(b);
         if (lane == 0) { cm[3 * (size_t)node] += a; cm[3 * (size_t)node + 1] = a; cm[3 * (size_t)node + 2] += b; }
     }
 }
@@ -1263,17 +1205,6 @@ __global__ __launch_bounds__(KMCF_BLOCK) void current_scatter_kernel(int n_rows_
     }
 }
 
-__device__ __forceinline__ double block_max4(double v, double *lds4)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-    if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const double t = fmax(fmax(lds4[0], lds4[1]), fmax(lds4[2], lds4[3]));
-    __syncthreads();
-    return t;
-}
-
 // One block: thread t adds atoms t, t + 256, ... in ascending order, then the block sum -- an order the input fixes.
 // out: [0] net[1], [1] -net[0], [2] sum through, [3] sum tunnel, [4] max through, [5] its site (lowest among equals; -1)
 __global__ __launch_bounds__(KMCF_BLOCK) void current_stats_kernel(int n_rows_atoms, const int *__restrict__ atom_site,
@@ -1287,13 +1218,13 @@ __global__ __launch_bounds__(KMCF_BLOCK) void current_stats_kernel(int n_rows_at
         su += 0.5 * cm[3 * ((size_t)a + 2) + 1];
         mx = fmax(mx, th);
     }
-    st = block_sum4(st, lds4);
-    su = block_sum4(su, lds4);
-    mx = block_max4(mx, lds4);
+    st = kmcf_block_sum(st, lds4);
+    su = kmcf_block_sum(su, lds4);
+    mx = kmcf_block_max(mx, lds4);
     double site = -2147483648.0;                                           // (minus the site: a maximum again)
     for (int a = threadIdx.x; a < n_rows_atoms; a += KMCF_BLOCK)
         if (0.5 * cm[3 * ((size_t)a + 2)] == mx) site = fmax(site, -(double)atom_site[a]);
-    site = block_max4(site, lds4);
+    site = kmcf_block_max(site, lds4);
     if (threadIdx.x == 0) {
         const bool found = site > -2147483648.0;
         out[0] = cm[3 * 1 + 2];
@@ -1305,24 +1236,11 @@ __global__ __launch_bounds__(KMCF_BLOCK) void current_stats_kernel(int n_rows_at
     }
 }
 
+// growth rule of the per-assembly buffers: a quarter more than needed, 64 elements at least
 template <typename T>
 int ensure(T **d, size_t *cap, size_t need)
 {
-    if (need <= *cap && *d) return KMCF_OK;
-    if (*d) KMCF_HIP(hipFree(*d));
-    *d = nullptr;
-    const size_t n = std::max<size_t>(need + need / 4, 64);
-    KMCF_HIP(hipMalloc(reinterpret_cast<void **>(d), n * sizeof(T)));
-    *cap = n;
-    return KMCF_OK;
-}
-
-template <typename T>
-int dalloc(T **d, size_t n)
-{
-    KMCF_HIP(hipMalloc(reinterpret_cast<void **>(d), std::max<size_t>(n, 1) * sizeof(T)));
-    KMCF_HIP(hipMemset(*d, 0, std::max<size_t>(n, 1) * sizeof(T)));
-    return KMCF_OK;
+    return kmcf_dev_grow(d, cap, need, std::max<size_t>(need + need / 4, 64) - need);
 }
 
 }  // namespace
@@ -1333,15 +1251,13 @@ extern "C" int kmcf_tstate_destroy(kmcf_tstate *t)
     if (t->comm && t->comm->device >= 0) {
         hipSetDevice(t->comm->device);
         hipStreamSynchronize(t->comm->stream);
-        void *ptrs[] = {t->d_atom_site, t->d_site_is_atom, t->d_ax, t->d_ay, t->d_az, t->d_acb, t->d_ael, t->d_ach, t->d_acls,
-                        t->d_cls_col, t->d_col_node, t->d_diag_pos, t->d_ground, t->d_inv_perm, t->d_diag, t->d_diag_tot, t->d_rhs,
-                        t->d_tflag, t->d_blk, t->d_tidx, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz, t->d_tcb, t->d_rowcnt, t->d_tdiag,
-                        t->sub.d_rows, t->sub.d_mask, t->sub.d_voff, t->sub.d_val, t->sub.d_xsub, t->d_pdisp, t->d_scal, t->d_err,
-                        t->sub.d_tiles, t->sub.d_strips, t->sub.d_strip_first, t->sub.d_rowpart, t->sub.d_colpart,
-                        t->sub.d_jmask, t->sub.d_jvoff, t->sub.d_jval, t->sub.d_jcnt, t->sub.d_tile_local, t->sub.d_ypart, t->d_agree,
-                        t->d_cmap, t->d_cmstat};
-        for (void *p : ptrs)
-            if (p) hipFree(p);
+        kmcf_dev_free_all({t->d_atom_site, t->d_site_is_atom, t->d_ax, t->d_ay, t->d_az, t->d_acb, t->d_ael, t->d_ach, t->d_acls,
+                           t->d_cls_col, t->d_col_node, t->d_diag_pos, t->d_ground, t->d_inv_perm, t->d_diag, t->d_diag_tot, t->d_rhs,
+                           t->d_tflag, t->d_blk, t->d_tidx, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz, t->d_tcb, t->d_rowcnt, t->d_tdiag,
+                           t->sub.d_rows, t->sub.d_mask, t->sub.d_voff, t->sub.d_val, t->sub.d_xsub, t->d_pdisp, t->d_scal, t->d_err,
+                           t->sub.d_tiles, t->sub.d_strips, t->sub.d_strip_first, t->sub.d_rowpart, t->sub.d_colpart,
+                           t->sub.d_jmask, t->sub.d_jvoff, t->sub.d_jval, t->sub.d_jcnt, t->sub.d_tile_local, t->sub.d_ypart, t->d_agree,
+                           t->d_cmap, t->d_cmstat});
         if (t->h_pin) hipHostFree(t->h_pin);
         if (t->h_agree) hipHostFree(t->h_agree);
         if (t->h_cmstat) hipHostFree(t->h_cmstat);
@@ -1390,11 +1306,12 @@ extern "C" int kmcf_initialize_sparsity_T(kmcf_comm *c, const double *d_site_x, 
     const int n_loc = h_counts_T[rank], row0 = h_displs_T[rank];
     KMCF_TRY(upload(&t->d_atom_site, t->h_atom_site));
     KMCF_TRY(upload(&t->d_site_is_atom, is_atom));
-    KMCF_TRY(dalloc(&t->d_ax, (size_t)Na)); KMCF_TRY(dalloc(&t->d_ay, (size_t)Na)); KMCF_TRY(dalloc(&t->d_az, (size_t)Na));
-    KMCF_TRY(dalloc(&t->d_acb, (size_t)Na)); KMCF_TRY(dalloc(&t->d_ael, (size_t)Na)); KMCF_TRY(dalloc(&t->d_ach, (size_t)Na));
-    KMCF_TRY(dalloc(&t->d_acls, (size_t)Na));
+    const size_t na = (size_t)Na;      // (>= 4: no buffer below is empty; all of them start zeroed)
+    KMCF_TRY(kmcf_dev_alloc(&t->d_ax, na, true)); KMCF_TRY(kmcf_dev_alloc(&t->d_ay, na, true)); KMCF_TRY(kmcf_dev_alloc(&t->d_az, na, true));
+    KMCF_TRY(kmcf_dev_alloc(&t->d_acb, na, true)); KMCF_TRY(kmcf_dev_alloc(&t->d_ael, na, true)); KMCF_TRY(kmcf_dev_alloc(&t->d_ach, na, true));
+    KMCF_TRY(kmcf_dev_alloc(&t->d_acls, na, true));
     // On the CALLER's stream (kmcf_setup_stream, kmcf_internal.hpp): the first kernel that reads the caller's arrays.
-    gather_coords_kernel<<<grid1d(Na), KMCF_BLOCK, 0, kmcf_setup_stream(c)>>>(Na, t->d_atom_site, d_site_x, d_site_y, d_site_z, t->d_ax, t->d_ay, t->d_az);
+    gather_coords_kernel<<<kmcf_grid1d(Na), KMCF_BLOCK, 0, kmcf_setup_stream(c)>>>(Na, t->d_atom_site, d_site_x, d_site_y, d_site_z, t->d_ax, t->d_ay, t->d_az);
     KMCF_HIP(hipGetLastError());
     KMCF_HIP(hipStreamSynchronize(kmcf_setup_stream(c)));
     KMCF_HIP(hipGetLastError());
@@ -1500,25 +1417,28 @@ extern "C" int kmcf_initialize_sparsity_T(kmcf_comm *c, const double *d_site_x, 
     KMCF_TRY(upload(&t->d_ground, ground));
     KMCF_TRY(upload(&t->d_col_node, col_node));
     KMCF_TRY(upload(&t->d_inv_perm, t->h_inv_perm));
-    KMCF_TRY(dalloc(&t->d_cls_col, (size_t)n_loc + m->n_halo));
-    KMCF_TRY(dalloc(&t->d_diag, (size_t)n_loc)); KMCF_TRY(dalloc(&t->d_diag_tot, (size_t)n_loc)); KMCF_TRY(dalloc(&t->d_rhs, (size_t)n_loc + 2));
+    const size_t nl1 = (size_t)std::max(n_loc, 1);     // (a rank may hold no row)
+    KMCF_TRY(kmcf_dev_alloc(&t->d_cls_col, std::max<size_t>((size_t)n_loc + m->n_halo, 1), true));
+    KMCF_TRY(kmcf_dev_alloc(&t->d_diag, nl1, true)); KMCF_TRY(kmcf_dev_alloc(&t->d_diag_tot, nl1, true));
+    KMCF_TRY(kmcf_dev_alloc(&t->d_rhs, (size_t)n_loc + 2, true));
     // tunnel workspace sized by the atom count (grow-only buffers for the block itself)
-    const int nblk = (Na + KMCF_BLOCK * SCAN_ITEMS - 1) / (KMCF_BLOCK * SCAN_ITEMS);
-    KMCF_TRY(dalloc(&t->d_tflag, 1)); KMCF_TRY(dalloc(&t->d_blk, (size_t)2 * nblk + 2));
-    KMCF_TRY(dalloc(&t->d_tidx, (size_t)Na)); KMCF_TRY(dalloc(&t->d_tinfo, (size_t)Na));
-    KMCF_TRY(dalloc(&t->d_tx, (size_t)Na)); KMCF_TRY(dalloc(&t->d_ty, (size_t)Na)); KMCF_TRY(dalloc(&t->d_tz, (size_t)Na));
-    KMCF_TRY(dalloc(&t->d_tcb, (size_t)Na));
-    KMCF_TRY(dalloc(&t->d_pdisp, (size_t)Nsub + 2)); KMCF_TRY(dalloc(&t->d_scal, 4)); KMCF_TRY(dalloc(&t->d_err, 1));
+    const int nblk = (Na + KMCF_SCAN_TILE - 1) / KMCF_SCAN_TILE;
+    KMCF_TRY(kmcf_dev_alloc(&t->d_tflag, 1, true)); KMCF_TRY(kmcf_dev_alloc(&t->d_blk, (size_t)2 * nblk + 2, true));
+    KMCF_TRY(kmcf_dev_alloc(&t->d_tidx, na, true)); KMCF_TRY(kmcf_dev_alloc(&t->d_tinfo, na, true));
+    KMCF_TRY(kmcf_dev_alloc(&t->d_tx, na, true)); KMCF_TRY(kmcf_dev_alloc(&t->d_ty, na, true)); KMCF_TRY(kmcf_dev_alloc(&t->d_tz, na, true));
+    KMCF_TRY(kmcf_dev_alloc(&t->d_tcb, na, true));
+    KMCF_TRY(kmcf_dev_alloc(&t->d_pdisp, (size_t)Nsub + 2, true)); KMCF_TRY(kmcf_dev_alloc(&t->d_scal, 4, true));
+    KMCF_TRY(kmcf_dev_alloc(&t->d_err, 1, true));
     KMCF_HIP(hipHostMalloc(reinterpret_cast<void **>(&t->h_pin), 8 * sizeof(int), hipHostMallocDefault));
     memset(t->h_pin, 0, 8 * sizeof(int));
-    KMCF_TRY(dalloc(&t->d_agree, (size_t)2 * P));
+    KMCF_TRY(kmcf_dev_alloc(&t->d_agree, (size_t)2 * P, true));
     KMCF_HIP(hipHostMalloc(reinterpret_cast<void **>(&t->h_agree), (size_t)(2 + 2 * P) * sizeof(double), hipHostMallocDefault));
     memset(t->h_agree, 0, (size_t)(2 + 2 * P) * sizeof(double));
     t->sub.counts.assign(P, 0);
     t->sub.displs.assign(P, 0);
     // scratch of kmcf_current_map (here, not at its first call: no allocation between the exchanges of a group)
     KMCF_CHECK((int64_t)3 * (Nsub + 2) < (int64_t)INT32_MAX, KMCF_ERR_ARG, "kmcf_initialize_sparsity_T: %d atoms exceed int32 indexing", Na);
-    KMCF_TRY(dalloc(&t->d_cmap, (size_t)3 * (Nsub + 2))); KMCF_TRY(dalloc(&t->d_cmstat, 8));
+    KMCF_TRY(kmcf_dev_alloc(&t->d_cmap, (size_t)3 * (Nsub + 2), true)); KMCF_TRY(kmcf_dev_alloc(&t->d_cmstat, 8, true));
     KMCF_HIP(hipHostMalloc(reinterpret_cast<void **>(&t->h_cmstat), 8 * sizeof(double), hipHostMallocDefault));
     memset(t->h_cmstat, 0, 8 * sizeof(double));
     t->cm_counts.resize((size_t)P); t->cm_displs.resize((size_t)P);
@@ -1669,7 +1589,8 @@ static int symm_setup(kmcf_tstate *t)
         KMCF_TRY(ensure(&sb.d_jvoff, &sb.cap_jvoff, (size_t)sb.n_tiles + 2));
         symj_mask_kernel<<<grid, KMCF_BLOCK, 0, st>>>(sb.n_strips, sb.d_strips, n_t, sb.n_groups, sb.d_mask, sb.d_jmask, sb.d_jcnt);
         long long *pin_j = reinterpret_cast<long long *>(t->h_pin + 6);
-        scan_exclusive_kernel<long long><<<1, KMCF_BLOCK, 0, st>>>((int)sb.n_tiles, sb.d_jcnt, sb.d_jvoff, nullptr);
+        // (a tile holds at most 4096 entries: the 256 counts of one pass of the scan add up to 2^20 at most)
+        kmcf_scan_counts_kernel<long long><<<1, KMCF_BLOCK, 0, st>>>((int)sb.n_tiles, sb.d_jcnt, sb.d_jvoff, 0);
         KMCF_HIP(hipGetLastError());
         KMCF_HIP(hipMemcpyAsync(pin_j, sb.d_jvoff + sb.n_tiles, sizeof(long long), hipMemcpyDeviceToHost, st));
         KMCF_HIP(hipStreamSynchronize(st));
@@ -1684,7 +1605,7 @@ static int symm_setup(kmcf_tstate *t)
     KMCF_HIP(hipGetLastError());
     // diagonal = -(row sums): one application to the vector of ones (the diagonal entries are still 0); spread: of ALL
     // points on every rank (a rank sets the diagonal of the diagonal tiles it holds)
-    fill_kernel<<<grid1d(64 * nb), KMCF_BLOCK, 0, st>>>(64 * nb, sb.d_xsub, 1.0);
+    fill_kernel<<<kmcf_grid1d(64 * nb), KMCF_BLOCK, 0, st>>>(64 * nb, sb.d_xsub, 1.0);
     KMCF_HIP(hipMemsetAsync(t->d_tdiag, 0, (size_t)n_t * sizeof(double), st));
     KMCF_TRY(symm_launch<0>(sb, sb.d_xsub, 0.0, st));
     if (sb.spread)
@@ -1693,7 +1614,7 @@ static int symm_setup(kmcf_tstate *t)
         sub_symm_reduce_kernel<0, false><<<nb, KMCF_BLOCK, 0, st>>>(n_t, nb, sb.d_strip_first, sb.d_rowpart, sb.d_colpart, nullptr, nullptr,
                                                                             t->d_tdiag, nullptr, nullptr, nullptr, 0);
     if (sb.jagged) symj_set_diag_kernel<<<std::max(1, (nb + 3) / 4), KMCF_BLOCK, 0, st>>>(n_t, nb, t->d_tdiag, t->d_tdiag, sb.d_jmask, sb.d_jvoff, sb.d_jval);
-    else symm_set_diag_kernel<<<grid1d(n_t), KMCF_BLOCK, 0, st>>>(n_t, nb, t->d_tdiag, t->d_tdiag, sb.d_tiles, sb.spread ? sb.d_tile_local : nullptr);
+    else symm_set_diag_kernel<<<kmcf_grid1d(n_t), KMCF_BLOCK, 0, st>>>(n_t, nb, t->d_tdiag, t->d_tdiag, sb.d_tiles, sb.spread ? sb.d_tile_local : nullptr);
     KMCF_HIP(hipMemsetAsync(sb.d_xsub, 0, (size_t)64 * nb * sizeof(double), st));      // the pad behind the last point stays 0
     KMCF_HIP(hipGetLastError());
     // partials of the p.Ap sum: one per block row (reduce kernel) / per 256 own points (combine kernel)
@@ -1712,27 +1633,27 @@ static int t_assemble_async(kmcf_tstate *t, const int *d_site_element, const int
     t->assembled = false;
     // 1. atom arrays (update_atom_arrays, :1341-1365) + invariance of the atom set
     KMCF_HIP(hipMemsetAsync(t->d_err, 0, sizeof(int), st));
-    check_atom_set_kernel<<<grid1d(t->N), KMCF_BLOCK, 0, st>>>(t->N, d_site_element, t->d_site_is_atom, t->d_err);
-    gather_atoms_kernel<<<grid1d(Na), KMCF_BLOCK, 0, st>>>(Na, t->d_atom_site, d_site_element, d_site_charge, d_site_CB_edge, d_metals,
+    check_atom_set_kernel<<<kmcf_grid1d(t->N), KMCF_BLOCK, 0, st>>>(t->N, d_site_element, t->d_site_is_atom, t->d_err);
+    gather_atoms_kernel<<<kmcf_grid1d(Na), KMCF_BLOCK, 0, st>>>(Na, t->d_atom_site, d_site_element, d_site_charge, d_site_CB_edge, d_metals,
                                                            num_metals, t->d_ael, t->d_ach, t->d_acb, t->d_acls);
     KMCF_HIP(hipGetLastError());
     // 2. neighbour values + diagonal (one pass)
     if (n_loc > 0) {
         const int n_cols = n_loc + m->n_halo;
-        t_cls_col_kernel<<<grid1d(n_cols), KMCF_BLOCK, 0, st>>>(n_cols, t->d_col_node, t->d_acls, t->d_cls_col);
+        t_cls_col_kernel<<<kmcf_grid1d(n_cols), KMCF_BLOCK, 0, st>>>(n_cols, t->d_col_node, t->d_acls, t->d_cls_col);
         const double dict[3] = {-p->high_G, -p->low_G, -p->loop_G};
         KMCF_TRY(kmcf_matrix_set_dictionary(m, dict, 3));
         constexpr int LPR = 16;
-        t_assemble_kernel<LPR><<<grid1d((int64_t)n_loc * LPR), KMCF_BLOCK, 0, st>>>(
+        t_assemble_kernel<LPR><<<kmcf_grid1d((int64_t)n_loc * LPR), KMCF_BLOCK, 0, st>>>(
             n_loc, m->d_row_ptr, m->d_col, m->d_val, t->d_diag_pos, t->d_ground, t->d_cls_col, p->high_G, p->low_G, p->loop_G,
             t->d_diag, m->coded ? m->d_idx16 : nullptr, m->coded ? m->d_diagv : nullptr, m->n_short);
         KMCF_HIP(hipGetLastError());
     }
     // 3. tunnel points of all ranks (get_is_tunnel_mpi + copy_if + MPI_Allgatherv, initialize_sparsity_T.cu:739-787)
     const int n_scan = Na - 1;                                        // atoms 0 .. N_atom - 2 are matrix rows
-    const int nblk = (Na + KMCF_BLOCK * SCAN_ITEMS - 1) / (KMCF_BLOCK * SCAN_ITEMS);
+    const int nblk = (Na + KMCF_SCAN_TILE - 1) / KMCF_SCAN_TILE;
     tunnel_count_kernel<<<nblk, KMCF_BLOCK, 0, st>>>(n_scan, t->d_ael, t->d_ax, p->contact_x_lo, p->contact_x_hi, t->d_blk);
-    scan_exclusive_kernel<int><<<1, KMCF_BLOCK, 0, st>>>(nblk, t->d_blk, t->d_blk + nblk, nullptr);
+    kmcf_scan_counts_kernel<int><<<1, KMCF_BLOCK, 0, st>>>(nblk, t->d_blk, t->d_blk + nblk, 0);
     tunnel_scatter_kernel<<<nblk, KMCF_BLOCK, 0, st>>>(n_scan, Na, t->d_ael, t->d_ax, t->d_ay, t->d_az, t->d_acb, d_metals, num_metals,
                                                        p->contact_x_lo, p->contact_x_hi, t->n_layers, t->n_inj, t->n_ext, t->d_blk + nblk,
                                                        t->d_tidx, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz, t->d_tcb);
@@ -1772,11 +1693,14 @@ static int t_assemble_async(kmcf_tstate *t, const int *d_site_element, const int
     sb.grid = ns > 0 ? wgrid : 0;
     sb.dense = sb.jagged = sb.spread = false;
     if (ns > 0) {
-        sub_rows_kernel<<<grid1d(ns), KMCF_BLOCK, 0, st>>>(ns, sb.row0, t->d_tidx, m->row0, t->d_inv_perm, sb.d_rows);
+        // a row holds at most n_t entries, and the scan adds the 256 counts of one pass in an int
+        KMCF_CHECK((int64_t)n_t * KMCF_BLOCK <= (int64_t)INT32_MAX, KMCF_ERR_ARG,
+                   "tunnel block: %d tunnel points exceed the row-offset scan's range (256 rows of that many entries in an int)", n_t);
+        sub_rows_kernel<<<kmcf_grid1d(ns), KMCF_BLOCK, 0, st>>>(ns, sb.row0, t->d_tidx, m->row0, t->d_inv_perm, sb.d_rows);
         tunnel_mask_kernel<<<wgrid, KMCF_BLOCK, 0, st>>>(ns, sb.row0, n_t, ng, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz, t->d_tcb, t->nn_dist,
                                                          p->tol, sb.d_mask, t->d_rowcnt);
         long long *pin_nnz = reinterpret_cast<long long *>(t->h_pin + 2);
-        scan_exclusive_kernel<long long><<<1, KMCF_BLOCK, 0, st>>>(ns, t->d_rowcnt, sb.d_voff, nullptr);
+        kmcf_scan_counts_kernel<long long><<<1, KMCF_BLOCK, 0, st>>>(ns, t->d_rowcnt, sb.d_voff, 0);
         KMCF_HIP(hipGetLastError());
         KMCF_HIP(hipMemcpyAsync(pin_nnz, sb.d_voff + ns, sizeof(long long), hipMemcpyDeviceToHost, st));
         KMCF_HIP(hipStreamSynchronize(st));
@@ -1840,9 +1764,9 @@ static int t_assemble_async(kmcf_tstate *t, const int *d_site_element, const int
     }
     // 4. preconditioner and right-hand side
     if (n_loc > 0) {
-        copy_diag_rhs_kernel<<<grid1d(n_loc), KMCF_BLOCK, 0, st>>>(n_loc, t->d_diag, t->d_diag_tot, t->d_col_node, p->loop_G * p->Vd, t->d_rhs);
-        if (ns > 0) add_tunnel_diag_kernel<<<grid1d(ns), KMCF_BLOCK, 0, st>>>(ns, sb.d_rows, t->d_tdiag + (sb.spread ? sb.row0 : 0), t->d_diag_tot);
-        invert_kernel<<<grid1d(n_loc), KMCF_BLOCK, 0, st>>>(n_loc, t->d_diag_tot, m->d_dinv);
+        copy_diag_rhs_kernel<<<kmcf_grid1d(n_loc), KMCF_BLOCK, 0, st>>>(n_loc, t->d_diag, t->d_diag_tot, t->d_col_node, p->loop_G * p->Vd, t->d_rhs);
+        if (ns > 0) add_tunnel_diag_kernel<<<kmcf_grid1d(ns), KMCF_BLOCK, 0, st>>>(ns, sb.d_rows, t->d_tdiag + (sb.spread ? sb.row0 : 0), t->d_diag_tot);
+        invert_kernel<<<kmcf_grid1d(n_loc), KMCF_BLOCK, 0, st>>>(n_loc, t->d_diag_tot, m->d_dinv);
         KMCF_HIP(hipGetLastError());
     }
     m->sub = &t->sub;
@@ -1863,7 +1787,7 @@ int kmcf_subop_begin(kmcf_matrix *m, bool skip_if_done)
     if (sb->n_glob == 0) return KMCF_OK;
     const int chk = skip_if_done ? 1 : 0;
     if (sb->n_loc > 0) {
-        sub_pack_kernel<<<grid1d(sb->n_loc), KMCF_BLOCK, 0, st>>>(sb->n_loc, sb->d_rows, m->d_p, sb->d_xsub + sb->row0, m->d_S, chk);
+        sub_pack_kernel<<<kmcf_grid1d(sb->n_loc), KMCF_BLOCK, 0, st>>>(sb->n_loc, sb->d_rows, m->d_p, sb->d_xsub + sb->row0, m->d_S, chk);
         KMCF_HIP(hipGetLastError());
     }
     if (c->nranks == 1 && !c->force_collectives) return KMCF_OK;
@@ -2068,7 +1992,7 @@ extern "C" int kmcf_update_power_sparse(kmcf_tstate *t, const int *d_site_elemen
     // every rank gets all Nsub potentials (the reference gathers them on rank 0 only, :1782)
     KMCF_TRY(kmcf_comm_allgatherv_double(c, d_atom_virtual_potentials, m->counts.data(), m->displs.data()));
     // scaled by G0 in place, all N_atom + 2 entries (:2038-2040)
-    scale_kernel<<<grid1d(Na + 2), KMCF_BLOCK, 0, st>>>(Na + 2, d_atom_virtual_potentials, p->G0);
+    scale_kernel<<<kmcf_grid1d(Na + 2), KMCF_BLOCK, 0, st>>>(Na + 2, d_atom_virtual_potentials, p->G0);
     // I_macro on the owner of row 1, then shared
     const bool own1 = m->row0 <= 1 && 1 < m->row0 + n_loc;
     imacro_kernel<<<1, KMCF_BLOCK, 0, st>>>(own1 ? t->h_inv_perm[1 - m->row0] : -1, m->d_row_ptr, m->d_col, m->d_val, t->d_col_node,
@@ -2081,16 +2005,16 @@ extern "C" int kmcf_update_power_sparse(kmcf_tstate *t, const int *d_site_elemen
     if (p->solve_heating) {
         // shift (:2068-2071), forward currents and their row sums (:2086-2098), P = I_neg m (:2100-2131), copy_pdisp (:2137)
         min_kernel<<<1, KMCF_BLOCK, 0, st>>>(Na + 2, d_atom_virtual_potentials, t->d_scal + 1);
-        shift_kernel<<<grid1d(Na + 2), KMCF_BLOCK, 0, st>>>(Na + 2, d_atom_virtual_potentials, t->d_scal + 1);
+        shift_kernel<<<kmcf_grid1d(Na + 2), KMCF_BLOCK, 0, st>>>(Na + 2, d_atom_virtual_potentials, t->d_scal + 1);
         double *psum = m->d_r, *isum = m->d_Ap;                          // workspace vectors, free after the solve
         if (n_loc > 0) {
-            power_neighbour_kernel<16><<<grid1d((int64_t)n_loc * 16), KMCF_BLOCK, 0, st>>>(
+            power_neighbour_kernel<16><<<kmcf_grid1d((int64_t)n_loc * 16), KMCF_BLOCK, 0, st>>>(
                 n_loc, m->d_row_ptr, m->d_col, m->d_val, t->d_diag_pos, t->d_col_node, d_atom_virtual_potentials, p->Vd, psum, isum);
             KMCF_HIP(hipGetLastError());
         }
         if (t->sub.spread) {                                               // (every rank of the group: its strips, then the gather)
             kmcf_subop &sb = t->sub;
-            gather_tunnel_pot_kernel<<<grid1d(sb.n_glob), KMCF_BLOCK, 0, st>>>(sb.n_glob, t->d_tidx, d_atom_virtual_potentials, sb.d_xsub);
+            gather_tunnel_pot_kernel<<<kmcf_grid1d(sb.n_glob), KMCF_BLOCK, 0, st>>>(sb.n_glob, t->d_tidx, d_atom_virtual_potentials, sb.d_xsub);
             KMCF_TRY(symm_launch<1>(sb, sb.d_xsub, p->Vd, st));
             KMCF_TRY((symm_spread_finish<1, false>(c, sb, sb.n_loc, sb.row0, sb.d_rows, nullptr, psum, isum, nullptr, nullptr, 0)));
             KMCF_HIP(hipMemsetAsync(sb.d_xsub + sb.n_glob, 0, (size_t)(64 * sb.nb - sb.n_glob) * sizeof(double), st));
@@ -2098,7 +2022,7 @@ extern "C" int kmcf_update_power_sparse(kmcf_tstate *t, const int *d_site_elemen
         if (n_loc > 0) {
             if (t->sub.n_loc > 0 && t->sub.dense && !t->sub.spread) {
                 kmcf_subop &sb = t->sub;
-                gather_tunnel_pot_kernel<<<grid1d(sb.n_glob), KMCF_BLOCK, 0, st>>>(sb.n_glob, t->d_tidx, d_atom_virtual_potentials, sb.d_xsub);
+                gather_tunnel_pot_kernel<<<kmcf_grid1d(sb.n_glob), KMCF_BLOCK, 0, st>>>(sb.n_glob, t->d_tidx, d_atom_virtual_potentials, sb.d_xsub);
                 KMCF_TRY(symm_launch<1>(sb, sb.d_xsub, p->Vd, st));
                 sub_symm_reduce_kernel<1, false><<<sb.nb, KMCF_BLOCK, 0, st>>>(sb.n_glob, sb.nb, sb.d_strip_first, sb.d_rowpart, sb.d_colpart,
                                                                                           sb.d_rows, nullptr, psum, isum, nullptr, nullptr, 0);
@@ -2107,11 +2031,11 @@ extern "C" int kmcf_update_power_sparse(kmcf_tstate *t, const int *d_site_elemen
                 power_tunnel_kernel<<<t->sub.grid, KMCF_BLOCK, 0, st>>>(t->sub.n_loc, t->sub.row0, t->sub.n_groups, t->sub.d_mask, t->sub.d_voff,
                                                                        t->sub.d_val, t->d_tidx, t->sub.d_rows, d_atom_virtual_potentials, p->Vd,
                                                                        psum, isum);
-            power_finish_kernel<<<grid1d(n_loc), KMCF_BLOCK, 0, st>>>(n_loc, t->d_col_node, d_atom_virtual_potentials, psum, isum, t->d_pdisp);
+            power_finish_kernel<<<kmcf_grid1d(n_loc), KMCF_BLOCK, 0, st>>>(n_loc, t->d_col_node, d_atom_virtual_potentials, psum, isum, t->d_pdisp);
         }
         KMCF_HIP(hipGetLastError());
         KMCF_TRY(kmcf_comm_allgatherv_double(c, t->d_pdisp, m->counts.data(), m->displs.data()));
-        copy_pdisp_kernel<<<grid1d(Na - 1), KMCF_BLOCK, 0, st>>>(Na - 1, t->d_atom_site, t->d_acls, t->d_pdisp, p->alpha_disp, d_site_power);
+        copy_pdisp_kernel<<<kmcf_grid1d(Na - 1), KMCF_BLOCK, 0, st>>>(Na - 1, t->d_atom_site, t->d_acls, t->d_pdisp, p->alpha_disp, d_site_power);
         KMCF_HIP(hipGetLastError());
     }
     KMCF_HIP(hipStreamSynchronize(st));
@@ -2146,7 +2070,7 @@ extern "C" int kmcf_current_map(kmcf_tstate *t, const double *d_atom_virtual_pot
     if (d_site_net) KMCF_HIP(hipMemsetAsync(d_site_net, 0, (size_t)N * sizeof(double), st));
     // this rank's rows: the neighbour part sets the three sums of a node, the tunnel part adds the row's pairs of the bitmap
     if (n_loc > 0) {
-        current_neighbour_kernel<16><<<grid1d((int64_t)n_loc * 16), KMCF_BLOCK, 0, st>>>(n_loc, m->d_row_ptr, m->d_col, m->d_val, t->d_diag_pos,
+        current_neighbour_kernel<16><<<kmcf_grid1d((int64_t)n_loc * 16), KMCF_BLOCK, 0, st>>>(n_loc, m->d_row_ptr, m->d_col, m->d_val, t->d_diag_pos,
                                                                                          t->d_col_node, pot, t->d_cmap);
         KMCF_HIP(hipGetLastError());
     }
@@ -2158,7 +2082,7 @@ extern "C" int kmcf_current_map(kmcf_tstate *t, const double *d_atom_virtual_pot
     }
     // every rank gets all nodes (as d_pdisp is gathered: the row partition, three doubles a row)
     KMCF_TRY(kmcf_comm_allgatherv_double(c, t->d_cmap, t->cm_counts.data(), t->cm_displs.data()));
-    current_scatter_kernel<<<grid1d(Na - 1), KMCF_BLOCK, 0, st>>>(Na - 1, t->d_atom_site, t->d_cmap, d_site_current, d_site_tunnel, d_site_net);
+    current_scatter_kernel<<<kmcf_grid1d(Na - 1), KMCF_BLOCK, 0, st>>>(Na - 1, t->d_atom_site, t->d_cmap, d_site_current, d_site_tunnel, d_site_net);
     current_stats_kernel<<<1, KMCF_BLOCK, 0, st>>>(Na - 1, t->d_atom_site, t->d_cmap, t->d_cmstat);
     KMCF_HIP(hipGetLastError());
     KMCF_HIP(hipMemcpyAsync(t->h_cmstat, t->d_cmstat, 6 * sizeof(double), hipMemcpyDeviceToHost, st));

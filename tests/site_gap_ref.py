@@ -14,6 +14,7 @@ import numpy as np
 from scipy.spatial import cKDTree
 
 import clusters_ref as CR
+import site_kernels_ref as SK
 
 GAP_DTYPE = np.dtype([("gap", np.float64), ("gap2", np.float64), ("x_left", np.float64), ("x_right", np.float64),
                       ("site_left", np.int32), ("site_right", np.int32), ("n_left", np.int32), ("n_right", np.int32),
@@ -234,8 +235,127 @@ def _dense():
     return _shuffled(dict(name="dense", xyz=xyz, side=side, cell=cell, n_cells=3, r_max=0.5, cutoff=5.0), 7)
 
 
+def index_positions(c):
+    """position of every site in the index's cell order (cell id (cx ncy + cy) ncz + cz, ascending site id inside a cell):
+    the order in which the compaction scans the flags, SCAN_TILE of them per tile"""
+    coords, nc = index_coords(c)
+    cid = (coords[:, 0] * nc[1] + coords[:, 1]) * nc[2] + coords[:, 2]
+    pos = np.empty(len(cid), np.int64)
+    pos[np.argsort(cid, kind="stable")] = np.arange(len(cid))
+    return pos
+
+
+def _large():
+    """The 83 x 81 x 80 jittered lattice of the pairwise tests (537 840 sites, 263 scan tiles, index cells of 20 A), one gap
+    cell.  Members only at the two ends of the cell order: from position 256 tiles on (a random third each A, B, none) and
+    48 positions of the first tile -- the A and B counts of tiles 1 .. 255 are zero, so both totals and every offset of
+    the last tiles hold what the scan carries from its first pass of 256 tiles into its second.  One B site of the last
+    tile is moved to 0.3 A from an A site of the last tile: closer than two lattice sites can be (4 - 0.6 A), so
+    pair = (a, b, d2) is the answer by construction.  (The record itself would survive a lost carry, which moves all
+    those list positions alike: `large_two` is the case that notices.)"""
+    xyz = SK.pairwise_case("large")["xyz"].copy()
+    base = dict(xyz=xyz, cutoff=SK.CUTOFF)
+    last = np.flatnonzero(index_positions(base) >= 262 * SK.SCAN_TILE)
+    a, b = int(last[len(last) // 2]), int(last[len(last) // 2 + 1])             # two sites inside the last index cells
+    xyz[b] = xyz[a] + np.array([0.3, 0.0, 0.0])
+    pos = index_positions(base)                                                # (of the final coordinates)
+    rng = np.random.default_rng(263)
+    side = np.zeros(len(xyz), np.int32)
+    ends = (pos >= 256 * SK.SCAN_TILE) | ((pos >= 1000) & (pos < 1048))
+    side[ends] = rng.integers(0, 3, int(ends.sum()))
+    side[a], side[b] = 1, 2
+    return dict(name="large", xyz=xyz, side=side, cell=None, n_cells=1, r_max=SK.CUTOFF, cutoff=SK.CUTOFF,
+                pair=(a, b, float(d2_exact(xyz, a, b))))
+
+
+def _large_two():
+    """`large` with TWO gap cells, so that a record depends on what the scan carries from its first pass of 256 tiles into
+    its second: gap cell 0 = the positions below 256 tiles (its members: 48 positions of the first tile and a planted pair
+    there), gap cell 1 = the positions from 256 tiles on, its planted pair (a1, b1) at the very start of tile 256.  With
+    the carry lost, tile 256's first members are written to the list slots of the first tile's members: whichever write
+    stays, one cell loses a site of its planted pair (device_search(carry=False) shows both outcomes)."""
+    T = SK.SCAN_TILE
+    xyz = SK.pairwise_case("large")["xyz"].copy()
+    base = dict(xyz=xyz, cutoff=SK.CUTOFF)
+    at = np.argsort(index_positions(base))                                      # site at every position
+    a0, b0, a1, b1 = (int(at[p]) for p in (1010, 1011, 256 * T + 2, 256 * T + 3))
+    xyz[b0] = xyz[a0] + np.array([0.3, 0.0, 0.0])
+    xyz[b1] = xyz[a1] + np.array([0.3, 0.0, 0.0])
+    pos = index_positions(base)                                                # (of the final coordinates)
+    rng = np.random.default_rng(264)
+    side = np.zeros(len(xyz), np.int32)
+    first, tail = (pos >= 1000) & (pos < 1048), pos >= 256 * T
+    side[first] = rng.integers(0, 3, int(first.sum()))                         # a third each: A, B, none
+    side[tail] = rng.choice(np.array([0, 1, 2], np.int32), int(tail.sum()), p=[0.8, 0.1, 0.1])
+    side[[a0, a1]], side[[b0, b1]] = 1, 2
+    return dict(name="large_two", xyz=xyz, side=side, cell=(pos >= 256 * T).astype(np.int32), n_cells=2, r_max=SK.CUTOFF,
+                cutoff=SK.CUTOFF, pairs=[(a0, b0, float(d2_exact(xyz, a0, b0))), (a1, b1, float(d2_exact(xyz, a1, b1)))])
+
+
+def device_search(c, carry=True, later_write_stays=True):
+    """The compaction and search of csrc/kmcf_gap.hip restated step by step on the index's cell order -- per-tile counts of
+    the A and B flags, their exclusive scan in passes of 256 tiles, the scatter into the member lists, the walk of the
+    runs bpos[cell_start[..]] of the 27 index cells, the minimum per gap cell -- so that a defect of the scan can be put
+    in: carry=False starts every pass of the scan from 0 (offsets and the total), and later_write_stays picks which of
+    two writes to one list slot survives (ascending or descending tile).  Returns [(a, b, d2) or None per gap cell]."""
+    T = SK.SCAN_TILE
+    xyz, r2 = c["xyz"], c["r_max"] * c["r_max"]
+    N = len(xyz)
+    gcell = cells_of(c["cell"], c["n_cells"], N)
+    coords, nc = index_coords(c)
+    cid = (coords[:, 0] * nc[1] + coords[:, 1]) * nc[2] + coords[:, 2]
+    order = np.argsort(cid, kind="stable")
+    cell_start = np.searchsorted(cid[order], np.arange(int(nc.prod()) + 1))
+    flags = np.where(gcell[order] >= 0, c["side"][order] & 3, 0)
+
+    def positions(flag):                                                       # (list position of every slot, total)
+        cnt = np.add.reduceat(flag.astype(np.int64), np.arange(0, N, T))
+        off = np.zeros(len(cnt), np.int64)
+        total = 0
+        for p0 in range(0, len(cnt), 256):
+            base = total if carry else 0
+            off[p0:p0 + 256] = base + np.cumsum(cnt[p0:p0 + 256]) - cnt[p0:p0 + 256]
+            total = base + int(cnt[p0:p0 + 256].sum())
+        inside = np.cumsum(flag) - flag.astype(np.int64)
+        inside = inside - np.repeat(inside[::T], T)[:N]
+        return np.repeat(off, T)[:N] + inside, total
+
+    def scatter(flag, where, total):
+        t = np.flatnonzero(flag)
+        if not later_write_stays:
+            t = t[::-1]
+        lst = np.full(max(total, int(where[t].max()) + 1 if len(t) else 0), -1, np.int64)
+        lst[where[t]] = order[t]                                                # (a repeated index keeps the last value)
+        return lst[:total]
+
+    fa, fb = (flags & 1) != 0, (flags & 2) != 0
+    apos, n_a = positions(fa)
+    bpos, n_b = positions(fb)
+    alist, bsite = scatter(fa, apos, n_a), scatter(fb, bpos, n_b)
+    bpos = np.append(bpos, n_b)
+    best = [None] * c["n_cells"]
+    for a in alist[alist >= 0]:                                                # (-1: a slot below the total that nobody wrote)
+        cx, cy, cz = coords[a]
+        runs = []
+        for ax in range(max(cx - 1, 0), min(cx + 1, nc[0] - 1) + 1):
+            for ay in range(max(cy - 1, 0), min(cy + 1, nc[1] - 1) + 1):
+                lo = (ax * nc[1] + ay) * nc[2] + max(cz - 1, 0)
+                hi = (ax * nc[1] + ay) * nc[2] + min(cz + 1, nc[2] - 1)
+                runs.append(np.arange(bpos[cell_start[lo]], min(bpos[cell_start[hi + 1]], n_b)))
+        b = bsite[np.concatenate(runs)]
+        b = b[b >= 0]
+        b = b[gcell[b] == gcell[a]]
+        d2 = d2_exact(xyz, a, b)
+        for k in np.flatnonzero(d2 <= r2):
+            got = (float(d2[k]), int(a), int(b[k]))
+            if best[gcell[a]] is None or got < best[gcell[a]]:
+                best[gcell[a]] = got
+    return [None if g is None else (g[1], g[2], g[0]) for g in best]
+
+
 BUILDERS = {"planes": _planes, "straddle": _straddle, "rim": lambda: _rim(5.0),
-            "rim_below": lambda: _rim(float(np.nextafter(5.0, 0.0))), "mixed": _mixed, "dense": _dense}
+            "rim_below": lambda: _rim(float(np.nextafter(5.0, 0.0))), "mixed": _mixed, "dense": _dense, "large": _large,
+            "large_two": _large_two}
 _cache = {}
 
 

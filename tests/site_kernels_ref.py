@@ -18,7 +18,7 @@ from scipy.special import erfc
 Q_E = 1.60217663e-19                    # gpu_solvers.h:323
 OXYGEN_DEFECT, VACANCY = 1, 2           # src/utils.h:37-44
 OXIDE_TYPES = (3, 4)                    # any type that is neither a defect, a vacancy nor in the metal list
-SCAN_TILE = 2048                        # flags per block of the compaction scan (csrc/kmcf_pairwise.hip)
+SCAN_TILE = 2048                        # flags per block of the compaction scan (KMCF_SCAN_TILE, csrc/kmcf_block.hpp)
 CUTOFF = 20.0
 SENTINEL = 123.0
 

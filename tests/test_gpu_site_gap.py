@@ -70,7 +70,7 @@ class _Index:
         self.km.lib.load().kmcf_pairwise_destroy(self.handle)
 
 
-@pytest.mark.parametrize("name", ["planes", "straddle", "rim", "rim_below", "mixed", "dense"])
+@pytest.mark.parametrize("name", ["planes", "straddle", "rim", "rim_below", "mixed", "dense", "large", "large_two"])
 def test_site_sets_match_the_restatement(km, comm, name):
     ix = _Index(km, comm, GR.case(name))
     try:

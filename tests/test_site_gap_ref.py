@@ -195,6 +195,64 @@ def test_dense_fills_one_index_cell():
     assert stats["cells_open"] == 3 and (gaps["gap2"] > 0).all()
 
 
+def test_large_members_sit_at_the_two_ends_of_263_tiles_and_the_planted_pair_wins():
+    c = GR.case("large")
+    tile = GR.index_positions(c) // GR.SK.SCAN_TILE
+    N = len(c["xyz"])
+    assert N == 537840 and tile.max() == 262 and c["cutoff"] == c["r_max"] == 20.0
+    for bit in (1, 2):                                             # A, B: per-tile counts as the compaction forms them
+        cnt = np.bincount(tile[(c["side"] & bit) != 0], minlength=263)
+        print("set %d: first tile %d, tiles 1..255 %d, tiles 256..262 %s" % (bit, cnt[0], cnt[1:256].sum(), cnt[256:].tolist()))
+        assert cnt[0] >= 8 and cnt[1:256].sum() == 0 and (cnt[256:] >= 100).all()
+    a, b, d2 = c["pair"]
+    assert tile[a] == 262 and tile[b] == 262 and c["side"][a] == 1 and c["side"][b] == 2
+    assert 0.0899 < d2 < 0.0901 and d2 == GR.d2_exact(c["xyz"], a, b)
+    # no two other members come near that: the lattice leaves 4 - 0.6 A between any two sites, and b lies 0.3 A from one
+    others = np.setdiff1d(np.flatnonzero(c["side"]), [b])
+    d, _ = GR.cKDTree(c["xyz"][others]).query(c["xyz"][others], k=2)
+    assert d[:, 1].min() >= 3.4
+    assert np.sort(GR.cKDTree(c["xyz"][others]).query(c["xyz"][b], k=2)[0])[1] >= 3.1
+    gaps, stats = GR.reference("large")
+    g = gaps[0]
+    assert (g["site_left"], g["site_right"], g["gap2"]) == (a, b, d2) and g["bridged"] == 0
+    assert (g["x_left"], g["x_right"]) == (c["xyz"][a, 0], c["xyz"][b, 0])
+    assert stats["cells_open"] == 1 and stats["n_both"] == 0
+    assert stats["n_left"] == int((c["side"] == 1).sum()) and stats["n_right"] == int((c["side"] == 2).sum())
+    assert 3000 <= stats["n_left"] <= 6000 and 3000 <= stats["n_right"] <= 6000
+
+
+def test_large_two_has_a_record_that_depends_on_the_carry_of_the_scan():
+    """`large` itself cannot tell a lost carry: its pair lies in the last tile, and without the carry every list position
+    from tile 256 on moves down by the same amount.  `large_two` can: shown here on the step-by-step restatement of the
+    device's compaction and search, first intact (it gives the restatement's records), then with every pass of the scan
+    starting from 0, for either survivor of the two writes that then meet in one list slot."""
+    c = GR.case("large_two")
+    T = GR.SK.SCAN_TILE
+    pos = GR.index_positions(c)
+    tile = pos // T
+    (a0, b0, d0), (a1, b1, d1) = c["pairs"]
+    assert tile.max() == 262 and c["n_cells"] == 2 and np.array_equal(c["cell"], (tile >= 256).astype(np.int32))
+    cnt = {bit: np.bincount(tile[(c["side"] & bit) != 0], minlength=263) for bit in (1, 2)}
+    for bit in (1, 2):
+        print("set %d: first tile %d, tiles 256..262 %s" % (bit, cnt[bit][0], cnt[bit][256:].tolist()))
+        assert cnt[bit][0] >= 8 and cnt[bit][1:256].sum() == 0 and (cnt[bit][256:] >= 100).all()
+    assert tile[a0] == 0 and tile[b0] == 0 and tile[a1] == 256 and tile[b1] == 256
+    # the planted sites of cell 1 are among the first members of tile 256: as many as the first tile holds
+    for site, bit in ((a1, 1), (b1, 2)):
+        rank = int(((tile == 256) & ((c["side"] & bit) != 0) & (pos < pos[site])).sum())
+        assert rank < cnt[bit][0], (rank, cnt[bit][0])
+    assert 0.0899 < d0 < 0.0901 and 0.0899 < d1 < 0.0901
+    gaps, stats = GR.reference("large_two")
+    want = [(a0, b0, d0), (a1, b1, d1)]
+    assert [(g["site_left"], g["site_right"], g["gap2"]) for g in gaps] == want and stats["cells_open"] == 2
+    assert GR.device_search(c) == want
+    for later in (True, False):
+        broken = GR.device_search(c, carry=False, later_write_stays=later)
+        print("scan without its carry, %s write stays:" % ("later" if later else "earlier"), broken)
+        assert broken != want
+        assert (broken[0] != want[0]) if later else (broken[1] != want[1])   # the cell whose members were overwritten
+
+
 # ---- struct layout and argument errors ---------------------------------------------------------------------------------------
 
 def test_python_struct_layout(km):

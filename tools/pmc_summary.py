@@ -21,7 +21,7 @@ def kernel_source_sha():
     """What bench.py compares before it reports a committed traffic figure: the SpMV kernels' source as profiled."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     h = hashlib.sha256()
-    for f in sorted(glob.glob(os.path.join(root, "*_amd", "csrc", "kmcf_spmv.hip")) + glob.glob(os.path.join(root, "*_amd", "csrc", "kmcf_internal.hpp"))):
+    for f in sorted(sum((glob.glob(os.path.join(root, "*_amd", "csrc", name)) for name in ("kmcf_spmv.hip", "kmcf_internal.hpp", "kmcf_block.hpp")), [])):
         h.update(open(f, "rb").read())
     return h.hexdigest()[:16]
 
