@@ -17,15 +17,7 @@ namespace {
 __device__ __forceinline__ double site_dist_dev(double x1, double y1, double z1, double x2, double y2, double z2,
                                                 double ly, double lz, int pbc)
 {
-    if (pbc == 1) {
-        double dist_x = x1 - x2;
-        double fy = (y1 - y2) / ly;
-        fy -= round(fy);
-        double fz = (z1 - z2) / lz;
-        fz -= round(fz);
-        double dy = fy * ly, dz = fz * lz;
-        return sqrt(dist_x * dist_x + dy * dy + dz * dz);
-    }
+    if (pbc == 1) return kmcf_min_image_dist(x1, y1, z1, x2, y2, z2, ly, lz);
     double dx = x2 - x1, dy = y2 - y1, dz = z2 - z1;
     return sqrt(dx * dx + dy * dy + dz * dz);
 }

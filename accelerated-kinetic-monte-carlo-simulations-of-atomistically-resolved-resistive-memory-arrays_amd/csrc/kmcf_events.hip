@@ -117,6 +117,36 @@ __device__ __forceinline__ const double *ev_T(thermal_field th) { return th.T; }
 __device__ __forceinline__ const double *ev_T() { return nullptr; }
 __device__ __forceinline__ int *ev_bad(thermal_field th) { return th.bad; }
 __device__ __forceinline__ int *ev_bad() { return nullptr; }
+// The periodic instantiations (kmcf_events_set_lattice with pbc == 1) take one ev_lattice LAST in the pack and form the
+// minimum-image distance; without it the pack, the parameter list and the distance expression are the ones above.
+struct ev_lattice { double ly, lz; };
+__device__ __forceinline__ const double *ev_T(thermal_field th, ev_lattice) { return th.T; }
+__device__ __forceinline__ const double *ev_T(ev_lattice) { return nullptr; }
+__device__ __forceinline__ int *ev_bad(thermal_field th, ev_lattice) { return th.bad; }
+__device__ __forceinline__ int *ev_bad(ev_lattice) { return nullptr; }
+__device__ __forceinline__ double ev_pair_dist(const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ z, int i, int j)
+{
+    const double dx = x[j] - x[i], dy = y[j] - y[i], dz = z[j] - z[i];
+    return sqrt(dx * dx + dy * dy + dz * dz);
+}
+__device__ __forceinline__ double ev_pair_dist(const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ z, int i, int j,
+                                               thermal_field)
+{
+    return ev_pair_dist(x, y, z, i, j);
+}
+__device__ __forceinline__ double ev_pair_dist(const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ z, int i, int j,
+                                               ev_lattice L)
+{
+    return kmcf_min_image_dist(x[i], y[i], z[i], x[j], y[j], z[j], L.ly, L.lz);
+}
+__device__ __forceinline__ double ev_pair_dist(const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ z, int i, int j,
+                                               thermal_field, ev_lattice L)
+{
+    return ev_pair_dist(x, y, z, i, j, L);
+}
+template <class... TH> struct ev_pack_periodic : std::false_type {};
+template <class... TH> struct ev_pack_periodic<ev_lattice, TH...> : std::true_type {};
+template <class T0, class... TH> struct ev_pack_periodic<T0, TH...> : ev_pack_periodic<TH...> {};
 
 // build_event_list_split, src/kmc_events.cu:128-207.  MODE = the rate mode (include/kmcfield.h).  KMCF_RATE_T_BG is
 // instantiated with an empty pack: the parameter list and the arithmetic of the kernel before the thermal modes.
@@ -132,7 +162,8 @@ __global__ __launch_bounds__(KMCF_BLOCK) void build_event_list_kernel(
     const int *__restrict__ charge, layer_energies E, unsigned char *__restrict__ event_type,
     double *__restrict__ event_prob, TH... th)
 {
-    static_assert(MODE == KMCF_RATE_T_BG ? sizeof...(TH) == 0 : sizeof...(TH) == 1, "thermal modes take one thermal_field");
+    static_assert(sizeof...(TH) == (MODE == KMCF_RATE_T_BG ? 0 : 1) + (ev_pack_periodic<TH...>::value ? 1 : 0),
+                  "thermal modes take one thermal_field, periodic instantiations one ev_lattice behind it");
     const double kB = 8.617333262e-5, epsilon = 1e-200;
     const double *__restrict__ T = ev_T(th...);
     int *__restrict__ bad = ev_bad(th...);
@@ -143,8 +174,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void build_event_list_kernel(
         const int i = (int)(id / nn) + start_i;
         const int j = neigh_idx[id];
         if (j >= 0 && j < N) {
-            const double dx = x[j] - x[i], dy = y[j] - y[i], dz = z[j] - z[i];
-            const double dist = 1e-10 * sqrt(dx * dx + dy * dy + dz * dz);
+            const double dist = 1e-10 * ev_pair_dist(x, y, z, i, j, th...);
             const int ei = element[i], ej = element[j];
             const double dpot = pot[i] - pot[j];
             double EA = 0.0;
@@ -1044,9 +1074,25 @@ void launch_build_event_list(int rate_mode, int grid, hipStream_t st, int N, int
                              const int *d_site_layer, double T_bg, double freq, double sigma, double k, const double *d_x,
                              const double *d_y, const double *d_z, const double *d_pot, const int *d_site_element,
                              const int *d_site_charge, const layer_energies &E, unsigned char *d_type, double *d_prob,
-                             const double *d_site_temperature, int *d_bad)
+                             const double *d_site_temperature, int *d_bad, const kmcf_comm *c)
 {
     const thermal_field th = {d_site_temperature, d_bad};
+    if (c->ev_pbc) {                            // the periodic instantiations: nothing below changes
+        const ev_lattice L = {c->ev_ly, c->ev_lz};
+        if (rate_mode == KMCF_RATE_EKIN)
+            build_event_list_kernel<KMCF_RATE_EKIN><<<grid, KMCF_BLOCK, 0, st>>>(N, count, start_i, nn, d_neigh_idx, d_site_layer, T_bg,
+                                                                                 freq, sigma, k, d_x, d_y, d_z, d_pot, d_site_element,
+                                                                                 d_site_charge, E, d_type, d_prob, th, L);
+        else if (rate_mode == KMCF_RATE_T_SITE)
+            build_event_list_kernel<KMCF_RATE_T_SITE><<<grid, KMCF_BLOCK, 0, st>>>(N, count, start_i, nn, d_neigh_idx, d_site_layer, T_bg,
+                                                                                   freq, sigma, k, d_x, d_y, d_z, d_pot, d_site_element,
+                                                                                   d_site_charge, E, d_type, d_prob, th, L);
+        else
+            build_event_list_kernel<KMCF_RATE_T_BG><<<grid, KMCF_BLOCK, 0, st>>>(N, count, start_i, nn, d_neigh_idx, d_site_layer, T_bg,
+                                                                                 freq, sigma, k, d_x, d_y, d_z, d_pot, d_site_element,
+                                                                                 d_site_charge, E, d_type, d_prob, L);
+        return;
+    }
     if (rate_mode == KMCF_RATE_EKIN)
         build_event_list_kernel<KMCF_RATE_EKIN><<<grid, KMCF_BLOCK, 0, st>>>(N, count, start_i, nn, d_neigh_idx, d_site_layer, T_bg, freq,
                                                                              sigma, k, d_x, d_y, d_z, d_pot, d_site_element,
@@ -1189,7 +1235,7 @@ int execute_kmc_step_impl(const char *what, kmcf_comm *c, int N, const int *h_co
         const int g = build_grid(M);
         launch_build_event_list(rate_mode, g, st, N, count, start_i, nn, d_neigh_idx, d_site_layer, T_bg, freq, sigma, k, d_x, d_y, d_z,
                                 d_site_potential_charge, d_site_element, d_site_charge, E, d_type, d_prob, d_site_temperature,
-                                thermal ? w->d_tbad + rank : nullptr);
+                                thermal ? w->d_tbad + rank : nullptr, c);
         zero_and_sum_kernel<<<nb, KMCF_BLOCK, 0, st>>>(M, start_i, nn, d_neigh_idx, d_type, d_prob, -1, -1, d_tsum);
         if (P == 1 && count == N && !kmcf_opt_set(c, KNOB_EVENTS_FULLSCAN)) {
             // the neighbour lists are built once per run (kmc_main.cpp:199): the verdict on their symmetry is
@@ -1437,6 +1483,21 @@ extern "C" int kmcf_events_reset(kmcf_comm *c)
     return KMCF_OK;
 }
 
+extern "C" int kmcf_events_set_lattice(kmcf_comm *c, const double *h_lattice, int pbc)
+{
+    const char *what = "kmcf_events_set_lattice";
+    KMCF_CHECK(c, KMCF_ERR_ARG, "%s: c is NULL", what);
+    KMCF_CHECK(pbc == 0 || pbc == 1, KMCF_ERR_ARG, "%s: pbc = %d is neither 0 nor 1", what, pbc);
+    if (pbc == 0) { c->ev_pbc = 0; c->ev_ly = c->ev_lz = 0.0; return KMCF_OK; }
+    KMCF_CHECK(h_lattice, KMCF_ERR_ARG, "%s: h_lattice is NULL with pbc = 1", what);
+    KMCF_CHECK(std::isfinite(h_lattice[1]) && h_lattice[1] > 0, KMCF_ERR_ARG, "%s: the period in y, h_lattice[1] = %g, is not finite and > 0",
+               what, h_lattice[1]);
+    KMCF_CHECK(std::isfinite(h_lattice[2]) && h_lattice[2] > 0, KMCF_ERR_ARG, "%s: the period in z, h_lattice[2] = %g, is not finite and > 0",
+               what, h_lattice[2]);
+    c->ev_pbc = 1; c->ev_ly = h_lattice[1]; c->ev_lz = h_lattice[2];
+    return KMCF_OK;
+}
+
 extern "C" int kmcf_execute_kmc_step_thermal(kmcf_comm *c, int N, const int *h_count, const int *h_displs, int nn,
                                              const int *d_neigh_idx, const int *d_site_layer, double T_bg, double freq,
                                              double sigma, double k, const double *d_x, const double *d_y, const double *d_z,
@@ -1491,7 +1552,7 @@ extern "C" int kmcf_event_rates(kmcf_comm *c, int N, const int *h_count, const i
     if (ok) {
         launch_build_event_list(rate_mode, build_grid(M), st, N, count, start_i, nn, d_neigh_idx, d_site_layer, T_bg, freq, sigma, k,
                                 d_x, d_y, d_z, d_site_potential_charge, d_site_element, d_site_charge, E, d_type, d_prob,
-                                d_site_temperature, thermal ? d_bad : nullptr);
+                                d_site_temperature, thermal ? d_bad : nullptr, c);
         ok = hipGetLastError() == hipSuccess &&
              hipMemcpyAsync(&bad_site, d_bad, sizeof(int), hipMemcpyDeviceToHost, st) == hipSuccess &&
              (!h_type || hipMemcpyAsync(h_type, d_type, M, hipMemcpyDeviceToHost, st) == hipSuccess) &&

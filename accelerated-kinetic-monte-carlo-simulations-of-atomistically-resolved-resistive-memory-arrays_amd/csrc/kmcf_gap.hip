@@ -393,6 +393,8 @@ int gp_check_common(const char *what, const kmcf_pairwise *p, const double *d_x,
     KMCF_CHECK(n_cells >= 1, KMCF_ERR_ARG, "%s: n_cells = %d is not >= 1", what, n_cells);
     KMCF_CHECK(d_site_cell || n_cells == 1, KMCF_ERR_ARG, "%s: d_site_cell is NULL with n_cells = %d", what, n_cells);
     KMCF_CHECK(p, KMCF_ERR_ARG, "%s: p is NULL", what);
+    KMCF_CHECK(!p->pbc, KMCF_ERR_ARG, "%s: the index is periodic (kmcf_compute_cutoff_list_pbc with pbc = 1) and the gap search is "
+               "non-periodic: build a non-periodic index for it", what);
     KMCF_CHECK(r_max <= p->cutoff, KMCF_ERR_ARG, "%s: r_max = %g exceeds the index's cutoff radius %g", what, r_max, p->cutoff);
     return KMCF_OK;
 }

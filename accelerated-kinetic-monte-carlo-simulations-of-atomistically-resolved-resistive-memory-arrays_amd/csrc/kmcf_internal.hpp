@@ -123,6 +123,10 @@ struct kmcf_comm {
     struct kmcf_event_cache *ev_cache = nullptr;
     // workspace of kmcf_conductive_clusters (kmcf_clusters.hip): buffers only, no result outlives a call
     struct kmcf_cluster_ws *cl_ws = nullptr;
+    // geometry of the event step's pair distance (kmcf_events_set_lattice): 1 = minimum image in y and z with these periods.
+    // Plain values: kmcf_events_reset leaves them, they go with the communicator
+    int ev_pbc = 0;
+    double ev_ly = 0.0, ev_lz = 0.0;
     kmcf_knob_overrides opts;           // kmcf_set_option: this communicator's knob values (kmcf_opt*)
     bool connect_begun = false;         // kmcf_comm_connect / kmcf_comm_p2p_export ran (or a loopback group was created):
                                         // connect-scope knobs are refused from here on
@@ -217,10 +221,21 @@ __host__ __device__ inline int kmcf_cell_coord(double v, double v0, double inv, 
     return c < 0 ? 0 : (c >= nc ? nc - 1 : c);
 }
 
+// A periodic index (kmcf_compute_cutoff_list_pbc, pbc == 1) keeps x as above; in y and z its cells tile one period
+// [y0, y0 + Ly) exactly: ncy = max(1, floor(Ly / cutoff)) cells of width Ly / ncy >= cutoff, coordinate
+// kmcf_cell_coord(y, y0, ncy / Ly, ncy).  Same cell id, same order inside a cell: the compaction kernels are shared.
+struct kmcf_cell_grid_pbc {
+    double x0, y0, z0, inv_x, inv_y, inv_z, ly, lz;
+    int ncx, ncy, ncz;
+};
+
 struct kmcf_pairwise {
     kmcf_comm *comm = nullptr;
     int N = 0;
     double cutoff = 20.0;
+    int pbc = 0;                   // 1: periodic index; lattice = the caller's h_lattice (zeros when none was given)
+    double lattice[3] = {0, 0, 0};
+    double inv_y = 0, inv_z = 0;   // periodic index only: ncy / Ly, ncz / Lz
     double x0 = 0, y0 = 0, z0 = 0, inv = 0;
     int ncx = 1, ncy = 1, ncz = 1;
     int ncell = 1;
@@ -232,6 +247,7 @@ struct kmcf_pairwise {
     int n_blocks = 0;
     struct kmcf_gap_ws *gap_ws = nullptr;   // scratch of kmcf_site_set_gap / kmcf_filament_gap (kmcf_gap.hip): buffers only
     kmcf_cell_grid grid() const { return kmcf_cell_grid{x0, y0, z0, inv, cutoff, ncx, ncy, ncz}; }
+    kmcf_cell_grid_pbc grid_pbc() const { return kmcf_cell_grid_pbc{x0, y0, z0, inv, inv_y, inv_z, lattice[1], lattice[2], ncx, ncy, ncz}; }
 };
 void kmcf_gap_ws_free(kmcf_pairwise *p);
 
@@ -686,6 +702,21 @@ inline hipStream_t kmcf_setup_stream(const kmcf_comm *c) { return c->caller_stre
 // shuffle loop: the results (and with them the device-order restatement the tests compare with) do not change.
 // All 64 lanes must be active.  (tools/lab/xlane_lab.hip checks the patterns against __shfl_xor.)
 #if defined(__HIPCC__)
+// The reference's four-argument site_dist_gpu with pbc == 1 (src/gpu_solvers.h:287-319), operation for operation: x is
+// never periodic, y and z take the minimum image through round() -- the C round, half away from zero.  One distance for
+// the K pattern, the periodic neighbour list, the periodic pairwise term and the periodic event list.
+__device__ __forceinline__ double kmcf_min_image_dist(double x1, double y1, double z1, double x2, double y2, double z2,
+                                                      double ly, double lz)
+{
+    double dist_x = x1 - x2;
+    double fy = (y1 - y2) / ly;
+    fy -= round(fy);
+    double fz = (z1 - z2) / lz;
+    fz -= round(fz);
+    double dy = fy * ly, dz = fz * lz;
+    return sqrt(dist_x * dist_x + dy * dy + dz * dz);
+}
+
 typedef unsigned int kmcf_u2 __attribute__((ext_vector_type(2)));
 template <int CTRL>
 __device__ __forceinline__ double kmcf_dpp_f64(double v)

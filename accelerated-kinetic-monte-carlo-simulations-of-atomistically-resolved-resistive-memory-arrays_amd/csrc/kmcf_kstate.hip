@@ -46,6 +46,39 @@ __global__ __launch_bounds__(KMCF_BLOCK) void neighbor_list_kernel(
     }
 }
 
+// The same list under the minimum image in y and z (kmcf_neighbor_list_pbc, pbc == 1): the wrapped cell grid of the K
+// pattern, or -- cells == 0: fewer than 3 cells fit a period, or the sites span one -- every site j in turn.
+__global__ __launch_bounds__(KMCF_BLOCK) void neighbor_list_pbc_kernel(
+    cell_grid g, int cells, const int *__restrict__ cell_start, const int *__restrict__ cell_items,
+    const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ z,
+    double nn_dist, double ly, double lz, int N, int nn, int count, int displ, int *__restrict__ neigh_idx,
+    int *__restrict__ overflow)
+{
+    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < count; idx += gridDim.x * blockDim.x) {
+        const int i = idx + displ;
+        int buf[NL_CAP];
+        int n = 0;
+        if (cells) {
+            for_each_neighbour(g, cell_start, cell_items, x, y, z, i, nn_dist, ly, lz, 1, 0, N, [&](int j) {
+                if (j == i) return;
+                if (n >= NL_CAP) { *overflow = 1; return; }
+                int k = n;
+                while (k > 0 && buf[k - 1] > j) { buf[k] = buf[k - 1]; --k; }
+                buf[k] = j;
+                ++n;
+            });
+        } else {
+            const double xi = x[i], yi = y[i], zi = z[i];
+            for (int j = 0; j < N; ++j) {                       // ascending j: no sorting
+                if (j == i || !(kmcf_min_image_dist(xi, yi, zi, x[j], y[j], z[j], ly, lz) < nn_dist)) continue;
+                if (n >= NL_CAP) { *overflow = 1; break; }
+                buf[n++] = j;
+            }
+        }
+        for (int t = 0; t < nn; ++t) neigh_idx[(size_t)idx * nn + t] = (t < n) ? buf[t] : -1;
+    }
+}
+
 // ---------------------------------------------------------------- charge
 // update_charge, src/potential_solver_gpu.cu:12-63.  16 lanes per site.
 __device__ __forceinline__ bool is_metal_dev(const int *__restrict__ metals, int num_metals, int e)
@@ -846,18 +879,20 @@ extern "C" int kmcf_update_temperature_global(kmcf_comm *c, const double *d_site
     return KMCF_OK;
 }
 
-extern "C" int kmcf_neighbor_list(kmcf_comm *c, const double *d_x, const double *d_y, const double *d_z, int N,
-                                  double nn_dist, int nn, int count, int displ, int *d_neigh_idx)
+// kmcf_neighbor_list (pbc == 0: lattice unused) and kmcf_neighbor_list_pbc
+static int neighbor_list_impl(const char *what, kmcf_comm *c, const double *d_x, const double *d_y, const double *d_z, int N,
+                              const double *h_lattice, int pbc, double nn_dist, int nn, int count, int displ, int *d_neigh_idx)
 {
-    KMCF_CHECK(c && d_x && d_y && d_z && d_neigh_idx, KMCF_ERR_ARG, "kmcf_neighbor_list: null argument");
-    KMCF_CHECK(c->device >= 0, KMCF_ERR_STATE, "kmcf_neighbor_list: host-only communicator");
-    KMCF_CHECK(nn > 0 && nn <= NL_CAP && count >= 0 && displ >= 0 && displ + count <= N, KMCF_ERR_ARG, "kmcf_neighbor_list: bad sizes");
+    KMCF_CHECK(c && d_x && d_y && d_z && d_neigh_idx, KMCF_ERR_ARG, "%s: null argument", what);
+    KMCF_CHECK(c->device >= 0, KMCF_ERR_STATE, "%s: host-only communicator", what);
+    KMCF_CHECK(nn > 0 && nn <= NL_CAP && count >= 0 && displ >= 0 && displ + count <= N, KMCF_ERR_ARG, "%s: bad sizes", what);
     KMCF_TRY(kmcf_enter(c));
     host_cells hc;
-    const double lattice[3] = {1, 1, 1};
-    KMCF_TRY(build_cells(d_x, d_y, d_z, N, lattice, 0, nn_dist, &hc));
+    const double open_lattice[3] = {1, 1, 1};
+    const double *lattice = pbc ? h_lattice : open_lattice;
+    KMCF_TRY(build_cells(d_x, d_y, d_z, N, lattice, pbc, nn_dist, &hc));
     {
-        const int rcv = coords_seen_by_kernels(hc, d_x, d_y, d_z, N, kmcf_setup_stream(c), "kmcf_neighbor_list");
+        const int rcv = coords_seen_by_kernels(hc, d_x, d_y, d_z, N, kmcf_setup_stream(c), what);
         if (rcv != KMCF_OK) { hc.release(); return rcv; }
     }
     int *d_over = nullptr;
@@ -865,8 +900,13 @@ extern "C" int kmcf_neighbor_list(kmcf_comm *c, const double *d_x, const double 
     hipStream_t ss = kmcf_setup_stream(c);                       // (the caller's stream: see kmcf_internal.hpp)
     KMCF_HIP(hipMemsetAsync(d_over, 0, sizeof(int), ss));
     if (count > 0) {
-        neighbor_list_kernel<<<kmcf_grid1d(count, 1 << 20), KMCF_BLOCK, 0, ss>>>(
-            hc.g, hc.d_cell_start, hc.d_cell_items, d_x, d_y, d_z, nn_dist, N, nn, count, displ, d_neigh_idx, d_over);
+        if (pbc)
+            neighbor_list_pbc_kernel<<<kmcf_grid1d(count, 1 << 20), KMCF_BLOCK, 0, ss>>>(
+                hc.g, hc.usable ? 1 : 0, hc.d_cell_start, hc.d_cell_items, d_x, d_y, d_z, nn_dist, lattice[1], lattice[2], N, nn,
+                count, displ, d_neigh_idx, d_over);
+        else
+            neighbor_list_kernel<<<kmcf_grid1d(count, 1 << 20), KMCF_BLOCK, 0, ss>>>(
+                hc.g, hc.d_cell_start, hc.d_cell_items, d_x, d_y, d_z, nn_dist, N, nn, count, displ, d_neigh_idx, d_over);
         KMCF_HIP(hipGetLastError());
     }
     int over = 0;
@@ -874,6 +914,28 @@ extern "C" int kmcf_neighbor_list(kmcf_comm *c, const double *d_x, const double 
     KMCF_HIP(hipStreamSynchronize(ss));
     hipFree(d_over);
     hc.release();
-    KMCF_CHECK(!over, KMCF_ERR_ARG, "kmcf_neighbor_list: a site has more than %d neighbours within nn_dist", NL_CAP);
+    KMCF_CHECK(!over, KMCF_ERR_ARG, "%s: a site has more than %d neighbours within nn_dist", what, NL_CAP);
     return KMCF_OK;
+}
+
+extern "C" int kmcf_neighbor_list(kmcf_comm *c, const double *d_x, const double *d_y, const double *d_z, int N,
+                                  double nn_dist, int nn, int count, int displ, int *d_neigh_idx)
+{
+    return neighbor_list_impl("kmcf_neighbor_list", c, d_x, d_y, d_z, N, nullptr, 0, nn_dist, nn, count, displ, d_neigh_idx);
+}
+
+extern "C" int kmcf_neighbor_list_pbc(kmcf_comm *c, const double *d_x, const double *d_y, const double *d_z, int N,
+                                      const double *h_lattice, int pbc, double nn_dist, int nn, int count, int displ,
+                                      int *d_neigh_idx)
+{
+    const char *what = "kmcf_neighbor_list_pbc";
+    KMCF_CHECK(pbc == 0 || pbc == 1, KMCF_ERR_ARG, "%s: pbc = %d is neither 0 nor 1", what, pbc);
+    if (pbc) {
+        KMCF_CHECK(h_lattice, KMCF_ERR_ARG, "%s: h_lattice is NULL with pbc = 1", what);
+        KMCF_CHECK(std::isfinite(h_lattice[1]) && h_lattice[1] > 0, KMCF_ERR_ARG, "%s: the period in y, h_lattice[1] = %g, is not finite and > 0",
+                   what, h_lattice[1]);
+        KMCF_CHECK(std::isfinite(h_lattice[2]) && h_lattice[2] > 0, KMCF_ERR_ARG, "%s: the period in z, h_lattice[2] = %g, is not finite and > 0",
+                   what, h_lattice[2]);
+    }
+    return neighbor_list_impl(what, c, d_x, d_y, d_z, N, h_lattice, pbc, nn_dist, nn, count, displ, d_neigh_idx);
 }

@@ -13,6 +13,8 @@
 // Result per site = sum over charged j != i with dist < cutoff of  q_j erfc(r/(sigma sqrt 2)) k q / r
 // (v_solve_gpu, src/gpu_solvers.h:321-329), the same set the reference's list yields as long as charged
 // sites are V / Od (update_charge only ever charges those, potential_solver_gpu.cu:27-60).
+// kmcf_compute_cutoff_list_pbc builds the same index over one period in y and z; pairwise_pbc_kernel then takes the
+// minimum image.
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -99,7 +101,159 @@ __global__ __launch_bounds__(KMCF_BLOCK) void pairwise_kernel(
     }
 }
 
+// The same sum on a periodic index (kmcf_cell_grid_pbc): the charged j != i whose minimum-image distance (y and z,
+// kmcf_min_image_dist) is below the cutoff.  Every cell is visited once: in y the distinct cells of {cy-1, cy, cy+1} mod
+// ncy (one for ncy == 1, two for ncy == 2, else three); in z the cells {cz-1, cz, cz+1} mod ncz as runs of the compacted
+// list -- the whole column when ncz <= 3, [cz-1, cz+1] inside, and [0, hi] + [lo, ncz-1] when cz sits on a face.  All
+// bounds depend on the site alone, so they are the same for its 16 lanes; only the walk over a run is per lane.  A pair
+// has ONE distance, the minimum image: where a period is shorter than two cutoffs no second image is added.
+__global__ __launch_bounds__(KMCF_BLOCK) void pairwise_pbc_kernel(
+    kmcf_cell_grid_pbc g, const int *__restrict__ cell_start, const int *__restrict__ flag_pos, const int *__restrict__ clist,
+    const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ z,
+    const int *__restrict__ charge, double sigma, double k, double cutoff, int count, int displ,
+    double *__restrict__ potential)
+{
+    constexpr int LPS = 16, SPB = KMCF_BLOCK / LPS;
+    const double q = 1.60217663e-19;            // gpu_solvers.h:323
+    const int lane = threadIdx.x % LPS;
+    const int groups = (count + SPB - 1) / SPB;
+    const int ny = min(g.ncy, 3);               // y cells a site visits
+    for (int grp = blockIdx.x; grp < groups; grp += gridDim.x) {
+        const int idx = grp * SPB + threadIdx.x / LPS;
+        const bool valid = idx < count;
+        const int i = displ + idx;
+        double acc = 0.0;
+        if (valid) {
+            const double xi = x[i], yi = y[i], zi = z[i];
+            const int cx = kmcf_cell_coord(xi, g.x0, g.inv_x, g.ncx), cy = kmcf_cell_coord(yi, g.y0, g.inv_y, g.ncy),
+                      cz = kmcf_cell_coord(zi, g.z0, g.inv_z, g.ncz);
+            // z runs [lo0, hi0] and, if n_runs == 2, [lo1, hi1]
+            int n_runs = 1, lo0 = cz - 1, hi0 = cz + 1, lo1 = 0, hi1 = -1;
+            if (g.ncz <= 3) { lo0 = 0; hi0 = g.ncz - 1; }
+            else if (cz == 0) { lo0 = 0; hi0 = 1; lo1 = hi1 = g.ncz - 1; n_runs = 2; }
+            else if (cz == g.ncz - 1) { lo0 = 0; hi0 = 0; lo1 = g.ncz - 2; hi1 = g.ncz - 1; n_runs = 2; }
+            const int ay0 = g.ncy == 1 ? cy : cy - 1 + g.ncy;
+            for (int ax = max(cx - 1, 0); ax <= min(cx + 1, g.ncx - 1); ++ax)
+                for (int sy = 0; sy < ny; ++sy) {
+                    const int col = (ax * g.ncy + (ay0 + sy) % g.ncy) * g.ncz;
+                    for (int run = 0; run < n_runs; ++run) {
+                        const int b = flag_pos[cell_start[col + (run ? lo1 : lo0)]];
+                        const int e = flag_pos[cell_start[col + (run ? hi1 : hi0) + 1]];
+                        for (int t = b + lane; t < e; t += LPS) {
+                            const int j = clist[t];
+                            if (j == i) continue;
+                            const double dist = kmcf_min_image_dist(xi, yi, zi, x[j], y[j], z[j], g.ly, g.lz);
+                            if (dist < cutoff) {
+                                const double r = 1e-10 * dist;
+                                acc += (double)charge[j] * erfc(r / (sigma * sqrt(2.0))) * k * q / r;
+                            }
+                        }
+                    }
+                }
+        }
+#pragma unroll
+        for (int off = LPS / 2; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
+        if (valid && lane == 0) potential[i] = acc;
+    }
+}
+
+// the sites in cell order and the buffers of the per-step compaction, from the host copy of the coordinates; coord(s)
+// is the cell id of site s
+template <class F>
+int index_cells(kmcf_pairwise *p, F cell_of_site)
+{
+    const int N = p->N;
+    std::vector<int> start((size_t)p->ncell + 1, 0), cid((size_t)N), order((size_t)N);
+    for (int s = 0; s < N; ++s) {
+        cid[s] = cell_of_site(s);
+        start[cid[s] + 1]++;
+    }
+    for (int cc = 0; cc < p->ncell; ++cc) start[cc + 1] += start[cc];
+    std::vector<int> fill(start.begin(), start.end() - 1);
+    for (int s = 0; s < N; ++s) order[fill[cid[s]]++] = s;
+    p->n_blocks = (N + KMCF_SCAN_TILE - 1) / KMCF_SCAN_TILE;
+    KMCF_TRY(kmcf_dev_alloc(&p->d_cell_order, (size_t)N, false));
+    KMCF_TRY(kmcf_dev_alloc(&p->d_cell_start, (size_t)p->ncell + 1, false));
+    KMCF_TRY(kmcf_dev_alloc(&p->d_flag_pos, (size_t)N + 1, false));
+    KMCF_TRY(kmcf_dev_alloc(&p->d_block_sum, (size_t)p->n_blocks + 1, false));
+    KMCF_TRY(kmcf_dev_alloc(&p->d_clist, (size_t)N, false));
+    KMCF_HIP(hipMemcpy(p->d_cell_order, order.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice));
+    KMCF_HIP(hipMemcpy(p->d_cell_start, start.data(), start.size() * sizeof(int), hipMemcpyHostToDevice));
+    return KMCF_OK;
+}
+
+void pairwise_release(kmcf_pairwise *p)
+{
+    kmcf_dev_free_all({p->d_cell_order, p->d_cell_start, p->d_flag_pos, p->d_block_sum, p->d_clist});
+    delete p;
+}
+
 }  // namespace
+
+extern "C" int kmcf_compute_cutoff_list_pbc(kmcf_comm *c, const double *d_x, const double *d_y, const double *d_z, int N,
+                                            double cutoff_radius, const double *h_lattice, int pbc, kmcf_pairwise **out)
+{
+    const char *what = "kmcf_compute_cutoff_list_pbc";
+    KMCF_CHECK(pbc == 0 || pbc == 1, KMCF_ERR_ARG, "%s: pbc = %d is neither 0 nor 1", what, pbc);
+    if (pbc == 0) {                                 // today's index, whatever the lattice says
+        KMCF_TRY(kmcf_compute_cutoff_list(c, d_x, d_y, d_z, N, cutoff_radius, out));
+        if (h_lattice) std::copy(h_lattice, h_lattice + 3, (*out)->lattice);
+        return KMCF_OK;
+    }
+    KMCF_CHECK(c && d_x && d_y && d_z && out && N > 0 && cutoff_radius > 0, KMCF_ERR_ARG, "%s: bad argument", what);
+    KMCF_CHECK(h_lattice, KMCF_ERR_ARG, "%s: h_lattice is NULL with pbc = 1", what);
+    const double Ly = h_lattice[1], Lz = h_lattice[2];
+    KMCF_CHECK(std::isfinite(Ly) && Ly > 0, KMCF_ERR_ARG, "%s: the period in y, h_lattice[1] = %g, is not finite and > 0", what, Ly);
+    KMCF_CHECK(std::isfinite(Lz) && Lz > 0, KMCF_ERR_ARG, "%s: the period in z, h_lattice[2] = %g, is not finite and > 0", what, Lz);
+    KMCF_CHECK(c->device >= 0, KMCF_ERR_STATE, "%s: host-only communicator", what);
+    KMCF_TRY(kmcf_enter(c));
+    std::vector<double> x(N), y(N), z(N);
+    KMCF_HIP(hipMemcpy(x.data(), d_x, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
+    KMCF_HIP(hipMemcpy(y.data(), d_y, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
+    KMCF_HIP(hipMemcpy(z.data(), d_z, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
+    double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
+    for (int s = 0; s < N; ++s) {
+        lo[0] = std::min(lo[0], x[s]); hi[0] = std::max(hi[0], x[s]);
+        lo[1] = std::min(lo[1], y[s]); hi[1] = std::max(hi[1], y[s]);
+        lo[2] = std::min(lo[2], z[s]); hi[2] = std::max(hi[2], z[s]);
+    }
+    // the cells tile [min, min + L): a site at min + L or beyond has no cell of its own
+    KMCF_CHECK(hi[1] - lo[1] < Ly, KMCF_ERR_ARG, "%s: the sites span %.17g in y, a whole period (%.17g) or more: wrap them into one cell first",
+               what, hi[1] - lo[1], Ly);
+    KMCF_CHECK(hi[2] - lo[2] < Lz, KMCF_ERR_ARG, "%s: the sites span %.17g in z, a whole period (%.17g) or more: wrap them into one cell first",
+               what, hi[2] - lo[2], Lz);
+    kmcf_pairwise *p = new kmcf_pairwise();
+    p->comm = c; p->N = N; p->cutoff = cutoff_radius; p->pbc = 1;
+    std::copy(h_lattice, h_lattice + 3, p->lattice);
+    p->x0 = lo[0]; p->y0 = lo[1]; p->z0 = lo[2]; p->inv = 1.0 / cutoff_radius;
+    p->ncx = (int)std::floor((hi[0] - lo[0]) * p->inv) + 1;
+    const double ny = std::floor(Ly / cutoff_radius), nz = std::floor(Lz / cutoff_radius);
+    const double ncell = (double)p->ncx * std::max(ny, 1.0) * std::max(nz, 1.0);
+    if (!(ncell < (double)(1 << 30))) {
+        delete p;
+        kmcf_set_error("%s: cell grid too large (%g cells)", what, ncell);
+        return KMCF_ERR_ARG;
+    }
+    p->ncy = std::max(1, (int)ny); p->ncz = std::max(1, (int)nz);
+    p->inv_y = p->ncy / Ly; p->inv_z = p->ncz / Lz;
+    p->ncell = p->ncx * p->ncy * p->ncz;
+    const int rc = index_cells(p, [&](int s) {
+        return (kmcf_cell_coord(x[s], p->x0, p->inv, p->ncx) * p->ncy + kmcf_cell_coord(y[s], p->y0, p->inv_y, p->ncy)) * p->ncz +
+               kmcf_cell_coord(z[s], p->z0, p->inv_z, p->ncz);
+    });
+    if (rc != KMCF_OK) { pairwise_release(p); return rc; }
+    *out = p;
+    return KMCF_OK;
+}
+
+extern "C" int kmcf_pairwise_periodic(const kmcf_pairwise *p, int *pbc, double *h_lattice)
+{
+    KMCF_CHECK(p, KMCF_ERR_ARG, "kmcf_pairwise_periodic: p is NULL");
+    KMCF_CHECK(pbc, KMCF_ERR_ARG, "kmcf_pairwise_periodic: pbc is NULL");
+    *pbc = p->pbc;
+    if (h_lattice) std::copy(p->lattice, p->lattice + 3, h_lattice);
+    return KMCF_OK;
+}
 
 extern "C" int kmcf_compute_cutoff_list(kmcf_comm *c, const double *d_x, const double *d_y, const double *d_z, int N,
                                         double cutoff_radius, kmcf_pairwise **out)
@@ -124,23 +278,11 @@ extern "C" int kmcf_compute_cutoff_list(kmcf_comm *c, const double *d_x, const d
     p->ncy = (int)std::floor((hi[1] - lo[1]) * p->inv) + 1;
     p->ncz = (int)std::floor((hi[2] - lo[2]) * p->inv) + 1;
     p->ncell = p->ncx * p->ncy * p->ncz;
-    std::vector<int> start((size_t)p->ncell + 1, 0), cid((size_t)N), order((size_t)N);
-    for (int s = 0; s < N; ++s) {
-        cid[s] = (kmcf_cell_coord(x[s], p->x0, p->inv, p->ncx) * p->ncy + kmcf_cell_coord(y[s], p->y0, p->inv, p->ncy)) * p->ncz +
-                 kmcf_cell_coord(z[s], p->z0, p->inv, p->ncz);
-        start[cid[s] + 1]++;
-    }
-    for (int cc = 0; cc < p->ncell; ++cc) start[cc + 1] += start[cc];
-    std::vector<int> fill(start.begin(), start.end() - 1);
-    for (int s = 0; s < N; ++s) order[fill[cid[s]]++] = s;
-    p->n_blocks = (N + KMCF_SCAN_TILE - 1) / KMCF_SCAN_TILE;
-    KMCF_TRY(kmcf_dev_alloc(&p->d_cell_order, (size_t)N, false));
-    KMCF_TRY(kmcf_dev_alloc(&p->d_cell_start, (size_t)p->ncell + 1, false));
-    KMCF_TRY(kmcf_dev_alloc(&p->d_flag_pos, (size_t)N + 1, false));
-    KMCF_TRY(kmcf_dev_alloc(&p->d_block_sum, (size_t)p->n_blocks + 1, false));
-    KMCF_TRY(kmcf_dev_alloc(&p->d_clist, (size_t)N, false));
-    KMCF_HIP(hipMemcpy(p->d_cell_order, order.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice));
-    KMCF_HIP(hipMemcpy(p->d_cell_start, start.data(), start.size() * sizeof(int), hipMemcpyHostToDevice));
+    const int rc = index_cells(p, [&](int s) {
+        return (kmcf_cell_coord(x[s], p->x0, p->inv, p->ncx) * p->ncy + kmcf_cell_coord(y[s], p->y0, p->inv, p->ncy)) * p->ncz +
+               kmcf_cell_coord(z[s], p->z0, p->inv, p->ncz);
+    });
+    if (rc != KMCF_OK) { pairwise_release(p); return rc; }
     *out = p;
     return KMCF_OK;
 }
@@ -174,9 +316,14 @@ extern "C" int kmcf_poisson_gridless(kmcf_pairwise *p, const double *d_x, const 
     if (count > 0) {
         int64_t grid = ((int64_t)count * 16 + KMCF_BLOCK - 1) / KMCF_BLOCK;
         if (grid > 8192) grid = 8192;
-        pairwise_kernel<<<(int)grid, KMCF_BLOCK, 0, st>>>(p->grid(), p->d_cell_start, p->d_flag_pos, p->d_clist, d_x, d_y, d_z,
-                                                         d_site_charge, sigma, k, p->cutoff, count, displ,
-                                                         d_site_potential_charge);
+        if (p->pbc)
+            pairwise_pbc_kernel<<<(int)grid, KMCF_BLOCK, 0, st>>>(p->grid_pbc(), p->d_cell_start, p->d_flag_pos, p->d_clist, d_x, d_y,
+                                                                 d_z, d_site_charge, sigma, k, p->cutoff, count, displ,
+                                                                 d_site_potential_charge);
+        else
+            pairwise_kernel<<<(int)grid, KMCF_BLOCK, 0, st>>>(p->grid(), p->d_cell_start, p->d_flag_pos, p->d_clist, d_x, d_y, d_z,
+                                                             d_site_charge, sigma, k, p->cutoff, count, displ,
+                                                             d_site_potential_charge);
         KMCF_HIP(hipGetLastError());
     }
     KMCF_HIP(hipStreamSynchronize(st));

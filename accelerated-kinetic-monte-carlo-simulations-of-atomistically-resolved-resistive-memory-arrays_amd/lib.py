@@ -169,6 +169,8 @@ SIGNATURES = {
     "kmcf_update_CB_edge_sparse": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int,
                                              C.c_double, C.c_double, C.c_double, C.POINTER(SolveStats)]),
     "kmcf_compute_cutoff_list": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_double, C.POINTER(_P)]),
+    "kmcf_compute_cutoff_list_pbc": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_double, _DP, C.c_int, C.POINTER(_P)]),
+    "kmcf_pairwise_periodic": (C.c_int, [_P, _IP, _DP]),
     "kmcf_pairwise_destroy": (C.c_int, [_P]),
     "kmcf_poisson_gridless": (C.c_int, [_P, _P, _P, _P, _P, C.c_double, C.c_double, C.c_int, C.c_int, _P]),
     "kmcf_initialize_sparsity_T": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _IP, _IP,
@@ -195,6 +197,7 @@ SIGNATURES = {
                                         C.c_double, _P, _P, _P, _P, _P, _P, C.c_int, _DP, _DP, _DP, _DP, _P, _P,
                                         C.c_int, _DP, _IP, _IP]),
     "kmcf_events_reset": (C.c_int, [_P]),
+    "kmcf_events_set_lattice": (C.c_int, [_P, _DP, C.c_int]),
     "kmcf_execute_kmc_step_thermal": (C.c_int, [_P, C.c_int, _IP, _IP, C.c_int, _P, _P, C.c_double, C.c_double,
                                                 C.c_double, C.c_double, _P, _P, _P, _P, _P, _P, C.c_int, _DP, _DP, _DP,
                                                 _DP, _P, _P, C.c_int, _DP, _IP, _IP, _P, C.c_int]),
@@ -207,6 +210,7 @@ SIGNATURES = {
     "kmcf_filament_gap": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P,
                                     C.c_int, C.POINTER(Gap), C.c_int, C.c_double, C.c_double, _IP, _P, C.POINTER(GapStats)]),
     "kmcf_neighbor_list":(C.c_int, [_P, _P, _P, _P, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _P]),
+    "kmcf_neighbor_list_pbc": (C.c_int, [_P, _P, _P, _P, C.c_int, _DP, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _P]),
 }
 
 _lib = None

@@ -206,13 +206,20 @@ class GPUBuffers:
 # gpu_solvers.h surface
 # --------------------------------------------------------------------------
 
-def compute_neighbor_list(kmc_comm, gpubuf, nn_dist=3.5, max_num_neighbors=52):
-    """compute_neighbor_list (gpu_solvers.h:43; src/neighbor_lists_gpu.cu:252-292)."""
+def compute_neighbor_list(kmc_comm, gpubuf, nn_dist=3.5, max_num_neighbors=52, pbc=0):
+    """compute_neighbor_list (gpu_solvers.h:43; src/neighbor_lists_gpu.cu:252-292).  pbc = 1: the minimum image in y and z
+    with the periods of gpubuf.lattice_host (kmcf_neighbor_list_pbc); the default is kmcf_neighbor_list."""
     lib = _L.load()
     count = int(kmc_comm.counts_events[kmc_comm.rank_events])
     displ = int(kmc_comm.displs_events[kmc_comm.rank_events])
     gpubuf.neigh_idx = torch.empty(max(count, 1) * max_num_neighbors, dtype=torch.int32, device=gpubuf.device)
     gpubuf.nn_ = max_num_neighbors
+    if pbc:
+        lat, latp = _da(gpubuf.lattice_host)
+        _L.check(lib.kmcf_neighbor_list_pbc(kmc_comm.handle, _ptr(gpubuf.site_x), _ptr(gpubuf.site_y), _ptr(gpubuf.site_z),
+                                            gpubuf.N_, latp, int(pbc), float(nn_dist), max_num_neighbors, count, displ,
+                                            _ptr(gpubuf.neigh_idx)), "kmcf_neighbor_list_pbc")
+        return
     _L.check(lib.kmcf_neighbor_list(kmc_comm.handle, _ptr(gpubuf.site_x), _ptr(gpubuf.site_y), _ptr(gpubuf.site_z),
                                     gpubuf.N_, float(nn_dist), max_num_neighbors, count, displ,
                                     _ptr(gpubuf.neigh_idx)), "kmcf_neighbor_list")
@@ -434,11 +441,20 @@ def sum_and_gather_potential(gpubuf, num_atoms_first_layer, kmc_comm):
                                                int(num_atoms_first_layer), cp, dp), "kmcf_sum_and_gather_potential")
 
 
-def compute_cutoff_list(kmc_comm, gpubuf, cutoff_radius=20.0):
+def compute_cutoff_list(kmc_comm, gpubuf, cutoff_radius=20.0, pbc=0):
     """compute_cutoff_list (gpu_solvers.h:46; src/neighbor_lists_gpu.cu:293-372).  gpubuf.cutoff_idx becomes
-    the opaque spatial index that replaces the reference's N x N_cutoff index list."""
+    the opaque spatial index that replaces the reference's N x N_cutoff index list.  pbc = 1: a periodic index with the
+    periods of gpubuf.lattice_host (kmcf_compute_cutoff_list_pbc), on which poisson_gridless_gpu takes the minimum image;
+    the default is kmcf_compute_cutoff_list."""
     lib = _L.load()
     h = C.c_void_p()
+    if pbc:
+        lat, latp = _da(gpubuf.lattice_host)
+        _L.check(lib.kmcf_compute_cutoff_list_pbc(kmc_comm.handle, _ptr(gpubuf.site_x), _ptr(gpubuf.site_y), _ptr(gpubuf.site_z),
+                                                  gpubuf.N_, float(cutoff_radius), latp, int(pbc), C.byref(h)),
+                 "kmcf_compute_cutoff_list_pbc")
+        gpubuf.cutoff_idx = h
+        return
     _L.check(lib.kmcf_compute_cutoff_list(kmc_comm.handle, _ptr(gpubuf.site_x), _ptr(gpubuf.site_y),
                                           _ptr(gpubuf.site_z), gpubuf.N_, float(cutoff_radius), C.byref(h)),
              "kmcf_compute_cutoff_list")
@@ -589,6 +605,16 @@ def events_reset(kmc_comm):
     """kmcf_events_reset: drop the event step's workspace, the symmetry verdict of the neighbour list and a replicated
     group's gathered lists; the next step works them out again.  In a group: every rank, between the same two steps."""
     _L.check(_L.load().kmcf_events_reset(kmc_comm.handle), "kmcf_events_reset")
+
+
+def events_set_lattice(kmc_comm, lattice, pbc):
+    """kmcf_events_set_lattice: the pair distance of the event rates on this communicator from now on -- pbc = 1: minimum
+    image in y and z with the periods lattice[1], lattice[2]; pbc = 0 (lattice may be None): the open-boundary default.
+    events_reset does not clear it.  In a group: every rank alike."""
+    latp = None
+    if lattice is not None:
+        lat, latp = _da(lattice)
+    _L.check(_L.load().kmcf_events_set_lattice(kmc_comm.handle, latp, int(pbc)), "kmcf_events_set_lattice")
 
 
 def event_rates(kmc_comm, N, count, displs, nn, neigh_idx, site_layer, T_bg, freq, sigma, k, posx, posy, posz,

@@ -105,6 +105,80 @@ def load_device_5nm(state="init"):
                 T_bg=float(g["background_temp"]), name="5nm_device")
 
 
+def c_round(f):
+    """round() of C, half away from zero (np.round rounds half to even)"""
+    f = np.asarray(f, np.float64)
+    r = np.trunc(f)
+    return r + np.where(np.abs(f - r) >= 0.5, np.sign(f), 0.0)
+
+
+def min_image_dist(a, b, lattice):
+    """The library's periodic distance (include/kmcfield.h, kmcf_compute_cutoff_list_pbc), operation for operation: x is
+    never periodic, y and z take the minimum image with the periods lattice[1], lattice[2]."""
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    dx = a[..., 0] - b[..., 0]
+    fy = (a[..., 1] - b[..., 1]) / lattice[1]
+    fy = fy - c_round(fy)
+    fz = (a[..., 2] - b[..., 2]) / lattice[2]
+    fz = fz - c_round(fz)
+    dy, dz = fy * lattice[1], fz * lattice[2]
+    return np.sqrt(dx * dx + dy * dy + dz * dz)
+
+
+def min_image_pairs(xyz, lattice, reach):
+    """(i, j, dist), i < j, of every pair of sites closer than `reach` under min_image_dist.  A wrapped cell list in numpy:
+    at least 3 cells of edge >= reach tile each period, so every pair is met once."""
+    xyz = np.asarray(xyz, np.float64)
+    N = len(xyz)
+    lo = xyz.min(0)
+    ny, nz = int(lattice[1] // reach), int(lattice[2] // reach)
+    assert ny >= 3 and nz >= 3 and np.all(xyz.max(0)[1:] - lo[1:] < np.asarray(lattice)[1:])
+    cx = np.floor((xyz[:, 0] - lo[0]) / reach).astype(np.int64)
+    cy = np.minimum(np.floor((xyz[:, 1] - lo[1]) * (ny / lattice[1])).astype(np.int64), ny - 1)
+    cz = np.minimum(np.floor((xyz[:, 2] - lo[2]) * (nz / lattice[2])).astype(np.int64), nz - 1)
+    nx = int(cx.max()) + 1
+    cid = (cx * ny + cy) * nz + cz
+    order = np.argsort(cid, kind="stable")
+    scid = cid[order]
+    out = []
+    for sx in (-1, 0, 1):
+        ax = cx + sx
+        ok = (ax >= 0) & (ax < nx)
+        for sy in (-1, 0, 1):
+            for sz in (-1, 0, 1):
+                tid = (ax * ny + (cy + sy) % ny) * nz + (cz + sz) % nz
+                b = np.searchsorted(scid, tid, "left")
+                cnt = np.where(ok, np.searchsorted(scid, tid, "right") - b, 0)
+                i = np.repeat(np.arange(N), cnt)
+                j = order[np.repeat(b, cnt) + np.arange(int(cnt.sum())) - np.repeat(np.cumsum(cnt) - cnt, cnt)]
+                keep = i < j
+                i, j = i[keep], j[keep]
+                dist = min_image_dist(xyz[i], xyz[j], lattice)
+                keep = dist < reach
+                out.append((i[keep], j[keep], dist[keep]))
+    i, j, dist = (np.concatenate(c) for c in zip(*out))
+    order = np.lexsort((j, i))
+    return i[order], j[order], dist[order]
+
+
+def periodic_5nm(state="init"):
+    """The 5 nm example as the periodic cell it is (pbc = 1 in y and z).  Under the minimum image 13 of its 37 650 sites
+    duplicate another site: the file holds both faces of the cell.  Of every pair of sites closer than 0.5 A the one with
+    the larger id is dropped; all 13 lie in the interface, the contacts are untouched.  dict as load_device_5nm, with
+    pbc = 1, the 37 637 remaining sites and `dropped`, the ids taken out; the potential snapshot is cut alike."""
+    d = load_device_5nm(state)
+    _, j, _ = min_image_pairs(d["xyz"], d["lattice"], 0.5)
+    dropped = np.unique(j)
+    NL = d["N_contact"]
+    assert len(dropped) and dropped.min() >= NL and dropped.max() < d["N"] - NL
+    keep = np.ones(d["N"], bool)
+    keep[dropped] = False
+    for key in ("xyz", "element", "element_snap6", "potential_snap6"):
+        d[key] = d[key][keep]
+    d.update(N=int(keep.sum()), pbc=1, dropped=dropped, name="5nm_device_periodic")
+    return d
+
+
 def _stripes(coord, length, n_lines, fill):
     """mask of `n_lines` equally spaced stripes covering the fraction `fill` of [0, length)."""
     period = length / n_lines

@@ -404,9 +404,31 @@ int kmcf_compute_cutoff_list(kmcf_comm *c, const double *d_x, const double *d_y,
                              double cutoff_radius, kmcf_pairwise **out);
 int kmcf_pairwise_destroy(kmcf_pairwise *p);
 
+/* Periodic boundaries in y and z (the simulator's `pbc` parameter).  ONE distance applies to everything periodic in
+ * this library -- the K pattern (kmcf_initialize_sparsity_K), kmcf_neighbor_list_pbc, the index below and the event
+ * step after kmcf_events_set_lattice -- the reference's four-argument site_dist (src/gpu_solvers.h:287-319):
+ *     dx = x1 - x2;   fy = (y1 - y2) / Ly;  fy -= round(fy);  dy = fy * Ly;   z like y;   dist = sqrt(dx*dx + dy*dy + dz*dz)
+ * with Ly = h_lattice[1], Lz = h_lattice[2] and round() the C round (half away from zero); x is never periodic.  Only
+ * the minimum image counts: where a period is shorter than two cutoffs, a second image inside the cutoff is NOT added.
+ * With pbc == 0 every function keeps the open-boundary expression (and result bytes) of its non-periodic entry point.
+ *
+ * kmcf_compute_cutoff_list_pbc: the spatial index with pbc and the periods remembered.  pbc == 0: exactly the index of
+ * kmcf_compute_cutoff_list (h_lattice may be NULL).  pbc == 1: x as before; in y the cells tile [min y, min y + Ly)
+ * exactly, max(1, floor(Ly / cutoff)) cells of width >= cutoff; z likewise.  kmcf_poisson_gridless on such an index sums
+ * over the charged j != i whose minimum-image distance is < cutoff (same term, no atomics, same bytes on every call).
+ * KMCF_ERR_ARG, kmcf_last_error naming the axis: pbc outside 0 / 1; with pbc == 1 a NULL h_lattice, a period that is
+ * not finite or <= 0 (both before anything needs a device), or sites that span a whole period (max - min >= L) on a
+ * periodic axis -- wrap them into one cell first. */
+int kmcf_compute_cutoff_list_pbc(kmcf_comm *c, const double *d_x, const double *d_y, const double *d_z, int N,
+                                 double cutoff_radius, const double *h_lattice /* 3, host */, int pbc, kmcf_pairwise **out);
+/* Inspection: *pbc and (h_lattice may be NULL) the three lattice values the index was built with (zeros if none). */
+int kmcf_pairwise_periodic(const kmcf_pairwise *p, int *pbc, double *h_lattice /* 3, may be NULL */);
+
 /* poisson_gridless_gpu (src/potential_solver_gpu.cu:1620-1655): for the sites
  * [displ, displ+count): site_potential_charge[i] = sum over charged sites j != i within
- * the cutoff of q_j erfc(r/(sigma sqrt 2)) k q / r  (v_solve_gpu, src/gpu_solvers.h:321-329). */
+ * the cutoff of q_j erfc(r/(sigma sqrt 2)) k q / r  (v_solve_gpu, src/gpu_solvers.h:321-329).
+ * "Within the cutoff" is the open-boundary distance on an index of kmcf_compute_cutoff_list, the minimum-image
+ * distance on a periodic index of kmcf_compute_cutoff_list_pbc. */
 int kmcf_poisson_gridless(kmcf_pairwise *p, const double *d_x, const double *d_y, const double *d_z,
                           const int *d_site_charge, double sigma, double k, int count, int displ,
                           double *d_site_potential_charge);
@@ -453,6 +475,15 @@ int kmcf_execute_kmc_step(kmcf_comm *c, int N, const int *h_count, const int *h_
  * is given.  For callers that change a neighbour list in place or reuse its memory; in a group, every rank calls it
  * between the same two steps.  Costs one symmetry pass and the allocations on the next step, nothing per step. */
 int kmcf_events_reset(kmcf_comm *c);
+
+/* Geometry of the pair distance that enters self_int_V in the event rates, for every later kmcf_execute_kmc_step,
+ * kmcf_execute_kmc_step_thermal and kmcf_event_rates on this communicator.  pbc == 1: the minimum-image distance above
+ * with Ly = h_lattice[1], Lz = h_lattice[2] (copied; pass the list of kmcf_neighbor_list_pbc, whose wrap pairs are the
+ * ones this matters for).  pbc == 0 (the default of a new communicator; h_lattice may be NULL): the open-boundary
+ * distance -- the kernels, and the bytes, of a communicator that never called this.  Nothing else in the step changes.
+ * kmcf_events_reset does not clear the setting, kmcf_comm_destroy does.  In a group every rank sets it alike; this is
+ * NOT checked.  KMCF_ERR_ARG: NULL c, pbc outside 0 / 1, NULL h_lattice or a period not finite or <= 0 with pbc == 1. */
+int kmcf_events_set_lattice(kmcf_comm *c, const double *h_lattice /* 3, host; may be NULL with pbc == 0 */, int pbc);
 
 /* Rate modes of the thermal step.  EA: the activation energy kmcf_execute_kmc_step forms; s: the site whose
  * temperature counts -- j for generation, i for recombination, vacancy diffusion and ion diffusion. */
@@ -554,7 +585,9 @@ int kmcf_conductive_clusters(kmcf_comm *c, int N, int nn, const int *d_neigh_idx
  * cell_of_site); any other value: the site belongs to no cell and enters no pair.  d_site_cell NULL requires
  * n_cells == 1 and puts every site in cell 0.
  * Pair of cell c: (a, b) with a in A, b in B, both in cell c; a == b is allowed.  dx = x[a] - x[b], likewise dy, dz;
- * d2 = (dx*dx + dy*dy) + dz*dz, every operation rounded to double (no fused multiply-add); the distance is non-periodic.
+ * d2 = (dx*dx + dy*dy) + dz*dz, every operation rounded to double (no fused multiply-add); the distance is non-periodic, and the
+ * search refuses a periodic index (kmcf_compute_cutoff_list_pbc with pbc == 1) with KMCF_ERR_ARG: its pruning by the
+ * distances to the cell faces does not carry over to wrapped cells.  Build a non-periodic index for the gap.
  * A pair counts iff d2 <= r_max*r_max, that product formed in double.
  * Result per cell: the pair with the smallest d2; among equal d2 the smallest a, then the smallest b.  A site in both sets
  * gives gap2 = 0 through the pair (a, a).  gap2, the two sites, x_left / x_right and the counts are exact; gap =
@@ -775,6 +808,17 @@ int kmcf_update_temperature_local(kmcf_kstate *k, const int *d_site_element, con
  * instead of the O(N^2) scan.  d_neigh_idx: count*nn ints. */
 int kmcf_neighbor_list(kmcf_comm *c, const double *d_x, const double *d_y, const double *d_z, int N,
                        double nn_dist, int nn, int count, int displ, int *d_neigh_idx);
+
+/* The same list under periodic boundaries in y and z: pbc == 1 takes the minimum-image distance (see
+ * kmcf_compute_cutoff_list_pbc) with the periods h_lattice[1], h_lattice[2]; same output contract (ascending j, -1
+ * padded, rows truncated at nn, the error for a site with too many neighbours).  The wrapped cell grid of
+ * kmcf_initialize_sparsity_K; where fewer than 3 cells of nn_dist fit a period, or the sites span one, every pair is
+ * tested.  pbc == 0: the bytes of kmcf_neighbor_list (h_lattice may be NULL).  Everything that reads the list --
+ * kmcf_update_charge, the event step, kmcf_conductive_clusters, the heat pattern -- is periodic through it.
+ * KMCF_ERR_ARG: as kmcf_neighbor_list, and pbc outside 0 / 1, NULL h_lattice or a period not finite or <= 0 with pbc == 1. */
+int kmcf_neighbor_list_pbc(kmcf_comm *c, const double *d_x, const double *d_y, const double *d_z, int N,
+                           const double *h_lattice /* 3, host */, int pbc, double nn_dist, int nn, int count, int displ,
+                           int *d_neigh_idx);
 
 #ifdef __cplusplus
 }

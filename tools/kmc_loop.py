@@ -3,13 +3,15 @@
 boundary (K) solve, pairwise term, sum/gather, KMC events -- with the per-module wall times the reference
 prints into output<size>_<rank>.txt ("Z - calculation time - ...").
 
-    python tools/kmc_loop.py [--workload 5nm|40nm|conducting] [--steps 6] [--T 300] [--current] [--rate-mode bg|ekin|site]
+    python tools/kmc_loop.py [--workload 5nm|5nm-periodic|40nm|conducting] [--steps 6] [--T 300] [--current] [--rate-mode bg|ekin|site]
                              [--clusters] [--current-map] [--scheme all|half|third --select W,B] [--gap R]
 
 --current adds the electro-thermal stages after the potential and before the events: conduction-band edge, current
 solve with heating (site_power), local heat solve (site_temperature); --rate-mode ekin | site lets the event rates read
 that field (kmcf_execute_kmc_step_thermal).  Workload `conducting`: the 4 x 4 crossbar with a vacancy filament of
-tests/test_gpu_conducting.py, whose current is a property of the device.  --clusters runs the conductive cluster analysis
+tests/test_gpu_conducting.py, whose current is a property of the device.  Workload `5nm-periodic`: the 5 nm example as the
+periodic cell it is (structure.periodic_5nm, pbc = 1 in y and z): neighbour list, K pattern, the spatial index of the pairwise
+term and the pair distance of the event rates all take the minimum image; the step line is the one of `5nm`.  --clusters runs the conductive cluster analysis
 (kmcf_conductive_clusters) after the charge update of every step: whether a filament bridges the electrodes, without a
 current solve; the step line gains `clusters <ms> (<vacancy clusters> vac, largest <sites>, bridging <filaments>)`, the
 time in milliseconds of device time.  --current-map (with --current) runs the site-resolved current map (kmcf_current_map)
@@ -41,7 +43,7 @@ import kmcfield_amd as km  # noqa: E402
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", default="5nm", choices=["5nm", "40nm", "conducting"])
+    ap.add_argument("--workload", default="5nm", choices=["5nm", "5nm-periodic", "40nm", "conducting"])
     ap.add_argument("--steps", type=int, default=6)
     ap.add_argument("--T", type=float, default=300.0)
     ap.add_argument("--max-events", type=int, default=100000)
@@ -60,7 +62,10 @@ def main():
                     help="filament gap analysis after every charge update, searched up to R angstrom (<= 20): gap, pair and "
                          "counts per crossbar cell; with --clusters also the constriction of a bridging filament")
     a = ap.parse_args()
-    if a.scheme and a.workload == "5nm":
+    periodic = a.workload == "5nm-periodic"
+    if periodic and a.gap is not None:
+        ap.error("--gap: the gap search is non-periodic and refuses the periodic index of --workload 5nm-periodic")
+    if a.scheme and a.workload in ("5nm", "5nm-periodic"):
         ap.error("--scheme needs a crossbar with lines: --workload 40nm or conducting")
     if a.current_map and not a.current:
         ap.error("--current-map needs --current (the map reads the potentials of the current solve)")
@@ -71,6 +76,8 @@ def main():
     S = km.solvers
     if a.workload == "5nm":
         d = km.structure.load_device_5nm("init")
+    elif periodic:
+        d = km.structure.periodic_5nm("init")
     elif a.workload == "conducting":
         d = km.structure.synth_crossbar_40nm(tiles=4, filament=4.0)
     else:
@@ -81,12 +88,14 @@ def main():
     comm.connect()
     buf = S.GPUBuffers(N, d["element"], d["xyz"][:, 0], d["xyz"][:, 1], d["xyz"][:, 2], 52, d["sigma"], d["k"],
                        d["lattice"], d["metals"])
-    S.compute_neighbor_list(comm, buf, d["nn_dist"], 52)
-    S.compute_cutoff_list(comm, buf, 20.0)
+    pbc = 1 if periodic else 0                # (the other workloads keep the reference GPU path's open list and pairwise term)
+    S.compute_neighbor_list(comm, buf, d["nn_dist"], 52, pbc=pbc)
+    S.compute_cutoff_list(comm, buf, 20.0, pbc=pbc)
+    S.events_set_lattice(comm, d["lattice"], pbc)
     S.initialize_sparsity_K(buf, d["pbc"], d["nn_dist"], NL, comm)
     layers = km.structure.LAYERS
     xs = d["xyz"][:, 0]
-    if a.workload != "5nm":      # the synthetic crossbar shares the 5 nm stack along x
+    if a.workload not in ("5nm", "5nm-periodic"):      # the synthetic crossbar shares the 5 nm stack along x
         xs = np.clip(xs, layers[0]["start_x"], layers[-1]["end_x"])
     lay = torch.as_tensor(S.site_layers(xs, layers), device="cuda")
     rng = S.RandomNumberGenerator(km.structure.RND_SEED_KMC)
@@ -111,7 +120,7 @@ def main():
         buf.site_potential_boundary.copy_(torch.as_tensor(contacts))      # once: the solve reads the slots, never writes them
     gap_cells, n_gap_cells, gap_bins = None, 1, None
     if a.gap is not None:
-        if a.workload != "5nm":
+        if a.workload not in ("5nm", "5nm-periodic"):
             cells = km.structure.crossbar_lines(d)[2] if cell_of_site is None else cell_of_site
             gap_cells, n_gap_cells = torch.as_tensor(cells, device="cuda"), int(cells.max()) + 1
         if a.clusters:
