@@ -8,7 +8,11 @@ of magnitude ~30); SpMV |dy| <= 1e-12 sum|a||x|; I_macro 1e-9 relative; power 1e
 Split PCG: against the oracle adding in the DEVICE's order on the system as assembled on the device
 (oracle/kmcf_oracle_order.c: row-per-lane, boundary-row, long-row and tunnel-block kernels, rank-ordered sums):
 iteration count and potentials IDENTICAL; against the oracle's natural order: iterates at 5 iterations 1e-10, the
-converged solution's TRUE residual <= 3 x the oracle's own true residual."""
+converged solution's TRUE residual <= 3 x the oracle's own true residual.
+
+small_device(seed=7) has 208 atoms and 62 tunnel points: one 64-bit mask word, one tile, one strip.  The block sizes
+around the mask word and the tile, reverse bias and inputs ON the strict comparisons are in
+tests/test_gpu_tpath_synthetic.py, against the dense reference of tests/tpath_ref.py."""
 import threading
 
 import os
