@@ -14,8 +14,9 @@
 //    the consuming kernel (bitwise reproducible, no fp64 atomics).  With several
 //    ranks a 1-block finalize + ncclAllReduce on the compute stream sits in between.
 //
-// HBM traffic per iteration besides the SpMV: p update 3R+1W, x/r update 5R+2W
-// vector passes = 88 B/row (the reference's op sequence: 144 B/row).
+// Vector traffic per iteration besides the SpMV: p update 3R+1W, r update 3R+1W, and the x update (1R+1W and one more
+// read of p) once in KMCF_CG_XBATCH = B iterations: 80 - 8 (B-1)/B bytes per row (the reference's op sequence: 144 B/row,
+// SURVEY 8d).
 #include <chrono>
 #include <cmath>
 #include <cstring>
@@ -83,39 +84,75 @@ __global__ __launch_bounds__(KMCF_BLOCK) void cg_finalize_kernel(part_ref p0, in
     }
 }
 
-// Loop head of iteration k: stopping rule, beta, p = z + beta p   (:217-227) -- and the x += alpha p of iteration
-// k-1 (:243), which is applied HERE, where the old p is read anyway: the residual kernel does not touch x and p
+// The x += alpha p still pending, oldest first: x = ((x + a_0 p_0) + a_1 p_1) + ...  -- the operations and operands of
+// applying them one by one as they arose.  Runtime count; the cold paths (a loop that stops or ends on its limit).
+__device__ __forceinline__ void xring_apply2(double2 &xv, const kmcf_xring &h, const double (&a)[4], int pending, int i)
+{
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (j >= h.nb - pending && j < h.nb) {
+            const double2 pv = reinterpret_cast<const double2 *>(h.p[j])[i];
+            xv.x = xv.x + a[j] * pv.x;
+            xv.y = xv.y + a[j] * pv.y;
+        }
+}
+__device__ __forceinline__ void xring_apply1(double &xv, const kmcf_xring &h, const double (&a)[4], int pending, int i)
+{
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (j >= h.nb - pending && j < h.nb) xv = xv + a[j] * h.p[j][i];
+}
+__device__ __forceinline__ void xring_steps(const kmcf_xring &h, const kmcf_scalars *S, double (&a)[4])
+{
+#pragma unroll
+    for (int j = 0; j < 4; ++j) a[j] = j < h.nb ? S->xa_ring[h.slot[j]] : 0.0;
+}
+
+// Loop head of iteration k: stopping rule, beta, p = z + beta p   (:217-227) -- and the x += alpha p of the iterations
+// before (:243), which are applied HERE, where the old p is read anyway: the residual kernel does not touch x and p
 // (80 instead of 88 bytes per row and iteration; the same operation on the same operands, one kernel later).
-// An update still pending when the loop ends is applied by cg_x_kernel or by the caller's output kernel.
-template <bool PRECOND>
-__global__ __launch_bounds__(KMCF_BLOCK) void cg_p_kernel(int n, double *__restrict__ p, const double *__restrict__ r,
-                                                          const double *__restrict__ dinv, part_ref prz, part_ref pbb,
-                                                          kmcf_scalars *__restrict__ S, int k, int first,
-                                                          double tol2, int check_tol, double *__restrict__ x)
+// Nothing in an iteration reads x, so with KMCF_CG_XBATCH = B > 1 the direction is not overwritten in place: p_k goes to
+// slot k % B of a ring of B buffers (h: the ring from the slot written longest ago -- this launch's target -- to p_(k-1)),
+// up to B updates stay pending, and one launch in B applies them in order (NF = B: the flush instance; NF = 0 does not
+// touch x).  B = 1: every launch behind the first is the flush instance on one buffer, i.e. the kernel as it was.
+// The target of a flush launch IS the buffer of the oldest pending p -- every thread reads its element of it before it
+// writes it -- so the ring's pointers are not __restrict__.
+// Updates still pending when the loop ends are applied by cg_x_kernel or by the caller's output kernel.
+template <bool PRECOND, int NF>
+__global__ __launch_bounds__(KMCF_BLOCK) void cg_p_kernel(int n, kmcf_xring h, const double *p_prev, double *p_out,
+                                                          const double *__restrict__ r, const double *__restrict__ dinv,
+                                                          part_ref prz, part_ref pbb, kmcf_scalars *__restrict__ S, int k,
+                                                          int first, double tol2, int check_tol, double *__restrict__ x,
+                                                          int pending)
 {
     __shared__ double lds4[4];
     const int parity = k & 1;
     // Everything this block needs is requested before anything is waited for (scalars, the partial sums of the
-    // previous kernel, the block's first elements): a block lives for one or two elements per lane, so a chain of
-    // dependent loads in front of its stream would be most of its life.
+    // previous kernel, the block's first elements -- of every pending p in the flush instance): a block lives for one
+    // or two elements per lane, so a chain of dependent loads in front of its stream would be most of its life.
     const int n2 = n >> 1;
     const double2 *r2 = reinterpret_cast<const double2 *>(r), *d2 = reinterpret_cast<const double2 *>(dinv);
-    double2 *p2 = reinterpret_cast<double2 *>(p);
+    const double2 *q2 = reinterpret_cast<const double2 *>(p_prev);
+    double2 *p2 = reinterpret_cast<double2 *>(p_out);
     const int i0 = blockIdx.x * KMCF_BLOCK + threadIdx.x;
     // stopped by an EARLIER launch?  (S->done itself is written by block 0 of this very launch when the stopping rule
-    // fires: a block scheduled late would see it, return here and skip its share of the pending x update below)
+    // fires: a block scheduled late would see it, return here and skip its share of the pending x updates below)
     const int stop_k = S->stop_k;
     const bool done = stop_k != 0 && stop_k != k;
     const double rz_prev = S->rz[parity ^ 1], bb_saved = S->bb;
     double2 *x2 = reinterpret_cast<double2 *>(x);
-    const int pending = S->x_pending;
-    const double xa = S->xa;
+    double xa[NF > 0 ? NF : 1];
+#pragma unroll
+    for (int j = 0; j < NF; ++j) xa[j] = S->xa_ring[h.slot[j]];
     double2 z0 = make_double2(0.0, 0.0), dv0 = make_double2(1.0, 1.0), pv0 = make_double2(0.0, 0.0), xv0 = pv0;
+    double2 hv0[NF > 1 ? NF - 1 : 1];                  // the pending p older than p_(k-1), oldest first
     if (!first && i0 < n2) {
         z0 = r2[i0];
         if (PRECOND) dv0 = d2[i0];
-        pv0 = p2[i0];
-        if (pending) xv0 = x2[i0];
+#pragma unroll
+        for (int j = 0; j < NF - 1; ++j) hv0[j] = reinterpret_cast<const double2 *>(h.p[j])[i0];
+        pv0 = q2[i0];
+        if (NF > 0) xv0 = x2[i0];
     }
     const double rz_new = reduce_partials(prz, lds4);
     if (done) return;
@@ -135,17 +172,21 @@ __global__ __launch_bounds__(KMCF_BLOCK) void cg_p_kernel(int n, double *__restr
         else { S->stop_k = k; S->done = 1; }
     }
     if (!go) {
-        // the last iteration's x += alpha p, then nothing more (later kernels see S->done)
+        // the x += alpha p of the last iterations -- however many are pending, in order -- then nothing more (later
+        // kernels see S->done).  Cold: read from the ring, whatever this instance has requested above.
         if (pending) {
-            if (i0 < n2) { xv0.x = xv0.x + xa * pv0.x; xv0.y = xv0.y + xa * pv0.y; x2[i0] = xv0; }
-            for (int i = i0 + gridDim.x * KMCF_BLOCK; i < n2; i += gridDim.x * KMCF_BLOCK) {
+            double a[4];
+            xring_steps(h, S, a);
+            for (int i = i0; i < n2; i += gridDim.x * KMCF_BLOCK) {
                 double2 xv = x2[i];
-                const double2 pv = p2[i];
-                xv.x = xv.x + xa * pv.x;
-                xv.y = xv.y + xa * pv.y;
+                xring_apply2(xv, h, a, pending, i);
                 x2[i] = xv;
             }
-            if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) x[n - 1] = x[n - 1] + xa * p[n - 1];
+            if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+                double xv = x[n - 1];
+                xring_apply1(xv, h, a, pending, n - 1);
+                x[n - 1] = xv;
+            }
         }
         return;
     }
@@ -156,11 +197,17 @@ __global__ __launch_bounds__(KMCF_BLOCK) void cg_p_kernel(int n, double *__restr
             if (PRECOND) { const double2 dv = d2[i]; rv.x *= dv.x; rv.y *= dv.y; }
             p2[i] = rv;                                                    // :226 dcopy(z -> p)
         }
-        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) p[n - 1] = PRECOND ? r[n - 1] * dinv[n - 1] : r[n - 1];
+        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) p_out[n - 1] = PRECOND ? r[n - 1] * dinv[n - 1] : r[n - 1];
     } else {
         const double beta = rz_new / rz_prev;                              // :220
         if (i0 < n2) {                                                     // (the prefetched element)
-            if (pending) { xv0.x = xv0.x + xa * pv0.x; xv0.y = xv0.y + xa * pv0.y; x2[i0] = xv0; }   // :243 of k-1
+            if (NF > 0) {                                                  // :243 of k-NF .. k-1
+#pragma unroll
+                for (int j = 0; j < NF - 1; ++j) { xv0.x = xv0.x + xa[j] * hv0[j].x; xv0.y = xv0.y + xa[j] * hv0[j].y; }
+                xv0.x = xv0.x + xa[NF > 0 ? NF - 1 : 0] * pv0.x;
+                xv0.y = xv0.y + xa[NF > 0 ? NF - 1 : 0] * pv0.y;
+                x2[i0] = xv0;
+            }
             if (PRECOND) { z0.x *= dv0.x; z0.y *= dv0.y; }
             pv0.x = beta * pv0.x + z0.x;                                   // :221 dscal, :222 daxpy
             pv0.y = beta * pv0.y + z0.y;
@@ -169,11 +216,16 @@ __global__ __launch_bounds__(KMCF_BLOCK) void cg_p_kernel(int n, double *__restr
         for (int i = i0 + gridDim.x * KMCF_BLOCK; i < n2; i += gridDim.x * KMCF_BLOCK) {
             double2 z = r2[i];
             if (PRECOND) { const double2 dv = d2[i]; z.x *= dv.x; z.y *= dv.y; }
-            double2 pv = p2[i];
-            if (pending) {
+            double2 hv[NF > 1 ? NF - 1 : 1];
+#pragma unroll
+            for (int j = 0; j < NF - 1; ++j) hv[j] = reinterpret_cast<const double2 *>(h.p[j])[i];
+            double2 pv = q2[i];
+            if (NF > 0) {
                 double2 xv = x2[i];
-                xv.x = xv.x + xa * pv.x;
-                xv.y = xv.y + xa * pv.y;
+#pragma unroll
+                for (int j = 0; j < NF - 1; ++j) { xv.x = xv.x + xa[j] * hv[j].x; xv.y = xv.y + xa[j] * hv[j].y; }
+                xv.x = xv.x + xa[NF > 0 ? NF - 1 : 0] * pv.x;
+                xv.y = xv.y + xa[NF > 0 ? NF - 1 : 0] * pv.y;
                 x2[i] = xv;
             }
             pv.x = beta * pv.x + z.x;
@@ -182,8 +234,15 @@ __global__ __launch_bounds__(KMCF_BLOCK) void cg_p_kernel(int n, double *__restr
         }
         if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
             const double z = PRECOND ? r[n - 1] * dinv[n - 1] : r[n - 1];
-            if (pending) x[n - 1] = x[n - 1] + xa * p[n - 1];
-            p[n - 1] = beta * p[n - 1] + z;
+            const double pl = p_prev[n - 1];
+            if (NF > 0) {
+                double xv = x[n - 1];
+#pragma unroll
+                for (int j = 0; j < NF - 1; ++j) xv = xv + xa[j] * h.p[j][n - 1];
+                xv = xv + xa[NF > 0 ? NF - 1 : 0] * pl;
+                x[n - 1] = xv;
+            }
+            p_out[n - 1] = beta * pl + z;
         }
     }
 }
@@ -193,7 +252,7 @@ template <bool PRECOND>
 __global__ __launch_bounds__(KMCF_BLOCK) void cg_xr_kernel(int n, double *__restrict__ r, const double *__restrict__ Ap,
                                                            const double *__restrict__ dinv, part_ref ppap,
                                                            kmcf_scalars *__restrict__ S, int parity,
-                                                           double *__restrict__ part_rz)
+                                                           double *__restrict__ part_rz, int xa_slot, int pending_after)
 {
     __shared__ double lds4[4];
     // two elements per lane and step (16-byte loads and stores; the workspace vectors are 256-byte aligned);
@@ -244,17 +303,25 @@ __global__ __launch_bounds__(KMCF_BLOCK) void cg_xr_kernel(int n, double *__rest
     double t = kmcf_block_sum(rz, lds4);
     if (threadIdx.x == 0) {
         part_rz[blockIdx.x] = t;
-        if (blockIdx.x == 0) { S->pAp = pAp; S->xa = a; S->x_pending = 1; }
+        // (the step length goes into the ring slot of this iteration's p; pending_after: the host's count, one more
+        //  than the loop head of this iteration left)
+        if (blockIdx.x == 0) { S->pAp = pAp; S->xa = a; S->xa_ring[xa_slot] = a; S->x_pending = pending_after; }
     }
 }
 
-// The x += alpha p still pending when the loop ended on its iteration limit.
-__global__ __launch_bounds__(KMCF_BLOCK) void cg_x_kernel(int n, double *__restrict__ x, const double *__restrict__ p,
+// The x += alpha p still pending when the loop ended on its iteration limit, oldest first.
+__global__ __launch_bounds__(KMCF_BLOCK) void cg_x_kernel(int n, double *__restrict__ x, kmcf_xring h,
                                                           const kmcf_scalars *__restrict__ S)
 {
-    if (S->done || !S->x_pending) return;
-    const double a = S->xa;
-    for (int i = blockIdx.x * KMCF_BLOCK + threadIdx.x; i < n; i += gridDim.x * KMCF_BLOCK) x[i] = x[i] + a * p[i];
+    const int pending = S->x_pending;
+    if (S->done || !pending) return;
+    double a[4];
+    xring_steps(h, S, a);
+    for (int i = blockIdx.x * KMCF_BLOCK + threadIdx.x; i < n; i += gridDim.x * KMCF_BLOCK) {
+        double xv = x[i];
+        xring_apply1(xv, h, a, pending, i);
+        x[i] = xv;
+    }
 }
 
 // After the loop: the r.z the reference prints (:273) if the loop did not end on the stopping rule.
@@ -325,6 +392,31 @@ int pcg_collect(kmcf_matrix *m, double tol2, int absolute, kmcf_solve_stats_t *s
     return KMCF_OK;
 }
 
+// The ring as the loop head of iteration k sees it: slots k % B (written B iterations ago: the target) ... (k - 1) % B.
+kmcf_xring xring_at(double *const (&ring)[4], int B, int k)
+{
+    kmcf_xring h = {};
+    h.nb = B;
+    for (int i = 0; i < B; ++i) { h.p[i] = ring[(k + i) % B]; h.slot[i] = (k + i) % B; }
+    return h;
+}
+
+template <bool PRECOND>
+void cg_p_launch(int nf, int grid, hipStream_t st, int n, const kmcf_xring &h, const double *p_prev, double *p_out, const double *r,
+                 const double *dinv, const part_ref &prz, const part_ref &pbb, kmcf_scalars *S, int k, int first, double tol2,
+                 int check_tol, double *x, int pending)
+{
+#define KMCF_CG_P(NF) cg_p_kernel<PRECOND, NF><<<grid, KMCF_BLOCK, 0, st>>>(n, h, p_prev, p_out, r, dinv, prz, pbb, S, k, first, tol2, check_tol, x, pending)
+    switch (nf) {
+    case 0: KMCF_CG_P(0); break;
+    case 1: KMCF_CG_P(1); break;
+    case 2: KMCF_CG_P(2); break;
+    case 3: KMCF_CG_P(3); break;
+    default: KMCF_CG_P(4); break;
+    }
+#undef KMCF_CG_P
+}
+
 // flags: bit 0 = d_p already holds x0 (the fused input kernel wrote it), bit 1 = leave the final synchronisation and
 // the statistics to the caller (pcg_collect), who has more work to enqueue first
 template <bool PRECOND>
@@ -365,6 +457,27 @@ int pcg_loop(kmcf_matrix *m, double tol, int max_it, int fixed_iters, int absolu
     const bool direct = multi && c->nranks > 1 && kmcf_p2p_direct(m);
     const u64 halo0 = direct ? *kmcf_p2p_halo_seq(m, 0) : 0;
 
+    // The p ring (KMCF_CG_XBATCH = B; cg_p_kernel): slot 0 is d_p itself -- it holds x0 for the A x0 above -- and p_k
+    // lives in slot k % B.  One rank only: a group's halo lands behind d_p.  m->d_p follows the ring through the loop
+    // and is the original buffer again on every way out of it.
+    const int B = multi ? 1 : std::min(std::max(kmcf_opt_int(c, KNOB_CG_XBATCH, KMCF_CG_XBATCH_DEFAULT), 1), 4);
+    double *ring[4] = {m->d_p, nullptr, nullptr, nullptr};
+    for (int j = 1; j < B; ++j) {
+        if (!m->d_p_ring[j - 1]) {
+            const size_t len = (size_t)n + m->n_halo + 2;
+            KMCF_TRY(kmcf_dev_alloc(&m->d_p_ring[j - 1], len, false));
+            KMCF_HIP(hipMemsetAsync(m->d_p_ring[j - 1], 0, len * sizeof(double), st));
+        }
+        ring[j] = m->d_p_ring[j - 1];
+    }
+    struct p_restore {
+        kmcf_matrix *m;
+        double *p0;
+        ~p_restore() { m->d_p = p0; }
+    } restore{m, m->d_p};
+    int pending = 0;                               // x += alpha p not applied yet (the device's S->x_pending while it runs)
+    m->xring = xring_at(ring, B, 1);
+
     int launched = 0;
     bool done = false;
     // chunks of 2, 4, 8 ... KMCF_CHUNK_ITERS iterations: a warm-started solve (every KMC step but the first)
@@ -377,16 +490,22 @@ int pcg_loop(kmcf_matrix *m, double tol, int max_it, int fixed_iters, int absolu
         for (int i = 0; i < chunk; ++i) {
             const int k = launched + i + 1;  // reference's k
             const int parity = k & 1;
-            cg_p_kernel<PRECOND><<<vg, KMCF_BLOCK, 0, st>>>(n, m->d_p, m->d_r, m->d_dinv, prz, pbb, S, k,
-                                                            k == 1 ? 1 : 0, tol2, check_tol, m->d_x);
+            // loop head: all `pending` updates of x if the ring is full, none otherwise; p_k into slot k % B
+            const int nf = pending == B ? B : 0;
+            const kmcf_xring h = xring_at(ring, B, k);
+            cg_p_launch<PRECOND>(nf, vg, st, n, h, ring[(k - 1) % B], ring[k % B], m->d_r, m->d_dinv, prz, pbb, S, k, k == 1 ? 1 : 0, tol2,
+                                 check_tol, m->d_x, pending);
             KMCF_HIP(hipGetLastError());
+            if (nf) pending = 0;
+            m->d_p = ring[k % B];                  // (every SpMV path reads m->d_p when it launches)
             KMCF_TRY(kmcf_spmv_device(m, true, true));
             if (multi) {
                 cg_finalize_kernel<<<1, KMCF_BLOCK, 0, st>>>(ppap_loc, 2, pr_none(), -1, S, 1);
                 KMCF_HIP(hipGetLastError());
                 KMCF_TRY(kmcf_comm_allreduce_sum(c, &S->red[2], 1));
             }
-            cg_xr_kernel<PRECOND><<<vg, KMCF_BLOCK, 0, st>>>(n, m->d_r, m->d_Ap, m->d_dinv, ppap, S, parity, m->d_part_b);
+            ++pending;
+            cg_xr_kernel<PRECOND><<<vg, KMCF_BLOCK, 0, st>>>(n, m->d_r, m->d_Ap, m->d_dinv, ppap, S, parity, m->d_part_b, k % B, pending);
             KMCF_HIP(hipGetLastError());
             if (multi) {
                 cg_finalize_kernel<<<1, KMCF_BLOCK, 0, st>>>(prz_loc, 0, pr_none(), -1, S, 1);
@@ -397,6 +516,7 @@ int pcg_loop(kmcf_matrix *m, double tol, int max_it, int fixed_iters, int absolu
         launched += chunk;
         if (check_tol) KMCF_TRY(cg_chunk_check(c, S, st, &done));
     }
+    m->xring = xring_at(ring, B, launched + 1);    // the ring as the next loop head would see it: pending updates last
     if (direct) {       // one SpMV (put, consumption, acknowledgement) per iteration that went on
         const u64 executed = done ? (u64)c->h_pinned[1] : (u64)launched;
         *kmcf_p2p_halo_seq(m, 0) = *kmcf_p2p_halo_seq(m, 1) = halo0 + executed;
@@ -409,7 +529,7 @@ int pcg_loop(kmcf_matrix *m, double tol, int max_it, int fixed_iters, int absolu
             KMCF_HIP(hipGetLastError());
         }
         if (!(flags & 2)) {                        //  ... and applies the pending x update on its way)
-            cg_x_kernel<<<vg, KMCF_BLOCK, 0, st>>>(n, m->d_x, m->d_p, S);
+            cg_x_kernel<<<vg, KMCF_BLOCK, 0, st>>>(n, m->d_x, m->xring, S);
             KMCF_HIP(hipGetLastError());
         }
     }
@@ -1027,7 +1147,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void cg_in_kernel(int n, const int *__r
     }
 }
 __global__ __launch_bounds__(KMCF_BLOCK) void cg_out_kernel(int n, const int *__restrict__ perm, const double *__restrict__ r,
-                                                            const double *__restrict__ x, const double *__restrict__ p,
+                                                            const double *__restrict__ x, kmcf_xring ring,
                                                             double *__restrict__ r_u, double *__restrict__ x_u,
                                                             const kmcf_scalars *__restrict__ S, kmcf_scalars *__restrict__ host_S,
                                                             part_ref tail_rz)
@@ -1045,16 +1165,18 @@ __global__ __launch_bounds__(KMCF_BLOCK) void cg_out_kernel(int n, const int *__
             *host_S = h;
         }
     }
-    // a loop that ended on its iteration limit has left its last x += alpha p to this kernel (cg_p_kernel)
-    const bool pending = !S->done && S->x_pending;
-    const double a = S->xa;
+    // a loop that ended on its iteration limit has left its last x += alpha p to this kernel (cg_p_kernel): up to
+    // KMCF_CG_XBATCH of them, applied oldest first from the p ring
+    const int pending = S->done ? 0 : S->x_pending;
+    double a[4];
+    xring_steps(ring, S, a);
     int first, end, stride;
     xcd_range(n, first, end, stride);
     for (int i = first; i < end; i += stride) {
         const int s = perm ? perm[i] : i;
         r_u[s] = r[i];
         double xv = x[i];
-        if (pending) xv = xv + a * p[i];
+        if (pending) xring_apply1(xv, ring, a, pending, i);
         x_u[s] = xv;
     }
 }
@@ -1089,7 +1211,7 @@ extern "C" int kmcf_pcg_jacobi(kmcf_matrix *m, double *d_r, double *d_x, const d
     KMCF_TRY(pcg_workspace_flags(m, d_diag_inv != nullptr, relative_tolerance, max_iterations, fixed_iters, stats, 1 | 2));
     const double t_b = trace ? now() : 0.0;
     const bool tail_here = !(c->nranks > 1 || c->force_collectives) && !kmcf_cg_single_reduction(m) && n > 0 && !m->last_solve_resident;
-    cg_out_kernel<<<perm_grid(std::max(n, 1)), KMCF_BLOCK, 0, c->stream>>>(n, m->d_perm, m->d_r, m->d_x, m->d_p, d_r, d_x, m->d_S, c->h_scal,
+    cg_out_kernel<<<perm_grid(std::max(n, 1)), KMCF_BLOCK, 0, c->stream>>>(n, m->d_perm, m->d_r, m->d_x, m->xring, d_r, d_x, m->d_S, c->h_scal,
                                                                            tail_here ? pr1(m->d_part_b, kmcf_vec_grid(n)) : pr_none());
     KMCF_HIP(hipGetLastError());
     KMCF_HIP(hipEventRecord(c->ev_call1, c->stream));

@@ -627,6 +627,7 @@ __global__ __launch_bounds__(KMCF_BLOCK * TPB) void cgr_kernel(const cgr_args A)
         h.red[0] = h.red[1] = h.red[2] = h.red[3] = 0.0;
         h.alpha[0] = h.alpha[1] = a_old;
         h.done = done; h.iters = iters; h.x_pending = 0; h.stop_k = 0; h.xa = 0.0;
+        h.xa_ring[0] = h.xa_ring[1] = h.xa_ring[2] = h.xa_ring[3] = 0.0;
         *A.S = h;
         *A.seq = seq + 1;
     }

@@ -47,6 +47,7 @@ void kmcf_set_error(const char *fmt, ...);
 constexpr int KMCF_BLOCK = 256;          // 4 wavefronts
 constexpr int KMCF_MAX_PARTIALS = 2048;  // = 256 CUs x 8 resident blocks
 constexpr int KMCF_CHUNK_ITERS = 32;     // CG iterations enqueued between convergence read-backs
+constexpr int KMCF_CG_XBATCH_DEFAULT = 4; // classic kernel loop of one rank: iterations per x update (KMCF_CG_XBATCH)
 constexpr int KMCF_DICT_MAX = 62;        // value dictionary of the coded window SpMV (codes 0..61)
 constexpr int KMCF_CODE_DIAG = 63;       // code of a row's diagonal entry (value in d_diagv)
 constexpr int KMCF_SLOT_BITS = 10;       // window slots < 1024
@@ -63,10 +64,21 @@ struct kmcf_scalars {
     double alpha[2];  // single-reduction CG: step length ping-pong by iteration parity
     int done;         // stopping rule met
     int iters;        // iterations executed
-    int x_pending;    // classic loop: x += xa * p of the last iteration is still to be applied (cg_p / cg_x / cg_out)
+    int x_pending;    // classic loop: how many x += alpha p of the last iterations are still to be applied (cg_p / cg_x /
+                      // cg_out): 0 or 1 without batching, up to KMCF_CG_XBATCH with it
     int stop_k;       // iteration whose loop-head kernel set `done` (0: none).  That kernel's own blocks test THIS word,
                       // never `done`: block 0 writes `done` while other blocks of the same launch may not have started
-    double xa;        // ... its step length
+    double xa;        // ... the step length of the newest of them
+    double xa_ring[4]; // step length of iteration k in slot k % B (B = KMCF_CG_XBATCH), next to p_k in the p ring
+};
+
+// The p ring of the classic loop as one launch sees it (KMCF_CG_XBATCH = nb): the nb buffers from the one written longest
+// ago to the newest, and the xa_ring slot of the step length that goes with each.  The updates still pending are the
+// LAST x_pending entries, in the order they have to be applied in.
+struct kmcf_xring {
+    double *p[4];
+    int slot[4];
+    int nb;
 };
 
 struct kmcf_matrix;
@@ -320,6 +332,9 @@ struct kmcf_matrix {
     double *d_r = nullptr;
     double *d_x = nullptr;
     double *d_dinv = nullptr;
+    double *d_p_ring[3] = {nullptr, nullptr, nullptr};   // classic loop with KMCF_CG_XBATCH = B > 1: p_k lives in ring slot k % B, slot 0
+                                       // is d_p itself, slots 1 .. B-1 are these (sized and zeroed like d_p at the first batched solve)
+    kmcf_xring xring = {};             // the ring as the last classic loop left it (cg_x_kernel, cg_out_kernel)
     double *d_pd = nullptr;            // single-reduction CG: search direction p (d_p then carries z)
     double *d_s = nullptr;             // single-reduction CG: s = A p by recurrence
     double *d_part_a = nullptr;        // pAp partials: [0, MAXP) interior rows | [MAXP, 2 MAXP) boundary rows |

@@ -14,7 +14,7 @@ enum kmcf_knob_id {
     KNOB_BRICK, KNOB_SPMV_KIND, KNOB_SPMV_CODED, KNOB_SPMV_SELL, KNOB_SPMV_SELLV, KNOB_SPMV_SELL_ROWS,
     KNOB_SPMV_SELL_SORT, KNOB_SPMV_NT, KNOB_SELL_NT, KNOB_SELL_PACK, KNOB_LONG_ROW, KNOB_CB_SCALED, KNOB_SUB_DENSE, KNOB_SUB_STRIP,
     KNOB_EVENTS_PERSISTENT, KNOB_EVENTS_FULLSCAN, KNOB_EVENTS_PARTITIONED, KNOB_EV_TREL, KNOB_CG_VARIANT,
-    KNOB_CG_RESIDENT, KNOB_CGR_TPB, KNOB_CGR_G1, KNOB_CGR_DELAY, KNOB_CGR_RDELAY, KNOB_CGR_ADAPT, KNOB_CGR_TIMEOUT_MS,
+    KNOB_CG_XBATCH, KNOB_CG_RESIDENT, KNOB_CGR_TPB, KNOB_CGR_G1, KNOB_CGR_DELAY, KNOB_CGR_RDELAY, KNOB_CGR_ADAPT, KNOB_CGR_TIMEOUT_MS,
     KNOB_CGR_CLASSIC_TILES, KNOB_TRANSPORT, KNOB_P2P_WINDOW_MB, KNOB_P2P_TIMEOUT_MS, KNOB_P2P_DIRECT, KNOB_P2P_AR,
     KNOB_FORCE_COMM, KNOB_LOOPBACK_TIMEOUT_S, KNOB_DEVICE_SHARE, KNOB_ENTER_ALWAYS, KNOB_TRACE, KNOB_COUNT
 };
@@ -86,6 +86,8 @@ inline constexpr kmcf_knob_def kmcf_knobs[] = {
      KNOB_COMM, false, kv_int(1, 2048)},
     {KNOB_CG_VARIANT, "KMCF_CG_VARIANT", "classic on one rank, cg1r in a group", "classic / cg1r (any value starting with cg)", "CG recurrence",
      KNOB_COMM, true, kv_enum("classic|cg1r")},
+    {KNOB_CG_XBATCH, "KMCF_CG_XBATCH", "4", "1 / 2 / 3 / 4", "classic kernel loop of one rank: x += alpha p applied once in this many iterations, from a ring of p buffers",
+     KNOB_COMM, false, kv_enum("1|2|3|4")},
     {KNOB_CG_RESIDENT, "KMCF_CG_RESIDENT", "1", "0 / 1", "0: no register-resident launch",
      KNOB_COMM, true, kv_enum("0|1")},
     {KNOB_CGR_TPB, "KMCF_CGR_TPB", "smallest that fits", "1 / 2 / 4", "resident launch: tiles per block",

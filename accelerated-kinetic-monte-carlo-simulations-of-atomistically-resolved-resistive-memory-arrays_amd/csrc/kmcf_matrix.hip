@@ -459,6 +459,7 @@ extern "C" int kmcf_matrix_destroy(kmcf_matrix *m)
         kmcf_dev_free_all({m->d_row_ptr, m->d_col, m->d_val, m->d_boundary_rows, m->d_is_boundary, m->d_send_idx,
                            m->d_send_buf, m->d_halo_gid, m->d_p, m->d_Ap, m->d_r, m->d_x, m->d_dinv,
                            m->d_part_a, m->d_part_b, m->d_part_c, m->d_S, m->d_perm, m->d_pd, m->d_s,
+                           m->d_p_ring[0], m->d_p_ring[1], m->d_p_ring[2],
                            m->d_long_items, m->d_long_part, m->d_long_ctr, m->d_build_tab});
     }
     delete m;
