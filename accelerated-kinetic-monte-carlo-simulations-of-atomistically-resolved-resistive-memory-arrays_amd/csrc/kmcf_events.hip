@@ -3,15 +3,16 @@
 // (:128-207), zero_out_events_split (:237-256), read_out_event (:257-269), execute_event (:284-331).
 //
 // Reference per EVENT: thrust::inclusive_scan over all count*nn slots (16 B/slot read + 8 B/slot written),
-// a device upper_bound, a full zero-out pass, three host syncs.  Here the list keeps a two-level sum tree
-// (one sum per 2048-slot tile, one per group of 256 tiles), no scan array at all:
-//   per step : build kernel (type u8 + probability f64 per slot), tile sums, symmetry check of the lists
-//   per event: select = three block-wide searches (group sums, the <= 256 tile sums of one group, the <= 2048
-//              slots of one tile) -> execute -> zero the events touching the pair and refresh the affected
-//              tile and group sums.  One rank with symmetric neighbour lists: only the rows of i, j and of
-//              their listed neighbours are visited (<= 2 + 2 nn rows, <= 4 nn + 4 tiles), select + execute +
-//              zero-out are one launch, and the whole event needs ONE host sync; otherwise a full pass over
-//              this rank's slots (the reference's way).
+// a device upper_bound, a full zero-out pass, three host syncs.  Here the list keeps sum trees and no scan array.  Per
+// step (execute_kmc_step_impl): the build kernel (type u8 + probability f64 per slot), the sums of the 2048-slot tiles,
+// once per neighbour list the verdict on its symmetry; then the events on exactly one of three paths:
+//   step_persistent      the default (one rank holds all rows, symmetric lists, nn <= 63): ONE block runs a whole batch of
+//                        events (event_batch_kernel) on a sum tree aligned to rows; uniforms, log and state lie in pinned
+//                        host memory that the kernel reads and writes and the host polls: no copy, no synchronise per batch
+//   step_three_launches  such lists with nn > 63 or KMCF_EVENTS_PERSISTENT=0: per event select + execute + zero-out through
+//                        the lists of i and j, the affected tile sums, the affected group sums; one synchronise per batch
+//   step_fullscan        the rest (partitioned rank group, a list that is not symmetric, KMCF_EVENTS_FULLSCAN): the
+//                        reference's scheme, a full pass over this rank's slots and two all-gathers + host syncs per event
 // Same selection rule (first slot whose inclusive cumulative sum exceeds u * total), same event rules,
 // same loop (events are drawn until the LAST drawn residence time reaches 1/freq; that last draw is the
 // returned time).  Ranks own contiguous site ranges; the partial totals are all-gathered and the rank
@@ -34,21 +35,21 @@ struct kmcf_rng {
 
 // Workspace of kmcf_execute_kmc_step, owned by the communicator (kmcf_comm::ev_cache).
 struct kmcf_event_cache {
-    size_t M = 0;                       // event slots of this rank (count * nn)
-    int P = 0, nn = 0;
-    unsigned char *d_type = nullptr;
+    size_t M = 0;                       // the shape it was allocated for (ev_workspace): event slots of this rank (count * nn),
+    int P = 0, nn = 0;                  // ranks sharing the list, slots per row
+    unsigned char *d_type = nullptr;    // every path:
     double *d_prob = nullptr, *d_tsum = nullptr, *d_gsum = nullptr, *d_tot = nullptr;
     int *d_ij = nullptr, *d_aff = nullptr, *d_asym = nullptr;
     int *d_tbad = nullptr;              // thermal rate modes: one word per rank, the first site with an unusable temperature
-    double *d_u = nullptr, *d_totlog = nullptr;     // batch: uniforms in, totals out
+    double *d_u = nullptr, *d_totlog = nullptr;     // step_three_launches: a batch's uniforms in; totals, log and state out
     int *d_evlog = nullptr;
-    void *d_state = nullptr;
-    char *h_pin = nullptr;                          // persistent batches: state | event log | totals | uniforms, pinned, written / read by the kernel itself
-    int batch_number = 0;
-    // row-aligned sum tree of the persistent batch kernel: one sum per row (nn slots), per tile of EV_RT rows, per
-    // group of EV_GROUP tiles
+    void *d_state = nullptr;                        // event_batch_state
+    // step_persistent: the row-aligned sum tree (one sum per row of nn slots, per tile of EV_RT rows, per group of EV_GROUP
+    // tiles), the pinned ev_batch_host and the number of the batch enqueued last
     double *d_rsum = nullptr, *d_tsum2 = nullptr, *d_gsum2 = nullptr;
-    const int *sym_key = nullptr;       // neighbour list the symmetry verdict belongs to
+    void *h_pin = nullptr;
+    int batch_number = 0;
+    const int *sym_key = nullptr;       // neighbour list (and its N) the symmetry verdict belongs to
     int sym_N = 0;
     bool symmetric = false;
     // replicated step of a multi-rank group: the neighbour lists of ALL sites, gathered once
@@ -1068,59 +1069,36 @@ __global__ __launch_bounds__(KMCF_BLOCK) void check_symmetry_kernel(int N, int n
 }
 
 constexpr int EV_NO_BAD_SITE = 0x7f7f7f7f;                  // (what hipMemset 0x7f leaves: above every site id)
+constexpr int EV_BMAX3 = 128;                               // events per batch of the three-launch path
 
-// the one pass over the count * nn slots, in the instantiation of the rate mode
-void launch_build_event_list(int rate_mode, int grid, hipStream_t st, int N, int count, int start_i, int nn, const int *d_neigh_idx,
-                             const int *d_site_layer, double T_bg, double freq, double sigma, double k, const double *d_x,
-                             const double *d_y, const double *d_z, const double *d_pot, const int *d_site_element,
-                             const int *d_site_charge, const layer_energies &E, unsigned char *d_type, double *d_prob,
-                             const double *d_site_temperature, int *d_bad, const kmcf_comm *c)
-{
-    const thermal_field th = {d_site_temperature, d_bad};
-    if (c->ev_pbc) {                            // the periodic instantiations: nothing below changes
-        const ev_lattice L = {c->ev_ly, c->ev_lz};
-        if (rate_mode == KMCF_RATE_EKIN)
-            build_event_list_kernel<KMCF_RATE_EKIN><<<grid, KMCF_BLOCK, 0, st>>>(N, count, start_i, nn, d_neigh_idx, d_site_layer, T_bg,
-                                                                                 freq, sigma, k, d_x, d_y, d_z, d_pot, d_site_element,
-                                                                                 d_site_charge, E, d_type, d_prob, th, L);
-        else if (rate_mode == KMCF_RATE_T_SITE)
-            build_event_list_kernel<KMCF_RATE_T_SITE><<<grid, KMCF_BLOCK, 0, st>>>(N, count, start_i, nn, d_neigh_idx, d_site_layer, T_bg,
-                                                                                   freq, sigma, k, d_x, d_y, d_z, d_pot, d_site_element,
-                                                                                   d_site_charge, E, d_type, d_prob, th, L);
-        else
-            build_event_list_kernel<KMCF_RATE_T_BG><<<grid, KMCF_BLOCK, 0, st>>>(N, count, start_i, nn, d_neigh_idx, d_site_layer, T_bg,
-                                                                                 freq, sigma, k, d_x, d_y, d_z, d_pot, d_site_element,
-                                                                                 d_site_charge, E, d_type, d_prob, L);
-        return;
-    }
-    if (rate_mode == KMCF_RATE_EKIN)
-        build_event_list_kernel<KMCF_RATE_EKIN><<<grid, KMCF_BLOCK, 0, st>>>(N, count, start_i, nn, d_neigh_idx, d_site_layer, T_bg, freq,
-                                                                             sigma, k, d_x, d_y, d_z, d_pot, d_site_element,
-                                                                             d_site_charge, E, d_type, d_prob, th);
-    else if (rate_mode == KMCF_RATE_T_SITE)
-        build_event_list_kernel<KMCF_RATE_T_SITE><<<grid, KMCF_BLOCK, 0, st>>>(N, count, start_i, nn, d_neigh_idx, d_site_layer, T_bg, freq,
-                                                                               sigma, k, d_x, d_y, d_z, d_pot, d_site_element,
-                                                                               d_site_charge, E, d_type, d_prob, th);
-    else
-        build_event_list_kernel<KMCF_RATE_T_BG><<<grid, KMCF_BLOCK, 0, st>>>(N, count, start_i, nn, d_neigh_idx, d_site_layer, T_bg, freq,
-                                                                             sigma, k, d_x, d_y, d_z, d_pot, d_site_element,
-                                                                             d_site_charge, E, d_type, d_prob);
-}
+// Host side.  What an event list is built from: the arguments the three entry points share, filled once by each.
+struct ev_step_in {
+    int N, nn;
+    const int *d_neigh_idx, *d_site_layer;
+    double T_bg, freq, sigma, k;
+    const double *d_x, *d_y, *d_z, *d_pot;
+    const int *d_element, *d_charge;
+    const double *d_T; int rate_mode;   // site temperatures of the thermal rate modes (KMCF_RATE_T_BG: never read)
+    layer_energies E;                   // filled by check_step_args
+};
+struct ev_energies { int num_layers; const double *gen, *rec, *vdiff, *odiff; };    // ... as the entry points receive E
+// ... and what only a step has (the site arrays once more: the events change them)
+struct ev_step_io { int *d_element, *d_charge; double (*next_random)(void *); void *rng_user; int max_events, *h_event_log; };
 
-int build_grid(size_t M)
-{
-    int64_t g = ((int64_t)M + KMCF_BLOCK * 4 - 1) / (KMCF_BLOCK * 4);
-    return (int)std::min<int64_t>(g, 16384);
-}
-
-void fill_layer_energies(layer_energies &E, int num_layers, const double *h_E_gen, const double *h_E_rec, const double *h_E_Vdiff,
-                         const double *h_E_Odiff)
-{
-    for (int l = 0; l < MAX_LAYERS; ++l) {
-        E.gen[l] = l < num_layers ? h_E_gen[l] : 0.0; E.rec[l] = l < num_layers ? h_E_rec[l] : 0.0;
-        E.vdiff[l] = l < num_layers ? h_E_Vdiff[l] : 0.0; E.odiff[l] = l < num_layers ? h_E_Odiff[l] : 0.0;
-    }
-}
+// One call of the step as its paths see it.
+struct ev_step {
+    const char *what;                   // the entry point, for messages
+    kmcf_comm *c; kmcf_event_cache *w;  // ... and its workspace (ev_workspace)
+    ev_step_in in;                      // (d_neigh_idx: the gathered list in a replicated group)
+    ev_step_io io;
+    int P, rank, count, start_i;        // ranks that share the list (1: alone or replicated), this rank's rows
+    size_t M;                           // its slots, count * nn
+    int nb, ng;                         // tiles of EV_TILE slots, groups of EV_GROUP tiles
+    bool thermal, bad_read = false;     // thermal rate mode; the read of the ranks' bad-site words is enqueued (ev_read_bad)
+    std::vector<int> h_bad;
+    double t = 0.0;                     // residence time of the event executed last
+    int nev = 0, rc = KMCF_OK;          // events executed; the first failure: no path goes on after one
+};
 
 // what the thermal entry points check on top of the step's own checks; before anything that needs a device
 int check_thermal_args(const char *what, int rate_mode, const double *d_site_temperature, double T_bg)
@@ -1132,344 +1110,379 @@ int check_thermal_args(const char *what, int rate_mode, const double *d_site_tem
     return KMCF_OK;
 }
 
-// kmcf_execute_kmc_step (rate_mode KMCF_RATE_T_BG, no field) and kmcf_execute_kmc_step_thermal
-int execute_kmc_step_impl(const char *what, kmcf_comm *c, int N, const int *h_count, const int *h_displs, int nn,
-                          const int *d_neigh_idx, const int *d_site_layer, double T_bg, double freq,
-                          double sigma, double k, const double *d_x, const double *d_y, const double *d_z,
-                          const double *d_site_potential_charge, int *d_site_element, int *d_site_charge,
-                          int num_layers, const double *h_E_gen, const double *h_E_rec,
-                          const double *h_E_Vdiff, const double *h_E_Odiff,
-                          double (*next_random)(void *), void *rng_user, int max_events,
-                          double *event_time, int *n_events, int *h_event_log,
-                          const double *d_site_temperature, int rate_mode)
+// The null and size checks of the step and of kmcf_event_rates (rest_given: the pointers only the caller has); then s.E.
+int check_step_args(const char *what, const kmcf_comm *c, const int *h_count, const int *h_displs, ev_step_in &s, const ev_energies &e,
+                    bool rest_given)
 {
-    KMCF_CHECK(c && h_count && h_displs && d_neigh_idx && d_site_layer && d_x && d_y && d_z && d_site_potential_charge &&
-                   d_site_element && d_site_charge && h_E_gen && h_E_rec && h_E_Vdiff && h_E_Odiff && next_random && event_time,
-               KMCF_ERR_ARG, "%s: null argument", what);
+    KMCF_CHECK(c && h_count && h_displs && s.d_neigh_idx && s.d_site_layer && s.d_x && s.d_y && s.d_z && s.d_pot && s.d_element && s.d_charge &&
+                   e.gen && e.rec && e.vdiff && e.odiff && rest_given, KMCF_ERR_ARG, "%s: null argument", what);
     KMCF_CHECK(c->device >= 0, KMCF_ERR_STATE, "%s: host-only communicator", what);
-    KMCF_CHECK(num_layers > 0 && num_layers <= MAX_LAYERS && nn > 0 && freq > 0, KMCF_ERR_ARG, "%s: bad sizes", what);
-    const bool thermal = rate_mode != KMCF_RATE_T_BG;
-    KMCF_TRY(kmcf_enter(c));
-    hipStream_t st = c->stream;
-    // Multi-rank groups: the reference partitions the event list and pays a zero-out pass, an MPI_Allgather, an
-    // MPI_Bcast and two host synchronisations PER EVENT (:423-459; ~1e4 events per 40 nm step).  The site arrays
-    // are replicated on every rank anyway, so here every rank runs the whole step on the whole list: the neighbour
-    // lists are gathered once, the generators are in the same state by contract, and the ranks execute the same
-    // events with no collective and no extra synchronisation at all.  KMCF_EVENTS_PARTITIONED=1 keeps the
-    // reference's scheme.
-    const bool replicate = c->nranks > 1 && !kmcf_opt_set(c, KNOB_EVENTS_PARTITIONED);
-    const int P = replicate ? 1 : c->nranks, rank = replicate ? 0 : c->rank;
-    const int count = replicate ? N : h_count[rank], start_i = replicate ? 0 : h_displs[rank];
-    const size_t M = (size_t)count * nn;
-    const int nb = (int)((M + EV_TILE - 1) / EV_TILE);
-    const int ng = std::max((nb + EV_GROUP - 1) / EV_GROUP, 1);
-    layer_energies E;
-    fill_layer_energies(E, num_layers, h_E_gen, h_E_rec, h_E_Vdiff, h_E_Odiff);
-    const int n_aff = 4 * nn + 4;
-    // workspace kept on the communicator between steps: the reference allocates and frees its event arrays on
-    // every call (:352-361); at 40 nm that is 0.8 GB per step
-    if (c->ev_cache && (c->ev_cache->M != M || c->ev_cache->P != P || c->ev_cache->nn != nn)) kmcf_event_cache_free(c);
+    KMCF_CHECK(e.num_layers > 0 && e.num_layers <= MAX_LAYERS && s.nn > 0 && s.freq > 0, KMCF_ERR_ARG, "%s: bad sizes", what);
+    for (int l = 0; l < MAX_LAYERS; ++l) {
+        s.E.gen[l] = l < e.num_layers ? e.gen[l] : 0.0; s.E.rec[l] = l < e.num_layers ? e.rec[l] : 0.0;
+        s.E.vdiff[l] = l < e.num_layers ? e.vdiff[l] : 0.0; s.E.odiff[l] = l < e.num_layers ? e.odiff[l] : 0.0;
+    }
+    return KMCF_OK;
+}
+
+int build_grid(size_t M) { return (int)std::min<int64_t>(((int64_t)M + KMCF_BLOCK * 4 - 1) / (KMCF_BLOCK * 4), 16384); }
+
+// The one pass over the count * nn slots of the rows from start_i: the instance of the rate mode, periodic where the
+// communicator is (kmcf_events_set_lattice).  d_bad: the word of the thermal modes (KMCF_RATE_T_BG: not passed on).
+void launch_build_event_list(const kmcf_comm *c, const ev_step_in &s, int count, int start_i, unsigned char *d_type, double *d_prob, int *d_bad)
+{
+    const thermal_field th = {s.d_T, d_bad};
+    auto launch = [&](auto mode, auto... tail) {
+        build_event_list_kernel<decltype(mode)::value><<<build_grid((size_t)count * s.nn), KMCF_BLOCK, 0, c->stream>>>(
+            s.N, count, start_i, s.nn, s.d_neigh_idx, s.d_site_layer, s.T_bg, s.freq, s.sigma, s.k, s.d_x, s.d_y, s.d_z, s.d_pot,
+            s.d_element, s.d_charge, s.E, d_type, d_prob, tail...);
+    };
+    auto by_mode = [&](auto... lattice) {
+        if (s.rate_mode == KMCF_RATE_EKIN) launch(std::integral_constant<int, KMCF_RATE_EKIN>{}, th, lattice...);
+        else if (s.rate_mode == KMCF_RATE_T_SITE) launch(std::integral_constant<int, KMCF_RATE_T_SITE>{}, th, lattice...);
+        else launch(std::integral_constant<int, KMCF_RATE_T_BG>{}, lattice...);
+    };
+    if (c->ev_pbc) by_mode(ev_lattice{c->ev_ly, c->ev_lz});
+    else by_mode();
+}
+
+template <class T> bool ev_alloc(T **d, size_t n) { return kmcf_dev_alloc(d, n, false) == KMCF_OK; }
+
+// The buffers every path uses, kept on the communicator between steps (the reference allocates and frees its event arrays on
+// every call, :352-361; 0.8 GB per step at 40 nm), replaced when the shape changes.  A path's own are allocated where it starts.
+int ev_workspace(ev_step &S)
+{
+    kmcf_comm *c = S.c;
+    const int nn = S.in.nn;
+    if (c->ev_cache && (c->ev_cache->M != S.M || c->ev_cache->P != S.P || c->ev_cache->nn != nn)) kmcf_event_cache_free(c);
     if (!c->ev_cache) {
         kmcf_event_cache *w = new kmcf_event_cache();
-        w->M = M; w->P = P; w->nn = nn;
-        c->ev_cache = w;
-        if (hipMalloc(reinterpret_cast<void **>(&w->d_type), std::max<size_t>(M, 1)) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void **>(&w->d_prob), std::max<size_t>(M, 1) * sizeof(double)) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void **>(&w->d_tsum), (size_t)std::max(nb, 1) * sizeof(double)) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void **>(&w->d_gsum), (size_t)ng * sizeof(double)) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void **>(&w->d_tot), (size_t)P * sizeof(double)) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void **>(&w->d_ij), (size_t)3 * P * sizeof(int)) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void **>(&w->d_aff), (size_t)n_aff * sizeof(int)) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void **>(&w->d_asym), sizeof(int)) != hipSuccess) {
+        w->M = S.M; w->P = S.P; w->nn = nn; c->ev_cache = w;
+        const size_t M1 = std::max<size_t>(S.M, 1);
+        if (!(ev_alloc(&w->d_type, M1) && ev_alloc(&w->d_prob, M1) && ev_alloc(&w->d_tsum, std::max(S.nb, 1)) && ev_alloc(&w->d_gsum, S.ng) &&
+              ev_alloc(&w->d_tot, S.P) && ev_alloc(&w->d_ij, 3 * S.P) && ev_alloc(&w->d_aff, 4 * nn + 4) && ev_alloc(&w->d_asym, 1))) {
             kmcf_event_cache_free(c);
-            kmcf_set_error("%s: out of device memory for %zu event slots", what, M);
+            kmcf_set_error("%s: out of device memory for %zu event slots", S.what, S.M);
             return KMCF_ERR_HIP;
         }
     }
-    kmcf_event_cache *w = c->ev_cache;
-    if (thermal && !w->d_tbad) KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&w->d_tbad), (size_t)P * sizeof(int)));
-    if (replicate) {
-        if (w->full_key != d_neigh_idx || w->full_N != N) {     // the lists are built once per run (kmc_main.cpp:199)
-            if (w->d_neigh_full) { hipFree(w->d_neigh_full); w->d_neigh_full = nullptr; }
-            KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&w->d_neigh_full), (size_t)N * nn * sizeof(int)));
-            const int R = c->nranks;
-            std::vector<int> cn(R), dn(R);
-            for (int q = 0; q < R; ++q) {
-                KMCF_CHECK((int64_t)h_count[q] * nn < INT32_MAX && (int64_t)h_displs[q] * nn < INT32_MAX, KMCF_ERR_ARG,
-                           "%s: neighbour list too large for the int32 gather", what);
-                cn[q] = h_count[q] * nn; dn[q] = h_displs[q] * nn;
-            }
-            if (h_count[c->rank] > 0)
-                KMCF_HIP(hipMemcpyAsync(w->d_neigh_full + (size_t)dn[c->rank], d_neigh_idx, (size_t)cn[c->rank] * sizeof(int),
-                                        hipMemcpyDeviceToDevice, st));
-            KMCF_TRY(kmcf_comm_allgatherv_int(c, w->d_neigh_full, cn.data(), dn.data()));
-            w->full_key = d_neigh_idx;
-            w->full_N = N;
+    S.w = c->ev_cache;
+    return KMCF_OK;
+}
+
+// Replicated step of a multi-rank group: the neighbour lists of ALL sites, gathered when the caller's list is seen first
+// (the lists are built once per run, kmc_main.cpp:199); S.in.d_neigh_idx becomes the gathered copy.
+int ev_full_neighbours(ev_step &S, const int *h_count, const int *h_displs)
+{
+    kmcf_comm *c = S.c;
+    kmcf_event_cache *w = S.w;
+    const int N = S.in.N, nn = S.in.nn, R = c->nranks;
+    if (w->full_key != S.in.d_neigh_idx || w->full_N != N) {
+        if (w->d_neigh_full) { hipFree(w->d_neigh_full); w->d_neigh_full = nullptr; }
+        KMCF_TRY(kmcf_dev_alloc(&w->d_neigh_full, (size_t)N * nn, false));
+        std::vector<int> cn(R), dn(R);
+        for (int q = 0; q < R; ++q) {
+            KMCF_CHECK((int64_t)h_count[q] * nn < INT32_MAX && (int64_t)h_displs[q] * nn < INT32_MAX, KMCF_ERR_ARG,
+                       "%s: neighbour list too large for the int32 gather", S.what);
+            cn[q] = h_count[q] * nn; dn[q] = h_displs[q] * nn;
         }
-        d_neigh_idx = w->d_neigh_full;
+        if (h_count[c->rank] > 0)
+            KMCF_HIP(hipMemcpyAsync(w->d_neigh_full + (size_t)dn[c->rank], S.in.d_neigh_idx, (size_t)cn[c->rank] * sizeof(int),
+                                    hipMemcpyDeviceToDevice, c->stream));
+        KMCF_TRY(kmcf_comm_allgatherv_int(c, w->d_neigh_full, cn.data(), dn.data()));
+        w->full_key = S.in.d_neigh_idx; w->full_N = N;
     }
-    unsigned char *d_type = w->d_type;
-    double *d_prob = w->d_prob, *d_tsum = w->d_tsum, *d_gsum = w->d_gsum, *d_tot = w->d_tot;
-    int *d_ij = w->d_ij, *d_aff = w->d_aff, *d_asym = w->d_asym;
-    KMCF_HIP(hipMemsetAsync(d_gsum, 0, (size_t)ng * sizeof(double), st));
-    KMCF_HIP(hipMemsetAsync(d_asym, 0, sizeof(int), st));
+    S.in.d_neigh_idx = w->d_neigh_full;
+    return KMCF_OK;
+}
+
+// Thermal modes: the build kernel leaves the first site with an unusable temperature in d_tbad[rank]; the word comes back
+// with the step's first host round trip, before any event executes.  A partitioned group agrees on it first (every rank saw
+// only its own slots, and all must leave the step together).  Enqueues the read into S.h_bad, once; the caller synchronises.
+bool ev_read_bad(ev_step &S)
+{
+    if (!S.thermal || S.bad_read) return true;
+    S.bad_read = true;
+    std::vector<int> ones(S.P, 1), iota(S.P);
+    for (int q = 0; q < S.P; ++q) iota[q] = q;
+    if (S.P > 1 && kmcf_comm_allgatherv_int(S.c, S.w->d_tbad, ones.data(), iota.data()) != KMCF_OK) { S.rc = KMCF_ERR_COMM; return false; }
+    if (hipMemcpyAsync(S.h_bad.data(), S.w->d_tbad, (size_t)S.P * sizeof(int), hipMemcpyDeviceToHost, S.c->stream) == hipSuccess) return true;
+    S.rc = KMCF_ERR_HIP; return false;
+}
+
+// The smallest bad site of all ranks, EV_NO_BAD_SITE if there is none.  A step on a list whose symmetry is known pays one
+// synchronise for it here; the first sight of a list has brought the words along (ev_symmetric).
+int ev_bad_site(ev_step &S)
+{
+    // (whatever this rank's rc: a partitioned group's ranks all enter the all-gather of the word)
+    if (!S.bad_read && ev_read_bad(S) && hipStreamSynchronize(S.c->stream) != hipSuccess) S.rc = KMCF_ERR_HIP;
+    return *std::min_element(S.h_bad.begin(), S.h_bad.end());
+}
+
+// One rank holding all rows: does every listed neighbour list the site back?  The lists are built once per run (kmc_main.cpp:
+// 199): the verdict is kept with the workspace, keyed by the list's address and N.  The first sight of a list costs one
+// synchronise, which carries the thermal word too.
+bool ev_symmetric(ev_step &S)
+{
+    kmcf_event_cache *w = S.w;
+    hipStream_t st = S.c->stream;
+    if (w->sym_key != S.in.d_neigh_idx || w->sym_N != S.in.N) {
+        check_symmetry_kernel<<<build_grid(S.M), KMCF_BLOCK, 0, st>>>(S.in.N, S.in.nn, S.in.d_neigh_idx, w->d_asym);
+        int asym = 1;
+        ev_read_bad(S);
+        if (hipMemcpyAsync(&asym, w->d_asym, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess) S.rc = KMCF_ERR_HIP;
+        w->sym_key = S.in.d_neigh_idx; w->sym_N = S.in.N; w->symmetric = (asym == 0);
+    }
+    return w->symmetric;
+}
+
+// A batch on the host: uniforms in; state, (i, j, type) and (total rate, residence time) per event out.  step_persistent keeps
+// it in pinned memory that the kernel reads and writes itself, no copies; step_three_launches copies u up and the rest down.
+struct ev_batch_host {
+    alignas(64) event_batch_state state;        // polled by the host (state.seq): a cache line of its own
+    alignas(64) int log[3 * EV_BMAX];
+    double tot[2 * EV_BMAX], u[2 * EV_BMAX];
+};
+
+// The loop of the two batched paths.  Events are enqueued in batches with ONE host round trip per batch: the two
+// uniforms of every event of the batch are drawn ahead, the device decides after each event whether the step goes on,
+// and what is enqueued behind the step's last event returns at once.  With the library's own generator the draws are
+// made on a copy of its state and the real generator is advanced by what was consumed, so the caller's stream is used
+// exactly as by the reference (two draws per executed event); a foreign callback cannot be rewound, so it gets batches
+// of one.  run_batch(nbatch) enqueues a batch on b->u and returns with its results in *b; false: a HIP failure.
+template <class F>
+void ev_batch_loop(ev_step &S, int bmax, ev_batch_host *b, F &&run_batch)
+{
+    const ev_step_io &io = S.io;
+    volatile event_batch_state *state = &b->state;
+    const bool own_rng = (io.next_random == kmcf_rng_next);
+    int B = own_rng ? 4 : 1;
+    while (S.rc == KMCF_OK && S.t < 1 / S.in.freq && S.nev < io.max_events) {           // :418
+        const int nbatch = std::min(B, io.max_events - S.nev);
+        if (own_rng) {
+            kmcf_rng peek = *static_cast<kmcf_rng *>(io.rng_user);
+            for (int q = 0; q < 2 * nbatch; ++q) b->u[q] = peek.distribution(peek.rng);
+        } else {
+            b->u[0] = io.next_random(io.rng_user);                                        // :430
+            b->u[1] = io.next_random(io.rng_user);                                        // :479
+        }
+        state->done = 0; state->n_exec = 0; state->seq = 0;     // (seq: never equal to the number about to be waited for)
+        if (!run_batch(nbatch)) { S.rc = KMCF_ERR_HIP; break; }
+        const int n = state->n_exec, done = state->done;
+        for (int e = 0; e < n; ++e)
+            if (io.h_event_log) for (int q = 0; q < 3; ++q) io.h_event_log[3 * (S.nev + e) + q] = b->log[3 * e + q];
+        // residence time of the last executed event as the device computed it (:479); whether it ends the
+        // step was decided there too (state.done), so the two can never disagree
+        if (n > 0) S.t = b->tot[2 * (n - 1) + 1];
+        if (own_rng) for (int q = 0; q < 2 * n; ++q) io.next_random(io.rng_user);        // consume what was used
+        S.nev += n;
+        if (done == 2 || n == 0) {
+            kmcf_set_error("%s: no event could be selected (total rate %g)", S.what, n < nbatch ? b->tot[2 * n] : 0.0);
+            S.rc = KMCF_ERR_STATE;
+        }
+        if (own_rng && n == nbatch && done == 0 && B < bmax) B *= 2;
+    }
+}
+
+// Wait for the batch's number in state.seq, the batch kernel's last write: no sleep in hipStreamSynchronize per batch (a
+// one-event step of the 5 nm device: see DESIGN 8).  After 10 ms the synchronise after all: the number is there, or the kernel failed.
+bool ev_poll_batch(hipStream_t st, const volatile event_batch_state *state, int number)
+{
+    const auto t_poll = std::chrono::steady_clock::now();
+    int spins = 0;
+    while (__atomic_load_n(const_cast<const int *>(&state->seq), __ATOMIC_ACQUIRE) != number)
+        if ((++spins & 255) == 0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t_poll).count() > 10e-3)
+            return hipStreamSynchronize(st) == hipSuccess && state->seq == number;
+    return true;
+}
+
+// the supertile sums the batch kernel can keep in LDS beside its own arrays (0: it walks the tile sums in memory)
+int ev_batch_lds(long long n_tiles, long long n_groups)
+{
+    const long long n_st = (n_tiles + EV_ST - 1) / EV_ST;
+    hipFuncAttributes fa;
+    const bool fits = n_groups <= EV_GLDS && n_st <= EV_STMAX &&
+                      hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(event_batch_kernel)) == hipSuccess &&
+                      fa.sharedSizeBytes + (size_t)n_st * sizeof(double) <= (size_t)160 * 1024 &&
+                      hipFuncSetAttribute(reinterpret_cast<const void *>(event_batch_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          (int)(n_st * sizeof(double))) == hipSuccess;
+    (void)hipGetLastError();
+    return fits ? (int)n_st : 0;
+}
+
+// Persistent batch kernel with its row-aligned sums: one launch per batch, the results polled in the pinned block.
+void step_persistent(ev_step &S)
+{
+    kmcf_event_cache *w = S.w;
+    hipStream_t st = S.c->stream;
+    const int count = S.count, nn = S.in.nn;
+    const long long n_tiles = ((long long)count + EV_RT - 1) / EV_RT, n_groups = (n_tiles + EV_GROUP - 1) / EV_GROUP;
+    if (!w->d_rsum && !(ev_alloc(&w->d_rsum, std::max(count, 1)) && ev_alloc(&w->d_tsum2, std::max<long long>(n_tiles, 1)) &&
+                        ev_alloc(&w->d_gsum2, std::max<long long>(n_groups, 1)))) { S.rc = KMCF_ERR_HIP; return; }
+    auto lgrid = [](long long n_waves) { return (int)std::min<long long>(std::max<long long>((n_waves + 3) / 4, 1), 65536); };
+    ev_tree_level_kernel<<<lgrid(count), KMCF_BLOCK, 0, st>>>(0, count, (long long)S.M, nn, w->d_prob, w->d_rsum);
+    ev_tree_level_kernel<<<lgrid((n_tiles + 1) / 2), KMCF_BLOCK, 0, st>>>(1, n_tiles, count, nn, w->d_rsum, w->d_tsum2);
+    ev_tree_level_kernel<<<lgrid(n_groups), KMCF_BLOCK, 0, st>>>(2, n_groups, n_tiles, nn, w->d_tsum2, w->d_gsum2);
+    if (!w->h_pin) {
+        if (hipHostMalloc(&w->h_pin, sizeof(ev_batch_host), hipHostMallocDefault) != hipSuccess) { S.rc = KMCF_ERR_HIP; return; }
+        memset(w->h_pin, 0, sizeof(ev_batch_host)); w->batch_number = 0;    // (the polled number starts below the first one waited for)
+    }
+    ev_batch_host *pin = static_cast<ev_batch_host *>(w->h_pin);
+    event_batch_args A;
+    A.count = count; A.nn = nn; A.n_tiles = n_tiles; A.n_groups = n_groups; A.inv_freq = 1 / S.in.freq;
+    // (KMCF_EV_TREL: tests shrink the claim range to drive the kernel's out-of-range path)
+    A.trel_max = std::min(std::max(kmcf_opt_int(S.c, KNOB_EV_TREL, EV_TREL), 1), EV_TREL);
+    ev_batch_loop(S, EV_BMAX, pin, [&](int nbatch) {
+        if (w->batch_number == 0x7fffffff) w->batch_number = 0;
+        A.nbatch = nbatch; A.number = ++w->batch_number; A.n_st = ev_batch_lds(n_tiles, n_groups);
+        event_batch_kernel<<<1, EV_PB, (size_t)A.n_st * sizeof(double), st>>>(A, w->d_prob, w->d_type, S.in.d_neigh_idx, w->d_rsum, w->d_tsum2,
+                                                                              w->d_gsum2, S.io.d_element, S.io.d_charge, pin->log, pin->tot,
+                                                                              pin->u, &pin->state);
+        return hipGetLastError() == hipSuccess && ev_poll_batch(st, &pin->state, A.number);
+    });
+}
+
+// Three launches per event (select + execute + zero-out, tile sums, group sums): all group sums once, afterwards only
+// the groups of the tiles an event touched; uniforms up and results down through device buffers, one synchronise per batch.
+void step_three_launches(ev_step &S)
+{
+    kmcf_event_cache *w = S.w;
+    hipStream_t st = S.c->stream;
+    const int nn = S.in.nn, n_aff = 4 * nn + 4;
+    group_sum_kernel<<<(S.ng + KMCF_BLOCK - 1) / KMCF_BLOCK, KMCF_BLOCK, 0, st>>>(S.nb, w->d_tsum, S.ng, w->d_gsum);
+    if (!w->d_u && !(ev_alloc(&w->d_u, 2 * EV_BMAX3) && ev_alloc(&w->d_totlog, 2 * EV_BMAX3) && ev_alloc(&w->d_evlog, 3 * EV_BMAX3) &&
+                     hipMalloc(&w->d_state, sizeof(event_batch_state)) == hipSuccess)) { S.rc = KMCF_ERR_HIP; return; }
+    event_batch_state *d_state = static_cast<event_batch_state *>(w->d_state);
+    ev_batch_host h;
+    ev_batch_loop(S, EV_BMAX3, &h, [&](int nbatch) {
+        if (hipMemcpyAsync(w->d_u, h.u, 2 * nbatch * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess ||
+            hipMemsetAsync(d_state, 0, sizeof(event_batch_state), st) != hipSuccess) return false;
+        for (int ev = 0; ev < nbatch; ++ev) {
+            select_event_kernel<true><<<1, KMCF_BLOCK, 0, st>>>(S.M, S.nb, S.ng, S.start_i, nn, -1.0, 0.0, w->d_gsum, w->d_tsum, w->d_prob,
+                                                                w->d_type, S.in.d_neigh_idx, w->d_evlog, w->d_totlog, S.io.d_element,
+                                                                S.io.d_charge, w->d_aff, ev, w->d_u, d_state, 1 / S.in.freq);
+            tile_sum_kernel<<<n_aff, KMCF_BLOCK, 0, st>>>(S.M, w->d_prob, w->d_aff, w->d_tsum);
+            group_sum_aff_kernel<<<n_aff, KMCF_BLOCK, 0, st>>>(w->d_aff, S.nb, w->d_tsum, w->d_gsum);
+        }
+        return hipMemcpyAsync(&h.state, d_state, sizeof(h.state), hipMemcpyDeviceToHost, st) == hipSuccess &&
+               hipMemcpyAsync(h.log, w->d_evlog, 3 * nbatch * sizeof(int), hipMemcpyDeviceToHost, st) == hipSuccess &&
+               hipMemcpyAsync(h.tot, w->d_totlog, 2 * nbatch * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
+               hipStreamSynchronize(st) == hipSuccess;
+    });
+}
+
+// The reference's scheme (:418-479): per event a full pass over this rank's slots, the ranks' totals all-gathered, the
+// rank whose range holds the drawn number selects, the selection all-gathered; two host synchronisations per event.
+void step_fullscan(ev_step &S)
+{
+    kmcf_comm *c = S.c;
+    kmcf_event_cache *w = S.w;
+    hipStream_t st = c->stream;
+    const int P = S.P, rank = S.rank, N = S.in.N, nn = S.in.nn, nb = S.nb, ng = S.ng;
+    const size_t M = S.M;
+    double *d_tot = w->d_tot; int *d_ij = w->d_ij, ij[3];
     std::vector<int> ones(P, 1), iota(P), threes(P, 3), iota3(P);
     for (int q = 0; q < P; ++q) { iota[q] = q; iota3[q] = 3 * q; }
-    int rc = KMCF_OK;
-    auto fail = [&](int code) { rc = code; };
-    bool fast = false;   // neighbour-list zero-out + one host sync per event
-    // Thermal modes: the build kernel leaves the first site with an unusable temperature in d_tbad[rank]; the word comes
-    // back with the step's first host round trip, before any event executes.  A partitioned group agrees on it first
-    // (every rank saw only its own slots, and all must leave the step together).
-    std::vector<int> h_bad(P, EV_NO_BAD_SITE);
-    if (thermal) KMCF_HIP(hipMemsetAsync(w->d_tbad, 0x7f, (size_t)P * sizeof(int), st));
-    bool bad_read = false;
-    auto read_bad = [&]() {       // enqueue the read of the verdict (the caller synchronises)
-        if (!thermal || bad_read) return true;
-        bad_read = true;
-        if (P > 1 && kmcf_comm_allgatherv_int(c, w->d_tbad, ones.data(), iota.data()) != KMCF_OK) { fail(KMCF_ERR_COMM); return false; }
-        if (hipMemcpyAsync(h_bad.data(), w->d_tbad, (size_t)P * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess) { fail(KMCF_ERR_HIP); return false; }
-        return true;
-    };
-    if (M > 0) {
-        const int g = build_grid(M);
-        launch_build_event_list(rate_mode, g, st, N, count, start_i, nn, d_neigh_idx, d_site_layer, T_bg, freq, sigma, k, d_x, d_y, d_z,
-                                d_site_potential_charge, d_site_element, d_site_charge, E, d_type, d_prob, d_site_temperature,
-                                thermal ? w->d_tbad + rank : nullptr, c);
-        zero_and_sum_kernel<<<nb, KMCF_BLOCK, 0, st>>>(M, start_i, nn, d_neigh_idx, d_type, d_prob, -1, -1, d_tsum);
-        if (P == 1 && count == N && !kmcf_opt_set(c, KNOB_EVENTS_FULLSCAN)) {
-            // the neighbour lists are built once per run (kmc_main.cpp:199): the verdict on their symmetry is
-            // kept with the workspace, keyed by the list's address and shape
-            if (w->sym_key != d_neigh_idx || w->sym_N != N) {
-                check_symmetry_kernel<<<g, KMCF_BLOCK, 0, st>>>(N, nn, d_neigh_idx, d_asym);
-                int asym = 1;
-                read_bad();
-                if (hipMemcpyAsync(&asym, d_asym, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
-                    hipStreamSynchronize(st) != hipSuccess) fail(KMCF_ERR_HIP);
-                w->sym_key = d_neigh_idx;
-                w->sym_N = N;
-                w->symmetric = (asym == 0);
-            }
-            fast = w->symmetric;
-        }
-    }
-    if (thermal) {
-        // (whatever this rank's rc: a partitioned group's ranks all enter the all-gather of the word)
-        if (!bad_read && read_bad() && hipStreamSynchronize(st) != hipSuccess) fail(KMCF_ERR_HIP);
-        const int bad_site = *std::min_element(h_bad.begin(), h_bad.end());
-        if (rc == KMCF_OK && bad_site != EV_NO_BAD_SITE) {
-            kmcf_set_error("%s: the temperature of site %d is not finite or not > 0 (it owns an event)", what, bad_site);
-            *event_time = 0.0;
-            if (n_events) *n_events = 0;
-            return KMCF_ERR_ARG;
-        }
-    }
-    double t = 0.0;
-    int nev = 0;
     std::vector<double> totals(P);
-    const int ggrid = (ng + KMCF_BLOCK - 1) / KMCF_BLOCK;
-    if (fast && M > 0 && rc == KMCF_OK) {
-        // Fast path.  All group sums once, afterwards only the groups of the tiles an event touched; three
-        // launches per event (select + execute + zero-out, tile sums, group sums); events are enqueued in
-        // batches with ONE host round trip per batch: the two uniforms of every event of the batch are drawn
-        // ahead, the device decides after each event whether the step goes on, and the launches behind the
-        // step's last event return at once.  With the library's own generator the draws are made on a copy of
-        // its state and the real generator is advanced by what was consumed, so the caller's stream is used
-        // exactly as by the reference (two draws per executed event); a foreign callback cannot be rewound,
-        // so it gets batches of one.
-        // persistent batch kernel (default; KMCF_EVENTS_PERSISTENT=0: three launches per event) with its row-aligned sums
-        const bool persistent = kmcf_opt_int(c, KNOB_EVENTS_PERSISTENT, 1) != 0 && nn <= 63;
-        const long long n_tiles2 = ((long long)count + EV_RT - 1) / EV_RT, n_groups2 = (n_tiles2 + EV_GROUP - 1) / EV_GROUP;
-        if (persistent) {
-            if (!w->d_rsum &&
-                (hipMalloc(reinterpret_cast<void **>(&w->d_rsum), (size_t)std::max(count, 1) * sizeof(double)) != hipSuccess ||
-                 hipMalloc(reinterpret_cast<void **>(&w->d_tsum2), (size_t)std::max<long long>(n_tiles2, 1) * sizeof(double)) != hipSuccess ||
-                 hipMalloc(reinterpret_cast<void **>(&w->d_gsum2), (size_t)std::max<long long>(n_groups2, 1) * sizeof(double)) != hipSuccess)) fail(KMCF_ERR_HIP);
-            if (rc == KMCF_OK) {
-                auto lgrid = [](long long n_waves) { return (int)std::min<long long>(std::max<long long>((n_waves + 3) / 4, 1), 65536); };
-                ev_tree_level_kernel<<<lgrid(count), KMCF_BLOCK, 0, st>>>(0, count, (long long)M, nn, d_prob, w->d_rsum);
-                ev_tree_level_kernel<<<lgrid((n_tiles2 + 1) / 2), KMCF_BLOCK, 0, st>>>(1, n_tiles2, count, nn, w->d_rsum, w->d_tsum2);
-                ev_tree_level_kernel<<<lgrid(n_groups2), KMCF_BLOCK, 0, st>>>(2, n_groups2, n_tiles2, nn, w->d_tsum2, w->d_gsum2);
-            }
-        } else {
-            group_sum_kernel<<<ggrid, KMCF_BLOCK, 0, st>>>(nb, d_tsum, ng, d_gsum);
+    while (S.rc == KMCF_OK && S.t < 1 / S.in.freq && S.nev < S.io.max_events) {         // :418
+        if (M > 0) group_sum_kernel<<<(ng + KMCF_BLOCK - 1) / KMCF_BLOCK, KMCF_BLOCK, 0, st>>>(nb, w->d_tsum, ng, w->d_gsum);
+        total_kernel<<<1, 64, 0, st>>>(ng, w->d_gsum, d_tot + rank);
+        if (kmcf_comm_allgatherv_double(c, d_tot, ones.data(), iota.data()) != KMCF_OK) { S.rc = KMCF_ERR_COMM; break; }   // MPI_Allgather :423
+        if (hipMemcpyAsync(totals.data(), d_tot, (size_t)P * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess) { S.rc = KMCF_ERR_HIP; break; }
+        for (int q = 1; q < P; ++q) totals[q] += totals[q - 1];                           // :425-427
+        const double total = totals[P - 1];
+        double number = S.io.next_random(S.io.rng_user) * total;                          // :430
+        int source_rank = P - 1;
+        for (int q = 0; q < P; ++q)
+            if (number < totals[q]) { source_rank = q; break; }                           // :432-437
+        if (hipMemsetAsync(d_ij + 3 * rank, 0xff, 3 * sizeof(int), st) != hipSuccess) { S.rc = KMCF_ERR_HIP; break; }
+        if (rank == source_rank && M > 0) {
+            if (rank > 0) number -= totals[rank - 1];                                     // :440-442
+            if (number < 0) number = 0;
+            select_event_kernel<false><<<1, KMCF_BLOCK, 0, st>>>(M, nb, ng, S.start_i, nn, number, 0.0, w->d_gsum, w->d_tsum, w->d_prob,
+                                                                 w->d_type, S.in.d_neigh_idx, d_ij + 3 * rank, d_tot + rank,
+                                                                 nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0.0);
         }
-        const int BMAX = persistent ? EV_BMAX : 128;
-        // (KMCF_EV_TREL: tests shrink the claim range to drive the kernel's out-of-range path)
-        const int trel_max = std::min(std::max(kmcf_opt_int(c, KNOB_EV_TREL, EV_TREL), 1), EV_TREL);
-        const bool own_rng = (next_random == kmcf_rng_next);
-        if (!w->d_u &&
-            (hipMalloc(reinterpret_cast<void **>(&w->d_u), 2 * 512 * sizeof(double)) != hipSuccess ||
-             hipMalloc(reinterpret_cast<void **>(&w->d_totlog), 2 * 512 * sizeof(double)) != hipSuccess ||
-             hipMalloc(reinterpret_cast<void **>(&w->d_evlog), 3 * 512 * sizeof(int)) != hipSuccess ||
-             hipMalloc(reinterpret_cast<void **>(&w->d_state), sizeof(event_batch_state)) != hipSuccess)) fail(KMCF_ERR_HIP);
-        double *d_u = w->d_u, *d_totlog = w->d_totlog;
-        int *d_evlog = w->d_evlog;
-        event_batch_state *d_state = static_cast<event_batch_state *>(w->d_state);
-        // Persistent batches hand their results over in pinned host memory, which the kernel writes itself and the host
-        // polls (state.seq): no copies in either direction, no sleep in hipStreamSynchronize per batch (a one-event step
-        // of the 5 nm device: 0.15 -> see DESIGN 8).  Three launches per event, or no pinned block: device buffers and copies.
-        const bool pinned = persistent;
-        constexpr size_t PIN_LOG = 64, PIN_TOT = PIN_LOG + 3 * EV_BMAX * sizeof(int), PIN_U = PIN_TOT + 2 * EV_BMAX * sizeof(double),
-                         PIN_END = PIN_U + 2 * EV_BMAX * sizeof(double);
-        if (pinned && !w->h_pin) {
-            if (hipHostMalloc(reinterpret_cast<void **>(&w->h_pin), PIN_END, hipHostMallocDefault) != hipSuccess) fail(KMCF_ERR_HIP);
-            else { memset(w->h_pin, 0, PIN_END); w->batch_number = 0; }      // the polled number (state.seq) starts below the first one waited for
-        }
-        std::vector<double> h_u_v(2 * BMAX), h_tot_v(2 * BMAX);
-        std::vector<int> h_log_v(3 * BMAX);
-        const bool pin_ok = pinned && w->h_pin;
-        volatile event_batch_state *p_state = pin_ok ? reinterpret_cast<volatile event_batch_state *>(w->h_pin) : nullptr;
-        double *h_u = pin_ok ? reinterpret_cast<double *>(w->h_pin + PIN_U) : h_u_v.data();
-        double *h_tot = pin_ok ? reinterpret_cast<double *>(w->h_pin + PIN_TOT) : h_tot_v.data();
-        int *h_log = pin_ok ? reinterpret_cast<int *>(w->h_pin + PIN_LOG) : h_log_v.data();
-        int B = own_rng ? 4 : 1;
-        while (rc == KMCF_OK && t < 1 / freq && nev < max_events) {                      // :418
-            const int nbatch = std::min(B, max_events - nev);
-            if (own_rng) {
-                kmcf_rng peek = *static_cast<kmcf_rng *>(rng_user);
-                for (int q = 0; q < 2 * nbatch; ++q) h_u[q] = peek.distribution(peek.rng);
-            } else {
-                h_u[0] = next_random(rng_user);                                           // :430
-                h_u[1] = next_random(rng_user);                                           // :479
-            }
-            event_batch_state hs = {0, 0, 0, 0};
-            if (pin_ok) {
-                if (w->batch_number == 0x7fffffff) w->batch_number = 0;
-                p_state->done = 0; p_state->n_exec = 0; p_state->seq = 0;      // never equal to the number about to be waited for
-            } else if (hipMemcpyAsync(d_u, h_u, 2 * nbatch * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess ||
-                       hipMemsetAsync(d_state, 0, sizeof(event_batch_state), st) != hipSuccess) { fail(KMCF_ERR_HIP); break; }
-            if (persistent) {
-                event_batch_args A;
-                A.count = count; A.nn = nn; A.nbatch = nbatch; A.trel_max = trel_max; A.n_tiles = n_tiles2; A.n_groups = n_groups2; A.inv_freq = 1 / freq;
-                A.number = pin_ok ? ++w->batch_number : 0;
-                // the supertile sums in LDS where they fit beside the kernel's own arrays (else: the round-3 walk)
-                A.n_st = 0;
-                size_t dyn = 0;
-                {
-                    const long long n_st = (n_tiles2 + EV_ST - 1) / EV_ST;
-                    hipFuncAttributes fa;
-                    if (n_groups2 <= EV_GLDS && n_st <= EV_STMAX &&
-                        hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(event_batch_kernel)) == hipSuccess &&
-                        fa.sharedSizeBytes + (size_t)n_st * sizeof(double) <= (size_t)160 * 1024 &&
-                        hipFuncSetAttribute(reinterpret_cast<const void *>(event_batch_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)(n_st * sizeof(double))) == hipSuccess) {
-                        A.n_st = (int)n_st;
-                        dyn = (size_t)n_st * sizeof(double);
-                    }
-                    (void)hipGetLastError();
-                }
-                if (pin_ok)
-                    event_batch_kernel<<<1, EV_PB, dyn, st>>>(A, d_prob, d_type, d_neigh_idx, w->d_rsum, w->d_tsum2, w->d_gsum2, d_site_element,
-                                                                  d_site_charge, h_log, h_tot, h_u, const_cast<event_batch_state *>(p_state));
-                else
-                    event_batch_kernel<<<1, EV_PB, dyn, st>>>(A, d_prob, d_type, d_neigh_idx, w->d_rsum, w->d_tsum2, w->d_gsum2, d_site_element,
-                                                                  d_site_charge, d_evlog, d_totlog, d_u, d_state);
-            }
-            for (int ev = 0; ev < nbatch && !persistent; ++ev) {
-                select_event_kernel<true><<<1, KMCF_BLOCK, 0, st>>>(M, nb, ng, start_i, nn, -1.0, 0.0, d_gsum, d_tsum, d_prob, d_type,
-                                                                    d_neigh_idx, d_evlog, d_totlog, d_site_element, d_site_charge,
-                                                                    d_aff, ev, d_u, d_state, 1 / freq);
-                tile_sum_kernel<<<n_aff, KMCF_BLOCK, 0, st>>>(M, d_prob, d_aff, d_tsum);
-                group_sum_aff_kernel<<<n_aff, KMCF_BLOCK, 0, st>>>(d_aff, nb, d_tsum, d_gsum);
-            }
-            if (pin_ok) {
-                if (hipGetLastError() != hipSuccess) { fail(KMCF_ERR_HIP); break; }
-                const int number = w->batch_number;
-                const auto t_poll = std::chrono::steady_clock::now();
-                int spins = 0;
-                bool synced = false;
-                while (__atomic_load_n(const_cast<const int *>(&p_state->seq), __ATOMIC_ACQUIRE) != number) {
-                    if ((++spins & 255) == 0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t_poll).count() > 10e-3) {
-                        if (hipStreamSynchronize(st) != hipSuccess) rc = KMCF_ERR_HIP;     // (then the number is there, or the kernel failed)
-                        synced = true;
-                        break;
-                    }
-                }
-                if (rc != KMCF_OK || (synced && p_state->seq != number)) { fail(KMCF_ERR_HIP); break; }
-                hs.done = p_state->done; hs.n_exec = p_state->n_exec;
-            } else if (hipMemcpyAsync(&hs, d_state, sizeof(hs), hipMemcpyDeviceToHost, st) != hipSuccess ||
-                       hipMemcpyAsync(h_log, d_evlog, 3 * nbatch * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
-                       hipMemcpyAsync(h_tot, d_totlog, 2 * nbatch * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
-                       hipStreamSynchronize(st) != hipSuccess) { fail(KMCF_ERR_HIP); break; }
-            const int n = hs.n_exec;
-            for (int e = 0; e < n; ++e)
-                if (h_event_log) for (int q = 0; q < 3; ++q) h_event_log[3 * (nev + e) + q] = h_log[3 * e + q];
-            // residence time of the last executed event as the device computed it (:479); whether it ends the
-            // step was decided there too (hs.done), so the two can never disagree
-            if (n > 0) t = h_tot[2 * (n - 1) + 1];
-            if (own_rng) for (int q = 0; q < 2 * n; ++q) next_random(rng_user);           // consume what was used
-            nev += n;
-            if (rc == KMCF_OK && (hs.done == 2 || n == 0)) {
-                kmcf_set_error("%s: no event could be selected (total rate %g)", what, n < nbatch ? h_tot[2 * n] : 0.0);
-                fail(KMCF_ERR_STATE);
-            }
-            if (own_rng && n == nbatch && hs.done == 0 && B < BMAX) B *= 2;
-        }
-    }
-    while (!fast && rc == KMCF_OK && t < 1 / freq && nev < max_events) {                 // :418
-        if (M > 0) group_sum_kernel<<<ggrid, KMCF_BLOCK, 0, st>>>(nb, d_tsum, ng, d_gsum);
-        double total = 0.0;
-        int ij[3];
-        int source_rank = 0;
-        {
-            total_kernel<<<1, 64, 0, st>>>(ng, d_gsum, d_tot + rank);
-            if (kmcf_comm_allgatherv_double(c, d_tot, ones.data(), iota.data()) != KMCF_OK) { fail(KMCF_ERR_COMM); break; }   // MPI_Allgather :423
-            if (hipMemcpyAsync(totals.data(), d_tot, (size_t)P * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
-                hipStreamSynchronize(st) != hipSuccess) { fail(KMCF_ERR_HIP); break; }
-            for (int q = 1; q < P; ++q) totals[q] += totals[q - 1];                       // :425-427
-            total = totals[P - 1];
-            double number = next_random(rng_user) * total;                                // :430
-            source_rank = P - 1;
-            for (int q = 0; q < P; ++q)
-                if (number < totals[q]) { source_rank = q; break; }                       // :432-437
-            if (hipMemsetAsync(d_ij + 3 * rank, 0xff, 3 * sizeof(int), st) != hipSuccess) { fail(KMCF_ERR_HIP); break; }
-            if (rank == source_rank && M > 0) {
-                if (rank > 0) number -= totals[rank - 1];                                 // :440-442
-                if (number < 0) number = 0;
-                select_event_kernel<false><<<1, KMCF_BLOCK, 0, st>>>(M, nb, ng, start_i, nn, number, 0.0, d_gsum, d_tsum, d_prob,
-                                                                     d_type, d_neigh_idx, d_ij + 3 * rank, d_tot + rank,
-                                                                     nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0.0);
-            }
-            if (kmcf_comm_allgatherv_int(c, d_ij, threes.data(), iota3.data()) != KMCF_OK) { fail(KMCF_ERR_COMM); break; }  // MPI_Bcast :455-459
-            if (hipMemcpyAsync(ij, d_ij + 3 * source_rank, 3 * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
-                hipStreamSynchronize(st) != hipSuccess) { fail(KMCF_ERR_HIP); break; }
-            if (ij[0] >= 0 && ij[0] < N && ij[1] >= 0 && ij[1] < N) {
-                execute_event_kernel<<<1, 64, 0, st>>>(d_site_element, d_site_charge, d_ij + 3 * source_rank);
-                if (M > 0) zero_and_sum_kernel<<<nb, KMCF_BLOCK, 0, st>>>(M, start_i, nn, d_neigh_idx, d_type, d_prob, ij[0], ij[1], d_tsum);
-            }
-        }
+        if (kmcf_comm_allgatherv_int(c, d_ij, threes.data(), iota3.data()) != KMCF_OK) { S.rc = KMCF_ERR_COMM; break; }  // MPI_Bcast :455-459
+        if (hipMemcpyAsync(ij, d_ij + 3 * source_rank, 3 * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess) { S.rc = KMCF_ERR_HIP; break; }
         if (ij[0] < 0 || ij[0] >= N || ij[1] < 0 || ij[1] >= N) {
-            kmcf_set_error("%s: no event could be selected (total rate %g)", what, total);
-            fail(KMCF_ERR_STATE);
-            break;
+            kmcf_set_error("%s: no event could be selected (total rate %g)", S.what, total);
+            S.rc = KMCF_ERR_STATE; break;
         }
-        if (h_event_log) { h_event_log[3 * nev] = ij[0]; h_event_log[3 * nev + 1] = ij[1]; h_event_log[3 * nev + 2] = ij[2]; }
-        t = -std::log(next_random(rng_user)) / total;                                     // :479
-        ++nev;
+        execute_event_kernel<<<1, 64, 0, st>>>(S.io.d_element, S.io.d_charge, d_ij + 3 * source_rank);
+        if (M > 0) zero_and_sum_kernel<<<nb, KMCF_BLOCK, 0, st>>>(M, S.start_i, nn, S.in.d_neigh_idx, w->d_type, w->d_prob, ij[0], ij[1], w->d_tsum);
+        if (S.io.h_event_log) for (int q = 0; q < 3; ++q) S.io.h_event_log[3 * S.nev + q] = ij[q];
+        S.t = -std::log(S.io.next_random(S.io.rng_user)) / total;                         // :479
+        ++S.nev;
     }
-    if (rc == KMCF_OK && hipStreamSynchronize(st) != hipSuccess) rc = KMCF_ERR_HIP;
-    if (rc == KMCF_ERR_HIP) kmcf_set_error("%s: HIP failure: %s", what, hipGetErrorString(hipGetLastError()));
-    *event_time = t;
-    if (n_events) *n_events = nev;
-    return rc;
+}
+
+// kmcf_execute_kmc_step (rate_mode KMCF_RATE_T_BG, no field) and kmcf_execute_kmc_step_thermal: checks, layout,
+// workspace, build and first sums, the two verdicts, then the events on one path.
+int execute_kmc_step_impl(const char *what, kmcf_comm *c, const int *h_count, const int *h_displs, ev_step_in in, const ev_energies &e,
+                          const ev_step_io &io, double *event_time, int *n_events)
+{
+    KMCF_TRY(check_step_args(what, c, h_count, h_displs, in, e, io.next_random && event_time));
+    KMCF_TRY(kmcf_enter(c));
+    hipStream_t st = c->stream;
+    // Multi-rank groups: the reference partitions the event list and pays a zero-out pass, an MPI_Allgather, an MPI_Bcast and
+    // two host synchronisations PER EVENT (:423-459; ~1e4 events per 40 nm step).  The site arrays are replicated on every rank
+    // anyway, so here every rank runs the whole step on the whole list: the neighbour lists are gathered once, the generators
+    // are in the same state by contract, and the ranks execute the same events with no collective and no extra synchronisation
+    // at all.  KMCF_EVENTS_PARTITIONED=1 keeps the reference's scheme.
+    const bool replicate = c->nranks > 1 && !kmcf_opt_set(c, KNOB_EVENTS_PARTITIONED);
+    ev_step S;
+    S.what = what; S.c = c; S.in = in; S.io = io;
+    S.P = replicate ? 1 : c->nranks; S.rank = replicate ? 0 : c->rank;
+    S.count = replicate ? in.N : h_count[S.rank]; S.start_i = replicate ? 0 : h_displs[S.rank];
+    S.M = (size_t)S.count * in.nn; S.nb = (int)((S.M + EV_TILE - 1) / EV_TILE); S.ng = std::max((S.nb + EV_GROUP - 1) / EV_GROUP, 1);
+    KMCF_TRY(ev_workspace(S));
+    kmcf_event_cache *w = S.w;
+    S.thermal = in.rate_mode != KMCF_RATE_T_BG; S.h_bad.assign(S.P, EV_NO_BAD_SITE);
+    if (S.thermal && !w->d_tbad) KMCF_TRY(kmcf_dev_alloc(&w->d_tbad, (size_t)S.P, false));
+    if (replicate) KMCF_TRY(ev_full_neighbours(S, h_count, h_displs));
+    KMCF_HIP(hipMemsetAsync(w->d_gsum, 0, (size_t)S.ng * sizeof(double), st));
+    KMCF_HIP(hipMemsetAsync(w->d_asym, 0, sizeof(int), st));
+    if (S.thermal) KMCF_HIP(hipMemsetAsync(w->d_tbad, 0x7f, (size_t)S.P * sizeof(int), st));
+    bool fast = false;                  // one rank holds all rows and the lists are symmetric: the batched paths
+    if (S.M > 0) {
+        launch_build_event_list(c, S.in, S.count, S.start_i, w->d_type, w->d_prob, S.thermal ? w->d_tbad + S.rank : nullptr);
+        zero_and_sum_kernel<<<S.nb, KMCF_BLOCK, 0, st>>>(S.M, S.start_i, in.nn, S.in.d_neigh_idx, w->d_type, w->d_prob, -1, -1, w->d_tsum);
+        if (S.P == 1 && S.count == in.N && !kmcf_opt_set(c, KNOB_EVENTS_FULLSCAN)) fast = ev_symmetric(S);
+    }
+    const int bad_site = S.thermal ? ev_bad_site(S) : EV_NO_BAD_SITE;
+    if (S.rc == KMCF_OK && bad_site != EV_NO_BAD_SITE) {           // refused before any event: time 0, no event, no path, no wait
+        kmcf_set_error("%s: the temperature of site %d is not finite or not > 0 (it owns an event)", what, bad_site);
+        S.rc = KMCF_ERR_ARG;
+    }
+    if (S.rc == KMCF_OK) {
+        if (!fast) step_fullscan(S);
+        else if (kmcf_opt_int(c, KNOB_EVENTS_PERSISTENT, 1) != 0 && in.nn <= 63) step_persistent(S);   // (EV_AFF: the rows of two wavefronts)
+        else step_three_launches(S);
+    }
+    if (S.rc == KMCF_OK && hipStreamSynchronize(st) != hipSuccess) S.rc = KMCF_ERR_HIP;
+    if (S.rc == KMCF_ERR_HIP) kmcf_set_error("%s: HIP failure: %s", what, hipGetErrorString(hipGetLastError()));
+    *event_time = S.t;
+    if (n_events) *n_events = S.nev;
+    return S.rc;
 }
 
 }  // namespace
 
-extern "C" int kmcf_execute_kmc_step(kmcf_comm *c, int N, const int *h_count, const int *h_displs, int nn,
-                                     const int *d_neigh_idx, const int *d_site_layer, double T_bg, double freq,
-                                     double sigma, double k, const double *d_x, const double *d_y, const double *d_z,
-                                     const double *d_site_potential_charge, int *d_site_element, int *d_site_charge,
-                                     int num_layers, const double *h_E_gen, const double *h_E_rec,
-                                     const double *h_E_Vdiff, const double *h_E_Odiff,
-                                     double (*next_random)(void *), void *rng_user, int max_events,
-                                     double *event_time, int *n_events, int *h_event_log)
+extern "C" int kmcf_execute_kmc_step(kmcf_comm *c, int N, const int *h_count, const int *h_displs, int nn, const int *d_neigh_idx,
+                                     const int *d_site_layer, double T_bg, double freq, double sigma, double k, const double *d_x,
+                                     const double *d_y, const double *d_z, const double *d_site_potential_charge, int *d_site_element,
+                                     int *d_site_charge, int num_layers, const double *h_E_gen, const double *h_E_rec,
+                                     const double *h_E_Vdiff, const double *h_E_Odiff, double (*next_random)(void *), void *rng_user,
+                                     int max_events, double *event_time, int *n_events, int *h_event_log)
 {
-    return execute_kmc_step_impl("kmcf_execute_kmc_step", c, N, h_count, h_displs, nn, d_neigh_idx, d_site_layer, T_bg, freq, sigma, k,
-                                 d_x, d_y, d_z, d_site_potential_charge, d_site_element, d_site_charge, num_layers, h_E_gen, h_E_rec,
-                                 h_E_Vdiff, h_E_Odiff, next_random, rng_user, max_events, event_time, n_events, h_event_log,
-                                 nullptr, KMCF_RATE_T_BG);
+    const ev_step_in in = {N, nn, d_neigh_idx, d_site_layer, T_bg, freq, sigma, k, d_x, d_y, d_z, d_site_potential_charge,
+                           d_site_element, d_site_charge, nullptr, KMCF_RATE_T_BG, {}};
+    return execute_kmc_step_impl("kmcf_execute_kmc_step", c, h_count, h_displs, in, {num_layers, h_E_gen, h_E_rec, h_E_Vdiff, h_E_Odiff},
+                                 {d_site_element, d_site_charge, next_random, rng_user, max_events, h_event_log}, event_time, n_events);
 }
 
 extern "C" int kmcf_events_reset(kmcf_comm *c)
@@ -1498,39 +1511,35 @@ extern "C" int kmcf_events_set_lattice(kmcf_comm *c, const double *h_lattice, in
     return KMCF_OK;
 }
 
-extern "C" int kmcf_execute_kmc_step_thermal(kmcf_comm *c, int N, const int *h_count, const int *h_displs, int nn,
-                                             const int *d_neigh_idx, const int *d_site_layer, double T_bg, double freq,
-                                             double sigma, double k, const double *d_x, const double *d_y, const double *d_z,
+extern "C" int kmcf_execute_kmc_step_thermal(kmcf_comm *c, int N, const int *h_count, const int *h_displs, int nn, const int *d_neigh_idx,
+                                             const int *d_site_layer, double T_bg, double freq, double sigma, double k,
+                                             const double *d_x, const double *d_y, const double *d_z,
                                              const double *d_site_potential_charge, int *d_site_element, int *d_site_charge,
-                                             int num_layers, const double *h_E_gen, const double *h_E_rec,
-                                             const double *h_E_Vdiff, const double *h_E_Odiff,
-                                             double (*next_random)(void *), void *rng_user, int max_events,
+                                             int num_layers, const double *h_E_gen, const double *h_E_rec, const double *h_E_Vdiff,
+                                             const double *h_E_Odiff, double (*next_random)(void *), void *rng_user, int max_events,
                                              double *event_time, int *n_events, int *h_event_log,
                                              const double *d_site_temperature, int rate_mode)
 {
-    KMCF_TRY(check_thermal_args("kmcf_execute_kmc_step_thermal", rate_mode, d_site_temperature, T_bg));
-    return execute_kmc_step_impl("kmcf_execute_kmc_step_thermal", c, N, h_count, h_displs, nn, d_neigh_idx, d_site_layer, T_bg, freq,
-                                 sigma, k, d_x, d_y, d_z, d_site_potential_charge, d_site_element, d_site_charge, num_layers, h_E_gen,
-                                 h_E_rec, h_E_Vdiff, h_E_Odiff, next_random, rng_user, max_events, event_time, n_events, h_event_log,
-                                 d_site_temperature, rate_mode);
+    const char *what = "kmcf_execute_kmc_step_thermal";
+    KMCF_TRY(check_thermal_args(what, rate_mode, d_site_temperature, T_bg));
+    const ev_step_in in = {N, nn, d_neigh_idx, d_site_layer, T_bg, freq, sigma, k, d_x, d_y, d_z, d_site_potential_charge,
+                           d_site_element, d_site_charge, d_site_temperature, rate_mode, {}};
+    return execute_kmc_step_impl(what, c, h_count, h_displs, in, {num_layers, h_E_gen, h_E_rec, h_E_Vdiff, h_E_Odiff},
+                                 {d_site_element, d_site_charge, next_random, rng_user, max_events, h_event_log}, event_time, n_events);
 }
 
-extern "C" int kmcf_event_rates(kmcf_comm *c, int N, const int *h_count, const int *h_displs, int nn,
-                                const int *d_neigh_idx, const int *d_site_layer, double T_bg, double freq,
-                                double sigma, double k, const double *d_x, const double *d_y, const double *d_z,
-                                const double *d_site_potential_charge, const int *d_site_element,
-                                const int *d_site_charge, int num_layers, const double *h_E_gen,
+extern "C" int kmcf_event_rates(kmcf_comm *c, int N, const int *h_count, const int *h_displs, int nn, const int *d_neigh_idx,
+                                const int *d_site_layer, double T_bg, double freq, double sigma, double k, const double *d_x,
+                                const double *d_y, const double *d_z, const double *d_site_potential_charge,
+                                const int *d_site_element, const int *d_site_charge, int num_layers, const double *h_E_gen,
                                 const double *h_E_rec, const double *h_E_Vdiff, const double *h_E_Odiff,
-                                const double *d_site_temperature, int rate_mode,
-                                unsigned char *h_type, double *h_prob)
+                                const double *d_site_temperature, int rate_mode, unsigned char *h_type, double *h_prob)
 {
     const char *what = "kmcf_event_rates";
     KMCF_TRY(check_thermal_args(what, rate_mode, d_site_temperature, T_bg));
-    KMCF_CHECK(c && h_count && h_displs && d_neigh_idx && d_site_layer && d_x && d_y && d_z && d_site_potential_charge &&
-                   d_site_element && d_site_charge && h_E_gen && h_E_rec && h_E_Vdiff && h_E_Odiff,
-               KMCF_ERR_ARG, "%s: null argument", what);
-    KMCF_CHECK(c->device >= 0, KMCF_ERR_STATE, "%s: host-only communicator", what);
-    KMCF_CHECK(num_layers > 0 && num_layers <= MAX_LAYERS && nn > 0 && freq > 0, KMCF_ERR_ARG, "%s: bad sizes", what);
+    ev_step_in in = {N, nn, d_neigh_idx, d_site_layer, T_bg, freq, sigma, k, d_x, d_y, d_z, d_site_potential_charge,
+                     d_site_element, d_site_charge, d_site_temperature, rate_mode, {}};
+    KMCF_TRY(check_step_args(what, c, h_count, h_displs, in, {num_layers, h_E_gen, h_E_rec, h_E_Vdiff, h_E_Odiff}, true));
     KMCF_TRY(kmcf_enter(c));
     hipStream_t st = c->stream;
     // this rank's own rows, whatever the group's event step does with them (replicated or partitioned): the caller's
@@ -1538,21 +1547,12 @@ extern "C" int kmcf_event_rates(kmcf_comm *c, int N, const int *h_count, const i
     const int count = h_count[c->rank], start_i = h_displs[c->rank];
     const size_t M = (size_t)count * nn;
     if (M == 0) return KMCF_OK;
-    layer_energies E;
-    fill_layer_energies(E, num_layers, h_E_gen, h_E_rec, h_E_Vdiff, h_E_Odiff);
-    const bool thermal = rate_mode != KMCF_RATE_T_BG;
     unsigned char *d_type = nullptr;
     double *d_prob = nullptr;
-    int *d_bad = nullptr;
-    int bad_site = EV_NO_BAD_SITE;
-    bool ok = hipMalloc(reinterpret_cast<void **>(&d_type), M) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void **>(&d_prob), M * sizeof(double)) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void **>(&d_bad), sizeof(int)) == hipSuccess &&
-              hipMemsetAsync(d_bad, 0x7f, sizeof(int), st) == hipSuccess;
+    int *d_bad = nullptr, bad_site = EV_NO_BAD_SITE;
+    bool ok = ev_alloc(&d_type, M) && ev_alloc(&d_prob, M) && ev_alloc(&d_bad, 1) && hipMemsetAsync(d_bad, 0x7f, sizeof(int), st) == hipSuccess;
     if (ok) {
-        launch_build_event_list(rate_mode, build_grid(M), st, N, count, start_i, nn, d_neigh_idx, d_site_layer, T_bg, freq, sigma, k,
-                                d_x, d_y, d_z, d_site_potential_charge, d_site_element, d_site_charge, E, d_type, d_prob,
-                                d_site_temperature, thermal ? d_bad : nullptr, c);
+        launch_build_event_list(c, in, count, start_i, d_type, d_prob, rate_mode != KMCF_RATE_T_BG ? d_bad : nullptr);
         ok = hipGetLastError() == hipSuccess &&
              hipMemcpyAsync(&bad_site, d_bad, sizeof(int), hipMemcpyDeviceToHost, st) == hipSuccess &&
              (!h_type || hipMemcpyAsync(h_type, d_type, M, hipMemcpyDeviceToHost, st) == hipSuccess) &&
@@ -1560,9 +1560,7 @@ extern "C" int kmcf_event_rates(kmcf_comm *c, int N, const int *h_count, const i
              hipStreamSynchronize(st) == hipSuccess;
     }
     if (!ok) kmcf_set_error("%s: HIP failure: %s", what, hipGetErrorString(hipGetLastError()));
-    if (d_type) hipFree(d_type);
-    if (d_prob) hipFree(d_prob);
-    if (d_bad) hipFree(d_bad);
+    kmcf_dev_free_all({d_type, d_prob, d_bad});
     if (!ok) return KMCF_ERR_HIP;
     KMCF_CHECK(bad_site == EV_NO_BAD_SITE, KMCF_ERR_ARG, "%s: the temperature of site %d is not finite or not > 0 (it owns an event)",
                what, bad_site);

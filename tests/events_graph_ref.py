@@ -356,6 +356,8 @@ BUILDERS = {
     "nn63": lambda: graph_case("nn63", ring_list(9006, list(range(1, 32)) + [4503], True, 63), 60, 8),
     "nn64": lambda: graph_case("nn64", ring_list(7001, list(range(1, 33)), True, 64), 60, 9),
     "nn70": lambda: graph_case("nn70", ring_list(7001, list(range(1, 36)), False, 70), 60, 10),
+    # nn70's N with local7's list: the two share one communicator in test_one_communicator_through_every_path
+    "ring7_7001": lambda: graph_case("ring7_7001", ring_list(7001, [1, 2, 70], False, 7), 60, 14),
     "scatter": lambda: graph_case("scatter", ring_list(600077, [1] + [24576 * k + 5 for k in range(1, 13)], True, 26), 60, 11),
     "mixed": _mixed,
     "many": lambda: _many(4096),

@@ -40,7 +40,7 @@ def _common(name, c, ref, m, min_types=3):
     assert len(np.unique(ref["log"][:, 2])) >= min_types
 
 
-@pytest.mark.parametrize("name", ["pairs1", "chain2", "local7", "nn63", "nn64", "nn70", "many", "many_capped"])
+@pytest.mark.parametrize("name", ["pairs1", "chain2", "local7", "nn63", "nn64", "nn70", "ring7_7001", "many", "many_capped"])
 def test_small_graphs(oracle, name):
     c, ref, m, fp = _stats(oracle, name)
     _common(name, c, ref, m)
@@ -57,6 +57,8 @@ def test_small_graphs(oracle, name):
         assert c["nn"] == G.NN_PERSISTENT and (valid == 63).all()                  # n_aff = 2 nn + 2 = 128 = EV_AFF
     if name in ("nn64", "nn70"):
         assert c["nn"] > G.NN_PERSISTENT                                           # three launches per event
+    if name == "ring7_7001":
+        assert c["N"] == G.case("nn70")["N"] and c["nn"] <= G.NN_PERSISTENT and nt > 1     # nn70's rows, on the persistent path
     if name == "many":
         assert ref["n"] > (4 + 8 + 16 + 32 + 64 + 128 + 256) + G.EV_BMAX           # batches of 4 .. 256, one of 512, into a second of 512
         assert len(np.unique(ref["log"][:, 2])) == 4

@@ -264,6 +264,40 @@ def test_verdict_cache_list_changed_in_place(km, oracle):
         dv.close()
 
 
+def test_one_communicator_through_every_path(km, oracle, monkeypatch):
+    """ONE communicator whose workspace changes shape and path between steps (every other test opens a fresh one per case).
+    ring7_7001 and nn70 have the same N: the persistent path (its tree and pinned block are allocated), nn70 (nn changes:
+    the cache is rebuilt; nn > 63: three launches, their device batch buffers), then ring7_7001 on the full pass, on three
+    launches and on the persistent path again -- a workspace that holds the buffers of all three paths --, and once more
+    after kmcf_events_reset.  Every step against oracle.kmc_step."""
+    ring, wide = G.case("ring7_7001"), G.case("nn70")
+    assert ring["N"] == wide["N"] and ring["nn"] <= G.NN_PERSISTENT < wide["nn"]
+    dv = _Dev(km, ring)
+    lists = {"ring7_7001": dv.neigh, "nn70": dv.i32(wide["neigh"].reshape(-1))}
+
+    def step(name, knob=None):
+        for k in KNOBS:
+            monkeypatch.delenv(k, raising=False)
+        if knob:
+            monkeypatch.setenv(*knob)
+        c = G.case(name)
+        dv.neigh = lists[name]
+        dv.load(c)
+        rng = km.solvers.RandomNumberGenerator(c["seed"])
+        _same(oracle, dv, dv.step(rng), G.reference(oracle, name), rng)
+
+    try:
+        step("ring7_7001")
+        step("nn70")
+        step("ring7_7001", ("KMCF_EVENTS_FULLSCAN", "1"))
+        step("ring7_7001", ("KMCF_EVENTS_PERSISTENT", "0"))
+        step("ring7_7001")
+        km.solvers.events_reset(dv.comm)
+        step("ring7_7001")
+    finally:
+        dv.close()
+
+
 def test_verdict_cache_list_at_another_address(km, oracle):
     """... and asym's list in a new tensor while the old one is alive: another address, a fresh verdict by itself."""
     c = G.case("local7")
