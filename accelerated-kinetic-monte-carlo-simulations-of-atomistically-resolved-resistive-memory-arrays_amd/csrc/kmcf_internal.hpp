@@ -552,6 +552,18 @@ inline bool kmcf_cg_single_reduction(const kmcf_matrix *m)
     return cg1r;
 }
 
+// f(b...) with each runtime bool turned into std::true_type / std::false_type, in order: one instance of f per
+// combination, so that a dispatcher names its kernel once.
+template <class F>
+void with_bools(F &&f) { f(); }
+
+template <class F, class... B>
+void with_bools(F &&f, bool b, B... rest)
+{
+    if (b) with_bools([&](auto... t) { f(std::true_type{}, t...); }, rest...);
+    else with_bools([&](auto... t) { f(std::false_type{}, t...); }, rest...);
+}
+
 // Sub-block operator of a split matrix A = A_csr + P^T S P (the T matrix's tunnel block): S acts on the
 // sub-vector of the n_glob sub points of ALL ranks; this rank owns rows [displs[rank], +counts[rank]).
 // Stored as a bitmap over the n_glob columns (one 64-bit mask per 64 columns and row) plus the packed f64
@@ -568,9 +580,13 @@ struct kmcf_subop {
     double *d_xsub = nullptr;                // n_glob: gathered sub-vector
     long long nnz = 0;
     size_t cap_mask = 0, cap_val = 0, cap_rows = 0, cap_x = 0, cap_voff = 0;
-    int grid = 0;                            // blocks of the operator kernel = partials it writes
-    // Dense symmetric storage (kmcf_tstate.hip: sub_symm_kernel), chosen per assembly for one rank when the block is
-    // more than half full (the vacancy-vacancy block of a large device is ~100 % dense): the upper block triangle
+    // p.Ap partials one application writes (= blocks of the kernel that writes them): bitmap, one per block of
+    // sub_spmv_kernel (a wave per own row; 0 without own rows); tiles of one rank, one per block row (sub_symm_reduce_kernel:
+    // nb); tiles spread over a group, one per 256 own points (sub_combine_kernel; 0 without own points)
+    int grid = 0;
+    // Dense symmetric storage (kmcf_tstate.hip: sub_symm_kernel), chosen per assembly when the block has 2048 points or
+    // more and is more than a QUARTER full (the rule and its numbers: kmcf_subplan.hpp; the vacancy-vacancy block of a
+    // large device is ~100 % dense): the upper block triangle
     // as 64 x 64 tiles of f64 (zeros where the pattern has no entry), diagonal tiles complete.  Half the bytes of the
     // packed full block per application; every tile serves its block row (row sums) and, transposed out of LDS, its
     // block column (column sums); partial sums are written per strip / tile and added in a fixed order.

@@ -847,18 +847,6 @@ int grid_for(int64_t work_items, int per_block)
     return (int)((g + 7) / 8 * 8);
 }
 
-// f(b...) with each runtime bool turned into std::true_type / std::false_type, in order: one instance of f per
-// combination, so that a dispatcher names its kernel once.
-template <class F>
-void with_bools(F &&f) { f(); }
-
-template <class F, class... B>
-void with_bools(F &&f, bool b, B... rest)
-{
-    if (b) with_bools([&](auto... t) { f(std::true_type{}, t...); }, rest...);
-    else with_bools([&](auto... t) { f(std::false_type{}, t...); }, rest...);
-}
-
 template <int LPR>
 void launch_vec(kmcf_matrix *m, bool with_dot, bool skip_if_done, bool boundary_pass)
 {

@@ -27,8 +27,20 @@
 
 #include "kmcf_cells.hpp"
 #include "kmcf_internal.hpp"
+#include "kmcf_subplan.hpp"
+
+static_assert(KMCF_SUB_MAX_PARTIALS == KMCF_MAX_PARTIALS && KMCF_SUB_BLOCK == KMCF_BLOCK, "kmcf_subplan.hpp restates the two constants");
+static_assert(sizeof(kmcf_strip) == sizeof(int4), "a strip is uploaded as is to kmcf_subop::d_strips");
 
 int kmcf_pcg_workspace(kmcf_matrix *m, bool precond, double tol, int max_it, int fixed_iters, kmcf_solve_stats_t *stats);
+
+// the read-backs of an assembly and of the power pass, in pinned memory
+struct t_pinned {
+    int n_t, err;          // tunnel points of all ranks; the atom set differs from the one at init
+    long long nnz;         // entries of this rank's rows of the tunnel block
+    double imacro;
+    long long jnnz;        // entries stored by the jagged tiles
+};
 
 struct kmcf_tstate {
     kmcf_comm *comm = nullptr;
@@ -52,7 +64,7 @@ struct kmcf_tstate {
     int *d_inv_perm = nullptr;
     double *d_diag = nullptr, *d_diag_tot = nullptr, *d_rhs = nullptr;
     // tunnel points (all ranks' points on every rank: site arrays are replicated)
-    int *d_tflag = nullptr, *d_blk = nullptr, *d_tidx = nullptr, *d_tinfo = nullptr;
+    int *d_blk = nullptr, *d_tidx = nullptr, *d_tinfo = nullptr;
     double *d_tx = nullptr, *d_ty = nullptr, *d_tz = nullptr, *d_tcb = nullptr;
     int *d_rowcnt = nullptr;
     double *d_tdiag = nullptr;
@@ -63,7 +75,7 @@ struct kmcf_tstate {
     double *d_pdisp = nullptr;                     // Nsub
     double *d_scal = nullptr;                      // [0] imacro, [1] min
     int *d_err = nullptr;
-    int *h_pin = nullptr;                          // pinned: [0] n_t, [1] err, [2..3] nnz (long long)
+    t_pinned *h_pin = nullptr;
     double *d_agree = nullptr, *h_agree = nullptr; // storage vote of a rank group: 2 P on the device; pinned 2 + 2 P
     bool assembled = false;
     kmcf_current_params_t par{};
@@ -598,9 +610,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void copy_pdisp_kernel(int n_atoms_in_m
 
 
 // ---------------------------------------------------------------- dense symmetric sub-block (kmcf_subop::dense)
-// Tile (I, J), J >= I, of the upper block triangle: 64 x 64 f64, row-major, at tile index I nb - I (I - 1) / 2 + (J - I).
-__host__ __device__ inline long long symm_tile_index(int nb, int I, int J) { return (long long)I * nb - (long long)I * (I - 1) / 2 + (J - I); }
-
+// (tile (I, J), J >= I, of the upper block triangle: at symm_tile_index(nb, I, J), kmcf_subplan.hpp)
 constexpr int SYM_LD = 65;                                   // LDS row stride (doubles): row- AND column-wise reads conflict-free
 constexpr int SYM_WAVE_DOUBLES = 64 * SYM_LD + 256;          // tile + four 64-vectors per wave
 
@@ -1243,6 +1253,17 @@ int ensure(T **d, size_t *cap, size_t need)
     return kmcf_dev_grow(d, cap, need, std::max<size_t>(need + need / 4, 64) - need);
 }
 
+// blocks of a kernel that gives a wave to each of ns rows (KMCF_BLOCK / 64 = 4 waves a block: (ns + 3) / 4), at most
+// one per p.Ap partial
+int wave_row_grid(int ns)
+{
+    constexpr int wpb = KMCF_BLOCK / 64;
+    return std::max(1, std::min((ns + wpb - 1) / wpb, KMCF_MAX_PARTIALS));
+}
+
+// blocks of a kernel that gives a wave to each strip of tiles
+int strip_grid(int n_strips) { return std::max(1, std::min((n_strips + 3) / 4, 8192)); }
+
 }  // namespace
 
 extern "C" int kmcf_tstate_destroy(kmcf_tstate *t)
@@ -1253,7 +1274,7 @@ extern "C" int kmcf_tstate_destroy(kmcf_tstate *t)
         hipStreamSynchronize(t->comm->stream);
         kmcf_dev_free_all({t->d_atom_site, t->d_site_is_atom, t->d_ax, t->d_ay, t->d_az, t->d_acb, t->d_ael, t->d_ach, t->d_acls,
                            t->d_cls_col, t->d_col_node, t->d_diag_pos, t->d_ground, t->d_inv_perm, t->d_diag, t->d_diag_tot, t->d_rhs,
-                           t->d_tflag, t->d_blk, t->d_tidx, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz, t->d_tcb, t->d_rowcnt, t->d_tdiag,
+                           t->d_blk, t->d_tidx, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz, t->d_tcb, t->d_rowcnt, t->d_tdiag,
                            t->sub.d_rows, t->sub.d_mask, t->sub.d_voff, t->sub.d_val, t->sub.d_xsub, t->d_pdisp, t->d_scal, t->d_err,
                            t->sub.d_tiles, t->sub.d_strips, t->sub.d_strip_first, t->sub.d_rowpart, t->sub.d_colpart,
                            t->sub.d_jmask, t->sub.d_jvoff, t->sub.d_jval, t->sub.d_jcnt, t->sub.d_tile_local, t->sub.d_ypart, t->d_agree,
@@ -1269,87 +1290,97 @@ extern "C" int kmcf_tstate_destroy(kmcf_tstate *t)
 
 extern "C" kmcf_matrix *kmcf_tstate_matrix(kmcf_tstate *t) { return t ? t->T : nullptr; }
 
-extern "C" int kmcf_initialize_sparsity_T(kmcf_comm *c, const double *d_site_x, const double *d_site_y, const double *d_site_z,
-                                          const int *d_site_element, int N, double nn_dist, int num_source_inj,
-                                          int num_ground_ext, int num_layers_contact, const int *h_counts_T,
-                                          const int *h_displs_T, kmcf_tstate **out)
+// ---------------------------------------------------------------- kmcf_initialize_sparsity_T, step by step
+struct t_host_coords { std::vector<double> x, y, z; };      // the atoms' coordinates as the gather kernel wrote them
+
+static int init_check_args(const kmcf_comm *c, const double *d_site_x, const double *d_site_y, const double *d_site_z,
+                           const int *d_site_element, int N, double nn_dist, int num_source_inj, int num_ground_ext,
+                           int num_layers_contact, const int *h_counts_T, const int *h_displs_T, kmcf_tstate **out)
 {
     KMCF_CHECK(c && d_site_x && d_site_y && d_site_z && d_site_element && h_counts_T && h_displs_T && out, KMCF_ERR_ARG,
                "kmcf_initialize_sparsity_T: null argument");
     KMCF_CHECK(c->device >= 0, KMCF_ERR_STATE, "kmcf_initialize_sparsity_T: host-only communicator");
     KMCF_CHECK(N > 0 && num_source_inj > 0 && num_ground_ext > 0 && num_layers_contact > 0 && nn_dist > 0, KMCF_ERR_ARG,
                "kmcf_initialize_sparsity_T: bad sizes");
-    KMCF_TRY(kmcf_enter(c));
-    hipStream_t st = c->stream;
-    KMCF_HIP(hipStreamSynchronize(st));
-    // atoms = sites that are not interstitials (is_defect, src/gpu_solvers.h:331-337), in site order
+    return KMCF_OK;
+}
+
+// atoms = sites that are not interstitials (is_defect, src/gpu_solvers.h:331-337), in site order; the per-atom arrays
+static int init_atom_set(kmcf_tstate *t, const int *d_site_element, const int *h_counts_T)
+{
+    const int N = t->N;
     std::vector<int> el((size_t)N);
     KMCF_HIP(hipMemcpy(el.data(), d_site_element, (size_t)N * sizeof(int), hipMemcpyDeviceToHost));
-    kmcf_tstate *t = new kmcf_tstate();
-    struct guard_t { kmcf_tstate *t; ~guard_t() { if (t) kmcf_tstate_destroy(t); } } guard{t};
-    t->comm = c; t->N = N; t->n_inj = num_source_inj; t->n_ext = num_ground_ext; t->n_layers = num_layers_contact;
-    t->nn_dist = nn_dist;
     std::vector<unsigned char> is_atom((size_t)N, 0);
     for (int s = 0; s < N; ++s)
         if (el[s] != EL_DEFECT && el[s] != EL_OXYGEN_DEFECT) { t->h_atom_site.push_back(s); is_atom[s] = 1; }
     const int Na = t->N_atom = (int)t->h_atom_site.size();
     const int Nsub = t->Nsub = Na + 1;
-    KMCF_CHECK(Na >= 4 && num_source_inj + 2 < Nsub && num_ground_ext < Na, KMCF_ERR_ARG,
-               "kmcf_initialize_sparsity_T: %d atoms for %d injection / %d extraction atoms", Na, num_source_inj, num_ground_ext);
-    const int P = c->nranks, rank = c->rank;
-    {
-        int64_t tot = 0;
-        for (int q = 0; q < P; ++q) tot += h_counts_T[q];
-        KMCF_CHECK(tot == Nsub, KMCF_ERR_ARG, "kmcf_initialize_sparsity_T: counts_T sum to %lld, the matrix has N_atom + 1 = %d rows",
-                   (long long)tot, Nsub);
-    }
-    const int n_loc = h_counts_T[rank], row0 = h_displs_T[rank];
+    KMCF_CHECK(Na >= 4 && t->n_inj + 2 < Nsub && t->n_ext < Na, KMCF_ERR_ARG,
+               "kmcf_initialize_sparsity_T: %d atoms for %d injection / %d extraction atoms", Na, t->n_inj, t->n_ext);
+    int64_t tot = 0;
+    for (int q = 0; q < t->comm->nranks; ++q) tot += h_counts_T[q];
+    KMCF_CHECK(tot == Nsub, KMCF_ERR_ARG, "kmcf_initialize_sparsity_T: counts_T sum to %lld, the matrix has N_atom + 1 = %d rows",
+               (long long)tot, Nsub);
     KMCF_TRY(upload(&t->d_atom_site, t->h_atom_site));
     KMCF_TRY(upload(&t->d_site_is_atom, is_atom));
     const size_t na = (size_t)Na;      // (>= 4: no buffer below is empty; all of them start zeroed)
     KMCF_TRY(kmcf_dev_alloc(&t->d_ax, na, true)); KMCF_TRY(kmcf_dev_alloc(&t->d_ay, na, true)); KMCF_TRY(kmcf_dev_alloc(&t->d_az, na, true));
     KMCF_TRY(kmcf_dev_alloc(&t->d_acb, na, true)); KMCF_TRY(kmcf_dev_alloc(&t->d_ael, na, true)); KMCF_TRY(kmcf_dev_alloc(&t->d_ach, na, true));
     KMCF_TRY(kmcf_dev_alloc(&t->d_acls, na, true));
+    return KMCF_OK;
+}
+
+// the atoms' coordinates out of the caller's site arrays, on the device and (read back and checked) on the host
+static int init_gather_coords(kmcf_tstate *t, const double *d_site_x, const double *d_site_y, const double *d_site_z, t_host_coords *xyz)
+{
+    kmcf_comm *c = t->comm;
+    const int N = t->N, Na = t->N_atom;
     // On the CALLER's stream (kmcf_setup_stream, kmcf_internal.hpp): the first kernel that reads the caller's arrays.
     gather_coords_kernel<<<kmcf_grid1d(Na), KMCF_BLOCK, 0, kmcf_setup_stream(c)>>>(Na, t->d_atom_site, d_site_x, d_site_y, d_site_z, t->d_ax, t->d_ay, t->d_az);
     KMCF_HIP(hipGetLastError());
     KMCF_HIP(hipStreamSynchronize(kmcf_setup_stream(c)));
     KMCF_HIP(hipGetLastError());
-    KMCF_HIP(hipStreamSynchronize(st));
-    std::vector<double> ax((size_t)Na), ay((size_t)Na), az((size_t)Na);
-    KMCF_HIP(hipMemcpy(ax.data(), t->d_ax, (size_t)Na * sizeof(double), hipMemcpyDeviceToHost));
-    KMCF_HIP(hipMemcpy(ay.data(), t->d_ay, (size_t)Na * sizeof(double), hipMemcpyDeviceToHost));
-    KMCF_HIP(hipMemcpy(az.data(), t->d_az, (size_t)Na * sizeof(double), hipMemcpyDeviceToHost));
-    {
-        // what the gather kernel read must be what a synchronous copy of the caller's arrays reads (the failure this
-        // guards against built a pattern from coordinates whose y and z were still zero: silently)
-        std::vector<double> sx((size_t)N);
-        const double *src[3] = {d_site_x, d_site_y, d_site_z};
-        const std::vector<double> *got[3] = {&ax, &ay, &az};
-        for (int q = 0; q < 3; ++q) {
-            KMCF_HIP(hipMemcpy(sx.data(), src[q], (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
-            for (int a = 0; a < Na; ++a)
-                KMCF_CHECK(memcmp(&(*got[q])[(size_t)a], &sx[(size_t)t->h_atom_site[(size_t)a]], sizeof(double)) == 0, KMCF_ERR_STATE,
-                           "kmcf_initialize_sparsity_T: the gather kernel does not see the site coordinates the host copy sees (atom %d, "
-                           "coordinate %d: %.17g against %.17g): an upload of the caller's arrays has not completed for this stream -- "
-                           "upload from pinned memory, or synchronise the upload's stream, before the call", a, q, (*got[q])[(size_t)a],
-                           sx[(size_t)t->h_atom_site[(size_t)a]]);
-        }
+    KMCF_HIP(hipStreamSynchronize(c->stream));
+    std::vector<double> *got[3] = {&xyz->x, &xyz->y, &xyz->z};
+    const double *dev[3] = {t->d_ax, t->d_ay, t->d_az};
+    for (int q = 0; q < 3; ++q) {
+        got[q]->resize((size_t)Na);
+        KMCF_HIP(hipMemcpy(got[q]->data(), dev[q], (size_t)Na * sizeof(double), hipMemcpyDeviceToHost));
     }
+    // what the gather kernel read must be what a synchronous copy of the caller's arrays reads (the failure this
+    // guards against built a pattern from coordinates whose y and z were still zero: silently)
+    std::vector<double> sx((size_t)N);
+    const double *src[3] = {d_site_x, d_site_y, d_site_z};
+    for (int q = 0; q < 3; ++q) {
+        KMCF_HIP(hipMemcpy(sx.data(), src[q], (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
+        for (int a = 0; a < Na; ++a)
+            KMCF_CHECK(memcmp(&(*got[q])[(size_t)a], &sx[(size_t)t->h_atom_site[(size_t)a]], sizeof(double)) == 0, KMCF_ERR_STATE,
+                       "kmcf_initialize_sparsity_T: the gather kernel does not see the site coordinates the host copy sees (atom %d, "
+                       "coordinate %d: %.17g against %.17g): an upload of the caller's arrays has not completed for this stream -- "
+                       "upload from pinned memory, or synchronise the upload's stream, before the call", a, q, (*got[q])[(size_t)a],
+                       sx[(size_t)t->h_atom_site[(size_t)a]]);
+    }
+    return KMCF_OK;
+}
 
-    // atom-atom pattern of this rank's atom rows (calc_nnz_per_row_T / assemble_T_col_indices, "direct terms",
-    // src/initialize_sparsity_T.cu:62-72, 166-177; the diagonal comes with it: dist 0 < nn_dist)
-    const int a0 = std::max(row0, 2) - 2, a1 = std::max(row0 + n_loc, 2) - 2;      // atoms [a0, a1) = rows [a0 + 2, a1 + 2)
-    std::vector<int> arp, acol;
-    {
-        host_cells hc;
-        const double lattice[3] = {1, 1, 1};
-        KMCF_TRY(build_cells(t->d_ax, t->d_ay, t->d_az, Na, lattice, 0, nn_dist, &hc));
-        const int rc = build_pattern(hc, t->d_ax, t->d_ay, t->d_az, lattice, 0, nn_dist, a0, a1 - a0, 0, Na - 1, &arp, &acol, st);
-        hc.release();
-        if (rc != KMCF_OK) return rc;
-    }
-    // rows of this rank with GLOBAL columns (src/initialize_sparsity_T.cu:27-60, 126-164)
+// atom-atom pattern of the atom rows [a0, a1) (calc_nnz_per_row_T / assemble_T_col_indices, "direct terms",
+// src/initialize_sparsity_T.cu:62-72, 166-177; the diagonal comes with it: dist 0 < nn_dist)
+static int init_atom_pattern(kmcf_tstate *t, int a0, int a1, std::vector<int> *arp, std::vector<int> *acol)
+{
+    host_cells hc;
+    const double lattice[3] = {1, 1, 1};
+    KMCF_TRY(build_cells(t->d_ax, t->d_ay, t->d_az, t->N_atom, lattice, 0, t->nn_dist, &hc));
+    const int rc = build_pattern(hc, t->d_ax, t->d_ay, t->d_az, lattice, 0, t->nn_dist, a0, a1 - a0, 0, t->N_atom - 1, arp, acol, t->comm->stream);
+    hc.release();
+    return rc;
+}
+
+// rows [row0, row0 + n_loc) with GLOBAL columns (src/initialize_sparsity_T.cu:27-60, 126-164): the two virtual nodes'
+// rows, and the atom rows out of the atom-atom pattern (atom a is row a + 2; arp / acol start at atom a0)
+static int init_rows(kmcf_tstate *t, int row0, int n_loc, int a0, const std::vector<int> &arp, const std::vector<int> &acol)
+{
+    const int Nsub = t->Nsub, num_source_inj = t->n_inj, num_ground_ext = t->n_ext;
     std::vector<int> &rp = t->h_row_ptr, &col = t->h_col;
     rp.assign((size_t)n_loc + 1, 0);
     col.clear();
@@ -1370,29 +1401,37 @@ extern "C" int kmcf_initialize_sparsity_T(kmcf_comm *c, const double *d_site_x, 
         KMCF_CHECK(col.size() < (size_t)INT32_MAX, KMCF_ERR_ARG, "kmcf_initialize_sparsity_T: pattern exceeds int32 indexing");
         rp[r + 1] = (int)col.size();
     }
-    // internal row order: virtual nodes first, atoms in bricks like K (kmcf_kstate.hip); long rows are moved
-    // behind by the matrix builder
+    return KMCF_OK;
+}
+
+// internal row order: virtual nodes first, atoms in bricks like K (kmcf_kstate.hip); long rows are moved behind by the
+// matrix builder.  Empty: the caller's order.
+static std::vector<int> init_brick_order(const kmcf_comm *c, int row0, int n_loc, const t_host_coords &xyz)
+{
     std::vector<int> perm;
-    {
-        const double edge = kmcf_brick_edge(c);
-        if (edge > 0 && n_loc > 1) {
-            std::vector<int64_t> key((size_t)n_loc);
-            for (int r = 0; r < n_loc; ++r) {
-                const int i = row0 + r;
-                if (i < 2) { key[r] = -1; continue; }
-                const int a = i - 2;
-                const int64_t bx = (int64_t)std::floor(ax[a] / edge) + (1 << 19), by = (int64_t)std::floor(ay[a] / edge) + (1 << 19),
-                              bz = (int64_t)std::floor(az[a] / edge) + (1 << 19);
-                key[r] = (by << 42) | (bz << 21) | bx;
-            }
-            perm.resize((size_t)n_loc);
-            for (int r = 0; r < n_loc; ++r) perm[r] = r;
-            std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) { return key[a] < key[b]; });
-        }
+    const double edge = kmcf_brick_edge(c);
+    if (!(edge > 0 && n_loc > 1)) return perm;
+    std::vector<int64_t> key((size_t)n_loc);
+    for (int r = 0; r < n_loc; ++r) {
+        const int i = row0 + r;
+        if (i < 2) { key[r] = -1; continue; }
+        const int a = i - 2;
+        const int64_t bx = (int64_t)std::floor(xyz.x[a] / edge) + (1 << 19), by = (int64_t)std::floor(xyz.y[a] / edge) + (1 << 19),
+                      bz = (int64_t)std::floor(xyz.z[a] / edge) + (1 << 19);
+        key[r] = (by << 42) | (bz << 21) | bx;
     }
-    KMCF_TRY(kmcf_matrix_build(c, Nsub, h_counts_T, h_displs_T, rp.data(), col.data(), nullptr, perm.empty() ? nullptr : perm.data(), &t->T));
+    perm.resize((size_t)n_loc);
+    for (int r = 0; r < n_loc; ++r) perm[r] = r;
+    std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) { return key[a] < key[b]; });
+    return perm;
+}
+
+// per internal row: caller row, diagonal position, ground flag; per internal column: global node
+static int init_row_tables(kmcf_tstate *t, const t_host_coords &xyz)
+{
     kmcf_matrix *m = t->T;
-    // per internal row: caller row, diagonal position, ground flag; per internal column: global node
+    const int n_loc = m->n_loc, row0 = m->row0, Na = t->N_atom;
+    const std::vector<int> &rp = t->h_row_ptr, &col = t->h_col;
     std::vector<int> iperm((size_t)n_loc);                      // internal -> caller local row
     for (int i = 0; i < n_loc; ++i) iperm[i] = m->h_perm.empty() ? i : m->h_perm[i];
     t->h_inv_perm.assign((size_t)n_loc, 0);
@@ -1408,8 +1447,8 @@ extern "C" int kmcf_initialize_sparsity_T(kmcf_comm *c, const double *d_site_x, 
             if (col[j] == node) { diag_pos[i] = m->h_row_ptr[i] + (j - rp[r]); break; }
         if (node >= 2) {
             const int a = node - 2, g = Na - 1;
-            const double dx = ax[g] - ax[a], dy = ay[g] - ay[a], dz = az[g] - az[a];
-            ground[i] = std::sqrt(dx * dx + dy * dy + dz * dz) < nn_dist ? 1 : 0;      // current_solver_gpu.cu:1115-1117
+            const double dx = xyz.x[g] - xyz.x[a], dy = xyz.y[g] - xyz.y[a], dz = xyz.z[g] - xyz.z[a];
+            ground[i] = std::sqrt(dx * dx + dy * dy + dz * dz) < t->nn_dist ? 1 : 0;      // current_solver_gpu.cu:1115-1117
         }
     }
     for (int h = 0; h < m->n_halo; ++h) col_node[(size_t)n_loc + h] = halo_gid[h];
@@ -1417,35 +1456,85 @@ extern "C" int kmcf_initialize_sparsity_T(kmcf_comm *c, const double *d_site_x, 
     KMCF_TRY(upload(&t->d_ground, ground));
     KMCF_TRY(upload(&t->d_col_node, col_node));
     KMCF_TRY(upload(&t->d_inv_perm, t->h_inv_perm));
-    const size_t nl1 = (size_t)std::max(n_loc, 1);     // (a rank may hold no row)
+    return KMCF_OK;
+}
+
+template <typename T>
+static int pinned_zeroed(T **h, size_t n)
+{
+    KMCF_HIP(hipHostMalloc(reinterpret_cast<void **>(h), n * sizeof(T), hipHostMallocDefault));
+    memset(*h, 0, n * sizeof(T));
+    return KMCF_OK;
+}
+
+// what an assembly, the power pass and kmcf_current_map write besides the matrix (the block's own buffers grow per assembly)
+static int init_workspace(kmcf_tstate *t, const int *h_counts_T, const int *h_displs_T)
+{
+    const kmcf_matrix *m = t->T;
+    const int n_loc = m->n_loc, Na = t->N_atom, Nsub = t->Nsub, P = t->comm->nranks;
+    const size_t na = (size_t)Na, nl1 = (size_t)std::max(n_loc, 1);     // (a rank may hold no row)
     KMCF_TRY(kmcf_dev_alloc(&t->d_cls_col, std::max<size_t>((size_t)n_loc + m->n_halo, 1), true));
     KMCF_TRY(kmcf_dev_alloc(&t->d_diag, nl1, true)); KMCF_TRY(kmcf_dev_alloc(&t->d_diag_tot, nl1, true));
     KMCF_TRY(kmcf_dev_alloc(&t->d_rhs, (size_t)n_loc + 2, true));
-    // tunnel workspace sized by the atom count (grow-only buffers for the block itself)
+    // tunnel workspace sized by the atom count
     const int nblk = (Na + KMCF_SCAN_TILE - 1) / KMCF_SCAN_TILE;
-    KMCF_TRY(kmcf_dev_alloc(&t->d_tflag, 1, true)); KMCF_TRY(kmcf_dev_alloc(&t->d_blk, (size_t)2 * nblk + 2, true));
+    KMCF_TRY(kmcf_dev_alloc(&t->d_blk, (size_t)2 * nblk + 2, true));
     KMCF_TRY(kmcf_dev_alloc(&t->d_tidx, na, true)); KMCF_TRY(kmcf_dev_alloc(&t->d_tinfo, na, true));
     KMCF_TRY(kmcf_dev_alloc(&t->d_tx, na, true)); KMCF_TRY(kmcf_dev_alloc(&t->d_ty, na, true)); KMCF_TRY(kmcf_dev_alloc(&t->d_tz, na, true));
     KMCF_TRY(kmcf_dev_alloc(&t->d_tcb, na, true));
     KMCF_TRY(kmcf_dev_alloc(&t->d_pdisp, (size_t)Nsub + 2, true)); KMCF_TRY(kmcf_dev_alloc(&t->d_scal, 4, true));
     KMCF_TRY(kmcf_dev_alloc(&t->d_err, 1, true));
-    KMCF_HIP(hipHostMalloc(reinterpret_cast<void **>(&t->h_pin), 8 * sizeof(int), hipHostMallocDefault));
-    memset(t->h_pin, 0, 8 * sizeof(int));
+    KMCF_TRY(pinned_zeroed(&t->h_pin, 1));
     KMCF_TRY(kmcf_dev_alloc(&t->d_agree, (size_t)2 * P, true));
-    KMCF_HIP(hipHostMalloc(reinterpret_cast<void **>(&t->h_agree), (size_t)(2 + 2 * P) * sizeof(double), hipHostMallocDefault));
-    memset(t->h_agree, 0, (size_t)(2 + 2 * P) * sizeof(double));
+    KMCF_TRY(pinned_zeroed(&t->h_agree, (size_t)(2 + 2 * P)));
     t->sub.counts.assign(P, 0);
     t->sub.displs.assign(P, 0);
     // scratch of kmcf_current_map (here, not at its first call: no allocation between the exchanges of a group)
     KMCF_CHECK((int64_t)3 * (Nsub + 2) < (int64_t)INT32_MAX, KMCF_ERR_ARG, "kmcf_initialize_sparsity_T: %d atoms exceed int32 indexing", Na);
     KMCF_TRY(kmcf_dev_alloc(&t->d_cmap, (size_t)3 * (Nsub + 2), true)); KMCF_TRY(kmcf_dev_alloc(&t->d_cmstat, 8, true));
-    KMCF_HIP(hipHostMalloc(reinterpret_cast<void **>(&t->h_cmstat), 8 * sizeof(double), hipHostMallocDefault));
-    memset(t->h_cmstat, 0, 8 * sizeof(double));
+    KMCF_TRY(pinned_zeroed(&t->h_cmstat, 8));
     t->cm_counts.resize((size_t)P); t->cm_displs.resize((size_t)P);
     for (int q = 0; q < P; ++q) { t->cm_counts[q] = 3 * h_counts_T[q]; t->cm_displs[q] = 3 * h_displs_T[q]; }
+    return KMCF_OK;
+}
+
+extern "C" int kmcf_initialize_sparsity_T(kmcf_comm *c, const double *d_site_x, const double *d_site_y, const double *d_site_z,
+                                          const int *d_site_element, int N, double nn_dist, int num_source_inj,
+                                          int num_ground_ext, int num_layers_contact, const int *h_counts_T,
+                                          const int *h_displs_T, kmcf_tstate **out)
+{
+    KMCF_TRY(init_check_args(c, d_site_x, d_site_y, d_site_z, d_site_element, N, nn_dist, num_source_inj, num_ground_ext,
+                             num_layers_contact, h_counts_T, h_displs_T, out));
+    KMCF_TRY(kmcf_enter(c));
+    KMCF_HIP(hipStreamSynchronize(c->stream));
+    kmcf_tstate *t = new kmcf_tstate();
+    struct guard_t { kmcf_tstate *t; ~guard_t() { if (t) kmcf_tstate_destroy(t); } } guard{t};      // (a half-built state)
+    t->comm = c; t->N = N; t->n_inj = num_source_inj; t->n_ext = num_ground_ext; t->n_layers = num_layers_contact;
+    t->nn_dist = nn_dist;
+    KMCF_TRY(init_atom_set(t, d_site_element, h_counts_T));
+    t_host_coords xyz;
+    KMCF_TRY(init_gather_coords(t, d_site_x, d_site_y, d_site_z, &xyz));
+    const int n_loc = h_counts_T[c->rank], row0 = h_displs_T[c->rank];
+    const int a0 = std::max(row0, 2) - 2, a1 = std::max(row0 + n_loc, 2) - 2;      // atoms [a0, a1) = rows [a0 + 2, a1 + 2)
+    std::vector<int> arp, acol;
+    KMCF_TRY(init_atom_pattern(t, a0, a1, &arp, &acol));
+    KMCF_TRY(init_rows(t, row0, n_loc, a0, arp, acol));
+    const std::vector<int> perm = init_brick_order(c, row0, n_loc, xyz);
+    KMCF_TRY(kmcf_matrix_build(c, t->Nsub, h_counts_T, h_displs_T, t->h_row_ptr.data(), t->h_col.data(), nullptr,
+                               perm.empty() ? nullptr : perm.data(), &t->T));
+    KMCF_TRY(init_row_tables(t, xyz));
+    KMCF_TRY(init_workspace(t, h_counts_T, h_displs_T));
     guard.t = nullptr;
     *out = t;
     return KMCF_OK;
+}
+
+// bytes this rank holds of the block's matrix, per storage form
+static int64_t tunnel_bytes(const kmcf_subop &sb)
+{
+    if (sb.jagged) return (int64_t)sb.jnnz * 8 + (int64_t)sb.n_tiles * 520;          // values + 64 masks and an offset per tile
+    if (sb.dense) return (int64_t)sb.n_tiles * 4096 * 8;                             // (spread: this rank's tiles)
+    return (int64_t)sb.nnz * 8 + (int64_t)sb.n_loc * ((sb.n_glob + 63) / 64) * 8;    // packed values + bitmap
 }
 
 extern "C" int kmcf_tstate_info(const kmcf_tstate *t, kmcf_tstate_info_t *info)
@@ -1460,10 +1549,7 @@ extern "C" int kmcf_tstate_info(const kmcf_tstate *t, kmcf_tstate_info_t *info)
     info->tunnel_first = t->assembled ? t->sub.row0 : 0;
     info->nnz_tunnel = t->assembled ? t->sub.nnz : 0;
     info->tunnel_dense = t->assembled && t->sub.dense ? (t->sub.jagged ? 2 : 1) : 0;
-    info->tunnel_bytes = !t->assembled ? 0
-                         : t->sub.jagged ? (int64_t)t->sub.jnnz * 8 + (int64_t)t->sub.n_tiles * 520
-                         : t->sub.dense ? (int64_t)t->sub.n_tiles * 4096 * 8
-                                        : (int64_t)t->sub.nnz * 8 + (int64_t)t->sub.n_loc * ((t->sub.n_glob + 63) / 64) * 8;
+    info->tunnel_bytes = t->assembled ? tunnel_bytes(t->sub) : 0;
     return KMCF_OK;
 }
 
@@ -1483,14 +1569,14 @@ extern "C" int kmcf_tstate_atom_sites(const kmcf_tstate *t, int *h_atom_site)
     return KMCF_OK;
 }
 
-
+// ---------------------------------------------------------------- the tile forms: one application
 // launches of the dense symmetric operator (dynamic LDS beyond 64 KB needs the attribute once per kernel)
 template <int MODE>
 static int symm_launch(kmcf_subop &sb, const double *x, double Vd, hipStream_t st, const kmcf_scalars *S = nullptr, int check_done = 0)
 {
     // (the attribute is set per launch: it is per device, and in-process groups launch from several host threads)
     const size_t lds = (size_t)4 * SYM_WAVE_DOUBLES * sizeof(double);
-    const int grid = std::max(1, std::min((sb.n_strips + 3) / 4, 8192));
+    const int grid = strip_grid(sb.n_strips);
     if (sb.jagged) {
         KMCF_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(sub_symj_kernel<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         sub_symj_kernel<MODE><<<grid, KMCF_BLOCK, lds, st>>>(sb.n_strips, sb.d_strips, sb.d_jmask, sb.d_jvoff, sb.d_jval, x, Vd, sb.d_rowpart, sb.d_colpart,
@@ -1526,130 +1612,160 @@ static int symm_spread_finish(kmcf_comm *c, kmcf_subop &sb, int ns, int row0, co
     return KMCF_OK;
 }
 
-// strips, tiles, values, diagonal of the dense symmetric storage (after the tunnel points are known): of one rank, or
-// (sb.spread) this rank's share of a group's
-static int symm_setup(kmcf_tstate *t)
+// Who applies the tiles: every rank of a group that deals them (also one without points of its own), one rank only
+// with points of its own.
+static bool symm_applies(const kmcf_subop &sb) { return sb.dense && (sb.spread || sb.n_loc > 0); }
+
+// One application of the tiles to sb.d_xsub: the tile kernel, then the parts added per block row (one rank) or per
+// rank, gathered and combined (group).  MODE 0: y[rows[i]] += the sums of points row0 ... row0 + ns (rows == nullptr:
+// y[i]), DOT: with the p.Ap partials into part; MODE 1 (the power pass, bias Vd): into y and y2.
+template <int MODE, bool DOT>
+static int symm_apply(kmcf_comm *c, kmcf_subop &sb, int ns, int row0, const int *rows, const double *p, double *y, double *y2,
+                      double *part, const kmcf_scalars *S, int chk, double Vd = 0.0)
+{
+    KMCF_TRY(symm_launch<MODE>(sb, sb.d_xsub, Vd, c->stream, S, chk));
+    if (sb.spread) return symm_spread_finish<MODE, DOT>(c, sb, ns, row0, rows, p, y, y2, part, S, chk);
+    sub_symm_reduce_kernel<MODE, DOT><<<sb.nb, KMCF_BLOCK, 0, c->stream>>>(sb.n_glob, sb.nb, sb.d_strip_first, sb.d_rowpart, sb.d_colpart, rows, p,
+                                                                           y, y2, part, S, chk);
+    KMCF_HIP(hipGetLastError());
+    return KMCF_OK;
+}
+
+// ---------------------------------------------------------------- the tile forms: setup (after the tunnel points are known)
+// strips of one rank, or (sb.spread) this rank's share of a group's: dealt, uploaded, their buffers sized
+static int symm_deal_upload(kmcf_tstate *t)
 {
     kmcf_subop &sb = t->sub;
     kmcf_comm *c = t->comm;
     hipStream_t st = c->stream;
-    const kmcf_current_params_t *p = &t->par;
-    const int n_t = sb.n_glob, nb = (n_t + 63) / 64;
+    const int nb = sb.nb = (sb.n_glob + 63) / 64;
     const int P = sb.spread ? c->nranks : 1, rank = sb.spread ? c->rank : 0;
-    sb.nb = nb;
     sb.n_tiles_glob = (long long)nb * (nb + 1) / 2;
-    KMCF_CHECK(sb.n_tiles_glob < (long long)INT32_MAX, KMCF_ERR_ARG, "tunnel block of %d points: tile index exceeds int32", n_t);
-    const int strip_len = std::max(1, kmcf_opt_int(c, KNOB_SUB_STRIP, 16));
-    std::vector<int4> strips;
-    std::vector<int> first((size_t)nb + 1, 0), tile_local;
-    if (sb.spread) tile_local.assign((size_t)sb.n_tiles_glob, -1);
-    // the deal: strip after strip (block rows ascending, then columns) to the rank that holds the fewest tiles so far,
-    // the lowest such rank -- within a strip's length of even, whatever the mix of full and ragged strips
-    std::vector<long long> held((size_t)P, 0);
-    long long n_mine = 0;
-    for (int I = 0; I < nb; ++I) {
-        first[I] = (int)strips.size();
-        for (int J = I; J < nb; J += strip_len) {
-            const int len = std::min(strip_len, nb - J);
-            const int owner = (int)(std::min_element(held.begin(), held.end()) - held.begin());
-            held[owner] += len;
-            if (owner != rank) continue;
-            strips.push_back(make_int4(I, J, len, (int)(sb.spread ? n_mine : symm_tile_index(nb, I, J))));
-            if (sb.spread)
-                for (int q = 0; q < len; ++q) tile_local[(size_t)symm_tile_index(nb, I, J + q)] = (int)(n_mine + q);
-            n_mine += len;
-        }
-    }
-    first[nb] = (int)strips.size();
-    sb.n_tiles = n_mine;
-    sb.n_strips = (int)strips.size();
+    KMCF_CHECK(sb.n_tiles_glob < (long long)INT32_MAX, KMCF_ERR_ARG, "tunnel block of %d points: tile index exceeds int32", sb.n_glob);
+    const kmcf_strip_deal deal = kmcf_deal_strips(nb, std::max(1, kmcf_opt_int(c, KNOB_SUB_STRIP, 16)), P, rank, sb.spread);
+    sb.n_tiles = deal.n_tiles;
+    sb.n_strips = (int)deal.strips.size();
     if (!sb.jagged) KMCF_TRY(ensure(&sb.d_tiles, &sb.cap_tiles, (size_t)std::max<long long>(sb.n_tiles, 1) * 4096));
-    KMCF_TRY(ensure(&sb.d_strips, &sb.cap_strips, strips.size() + 1));
-    KMCF_TRY(ensure(&sb.d_strip_first, &sb.cap_sf, first.size()));
+    KMCF_TRY(ensure(&sb.d_strips, &sb.cap_strips, deal.strips.size() + 1));
+    KMCF_TRY(ensure(&sb.d_strip_first, &sb.cap_sf, deal.first.size()));
     KMCF_TRY(ensure(&sb.d_rowpart, &sb.cap_rowpart, (size_t)(sb.n_strips + 1) * 128));
     KMCF_TRY(ensure(&sb.d_colpart, &sb.cap_colpart, (size_t)std::max<long long>(sb.n_tiles, 1) * 128));
-    if (!strips.empty()) KMCF_HIP(hipMemcpyAsync(sb.d_strips, strips.data(), strips.size() * sizeof(int4), hipMemcpyHostToDevice, st));
-    KMCF_HIP(hipMemcpyAsync(sb.d_strip_first, first.data(), first.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    if (!deal.strips.empty())
+        KMCF_HIP(hipMemcpyAsync(sb.d_strips, deal.strips.data(), deal.strips.size() * sizeof(kmcf_strip), hipMemcpyHostToDevice, st));
+    KMCF_HIP(hipMemcpyAsync(sb.d_strip_first, deal.first.data(), deal.first.size() * sizeof(int), hipMemcpyHostToDevice, st));
     if (sb.spread) {
-        KMCF_TRY(ensure(&sb.d_tile_local, &sb.cap_tile_local, tile_local.size() + 1));
+        KMCF_TRY(ensure(&sb.d_tile_local, &sb.cap_tile_local, deal.tile_local.size() + 1));
         KMCF_TRY(ensure(&sb.d_ypart, &sb.cap_ypart, (size_t)2 * P * 64 * nb));
-        KMCF_HIP(hipMemcpyAsync(sb.d_tile_local, tile_local.data(), tile_local.size() * sizeof(int), hipMemcpyHostToDevice, st));
+        KMCF_HIP(hipMemcpyAsync(sb.d_tile_local, deal.tile_local.data(), deal.tile_local.size() * sizeof(int), hipMemcpyHostToDevice, st));
         for (int w = 1; w <= 2; ++w) {                              // slices of the partials' all-gather: one / two sums per point
             sb.y_counts[w - 1].assign((size_t)P, w * 64 * nb);
             sb.y_displs[w - 1].resize((size_t)P);
             for (int q = 0; q < P; ++q) sb.y_displs[w - 1][q] = q * w * 64 * nb;
         }
     }
-    KMCF_HIP(hipStreamSynchronize(st));                            // (the host vectors go out of scope)
-    const int grid = std::max(1, std::min((sb.n_strips + 3) / 4, 8192));
-    if (sb.jagged) {
-        // masks tile-major, entries per tile -> first value of every tile -> values in layer order
-        KMCF_TRY(ensure(&sb.d_jmask, &sb.cap_jmask, (size_t)sb.n_tiles * 64));
-        KMCF_TRY(ensure(&sb.d_jcnt, &sb.cap_jcnt, (size_t)sb.n_tiles + 1));
-        KMCF_TRY(ensure(&sb.d_jvoff, &sb.cap_jvoff, (size_t)sb.n_tiles + 2));
-        symj_mask_kernel<<<grid, KMCF_BLOCK, 0, st>>>(sb.n_strips, sb.d_strips, n_t, sb.n_groups, sb.d_mask, sb.d_jmask, sb.d_jcnt);
-        long long *pin_j = reinterpret_cast<long long *>(t->h_pin + 6);
-        // (a tile holds at most 4096 entries: the 256 counts of one pass of the scan add up to 2^20 at most)
-        kmcf_scan_counts_kernel<long long><<<1, KMCF_BLOCK, 0, st>>>((int)sb.n_tiles, sb.d_jcnt, sb.d_jvoff, 0);
-        KMCF_HIP(hipGetLastError());
-        KMCF_HIP(hipMemcpyAsync(pin_j, sb.d_jvoff + sb.n_tiles, sizeof(long long), hipMemcpyDeviceToHost, st));
-        KMCF_HIP(hipStreamSynchronize(st));
-        sb.jnnz = *pin_j;
-        KMCF_TRY(ensure(&sb.d_jval, &sb.cap_jval, (size_t)sb.jnnz + 64));
-        symj_fill_kernel<<<grid, KMCF_BLOCK, 0, st>>>(sb.n_strips, sb.d_strips, n_t, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz, t->d_tcb, p->tol, p->m_e,
-                                                     p->V0, sb.d_jmask, sb.d_jvoff, sb.d_jval);
-    } else {
-        tunnel_dense_fill_kernel<<<grid, KMCF_BLOCK, 0, st>>>(sb.n_strips, sb.d_strips, n_t, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz, t->d_tcb, t->nn_dist,
-                                                             p->tol, p->m_e, p->V0, sb.d_tiles);
-    }
+    KMCF_HIP(hipStreamSynchronize(st));                            // (the deal goes out of scope)
+    return KMCF_OK;
+}
+
+// jagged tiles: masks tile-major, entries per tile -> first value of every tile -> values in layer order
+static int symm_fill_jagged(kmcf_tstate *t)
+{
+    kmcf_subop &sb = t->sub;
+    hipStream_t st = t->comm->stream;
+    const kmcf_current_params_t *p = &t->par;
+    const int grid = strip_grid(sb.n_strips);
+    KMCF_TRY(ensure(&sb.d_jmask, &sb.cap_jmask, (size_t)sb.n_tiles * 64));
+    KMCF_TRY(ensure(&sb.d_jcnt, &sb.cap_jcnt, (size_t)sb.n_tiles + 1));
+    KMCF_TRY(ensure(&sb.d_jvoff, &sb.cap_jvoff, (size_t)sb.n_tiles + 2));
+    symj_mask_kernel<<<grid, KMCF_BLOCK, 0, st>>>(sb.n_strips, sb.d_strips, sb.n_glob, sb.n_groups, sb.d_mask, sb.d_jmask, sb.d_jcnt);
+    // (a tile holds at most 4096 entries: the 256 counts of one pass of the scan add up to 2^20 at most)
+    kmcf_scan_counts_kernel<long long><<<1, KMCF_BLOCK, 0, st>>>((int)sb.n_tiles, sb.d_jcnt, sb.d_jvoff, 0);
     KMCF_HIP(hipGetLastError());
-    // diagonal = -(row sums): one application to the vector of ones (the diagonal entries are still 0); spread: of ALL
-    // points on every rank (a rank sets the diagonal of the diagonal tiles it holds)
+    KMCF_HIP(hipMemcpyAsync(&t->h_pin->jnnz, sb.d_jvoff + sb.n_tiles, sizeof(long long), hipMemcpyDeviceToHost, st));
+    KMCF_HIP(hipStreamSynchronize(st));
+    sb.jnnz = t->h_pin->jnnz;
+    KMCF_TRY(ensure(&sb.d_jval, &sb.cap_jval, (size_t)sb.jnnz + 64));
+    symj_fill_kernel<<<grid, KMCF_BLOCK, 0, st>>>(sb.n_strips, sb.d_strips, sb.n_glob, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz, t->d_tcb, p->tol, p->m_e,
+                                                 p->V0, sb.d_jmask, sb.d_jvoff, sb.d_jval);
+    KMCF_HIP(hipGetLastError());
+    return KMCF_OK;
+}
+
+static int symm_fill_dense(kmcf_tstate *t)
+{
+    kmcf_subop &sb = t->sub;
+    const kmcf_current_params_t *p = &t->par;
+    tunnel_dense_fill_kernel<<<strip_grid(sb.n_strips), KMCF_BLOCK, 0, t->comm->stream>>>(sb.n_strips, sb.d_strips, sb.n_glob, t->d_tinfo, t->d_tx, t->d_ty,
+                                                                                          t->d_tz, t->d_tcb, t->nn_dist, p->tol, p->m_e, p->V0, sb.d_tiles);
+    KMCF_HIP(hipGetLastError());
+    return KMCF_OK;
+}
+
+// diagonal = -(row sums): one application to the vector of ones (the diagonal entries are still 0); spread: of ALL
+// points on every rank (a rank sets the diagonal of the diagonal tiles it holds)
+static int symm_diagonal(kmcf_tstate *t)
+{
+    kmcf_subop &sb = t->sub;
+    hipStream_t st = t->comm->stream;
+    const int n_t = sb.n_glob, nb = sb.nb;
     fill_kernel<<<kmcf_grid1d(64 * nb), KMCF_BLOCK, 0, st>>>(64 * nb, sb.d_xsub, 1.0);
     KMCF_HIP(hipMemsetAsync(t->d_tdiag, 0, (size_t)n_t * sizeof(double), st));
-    KMCF_TRY(symm_launch<0>(sb, sb.d_xsub, 0.0, st));
-    if (sb.spread)
-        KMCF_TRY((symm_spread_finish<0, false>(c, sb, n_t, 0, nullptr, nullptr, t->d_tdiag, nullptr, nullptr, nullptr, 0)));
-    else
-        sub_symm_reduce_kernel<0, false><<<nb, KMCF_BLOCK, 0, st>>>(n_t, nb, sb.d_strip_first, sb.d_rowpart, sb.d_colpart, nullptr, nullptr,
-                                                                            t->d_tdiag, nullptr, nullptr, nullptr, 0);
+    KMCF_TRY((symm_apply<0, false>(t->comm, sb, n_t, 0, nullptr, nullptr, t->d_tdiag, nullptr, nullptr, nullptr, 0)));
     if (sb.jagged) symj_set_diag_kernel<<<std::max(1, (nb + 3) / 4), KMCF_BLOCK, 0, st>>>(n_t, nb, t->d_tdiag, t->d_tdiag, sb.d_jmask, sb.d_jvoff, sb.d_jval);
     else symm_set_diag_kernel<<<kmcf_grid1d(n_t), KMCF_BLOCK, 0, st>>>(n_t, nb, t->d_tdiag, t->d_tdiag, sb.d_tiles, sb.spread ? sb.d_tile_local : nullptr);
     KMCF_HIP(hipMemsetAsync(sb.d_xsub, 0, (size_t)64 * nb * sizeof(double), st));      // the pad behind the last point stays 0
     KMCF_HIP(hipGetLastError());
-    // partials of the p.Ap sum: one per block row (reduce kernel) / per 256 own points (combine kernel)
-    sb.grid = sb.spread ? (sb.n_loc + KMCF_BLOCK - 1) / KMCF_BLOCK : nb;
     return KMCF_OK;
 }
 
-static int t_assemble_async(kmcf_tstate *t, const int *d_site_element, const int *d_site_charge, const double *d_site_CB_edge,
-                            const int *d_metals, int num_metals, const kmcf_current_params_t *p)
+static int symm_setup(kmcf_tstate *t)
 {
-    kmcf_comm *c = t->comm;
-    kmcf_matrix *m = t->T;
-    hipStream_t st = c->stream;
-    const int Na = t->N_atom, n_loc = m->n_loc, P = c->nranks, rank = c->rank;
-    t->par = *p;
-    t->assembled = false;
-    // 1. atom arrays (update_atom_arrays, :1341-1365) + invariance of the atom set
+    KMCF_TRY(symm_deal_upload(t));
+    KMCF_TRY(t->sub.jagged ? symm_fill_jagged(t) : symm_fill_dense(t));
+    return symm_diagonal(t);
+}
+
+// ---------------------------------------------------------------- one assembly, stage by stage (t->par holds the parameters)
+// 1. atom arrays (update_atom_arrays, :1341-1365) + invariance of the atom set (the verdict is read in stage 3)
+static int asm_atoms(kmcf_tstate *t, const int *d_site_element, const int *d_site_charge, const double *d_site_CB_edge,
+                     const int *d_metals, int num_metals)
+{
+    hipStream_t st = t->comm->stream;
+    const int Na = t->N_atom;
     KMCF_HIP(hipMemsetAsync(t->d_err, 0, sizeof(int), st));
     check_atom_set_kernel<<<kmcf_grid1d(t->N), KMCF_BLOCK, 0, st>>>(t->N, d_site_element, t->d_site_is_atom, t->d_err);
     gather_atoms_kernel<<<kmcf_grid1d(Na), KMCF_BLOCK, 0, st>>>(Na, t->d_atom_site, d_site_element, d_site_charge, d_site_CB_edge, d_metals,
                                                            num_metals, t->d_ael, t->d_ach, t->d_acb, t->d_acls);
     KMCF_HIP(hipGetLastError());
-    // 2. neighbour values + diagonal (one pass)
-    if (n_loc > 0) {
-        const int n_cols = n_loc + m->n_halo;
-        t_cls_col_kernel<<<kmcf_grid1d(n_cols), KMCF_BLOCK, 0, st>>>(n_cols, t->d_col_node, t->d_acls, t->d_cls_col);
-        const double dict[3] = {-p->high_G, -p->low_G, -p->loop_G};
-        KMCF_TRY(kmcf_matrix_set_dictionary(m, dict, 3));
-        constexpr int LPR = 16;
-        t_assemble_kernel<LPR><<<kmcf_grid1d((int64_t)n_loc * LPR), KMCF_BLOCK, 0, st>>>(
-            n_loc, m->d_row_ptr, m->d_col, m->d_val, t->d_diag_pos, t->d_ground, t->d_cls_col, p->high_G, p->low_G, p->loop_G,
-            t->d_diag, m->coded ? m->d_idx16 : nullptr, m->coded ? m->d_diagv : nullptr, m->n_short);
-        KMCF_HIP(hipGetLastError());
-    }
-    // 3. tunnel points of all ranks (get_is_tunnel_mpi + copy_if + MPI_Allgatherv, initialize_sparsity_T.cu:739-787)
+    return KMCF_OK;
+}
+
+// 2. neighbour values + their diagonal (one pass), the dictionary of the coded SpMV
+static int asm_neighbour_values(kmcf_tstate *t)
+{
+    kmcf_matrix *m = t->T;
+    hipStream_t st = t->comm->stream;
+    const kmcf_current_params_t *p = &t->par;
+    const int n_loc = m->n_loc, n_cols = n_loc + m->n_halo;
+    if (n_loc == 0) return KMCF_OK;
+    t_cls_col_kernel<<<kmcf_grid1d(n_cols), KMCF_BLOCK, 0, st>>>(n_cols, t->d_col_node, t->d_acls, t->d_cls_col);
+    const double dict[3] = {-p->high_G, -p->low_G, -p->loop_G};
+    KMCF_TRY(kmcf_matrix_set_dictionary(m, dict, 3));
+    constexpr int LPR = 16;
+    t_assemble_kernel<LPR><<<kmcf_grid1d((int64_t)n_loc * LPR), KMCF_BLOCK, 0, st>>>(
+        n_loc, m->d_row_ptr, m->d_col, m->d_val, t->d_diag_pos, t->d_ground, t->d_cls_col, p->high_G, p->low_G, p->loop_G,
+        t->d_diag, m->coded ? m->d_idx16 : nullptr, m->coded ? m->d_diagv : nullptr, m->n_short);
+    KMCF_HIP(hipGetLastError());
+    return KMCF_OK;
+}
+
+// 3. tunnel points of all ranks (get_is_tunnel_mpi + copy_if + MPI_Allgatherv, initialize_sparsity_T.cu:739-787): count,
+// scan, scatter; the one synchronising read-back (their number, the atom-set verdict); their atom indices on the host
+static int asm_tunnel_points(kmcf_tstate *t, const int *d_metals, int num_metals)
+{
+    hipStream_t st = t->comm->stream;
+    const kmcf_current_params_t *p = &t->par;
+    const int Na = t->N_atom;
     const int n_scan = Na - 1;                                        // atoms 0 .. N_atom - 2 are matrix rows
     const int nblk = (Na + KMCF_SCAN_TILE - 1) / KMCF_SCAN_TILE;
     tunnel_count_kernel<<<nblk, KMCF_BLOCK, 0, st>>>(n_scan, t->d_ael, t->d_ax, p->contact_x_lo, p->contact_x_hi, t->d_blk);
@@ -1658,17 +1774,26 @@ static int t_assemble_async(kmcf_tstate *t, const int *d_site_element, const int
                                                        p->contact_x_lo, p->contact_x_hi, t->n_layers, t->n_inj, t->n_ext, t->d_blk + nblk,
                                                        t->d_tidx, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz, t->d_tcb);
     KMCF_HIP(hipGetLastError());
-    KMCF_HIP(hipMemcpyAsync(t->h_pin, t->d_blk + 2 * nblk, sizeof(int), hipMemcpyDeviceToHost, st));   // total = n_t
-    KMCF_HIP(hipMemcpyAsync(t->h_pin + 1, t->d_err, sizeof(int), hipMemcpyDeviceToHost, st));
+    KMCF_HIP(hipMemcpyAsync(&t->h_pin->n_t, t->d_blk + 2 * nblk, sizeof(int), hipMemcpyDeviceToHost, st));   // total = n_t
+    KMCF_HIP(hipMemcpyAsync(&t->h_pin->err, t->d_err, sizeof(int), hipMemcpyDeviceToHost, st));
     KMCF_HIP(hipStreamSynchronize(st));
-    KMCF_CHECK(t->h_pin[1] == 0, KMCF_ERR_STATE,
+    KMCF_CHECK(t->h_pin->err == 0, KMCF_ERR_STATE,
                "kmcf_t_assemble: the set of atom sites differs from the one at kmcf_initialize_sparsity_T (call it again)");
-    const int n_t = t->h_pin[0];
+    const int n_t = t->h_pin->n_t;
     t->h_tidx.resize((size_t)n_t);
     if (n_t > 0) KMCF_HIP(hipMemcpy(t->h_tidx.data(), t->d_tidx, (size_t)n_t * sizeof(int), hipMemcpyDeviceToHost));
-    // counts_subblock / displ_subblock (:752-758): tunnel points by owner of their matrix row (atom index + 2)
+    return KMCF_OK;
+}
+
+// 4. counts_subblock / displ_subblock (:752-758): tunnel points by owner of their matrix row (atom index + 2); the
+// buffers sized by this rank's share; the storage form reset to the bitmap
+static int asm_partition(kmcf_tstate *t)
+{
+    const kmcf_matrix *m = t->T;
     kmcf_subop &sb = t->sub;
-    for (int q = 0; q < P; ++q) {
+    hipStream_t st = t->comm->stream;
+    const int n_t = (int)t->h_tidx.size(), rank = t->comm->rank;
+    for (int q = 0; q < t->comm->nranks; ++q) {
         const int lo = m->displs[q], hi = m->displs[q] + m->counts[q];
         const int b = (int)(std::lower_bound(t->h_tidx.begin(), t->h_tidx.end(), lo - 2) - t->h_tidx.begin());
         const int e = (int)(std::lower_bound(t->h_tidx.begin(), t->h_tidx.end(), hi - 2) - t->h_tidx.begin());
@@ -1688,88 +1813,115 @@ static int t_assemble_async(kmcf_tstate *t, const int *d_site_element, const int
     KMCF_TRY(ensure(&sb.d_xsub, &sb.cap_x, (size_t)n_t + 320));          // + 256: the 4-group unroll reads x_sub[j + 192] only when set
     KMCF_TRY(ensure(&t->d_rowcnt, &t->cap_rowcnt, (size_t)ns + 1));
     KMCF_TRY(ensure(&t->d_tdiag, &t->cap_tdiag, (size_t)n_t + 1));       // (per LOCAL point; the spread tiles: per point of all ranks)
-    const int wpb = KMCF_BLOCK / 64;
-    const int wgrid = std::max(1, std::min((ns + wpb - 1) / wpb, KMCF_MAX_PARTIALS));
-    sb.grid = ns > 0 ? wgrid : 0;
     sb.dense = sb.jagged = sb.spread = false;
-    if (ns > 0) {
-        // a row holds at most n_t entries, and the scan adds the 256 counts of one pass in an int
-        KMCF_CHECK((int64_t)n_t * KMCF_BLOCK <= (int64_t)INT32_MAX, KMCF_ERR_ARG,
-                   "tunnel block: %d tunnel points exceed the row-offset scan's range (256 rows of that many entries in an int)", n_t);
-        sub_rows_kernel<<<kmcf_grid1d(ns), KMCF_BLOCK, 0, st>>>(ns, sb.row0, t->d_tidx, m->row0, t->d_inv_perm, sb.d_rows);
-        tunnel_mask_kernel<<<wgrid, KMCF_BLOCK, 0, st>>>(ns, sb.row0, n_t, ng, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz, t->d_tcb, t->nn_dist,
-                                                         p->tol, sb.d_mask, t->d_rowcnt);
-        long long *pin_nnz = reinterpret_cast<long long *>(t->h_pin + 2);
-        kmcf_scan_counts_kernel<long long><<<1, KMCF_BLOCK, 0, st>>>(ns, t->d_rowcnt, sb.d_voff, 0);
-        KMCF_HIP(hipGetLastError());
-        KMCF_HIP(hipMemcpyAsync(pin_nnz, sb.d_voff + ns, sizeof(long long), hipMemcpyDeviceToHost, st));
-        KMCF_HIP(hipStreamSynchronize(st));
-        sb.nnz = *pin_nnz;
+    return KMCF_OK;
+}
+
+// 5. the bitmap of this rank's rows (every form keeps it: the tiles are filled from it, kmcf_current_map walks it) and
+// the scan of its row counts; the second synchronising read-back: the rows' entries
+static int asm_bitmap_pattern(kmcf_tstate *t)
+{
+    kmcf_subop &sb = t->sub;
+    hipStream_t st = t->comm->stream;
+    const int ns = sb.n_loc, n_t = sb.n_glob;
+    if (ns == 0) return KMCF_OK;
+    // a row holds at most n_t entries, and the scan adds the 256 counts of one pass in an int
+    KMCF_CHECK((int64_t)n_t * KMCF_BLOCK <= (int64_t)INT32_MAX, KMCF_ERR_ARG,
+               "tunnel block: %d tunnel points exceed the row-offset scan's range (256 rows of that many entries in an int)", n_t);
+    sub_rows_kernel<<<kmcf_grid1d(ns), KMCF_BLOCK, 0, st>>>(ns, sb.row0, t->d_tidx, t->T->row0, t->d_inv_perm, sb.d_rows);
+    tunnel_mask_kernel<<<wave_row_grid(ns), KMCF_BLOCK, 0, st>>>(ns, sb.row0, n_t, sb.n_groups, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz, t->d_tcb,
+                                                                 t->nn_dist, t->par.tol, sb.d_mask, t->d_rowcnt);
+    kmcf_scan_counts_kernel<long long><<<1, KMCF_BLOCK, 0, st>>>(ns, t->d_rowcnt, sb.d_voff, 0);
+    KMCF_HIP(hipGetLastError());
+    KMCF_HIP(hipMemcpyAsync(&t->h_pin->nnz, sb.d_voff + ns, sizeof(long long), hipMemcpyDeviceToHost, st));
+    KMCF_HIP(hipStreamSynchronize(st));
+    sb.nnz = t->h_pin->nnz;
+    return KMCF_OK;
+}
+
+// 6. the storage form (the rule: kmcf_subplan.hpp).  A group votes: one all-gather of (entries of my rows, my share of
+// the tiles fits), after which every rank decides alike.
+static int asm_choose_storage(kmcf_tstate *t)
+{
+    kmcf_subop &sb = t->sub;
+    kmcf_comm *c = t->comm;
+    hipStream_t st = c->stream;
+    const int n_t = sb.n_glob, P = c->nranks;
+    if (n_t == 0) return KMCF_OK;
+    const char *env = kmcf_opt(c, KNOB_SUB_DENSE);
+    const int override = env ? atoi(env) : KMCF_SUB_AUTO;
+    auto free_bytes = [](size_t *fr) { size_t tot = 0; return hipMemGetInfo(fr, &tot) == hipSuccess; };
+    if (P == 1) {
+        const kmcf_sub_form f = kmcf_sub_form_one_rank(n_t, sb.nnz, sb.cap_tiles, sb.cap_jval, override, free_bytes);
+        sb.dense = f.dense;
+        sb.jagged = f.jagged;
+        return KMCF_OK;
     }
-    // Storage of the block: dense symmetric tiles when the block is more than a QUARTER full, else the bitmap + packed
-    // values.  In bytes the tiles (4 n^2) win from half full on (8 d n^2 + n^2 / 8 for the bitmap form); in time from a
-    // quarter on: the tile kernel streams at 5.3 TB/s, the bitmap kernel -- a load of 64 x d values per mask word -- at 2.7
-    // (the reference's contact window at 40 nm, 44 % full: 3.8 against 6.3 ms per application).  Not when the tiles would
-    // take more than 60 % of the free device memory.
-    // Round 4: the same tiles holding only their ENTRIES (jagged: 4 B per entry of the full block + 1 bit per position,
-    // the same sums bit for bit, 2.2 x less memory at 44 % -- but bound by its instruction count, not its bytes: the
-    // reference's window on the 4 x 4-cell device, 17 722 points, 44 % full: dense tiles 0.28, jagged tiles 0.41,
-    // bitmap 0.49 ms per iteration) where the dense tiles do not fit the device's memory (one rank).
-    // A rank GROUP (round 4): the dense tiles' strips dealt to the ranks (kmcf_subop::spread) under the same rule,
-    // weighed on the whole block -- the ranks agree through one small all-gather (entries of their rows, and whether
-    // their share of the tiles fits) so that all of them take the same branch.
-    // KMCF_SUB_DENSE = 0 bitmap / 1 dense tiles / 2 jagged tiles (one rank; a group: dense tiles) overrides.
-    if (n_t > 0) {
-        const long long nbl = (n_t + 63) / 64, all_tiles = nbl * (nbl + 1) / 2;
-        const double nn2 = (double)n_t * (double)n_t, nbt = nn2 / 8192;
-        const char *env = kmcf_opt(c, KNOB_SUB_DENSE);
-        if (P == 1) {
-            sb.dense = n_t >= 2048 && 4.0 * (double)sb.nnz > nn2;
-            if (sb.dense && sb.cap_tiles < (size_t)all_tiles * 4096) {
-                size_t fr = 0, tot = 0;
-                if (hipMemGetInfo(&fr, &tot) == hipSuccess && 4.0 * nn2 + 1024.0 * nbt > 0.6 * (double)fr) {
-                    sb.jagged = 4.0 * (double)sb.nnz + 1544.0 * nbt <= 0.6 * (double)fr + 8.0 * (double)sb.cap_jval;
-                    sb.dense = sb.jagged;
-                }
-            }
-            if (env) { sb.dense = atoi(env) != 0; sb.jagged = sb.dense && atoi(env) == 2; }
-            if (nbl > KMCF_MAX_PARTIALS) sb.dense = sb.jagged = false;       // (one p.Ap partial per block row)
-        } else if (!(env && atoi(env) == 0)) {
-            // what this rank would hold: every P-th strip; 32 KB a tile + its parts
-            const double share = ((double)all_tiles / P + nbl) * (32768.0 + 1024.0);
-            size_t fr = 0, tot = 0;
-            const bool fits = sb.cap_tiles * sizeof(double) >= share || (hipMemGetInfo(&fr, &tot) == hipSuccess && share <= 0.6 * (double)fr);
-            double *h_ag = reinterpret_cast<double *>(t->h_agree);
-            h_ag[0] = (double)sb.nnz; h_ag[1] = fits ? 1.0 : 0.0;
-            KMCF_HIP(hipMemcpyAsync(t->d_agree + 2 * rank, h_ag, 2 * sizeof(double), hipMemcpyHostToDevice, st));
-            std::vector<int> cnt((size_t)P, 2), dsp((size_t)P);
-            for (int q = 0; q < P; ++q) dsp[q] = 2 * q;
-            KMCF_TRY(kmcf_comm_allgatherv_double(c, t->d_agree, cnt.data(), dsp.data()));
-            KMCF_HIP(hipMemcpyAsync(h_ag + 2, t->d_agree, (size_t)2 * P * sizeof(double), hipMemcpyDeviceToHost, st));
-            KMCF_HIP(hipStreamSynchronize(st));
-            double nnz_all = 0.0;
-            bool fit_all = true;
-            for (int q = 0; q < P; ++q) { nnz_all += h_ag[2 + 2 * q]; fit_all = fit_all && h_ag[3 + 2 * q] != 0.0; }
-            sb.dense = sb.spread = fit_all && (ns + KMCF_BLOCK - 1) / KMCF_BLOCK <= KMCF_MAX_PARTIALS &&
-                                   (env ? atoi(env) != 0 : n_t >= 2048 && 4.0 * nnz_all > nn2);
-        }
-        if (sb.dense) {
-            KMCF_TRY(symm_setup(t));
-        } else if (ns > 0) {
-            KMCF_TRY(ensure(&sb.d_val, &sb.cap_val, (size_t)sb.nnz + 64));
-            tunnel_value_kernel<<<wgrid, KMCF_BLOCK, 0, st>>>(ns, sb.row0, ng, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz, t->d_tcb, t->nn_dist, p->tol,
-                                                              p->m_e, p->V0, sb.d_mask, sb.d_voff, sb.d_val, t->d_tdiag);
-            KMCF_HIP(hipGetLastError());
-        }
-    }
-    // 4. preconditioner and right-hand side
-    if (n_loc > 0) {
-        copy_diag_rhs_kernel<<<kmcf_grid1d(n_loc), KMCF_BLOCK, 0, st>>>(n_loc, t->d_diag, t->d_diag_tot, t->d_col_node, p->loop_G * p->Vd, t->d_rhs);
-        if (ns > 0) add_tunnel_diag_kernel<<<kmcf_grid1d(ns), KMCF_BLOCK, 0, st>>>(ns, sb.d_rows, t->d_tdiag + (sb.spread ? sb.row0 : 0), t->d_diag_tot);
-        invert_kernel<<<kmcf_grid1d(n_loc), KMCF_BLOCK, 0, st>>>(n_loc, t->d_diag_tot, m->d_dinv);
+    const kmcf_sub_vote vote = kmcf_sub_group_vote(n_t, P, sb.cap_tiles, override, free_bytes);
+    if (vote == KMCF_SUB_NO_VOTE) return KMCF_OK;
+    double *h_ag = t->h_agree;
+    h_ag[0] = (double)sb.nnz; h_ag[1] = vote == KMCF_SUB_FITS ? 1.0 : 0.0;
+    KMCF_HIP(hipMemcpyAsync(t->d_agree + 2 * c->rank, h_ag, 2 * sizeof(double), hipMemcpyHostToDevice, st));
+    std::vector<int> cnt((size_t)P, 2), dsp((size_t)P);
+    for (int q = 0; q < P; ++q) dsp[q] = 2 * q;
+    KMCF_TRY(kmcf_comm_allgatherv_double(c, t->d_agree, cnt.data(), dsp.data()));
+    KMCF_HIP(hipMemcpyAsync(h_ag + 2, t->d_agree, (size_t)2 * P * sizeof(double), hipMemcpyDeviceToHost, st));
+    KMCF_HIP(hipStreamSynchronize(st));
+    double nnz_all = 0.0;
+    bool fit_all = true;
+    for (int q = 0; q < P; ++q) { nnz_all += h_ag[2 + 2 * q]; fit_all = fit_all && h_ag[3 + 2 * q] != 0.0; }
+    sb.dense = sb.spread = kmcf_sub_group_spread(n_t, sb.n_loc, nnz_all, fit_all, override);
+    return KMCF_OK;
+}
+
+// 7. the values in the form chosen, the tunnel diagonal with them; the p.Ap partials of one application (sb.grid)
+static int asm_values(kmcf_tstate *t)
+{
+    kmcf_subop &sb = t->sub;
+    const kmcf_current_params_t *p = &t->par;
+    const int ns = sb.n_loc;
+    if (sb.dense) {
+        KMCF_TRY(symm_setup(t));
+    } else if (ns > 0) {
+        KMCF_TRY(ensure(&sb.d_val, &sb.cap_val, (size_t)sb.nnz + 64));
+        tunnel_value_kernel<<<wave_row_grid(ns), KMCF_BLOCK, 0, t->comm->stream>>>(ns, sb.row0, sb.n_groups, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz, t->d_tcb,
+                                                                                   t->nn_dist, p->tol, p->m_e, p->V0, sb.d_mask, sb.d_voff, sb.d_val, t->d_tdiag);
         KMCF_HIP(hipGetLastError());
     }
-    m->sub = &t->sub;
+    sb.grid = sb.spread ? (ns + KMCF_BLOCK - 1) / KMCF_BLOCK : sb.dense ? sb.nb : ns > 0 ? wave_row_grid(ns) : 0;
+    return KMCF_OK;
+}
+
+// 8. preconditioner and right-hand side
+static int asm_precond_rhs(kmcf_tstate *t)
+{
+    kmcf_matrix *m = t->T;
+    const kmcf_subop &sb = t->sub;
+    hipStream_t st = t->comm->stream;
+    const int n_loc = m->n_loc, ns = sb.n_loc;
+    if (n_loc == 0) return KMCF_OK;
+    copy_diag_rhs_kernel<<<kmcf_grid1d(n_loc), KMCF_BLOCK, 0, st>>>(n_loc, t->d_diag, t->d_diag_tot, t->d_col_node, t->par.loop_G * t->par.Vd, t->d_rhs);
+    if (ns > 0) add_tunnel_diag_kernel<<<kmcf_grid1d(ns), KMCF_BLOCK, 0, st>>>(ns, sb.d_rows, t->d_tdiag + (sb.spread ? sb.row0 : 0), t->d_diag_tot);
+    invert_kernel<<<kmcf_grid1d(n_loc), KMCF_BLOCK, 0, st>>>(n_loc, t->d_diag_tot, m->d_dinv);
+    KMCF_HIP(hipGetLastError());
+    return KMCF_OK;
+}
+
+// (an error return from any stage leaves assembled == false)
+static int t_assemble_async(kmcf_tstate *t, const int *d_site_element, const int *d_site_charge, const double *d_site_CB_edge,
+                            const int *d_metals, int num_metals, const kmcf_current_params_t *p)
+{
+    t->par = *p;
+    t->assembled = false;
+    KMCF_TRY(asm_atoms(t, d_site_element, d_site_charge, d_site_CB_edge, d_metals, num_metals));
+    KMCF_TRY(asm_neighbour_values(t));
+    KMCF_TRY(asm_tunnel_points(t, d_metals, num_metals));
+    KMCF_TRY(asm_partition(t));
+    KMCF_TRY(asm_bitmap_pattern(t));
+    KMCF_TRY(asm_choose_storage(t));
+    KMCF_TRY(asm_values(t));
+    KMCF_TRY(asm_precond_rhs(t));
+    t->T->sub = &t->sub;
     t->assembled = true;
     return KMCF_OK;
 }
@@ -1817,31 +1969,19 @@ int kmcf_subop_finish(kmcf_matrix *m, bool with_dot, bool skip_if_done)
         sb->gather_pending = false;
     }
     double *part = m->d_part_a + 3 * KMCF_MAX_PARTIALS;
-    if (sb->spread) {                                                          // (every rank: also one without points of its own)
-        KMCF_TRY(symm_launch<0>(*sb, sb->d_xsub, 0.0, st, m->d_S, chk));
-        if (with_dot) return symm_spread_finish<0, true>(c, *sb, sb->n_loc, sb->row0, sb->d_rows, m->d_p, m->d_Ap, nullptr, part, m->d_S, chk);
-        return symm_spread_finish<0, false>(c, *sb, sb->n_loc, sb->row0, sb->d_rows, m->d_p, m->d_Ap, nullptr, part, m->d_S, chk);
-    }
-    if (sb->n_loc == 0) return KMCF_OK;
-    if (sb->dense) {
-        KMCF_TRY(symm_launch<0>(*sb, sb->d_xsub, 0.0, st, m->d_S, chk));       // (behind the stop: neither pass runs)
-        if (with_dot)
-            sub_symm_reduce_kernel<0, true><<<sb->grid, KMCF_BLOCK, 0, st>>>(sb->n_glob, sb->nb, sb->d_strip_first, sb->d_rowpart, sb->d_colpart,
-                                                                            sb->d_rows, m->d_p, m->d_Ap, nullptr, part, m->d_S, chk);
-        else
-            sub_symm_reduce_kernel<0, false><<<sb->grid, KMCF_BLOCK, 0, st>>>(sb->n_glob, sb->nb, sb->d_strip_first, sb->d_rowpart, sb->d_colpart,
-                                                                             sb->d_rows, m->d_p, m->d_Ap, nullptr, part, m->d_S, chk);
+    int rc = KMCF_OK;
+    if (symm_applies(*sb)) {                                                   // (behind the stop: neither pass runs)
+        with_bools([&](auto dot) {
+            rc = symm_apply<0, decltype(dot)::value>(c, *sb, sb->n_loc, sb->row0, sb->d_rows, m->d_p, m->d_Ap, nullptr, part, m->d_S, chk);
+        }, with_dot);
+    } else if (!sb->dense && sb->n_loc > 0) {
+        with_bools([&](auto dot) {
+            sub_spmv_kernel<decltype(dot)::value><<<sb->grid, KMCF_BLOCK, 0, st>>>(sb->n_loc, sb->n_glob, sb->n_groups, sb->d_mask, sb->d_voff, sb->d_val,
+                                                                                   sb->d_xsub, sb->d_rows, m->d_p, m->d_Ap, part, m->d_S, chk);
+        }, with_dot);
         KMCF_HIP(hipGetLastError());
-        return KMCF_OK;
     }
-    if (with_dot)
-        sub_spmv_kernel<true><<<sb->grid, KMCF_BLOCK, 0, st>>>(sb->n_loc, sb->n_glob, sb->n_groups, sb->d_mask, sb->d_voff, sb->d_val, sb->d_xsub,
-                                                              sb->d_rows, m->d_p, m->d_Ap, part, m->d_S, chk);
-    else
-        sub_spmv_kernel<false><<<sb->grid, KMCF_BLOCK, 0, st>>>(sb->n_loc, sb->n_glob, sb->n_groups, sb->d_mask, sb->d_voff, sb->d_val, sb->d_xsub,
-                                                               sb->d_rows, m->d_p, m->d_Ap, part, m->d_S, chk);
-    KMCF_HIP(hipGetLastError());
-    return KMCF_OK;
+    return rc;
 }
 
 static int check_params(const kmcf_current_params_t *p)
@@ -1881,6 +2021,88 @@ extern "C" int kmcf_tstate_get_vectors(const kmcf_tstate *t, double *h_diag_neig
     return KMCF_OK;
 }
 
+// ---------------------------------------------------------------- kmcf_tstate_get_tunnel (the tests' accessor): the values per form
+// jagged: this rank's tiles (64 x 64, zeros where no entry) out of the layers
+static int tunnel_tiles_from_layers(const kmcf_subop &sb, std::vector<double> *tiles)
+{
+    tiles->assign((size_t)sb.n_tiles * 4096, 0.0);
+    std::vector<unsigned long long> jm((size_t)sb.n_tiles * 64);
+    std::vector<long long> jo((size_t)sb.n_tiles + 1);
+    std::vector<double> jv((size_t)sb.jnnz + 1);
+    KMCF_HIP(hipMemcpy(jm.data(), sb.d_jmask, jm.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    KMCF_HIP(hipMemcpy(jo.data(), sb.d_jvoff, jo.size() * sizeof(long long), hipMemcpyDeviceToHost));
+    if (sb.jnnz) KMCF_HIP(hipMemcpy(jv.data(), sb.d_jval, (size_t)sb.jnnz * sizeof(double), hipMemcpyDeviceToHost));
+    for (long long tl = 0; tl < sb.n_tiles; ++tl) {
+        unsigned long long m[64];
+        for (int r = 0; r < 64; ++r) m[r] = jm[(size_t)tl * 64 + r];
+        long long pos = jo[(size_t)tl];
+        for (bool any = true; any;) {                    // layer by layer, rows ascending
+            any = false;
+            for (int r = 0; r < 64; ++r)
+                if (m[r]) {
+                    (*tiles)[(size_t)tl * 4096 + (size_t)r * 64 + __builtin_ctzll(m[r])] = jv[(size_t)pos++];
+                    m[r] &= m[r] - 1;
+                    any = true;
+                }
+        }
+    }
+    return KMCF_OK;
+}
+
+// spread: the tiles of this rank's rows lie on all ranks: the rows' entries are computed afresh as the bitmap storage
+// would (the same values: one symmetric expression per pair); the walk puts the diagonal entries in use in their place
+static int tunnel_rows_recomputed(const kmcf_tstate *t, double *h_val)
+{
+    const kmcf_subop &sb = t->sub;
+    const int ns = sb.n_loc;
+    double *d_v = nullptr, *d_dg = nullptr;
+    KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&d_v), ((size_t)sb.nnz + 64) * sizeof(double)));
+    if (hipMalloc(reinterpret_cast<void **>(&d_dg), ((size_t)ns + 1) * sizeof(double)) != hipSuccess) { hipFree(d_v); KMCF_HIP(hipErrorOutOfMemory); }
+    tunnel_value_kernel<<<wave_row_grid(ns), KMCF_BLOCK, 0, t->comm->stream>>>(ns, sb.row0, sb.n_groups, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz, t->d_tcb,
+                                                                               t->nn_dist, t->par.tol, t->par.m_e, t->par.V0, sb.d_mask, sb.d_voff, d_v, d_dg);
+    hipError_t e1 = hipGetLastError();
+    if (e1 == hipSuccess) e1 = hipStreamSynchronize(t->comm->stream);
+    if (e1 == hipSuccess) e1 = hipMemcpy(h_val, d_v, (size_t)sb.nnz * sizeof(double), hipMemcpyDeviceToHost);
+    hipFree(d_v); hipFree(d_dg);
+    KMCF_HIP(e1);
+    return KMCF_OK;
+}
+
+// The one walk of this rank's bitmap rows: row offsets and columns; values out of `tiles` when given (the tile forms of
+// one rank), the diagonal entries out of d_tdiag (spread), else h_val stays as it is (packed = CSR order already).
+static int tunnel_walk_bitmap(const kmcf_tstate *t, const std::vector<double> &tiles, int *h_row_ptr, int *h_col, double *h_val)
+{
+    const kmcf_subop &sb = t->sub;
+    const int ns = sb.n_loc, ng = sb.n_groups;
+    std::vector<double> tdiag_now;
+    if (sb.spread && h_val && ns) {
+        tdiag_now.resize((size_t)ns);
+        KMCF_HIP(hipMemcpy(tdiag_now.data(), t->d_tdiag + sb.row0, (size_t)ns * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    std::vector<unsigned long long> mk((size_t)ns * ng + 1);
+    if (ns) KMCF_HIP(hipMemcpy(mk.data(), sb.d_mask, (size_t)ns * ng * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    int64_t pos = 0;
+    if (h_row_ptr) h_row_ptr[0] = 0;
+    for (int s = 0; s < ns; ++s) {
+        for (int g = 0; g < ng; ++g) {
+            unsigned long long w = mk[(size_t)s * ng + g];
+            while (w) {
+                const int b = __builtin_ctzll(w);
+                if (h_col) h_col[pos] = g * 64 + b;
+                if (sb.spread && h_val && g * 64 + b == sb.row0 + s) h_val[pos] = tdiag_now[(size_t)s];
+                if (!tiles.empty()) {
+                    const int i = sb.row0 + s, j = g * 64 + b, lo = std::min(i, j), hi = std::max(i, j);
+                    h_val[pos] = tiles[(size_t)symm_tile_index(sb.nb, lo >> 6, hi >> 6) * 4096 + (size_t)(lo & 63) * 64 + (hi & 63)];
+                }
+                ++pos;
+                w &= w - 1;
+            }
+        }
+        if (h_row_ptr) h_row_ptr[s + 1] = (int)pos;
+    }
+    return KMCF_OK;
+}
+
 extern "C" int kmcf_tstate_get_tunnel(const kmcf_tstate *t, int *h_tunnel_idx, int *h_row_ptr, int *h_col, double *h_val, double *h_diag)
 {
     KMCF_CHECK(t, KMCF_ERR_ARG, "kmcf_tstate_get_tunnel: null state");
@@ -1889,79 +2111,56 @@ extern "C" int kmcf_tstate_get_tunnel(const kmcf_tstate *t, int *h_tunnel_idx, i
     KMCF_HIP(hipStreamSynchronize(t->comm->stream));
     const kmcf_subop &sb = t->sub;
     if (h_tunnel_idx && sb.n_glob) memcpy(h_tunnel_idx, t->h_tidx.data(), (size_t)sb.n_glob * sizeof(int));
-    const int ns = sb.n_loc, ng = sb.n_groups;
+    const int ns = sb.n_loc;
     if (h_diag && ns) KMCF_HIP(hipMemcpy(h_diag, t->d_tdiag + (sb.spread ? sb.row0 : 0), (size_t)ns * sizeof(double), hipMemcpyDeviceToHost));
     std::vector<double> tiles;
-    if (h_val && sb.nnz && sb.jagged) {                      // the same out of the layers of the jagged tiles
-        tiles.assign((size_t)sb.n_tiles * 4096, 0.0);
-        std::vector<unsigned long long> jm((size_t)sb.n_tiles * 64);
-        std::vector<long long> jo((size_t)sb.n_tiles + 1);
-        std::vector<double> jv((size_t)sb.jnnz + 1);
-        KMCF_HIP(hipMemcpy(jm.data(), sb.d_jmask, jm.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        KMCF_HIP(hipMemcpy(jo.data(), sb.d_jvoff, jo.size() * sizeof(long long), hipMemcpyDeviceToHost));
-        if (sb.jnnz) KMCF_HIP(hipMemcpy(jv.data(), sb.d_jval, (size_t)sb.jnnz * sizeof(double), hipMemcpyDeviceToHost));
-        for (long long tl = 0; tl < sb.n_tiles; ++tl) {
-            unsigned long long m[64];
-            for (int r = 0; r < 64; ++r) m[r] = jm[(size_t)tl * 64 + r];
-            long long pos = jo[(size_t)tl];
-            for (bool any = true; any;) {                    // layer by layer, rows ascending
-                any = false;
-                for (int r = 0; r < 64; ++r)
-                    if (m[r]) {
-                        tiles[(size_t)tl * 4096 + (size_t)r * 64 + __builtin_ctzll(m[r])] = jv[(size_t)pos++];
-                        m[r] &= m[r] - 1;
-                        any = true;
-                    }
-            }
-        }
-    } else if (h_val && sb.nnz && sb.spread) {
-        // the tiles of this rank's rows lie on all ranks: the rows' entries are computed afresh as the bitmap storage
-        // would (the same values: one symmetric expression per pair), the diagonal entries are the ones in use
-        double *d_v = nullptr, *d_dg = nullptr;
-        KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&d_v), ((size_t)sb.nnz + 64) * sizeof(double)));
-        if (hipMalloc(reinterpret_cast<void **>(&d_dg), ((size_t)ns + 1) * sizeof(double)) != hipSuccess) { hipFree(d_v); KMCF_HIP(hipErrorOutOfMemory); }
-        const int wgrid = std::max(1, std::min((ns + 3) / 4, KMCF_MAX_PARTIALS));
-        tunnel_value_kernel<<<wgrid, KMCF_BLOCK, 0, t->comm->stream>>>(ns, sb.row0, ng, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz, t->d_tcb, t->nn_dist,
-                                                                      t->par.tol, t->par.m_e, t->par.V0, sb.d_mask, sb.d_voff, d_v, d_dg);
-        hipError_t e1 = hipGetLastError();
-        if (e1 == hipSuccess) e1 = hipStreamSynchronize(t->comm->stream);
-        if (e1 == hipSuccess) e1 = hipMemcpy(h_val, d_v, (size_t)sb.nnz * sizeof(double), hipMemcpyDeviceToHost);
-        hipFree(d_v); hipFree(d_dg);
-        KMCF_HIP(e1);
-    } else if (h_val && sb.nnz && sb.dense) {                // values out of the upper tiles (test-sized blocks)
-        tiles.resize((size_t)sb.n_tiles * 4096);
-        KMCF_HIP(hipMemcpy(tiles.data(), sb.d_tiles, tiles.size() * sizeof(double), hipMemcpyDeviceToHost));
-    } else if (h_val && sb.nnz) {
-        KMCF_HIP(hipMemcpy(h_val, sb.d_val, (size_t)sb.nnz * sizeof(double), hipMemcpyDeviceToHost));   // packed = CSR order
-    }
-    if (h_row_ptr || h_col || !tiles.empty() || (sb.spread && h_val)) {
-        std::vector<double> tdiag_now;
-        if (sb.spread && h_val && ns) {
-            tdiag_now.resize((size_t)ns);
-            KMCF_HIP(hipMemcpy(tdiag_now.data(), t->d_tdiag + sb.row0, (size_t)ns * sizeof(double), hipMemcpyDeviceToHost));
-        }
-        std::vector<unsigned long long> mk((size_t)ns * ng + 1);
-        if (ns) KMCF_HIP(hipMemcpy(mk.data(), sb.d_mask, (size_t)ns * ng * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        int64_t pos = 0;
-        if (h_row_ptr) h_row_ptr[0] = 0;
-        for (int s = 0; s < ns; ++s) {
-            for (int g = 0; g < ng; ++g) {
-                unsigned long long w = mk[(size_t)s * ng + g];
-                while (w) {
-                    const int b = __builtin_ctzll(w);
-                    if (h_col) h_col[pos] = g * 64 + b;
-                    if (sb.spread && h_val && g * 64 + b == sb.row0 + s) h_val[pos] = tdiag_now[(size_t)s];
-                    if (!tiles.empty()) {
-                        const int i = sb.row0 + s, j = g * 64 + b, lo = std::min(i, j), hi = std::max(i, j);
-                        h_val[pos] = tiles[(size_t)symm_tile_index(sb.nb, lo >> 6, hi >> 6) * 4096 + (size_t)(lo & 63) * 64 + (hi & 63)];
-                    }
-                    ++pos;
-                    w &= w - 1;
-                }
-            }
-            if (h_row_ptr) h_row_ptr[s + 1] = (int)pos;
+    if (h_val && sb.nnz) {
+        if (sb.jagged) {
+            KMCF_TRY(tunnel_tiles_from_layers(sb, &tiles));
+        } else if (sb.spread) {
+            KMCF_TRY(tunnel_rows_recomputed(t, h_val));
+        } else if (sb.dense) {                               // values out of the upper tiles (test-sized blocks)
+            tiles.resize((size_t)sb.n_tiles * 4096);
+            KMCF_HIP(hipMemcpy(tiles.data(), sb.d_tiles, tiles.size() * sizeof(double), hipMemcpyDeviceToHost));
+        } else {
+            KMCF_HIP(hipMemcpy(h_val, sb.d_val, (size_t)sb.nnz * sizeof(double), hipMemcpyDeviceToHost));   // packed = CSR order
         }
     }
+    if (h_row_ptr || h_col || !tiles.empty() || (sb.spread && h_val)) KMCF_TRY(tunnel_walk_bitmap(t, tiles, h_row_ptr, h_col, h_val));
+    return KMCF_OK;
+}
+
+// The power pass on the scaled potentials: shift (:2068-2071), forward currents and their row sums (:2086-2098) of the
+// neighbour part and of the tunnel block in its form, P = I_neg m (:2100-2131), copy_pdisp (:2137)
+static int power_pass(kmcf_tstate *t, double *pot, double *d_site_power)
+{
+    kmcf_comm *c = t->comm;
+    kmcf_matrix *m = t->T;
+    kmcf_subop &sb = t->sub;
+    hipStream_t st = c->stream;
+    const kmcf_current_params_t *p = &t->par;
+    const int n_loc = m->n_loc, Na = t->N_atom;
+    min_kernel<<<1, KMCF_BLOCK, 0, st>>>(Na + 2, pot, t->d_scal + 1);
+    shift_kernel<<<kmcf_grid1d(Na + 2), KMCF_BLOCK, 0, st>>>(Na + 2, pot, t->d_scal + 1);
+    double *psum = m->d_r, *isum = m->d_Ap;                          // workspace vectors, free after the solve
+    if (n_loc > 0) {
+        power_neighbour_kernel<16><<<kmcf_grid1d((int64_t)n_loc * 16), KMCF_BLOCK, 0, st>>>(
+            n_loc, m->d_row_ptr, m->d_col, m->d_val, t->d_diag_pos, t->d_col_node, pot, p->Vd, psum, isum);
+        KMCF_HIP(hipGetLastError());
+    }
+    if (symm_applies(sb)) {
+        gather_tunnel_pot_kernel<<<kmcf_grid1d(sb.n_glob), KMCF_BLOCK, 0, st>>>(sb.n_glob, t->d_tidx, pot, sb.d_xsub);
+        KMCF_TRY((symm_apply<1, false>(c, sb, sb.n_loc, sb.row0, sb.d_rows, nullptr, psum, isum, nullptr, nullptr, 0, p->Vd)));
+        KMCF_HIP(hipMemsetAsync(sb.d_xsub + sb.n_glob, 0, (size_t)(64 * sb.nb - sb.n_glob) * sizeof(double), st));    // the pad stays 0
+    } else if (!sb.dense && sb.n_loc > 0) {
+        power_tunnel_kernel<<<sb.grid, KMCF_BLOCK, 0, st>>>(sb.n_loc, sb.row0, sb.n_groups, sb.d_mask, sb.d_voff, sb.d_val, t->d_tidx, sb.d_rows, pot,
+                                                            p->Vd, psum, isum);
+    }
+    if (n_loc > 0) power_finish_kernel<<<kmcf_grid1d(n_loc), KMCF_BLOCK, 0, st>>>(n_loc, t->d_col_node, pot, psum, isum, t->d_pdisp);
+    KMCF_HIP(hipGetLastError());
+    KMCF_TRY(kmcf_comm_allgatherv_double(c, t->d_pdisp, m->counts.data(), m->displs.data()));
+    copy_pdisp_kernel<<<kmcf_grid1d(Na - 1), KMCF_BLOCK, 0, st>>>(Na - 1, t->d_atom_site, t->d_acls, t->d_pdisp, p->alpha_disp, d_site_power);
+    KMCF_HIP(hipGetLastError());
     return KMCF_OK;
 }
 
@@ -2000,47 +2199,11 @@ extern "C" int kmcf_update_power_sparse(kmcf_tstate *t, const int *d_site_elemen
     KMCF_HIP(hipGetLastError());
     KMCF_TRY(kmcf_comm_allreduce_sum(c, t->d_scal, 1));
     // (into pinned memory that outlives this frame: the error returns below leave before the synchronisation)
-    double *h_im = reinterpret_cast<double *>(t->h_pin + 4);
-    KMCF_HIP(hipMemcpyAsync(h_im, t->d_scal, sizeof(double), hipMemcpyDeviceToHost, st));
-    if (p->solve_heating) {
-        // shift (:2068-2071), forward currents and their row sums (:2086-2098), P = I_neg m (:2100-2131), copy_pdisp (:2137)
-        min_kernel<<<1, KMCF_BLOCK, 0, st>>>(Na + 2, d_atom_virtual_potentials, t->d_scal + 1);
-        shift_kernel<<<kmcf_grid1d(Na + 2), KMCF_BLOCK, 0, st>>>(Na + 2, d_atom_virtual_potentials, t->d_scal + 1);
-        double *psum = m->d_r, *isum = m->d_Ap;                          // workspace vectors, free after the solve
-        if (n_loc > 0) {
-            power_neighbour_kernel<16><<<kmcf_grid1d((int64_t)n_loc * 16), KMCF_BLOCK, 0, st>>>(
-                n_loc, m->d_row_ptr, m->d_col, m->d_val, t->d_diag_pos, t->d_col_node, d_atom_virtual_potentials, p->Vd, psum, isum);
-            KMCF_HIP(hipGetLastError());
-        }
-        if (t->sub.spread) {                                               // (every rank of the group: its strips, then the gather)
-            kmcf_subop &sb = t->sub;
-            gather_tunnel_pot_kernel<<<kmcf_grid1d(sb.n_glob), KMCF_BLOCK, 0, st>>>(sb.n_glob, t->d_tidx, d_atom_virtual_potentials, sb.d_xsub);
-            KMCF_TRY(symm_launch<1>(sb, sb.d_xsub, p->Vd, st));
-            KMCF_TRY((symm_spread_finish<1, false>(c, sb, sb.n_loc, sb.row0, sb.d_rows, nullptr, psum, isum, nullptr, nullptr, 0)));
-            KMCF_HIP(hipMemsetAsync(sb.d_xsub + sb.n_glob, 0, (size_t)(64 * sb.nb - sb.n_glob) * sizeof(double), st));
-        }
-        if (n_loc > 0) {
-            if (t->sub.n_loc > 0 && t->sub.dense && !t->sub.spread) {
-                kmcf_subop &sb = t->sub;
-                gather_tunnel_pot_kernel<<<kmcf_grid1d(sb.n_glob), KMCF_BLOCK, 0, st>>>(sb.n_glob, t->d_tidx, d_atom_virtual_potentials, sb.d_xsub);
-                KMCF_TRY(symm_launch<1>(sb, sb.d_xsub, p->Vd, st));
-                sub_symm_reduce_kernel<1, false><<<sb.nb, KMCF_BLOCK, 0, st>>>(sb.n_glob, sb.nb, sb.d_strip_first, sb.d_rowpart, sb.d_colpart,
-                                                                                          sb.d_rows, nullptr, psum, isum, nullptr, nullptr, 0);
-                KMCF_HIP(hipMemsetAsync(sb.d_xsub + sb.n_glob, 0, (size_t)(64 * sb.nb - sb.n_glob) * sizeof(double), st));
-            } else if (t->sub.n_loc > 0 && !t->sub.dense)
-                power_tunnel_kernel<<<t->sub.grid, KMCF_BLOCK, 0, st>>>(t->sub.n_loc, t->sub.row0, t->sub.n_groups, t->sub.d_mask, t->sub.d_voff,
-                                                                       t->sub.d_val, t->d_tidx, t->sub.d_rows, d_atom_virtual_potentials, p->Vd,
-                                                                       psum, isum);
-            power_finish_kernel<<<kmcf_grid1d(n_loc), KMCF_BLOCK, 0, st>>>(n_loc, t->d_col_node, d_atom_virtual_potentials, psum, isum, t->d_pdisp);
-        }
-        KMCF_HIP(hipGetLastError());
-        KMCF_TRY(kmcf_comm_allgatherv_double(c, t->d_pdisp, m->counts.data(), m->displs.data()));
-        copy_pdisp_kernel<<<kmcf_grid1d(Na - 1), KMCF_BLOCK, 0, st>>>(Na - 1, t->d_atom_site, t->d_acls, t->d_pdisp, p->alpha_disp, d_site_power);
-        KMCF_HIP(hipGetLastError());
-    }
+    KMCF_HIP(hipMemcpyAsync(&t->h_pin->imacro, t->d_scal, sizeof(double), hipMemcpyDeviceToHost, st));
+    if (p->solve_heating) KMCF_TRY(power_pass(t, d_atom_virtual_potentials, d_site_power));
     KMCF_HIP(hipStreamSynchronize(st));
     KMCF_TRY(kmcf_p2p_check(c));
-    if (imacro) *imacro = *h_im;
+    if (imacro) *imacro = t->h_pin->imacro;
     if (stats) {
         float ms = 0.f;
         KMCF_HIP(hipEventElapsedTime(&ms, c->ev_a0, c->ev_a1));
@@ -2075,9 +2238,8 @@ extern "C" int kmcf_current_map(kmcf_tstate *t, const double *d_atom_virtual_pot
         KMCF_HIP(hipGetLastError());
     }
     if (sb.n_loc > 0) {
-        const int wgrid = std::max(1, std::min((sb.n_loc + KMCF_BLOCK / 64 - 1) / (KMCF_BLOCK / 64), KMCF_MAX_PARTIALS));
-        current_tunnel_kernel<<<wgrid, KMCF_BLOCK, 0, st>>>(sb.n_loc, sb.row0, sb.n_groups, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz, t->d_tcb,
-                                                            t->par.tol, t->par.m_e, t->par.V0, sb.d_mask, t->d_tidx, pot, t->d_cmap);
+        current_tunnel_kernel<<<wave_row_grid(sb.n_loc), KMCF_BLOCK, 0, st>>>(sb.n_loc, sb.row0, sb.n_groups, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz, t->d_tcb,
+                                                                              t->par.tol, t->par.m_e, t->par.V0, sb.d_mask, t->d_tidx, pot, t->d_cmap);
         KMCF_HIP(hipGetLastError());
     }
     // every rank gets all nodes (as d_pdisp is gathered: the row partition, three doubles a row)

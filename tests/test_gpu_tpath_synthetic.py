@@ -11,7 +11,9 @@ shift rtol 1e-15; converged solves identical to the oracle adding in the device'
 longdouble M) <= 3 x the natural-order oracle's.
 
 Every compared assembly is the SECOND on its state: the first runs on another band edge and charge vector
-(tpath_ref.other_state), so that grown buffers hold another pattern's masks and values."""
+(tpath_ref.other_state), so that grown buffers hold another pattern's masks and values.  Every form gets a fresh device
+-- except in (a'), where ONE state (one rank; one per rank of a group) goes through the forms in turn and must give a
+fresh state's values bit for bit."""
 import contextlib
 import threading
 
@@ -133,6 +135,135 @@ def test_assembly_one_rank(km, torch, monkeypatch, name, strip):
     for key in ("val", "diag", "row_ptr", "col"):                                                # jagged: the dense tiles' entries, same order
         np.testing.assert_array_equal(c["tn"][key], b["tn"][key])
     np.testing.assert_array_equal(c["dinv"], b["dinv"])
+
+
+# ------------------------------------------------------------------------------------------------ (a') one state, form after form
+def _assembled(S, buf, want, form, r0=0, nr=None):
+    """The file's comparison of one assembly + what must be bit-identical between a fresh and a reused state."""
+    tn = _compare_assembly(S, buf, want, r0, nr)
+    info = S.t_info(buf)
+    assert info["tunnel_dense"] == STORAGE[form], (form, info)
+    return dict(val=tn["val"].copy(), diag=tn["diag"].copy(), dinv=S.t_vectors(buf)["dinv"].copy(), bytes=info["tunnel_bytes"])
+
+
+def _same_as_fresh(got, fresh, what):
+    for key in ("val", "diag", "dinv"):
+        np.testing.assert_array_equal(got[key], fresh[key], err_msg="%s: %s differs from a fresh state's" % (what, key))
+    assert got["bytes"] == fresh["bytes"], (what, got["bytes"], fresh["bytes"])
+
+
+@pytest.mark.parametrize("name,strip", [("nt_129", 2), ("group_178", None)])
+def test_one_state_through_the_storage_forms(km, torch, monkeypatch, name, strip):
+    """ONE T state assembled as bitmap -> tiles -> jagged -> bitmap -> tiles (every other test gives each form a fresh
+    device): after each assembly the comparison with the dense reference, the form reported, and tunnel values, tunnel
+    diagonal and preconditioner bit-identical to a fresh state's in that form -- a flag, grid or pointer left behind by
+    the form before would show.  Then one split SpMV (test_split_spmv's bound) and the power pass on prescribed
+    potentials (test_current_and_power_on_prescribed_potentials' bars) on the state as the sequence left it."""
+    case = R.tpath_case(name)
+    Vd = case["par"]["Vd"]
+    if strip:
+        monkeypatch.setenv("KMCF_SUB_STRIP", str(strip))
+    fresh = {}
+    for form, dense in STORAGE.items():
+        monkeypatch.setenv("KMCF_SUB_DENSE", str(dense))
+        with _device(km, torch, name) as (S, buf, ref, kw):
+            S.t_assemble(buf, _prm(S, case, Vd))
+            fresh[form] = _assembled(S, buf, ref.as_csr(), form)
+    with _device(km, torch, name) as (S, buf, ref, kw):
+        want = ref.as_csr()
+        for k, form in enumerate(("bitmap", "tiles", "jagged", "bitmap", "tiles")):
+            monkeypatch.setenv("KMCF_SUB_DENSE", str(STORAGE[form]))
+            S.t_assemble(buf, _prm(S, case, Vd))
+            _same_as_fresh(_assembled(S, buf, want, form), fresh[form], "assembly %d (%s)" % (k, form))
+        # the split SpMV on the state as it stands (tiles)
+        mat = S.Distributed_matrix.from_handle(km.lib.load().kmcf_tstate_matrix(buf.T_distributed))
+        rng = np.random.default_rng(5)
+        x = rng.standard_normal(ref.Nsub) + 3.0 * rng.random(ref.Nsub)
+        p = torch.as_tensor(x, device="cuda")
+        Ap = torch.empty_like(p)
+        mat.spmv(p, Ap)
+        err = np.abs(Ap.cpu().numpy() - ref.M @ x.astype(R.LD))
+        bound = np.abs(ref.M) @ np.abs(x).astype(R.LD)
+        assert np.all(err <= 1e-12 * bound), (int(np.argmax(err / bound)), float((err / bound).max()))
+        # the power pass on prescribed potentials (0 iterations; it assembles once more, as tiles)
+        x0 = R.potentials(ref, Vd)
+        m = _m_of(ref, x0)
+        buf.atom_virtual_potentials.zero_()
+        buf.atom_virtual_potentials[:ref.Nsub] = torch.as_tensor(x0, device="cuda")
+        buf.site_power.fill_(-7.0)
+        im, st = S.update_power_gpu_sparse_dist(buf, *_args(case, Vd), True, False, 1.0, cg_tolerance=1e-30, cg_max_iterations=0, **kw)
+        assert st["iterations"] == 0 and S.t_info(buf)["tunnel_dense"] == 1
+        assert abs(im - ref.imacro(m)) <= 1e-11 * ref.imacro_scale(m), (im, ref.imacro(m))
+        pw, ms = ref.power(m, Vd, 1.0)
+        gp = buf.site_power.cpu().numpy()
+        np.testing.assert_allclose(buf.atom_virtual_potentials.cpu().numpy(), ms, rtol=1e-15, atol=0)
+        np.testing.assert_array_equal(gp == -7.0, pw == -7.0)
+        w = pw != -7.0
+        assert np.abs(gp - pw)[w].max() <= 1e-11 * np.abs(pw[w]).max(), float(np.abs(gp - pw)[w].max() / np.abs(pw[w]).max())
+        assert (gp[w] != 0).any() and np.all(gp[w] >= 0)
+
+
+def _group_through(km, torch, monkeypatch, name, P, forms):
+    """One state per rank of a loopback group of P, assembled in each of `forms` in turn (the knob changes while all
+    ranks wait at a barrier); per rank and assembly what _assembled returns."""
+    S = km.solvers
+    case = R.tpath_case(name)
+    Vd = case["par"]["Vd"]
+    ref = R.case_ref(name, Vd)
+    want = ref.as_csr()
+    N = len(case["element"])
+    step = [0]
+
+    def next_form():
+        monkeypatch.setenv("KMCF_SUB_DENSE", str(STORAGE[forms[step[0]]]))
+        step[0] += 1
+
+    next_form()
+    comms = S.KMC_comm.loopback_group(ref.Nsub, ref.Nsub, N, N, P)
+    gate = threading.Barrier(P, action=next_form, timeout=120)
+    out, errs = [[] for _ in range(P)], []
+
+    def work(r):
+        try:
+            torch.cuda.set_device(0)
+            comm = comms[r]
+            with _device(km, torch, name, Vd, comm=comm) as (S_, buf, ref_, kw):
+                r0, nr = int(comm.displs_T[r]), int(comm.counts_T[r])
+                for k, form in enumerate(forms):
+                    if k:
+                        gate.wait()
+                    S.t_assemble(buf, _prm(S, case, Vd))
+                    out[r].append(_assembled(S, buf, want, form, r0, nr))
+        except Exception as e:  # pragma: no cover
+            import traceback
+            gate.abort()
+            errs.append("rank %d: %s\n%s" % (r, e, traceback.format_exc()))
+
+    threads = [threading.Thread(target=work, args=(r,), daemon=True) for r in range(P)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join(180)
+    assert not errs, "\n".join(errs)
+    assert all(len(o) == len(forms) for o in out), "a rank did not finish"
+    for c in comms:
+        c.close()
+    return out
+
+
+def test_group_states_through_the_storage_forms(km, torch, monkeypatch):
+    """group_178 over three in-process ranks (loopback), strips of two tiles: one state per rank through tiles -> bitmap ->
+    tiles, every assembly compared as in test_one_state_through_the_storage_forms, against fresh groups in each form."""
+    monkeypatch.setenv("KMCF_SUB_STRIP", "2")
+    monkeypatch.delenv("KMCF_TRANSPORT", raising=False)
+    P, name = 3, "group_178"
+    fresh = {form: _group_through(km, torch, monkeypatch, name, P, (form,)) for form in ("tiles", "bitmap")}
+    assert sum(o[0]["bytes"] for o in fresh["tiles"]) == 6 * 32768                # really dealt: six tiles in all
+    seq = ("tiles", "bitmap", "tiles")
+    got = _group_through(km, torch, monkeypatch, name, P, seq)
+    for r in range(P):
+        for k, form in enumerate(seq):
+            _same_as_fresh(got[r][k], fresh[form][r][0], "rank %d, assembly %d (%s)" % (r, k, form))
 
 
 # ------------------------------------------------------------------------------------------------ (b) split SpMV
