@@ -381,7 +381,8 @@ int pcg_collect(kmcf_matrix *m, double tol2, int absolute, kmcf_solve_stats_t *s
         stats->iterations = hS.iters;
         stats->bb = hS.bb;
         stats->rz = hS.rz_last;
-        stats->relres = std::sqrt(hS.rz_last / hS.bb);
+        // (b = 0 from x0 = 0: the system is solved as it stands, and 0 / 0 is no residual)
+        stats->relres = hS.bb == 0.0 && hS.rz_last == 0.0 ? 0.0 : std::sqrt(hS.rz_last / hS.bb);
         stats->converged = (hS.done != 0) || !((absolute ? hS.rz_last : hS.rz_last / hS.bb) > tol2);
         if (loop_time) {                                   // (kmcf_pcg_jacobi times the whole call instead: the first
             float ms = 0.f;                                //  hipEventElapsedTime after a synchronisation costs ~13 us)

@@ -15,7 +15,7 @@ final residual do not see it.  Here the scalars themselves are held to tests/cg_
 
 tests/test_cg_ref.py holds the inputs to the conditions that make these checks see one lost row.  The path of every
 case is read back from the library (kmcf_matrix_info, kmcf_matrix_sum_plan), never assumed.  The solves run as the
-loop of kernels (KMCF_CG_RESIDENT=0; the resident launch is held bit for bit by the oracle tests).  Rank groups are
+loop of kernels (KMCF_CG_RESIDENT=0; the resident launch has tests/test_gpu_cgr_synthetic.py).  Rank groups are
 the in-process loopback group on one GPU; several GPUs stay unmeasured here.
 
 Every case prints its ratios of (b), device distance / float64-numpy distance (bar: 16), and the module's last test

@@ -303,7 +303,10 @@ def test_recurrence(km, torch, monkeypatch, resident):
                 monkeypatch.setenv("KMCF_SELL_PACK", pack)
             info = mat.replan()
             assert info["spmv_coded"] == 2, info
-            _apply(torch, mat, b)                                        # an SpMV call first: the loop's stream is in use
+            tpb = mat.sum_plan(with_csr=False)["resident_tpb"]                 # the path the solve below takes, not assumed
+            print("sell-packed recurrence resident=%s pack=%s: resident_tpb %d" % (resident, pack, tpb))
+            assert tpb > 0 if resident == "1" else tpb == 0, tpb
+            _apply(torch, mat, b)                                      # an SpMV call first: the loop's stream is in use
             r = torch.as_tensor(b.copy(), device="cuda")
             x = torch.zeros_like(r)
             st = km.solvers.conjugate_gradient_jacobi(mat, r, x, torch.as_tensor(dinv, device="cuda"), 1e-30, 0, fixed_iters=3)
