@@ -418,127 +418,113 @@ void cg_p_launch(int nf, int grid, hipStream_t st, int n, const kmcf_xring &h, c
 #undef KMCF_CG_P
 }
 
-// flags: bit 0 = d_p already holds x0 (the fused input kernel wrote it), bit 1 = leave the final synchronisation and
-// the statistics to the caller (pcg_collect), who has more work to enqueue first
-template <bool PRECOND>
-int pcg_loop(kmcf_matrix *m, double tol, int max_it, int fixed_iters, int absolute, kmcf_solve_stats_t *stats, int flags = 0)
-{
-    kmcf_comm *c = m->comm;
-    hipStream_t st = c->stream;
-    const int n = m->n_loc;
-    const int vg = kmcf_vec_grid(n);
+// ------------------------------------------------------------------------------------------------
+// A solve as a loop of kernels.  cg_run_loop (behind the kernels of both recurrences) is the driver: prologue (scalars,
+// p <- x0, A x0), growing chunks of iterations with a look at the stop flag behind each, epilogue.  A recurrence --
+// pcg_loop, pcg1_loop -- supplies its set-up (setup: before anything is enqueued; residual0: behind A x0), "enqueue
+// iteration k" and "after the loop" (sequence numbers of kmcf_cgplan.hpp, tail kernels), on top of what both share:
+struct cg_loop_state {
+    kmcf_matrix *const m;
+    const kmcf_cg_request &q;
+    kmcf_comm *const c = m->comm;
+    const hipStream_t st = c->stream;
+    kmcf_scalars *const S = m->d_S;
+    const int n = m->n_loc, vg = kmcf_vec_grid(n);
     const bool multi = c->nranks > 1 || c->force_collectives;
-    kmcf_scalars *S = m->d_S;
-    const double tol2 = tol * tol;
-    const int check_tol = fixed_iters > 0 ? 0 : (absolute ? 2 : 1);
-    const int limit = fixed_iters > 0 ? fixed_iters : max_it;
+    const double tol2 = q.tol * q.tol;
+    const int check_tol = q.fixed_iters > 0 ? 0 : (q.call == KMCF_CG_CALL_ABSOLUTE ? 2 : 1);   // 0 fixed count, 1 relative, 2 absolute rule
+    // what the kernels read for a sum: the local partial array, or -- a group -- the all-reduced scalar in S->red[slot]
+    part_ref reduced(const part_ref &loc, int slot) const { return multi ? pr1(&S->red[slot], 1) : loc; }
+};
 
-    // partial sources: local partial arrays, or the all-reduced scalar in S->red
-    part_ref prz_loc = pr1(m->d_part_b, vg);
-    part_ref pbb_loc = pr1(m->d_part_c, vg);
-    part_ref ppap_loc = pr_spmv(m);
-    part_ref prz = multi ? pr1(&S->red[0], 1) : prz_loc;
-    part_ref pbb = multi ? pr1(&S->red[1], 1) : pbb_loc;
-    part_ref ppap = multi ? pr1(&S->red[2], 1) : ppap_loc;
-
-    if (!(flags & 1) || n == 0) KMCF_HIP(hipMemsetAsync(S, 0, sizeof(kmcf_scalars), st));      // (flag 1: the input kernel zeroed them)
-    KMCF_HIP(hipEventRecord(c->ev_t0, st));
-    // p <- x0 ; Ap = A x0 ; r = b - Ap ; z ; r.z ; b.b    (:178-213)
-    if (!(flags & 1)) KMCF_HIP(hipMemcpyAsync(m->d_p, m->d_x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
-    KMCF_TRY(kmcf_spmv_device(m, false, false));
-    cg_init_kernel<PRECOND><<<vg, KMCF_BLOCK, 0, st>>>(n, m->d_r, m->d_Ap, m->d_dinv, m->d_part_b, m->d_part_c);
-    KMCF_HIP(hipGetLastError());
-    if (multi) {
-        cg_finalize_kernel<<<1, KMCF_BLOCK, 0, st>>>(prz_loc, 0, pbb_loc, 1, S, 0);
-        KMCF_HIP(hipGetLastError());
-        KMCF_TRY(kmcf_comm_allreduce_sum(c, &S->red[0], 2));
-    }
-    // "direct" peer-to-peer protocol: halo sequence numbers are counted per launch below and set back to per executed
-    // SpMV after the loop (see pcg1_loop)
-    const bool direct = multi && c->nranks > 1 && kmcf_p2p_direct(m);
-    const u64 halo0 = direct ? *kmcf_p2p_halo_seq(m, 0) : 0;
-
-    // The p ring (KMCF_CG_XBATCH = B; cg_p_kernel): slot 0 is d_p itself -- it holds x0 for the A x0 above -- and p_k
-    // lives in slot k % B.  One rank only: a group's halo lands behind d_p.  m->d_p follows the ring through the loop
-    // and is the original buffer again on every way out of it.
-    const int B = multi ? 1 : std::min(std::max(kmcf_opt_int(c, KNOB_CG_XBATCH, KMCF_CG_XBATCH_DEFAULT), 1), 4);
+template <bool PRECOND>
+struct pcg_loop : cg_loop_state {
+    const part_ref prz_loc = pr1(m->d_part_b, vg), pbb_loc = pr1(m->d_part_c, vg), ppap_loc = pr_spmv(m);
+    const part_ref prz = reduced(prz_loc, 0), pbb = reduced(pbb_loc, 1), ppap = reduced(ppap_loc, 2);
+    // "direct" peer-to-peer protocol: the SpMV counts halo sequence numbers per launch; set back to per executed SpMV
+    // after the loop
+    bool direct = false;
+    u64 halo0 = 0;
+    // The p ring (KMCF_CG_XBATCH = B; cg_p_kernel): slot 0 is d_p itself -- it holds x0 for the A x0 of the prologue --
+    // and p_k lives in slot k % B.  One rank only: a group's halo lands behind d_p.  m->d_p follows the ring through the
+    // loop and is the original buffer again on every way out of it.
+    int B = 1;
     double *ring[4] = {m->d_p, nullptr, nullptr, nullptr};
-    for (int j = 1; j < B; ++j) {
-        if (!m->d_p_ring[j - 1]) {
-            const size_t len = (size_t)n + m->n_halo + 2;
-            KMCF_TRY(kmcf_dev_alloc(&m->d_p_ring[j - 1], len, false));
-            KMCF_HIP(hipMemsetAsync(m->d_p_ring[j - 1], 0, len * sizeof(double), st));
-        }
-        ring[j] = m->d_p_ring[j - 1];
-    }
-    struct p_restore {
-        kmcf_matrix *m;
-        double *p0;
-        ~p_restore() { m->d_p = p0; }
-    } restore{m, m->d_p};
     int pending = 0;                               // x += alpha p not applied yet (the device's S->x_pending while it runs)
-    m->xring = xring_at(ring, B, 1);
 
-    int launched = 0;
-    bool done = false;
-    // chunks of 2, 4, 8 ... KMCF_CHUNK_ITERS iterations: a warm-started solve (every KMC step but the first)
-    // stops within a few iterations, and every iteration enqueued behind the stop is three empty launches
-    int chunk_cap = check_tol ? 2 : KMCF_CHUNK_ITERS;
-    while (launched < limit && !done) {
-        int chunk = limit - launched;
-        if (chunk > chunk_cap) chunk = chunk_cap;
-        chunk_cap = std::min(2 * chunk_cap, KMCF_CHUNK_ITERS);
-        for (int i = 0; i < chunk; ++i) {
-            const int k = launched + i + 1;  // reference's k
-            const int parity = k & 1;
-            // loop head: all `pending` updates of x if the ring is full, none otherwise; p_k into slot k % B
-            const int nf = pending == B ? B : 0;
-            const kmcf_xring h = xring_at(ring, B, k);
-            cg_p_launch<PRECOND>(nf, vg, st, n, h, ring[(k - 1) % B], ring[k % B], m->d_r, m->d_dinv, prz, pbb, S, k, k == 1 ? 1 : 0, tol2,
-                                 check_tol, m->d_x, pending);
+    pcg_loop(kmcf_matrix *m_, const kmcf_cg_request &q_) : cg_loop_state{m_, q_} {}
+    ~pcg_loop() { m->d_p = ring[0]; }
+    int setup() { return KMCF_OK; }
+
+    // r = b - Ap ; z ; r.z ; b.b    (:187-213)
+    int residual0()
+    {
+        cg_init_kernel<PRECOND><<<vg, KMCF_BLOCK, 0, st>>>(n, m->d_r, m->d_Ap, m->d_dinv, m->d_part_b, m->d_part_c);
+        KMCF_HIP(hipGetLastError());
+        if (multi) {
+            cg_finalize_kernel<<<1, KMCF_BLOCK, 0, st>>>(prz_loc, 0, pbb_loc, 1, S, 0);
             KMCF_HIP(hipGetLastError());
-            if (nf) pending = 0;
-            m->d_p = ring[k % B];                  // (every SpMV path reads m->d_p when it launches)
-            KMCF_TRY(kmcf_spmv_device(m, true, true));
-            if (multi) {
-                cg_finalize_kernel<<<1, KMCF_BLOCK, 0, st>>>(ppap_loc, 2, pr_none(), -1, S, 1);
-                KMCF_HIP(hipGetLastError());
-                KMCF_TRY(kmcf_comm_allreduce_sum(c, &S->red[2], 1));
-            }
-            ++pending;
-            cg_xr_kernel<PRECOND><<<vg, KMCF_BLOCK, 0, st>>>(n, m->d_r, m->d_Ap, m->d_dinv, ppap, S, parity, m->d_part_b, k % B, pending);
-            KMCF_HIP(hipGetLastError());
-            if (multi) {
-                cg_finalize_kernel<<<1, KMCF_BLOCK, 0, st>>>(prz_loc, 0, pr_none(), -1, S, 1);
-                KMCF_HIP(hipGetLastError());
-                KMCF_TRY(kmcf_comm_allreduce_sum(c, &S->red[0], 1));
-            }
+            KMCF_TRY(kmcf_comm_allreduce_sum(c, &S->red[0], 2));
         }
-        launched += chunk;
-        if (check_tol) KMCF_TRY(cg_chunk_check(c, S, st, &done));
+        direct = multi && c->nranks > 1 && kmcf_p2p_direct(m);
+        halo0 = direct ? *kmcf_p2p_halo_seq(m, 0) : 0;
+        B = multi ? 1 : std::min(std::max(kmcf_opt_int(c, KNOB_CG_XBATCH, KMCF_CG_XBATCH_DEFAULT), 1), 4);
+        for (int j = 1; j < B; ++j) {
+            if (!m->d_p_ring[j - 1]) {
+                const size_t len = (size_t)n + m->n_halo + 2;
+                KMCF_TRY(kmcf_dev_alloc(&m->d_p_ring[j - 1], len, false));
+                KMCF_HIP(hipMemsetAsync(m->d_p_ring[j - 1], 0, len * sizeof(double), st));
+            }
+            ring[j] = m->d_p_ring[j - 1];
+        }
+        return KMCF_OK;
     }
-    m->xring = xring_at(ring, B, launched + 1);    // the ring as the next loop head would see it: pending updates last
-    if (direct) {       // one SpMV (put, consumption, acknowledgement) per iteration that went on
-        const u64 executed = done ? (u64)c->h_pinned[1] : (u64)launched;
-        *kmcf_p2p_halo_seq(m, 0) = *kmcf_p2p_halo_seq(m, 1) = halo0 + executed;
+
+    // iteration k (the reference's k): loop head | SpMV + p.Ap | r, z update + r.z
+    int iteration(int k)
+    {
+        // loop head: all `pending` updates of x if the ring is full, none otherwise; p_k into slot k % B
+        const int nf = pending == B ? B : 0;
+        cg_p_launch<PRECOND>(nf, vg, st, n, xring_at(ring, B, k), ring[(k - 1) % B], ring[k % B], m->d_r, m->d_dinv, prz, pbb, S, k,
+                             k == 1 ? 1 : 0, tol2, check_tol, m->d_x, pending);
+        KMCF_HIP(hipGetLastError());
+        if (nf) pending = 0;
+        m->d_p = ring[k % B];                      // (every SpMV path reads m->d_p when it launches)
+        KMCF_TRY(kmcf_spmv_device(m, true, true));
+        if (multi) {
+            cg_finalize_kernel<<<1, KMCF_BLOCK, 0, st>>>(ppap_loc, 2, pr_none(), -1, S, 1);
+            KMCF_HIP(hipGetLastError());
+            KMCF_TRY(kmcf_comm_allreduce_sum(c, &S->red[2], 1));
+        }
+        ++pending;
+        cg_xr_kernel<PRECOND><<<vg, KMCF_BLOCK, 0, st>>>(n, m->d_r, m->d_Ap, m->d_dinv, ppap, S, k & 1, m->d_part_b, k % B, pending);
+        KMCF_HIP(hipGetLastError());
+        if (multi) {
+            cg_finalize_kernel<<<1, KMCF_BLOCK, 0, st>>>(prz_loc, 0, pr_none(), -1, S, 1);
+            KMCF_HIP(hipGetLastError());
+            KMCF_TRY(kmcf_comm_allreduce_sum(c, &S->red[0], 1));
+        }
+        return KMCF_OK;
     }
-    // the loop condition is evaluated once more after the last iteration (:217): it
-    // decides `converged` and provides the printed residual (:273)
-    if (!done) {
-        if (!(flags & 2) || multi) {               // (with flag 2 the caller's output kernel forms this last r.z itself ...
+
+    int after(const kmcf_cg_loop_end &e, kmcf_cg_result *res)
+    {
+        const kmcf_xring xring = xring_at(ring, B, e.launched + 1);    // the ring as the next loop head would see it: pending updates last
+        if (res) res->xring = xring;
+        if (direct) *kmcf_p2p_halo_seq(m, 0) = *kmcf_p2p_halo_seq(m, 1) = kmcf_cg_classic_halo_seq(halo0, e);
+        // the loop condition is evaluated once more after the last iteration (:217): it decides `converged` and provides
+        // the printed residual (:273)
+        if (!e.done && (!q.caller_collects || multi)) {    // (one rank: the caller's output kernel forms this last r.z itself ...
             cg_tail_kernel<<<1, KMCF_BLOCK, 0, st>>>(prz, S);
             KMCF_HIP(hipGetLastError());
         }
-        if (!(flags & 2)) {                        //  ... and applies the pending x update on its way)
-            cg_x_kernel<<<vg, KMCF_BLOCK, 0, st>>>(n, m->d_x, m->xring, S);
+        if (!e.done && !q.caller_collects) {               //  ... and applies the pending x updates on its way)
+            cg_x_kernel<<<vg, KMCF_BLOCK, 0, st>>>(n, m->d_x, xring, S);
             KMCF_HIP(hipGetLastError());
         }
+        return KMCF_OK;
     }
-    KMCF_HIP(hipEventRecord(c->ev_t1, st));
-    if (flags & 2) return KMCF_OK;                 // the caller's output kernel writes the scalars to the host
-    KMCF_HIP(hipMemcpyAsync(c->h_scal, S, sizeof(kmcf_scalars), hipMemcpyDeviceToHost, st));
-    return pcg_collect(m, tol2, absolute, stats);
-}
+};
 
 // ------------------------------------------------------------------------------------------------
 // Single-reduction PCG (Chronopoulos & Gear): the same Krylov iterates in exact arithmetic, but both
@@ -774,116 +760,107 @@ __global__ __launch_bounds__(KMCF_BLOCK) void cg1_finalize_kernel(part_ref pg, p
     if (threadIdx.x == 0) { S->red[0] = g; S->red[1] = d; S->red[2] = b; }
 }
 
-template <bool PRECOND>
-int pcg1_loop(kmcf_matrix *m, double tol, int max_it, int fixed_iters, int absolute, kmcf_solve_stats_t *stats, int flags = 0)
-{
-    kmcf_comm *c = m->comm;
-    hipStream_t st = c->stream;
-    const int n = m->n_loc;
-    const int vg = kmcf_vec_grid(n);
-    const bool multi = c->nranks > 1 || c->force_collectives;
-    kmcf_scalars *S = m->d_S;
-    const double tol2 = tol * tol;
-    const int check_tol = fixed_iters > 0 ? 0 : (absolute ? 2 : 1);
-    const int limit = fixed_iters > 0 ? fixed_iters : max_it;
-    if (!m->d_pd) {
-        KMCF_TRY(kmcf_dev_alloc(&m->d_pd, (size_t)n + 2, false));
-        KMCF_TRY(kmcf_dev_alloc(&m->d_s, (size_t)n + 2, false));
-    }
-    part_ref pg_loc = pr1(m->d_part_b, vg);
-    part_ref pb_loc = pr1(m->d_part_c, vg);
-    part_ref pd_loc = pr_spmv(m);
-    part_ref pg = multi ? pr1(&S->red[0], 1) : pg_loc;
-    part_ref pd = multi ? pr1(&S->red[1], 1) : pd_loc;
-    part_ref pb = multi ? pr1(&S->red[2], 1) : pb_loc;
+kmcf_part4 part4_of(const part_ref &r) { return kmcf_part4{{r.p[0], r.p[1], r.p[2], r.p[3]}, {r.n[0], r.n[1], r.n[2], r.n[3]}}; }
 
-    if (!(flags & 1) || n == 0) KMCF_HIP(hipMemsetAsync(S, 0, sizeof(kmcf_scalars), st));      // (flag 1: the input kernel zeroed them)
-    KMCF_HIP(hipEventRecord(c->ev_t0, st));
-    if (!(flags & 1)) KMCF_HIP(hipMemcpyAsync(m->d_p, m->d_x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
-    KMCF_TRY(kmcf_spmv_device(m, false, false));                       // A x0
-    cg1_init_kernel<PRECOND><<<vg, KMCF_BLOCK, 0, st>>>(n, m->d_r, m->d_Ap, m->d_dinv, m->d_p, m->d_part_b, m->d_part_c);
-    KMCF_HIP(hipGetLastError());
-    // "direct" peer-to-peer protocol: the exchanges ride in the update kernel (cg1_update_p2p_kernel).  Sequence numbers
-    // are counted per LAUNCH here and set back to per EXECUTED exchange after the loop (kernels behind the stop return
-    // at once, on every rank alike): the protocol's parities and acknowledgement windows need dense numbers.
-    const bool fused = multi && c->nranks > 1 && kmcf_p2p_direct(m);
+template <bool PRECOND>
+struct pcg1_loop : cg_loop_state {
+    const part_ref pg_loc = pr1(m->d_part_b, vg), pb_loc = pr1(m->d_part_c, vg), pd_loc = pr_spmv(m);   // gamma, b.b, delta
+    const part_ref pg = reduced(pg_loc, 0), pd = reduced(pd_loc, 1), pb = reduced(pb_loc, 2);
+    const kmcf_part4 parts[3] = {part4_of(pg_loc), part4_of(pd_loc), part4_of(pb_loc)};   // as kmcf_p2p_allreduce_parts takes them
+    // "direct" peer-to-peer protocol: the exchanges ride in the update kernel (fused).  Sequence numbers are counted per
+    // LAUNCH in the loop and set back to per EXECUTED exchange after it (kmcf_cgplan.hpp).
+    bool fused = false;
     // where the all-reduce of a fused iteration runs: inside the update kernel (every block waits for the P flags: one
     // kernel fewer; right when every rank has a GPU of its own) or in a 1-block kernel in front of it (KMCF_P2P_AR=split:
     // ranks SHARING a GPU -- rehearsals -- otherwise fill it with waiting blocks); bench.py times both and keeps the faster
-    const char *ar = kmcf_opt(c, KNOB_P2P_AR);
-    const bool ar_inside = !(ar && strcmp(ar, "split") == 0);
-    const bool p2p_red = multi && c->nranks > 1 && c->p2p_active;
-    const u64 red0 = p2p_red ? kmcf_p2p_red_seq(c) : 0, halo0 = fused ? *kmcf_p2p_halo_seq(m, 0) : 0;
+    bool ar_inside = true;
+    bool p2p_red = false;                          // the group's reductions run over the peer-to-peer transport
+    u64 red0 = 0, halo0 = 0;
 
-    int launched = 0;
-    bool done = false;
-    int chunk_cap = check_tol ? 2 : KMCF_CHUNK_ITERS;                  // growing chunks, see pcg_loop
-    while (launched < limit && !done) {
-        int chunk = limit - launched;
-        if (chunk > chunk_cap) chunk = chunk_cap;
-        chunk_cap = std::min(2 * chunk_cap, KMCF_CHUNK_ITERS);
-        for (int i = 0; i < chunk; ++i) {
-            const int k = launched + i + 1;
-            const int parity = k & 1, first = (k == 1) ? 1 : 0;
-            KMCF_TRY(kmcf_spmv_device(m, true, true, fused ? 1 : 0));  // w = A z, delta partials
-            if (fused) {
-                const u64 sh = *kmcf_p2p_halo_seq(m, 0);
-                if (ar_inside) {
-                    const u64 sr = kmcf_p2p_next_red_seq(c);
-                    cg1_update_kernel<PRECOND, true><<<vg, KMCF_BLOCK, 0, st>>>(n, m->d_x, m->d_r, m->d_pd, m->d_s, m->d_p, m->d_Ap, m->d_dinv,
-                                                                                pg_loc, pd_loc, pb_loc, S, parity, first, tol2, check_tol,
-                                                                                m->d_part_b, kmcf_p2p_dev_of(m), sr, sh, sh + 1, 1);
-                } else {
-                    // KMCF_P2P_AR=split: finalize + exchange in a 1-block kernel of its own, the update kernel reads the sums
-                    const kmcf_part4 parts[3] = {{{pg_loc.p[0], pg_loc.p[1], pg_loc.p[2], pg_loc.p[3]}, {pg_loc.n[0], pg_loc.n[1], pg_loc.n[2], pg_loc.n[3]}},
-                                                 {{pd_loc.p[0], pd_loc.p[1], pd_loc.p[2], pd_loc.p[3]}, {pd_loc.n[0], pd_loc.n[1], pd_loc.n[2], pd_loc.n[3]}},
-                                                 {{pb_loc.p[0], pb_loc.p[1], pb_loc.p[2], pb_loc.p[3]}, {pb_loc.n[0], pb_loc.n[1], pb_loc.n[2], pb_loc.n[3]}}};
-                    KMCF_TRY(kmcf_p2p_allreduce_parts(c, parts, 3, S, 1));
-                    cg1_update_kernel<PRECOND, true><<<vg, KMCF_BLOCK, 0, st>>>(n, m->d_x, m->d_r, m->d_pd, m->d_s, m->d_p, m->d_Ap, m->d_dinv,
-                                                                                pg, pd, pb, S, parity, first, tol2, check_tol, m->d_part_b,
-                                                                                kmcf_p2p_dev_of(m), 0, sh, sh + 1, 0);
-                }
-                KMCF_HIP(hipGetLastError());
-                *kmcf_p2p_halo_seq(m, 1) = sh + 1;                      // the halo of the next SpMV is put
-                continue;
-            }
-            if (multi && c->p2p_active && c->nranks > 1) {
-                // finalize + exchange in one 1-block kernel (the b.b partials only count in the first iteration:
-                // later ones re-send stale ones, which nobody reads)
-                const kmcf_part4 parts[3] = {{{pg_loc.p[0], pg_loc.p[1], pg_loc.p[2], pg_loc.p[3]}, {pg_loc.n[0], pg_loc.n[1], pg_loc.n[2], pg_loc.n[3]}},
-                                             {{pd_loc.p[0], pd_loc.p[1], pd_loc.p[2], pd_loc.p[3]}, {pd_loc.n[0], pd_loc.n[1], pd_loc.n[2], pd_loc.n[3]}},
-                                             {{pb_loc.p[0], pb_loc.p[1], pb_loc.p[2], pb_loc.p[3]}, {pb_loc.n[0], pb_loc.n[1], pb_loc.n[2], pb_loc.n[3]}}};
-                KMCF_TRY(kmcf_p2p_allreduce_parts(c, parts, 3, S, 1));
-            } else if (multi) {
-                cg1_finalize_kernel<<<1, KMCF_BLOCK, 0, st>>>(pg_loc, pd_loc, pb_loc, first, S);
-                KMCF_HIP(hipGetLastError());
-                KMCF_TRY(kmcf_comm_allreduce_sum(c, &S->red[0], 3));
-            }
-            cg1_update_kernel<PRECOND, false><<<vg, KMCF_BLOCK, 0, st>>>(n, m->d_x, m->d_r, m->d_pd, m->d_s, m->d_p, m->d_Ap,
-                                                                         m->d_dinv, pg, pd, pb, S, parity, first, tol2,
-                                                                         check_tol, m->d_part_b, kmcf_p2p_dev{}, 0, 0, 0, 0);
+    pcg1_loop(kmcf_matrix *m_, const kmcf_cg_request &q_) : cg_loop_state{m_, q_} {}
+
+    int setup()
+    {
+        if (m->d_pd) return KMCF_OK;
+        KMCF_TRY(kmcf_dev_alloc(&m->d_pd, (size_t)n + 2, false));
+        return kmcf_dev_alloc(&m->d_s, (size_t)n + 2, false);
+    }
+
+    // r = b - A x0 ; z = r .* dinv (into d_p: the SpMV's input) ; gamma ; b.b
+    int residual0()
+    {
+        cg1_init_kernel<PRECOND><<<vg, KMCF_BLOCK, 0, st>>>(n, m->d_r, m->d_Ap, m->d_dinv, m->d_p, m->d_part_b, m->d_part_c);
+        KMCF_HIP(hipGetLastError());
+        fused = multi && c->nranks > 1 && kmcf_p2p_direct(m);
+        const char *ar = kmcf_opt(c, KNOB_P2P_AR);
+        ar_inside = !(ar && strcmp(ar, "split") == 0);
+        p2p_red = multi && c->nranks > 1 && c->p2p_active;
+        red0 = p2p_red ? kmcf_p2p_red_seq(c) : 0;
+        halo0 = fused ? *kmcf_p2p_halo_seq(m, 0) : 0;
+        return KMCF_OK;
+    }
+
+    template <bool P2P>
+    int update(int k, const part_ref &g, const part_ref &d, const part_ref &b, const kmcf_p2p_dev &dev, u64 seq_red, u64 seq_ack, u64 seq_put,
+               int ar_in)
+    {
+        cg1_update_kernel<PRECOND, P2P><<<vg, KMCF_BLOCK, 0, st>>>(n, m->d_x, m->d_r, m->d_pd, m->d_s, m->d_p, m->d_Ap, m->d_dinv, g, d, b, S, k & 1,
+                                                                   k == 1 ? 1 : 0, tol2, check_tol, m->d_part_b, dev, seq_red, seq_ack, seq_put, ar_in);
+        KMCF_HIP(hipGetLastError());
+        if (P2P) *kmcf_p2p_halo_seq(m, 1) = seq_put;                   // the halo of the next SpMV is put
+        return KMCF_OK;
+    }
+
+    // fused, the all-reduce inside the update kernel, which reads the local partials
+    int update_fused(int k)
+    {
+        const u64 sh = *kmcf_p2p_halo_seq(m, 0), sr = kmcf_p2p_next_red_seq(c);
+        return update<true>(k, pg_loc, pd_loc, pb_loc, kmcf_p2p_dev_of(m), sr, sh, sh + 1, 1);
+    }
+
+    // fused with KMCF_P2P_AR=split: finalize + exchange in a 1-block kernel of its own, the update kernel reads the sums
+    int update_fused_split(int k)
+    {
+        const u64 sh = *kmcf_p2p_halo_seq(m, 0);
+        KMCF_TRY(kmcf_p2p_allreduce_parts(c, parts, 3, S, 1));
+        return update<true>(k, pg, pd, pb, kmcf_p2p_dev_of(m), 0, sh, sh + 1, 0);
+    }
+
+    // the reduction apart from the update: over peer-to-peer, finalize + exchange in one 1-block kernel (the b.b partials
+    // only count in the first iteration: later ones re-send stale ones, which nobody reads); over collectives, a 1-block
+    // finalize and the transport's all-reduce; one rank: none, the update kernel sums the partial arrays
+    int update_separate(int k)
+    {
+        if (p2p_red) {
+            KMCF_TRY(kmcf_p2p_allreduce_parts(c, parts, 3, S, 1));
+        } else if (multi) {
+            cg1_finalize_kernel<<<1, KMCF_BLOCK, 0, st>>>(pg_loc, pd_loc, pb_loc, k == 1 ? 1 : 0, S);
             KMCF_HIP(hipGetLastError());
+            KMCF_TRY(kmcf_comm_allreduce_sum(c, &S->red[0], 3));
         }
-        launched += chunk;
-        if (check_tol) KMCF_TRY(cg_chunk_check(c, S, st, &done));
+        return update<false>(k, pg, pd, pb, kmcf_p2p_dev{}, 0, 0, 0, 0);
     }
-    if (p2p_red && !fused) kmcf_p2p_set_red_seq(c, red0 + (done ? (u64)c->h_pinned[1] + 1 : (u64)launched));   // (skipped ones: no number)
-    if (fused) {
-        // exchanges that really ran: one all-reduce, one consumed halo and one acknowledgement per executed update kernel
-        // (iterations that went on + the one that stopped); a put by every update that went on + the stand-alone first
-        const u64 executed = done ? (u64)c->h_pinned[1] + 1 : (u64)launched;
-        kmcf_p2p_set_red_seq(c, red0 + executed);
-        u64 &hs = *kmcf_p2p_halo_seq(m, 0), &hp = *kmcf_p2p_halo_seq(m, 1);
-        hs = halo0 + executed;
-        hp = done ? hs : hs + 1;
-        if (hp > hs) {
-            // the loop ended on its iteration limit: the last update has put a halo no SpMV will read.  Consumed
-            // unread: acknowledged, so that the sequence stays dense (every rank does the same)
-            ++hs;
-            KMCF_TRY(kmcf_p2p_direct_ack(m, hs, false));
+
+    int iteration(int k)
+    {
+        KMCF_TRY(kmcf_spmv_device(m, true, true, fused ? 1 : 0));      // w = A z, delta partials
+        // (the fused transports named first: cg1_update_kernel<*, true> stays ahead of <*, false> in the code object)
+        if (fused) return ar_inside ? update_fused(k) : update_fused_split(k);
+        return update_separate(k);
+    }
+
+    int after(const kmcf_cg_loop_end &e, kmcf_cg_result *)
+    {
+        if (p2p_red && !fused) kmcf_p2p_set_red_seq(c, kmcf_cg1_red_seq(red0, e));
+        if (fused) {
+            const kmcf_cg1_fused_seq s = kmcf_cg1_fused_seq_after(red0, halo0, e);
+            kmcf_p2p_set_red_seq(c, s.red);
+            *kmcf_p2p_halo_seq(m, 0) = s.halo_consumed;
+            *kmcf_p2p_halo_seq(m, 1) = s.halo_put;
+            if (s.ack_owed) KMCF_TRY(kmcf_p2p_direct_ack(m, s.halo_consumed, false));
         }
-    }
-    if (!done) {   // r.z after the last iteration, for the printed residual
+        if (e.done) return KMCF_OK;
+        // r.z after the last iteration, for the printed residual
         if (multi) {
             cg_finalize_kernel<<<1, KMCF_BLOCK, 0, st>>>(pg_loc, 0, pr_none(), -1, S, 1);
             KMCF_HIP(hipGetLastError());
@@ -891,77 +868,101 @@ int pcg1_loop(kmcf_matrix *m, double tol, int max_it, int fixed_iters, int absol
         }
         cg_tail_kernel<<<1, KMCF_BLOCK, 0, st>>>(pg, S);
         KMCF_HIP(hipGetLastError());
+        return KMCF_OK;
     }
+};
+
+static_assert(KMCF_CG_CHUNK_MAX == KMCF_CHUNK_ITERS, "kmcf_cgplan.hpp carries its own copy of the largest chunk");
+
+// The driver.  m->d_r holds b, m->d_x the start guess, m->d_dinv 1/diag; q.x0_in_p: d_p already holds x0 and the
+// scalars are zero (the fused input kernel of kmcf_pcg_jacobi wrote both).
+template <class REC>
+int cg_run_loop(kmcf_matrix *m, const kmcf_cg_request &q, kmcf_solve_stats_t *stats, kmcf_cg_result *res)
+{
+    REC rec(m, q);
+    kmcf_comm *c = rec.c;
+    hipStream_t st = rec.st;
+    const int limit = q.fixed_iters > 0 ? q.fixed_iters : q.max_it;
+    KMCF_TRY(rec.setup());
+    if (!q.x0_in_p || rec.n == 0) KMCF_HIP(hipMemsetAsync(rec.S, 0, sizeof(kmcf_scalars), st));
+    KMCF_HIP(hipEventRecord(c->ev_t0, st));
+    // p <- x0 ; Ap = A x0    (:178-186)
+    if (!q.x0_in_p) KMCF_HIP(hipMemcpyAsync(m->d_p, m->d_x, (size_t)rec.n * sizeof(double), hipMemcpyDeviceToDevice, st));
+    KMCF_TRY(kmcf_spmv_device(m, false, false));
+    KMCF_TRY(rec.residual0());
+    int launched = 0, cap = kmcf_cg_first_chunk_cap(rec.check_tol != 0);
+    bool done = false;
+    while (launched < limit && !done) {
+        const int chunk = kmcf_cg_next_chunk(cap, limit - launched);
+        for (int i = 0; i < chunk; ++i) KMCF_TRY(rec.iteration(launched + i + 1));
+        launched += chunk;
+        if (rec.check_tol) KMCF_TRY(cg_chunk_check(c, rec.S, st, &done));
+    }
+    KMCF_TRY(rec.after(kmcf_cg_loop_end{done, done ? c->h_pinned[1] : 0, launched}, res));
     KMCF_HIP(hipEventRecord(c->ev_t1, st));
-    if (flags & 2) return KMCF_OK;
-    KMCF_HIP(hipMemcpyAsync(c->h_scal, S, sizeof(kmcf_scalars), hipMemcpyDeviceToHost, st));
-    return pcg_collect(m, tol2, absolute, stats);
+    if (q.caller_collects) return KMCF_OK;         // the caller's output kernel writes the scalars to the host
+    KMCF_HIP(hipMemcpyAsync(c->h_scal, rec.S, sizeof(kmcf_scalars), hipMemcpyDeviceToHost, st));
+    return pcg_collect(m, rec.tol2, q.call == KMCF_CG_CALL_ABSOLUTE, stats);
 }
 
 }  // namespace
 
-// Solve on the matrix workspace: m->d_r holds b, m->d_x the start guess, m->d_dinv 1/diag.
-static int pcg_workspace_run(kmcf_matrix *m, bool precond, double tol, int max_it, int fixed_iters, kmcf_solve_stats_t *stats, int flags);
-
-static int pcg_workspace_flags(kmcf_matrix *m, bool precond, double tol, int max_it, int fixed_iters, kmcf_solve_stats_t *stats, int flags)
-{
-    kmcf_comm *c = m->comm;
-    KMCF_TRY(kmcf_group_rendezvous(c));                   // (in-process test groups: see kmcf_internal.hpp)
-    c->in_solve = true;
-    const int rc = pcg_workspace_run(m, precond, tol, max_it, fixed_iters, stats, flags);
-    c->in_solve = false;
-    return rc;
-}
-
-// The single-reduction recurrence as ONE register-resident launch (kmcf_cgr.hip), for matrices whose tiles are all
-// resident at once.  Workspace in, workspace out, scalars in d_S -- like the loops.
-static int pcg_resident(kmcf_matrix *m, bool precond, double tol, int max_it, int fixed_iters, kmcf_solve_stats_t *stats, int flags, bool classic)
+// A recurrence as ONE register-resident launch (kmcf_cgr.hip), for matrices whose tiles are all resident at once.
+// Workspace in, workspace out (or q.b_src / q.x_user in their place), scalars in d_S -- like the loops.
+static int pcg_resident(kmcf_matrix *m, const kmcf_cg_request &q, kmcf_solve_stats_t *stats, bool classic)
 {
     kmcf_comm *c = m->comm;
     hipStream_t st = c->stream;
     KMCF_HIP(hipEventRecord(c->ev_t0, st));
-    KMCF_TRY(kmcf_cgr_solve(m, precond, tol, max_it, fixed_iters, classic));
-    m->last_solve_resident = true;
+    KMCF_TRY(kmcf_cgr_solve(m, q.precond, q.tol, q.max_it, q.fixed_iters, classic, q.b_src, q.x_user));
     KMCF_HIP(hipEventRecord(c->ev_t1, st));
-    if (flags & 2) return KMCF_OK;                 // the caller's output kernel writes the scalars to the host
+    if (q.caller_collects) return KMCF_OK;         // the caller's output kernel writes the scalars to the host
     KMCF_HIP(hipMemcpyAsync(c->h_scal, m->d_S, sizeof(kmcf_scalars), hipMemcpyDeviceToHost, st));
-    return pcg_collect(m, tol * tol, 0, stats);
+    return pcg_collect(m, q.tol * q.tol, 0, stats);
+}
+
+static kmcf_cg_path cg_path(kmcf_matrix *m, kmcf_cg_call call, bool has_limit)
+{
+    const kmcf_comm *c = m->comm;
+    return kmcf_cg_choose_path(call, c->nranks > 1 || c->force_collectives, kmcf_cg_single_reduction(m), kmcf_cgr_classic_applies(m),
+                               has_limit, [m] { return kmcf_cgr_usable(m); });
 }
 
 bool kmcf_pcg_resident_applies(kmcf_matrix *m)
 {
-    if (kmcf_cg_single_reduction(m)) return kmcf_cgr_usable(m);
-    return kmcf_cgr_classic_applies(m) && kmcf_cgr_usable(m);
+    const kmcf_comm *c = m->comm;
+    return kmcf_cg_resident_applies(c->nranks > 1 || c->force_collectives, kmcf_cg_single_reduction(m), kmcf_cgr_classic_applies(m),
+                                    [m] { return kmcf_cgr_usable(m); });
 }
 
-static int pcg_workspace_run(kmcf_matrix *m, bool precond, double tol, int max_it, int fixed_iters, kmcf_solve_stats_t *stats, int flags)
+// The one entry of every solve on the matrix workspace; the path is decided here and nowhere else (the table:
+// kmcf_cgplan.hpp).
+int kmcf_cg_solve(kmcf_matrix *m, const kmcf_cg_request &q, kmcf_solve_stats_t *stats, kmcf_cg_result *res)
 {
-    m->last_solve_resident = false;
-    // classic = the reference's recurrence and operation order (default for one rank);
-    // cg1r = single-reduction variant (default for multi-rank groups)
-    if (kmcf_cg_single_reduction(m)) {
-        const bool resident = kmcf_cgr_usable(m);
-        KMCF_TRY(kmcf_cgr_agreed(m));
-        if (resident && (fixed_iters > 0 || max_it > 0)) return pcg_resident(m, precond, tol, max_it, fixed_iters, stats, flags, false);
-        KMCF_CHECK(!m->solve_x_user && !m->solve_b_src, KMCF_ERR_STATE, "solve set up for a resident launch that does not apply");
-        if (precond) return pcg1_loop<true>(m, tol, max_it, fixed_iters, 0, stats, flags);
-        return pcg1_loop<false>(m, tol, max_it, fixed_iters, 0, stats, flags);
-    }
-    // the reference's recurrence as ONE register-resident launch, one rank: two reduction points per iteration, i.e. two
-    // waits for everybody's sums against three kernel boundaries (us per iteration, resident / loop: 5 nm device, 286 tiles:
-    // 8.2 / 10.9-12.6; a rank's eighth of the 40 nm matrix, 881 tiles: 13.4 / 15.4 -- until the launch was specialised per
-    // recurrence, lost two barriers and learnt to delay its first polls the eighth read 16.3 / 14.8 and the limit was 512
-    // tiles) -- wherever a resident launch fits (<= 1024 tiles; KMCF_CGR_CLASSIC_TILES lowers the limit)
-    if (kmcf_cgr_classic_applies(m) && (fixed_iters > 0 || max_it > 0) && kmcf_cgr_usable(m))
-        return pcg_resident(m, precond, tol, max_it, fixed_iters, stats, flags, true);
-    KMCF_CHECK(!m->solve_x_user && !m->solve_b_src, KMCF_ERR_STATE, "solve set up for a resident launch that does not apply");
-    if (precond) return pcg_loop<true>(m, tol, max_it, fixed_iters, 0, stats, flags);
-    return pcg_loop<false>(m, tol, max_it, fixed_iters, 0, stats, flags);
+    kmcf_comm *c = m->comm;
+    KMCF_TRY(kmcf_group_rendezvous(c));                   // (in-process test groups: see kmcf_internal.hpp)
+    c->in_solve = true;
+    struct leave_t { kmcf_comm *c; ~leave_t() { c->in_solve = false; } } leave{c};
+    const kmcf_cg_path path = cg_path(m, q.call, q.fixed_iters > 0 || q.max_it > 0);
+    // (a group's resident plan compares the ranks' group options: a difference found there is reported by every solve)
+    if (q.call == KMCF_CG_CALL_RESIDENT_OK && (path == KMCF_CG_RESIDENT_CG1R || path == KMCF_CG_LOOP_CG1R)) KMCF_TRY(kmcf_cgr_agreed(m));
+    if (res) *res = kmcf_cg_result{path, {}};
+    if (kmcf_cg_is_resident(path)) return pcg_resident(m, q, stats, path == KMCF_CG_RESIDENT_CLASSIC);
+    KMCF_CHECK(!q.x_user && !q.b_src, KMCF_ERR_STATE, "solve set up for a resident launch that does not apply");
+    int rc = KMCF_OK;
+    // (cg1r ahead of classic, a with_bools each: the kernels' template instances come out in the code object in the
+    //  order of their first use here, and this order keeps the object what it was)
+    if (path == KMCF_CG_LOOP_CG1R)
+        with_bools([&](auto precond) { rc = cg_run_loop<pcg1_loop<decltype(precond)::value>>(m, q, stats, res); }, q.precond);
+    else
+        with_bools([&](auto precond) { rc = cg_run_loop<pcg_loop<decltype(precond)::value>>(m, q, stats, res); }, q.precond);
+    return rc;
 }
 
-int kmcf_pcg_workspace(kmcf_matrix *m, bool precond, double tol, int max_it, int fixed_iters, kmcf_solve_stats_t *stats)
+int kmcf_pcg_workspace(kmcf_matrix *m, bool precond, double tol, int max_it, int fixed_iters, kmcf_solve_stats_t *stats,
+                       const double *b_src, double *x_user)
 {
-    return pcg_workspace_flags(m, precond, tol, max_it, fixed_iters, stats, 0);
+    return kmcf_cg_solve(m, kmcf_cg_request{KMCF_CG_CALL_RESIDENT_OK, precond, tol, max_it, fixed_iters, false, false, b_src, x_user}, stats);
 }
 
 namespace {
@@ -1018,27 +1019,6 @@ __global__ __launch_bounds__(KMCF_BLOCK) void scale_vector_kernel(int n, double 
 
 }  // namespace
 
-// CG with the absolute stopping rule of solve_sparse_CG_Jacobi on the workspace, as a loop of kernels.  One rank: the
-// reference's recurrence (whatever KMCF_CG_VARIANT says: the one-rank band-edge solve is what it always was).  A rank
-// group: the group's recurrence, chosen as for K.  Never the resident launch: the system in the matrix is not the one a
-// resident plan of m was made for, and that plan and its buffers are not touched.
-static int cg_absolute_loop(kmcf_matrix *m, bool precond, double tol, int max_it, kmcf_solve_stats_t *stats)
-{
-    kmcf_comm *c = m->comm;
-    if (!(c->nranks > 1 || c->force_collectives))
-        return precond ? pcg_loop<true>(m, tol, max_it, 0, 1, stats) : pcg_loop<false>(m, tol, max_it, 0, 1, stats);
-    KMCF_TRY(kmcf_group_rendezvous(c));                   // (in-process test groups: see kmcf_internal.hpp)
-    c->in_solve = true;
-    m->last_solve_resident = false;
-    int rc;
-    if (kmcf_cg_single_reduction(m))
-        rc = precond ? pcg1_loop<true>(m, tol, max_it, 0, 1, stats) : pcg1_loop<false>(m, tol, max_it, 0, 1, stats);
-    else
-        rc = precond ? pcg_loop<true>(m, tol, max_it, 0, 1, stats) : pcg_loop<false>(m, tol, max_it, 0, 1, stats);
-    c->in_solve = false;
-    return rc;
-}
-
 // solve_sparse_CG_Jacobi on the workspace: m->d_r = rhs, m->d_x = start guess (internal order).
 // Scales A (in place), rhs and the guess, solves, un-scales the solution into m->d_x.  If d_rhs_user is
 // given, the scaled rhs is written back to it (the reference scales the caller's rhs in place, :740).
@@ -1067,8 +1047,9 @@ int kmcf_scaled_cg_workspace(kmcf_matrix *m, double tol, int max_iterations, dou
     if (d_rhs_user) KMCF_TRY(kmcf_vec_out(m, d_rhs_user, m->d_r));
     // plain CG on the scaled system; the reference carries r = A y - b and p = -r (:826-836),
     // the same iterates as r = b - A y, p = r used here.  The unpreconditioned loop never
-    // touches d_dinv, so `dis` stays intact.
-    KMCF_TRY(cg_absolute_loop(m, false, std::sqrt(tol * tol), max_iterations, stats));
+    // touches d_dinv, so `dis` stays intact.  (The absolute rule as a loop of kernels, never the resident launch: the
+    // system in the matrix is not the one a resident plan of m was made for, and that plan and its buffers are not touched.)
+    KMCF_TRY(kmcf_cg_solve(m, kmcf_cg_request{KMCF_CG_CALL_ABSOLUTE, false, std::sqrt(tol * tol), max_iterations, 0}, stats));
     scale_vector_kernel<<<g, KMCF_BLOCK, 0, c->stream>>>(n, m->d_x, dis, 0);      // y = D^-1/2 y' (:864)
     KMCF_HIP(hipGetLastError());
     return KMCF_OK;
@@ -1083,18 +1064,12 @@ int kmcf_scaled_cg_workspace(kmcf_matrix *m, double tol, int max_iterations, dou
 // m->d_dinv = 1/diag on entry.
 int kmcf_jacobi_cg_workspace_absolute(kmcf_matrix *m, double tol, int max_iterations, kmcf_solve_stats_t *stats)
 {
-    return cg_absolute_loop(m, true, tol, max_iterations, stats);
+    return kmcf_cg_solve(m, kmcf_cg_request{KMCF_CG_CALL_ABSOLUTE, true, tol, max_iterations, 0}, stats);
 }
 
 int kmcf_pcg_workspace_loop(kmcf_matrix *m, double tol, int max_it, kmcf_solve_stats_t *stats)
 {
-    kmcf_comm *c = m->comm;
-    KMCF_TRY(kmcf_group_rendezvous(c));                   // (in-process test groups: see kmcf_internal.hpp)
-    c->in_solve = true;
-    m->last_solve_resident = false;
-    const int rc = kmcf_cg_single_reduction(m) ? pcg1_loop<true>(m, tol, max_it, 0, 0, stats) : pcg_loop<true>(m, tol, max_it, 0, 0, stats);
-    c->in_solve = false;
-    return rc;
+    return kmcf_cg_solve(m, kmcf_cg_request{KMCF_CG_CALL_LOOP_ONLY, true, tol, max_it, 0}, stats);
 }
 
 extern "C" int kmcf_solve_sparse_CG_Jacobi(kmcf_matrix *m, double *d_rhs, double *d_x, double tol, int max_iterations,
@@ -1209,10 +1184,13 @@ extern "C" int kmcf_pcg_jacobi(kmcf_matrix *m, double *d_r, double *d_x, const d
         cg_in_kernel<<<perm_grid(n), KMCF_BLOCK, 0, c->stream>>>(n, m->d_perm, d_r, d_x, d_diag_inv, m->d_r, m->d_x, m->d_p, m->d_dinv, m->d_S);
         KMCF_HIP(hipGetLastError());
     }
-    KMCF_TRY(pcg_workspace_flags(m, d_diag_inv != nullptr, relative_tolerance, max_iterations, fixed_iters, stats, 1 | 2));
+    kmcf_cg_request q{KMCF_CG_CALL_RESIDENT_OK, d_diag_inv != nullptr, relative_tolerance, max_iterations, fixed_iters};
+    q.x0_in_p = q.caller_collects = true;
+    kmcf_cg_result solved{};
+    KMCF_TRY(kmcf_cg_solve(m, q, stats, &solved));
     const double t_b = trace ? now() : 0.0;
-    const bool tail_here = !(c->nranks > 1 || c->force_collectives) && !kmcf_cg_single_reduction(m) && n > 0 && !m->last_solve_resident;
-    cg_out_kernel<<<perm_grid(std::max(n, 1)), KMCF_BLOCK, 0, c->stream>>>(n, m->d_perm, m->d_r, m->d_x, m->xring, d_r, d_x, m->d_S, c->h_scal,
+    const bool tail_here = kmcf_cg_tail_in_output(solved.path, c->nranks > 1 || c->force_collectives, n);
+    cg_out_kernel<<<perm_grid(std::max(n, 1)), KMCF_BLOCK, 0, c->stream>>>(n, m->d_perm, m->d_r, m->d_x, solved.xring, d_r, d_x, m->d_S, c->h_scal,
                                                                            tail_here ? pr1(m->d_part_b, kmcf_vec_grid(n)) : pr_none());
     KMCF_HIP(hipGetLastError());
     KMCF_HIP(hipEventRecord(c->ev_call1, c->stream));

@@ -841,7 +841,7 @@ int kmcf_cgr_plan_info(kmcf_matrix *m, int *tpb, int *g1, int *nblocks)
 
 // Enqueues one resident solve on the workspace (m->d_r: b in, r out; m->d_x: x0 in, x out; m->d_dinv), scalars into
 // m->d_S.  The caller synchronises and then calls kmcf_cgr_check.
-int kmcf_cgr_solve(kmcf_matrix *m, bool precond, double tol, int max_it, int fixed_iters, bool classic)
+int kmcf_cgr_solve(kmcf_matrix *m, bool precond, double tol, int max_it, int fixed_iters, bool classic, const double *b_src, double *x_user)
 {
     kmcf_cgr *g = m->cgr;
     KMCF_CHECK(g && g->tpb > 0, KMCF_ERR_STATE, "kmcf_cgr_solve: the matrix has no resident plan");
@@ -888,8 +888,8 @@ int kmcf_cgr_solve(kmcf_matrix *m, bool precond, double tol, int max_it, int fix
     A.stream = reinterpret_cast<const sell_pair *>(m->d_sell);
     A.dict = m->d_dict; A.diagv = m->d_diagv;
     A.r = m->d_r; A.x = m->d_x; A.dinv = precond ? m->d_dinv : nullptr;
-    A.b_src = m->solve_b_src ? m->solve_b_src : m->d_r;
-    A.x_user = m->solve_x_user;
+    A.b_src = b_src ? b_src : m->d_r;
+    A.x_user = x_user;
     A.perm = m->d_perm;
     A.S = m->d_S;
     A.zll = g->d_zll; A.zwords = (long long)g->zwords;

@@ -16,6 +16,7 @@
 
 #include "kmcfield.h"
 #include "kmcf_knobs.hpp"
+#include "kmcf_cgplan.hpp"
 
 // ---------------------------------------------------------------- errors
 void kmcf_set_error(const char *fmt, ...);
@@ -283,12 +284,6 @@ struct kmcf_matrix {
     unsigned int *d_long_ctr = nullptr;
     kmcf_subop *sub = nullptr;         // optional: y[sub rows] += S x_sub after the CSR part (T matrix)
     kmcf_p2p_halo *p2p = nullptr;      // halo landing zone / flags in the peer windows (p2p transport)
-    // optional, for the length of one kmcf_pcg_workspace call that runs resident (kmcf_pcg_resident_applies): the right-hand
-    // side where it lies (internal order, read-only) instead of d_r, and the start guess / solution in the CALLER's order and
-    // place instead of d_x -- the K solve of a KMC step then needs no copy and no permuting kernel around its one launch
-    const double *solve_b_src = nullptr;
-    double *solve_x_user = nullptr;
-    bool last_solve_resident = false;  // the solve enqueued last ran as ONE resident launch (its scalars are complete: no tail for the output kernel to form)
     struct kmcf_cgr *cgr = nullptr;    // plan and buffers of the register-resident solve (kmcf_cgr.hip); tpb == 0: does not qualify
     int row0 = 0;                 // displs[rank]
     int64_t nnz = 0;
@@ -334,7 +329,6 @@ struct kmcf_matrix {
     double *d_dinv = nullptr;
     double *d_p_ring[3] = {nullptr, nullptr, nullptr};   // classic loop with KMCF_CG_XBATCH = B > 1: p_k lives in ring slot k % B, slot 0
                                        // is d_p itself, slots 1 .. B-1 are these (sized and zeroed like d_p at the first batched solve)
-    kmcf_xring xring = {};             // the ring as the last classic loop left it (cg_x_kernel, cg_out_kernel)
     double *d_pd = nullptr;            // single-reduction CG: search direction p (d_p then carries z)
     double *d_s = nullptr;             // single-reduction CG: s = A p by recurrence
     double *d_part_a = nullptr;        // pAp partials: [0, MAXP) interior rows | [MAXP, 2 MAXP) boundary rows |
@@ -441,10 +435,6 @@ struct kmcf_kstate {
 // kstate.hip: site classes (d_cls) and their copy per internal column (d_cls_col) for the current elements and charges
 int kmcf_k_classes_async(kmcf_kstate *k, const int *d_site_element, const int *d_site_charge, const int *d_metals,
                          int num_metals);
-// cg.hip: Jacobi-PCG on the workspace (m->d_r = b, m->d_x = start guess, m->d_dinv) as a loop of kernels, never as the
-// resident launch: for systems other than the one m's resident plan was made for.  The rank group's recurrence.
-int kmcf_pcg_workspace_loop(kmcf_matrix *m, double tol, int max_it, kmcf_solve_stats_t *stats);
-
 void kmcf_spmv_plan_free(kmcf_matrix *m);  // frees the SpMV plan's buffers (kmcf_spmv.hip)
 void kmcf_sell_refine_order(const kmcf_comm *c, int n_short, int n_cols, const int *rp, const int *col, std::vector<int> &perm,
                             std::vector<int> &cuts);
@@ -650,6 +640,37 @@ int kmcf_matrix_set_dictionary(kmcf_matrix *m, const double *h_dict, int nd);
 // cg.hip
 int kmcf_halo_exchange_begin(kmcf_matrix *m);   // pack + send/recv on the comm stream
 int kmcf_halo_exchange_end(kmcf_matrix *m);     // compute stream waits for the halo
+// A CG solve on the matrix workspace: m->d_r holds b (r on return), m->d_x the start guess (x on return), m->d_dinv
+// 1/diag if precond.  What a caller asks ...
+struct kmcf_cg_request {
+    kmcf_cg_call call;                 // stopping rule, and whether the resident launch may serve it (kmcf_cgplan.hpp)
+    bool precond;
+    double tol;
+    int max_it, fixed_iters;           // fixed_iters > 0: that many iterations, no stopping rule
+    bool x0_in_p = false;              // d_p already holds x0 and the scalars are zero (the caller's input kernel wrote both)
+    bool caller_collects = false;      // the caller synchronises and reads the scalars itself: it has more work to enqueue first
+    // only for a solve that runs resident (the caller has asked kmcf_pcg_resident_applies): the right-hand side where it
+    // lies (internal order, read-only) instead of d_r, and the start guess / solution in the CALLER's order and place
+    // instead of d_x -- the K solve of a KMC step then needs no copy and no permuting kernel around its one launch
+    const double *b_src = nullptr;
+    double *x_user = nullptr;
+};
+// ... and what it needs to know afterwards: the path the solve took, and the p ring as a classic loop left it (updates of
+// x still pending are its last entries; a caller that collects applies them in its output kernel)
+struct kmcf_cg_result {
+    kmcf_cg_path path;
+    kmcf_xring xring;
+};
+int kmcf_cg_solve(kmcf_matrix *m, const kmcf_cg_request &q, kmcf_solve_stats_t *stats, kmcf_cg_result *res = nullptr);
+// its callers by name.  Relative rule, resident where that applies (K, T):
+int kmcf_pcg_workspace(kmcf_matrix *m, bool precond, double tol, int max_it, int fixed_iters, kmcf_solve_stats_t *stats,
+                       const double *b_src = nullptr, double *x_user = nullptr);
+// relative rule as a loop of kernels, never the resident launch: for systems other than the one m's resident plan was
+// made for (heat solve).  The recurrence by KMCF_CG_VARIANT / the rank count.
+int kmcf_pcg_workspace_loop(kmcf_matrix *m, double tol, int max_it, kmcf_solve_stats_t *stats);
+// solve_sparse_CG_Jacobi (absolute rule) in its literal, scaled form and as Jacobi-PCG on the unscaled matrix
+int kmcf_scaled_cg_workspace(kmcf_matrix *m, double tol, int max_iterations, double *d_rhs_user, kmcf_solve_stats_t *stats);
+int kmcf_jacobi_cg_workspace_absolute(kmcf_matrix *m, double tol, int max_iterations, kmcf_solve_stats_t *stats);
 // comm.hip
 // First call of every compute entry point: selects the device and orders the library's compute stream after
 // the work the caller has queued so far (buffers filled by kernels or async copies still in flight on the
@@ -693,13 +714,14 @@ int kmcf_p2p_direct_ack(kmcf_matrix *m, unsigned long long seq, bool skip_if_don
 // cgr.hip: register-resident PCG (one launch per solve) for matrices whose tiles are all resident at once
 bool kmcf_cgr_usable(kmcf_matrix *m);
 int kmcf_cgr_agreed(const kmcf_matrix *m);        // KMCF_ERR_STATE if the resident plan found the ranks' group knobs differing
-int kmcf_cgr_solve(kmcf_matrix *m, bool precond, double tol, int max_it, int fixed_iters, bool classic);
-bool kmcf_pcg_resident_applies(kmcf_matrix *m);      // kmcf_cg.hip: the next kmcf_pcg_workspace call on m runs as a resident launch
+// (b_src / x_user: kmcf_cg_request's, or nullptr for the workspace's d_r / d_x)
+int kmcf_cgr_solve(kmcf_matrix *m, bool precond, double tol, int max_it, int fixed_iters, bool classic, const double *b_src, double *x_user);
+bool kmcf_pcg_resident_applies(kmcf_matrix *m);      // kmcf_cg.hip: the next kmcf_pcg_workspace call on m (with a limit) runs as a resident launch
 int kmcf_cgr_check(kmcf_matrix *m);           // after the synchronisation: KMCF_ERR_STATE if a bounded wait expired
 int kmcf_cgr_plan_info(kmcf_matrix *m, int *tpb, int *g1, int *nblocks);
 void kmcf_cgr_free(kmcf_matrix *m);
 // the reference's recurrence runs as a resident launch on one rank, wherever a resident launch fits (kmcf_cg.hip:
-// pcg_workspace_run; KMCF_CGR_CLASSIC_TILES lowers the limit)
+// kmcf_cg_solve; KMCF_CGR_CLASSIC_TILES lowers the limit)
 inline bool kmcf_cgr_classic_applies(const kmcf_matrix *m)
 {
     return m->comm->nranks == 1 && !m->comm->force_collectives && m->n_sell_tiles <= kmcf_opt_int(m->comm, KNOB_CGR_CLASSIC_TILES, 1024);

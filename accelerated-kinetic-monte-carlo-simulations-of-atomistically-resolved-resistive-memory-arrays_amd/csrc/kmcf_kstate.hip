@@ -16,8 +16,6 @@
 #include "kmcf_cells.hpp"
 #include "kmcf_internal.hpp"
 
-int kmcf_pcg_workspace(kmcf_matrix *m, bool precond, double tol, int max_it, int fixed_iters, kmcf_solve_stats_t *stats);
-
 namespace {
 
 constexpr int EL_OXYGEN_DEFECT = 1, EL_VACANCY = 2;  // src/utils.h:37-44
@@ -665,9 +663,6 @@ __global__ __launch_bounds__(KMCF_BLOCK) void cb_finish_kernel(double *__restric
     }
 }
 
-int kmcf_scaled_cg_workspace(kmcf_matrix *m, double tol, int max_iterations, double *d_rhs_user, kmcf_solve_stats_t *stats);
-int kmcf_jacobi_cg_workspace_absolute(kmcf_matrix *m, double tol, int max_iterations, kmcf_solve_stats_t *stats);
-
 // update_CB_edge_gpu_sparse (src/potential_solver_gpu.cu:673-772): Laplace solve for the conduction-band
 // edge on the K pattern (the reference rebuilds an identical single-GPU pattern, initialize_sparsity_CB),
 // "either site metal" conductances, contacts at +Vd/2 / -Vd/2, solve_sparse_CG_Jacobi (tol 1e-14),
@@ -789,14 +784,11 @@ static int k_potential_solve(kmcf_kstate *k, const int *d_site_element, const in
     // the start guess / solution in the caller's array: no copy, no permuting kernel around it
     // (asked on EVERY rank, also one without rows: a group agrees on the resident launch through a collective the first time)
     const bool direct = kmcf_pcg_resident_applies(m) && m->n_loc > 0;
-    if (direct) { m->solve_b_src = k->d_rhs; m->solve_x_user = v_soln; }
-    else {
+    if (!direct) {
         KMCF_HIP(hipMemcpyAsync(m->d_r, k->d_rhs, bytes, hipMemcpyDeviceToDevice, c->stream));   // internal order already
         KMCF_TRY(kmcf_vec_in(m, m->d_x, v_soln));
     }
-    const int rc_solve = kmcf_pcg_workspace(m, true, relative_tolerance, max_iterations, 0, stats);
-    m->solve_b_src = nullptr; m->solve_x_user = nullptr;
-    KMCF_TRY(rc_solve);
+    KMCF_TRY(kmcf_pcg_workspace(m, true, relative_tolerance, max_iterations, 0, stats, direct ? k->d_rhs : nullptr, direct ? v_soln : nullptr));
     if (!direct) KMCF_TRY(kmcf_vec_out(m, v_soln, m->d_x));
     KMCF_HIP(hipStreamSynchronize(c->stream));
     if (per_site) KMCF_TRY(k_contacts_verdict(k, who));          // (the word arrived with the statistics: no wait of its own)

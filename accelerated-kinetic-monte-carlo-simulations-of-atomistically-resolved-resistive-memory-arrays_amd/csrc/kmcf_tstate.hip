@@ -32,8 +32,6 @@
 static_assert(KMCF_SUB_MAX_PARTIALS == KMCF_MAX_PARTIALS && KMCF_SUB_BLOCK == KMCF_BLOCK, "kmcf_subplan.hpp restates the two constants");
 static_assert(sizeof(kmcf_strip) == sizeof(int4), "a strip is uploaded as is to kmcf_subop::d_strips");
 
-int kmcf_pcg_workspace(kmcf_matrix *m, bool precond, double tol, int max_it, int fixed_iters, kmcf_solve_stats_t *stats);
-
 // the read-backs of an assembly and of the power pass, in pinned memory
 struct t_pinned {
     int n_t, err;          // tunnel points of all ranks; the atom set differs from the one at init

@@ -232,20 +232,33 @@ def test_replan_walk_on_one_matrix(km, torch, monkeypatch, variant):
 GROUPS = {"loopback-2": (2, None, [2500, 3500]), "loopback-3": (3, None, [1500, 2600, 1900]), "p2p-2": (2, "p2p", [3300, 2700])}
 
 
-@pytest.mark.parametrize("variant", VARIANTS)
-@pytest.mark.parametrize("path", list(PATHS))
-@pytest.mark.parametrize("group", list(GROUPS))
-def test_rank_group(km, torch, monkeypatch, group, path, variant):
+# every path and recurrence on every group (the peer-to-peer group's cg1r iteration: fused, the all-reduce inside the
+# update kernel) -- and the other two transports of that iteration, each with a sequence rule of its own after the loop:
+# the all-reduce in a 1-block kernel in front of the fused update, and the staged halo with a separate peer-to-peer
+# reduction.  The chain of solves of _runs -- three ended by their limit, then one stopped -- is what those rules see.
+P2P_KNOBS = {"": {}, "-arsplit": dict(KMCF_P2P_AR="split"), "-staged": dict(KMCF_P2P_DIRECT="0")}
+RANK_CASES = [pytest.param(g, p, v, "", id="%s-%s-%s" % (g, p, v)) for g in GROUPS for p in PATHS for v in VARIANTS]
+RANK_CASES += [pytest.param("p2p-2", "sell", "cg1r", k, id="p2p-2-sell-cg1r" + k) for k in ("-arsplit", "-staged")]
+
+
+@pytest.mark.parametrize("group,path,variant,p2p_knobs", RANK_CASES)
+def test_rank_group(km, torch, monkeypatch, group, path, variant, p2p_knobs):
     """The same system over P ranks of an in-process group, uneven partition: the interior kernels' instances that skip
     boundary rows, the boundary pass (vec kernel; on the peer-to-peer transport the halo kernel) and the long row on
     rank 0 each add their partials.  (a) - (c) on the gathered vectors; every rank returns the same scalars.  The
-    peer-to-peer group takes the system without the long row: its direct halo protocol does not run with one."""
+    peer-to-peer group takes the system without the long row: its direct halo protocol does not run with one.
+    Its cg1r iteration runs once per transport: fused with the all-reduce inside the update kernel (the default),
+    fused with KMCF_P2P_AR=split, and with the staged halo (KMCF_P2P_DIRECT=0) and a separate peer-to-peer reduction."""
     S = km.solvers
     P, transport, counts = GROUPS[group]
     sysname = "ragged" if transport is None else "ragged_nolong"
     s = R.system(sysname, PATHS[path]["values"], True)
     _force(monkeypatch, PATHS[path]["env"], variant)
     monkeypatch.setenv("KMCF_LOOPBACK_TIMEOUT_S", "30")
+    for k in ("KMCF_P2P_AR", "KMCF_P2P_DIRECT"):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in P2P_KNOBS[p2p_knobs].items():
+        monkeypatch.setenv(k, v)
     if transport:
         monkeypatch.setenv("KMCF_TRANSPORT", transport)
         monkeypatch.setenv("KMCF_P2P_TIMEOUT_MS", "20000")     # ranks are Python threads: their host-side set-up can be seconds apart
@@ -267,6 +280,7 @@ def test_rank_group(km, torch, monkeypatch, group, path, variant):
             sub = M[r0:r0 + nr]
             mat = S.Distributed_matrix(comm, n, counts, displs, sub.indices, sub.indptr, sub.data)
             res = dict(transport=comm.transport(), info=mat.info(), plan=mat.sum_plan(with_csr=False))
+            res["knobs"] = {k: comm.get_option(k) for k in P2P_KNOBS[p2p_knobs]}
             res["runs"] = _runs(km, torch, mat, s, slice(r0, r0 + nr))
             mat.close()
             out[r] = res
@@ -283,10 +297,11 @@ def test_rank_group(km, torch, monkeypatch, group, path, variant):
     assert all(o is not None for o in out), "a rank did not finish (deadlock?)"
     for c in comms:
         c.close()
-    label = "%s/%s/%s" % (group, path, variant)
+    label = "%s/%s/%s%s" % (group, path, variant, p2p_knobs)
     bad = []
     for r, o in enumerate(out):
         assert o["transport"] == ("p2p (in-process group)" if transport else "loopback"), o["transport"]
+        assert o["knobs"] == {k: (v, 1) for k, v in P2P_KNOBS[p2p_knobs].items()}, o["knobs"]
         bad += _path_errors(path, variant, o["info"], o["plan"], sysname == "ragged" and r == 0, "%s rank %d" % (label, r))
         if not (o["info"]["boundary_rows"] > 0 and o["info"]["halo_cols"] > 0 and o["plan"]["boundary_grid"] > 0):
             bad.append("rank %d: boundary_rows %d halo_cols %d" % (r, o["info"]["boundary_rows"], o["info"]["halo_cols"]))
