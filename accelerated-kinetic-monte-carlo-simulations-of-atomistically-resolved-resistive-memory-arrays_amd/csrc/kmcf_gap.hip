@@ -23,6 +23,10 @@
 // in a run that is walked, so the A sites that attain the minimum hold their exact (d2, smallest b), and the others --
 // whose stored minimum may be too large or missing -- never enter step 7.  The result does not depend on what was read.
 //
+// Periodic index (kmcf_site_set_gap_pbc / kmcf_filament_gap_pbc on an index of kmcf_compute_cutoff_list_pbc with pbc = 1):
+// step 6 is gp_search_pbc_kernel -- the minimum image in y and z, the wrapped cells each once, the bound in y taken to
+// the face through which the neighbour cell is adjacent ("Periodic search"); every other step is shared.
+//
 // Determinism: counts are integer adds, the minimum d2 and the packed pair are integer minima: every output is
 // independent of the execution order.  No thread waits for another.
 #include <cmath>
@@ -280,6 +284,111 @@ __global__ __launch_bounds__(KMCF_BLOCK) void gp_search_kernel(kmcf_cell_grid g,
     }
 }
 
+// Lower bound of the minimum-image |v_b - v| over the sites b of a periodic index's cell next to the cell of v, through
+// the face at f (lower: the face below v): the distance to that face, shortened by the relative 1e-9 of gp_face_dist, the
+// period included in the scale -- the margin also covers the roundings of the cell rule and of fy * Ly in the distance.
+__device__ __forceinline__ double gp_face_dist_pbc(double v, double f, bool lower, double edge, double period)
+{
+    const double d = (lower ? v - f : f - v) - 1e-9 * (fabs(f) + fabs(v) + edge + period);
+    return d > 0.0 ? d : 0.0;
+}
+
+// 6 on a periodic index: the search under the minimum image in y and z (kmcf_min_image_dist's arithmetic, squared).
+// Cells as in pairwise_pbc_kernel, each once: in y the distinct cells of {cy-1, cy, cy+1} mod ncy, in z the runs of the
+// compacted order.  All loop bounds and the pruning threshold depend on the member alone, so the 16 lanes of a group
+// never part in front of the shuffles; only the walk over a run is per lane.
+// Bound in y of a neighbour cell: ncy >= 3 -- the cell below (cy-1 mod ncy) is adjacent through the lower face of cy, the
+// cell above through the upper face, and the way round the period is at least one cell edge longer than either; ncy == 2
+// -- the other cell is adjacent through both faces: the smaller of the two; own cell (all there is for ncy == 1): 0.
+__global__ __launch_bounds__(KMCF_BLOCK) void gp_search_pbc_kernel(kmcf_cell_grid_pbc g, double edge_x,
+                                                                   const int *__restrict__ cell_start,
+                                                                   const int *__restrict__ bpos, const int *__restrict__ n_a,
+                                                                   const int *__restrict__ alist, const int *__restrict__ acell,
+                                                                   const int *__restrict__ bsite, const int *__restrict__ bcell,
+                                                                   const double *__restrict__ bx, const double *__restrict__ by,
+                                                                   const double *__restrict__ bz, const double *__restrict__ x,
+                                                                   const double *__restrict__ y, const double *__restrict__ z,
+                                                                   double rmax2, u64 *best, u64 *__restrict__ ad2,
+                                                                   int *__restrict__ ab)
+{
+    const int nA = *n_a;
+    const int lane = threadIdx.x % GP_LPS;
+    const int rows = (nA + GP_SPB - 1) / GP_SPB * GP_SPB;
+    const double inf = __longlong_as_double((long long)GP_INF);
+    const int ny = min(g.ncy, 3);               // y cells a member visits
+    const double edge_y = g.ly / (double)g.ncy;
+    for (int k = blockIdx.x * GP_SPB + threadIdx.x / GP_LPS; k < rows; k += gridDim.x * GP_SPB) {
+        const bool valid = k < nA;
+        double bd = inf;                    // this lane's minimum (d2, b)
+        int bb = 0x7fffffff;
+        int ca = -1;
+        if (valid) {
+            const int a = alist[k];
+            ca = acell[k];
+            const double xa = x[a], ya = y[a], za = z[a];
+            const int cx = kmcf_cell_coord(xa, g.x0, g.inv_x, g.ncx), cy = kmcf_cell_coord(ya, g.y0, g.inv_y, g.ncy),
+                      cz = kmcf_cell_coord(za, g.z0, g.inv_z, g.ncz);
+            // z runs [lo0, hi0] and, if n_runs == 2, [lo1, hi1]
+            int n_runs = 1, lo0 = cz - 1, hi0 = cz + 1, lo1 = 0, hi1 = -1;
+            if (g.ncz <= 3) { lo0 = 0; hi0 = g.ncz - 1; }
+            else if (cz == 0) { lo0 = 0; hi0 = 1; lo1 = hi1 = g.ncz - 1; n_runs = 2; }
+            else if (cz == g.ncz - 1) { lo0 = 0; hi0 = 0; lo1 = g.ncz - 2; hi1 = g.ncz - 1; n_runs = 2; }
+            const int ay0 = g.ncy == 1 ? cy : cy - 1 + g.ncy;
+            // the faces of the member's cell in y
+            const double below = gp_face_dist_pbc(ya, g.y0 + (double)cy * edge_y, true, edge_y, g.ly);
+            const double above = gp_face_dist_pbc(ya, g.y0 + (double)(cy + 1) * edge_y, false, edge_y, g.ly);
+            double thr = rmax2;             // no pair with a larger d2 can be the result (uniform over the group)
+            // (the group's first lane's read for all of them: the loops below must not part the group's lanes)
+            const double seen = __shfl(__longlong_as_double((long long)gp_load(best + ca)), 0, GP_LPS);
+            if (seen < thr) thr = seen;
+            for (int ax = max(cx - 1, 0); ax <= min(cx + 1, g.ncx - 1); ++ax) {
+                const double lx = ax == cx ? 0.0 : gp_face_dist(xa, g.x0, edge_x, cx, ax);
+                for (int sy = 0; sy < ny; ++sy) {
+                    const int ay = (ay0 + sy) % g.ncy;
+                    const double ly = ay == cy ? 0.0 : (g.ncy == 2 ? fmin(below, above) : (sy == 0 ? below : above));
+                    if (lx * lx + ly * ly > thr) continue;
+                    const int col = (ax * g.ncy + ay) * g.ncz;
+                    for (int run = 0; run < n_runs; ++run) {
+                        const int b = bpos[cell_start[col + (run ? lo1 : lo0)]];
+                        const int e = bpos[cell_start[col + (run ? hi1 : hi0) + 1]];
+                        for (int t = b + lane; t < e; t += GP_LPS) {
+                            if (bcell[t] != ca) continue;
+                            const double dx = xa - bx[t];
+                            double fy = (ya - by[t]) / g.ly;
+                            fy -= round(fy);
+                            double fz = (za - bz[t]) / g.lz;
+                            fz -= round(fz);
+                            const double dy = fy * g.ly, dz = fz * g.lz;
+                            const double d2 = (dx * dx + dy * dy) + dz * dz;
+                            if (d2 <= rmax2) {
+                                const int j = bsite[t];                  // (j == a is a pair like any other)
+                                if (d2 < bd || (d2 == bd && j < bb)) { bd = d2; bb = j; }
+                            }
+                        }
+                    }
+                    double m = bd;
+#pragma unroll
+                    for (int off = GP_LPS / 2; off >= 1; off >>= 1) m = fmin(m, __shfl_xor(m, off, 64));
+                    if (m < thr) thr = m;
+                }
+            }
+        }
+#pragma unroll
+        for (int off = GP_LPS / 2; off >= 1; off >>= 1) {
+            const double od = __shfl_xor(bd, off, 64);
+            const int ob = __shfl_xor(bb, off, 64);
+            if (od < bd || (od == bd && ob < bb)) { bd = od; bb = ob; }
+        }
+        if (valid && lane == 0) {
+            const bool found = bb != 0x7fffffff;
+            const u64 bits = (u64)__double_as_longlong(bd);
+            ad2[k] = bits;
+            ab[k] = found ? bb : -1;
+            if (found) atomicMin(best + ca, bits);
+        }
+    }
+}
+
 // 7: best[] is final (earlier launch); few A members attain it
 __global__ __launch_bounds__(KMCF_BLOCK) void gp_pair_kernel(const int *__restrict__ n_a, const int *__restrict__ alist,
                                                              const int *__restrict__ acell, const u64 *__restrict__ ad2,
@@ -382,7 +491,7 @@ int gp_workspace(kmcf_pairwise *p, size_t n_cells, size_t prof_words)
 
 // the argument checks both entry points share; p comes last: everything before it is checked without an index
 int gp_check_common(const char *what, const kmcf_pairwise *p, const double *d_x, const double *d_y, const double *d_z,
-                    double r_max, const int *d_site_cell, int n_cells, const kmcf_gap_t *h_gaps)
+                    double r_max, const int *d_site_cell, int n_cells, const kmcf_gap_t *h_gaps, bool periodic_ok)
 {
     KMCF_CHECK(d_x, KMCF_ERR_ARG, "%s: d_x is NULL", what);
     KMCF_CHECK(d_y, KMCF_ERR_ARG, "%s: d_y is NULL", what);
@@ -393,8 +502,8 @@ int gp_check_common(const char *what, const kmcf_pairwise *p, const double *d_x,
     KMCF_CHECK(n_cells >= 1, KMCF_ERR_ARG, "%s: n_cells = %d is not >= 1", what, n_cells);
     KMCF_CHECK(d_site_cell || n_cells == 1, KMCF_ERR_ARG, "%s: d_site_cell is NULL with n_cells = %d", what, n_cells);
     KMCF_CHECK(p, KMCF_ERR_ARG, "%s: p is NULL", what);
-    KMCF_CHECK(!p->pbc, KMCF_ERR_ARG, "%s: the index is periodic (kmcf_compute_cutoff_list_pbc with pbc = 1) and the gap search is "
-               "non-periodic: build a non-periodic index for it", what);
+    KMCF_CHECK(periodic_ok || !p->pbc, KMCF_ERR_ARG, "%s: the index is periodic (kmcf_compute_cutoff_list_pbc with pbc = 1) and "
+               "this gap search is non-periodic: call %s_pbc for the minimum image, or build a non-periodic index", what, what);
     KMCF_CHECK(r_max <= p->cutoff, KMCF_ERR_ARG, "%s: r_max = %g exceeds the index's cutoff radius %g", what, r_max, p->cutoff);
     return KMCF_OK;
 }
@@ -424,9 +533,15 @@ int gp_enqueue(kmcf_pairwise *p, const double *d_x, const double *d_y, const dou
     gp_scatter_kernel<<<nb, KMCF_BLOCK, 0, st>>>(N, nb, p->d_cell_order, d_side, d_site_cell, n_cells, d_x, d_y, d_z, w->d_sum,
                                                 w->d_bpos, w->d_alist, w->d_acell, w->d_bsite, w->d_bcell, w->d_bx, w->d_by,
                                                 w->d_bz);
-    gp_search_kernel<<<(int)search_grid, KMCF_BLOCK, 0, st>>>(p->grid(), p->d_cell_start, w->d_bpos, n_a, w->d_alist, w->d_acell,
-                                                             w->d_bsite, w->d_bcell, w->d_bx, w->d_by, w->d_bz, d_x, d_y, d_z,
-                                                             r_max * r_max, w->d_best, w->d_ad2, w->d_ab);
+    if (p->pbc)
+        gp_search_pbc_kernel<<<(int)search_grid, KMCF_BLOCK, 0, st>>>(p->grid_pbc(), p->cutoff, p->d_cell_start, w->d_bpos, n_a,
+                                                                     w->d_alist, w->d_acell, w->d_bsite, w->d_bcell, w->d_bx,
+                                                                     w->d_by, w->d_bz, d_x, d_y, d_z, r_max * r_max, w->d_best,
+                                                                     w->d_ad2, w->d_ab);
+    else
+        gp_search_kernel<<<(int)search_grid, KMCF_BLOCK, 0, st>>>(p->grid(), p->d_cell_start, w->d_bpos, n_a, w->d_alist,
+                                                                 w->d_acell, w->d_bsite, w->d_bcell, w->d_bx, w->d_by, w->d_bz,
+                                                                 d_x, d_y, d_z, r_max * r_max, w->d_best, w->d_ad2, w->d_ab);
     gp_pair_kernel<<<(int)pair_grid, KMCF_BLOCK, 0, st>>>(n_a, w->d_alist, w->d_acell, w->d_ad2, w->d_ab, w->d_best, w->d_pair);
     gp_record_kernel<<<cell_grid, KMCF_BLOCK, 0, st>>>(nc, w->d_best, w->d_pair, w->d_cnt, d_x, w->d_gaps, w->d_stats);
     if (profile) {
@@ -467,15 +582,13 @@ int gp_finish(kmcf_pairwise *p, int n_cells, kmcf_gap_t *h_gaps, size_t prof_wor
     return KMCF_OK;
 }
 
-}  // namespace
-
-extern "C" int kmcf_site_set_gap(kmcf_pairwise *p, const double *d_x, const double *d_y, const double *d_z,
-                                 const int *d_site_side, double r_max, const int *d_site_cell, int n_cells,
-                                 kmcf_gap_t *h_gaps, kmcf_gap_stats_t *stats)
+// the body of kmcf_site_set_gap and kmcf_site_set_gap_pbc: they differ in the name and in whether a periodic index passes
+int gp_site_set_gap(const char *what, bool periodic_ok, kmcf_pairwise *p, const double *d_x, const double *d_y, const double *d_z,
+                    const int *d_site_side, double r_max, const int *d_site_cell, int n_cells, kmcf_gap_t *h_gaps,
+                    kmcf_gap_stats_t *stats)
 {
-    const char *what = "kmcf_site_set_gap";
     KMCF_CHECK(d_site_side, KMCF_ERR_ARG, "%s: d_site_side is NULL", what);
-    KMCF_TRY(gp_check_common(what, p, d_x, d_y, d_z, r_max, d_site_cell, n_cells, h_gaps));
+    KMCF_TRY(gp_check_common(what, p, d_x, d_y, d_z, r_max, d_site_cell, n_cells, h_gaps, periodic_ok));
     kmcf_comm *c = p->comm;
     KMCF_TRY(kmcf_enter(c));
     KMCF_TRY(gp_workspace(p, (size_t)n_cells, 0));
@@ -484,13 +597,13 @@ extern "C" int kmcf_site_set_gap(kmcf_pairwise *p, const double *d_x, const doub
     return gp_finish(p, n_cells, h_gaps, 0, nullptr, nullptr, stats);
 }
 
-extern "C" int kmcf_filament_gap(kmcf_pairwise *p, int nn, const int *d_neigh_idx, const int *d_site_element,
-                                 const int *d_site_charge, const int *d_metals, int num_metals, const double *d_x,
-                                 const double *d_y, const double *d_z, int N_left_tot, int N_right_tot, double r_max,
-                                 const int *d_site_cell, int n_cells, kmcf_gap_t *h_gaps, int n_bins, double x_lo, double x_hi,
-                                 int *h_profile, int *d_site_side, kmcf_gap_stats_t *stats)
+// the body of kmcf_filament_gap and kmcf_filament_gap_pbc
+int gp_filament_gap(const char *what, bool periodic_ok, kmcf_pairwise *p, int nn, const int *d_neigh_idx, const int *d_site_element,
+                    const int *d_site_charge, const int *d_metals, int num_metals, const double *d_x, const double *d_y,
+                    const double *d_z, int N_left_tot, int N_right_tot, double r_max, const int *d_site_cell, int n_cells,
+                    kmcf_gap_t *h_gaps, int n_bins, double x_lo, double x_hi, int *h_profile, int *d_site_side,
+                    kmcf_gap_stats_t *stats)
 {
-    const char *what = "kmcf_filament_gap";
     KMCF_CHECK(d_neigh_idx, KMCF_ERR_ARG, "%s: d_neigh_idx is NULL", what);
     KMCF_CHECK(d_site_element, KMCF_ERR_ARG, "%s: d_site_element is NULL", what);
     KMCF_CHECK(d_site_charge, KMCF_ERR_ARG, "%s: d_site_charge is NULL", what);
@@ -502,7 +615,7 @@ extern "C" int kmcf_filament_gap(kmcf_pairwise *p, int nn, const int *d_neigh_id
     KMCF_CHECK(n_bins >= 0, KMCF_ERR_ARG, "%s: n_bins = %d is negative", what, n_bins);
     KMCF_CHECK(!h_profile || n_bins > 0, KMCF_ERR_ARG, "%s: h_profile is set with n_bins = 0", what);
     KMCF_CHECK(!h_profile || x_hi > x_lo, KMCF_ERR_ARG, "%s: h_profile is set with x_hi = %g not above x_lo = %g", what, x_hi, x_lo);
-    KMCF_TRY(gp_check_common(what, p, d_x, d_y, d_z, r_max, d_site_cell, n_cells, h_gaps));
+    KMCF_TRY(gp_check_common(what, p, d_x, d_y, d_z, r_max, d_site_cell, n_cells, h_gaps, periodic_ok));
     const int N = p->N;
     KMCF_CHECK((int64_t)N_left_tot + N_right_tot <= N, KMCF_ERR_ARG, "%s: N_left_tot + N_right_tot = %lld exceeds N = %d", what,
                (long long)N_left_tot + N_right_tot, N);
@@ -521,4 +634,42 @@ extern "C" int kmcf_filament_gap(kmcf_pairwise *p, int nn, const int *d_neigh_id
     KMCF_HIP(hipEventRecord(c->ev_t1, st));
     KMCF_TRY(gp_enqueue(p, d_x, d_y, d_z, side, r_max, d_site_cell, n_cells, cl.cls, n_bins, x_lo, x_hi, h_profile != nullptr));
     return gp_finish(p, n_cells, h_gaps, prof_words, h_profile, c->ev_t1, stats);
+}
+
+}  // namespace
+
+extern "C" int kmcf_site_set_gap(kmcf_pairwise *p, const double *d_x, const double *d_y, const double *d_z,
+                                 const int *d_site_side, double r_max, const int *d_site_cell, int n_cells,
+                                 kmcf_gap_t *h_gaps, kmcf_gap_stats_t *stats)
+{
+    return gp_site_set_gap("kmcf_site_set_gap", false, p, d_x, d_y, d_z, d_site_side, r_max, d_site_cell, n_cells, h_gaps, stats);
+}
+
+extern "C" int kmcf_site_set_gap_pbc(kmcf_pairwise *p, const double *d_x, const double *d_y, const double *d_z,
+                                     const int *d_site_side, double r_max, const int *d_site_cell, int n_cells,
+                                     kmcf_gap_t *h_gaps, kmcf_gap_stats_t *stats)
+{
+    return gp_site_set_gap("kmcf_site_set_gap_pbc", true, p, d_x, d_y, d_z, d_site_side, r_max, d_site_cell, n_cells, h_gaps, stats);
+}
+
+extern "C" int kmcf_filament_gap(kmcf_pairwise *p, int nn, const int *d_neigh_idx, const int *d_site_element,
+                                 const int *d_site_charge, const int *d_metals, int num_metals, const double *d_x,
+                                 const double *d_y, const double *d_z, int N_left_tot, int N_right_tot, double r_max,
+                                 const int *d_site_cell, int n_cells, kmcf_gap_t *h_gaps, int n_bins, double x_lo, double x_hi,
+                                 int *h_profile, int *d_site_side, kmcf_gap_stats_t *stats)
+{
+    return gp_filament_gap("kmcf_filament_gap", false, p, nn, d_neigh_idx, d_site_element, d_site_charge, d_metals, num_metals, d_x,
+                           d_y, d_z, N_left_tot, N_right_tot, r_max, d_site_cell, n_cells, h_gaps, n_bins, x_lo, x_hi, h_profile,
+                           d_site_side, stats);
+}
+
+extern "C" int kmcf_filament_gap_pbc(kmcf_pairwise *p, int nn, const int *d_neigh_idx, const int *d_site_element,
+                                     const int *d_site_charge, const int *d_metals, int num_metals, const double *d_x,
+                                     const double *d_y, const double *d_z, int N_left_tot, int N_right_tot, double r_max,
+                                     const int *d_site_cell, int n_cells, kmcf_gap_t *h_gaps, int n_bins, double x_lo,
+                                     double x_hi, int *h_profile, int *d_site_side, kmcf_gap_stats_t *stats)
+{
+    return gp_filament_gap("kmcf_filament_gap_pbc", true, p, nn, d_neigh_idx, d_site_element, d_site_charge, d_metals, num_metals,
+                           d_x, d_y, d_z, N_left_tot, N_right_tot, r_max, d_site_cell, n_cells, h_gaps, n_bins, x_lo, x_hi,
+                           h_profile, d_site_side, stats);
 }

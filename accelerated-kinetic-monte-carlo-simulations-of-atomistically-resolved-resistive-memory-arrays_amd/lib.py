@@ -209,6 +209,9 @@ SIGNATURES = {
     "kmcf_site_set_gap": (C.c_int, [_P, _P, _P, _P, _P, C.c_double, _P, C.c_int, C.POINTER(Gap), C.POINTER(GapStats)]),
     "kmcf_filament_gap": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P,
                                     C.c_int, C.POINTER(Gap), C.c_int, C.c_double, C.c_double, _IP, _P, C.POINTER(GapStats)]),
+    "kmcf_site_set_gap_pbc": (C.c_int, [_P, _P, _P, _P, _P, C.c_double, _P, C.c_int, C.POINTER(Gap), C.POINTER(GapStats)]),
+    "kmcf_filament_gap_pbc": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P,
+                                        C.c_int, C.POINTER(Gap), C.c_int, C.c_double, C.c_double, _IP, _P, C.POINTER(GapStats)]),
     "kmcf_neighbor_list":(C.c_int, [_P, _P, _P, _P, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _P]),
     "kmcf_neighbor_list_pbc": (C.c_int, [_P, _P, _P, _P, C.c_int, _DP, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _P]),
 }

@@ -683,29 +683,35 @@ def _gap_cells(gpubuf, site_cell, n_cells):
     return site_cell
 
 
-def site_set_gap(gpubuf, site_side, r_max, site_cell=None, n_cells=1):
+def site_set_gap(gpubuf, site_side, r_max, site_cell=None, n_cells=1, periodic=False):
     """kmcf_site_set_gap on the buffers' spatial index (gpubuf.cutoff_idx, compute_cutoff_list): per gap cell the nearest
     pair (a, b) of the sites with side bit 0 and the sites with side bit 1 within r_max (definitions:
     include/kmcfield.h).  site_side: int32 device tensor of N entries; site_cell: int32 tensor or array of N entries
-    (values outside [0, n_cells): no cell), or None with n_cells == 1.  Returns dict(gaps: numpy structured array
-    GAP_DTYPE of n_cells records, stats: dict)."""
+    (values outside [0, n_cells): no cell), or None with n_cells == 1.  periodic=True: kmcf_site_set_gap_pbc, which takes
+    the minimum image in y and z on a periodic index (compute_cutoff_list with pbc = 1) and is the plain call on any
+    other; the default refuses a periodic index.  Returns dict(gaps: numpy structured array GAP_DTYPE of n_cells
+    records, stats: dict)."""
     assert gpubuf.cutoff_idx is not None, "site_set_gap needs the spatial index: compute_cutoff_list first"
     assert site_side.dtype == torch.int32 and site_side.numel() == gpubuf.N_, "site_side: N int32 entries"
     cell = _gap_cells(gpubuf, site_cell, n_cells)
     gaps = np.zeros(int(n_cells), GAP_DTYPE)
     st = _L.GapStats()
-    _L.check(_L.load().kmcf_site_set_gap(gpubuf.cutoff_idx, _ptr(gpubuf.site_x), _ptr(gpubuf.site_y), _ptr(gpubuf.site_z),
-                                         _ptr(site_side), float(r_max), _ptr(cell), int(n_cells),
-                                         gaps.ctypes.data_as(C.POINTER(_L.Gap)), C.byref(st)), "kmcf_site_set_gap")
+    name = "kmcf_site_set_gap_pbc" if periodic else "kmcf_site_set_gap"
+    _L.check(getattr(_L.load(), name)(gpubuf.cutoff_idx, _ptr(gpubuf.site_x), _ptr(gpubuf.site_y), _ptr(gpubuf.site_z),
+                                      _ptr(site_side), float(r_max), _ptr(cell), int(n_cells),
+                                      gaps.ctypes.data_as(C.POINTER(_L.Gap)), C.byref(st)), name)
     return dict(gaps=gaps, stats=st.as_dict())
 
 
-def filament_gap(kmc_comm, gpubuf, N_left_tot, N_right_tot, r_max, site_cell=None, n_cells=1, bins=None, sides=True):
+def filament_gap(kmc_comm, gpubuf, N_left_tot, N_right_tot, r_max, site_cell=None, n_cells=1, bins=None, sides=True,
+                 periodic=False):
     """kmcf_filament_gap: how close the conductive matter attached to the left electrode comes to the matter attached to
     the right one, per gap cell (definitions: include/kmcfield.h).  Call it after update_charge_gpu and
     compute_cutoff_list, on the communicator the index was built with.  bins: None or (n_bins, x_lo, x_hi) for the
-    profile of the conductive vacancies along x.  Returns dict(gaps: numpy structured array GAP_DTYPE of n_cells records,
-    profile: int32 array (n_cells, n_bins, 3) -- last axis: side 1, 2, 3 -- or None, side: int32 device tensor of N
+    profile of the conductive vacancies along x.  periodic=True: kmcf_filament_gap_pbc -- the minimum image in y and z on
+    a periodic index (compute_cutoff_list with pbc = 1; build the list with compute_neighbor_list(pbc=1) as well, so that
+    the clusters wrap too), the plain call on any other; the default refuses a periodic index.  Returns dict(gaps: numpy
+    structured array GAP_DTYPE of n_cells records, profile: int32 array (n_cells, n_bins, 3) -- last axis: side 1, 2, 3 -- or None, side: int32 device tensor of N
     entries or None, stats: dict)."""
     N = gpubuf.N_
     assert gpubuf.cutoff_idx is not None, "filament_gap needs the spatial index: compute_cutoff_list first"
@@ -717,13 +723,14 @@ def filament_gap(kmc_comm, gpubuf, N_left_tot, N_right_tot, r_max, site_cell=Non
     profile = np.zeros((int(n_cells), n_bins, 3), np.int32) if bins is not None else None
     side = torch.empty(N, dtype=torch.int32, device=gpubuf.device) if sides else None
     st = _L.GapStats()
-    _L.check(_L.load().kmcf_filament_gap(gpubuf.cutoff_idx, gpubuf.nn_, _ptr(gpubuf.neigh_idx), _ptr(gpubuf.site_element),
-                                         _ptr(gpubuf.site_charge), _ptr(gpubuf.metal_types), gpubuf.num_metal_types_,
-                                         _ptr(gpubuf.site_x), _ptr(gpubuf.site_y), _ptr(gpubuf.site_z), int(N_left_tot),
-                                         int(N_right_tot), float(r_max), _ptr(cell), int(n_cells),
-                                         gaps.ctypes.data_as(C.POINTER(_L.Gap)), n_bins, x_lo, x_hi,
-                                         profile.ctypes.data_as(C.POINTER(C.c_int)) if profile is not None else None,
-                                         _ptr(side), C.byref(st)), "kmcf_filament_gap")
+    name = "kmcf_filament_gap_pbc" if periodic else "kmcf_filament_gap"
+    _L.check(getattr(_L.load(), name)(gpubuf.cutoff_idx, gpubuf.nn_, _ptr(gpubuf.neigh_idx), _ptr(gpubuf.site_element),
+                                      _ptr(gpubuf.site_charge), _ptr(gpubuf.metal_types), gpubuf.num_metal_types_,
+                                      _ptr(gpubuf.site_x), _ptr(gpubuf.site_y), _ptr(gpubuf.site_z), int(N_left_tot),
+                                      int(N_right_tot), float(r_max), _ptr(cell), int(n_cells),
+                                      gaps.ctypes.data_as(C.POINTER(_L.Gap)), n_bins, x_lo, x_hi,
+                                      profile.ctypes.data_as(C.POINTER(C.c_int)) if profile is not None else None,
+                                      _ptr(side), C.byref(st)), name)
     return dict(gaps=gaps, profile=profile, side=side, stats=st.as_dict())
 
 

@@ -585,9 +585,10 @@ int kmcf_conductive_clusters(kmcf_comm *c, int N, int nn, const int *d_neigh_idx
  * cell_of_site); any other value: the site belongs to no cell and enters no pair.  d_site_cell NULL requires
  * n_cells == 1 and puts every site in cell 0.
  * Pair of cell c: (a, b) with a in A, b in B, both in cell c; a == b is allowed.  dx = x[a] - x[b], likewise dy, dz;
- * d2 = (dx*dx + dy*dy) + dz*dz, every operation rounded to double (no fused multiply-add); the distance is non-periodic, and the
- * search refuses a periodic index (kmcf_compute_cutoff_list_pbc with pbc == 1) with KMCF_ERR_ARG: its pruning by the
- * distances to the cell faces does not carry over to wrapped cells.  Build a non-periodic index for the gap.
+ * d2 = (dx*dx + dy*dy) + dz*dz, every operation rounded to double (no fused multiply-add); the distance is non-periodic, and
+ * these two calls refuse a periodic index (kmcf_compute_cutoff_list_pbc with pbc == 1) with KMCF_ERR_ARG: their pruning by
+ * the distances to the cell faces does not carry over to wrapped cells.  kmcf_site_set_gap_pbc / kmcf_filament_gap_pbc
+ * (below) take the minimum image on such an index.
  * A pair counts iff d2 <= r_max*r_max, that product formed in double.
  * Result per cell: the pair with the smallest d2; among equal d2 the smallest a, then the smallest b.  A site in both sets
  * gives gap2 = 0 through the pair (a, a).  gap2, the two sites, x_left / x_right and the counts are exact; gap =
@@ -633,6 +634,39 @@ int kmcf_filament_gap(kmcf_pairwise *p, int nn, const int *d_neigh_idx, const in
                       const int *d_site_cell, int n_cells, kmcf_gap_t *h_gaps,
                       int n_bins, double x_lo, double x_hi, int *h_profile /* n_cells*n_bins*3, or NULL */,
                       int *d_site_side /* N out, or NULL */, kmcf_gap_stats_t *stats);
+
+/* The same two analyses under periodic y-z boundaries.  Parameter lists, outputs, argument checks and their order are
+ * those of kmcf_site_set_gap / kmcf_filament_gap (kmcf_last_error names the _pbc call); the one difference: a periodic
+ * index is accepted.
+ * On a non-periodic index (kmcf_compute_cutoff_list, or kmcf_compute_cutoff_list_pbc with pbc == 0) they launch the
+ * kernels of the plain calls and return their bytes.
+ * On a periodic index (kmcf_compute_cutoff_list_pbc with pbc == 1) the pair distance is the library's one minimum image,
+ * Ly and Lz being the periods the index was built with:
+ *     dx = x[a] - x[b]
+ *     fy = (y[a] - y[b]) / Ly;  fy -= round(fy);  dy = fy * Ly        (z likewise; round = C round, half away from zero)
+ *     d2 = (dx*dx + dy*dy) + dz*dz
+ * every operation rounded to double: no fused multiply-add, the division an IEEE division (no reciprocal multiply).  x is
+ * never periodic.  A pair has ONE distance, the minimum image: where a period is shorter than 2 r_max, a second image
+ * within r_max adds no pair.
+ * Everything else is the contract above: A and B from the side bits, a == b allowed (gap2 = 0); gap cells from
+ * d_site_cell; a pair counts iff d2 <= r_max*r_max; the winner has the smallest d2, then the smallest a, then the
+ * smallest b; r_max is at most the index's cutoff radius; the profile along x, the counts and the stats are unchanged
+ * (x is not periodic); gap = sqrt(gap2) is formed on the host; one synchronisation per call; two calls on the same input
+ * return the same bytes.
+ * kmcf_filament_gap_pbc derives the sides from the list it is given: pass the list of kmcf_neighbor_list_pbc (pbc == 1,
+ * the same periods) so that the clusters are periodic as well.  This is not checked (as with kmcf_events_set_lattice):
+ * an open list under a periodic distance gives open clusters measured across the wrap. */
+int kmcf_site_set_gap_pbc(kmcf_pairwise *p, const double *d_x, const double *d_y, const double *d_z,
+                          const int *d_site_side /* N: bit 0 left set, bit 1 right set */, double r_max,
+                          const int *d_site_cell /* N, or NULL */, int n_cells,
+                          kmcf_gap_t *h_gaps /* n_cells */, kmcf_gap_stats_t *stats /* or NULL */);
+int kmcf_filament_gap_pbc(kmcf_pairwise *p, int nn, const int *d_neigh_idx, const int *d_site_element,
+                          const int *d_site_charge, const int *d_metals, int num_metals,
+                          const double *d_x, const double *d_y, const double *d_z,
+                          int N_left_tot, int N_right_tot, double r_max,
+                          const int *d_site_cell, int n_cells, kmcf_gap_t *h_gaps,
+                          int n_bins, double x_lo, double x_hi, int *h_profile /* n_cells*n_bins*3, or NULL */,
+                          int *d_site_side /* N out, or NULL */, kmcf_gap_stats_t *stats);
 
 /* ---------------------------------------------------------------------- */
 /* T path: current solve (Kirchhoff matrix with two virtual nodes + WKB       */

@@ -21,7 +21,8 @@ after the power update of every step: the step line gains `current map <ms> (tun
 array are filled once by structure.bias_scheme (selected word line -Vd/2, selected bit line +Vd/2, the others by the scheme),
 the boundary solve is kmcf_background_potential_sparse_contacts, and the step line gains `events per cell [c0 c1 ...]`: the
 events of the step whose first site lies under crossing word * n_lines + bit.  The band-edge and current stages of --current
-still see the scalar Vd.  --gap R runs the filament gap analysis (kmcf_filament_gap) after the charge update of every step:
+still see the scalar Vd.  --gap R runs the filament gap analysis (kmcf_filament_gap; on `5nm-periodic`
+kmcf_filament_gap_pbc: periodic clusters, minimum-image distance) after the charge update of every step:
 how close the conductive matter attached to the left electrode comes to the matter attached to the right one, searched up
 to R angstrom (at most 20, the cell edge of the spatial index), per cell of structure.crossbar_lines on the crossbar
 workloads.  The step line gains `gap <ms clusters>+<ms search> [<cell>: <gap> A (<site_left>-<site_right>) L <n_left> R
@@ -63,8 +64,6 @@ def main():
                          "counts per crossbar cell; with --clusters also the constriction of a bridging filament")
     a = ap.parse_args()
     periodic = a.workload == "5nm-periodic"
-    if periodic and a.gap is not None:
-        ap.error("--gap: the gap search is non-periodic and refuses the periodic index of --workload 5nm-periodic")
     if a.scheme and a.workload in ("5nm", "5nm-periodic"):
         ap.error("--scheme needs a crossbar with lines: --workload 40nm or conducting")
     if a.current_map and not a.current:
@@ -147,7 +146,8 @@ def main():
             clusters = " | clusters %.3f (%d vac, largest %d, bridging %d)" % (cs["ms"], cs["n_vacancy_clusters"],
                                                                                   cs["largest_vacancy"], cs["n_bridging"])
         if a.gap is not None:
-            gp = S.filament_gap(comm, buf, NL, NL, a.gap, site_cell=gap_cells, n_cells=n_gap_cells, bins=gap_bins, sides=False)
+            gp = S.filament_gap(comm, buf, NL, NL, a.gap, site_cell=gap_cells, n_cells=n_gap_cells, bins=gap_bins, sides=False,
+                                periodic=periodic)
             cells = []
             for c, g in enumerate(gp["gaps"]):
                 if g["bridged"]:
