@@ -1,0 +1,760 @@
+// Tunnelling-chain analysis: per gap cell the bottleneck-optimal chain of hops from the left side to the right side
+// through floating bodies (kmcf_site_set_chain), and the same with sides and bodies derived from the device state
+// (kmcf_filament_chain).
+//
+// The reference has no counterpart.  Definitions (terminals, stones, homes, links, keys, chain): include/kmcfield.h and
+// DESIGN.md 3.12.  A VERTEX is named by one of its sites: a stone by its home, L_c / R_c by their smallest site id; the
+// per-vertex arrays below are indexed by that site.
+//
+// Launches, all on the compute stream (kmcf_filament_chain: behind the cluster pass and one kernel for sides and nodes):
+//   1    clear: per-cell words, homes, per-vertex words
+//   2    counts of the sides per gap cell, smallest L / R site per cell, home per node        [integer atomicAdd / atomicMin]
+//   3    vertex and vertex cell per site; stones and stone sites per cell; members = sites of the vertices of cells with
+//        both terminals and no site on both sides (NONE and BRIDGED cells drop out)
+//   4-6  compact the members per INDEX cell with coordinates, vertex cell, vertex and component (kmcf_block.hpp)
+//   round r = 1, 2, ... (Boruvka):
+//     a  search: 16 lanes per member walk the runs of the 27 surrounding index cells over the candidates of the same vertex
+//        cell and another component; the group's minimum (d2, smallest partner) is stored per member and lowers the
+//        component's best d2 (64-bit integer atomicMin on the bits: non-negative doubles order as integers)
+//     b  among the members that attain their component's d2, the smallest packed (min << 32 | max) wins (atomicMin)
+//     c  hook: every component root with a link appends it to the edge list and points at the other component's root; of
+//        a mutual choice (the only cycles: keys are unique) the smaller root stays and appends, the larger only hooks
+//     d  jump: every vertex follows the hooks to its new root; the per-component words are reset
+//     e  cells whose L and R are still in different components are counted into the round's flag word
+//     the host reads the flag words (one synchronisation) and stops when the round chose no link or no such cell is left:
+//     Boruvka's edges are edges of the minimum spanning forest, so the forest path between L and R is then final.
+//     f  before round 2: the members that found a partner in round 1 (the SURFACE members) are compacted over the member
+//        list (4-6 again); the others -- electrode and filament bulk -- have no site of another vertex within r_max and
+//        never gain one, as components only merge.  Before round 3 on: the components of the list are refreshed.
+//   the records and hop lists are put together on the host from the edge list (at most vertices - 1 edges).
+//
+// Round 1 also takes, per L member, the smallest d2 to an R member of its cell (direct2).  Pruning (as in kmcf_gap.hip: a
+// run of index cells is skipped only if its face-distance bound is GREATER than every threshold that still matters):
+// round 1 -- r_max^2, what the member itself has found (anything more would hide a member's partner and with it the
+// surface mark), and for L members the cell's direct2 so far; later rounds -- r_max^2, the component's best so far
+// (whatever value is read is >= the final one) and what the member has found.  Members that attain the final minimum hold
+// their exact (d2, smallest partner); the others never enter b.
+//
+// Determinism: every device result is an integer sum or minimum; the order of the edge list is not, and the host sorts it
+// by key before use.  No thread waits for another; the search stops after CH_MAX_ROUNDS rounds (KMCF_ERR_STATE).
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <limits>
+#include <unordered_map>
+#include <vector>
+
+#include "kmcf_internal.hpp"
+
+static_assert(sizeof(kmcf_chain_t) == 64, "kmcf_chain_t is 64 bytes");
+static_assert(sizeof(kmcf_hop_t) == 16, "kmcf_hop_t is 16 bytes");
+
+namespace {
+typedef unsigned long long u64;
+struct ch_edge {            // a chosen link: the pair (a < b), their vertices
+    u64 d2;
+    int a, b, va, vb;
+};
+static_assert(sizeof(ch_edge) == 24, "ch_edge is 24 bytes");
+}  // namespace
+
+struct kmcf_chain_ws {
+    int N = 0;
+    int *d_side = nullptr, *d_node = nullptr;    // kmcf_filament_chain without the caller's arrays
+    int *d_home = nullptr;                       // per node: smallest stone site
+    int *d_svert = nullptr, *d_svcell = nullptr; // per site: vertex (-1: no member) and vertex cell
+    int *d_surf = nullptr;                       // per site: found a partner in round 1
+    int *d_root = nullptr, *d_next = nullptr;    // per vertex: component root; the hook of this round
+    u64 *d_cbest = nullptr, *d_cpair = nullptr;  // per component root: bits of the smallest d2, packed pair
+    int *d_sum = nullptr;                        // tiles + 1: tile counts / offsets; the list's length in d_sum[tiles]
+    int *d_lpos = nullptr;                       // N + 1: exclusive scan of the list flags in index-cell order
+    int *d_lsite = nullptr, *d_lvcell = nullptr, *d_lvert = nullptr, *d_lcomp = nullptr;   // the list (index-cell order)
+    double *d_lx = nullptr, *d_ly = nullptr, *d_lz = nullptr;
+    u64 *d_ld2 = nullptr;                        // per list member: bits of its smallest d2
+    int *d_lj = nullptr;                         // ... and the partner (-1: none)
+    ch_edge *d_edges = nullptr;                  // N
+    int *d_flags = nullptr;                      // CH_F_*
+    size_t cap_cells = 0;
+    int *d_words = nullptr;                      // per gap cell: CH_W_*
+    u64 *d_direct = nullptr;                     // per gap cell: bits of direct2
+};
+
+void kmcf_chain_ws_free(kmcf_pairwise *p)
+{
+    if (!p || !p->chain_ws) return;
+    kmcf_chain_ws *w = p->chain_ws;
+    kmcf_dev_free_all({w->d_side, w->d_node, w->d_home, w->d_svert, w->d_svcell, w->d_surf, w->d_root, w->d_next, w->d_cbest,
+                       w->d_cpair, w->d_sum, w->d_lpos, w->d_lsite, w->d_lvcell, w->d_lvert, w->d_lcomp, w->d_lx, w->d_ly, w->d_lz,
+                       w->d_ld2, w->d_lj, w->d_edges, w->d_flags, w->d_words, w->d_direct});
+    delete w;
+    p->chain_ws = nullptr;
+}
+
+namespace {
+
+constexpr int CH_LPS = 16, CH_SPB = KMCF_BLOCK / CH_LPS;          // lanes per member, members per block
+constexpr u64 CH_INF = 0x7ff0000000000000ull;                    // bits of +infinity
+constexpr u64 CH_NO_PAIR = ~0ull;
+constexpr int CH_NO_SITE = 0x7fffffff;
+constexpr int CH_MAX_ROUNDS = 40;
+enum { CH_W_LEFT, CH_W_RIGHT, CH_W_BOTH, CH_W_STONES, CH_W_STONE_SITES, CH_W_LREP, CH_W_RREP, CH_W_WORDS = 8 };
+enum { CH_F_EDGES, CH_F_ERROR, CH_F_SURFACE, CH_F_OPEN0, CH_F_WORDS = CH_F_OPEN0 + CH_MAX_ROUNDS };
+
+// gap cell of a site, -1: none
+__device__ __forceinline__ int ch_cell(const int *__restrict__ site_cell, int n_cells, int i)
+{
+    const int c = site_cell ? site_cell[i] : 0;
+    return (unsigned)c < (unsigned)n_cells ? c : -1;
+}
+
+// both terminals and no site on both sides: the cell's vertices enter the search
+__device__ __forceinline__ bool ch_active(const int *__restrict__ words, int c)
+{
+    const int *q = words + (size_t)CH_W_WORDS * c;
+    return q[CH_W_LEFT] > 0 && q[CH_W_RIGHT] > 0 && q[CH_W_BOTH] == 0;
+}
+
+__device__ __forceinline__ u64 ch_load(const u64 *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// sides and nodes from the cluster pass: touch of the site's cluster; the label where that cluster floats
+__global__ __launch_bounds__(KMCF_BLOCK) void ch_side_node_kernel(int N, const unsigned char *__restrict__ cls,
+                                                                  const int *__restrict__ label, const int *__restrict__ touch,
+                                                                  int *__restrict__ side, int *__restrict__ node)
+{
+    const int i = blockIdx.x * KMCF_BLOCK + threadIdx.x;
+    if (i >= N) return;
+    const int t = cls[i] ? (touch[label[i]] & 3) : 0;
+    side[i] = t;
+    node[i] = (cls[i] && t == 0) ? label[i] : -1;
+}
+
+// 1
+__global__ __launch_bounds__(KMCF_BLOCK) void ch_clear_kernel(int N, size_t n_cells, int *__restrict__ home, int *__restrict__ root,
+                                                              int *__restrict__ next, u64 *__restrict__ cbest,
+                                                              u64 *__restrict__ cpair, int *__restrict__ words,
+                                                              u64 *__restrict__ direct, int *__restrict__ flags)
+{
+    const size_t i = (size_t)blockIdx.x * KMCF_BLOCK + threadIdx.x;
+    if (i < (size_t)N) {
+        home[i] = CH_NO_SITE;
+        root[i] = next[i] = (int)i;
+        cbest[i] = CH_INF;
+        cpair[i] = CH_NO_PAIR;
+    }
+    if (i < n_cells) {
+        int *q = words + CH_W_WORDS * i;
+#pragma unroll
+        for (int k = 0; k < CH_W_WORDS; ++k) q[k] = 0;
+        q[CH_W_LREP] = q[CH_W_RREP] = CH_NO_SITE;
+        direct[i] = CH_INF;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < CH_F_WORDS) flags[threadIdx.x] = 0;
+}
+
+// 2: a wave adds once per gap cell it meets; the smallest L / R site of a wave's share is its first lane that holds one
+__global__ __launch_bounds__(KMCF_BLOCK) void ch_count_kernel(int N, const int *__restrict__ side, const int *__restrict__ node,
+                                                              const int *__restrict__ site_cell, int n_cells, int *words, int *home)
+{
+    const int i = blockIdx.x * KMCF_BLOCK + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const int s = i < N ? (side[i] & 3) : 0;
+    const int c = i < N ? ch_cell(site_cell, n_cells, i) : -1;
+    if (i < N && s == 0 && c >= 0) {
+        const int n = node[i];
+        if ((unsigned)n < (unsigned)N) atomicMin(home + n, i);
+    }
+    bool todo = s != 0 && c >= 0;
+    for (u64 act = __ballot(todo); act; act = __ballot(todo)) {
+        const int leader = __ffsll((long long)act) - 1;
+        const int lc = __shfl(c, leader, 64);
+        const bool mine = todo && c == lc;
+        const u64 a1 = __ballot(mine && (s & 1)), a2 = __ballot(mine && (s & 2)), a3 = __ballot(mine && s == 3);
+        const u64 l1 = __ballot(mine && s == 1), r1 = __ballot(mine && s == 2);
+        if (lane == leader) {
+            int *q = words + (size_t)CH_W_WORDS * lc;
+            const int i0 = i - lane;
+            if (a1) atomicAdd(q + CH_W_LEFT, __popcll(a1));
+            if (a2) atomicAdd(q + CH_W_RIGHT, __popcll(a2));
+            if (a3) atomicAdd(q + CH_W_BOTH, __popcll(a3));
+            if (l1) atomicMin(q + CH_W_LREP, i0 + __ffsll((long long)l1) - 1);
+            if (r1) atomicMin(q + CH_W_RREP, i0 + __ffsll((long long)r1) - 1);
+        }
+        if (mine) todo = false;
+    }
+}
+
+// 3
+__global__ __launch_bounds__(KMCF_BLOCK) void ch_vertex_kernel(int N, const int *__restrict__ side, const int *__restrict__ node,
+                                                               const int *__restrict__ site_cell, int n_cells,
+                                                               const int *__restrict__ home, int *words,
+                                                               int *__restrict__ svert, int *__restrict__ svcell)
+{
+    const int i = blockIdx.x * KMCF_BLOCK + threadIdx.x;
+    if (i >= N) return;
+    const int s = side[i] & 3;
+    const int c = ch_cell(site_cell, n_cells, i);
+    int vert = -1, vc = -1;
+    if (c >= 0 && s == 0) {
+        const int n = node[i];
+        if ((unsigned)n < (unsigned)N) {
+            vert = home[n];
+            vc = ch_cell(site_cell, n_cells, vert);              // (the home is a stone site: it has a cell)
+            int *q = words + (size_t)CH_W_WORDS * vc;
+            atomicAdd(q + CH_W_STONE_SITES, 1);
+            if (vert == i) atomicAdd(q + CH_W_STONES, 1);
+        }
+    } else if (c >= 0 && s != 3) {
+        vc = c;
+        vert = words[(size_t)CH_W_WORDS * c + (s == 1 ? CH_W_LREP : CH_W_RREP)];   // (final: written by an earlier launch)
+    }
+    // the counts of the sides are final; the stone counts this kernel adds are not read here
+    const bool member = vert >= 0 && ch_active(words, vc);
+    svert[i] = member ? vert : -1;
+    svcell[i] = vc;
+}
+
+// 4: per-tile counts of the list flags.  surf == nullptr: the members; else: the surface members
+__device__ __forceinline__ int ch_flag(const int *__restrict__ svert, const int *__restrict__ surf, int i)
+{
+    return svert[i] >= 0 && (!surf || surf[i]);
+}
+
+__global__ __launch_bounds__(KMCF_BLOCK) void ch_flag_count_kernel(int N, const int *__restrict__ cell_order,
+                                                                   const int *__restrict__ svert, const int *__restrict__ surf,
+                                                                   int *__restrict__ sum)
+{
+    __shared__ int lds[4];
+    int f[KMCF_SCAN_ITEMS];
+    kmcf_tile_flags(N, f, [&](int t) { return ch_flag(svert, surf, cell_order[t]); });
+    const int n = kmcf_tile_count(f, lds);
+    if (threadIdx.x == 0) sum[blockIdx.x] = n;
+}
+
+// 6: positions of the flags (every slot of the cell order: the runs of the search start at cell boundaries) and the list
+__global__ __launch_bounds__(KMCF_BLOCK) void ch_scatter_kernel(int N, int nb, const int *__restrict__ cell_order,
+                                                                const int *__restrict__ svert, const int *__restrict__ surf,
+                                                                const int *__restrict__ svcell, const int *__restrict__ root,
+                                                                const double *__restrict__ x, const double *__restrict__ y,
+                                                                const double *__restrict__ z, const int *__restrict__ sum,
+                                                                int *__restrict__ lpos, int *__restrict__ lsite,
+                                                                int *__restrict__ lvcell, int *__restrict__ lvert,
+                                                                int *__restrict__ lcomp, double *__restrict__ lx,
+                                                                double *__restrict__ ly, double *__restrict__ lz)
+{
+    __shared__ int lds[4];
+    const int t0 = kmcf_tile_item0();
+    int f[KMCF_SCAN_ITEMS], site[KMCF_SCAN_ITEMS];
+    kmcf_tile_flags(N, f, [&](int t) { return ch_flag(svert, surf, site[t - t0] = cell_order[t]); });
+    int pos = kmcf_tile_pos(f, sum[blockIdx.x], lds);
+#pragma unroll
+    for (int k = 0; k < KMCF_SCAN_ITEMS; ++k) {
+        const int t = t0 + k;
+        if (t >= N) break;
+        lpos[t] = pos;
+        if (!f[k]) continue;
+        const int i = site[k], v = svert[i];
+        lsite[pos] = i;
+        lvcell[pos] = svcell[i];
+        lvert[pos] = v;
+        lcomp[pos] = root[v];
+        lx[pos] = x[i];
+        ly[pos] = y[i];
+        lz[pos] = z[i];
+        ++pos;
+    }
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == KMCF_BLOCK - 1) lpos[N] = sum[nb];
+}
+
+// Lower bound of |v_b - v| over the sites b of index cell column `a` next to the column `c` of v (a = c - 1 or c + 1):
+// the distance to the face between them, shortened by far more than the cell rule can misplace a site (relative 1e-9).
+// (The margin and the rule of the gap search, kmcf_gap.hip.)
+__device__ __forceinline__ double ch_face_dist(double v, double v0, double edge, int c, int a)
+{
+    const double f = v0 + (double)(a > c ? c + 1 : c) * edge;
+    const double d = (a > c ? f - v : v - f) - 1e-9 * (fabs(f) + fabs(v) + edge);
+    return d > 0.0 ? d : 0.0;
+}
+
+// a: the search of one round over the list.  A group of CH_LPS lanes per member; the loop runs over whole blocks of
+// groups, and every loop bound and threshold is uniform over a group, so its lanes reach the shuffles together.
+// FIRST: round 1 -- components are vertices, the surface marks, direct2.
+template <bool FIRST>
+__global__ __launch_bounds__(KMCF_BLOCK) void ch_search_kernel(kmcf_cell_grid g, const int *__restrict__ cell_start,
+                                                               const int *__restrict__ lpos, const int *__restrict__ n_list,
+                                                               const int *__restrict__ lsite, const int *__restrict__ lvcell,
+                                                               const int *__restrict__ lcomp, const double *__restrict__ lx,
+                                                               const double *__restrict__ ly, const double *__restrict__ lz,
+                                                               double rmax2, const int *__restrict__ words, u64 *cbest,
+                                                               u64 *direct, u64 *__restrict__ ld2, int *__restrict__ lj,
+                                                               int *__restrict__ surf, int *flags)
+{
+    const int n = *n_list;
+    const int lane = threadIdx.x % CH_LPS;
+    const int rows = (n + CH_SPB - 1) / CH_SPB * CH_SPB;
+    const double inf = __longlong_as_double((long long)CH_INF);
+    for (int k = blockIdx.x * CH_SPB + threadIdx.x / CH_LPS; k < rows; k += gridDim.x * CH_SPB) {
+        const bool valid = k < n;
+        double bd = inf;                    // this lane's minimum (d2, partner)
+        int bb = CH_NO_SITE;
+        double dd = inf;                    // FIRST, L members: this lane's smallest d2 to an R member of the cell
+        int vc = -1, comp = -1, a = -1;
+        bool is_left = false;
+        if (valid) {
+            a = lsite[k];
+            vc = lvcell[k];
+            comp = lcomp[k];
+            const double xa = lx[k], ya = ly[k], za = lz[k];
+            const int cx = kmcf_cell_coord(xa, g.x0, g.inv, g.ncx), cy = kmcf_cell_coord(ya, g.y0, g.inv, g.ncy),
+                      cz = kmcf_cell_coord(za, g.z0, g.inv, g.ncz);
+            double thr = rmax2;             // no pair with a larger d2 can be this member's or its component's result
+            double thr_dir = -1.0;          // ... or the cell's direct2 (L members of round 1 only)
+            int rrep = -1;
+            if (FIRST) {
+                const int *q = words + (size_t)CH_W_WORDS * vc;
+                is_left = comp == q[CH_W_LREP];
+                rrep = q[CH_W_RREP];
+                if (is_left) thr_dir = fmin(rmax2, __shfl(__longlong_as_double((long long)ch_load(direct + vc)), 0, CH_LPS));
+            } else {
+                // (the group's first lane's read for all of them: the loops below must not part the group's lanes)
+                const double seen = __shfl(__longlong_as_double((long long)ch_load(cbest + comp)), 0, CH_LPS);
+                if (seen < thr) thr = seen;
+            }
+            for (int ax = max(cx - 1, 0); ax <= min(cx + 1, g.ncx - 1); ++ax) {
+                const double fx = ax == cx ? 0.0 : ch_face_dist(xa, g.x0, g.edge, cx, ax);
+                for (int ay = max(cy - 1, 0); ay <= min(cy + 1, g.ncy - 1); ++ay) {
+                    const double fy = ay == cy ? 0.0 : ch_face_dist(ya, g.y0, g.edge, cy, ay);
+                    const double bound = fx * fx + fy * fy;
+                    if (bound > thr && bound > thr_dir) continue;
+                    // cells (ax, ay, cz-1..cz+1) are contiguous in the cell order: one run
+                    const int c_lo = (ax * g.ncy + ay) * g.ncz + max(cz - 1, 0);
+                    const int c_hi = (ax * g.ncy + ay) * g.ncz + min(cz + 1, g.ncz - 1);
+                    const int b = lpos[cell_start[c_lo]], e = lpos[cell_start[c_hi + 1]];
+                    if (b == e) continue;
+                    for (int t = b + lane; t < e; t += CH_LPS) {
+                        if (lvcell[t] != vc) continue;
+                        const int ct = lcomp[t];
+                        if (ct == comp) continue;
+                        const double dx = xa - lx[t], dy = ya - ly[t], dz = za - lz[t];
+                        const double d2 = (dx * dx + dy * dy) + dz * dz;
+                        if (d2 <= rmax2) {
+                            const int j = lsite[t];
+                            if (d2 < bd || (d2 == bd && j < bb)) { bd = d2; bb = j; }
+                            if (FIRST && is_left && ct == rrep && d2 < dd) dd = d2;
+                        }
+                    }
+                    double m = bd;
+#pragma unroll
+                    for (int off = CH_LPS / 2; off >= 1; off >>= 1) m = fmin(m, __shfl_xor(m, off, 64));
+                    if (m < thr) thr = m;
+                    if (FIRST && is_left) {
+                        double md = dd;
+#pragma unroll
+                        for (int off = CH_LPS / 2; off >= 1; off >>= 1) md = fmin(md, __shfl_xor(md, off, 64));
+                        if (md < thr_dir) thr_dir = md;
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int off = CH_LPS / 2; off >= 1; off >>= 1) {
+            const double od = __shfl_xor(bd, off, 64);
+            const int ob = __shfl_xor(bb, off, 64);
+            if (od < bd || (od == bd && ob < bb)) { bd = od; bb = ob; }
+            if (FIRST) dd = fmin(dd, __shfl_xor(dd, off, 64));
+        }
+        const bool found = valid && lane == 0 && bb != CH_NO_SITE;
+        if (valid && lane == 0) {
+            ld2[k] = (u64)__double_as_longlong(bd);
+            lj[k] = found ? bb : -1;
+            if (found) atomicMin(cbest + comp, (u64)__double_as_longlong(bd));
+            if (FIRST) {
+                surf[a] = found;
+                if (is_left && dd < inf) atomicMin(direct + vc, (u64)__double_as_longlong(dd));
+            }
+        }
+        if (FIRST) {
+            const u64 fm = __ballot(found);
+            if ((threadIdx.x & 63) == 0 && fm) atomicAdd(flags + CH_F_SURFACE, __popcll(fm));
+        }
+    }
+}
+
+// b: cbest[] is final (earlier launch); few members attain it
+__global__ __launch_bounds__(KMCF_BLOCK) void ch_pair_kernel(const int *__restrict__ n_list, const int *__restrict__ lsite,
+                                                             const int *__restrict__ lcomp, const u64 *__restrict__ ld2,
+                                                             const int *__restrict__ lj, const u64 *__restrict__ cbest, u64 *cpair)
+{
+    const int n = *n_list;
+    for (int k = blockIdx.x * KMCF_BLOCK + threadIdx.x; k < n; k += gridDim.x * KMCF_BLOCK) {
+        const int j = lj[k];
+        if (j < 0) continue;
+        const int comp = lcomp[k], a = lsite[k];
+        if (ld2[k] == cbest[comp]) atomicMin(cpair + comp, ((u64)(unsigned)min(a, j) << 32) | (unsigned)max(a, j));
+    }
+}
+
+// c: root[] and cpair[] are read, next[] and the edge list are written
+__global__ __launch_bounds__(KMCF_BLOCK) void ch_hook_kernel(int N, const int *__restrict__ svert, const int *__restrict__ root,
+                                                             const u64 *__restrict__ cbest, const u64 *__restrict__ cpair,
+                                                             int *__restrict__ next, ch_edge *__restrict__ edges, int *flags)
+{
+    const int v = blockIdx.x * KMCF_BLOCK + threadIdx.x;
+    if (v >= N) return;
+    int to = v;
+    const u64 pr = root[v] == v ? cpair[v] : CH_NO_PAIR;          // (a site that is no vertex has no pair)
+    if (pr != CH_NO_PAIR) {
+        ch_edge e;
+        e.d2 = cbest[v];
+        e.a = (int)(pr >> 32);
+        e.b = (int)(pr & 0xffffffffull);
+        e.va = svert[e.a];
+        e.vb = svert[e.b];
+        const int ra = root[e.va], rb = root[e.vb];
+        const int other = ra == v ? rb : ra;
+        const bool mutual = cpair[other] == pr;
+        if (!(mutual && v < other)) to = other;
+        if (!(mutual && v > other)) {
+            const int slot = atomicAdd(flags + CH_F_EDGES, 1);
+            if (slot < N) edges[slot] = e;
+            else atomicOr(flags + CH_F_ERROR, 1);
+        }
+    }
+    next[v] = to;
+}
+
+// d: the hooks form a forest (next[] is not written here); its depth is below N
+__global__ __launch_bounds__(KMCF_BLOCK) void ch_jump_kernel(int N, const int *__restrict__ next, int *__restrict__ root,
+                                                             u64 *__restrict__ cbest, u64 *__restrict__ cpair, int *flags)
+{
+    const int v = blockIdx.x * KMCF_BLOCK + threadIdx.x;
+    if (v >= N) return;
+    int r = root[v];
+    for (int s = 0; s < N; ++s) {
+        const int t = next[r];
+        if (t == r) break;
+        r = t;
+    }
+    if (next[r] != r) atomicOr(flags + CH_F_ERROR, 2);
+    root[v] = r;
+    cbest[v] = CH_INF;
+    cpair[v] = CH_NO_PAIR;
+}
+
+// e
+__global__ __launch_bounds__(KMCF_BLOCK) void ch_open_kernel(size_t n_cells, const int *__restrict__ words,
+                                                             const int *__restrict__ root, int *flag)
+{
+    const size_t c = (size_t)blockIdx.x * KMCF_BLOCK + threadIdx.x;
+    bool open = false;
+    if (c < n_cells && ch_active(words, (int)c)) {
+        const int *q = words + CH_W_WORDS * c;
+        open = root[q[CH_W_LREP]] != root[q[CH_W_RREP]];
+    }
+    const u64 m = __ballot(open);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(flag, __popcll(m));
+}
+
+// f (round 3 on): the components of the list
+__global__ __launch_bounds__(KMCF_BLOCK) void ch_comp_kernel(const int *__restrict__ n_list, const int *__restrict__ lvert,
+                                                             const int *__restrict__ root, int *__restrict__ lcomp)
+{
+    const int n = *n_list;
+    for (int k = blockIdx.x * KMCF_BLOCK + threadIdx.x; k < n; k += gridDim.x * KMCF_BLOCK) lcomp[k] = root[lvert[k]];
+}
+
+// scratch on the index, grown on demand and freed by kmcf_pairwise_destroy; it holds nothing a later call reads
+int ch_workspace(kmcf_pairwise *p, size_t n_cells)
+{
+    if (!p->chain_ws) {
+        kmcf_chain_ws *w = p->chain_ws = new kmcf_chain_ws();
+        const size_t n = (size_t)p->N, nb = (n + KMCF_SCAN_TILE - 1) / KMCF_SCAN_TILE;
+        w->N = p->N;
+        for (int **q : {&w->d_side, &w->d_node, &w->d_home, &w->d_svert, &w->d_svcell, &w->d_surf, &w->d_root, &w->d_next,
+                        &w->d_lsite, &w->d_lvcell, &w->d_lvert, &w->d_lcomp, &w->d_lj})
+            KMCF_TRY(kmcf_dev_alloc(q, n, false));
+        for (u64 **q : {&w->d_cbest, &w->d_cpair, &w->d_ld2}) KMCF_TRY(kmcf_dev_alloc(q, n, false));
+        for (double **q : {&w->d_lx, &w->d_ly, &w->d_lz}) KMCF_TRY(kmcf_dev_alloc(q, n, false));
+        KMCF_TRY(kmcf_dev_alloc(&w->d_lpos, n + 1, false));
+        KMCF_TRY(kmcf_dev_alloc(&w->d_sum, nb + 1, false));
+        KMCF_TRY(kmcf_dev_alloc(&w->d_edges, n, false));
+        KMCF_TRY(kmcf_dev_alloc(&w->d_flags, (size_t)CH_F_WORDS, false));
+    }
+    kmcf_chain_ws *w = p->chain_ws;
+    if (w->cap_cells < n_cells) {                      // two buffers of one capacity, exact size
+        w->cap_cells = 0;
+        KMCF_TRY(kmcf_dev_grow(&w->d_words, nullptr, (size_t)CH_W_WORDS * n_cells, 0));
+        KMCF_TRY(kmcf_dev_grow(&w->d_direct, nullptr, n_cells, 0));
+        w->cap_cells = n_cells;
+    }
+    return KMCF_OK;
+}
+
+// the argument checks both entry points share; p comes last: everything before it is checked without an index
+int ch_check_common(const char *what, const kmcf_pairwise *p, const double *d_x, const double *d_y, const double *d_z,
+                    double r_max, const int *d_site_cell, int n_cells, const kmcf_chain_t *h_chains, const kmcf_hop_t *h_hops,
+                    int max_hops)
+{
+    KMCF_CHECK(d_x, KMCF_ERR_ARG, "%s: d_x is NULL", what);
+    KMCF_CHECK(d_y, KMCF_ERR_ARG, "%s: d_y is NULL", what);
+    KMCF_CHECK(d_z, KMCF_ERR_ARG, "%s: d_z is NULL", what);
+    KMCF_CHECK(h_chains, KMCF_ERR_ARG, "%s: h_chains is NULL", what);
+    KMCF_CHECK(std::isfinite(r_max), KMCF_ERR_ARG, "%s: r_max is not finite", what);
+    KMCF_CHECK(r_max > 0.0, KMCF_ERR_ARG, "%s: r_max = %g is not > 0", what, r_max);
+    KMCF_CHECK(n_cells >= 1, KMCF_ERR_ARG, "%s: n_cells = %d is not >= 1", what, n_cells);
+    KMCF_CHECK(d_site_cell || n_cells == 1, KMCF_ERR_ARG, "%s: d_site_cell is NULL with n_cells = %d", what, n_cells);
+    KMCF_CHECK(max_hops >= 0, KMCF_ERR_ARG, "%s: max_hops = %d is negative", what, max_hops);
+    KMCF_CHECK(!h_hops || max_hops > 0, KMCF_ERR_ARG, "%s: h_hops is set with max_hops = 0", what);
+    KMCF_CHECK(h_hops || max_hops == 0, KMCF_ERR_ARG, "%s: h_hops is NULL with max_hops = %d", what, max_hops);
+    KMCF_CHECK(p, KMCF_ERR_ARG, "%s: p is NULL", what);
+    KMCF_CHECK(!p->pbc, KMCF_ERR_ARG, "%s: the index is periodic (kmcf_compute_cutoff_list_pbc with pbc = 1) and the chain "
+               "search is non-periodic: build a non-periodic index", what);
+    KMCF_CHECK(r_max <= p->cutoff, KMCF_ERR_ARG, "%s: r_max = %g exceeds the index's cutoff radius %g", what, r_max, p->cutoff);
+    return KMCF_OK;
+}
+
+// steps 4-6: the list of the members (surf == nullptr) or of the surface members
+void ch_compact(kmcf_pairwise *p, const int *surf, const double *d_x, const double *d_y, const double *d_z)
+{
+    kmcf_chain_ws *w = p->chain_ws;
+    hipStream_t st = p->comm->stream;
+    const int N = p->N, nb = (N + KMCF_SCAN_TILE - 1) / KMCF_SCAN_TILE;
+    ch_flag_count_kernel<<<nb, KMCF_BLOCK, 0, st>>>(N, p->d_cell_order, w->d_svert, surf, w->d_sum);
+    kmcf_scan_counts_kernel<int><<<1, KMCF_BLOCK, 0, st>>>(nb, w->d_sum, w->d_sum, nb + 1);
+    ch_scatter_kernel<<<nb, KMCF_BLOCK, 0, st>>>(N, nb, p->d_cell_order, w->d_svert, surf, w->d_svcell, w->d_root, d_x, d_y, d_z,
+                                                w->d_sum, w->d_lpos, w->d_lsite, w->d_lvcell, w->d_lvert, w->d_lcomp, w->d_lx,
+                                                w->d_ly, w->d_lz);
+}
+
+struct ch_result {
+    int rounds = 0, edges = 0, surface = 0;
+};
+
+// steps 1-6 and the rounds, behind whatever produced the sides and nodes; one synchronisation per round
+int ch_search(const char *what, kmcf_pairwise *p, const double *d_x, const double *d_y, const double *d_z, const int *d_side,
+              const int *d_node, double r_max, const int *d_site_cell, int n_cells, ch_result *res)
+{
+    kmcf_chain_ws *w = p->chain_ws;
+    hipStream_t st = p->comm->stream;
+    const int N = p->N, nb = (N + KMCF_SCAN_TILE - 1) / KMCF_SCAN_TILE;
+    const int site_grid = (N + KMCF_BLOCK - 1) / KMCF_BLOCK;
+    const size_t nc = (size_t)n_cells;
+    const int cell_grid = (int)((nc + KMCF_BLOCK - 1) / KMCF_BLOCK);
+    const int *n_list = w->d_sum + nb;
+    const int search_grid = (int)std::min<int64_t>(8192, ((int64_t)N + CH_SPB - 1) / CH_SPB);   // the kernel strides
+    const int list_grid = std::min(site_grid, 2048);
+    const double rmax2 = r_max * r_max;
+
+    ch_clear_kernel<<<std::max(site_grid, cell_grid), KMCF_BLOCK, 0, st>>>(N, nc, w->d_home, w->d_root, w->d_next, w->d_cbest,
+                                                                         w->d_cpair, w->d_words, w->d_direct, w->d_flags);
+    ch_count_kernel<<<site_grid, KMCF_BLOCK, 0, st>>>(N, d_side, d_node, d_site_cell, n_cells, w->d_words, w->d_home);
+    ch_vertex_kernel<<<site_grid, KMCF_BLOCK, 0, st>>>(N, d_side, d_node, d_site_cell, n_cells, w->d_home, w->d_words, w->d_svert,
+                                                      w->d_svcell);
+    ch_compact(p, nullptr, d_x, d_y, d_z);
+    int h[CH_F_WORDS];
+    int edges_before = 0;
+    for (int round = 1; round <= CH_MAX_ROUNDS; ++round) {
+        if (round == 1)
+            ch_search_kernel<true><<<search_grid, KMCF_BLOCK, 0, st>>>(p->grid(), p->d_cell_start, w->d_lpos, n_list, w->d_lsite,
+                                                                      w->d_lvcell, w->d_lcomp, w->d_lx, w->d_ly, w->d_lz, rmax2,
+                                                                      w->d_words, w->d_cbest, w->d_direct, w->d_ld2, w->d_lj,
+                                                                      w->d_surf, w->d_flags);
+        else
+            ch_search_kernel<false><<<search_grid, KMCF_BLOCK, 0, st>>>(p->grid(), p->d_cell_start, w->d_lpos, n_list, w->d_lsite,
+                                                                       w->d_lvcell, w->d_lcomp, w->d_lx, w->d_ly, w->d_lz, rmax2,
+                                                                       w->d_words, w->d_cbest, w->d_direct, w->d_ld2, w->d_lj,
+                                                                       w->d_surf, w->d_flags);
+        ch_pair_kernel<<<list_grid, KMCF_BLOCK, 0, st>>>(n_list, w->d_lsite, w->d_lcomp, w->d_ld2, w->d_lj, w->d_cbest, w->d_cpair);
+        ch_hook_kernel<<<site_grid, KMCF_BLOCK, 0, st>>>(N, w->d_svert, w->d_root, w->d_cbest, w->d_cpair, w->d_next, w->d_edges,
+                                                        w->d_flags);
+        ch_jump_kernel<<<site_grid, KMCF_BLOCK, 0, st>>>(N, w->d_next, w->d_root, w->d_cbest, w->d_cpair, w->d_flags);
+        ch_open_kernel<<<cell_grid, KMCF_BLOCK, 0, st>>>(nc, w->d_words, w->d_root, w->d_flags + CH_F_OPEN0 + round - 1);
+        KMCF_HIP(hipGetLastError());
+        KMCF_HIP(hipMemcpyAsync(h, w->d_flags, sizeof(h), hipMemcpyDeviceToHost, st));
+        KMCF_HIP(hipStreamSynchronize(st));
+        KMCF_CHECK(h[CH_F_ERROR] == 0, KMCF_ERR_STATE, "%s: the component forest is inconsistent (flag %d)", what, h[CH_F_ERROR]);
+        res->rounds = round;
+        res->edges = h[CH_F_EDGES];
+        res->surface = h[CH_F_SURFACE];
+        if (h[CH_F_EDGES] == edges_before || h[CH_F_OPEN0 + round - 1] == 0) return KMCF_OK;
+        edges_before = h[CH_F_EDGES];
+        if (round == 1) ch_compact(p, w->d_surf, d_x, d_y, d_z);
+        else ch_comp_kernel<<<list_grid, KMCF_BLOCK, 0, st>>>(n_list, w->d_lvert, w->d_root, w->d_lcomp);
+    }
+    KMCF_CHECK(false, KMCF_ERR_STATE, "%s: the search did not stop within %d rounds", what, CH_MAX_ROUNDS);
+    return KMCF_OK;
+}
+
+bool ch_key_less(const ch_edge &p, const ch_edge &q)
+{
+    return p.d2 != q.d2 ? p.d2 < q.d2 : (p.a != q.a ? p.a < q.a : p.b < q.b);
+}
+
+// the copies, the last synchronisation, and the host's part: the tree walk per cell, the records, the hop lists
+int ch_finish(kmcf_pairwise *p, int n_cells, const ch_result &res, kmcf_chain_t *h_chains, kmcf_hop_t *h_hops, int max_hops,
+              hipEvent_t ev_mid, kmcf_chain_stats_t *stats)
+{
+    kmcf_comm *c = p->comm;
+    kmcf_chain_ws *w = p->chain_ws;
+    hipStream_t st = c->stream;
+    const double inf = std::numeric_limits<double>::infinity();
+    std::vector<int> words((size_t)CH_W_WORDS * n_cells);
+    std::vector<u64> direct((size_t)n_cells);
+    std::vector<ch_edge> edges((size_t)res.edges);
+    KMCF_HIP(hipMemcpyAsync(words.data(), w->d_words, words.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+    KMCF_HIP(hipMemcpyAsync(direct.data(), w->d_direct, direct.size() * sizeof(u64), hipMemcpyDeviceToHost, st));
+    if (res.edges) KMCF_HIP(hipMemcpyAsync(edges.data(), w->d_edges, edges.size() * sizeof(ch_edge), hipMemcpyDeviceToHost, st));
+    KMCF_HIP(hipEventRecord(c->ev_call1, st));
+    KMCF_HIP(hipStreamSynchronize(st));
+
+    std::sort(edges.begin(), edges.end(), ch_key_less);
+    std::unordered_map<int, std::vector<int>> adj;             // vertex -> its forest edges, ascending key
+    for (int e = 0; e < (int)edges.size(); ++e) {
+        adj[edges[e].va].push_back(e);
+        adj[edges[e].vb].push_back(e);
+    }
+    kmcf_chain_stats_t s = {};
+    const kmcf_hop_t no_hop = {-1, -1, inf};
+    if (h_hops) std::fill(h_hops, h_hops + (size_t)n_cells * max_hops, no_hop);
+    std::unordered_map<int, int> via;                          // vertex -> the edge it was reached through
+    std::vector<int> stack;
+    std::vector<kmcf_hop_t> hops;
+    for (int k = 0; k < n_cells; ++k) {
+        const int *q = words.data() + (size_t)CH_W_WORDS * k;
+        kmcf_chain_t r;
+        r.hop_max = r.hop_max2 = r.direct2 = inf;
+        r.length = 0.0;
+        r.n_hops = 0;
+        r.neck_from = r.neck_to = -1;
+        r.n_stones = q[CH_W_STONES];
+        r.n_stone_sites = q[CH_W_STONE_SITES];
+        r.n_left = q[CH_W_LEFT];
+        r.n_right = q[CH_W_RIGHT];
+        s.n_stones += r.n_stones;
+        s.n_stone_sites += r.n_stone_sites;
+        if (q[CH_W_BOTH] > 0) {
+            r.status = KMCF_CHAIN_BRIDGED;
+            r.hop_max = r.hop_max2 = r.direct2 = 0.0;
+            ++s.cells_bridged;
+        } else if (r.n_left == 0 || r.n_right == 0) {
+            r.status = KMCF_CHAIN_NONE;
+            ++s.cells_none;
+        } else {
+            std::memcpy(&r.direct2, &direct[k], sizeof(double));
+            const int src = q[CH_W_LREP], dst = q[CH_W_RREP];
+            via.clear();
+            via[src] = -1;
+            stack.assign(1, src);
+            while (!stack.empty() && !via.count(dst)) {
+                const int v = stack.back();
+                stack.pop_back();
+                auto it = adj.find(v);
+                if (it == adj.end()) continue;
+                for (int e : it->second) {
+                    const int u = edges[e].va == v ? edges[e].vb : edges[e].va;
+                    if (via.emplace(u, e).second) stack.push_back(u);
+                }
+            }
+            if (!via.count(dst)) {
+                r.status = KMCF_CHAIN_OPEN;
+                ++s.cells_open;
+            } else {
+                r.status = KMCF_CHAIN_CHAINED;
+                ++s.cells_chained;
+                hops.clear();
+                for (int v = dst; v != src;) {                 // back from R: (from, to) with `to` on v's side
+                    const ch_edge &e = edges[via[v]];
+                    const bool to_b = e.vb == v;
+                    kmcf_hop_t hop;
+                    hop.from = to_b ? e.a : e.b;
+                    hop.to = to_b ? e.b : e.a;
+                    std::memcpy(&hop.d2, &e.d2, sizeof(double));
+                    hops.push_back(hop);
+                    v = to_b ? e.va : e.vb;
+                }
+                std::reverse(hops.begin(), hops.end());
+                r.n_hops = (int)hops.size();
+                size_t neck = 0;
+                for (size_t t = 0; t < hops.size(); ++t) {
+                    const kmcf_hop_t &a = hops[t], &b = hops[neck];
+                    const int alo = std::min(a.from, a.to), ahi = std::max(a.from, a.to);
+                    const int blo = std::min(b.from, b.to), bhi = std::max(b.from, b.to);
+                    if (a.d2 > b.d2 || (a.d2 == b.d2 && (alo > blo || (alo == blo && ahi > bhi)))) neck = t;
+                    r.length += std::sqrt(a.d2);
+                    if (h_hops && t < (size_t)max_hops) h_hops[(size_t)k * max_hops + t] = a;
+                }
+                r.hop_max2 = hops[neck].d2;
+                r.hop_max = std::sqrt(r.hop_max2);
+                r.neck_from = hops[neck].from;
+                r.neck_to = hops[neck].to;
+            }
+        }
+        h_chains[k] = r;
+    }
+    if (stats) {
+        s.surface_sites = res.surface;
+        s.rounds = res.rounds;
+        s.forest_edges = res.edges;
+        s.ms_clusters = 0.f;
+        if (ev_mid) KMCF_HIP(hipEventElapsedTime(&s.ms_clusters, c->ev_t0, ev_mid));
+        KMCF_HIP(hipEventElapsedTime(&s.ms_search, ev_mid ? ev_mid : c->ev_t0, c->ev_call1));
+        *stats = s;
+    }
+    return KMCF_OK;
+}
+
+}  // namespace
+
+extern "C" int kmcf_site_set_chain(kmcf_pairwise *p, const double *d_x, const double *d_y, const double *d_z,
+                                   const int *d_site_side, const int *d_site_node, double r_max, const int *d_site_cell,
+                                   int n_cells, kmcf_chain_t *h_chains, kmcf_hop_t *h_hops, int max_hops,
+                                   kmcf_chain_stats_t *stats)
+{
+    const char *what = "kmcf_site_set_chain";
+    KMCF_CHECK(d_site_side, KMCF_ERR_ARG, "%s: d_site_side is NULL", what);
+    KMCF_CHECK(d_site_node, KMCF_ERR_ARG, "%s: d_site_node is NULL", what);
+    KMCF_TRY(ch_check_common(what, p, d_x, d_y, d_z, r_max, d_site_cell, n_cells, h_chains, h_hops, max_hops));
+    kmcf_comm *c = p->comm;
+    KMCF_TRY(kmcf_enter(c));
+    KMCF_TRY(ch_workspace(p, (size_t)n_cells));
+    KMCF_HIP(hipEventRecord(c->ev_t0, c->stream));
+    ch_result res;
+    KMCF_TRY(ch_search(what, p, d_x, d_y, d_z, d_site_side, d_site_node, r_max, d_site_cell, n_cells, &res));
+    return ch_finish(p, n_cells, res, h_chains, h_hops, max_hops, nullptr, stats);
+}
+
+extern "C" int kmcf_filament_chain(kmcf_pairwise *p, int nn, const int *d_neigh_idx, const int *d_site_element,
+                                   const int *d_site_charge, const int *d_metals, int num_metals, const double *d_x,
+                                   const double *d_y, const double *d_z, int N_left_tot, int N_right_tot, double r_max,
+                                   const int *d_site_cell, int n_cells, kmcf_chain_t *h_chains, kmcf_hop_t *h_hops, int max_hops,
+                                   int *d_site_side, int *d_site_node, kmcf_chain_stats_t *stats)
+{
+    const char *what = "kmcf_filament_chain";
+    KMCF_CHECK(d_neigh_idx, KMCF_ERR_ARG, "%s: d_neigh_idx is NULL", what);
+    KMCF_CHECK(d_site_element, KMCF_ERR_ARG, "%s: d_site_element is NULL", what);
+    KMCF_CHECK(d_site_charge, KMCF_ERR_ARG, "%s: d_site_charge is NULL", what);
+    KMCF_CHECK(nn > 0, KMCF_ERR_ARG, "%s: nn = %d is not > 0", what, nn);
+    KMCF_CHECK(num_metals >= 0, KMCF_ERR_ARG, "%s: num_metals = %d is negative", what, num_metals);
+    KMCF_CHECK(num_metals == 0 || d_metals, KMCF_ERR_ARG, "%s: d_metals is NULL with num_metals = %d", what, num_metals);
+    KMCF_CHECK(N_left_tot >= 0, KMCF_ERR_ARG, "%s: N_left_tot = %d is negative", what, N_left_tot);
+    KMCF_CHECK(N_right_tot >= 0, KMCF_ERR_ARG, "%s: N_right_tot = %d is negative", what, N_right_tot);
+    KMCF_TRY(ch_check_common(what, p, d_x, d_y, d_z, r_max, d_site_cell, n_cells, h_chains, h_hops, max_hops));
+    const int N = p->N;
+    KMCF_CHECK((int64_t)N_left_tot + N_right_tot <= N, KMCF_ERR_ARG, "%s: N_left_tot + N_right_tot = %lld exceeds N = %d", what,
+               (long long)N_left_tot + N_right_tot, N);
+    kmcf_comm *c = p->comm;
+    KMCF_TRY(kmcf_enter(c));
+    KMCF_TRY(ch_workspace(p, (size_t)n_cells));
+    kmcf_chain_ws *w = p->chain_ws;
+    hipStream_t st = c->stream;
+    int *side = d_site_side ? d_site_side : w->d_side;
+    int *node = d_site_node ? d_site_node : w->d_node;
+    kmcf_cluster_dev cl;
+    KMCF_HIP(hipEventRecord(c->ev_t0, st));
+    KMCF_TRY(kmcf_clusters_enqueue(c, N, nn, d_neigh_idx, d_site_element, d_site_charge, d_metals, num_metals, d_x, N_left_tot,
+                                   N_right_tot, nullptr, false, 0, &cl));
+    ch_side_node_kernel<<<(N + KMCF_BLOCK - 1) / KMCF_BLOCK, KMCF_BLOCK, 0, st>>>(N, cl.cls, cl.label, cl.touch, side, node);
+    KMCF_HIP(hipEventRecord(c->ev_t1, st));
+    ch_result res;
+    KMCF_TRY(ch_search(what, p, d_x, d_y, d_z, side, node, r_max, d_site_cell, n_cells, &res));
+    return ch_finish(p, n_cells, res, h_chains, h_hops, max_hops, c->ev_t1, stats);
+}

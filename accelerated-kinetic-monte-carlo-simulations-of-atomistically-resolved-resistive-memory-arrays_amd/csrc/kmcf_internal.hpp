@@ -259,10 +259,12 @@ struct kmcf_pairwise {
     int *d_clist = nullptr;        // compacted charged sites (cell order), N
     int n_blocks = 0;
     struct kmcf_gap_ws *gap_ws = nullptr;   // scratch of kmcf_site_set_gap / kmcf_filament_gap (kmcf_gap.hip): buffers only
+    struct kmcf_chain_ws *chain_ws = nullptr;   // scratch of kmcf_site_set_chain / kmcf_filament_chain (kmcf_chain.hip): buffers only
     kmcf_cell_grid grid() const { return kmcf_cell_grid{x0, y0, z0, inv, cutoff, ncx, ncy, ncz}; }
     kmcf_cell_grid_pbc grid_pbc() const { return kmcf_cell_grid_pbc{x0, y0, z0, inv, inv_y, inv_z, lattice[1], lattice[2], ncx, ncy, ncz}; }
 };
 void kmcf_gap_ws_free(kmcf_pairwise *p);
+void kmcf_chain_ws_free(kmcf_pairwise *p);
 
 struct kmcf_subop;   // sub-block operator of the split T matrix (kmcf_tstate.hip)
 

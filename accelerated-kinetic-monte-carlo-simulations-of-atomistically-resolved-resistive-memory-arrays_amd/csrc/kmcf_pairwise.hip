@@ -293,6 +293,7 @@ extern "C" int kmcf_pairwise_destroy(kmcf_pairwise *p)
     hipSetDevice(p->comm->device);
     hipStreamSynchronize(p->comm->stream);
     kmcf_gap_ws_free(p);
+    kmcf_chain_ws_free(p);
     kmcf_dev_free_all({p->d_cell_order, p->d_cell_start, p->d_flag_pos, p->d_block_sum, p->d_clist});
     delete p;
     return KMCF_OK;

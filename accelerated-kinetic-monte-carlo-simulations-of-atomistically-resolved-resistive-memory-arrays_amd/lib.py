@@ -96,6 +96,28 @@ class GapStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class Chain(C.Structure):
+    """kmcf_chain_t"""
+    _fields_ = [("hop_max", C.c_double), ("hop_max2", C.c_double), ("length", C.c_double), ("direct2", C.c_double),
+                ("status", C.c_int), ("n_hops", C.c_int), ("neck_from", C.c_int), ("neck_to", C.c_int),
+                ("n_stones", C.c_int), ("n_stone_sites", C.c_int), ("n_left", C.c_int), ("n_right", C.c_int)]
+
+
+class Hop(C.Structure):
+    """kmcf_hop_t"""
+    _fields_ = [("from_", C.c_int), ("to", C.c_int), ("d2", C.c_double)]
+
+
+class ChainStats(C.Structure):
+    """kmcf_chain_stats_t"""
+    _fields_ = [("cells_none", C.c_int), ("cells_open", C.c_int), ("cells_chained", C.c_int), ("cells_bridged", C.c_int),
+                ("n_stones", C.c_int), ("n_stone_sites", C.c_int), ("surface_sites", C.c_int), ("rounds", C.c_int),
+                ("forest_edges", C.c_int), ("ms_clusters", C.c_float), ("ms_search", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class CurrentMapStats(C.Structure):
     """kmcf_current_map_stats_t"""
     _fields_ = [("i_injection", C.c_double), ("i_extraction", C.c_double), ("sum_through", C.c_double),
@@ -212,6 +234,10 @@ SIGNATURES = {
     "kmcf_site_set_gap_pbc": (C.c_int, [_P, _P, _P, _P, _P, C.c_double, _P, C.c_int, C.POINTER(Gap), C.POINTER(GapStats)]),
     "kmcf_filament_gap_pbc": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P,
                                         C.c_int, C.POINTER(Gap), C.c_int, C.c_double, C.c_double, _IP, _P, C.POINTER(GapStats)]),
+    "kmcf_site_set_chain": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_double, _P, C.c_int, C.POINTER(Chain), C.POINTER(Hop),
+                                      C.c_int, C.POINTER(ChainStats)]),
+    "kmcf_filament_chain": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P,
+                                      C.c_int, C.POINTER(Chain), C.POINTER(Hop), C.c_int, _P, _P, C.POINTER(ChainStats)]),
     "kmcf_neighbor_list":(C.c_int, [_P, _P, _P, _P, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _P]),
     "kmcf_neighbor_list_pbc": (C.c_int, [_P, _P, _P, _P, C.c_int, _DP, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _P]),
 }

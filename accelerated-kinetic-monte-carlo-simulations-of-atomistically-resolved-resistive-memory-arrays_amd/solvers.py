@@ -734,6 +734,63 @@ def filament_gap(kmc_comm, gpubuf, N_left_tot, N_right_tot, r_max, site_cell=Non
     return dict(gaps=gaps, profile=profile, side=side, stats=st.as_dict())
 
 
+CHAIN_DTYPE = np.dtype([("hop_max", np.float64), ("hop_max2", np.float64), ("length", np.float64), ("direct2", np.float64),
+                        ("status", np.int32), ("n_hops", np.int32), ("neck_from", np.int32), ("neck_to", np.int32),
+                        ("n_stones", np.int32), ("n_stone_sites", np.int32), ("n_left", np.int32),
+                        ("n_right", np.int32)])                                # kmcf_chain_t
+HOP_DTYPE = np.dtype([("from", np.int32), ("to", np.int32), ("d2", np.float64)])   # kmcf_hop_t
+CHAIN_NONE, CHAIN_OPEN, CHAIN_CHAINED, CHAIN_BRIDGED = 0, 1, 2, 3
+
+
+def _chain_out(n_cells, max_hops):
+    chains = np.zeros(int(n_cells), CHAIN_DTYPE)
+    hops = np.zeros((int(n_cells), int(max_hops)), HOP_DTYPE) if max_hops else None
+    return chains, hops, (hops.ctypes.data_as(C.POINTER(_L.Hop)) if hops is not None else None)
+
+
+def site_set_chain(gpubuf, site_side, site_node, r_max, site_cell=None, n_cells=1, max_hops=0):
+    """kmcf_site_set_chain on the buffers' spatial index (gpubuf.cutoff_idx, compute_cutoff_list): per gap cell the chain
+    of hops from the sites with side bit 0 to the sites with side bit 1 through the floating bodies of site_node whose
+    largest hop is as small as any chain's (definitions: include/kmcfield.h).  site_side, site_node: int32 device tensors
+    of N entries (a node outside [0, N): none); site_cell as in site_set_gap.  Returns dict(chains: numpy structured array
+    CHAIN_DTYPE of n_cells records, hops: HOP_DTYPE array (n_cells, max_hops) or None with max_hops == 0, stats: dict)."""
+    assert gpubuf.cutoff_idx is not None, "site_set_chain needs the spatial index: compute_cutoff_list first"
+    for name, t in (("site_side", site_side), ("site_node", site_node)):
+        assert t.dtype == torch.int32 and t.numel() == gpubuf.N_, name + ": N int32 entries"
+    cell = _gap_cells(gpubuf, site_cell, n_cells)
+    chains, hops, hp = _chain_out(n_cells, max_hops)
+    st = _L.ChainStats()
+    _L.check(_L.load().kmcf_site_set_chain(gpubuf.cutoff_idx, _ptr(gpubuf.site_x), _ptr(gpubuf.site_y), _ptr(gpubuf.site_z),
+                                           _ptr(site_side), _ptr(site_node), float(r_max), _ptr(cell), int(n_cells),
+                                           chains.ctypes.data_as(C.POINTER(_L.Chain)), hp, int(max_hops), C.byref(st)),
+             "kmcf_site_set_chain")
+    return dict(chains=chains, hops=hops, stats=st.as_dict())
+
+
+def filament_chain(kmc_comm, gpubuf, N_left_tot, N_right_tot, r_max, site_cell=None, n_cells=1, max_hops=0, sides=True,
+                   nodes=True):
+    """kmcf_filament_chain: the stepping-stone chain between the matter attached to the left electrode and the matter
+    attached to the right one through the floating conductive clusters, per gap cell (definitions: include/kmcfield.h).
+    Call it after update_charge_gpu and compute_cutoff_list, on the communicator the index was built with.  Returns
+    dict(chains, hops (or None), side / node: int32 device tensors of N entries or None, stats: dict)."""
+    N = gpubuf.N_
+    assert gpubuf.cutoff_idx is not None, "filament_chain needs the spatial index: compute_cutoff_list first"
+    assert gpubuf.neigh_idx is not None and gpubuf.neigh_idx.numel() == N * gpubuf.nn_, \
+        "filament_chain needs the neighbour list of the whole device"
+    cell = _gap_cells(gpubuf, site_cell, n_cells)
+    chains, hops, hp = _chain_out(n_cells, max_hops)
+    side = torch.empty(N, dtype=torch.int32, device=gpubuf.device) if sides else None
+    node = torch.empty(N, dtype=torch.int32, device=gpubuf.device) if nodes else None
+    st = _L.ChainStats()
+    _L.check(_L.load().kmcf_filament_chain(gpubuf.cutoff_idx, gpubuf.nn_, _ptr(gpubuf.neigh_idx), _ptr(gpubuf.site_element),
+                                           _ptr(gpubuf.site_charge), _ptr(gpubuf.metal_types), gpubuf.num_metal_types_,
+                                           _ptr(gpubuf.site_x), _ptr(gpubuf.site_y), _ptr(gpubuf.site_z), int(N_left_tot),
+                                           int(N_right_tot), float(r_max), _ptr(cell), int(n_cells),
+                                           chains.ctypes.data_as(C.POINTER(_L.Chain)), hp, int(max_hops), _ptr(side),
+                                           _ptr(node), C.byref(st)), "kmcf_filament_chain")
+    return dict(chains=chains, hops=hops, side=side, node=node, stats=st.as_dict())
+
+
 def k_assemble(gpubuf, Vd, high_G, low_G):
     lib = _L.load()
     _L.check(lib.kmcf_k_assemble(gpubuf.K_distributed, _ptr(gpubuf.site_element), _ptr(gpubuf.site_charge),

@@ -669,6 +669,90 @@ int kmcf_filament_gap_pbc(kmcf_pairwise *p, int nn, const int *d_neigh_idx, cons
                           int *d_site_side /* N out, or NULL */, kmcf_gap_stats_t *stats);
 
 /* ---------------------------------------------------------------------- */
+/* Tunnelling chain: the stepping-stone path between the electrode sides     */
+/* through floating bodies (no reference counterpart)                        */
+/* ---------------------------------------------------------------------- */
+/* The gap ignores everything attached to neither electrode.  Floating vacancy clusters and metal islands carry the
+ * trap-assisted tunnelling current of the high-resistance state: it hops left side, stone, stone, ..., right side, and
+ * the longest hop decides it.  Per gap cell these calls report the chain of hops whose longest hop is as short as any
+ * chain's.
+ * Inputs per site.  side: bit 0 left, bit 1 right, higher bits ignored (as in kmcf_site_set_gap).  node: the id of the
+ * floating body the site belongs to; any value outside [0, N) means none.  cell: the gap cell through d_site_cell /
+ * n_cells exactly as in the gap calls (NULL requires n_cells == 1; a value outside [0, n_cells): the site is in no cell).
+ * Terminals of gap cell c.  L_c = the sites with side bit 0 whose own cell is c, R_c the same with bit 1.  A site with
+ * both bits makes the cell BRIDGED.
+ * Stones.  A stone site has (side & 3) == 0, a valid node and a valid own cell.  The home of node n is the smallest site
+ * id among its stone sites; the whole node belongs to the gap cell of its home, and ALL its stone sites take part in that
+ * cell wherever they lie: a floating body is one object and is counted once.  The vertices of cell c are L_c, R_c and the
+ * nodes whose home cell is c.
+ * Pair distance.  d2 = (dx*dx + dy*dy) + dz*dz, every operation rounded to double, no fused multiply-add; non-periodic.  A
+ * pair counts iff d2 <= r_max*r_max, that product formed in double.  r_max is at most the index's cutoff radius.
+ * Link.  Two different vertices u, v of one cell are linked iff a pair (a in u, b in v) counts; the link's pair is the one
+ * with the smallest key (d2, min(a,b), max(a,b)).  Keys of different links differ, so the links are totally ordered.
+ * Chain of cell c.  The path between L_c and R_c in the minimum spanning forest of the cell's link graph under that order
+ * -- what Kruskal's algorithm produces on the links sorted by key; the keys being unique, the path is unique.  It is the
+ * path whose largest hop is as small as any path's.  Hops are reported oriented from L to R as (from, to, d2).
+ * direct2 is the d2 of the link L_c - R_c and is bit-equal to gap2 of kmcf_site_set_gap on the same sides.  Where that
+ * link ties with another pair of the same d2, the site pair may differ from the gap's: the gap breaks ties by (a, b), this
+ * contract by (min, max).
+ * Determinism: every output except the times depends on the input alone; two calls on the same input return the same bytes.
+ * Cost: the first search round looks at every member's whole neighbourhood within r_max, electrode bulk included; the
+ * later rounds run on the surface members only (those with a site of another vertex within r_max).  Measured on the 40 nm
+ * crossbar (1.6e6 sites, 2.4e5 members): the search takes 2.1 ms at r_max = 20 next to a cluster pass of
+ * 4.7 ms -- round 1 is the larger part of the search but does not dominate the call, which stays within 1.5 cluster passes
+ * at every radius up to the cutoff.  An index with a smaller cutoff, built for this call alone (kmcf_compute_cutoff_list
+ * with cutoff = r_max = 8, say), makes the search cheaper still: 0.8 ms against 1.4 ms at r_max = 8 on the 20 A index. */
+#define KMCF_CHAIN_NONE    0   /* L_c or R_c is empty                                   */
+#define KMCF_CHAIN_OPEN    1   /* both non-empty, no path                               */
+#define KMCF_CHAIN_CHAINED 2   /* a path exists                                         */
+#define KMCF_CHAIN_BRIDGED 3   /* a site with both bits: n_hops = 0, hop_max2 = direct2 = 0 */
+typedef struct {            /* 64 bytes */
+    double hop_max, hop_max2;    /* largest d2 on the chain (+infinity unless CHAINED or BRIDGED); hop_max = sqrt(hop_max2) */
+    double length;               /* sum of sqrt(d2) over the hops, added in chain order on the host; 0.0 without a hop */
+    double direct2;              /* d2 of the link L_c - R_c, +infinity if they are not linked     */
+    int status, n_hops;          /* KMCF_CHAIN_*; the true number of hops (also beyond max_hops)   */
+    int neck_from, neck_to;      /* the hop with the largest key, -1 when there is none            */
+    int n_stones, n_stone_sites; /* vertices / sites of the stones assigned to this cell           */
+    int n_left, n_right;         /* as in kmcf_gap_t                                               */
+} kmcf_chain_t;
+typedef struct { int from, to; double d2; } kmcf_hop_t;   /* 16 bytes */
+typedef struct {
+    int cells_none, cells_open, cells_chained, cells_bridged;
+    int n_stones, n_stone_sites;    /* whole device: the stones assigned to a cell                                    */
+    int surface_sites;              /* members of the search (sites of the vertices of OPEN / CHAINED cells) that have a
+                                       site of another vertex of their cell within r_max                               */
+    int rounds, forest_edges;       /* search rounds run; spanning-forest edges found before the search stopped        */
+    float ms_clusters, ms_search;   /* device time (HIP events), as in kmcf_gap_stats_t                                */
+} kmcf_chain_stats_t;
+
+/* LOCAL operations on WHOLE-device arrays of the index's N sites, as the gap calls; scratch lives on the index (freed by
+ * kmcf_pairwise_destroy).  h_chains: n_cells records out.  h_hops[c*max_hops + k] holds hop k of cell c for
+ * k < min(n_hops, max_hops); the rest of a cell's slots are {-1, -1, +infinity}; h_hops may be NULL when max_hops == 0.
+ * stats may be NULL.  One synchronisation per search round (a flag read) and one at the end.
+ * KMCF_ERR_ARG (before anything needs a device; kmcf_last_error names the argument): NULL coordinates, d_site_side,
+ * d_site_node, h_chains or p; r_max not finite, <= 0, or larger than the index's cutoff radius; n_cells < 1, or NULL
+ * d_site_cell with n_cells != 1; max_hops < 0, h_hops set with max_hops == 0 or NULL with max_hops > 0; a periodic index
+ * (the periodic form is a later change).  KMCF_ERR_STATE: the search did not stop within 40 rounds. */
+int kmcf_site_set_chain(kmcf_pairwise *p, const double *d_x, const double *d_y, const double *d_z,
+                        const int *d_site_side /* N */, const int *d_site_node /* N */, double r_max,
+                        const int *d_site_cell /* N, or NULL */, int n_cells,
+                        kmcf_chain_t *h_chains /* n_cells */, kmcf_hop_t *h_hops /* n_cells*max_hops, or NULL */,
+                        int max_hops, kmcf_chain_stats_t *stats /* or NULL */);
+
+/* The cluster pass of kmcf_conductive_clusters (as kmcf_filament_gap runs it), then: side[i] = touch of i's cluster for
+ * members and 0 for non-members; node[i] = the cluster label of i for the members of clusters with touch 0, metal and
+ * vacancy clusters alike, and -1 for every other site; then the search above.  d_site_side, d_site_node: N ints out, or
+ * NULL.  KMCF_ERR_ARG as above, and the list / metals / contact-count checks of kmcf_filament_gap. */
+int kmcf_filament_chain(kmcf_pairwise *p, int nn, const int *d_neigh_idx, const int *d_site_element,
+                        const int *d_site_charge, const int *d_metals, int num_metals,
+                        const double *d_x, const double *d_y, const double *d_z,
+                        int N_left_tot, int N_right_tot, double r_max,
+                        const int *d_site_cell, int n_cells, kmcf_chain_t *h_chains,
+                        kmcf_hop_t *h_hops /* n_cells*max_hops, or NULL */, int max_hops,
+                        int *d_site_side /* N out, or NULL */, int *d_site_node /* N out, or NULL */,
+                        kmcf_chain_stats_t *stats);
+
+/* ---------------------------------------------------------------------- */
 /* T path: current solve (Kirchhoff matrix with two virtual nodes + WKB       */
 /* tunnelling sub-block), SURVEY 8 rows a14 / f3.  PARITY UNPINNED: no         */
 /* reference fixture exercises it (src/KMC_comm.h:243 disables it from main).  */

@@ -5,6 +5,7 @@ prints into output<size>_<rank>.txt ("Z - calculation time - ...").
 
     python tools/kmc_loop.py [--workload 5nm|5nm-periodic|40nm|conducting] [--steps 6] [--T 300] [--current] [--rate-mode bg|ekin|site]
                              [--clusters] [--current-map] [--scheme all|half|third --select W,B] [--gap R]
+                             [--chain R [--chain-hops K]]
 
 --current adds the electro-thermal stages after the potential and before the events: conduction-band edge, current
 solve with heating (site_power), local heat solve (site_temperature); --rate-mode ekin | site lets the event rates read
@@ -27,7 +28,13 @@ how close the conductive matter attached to the left electrode comes to the matt
 to R angstrom (at most 20, the cell edge of the spatial index), per cell of structure.crossbar_lines on the crossbar
 workloads.  The step line gains `gap <ms clusters>+<ms search> [<cell>: <gap> A (<site_left>-<site_right>) L <n_left> R
 <n_right> | <cell>: bridged (<n_both> sites) L .. R .. | <cell>: none L .. R ..]`; with --clusters a bridged cell also shows
-`constriction <sites>`: the smallest number of filament vacancies in a slice of 3.2 angstrom along x.
+`constriction <sites>`: the smallest number of filament vacancies in a slice of 3.2 angstrom along x.  --chain R runs the
+tunnelling-chain analysis (kmcf_filament_chain) next to it: per cell the chain of hops from the left side to the right
+side through the floating conductive clusters whose longest hop is as short as any chain's, hops of at most R angstrom
+(at most 20; not on `5nm-periodic`: the search is non-periodic).  The step line gains `chain <ms clusters>+<ms search>
+(<rounds> rounds, <surface sites> surface) [<cell>: <hops> hops, longest <hop_max> A (<from>-<to>), length <length> A,
+direct <sqrt(direct2)> A, <stones> stones | <cell>: bridged | <cell>: open, .. stones | <cell>: none]`; --chain-hops K also
+lists the first K hops of every chain as `<from>-<to> <hop> A`.
 """
 import argparse
 import os
@@ -62,6 +69,10 @@ def main():
     ap.add_argument("--gap", type=float, default=None, metavar="R",
                     help="filament gap analysis after every charge update, searched up to R angstrom (<= 20): gap, pair and "
                          "counts per crossbar cell; with --clusters also the constriction of a bridging filament")
+    ap.add_argument("--chain", type=float, default=None, metavar="R",
+                    help="tunnelling-chain analysis after every charge update, hops of at most R angstrom (<= 20): the "
+                         "stepping-stone chain between the electrode sides per crossbar cell, its longest hop and length")
+    ap.add_argument("--chain-hops", type=int, default=0, metavar="K", help="with --chain: list the first K hops of every chain")
     a = ap.parse_args()
     periodic = a.workload == "5nm-periodic"
     if a.scheme and a.workload in ("5nm", "5nm-periodic"):
@@ -70,6 +81,12 @@ def main():
         ap.error("--current-map needs --current (the map reads the potentials of the current solve)")
     if a.gap is not None and not 0.0 < a.gap <= 20.0:
         ap.error("--gap %g: the search radius is > 0 and at most 20 (the cell edge of the spatial index)" % a.gap)
+    if a.chain is not None and not 0.0 < a.chain <= 20.0:
+        ap.error("--chain %g: the hop length is > 0 and at most 20 (the cell edge of the spatial index)" % a.chain)
+    if a.chain is not None and a.workload == "5nm-periodic":
+        ap.error("--chain: the chain search is non-periodic and refuses the periodic index of 5nm-periodic")
+    if a.chain_hops < 0 or (a.chain_hops and a.chain is None):
+        ap.error("--chain-hops K: K >= 0, with --chain")
     if a.rate_mode != "bg" and not a.current:
         ap.error("--rate-mode %s needs --current (the heat solve provides the site temperatures)" % a.rate_mode)
     S = km.solvers
@@ -118,11 +135,11 @@ def main():
         cell_of_site = km.structure.crossbar_lines(d)[2]
         buf.site_potential_boundary.copy_(torch.as_tensor(contacts))      # once: the solve reads the slots, never writes them
     gap_cells, n_gap_cells, gap_bins = None, 1, None
-    if a.gap is not None:
+    if a.gap is not None or a.chain is not None:
         if a.workload not in ("5nm", "5nm-periodic"):
             cells = km.structure.crossbar_lines(d)[2] if cell_of_site is None else cell_of_site
             gap_cells, n_gap_cells = torch.as_tensor(cells, device="cuda"), int(cells.max()) + 1
-        if a.clusters:
+        if a.clusters and a.gap is not None:
             x_lo, x_hi = float(d["xyz"][:, 0].min()), float(d["xyz"][:, 0].max()) + 1e-6
             gap_bins = (int(np.ceil((x_hi - x_lo) / 3.2)), x_lo, x_hi)
     comm.sync()
@@ -162,6 +179,26 @@ def main():
                     what = "none"
                 cells.append("%d: %s L %d R %d" % (c, what, g["n_left"], g["n_right"]))
             clusters += " | gap %.3f+%.3f [%s]" % (gp["stats"]["ms_clusters"], gp["stats"]["ms_search"], " | ".join(cells))
+        if a.chain is not None:
+            ch = S.filament_chain(comm, buf, NL, NL, a.chain, site_cell=gap_cells, n_cells=n_gap_cells, max_hops=a.chain_hops,
+                                  sides=False, nodes=False)
+            cells = []
+            for c, r in enumerate(ch["chains"]):
+                if r["status"] == S.CHAIN_BRIDGED:
+                    what = "bridged"
+                elif r["status"] == S.CHAIN_CHAINED:
+                    what = "%d hops, longest %.4f A (%d-%d), length %.4f A, direct %.4f A, %d stones" % (
+                        r["n_hops"], r["hop_max"], r["neck_from"], r["neck_to"], r["length"], np.sqrt(r["direct2"]), r["n_stones"])
+                    for h in ch["hops"][c][:min(r["n_hops"], a.chain_hops)] if a.chain_hops else ():
+                        what += ", %d-%d %.4f A" % (h["from"], h["to"], np.sqrt(h["d2"]))
+                elif r["status"] == S.CHAIN_OPEN:
+                    what = "open, %d stones" % r["n_stones"]
+                else:
+                    what = "none"
+                cells.append("%d: %s" % (c, what))
+            st_c = ch["stats"]
+            clusters += " | chain %.3f+%.3f (%d rounds, %d surface) [%s]" % (st_c["ms_clusters"], st_c["ms_search"], st_c["rounds"],
+                                                                            st_c["surface_sites"], " | ".join(cells))
         if a.scheme:
             tb, st = timed(lambda: S.background_potential_gpu_sparse_contacts(buf, N, NL, NL, d["high_G"], d["low_G"],
                                                                               len(d["metals"])))
