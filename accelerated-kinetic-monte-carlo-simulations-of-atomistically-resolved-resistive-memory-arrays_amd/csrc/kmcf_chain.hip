@@ -35,6 +35,12 @@
 // (whatever value is read is >= the final one) and what the member has found.  Members that attain the final minimum hold
 // their exact (d2, smallest partner); the others never enter b.
 //
+// Periodic index (kmcf_site_set_chain_pbc / kmcf_filament_chain_pbc on an index of kmcf_compute_cutoff_list_pbc with pbc = 1):
+// step a is ch_search_pbc_kernel -- the minimum image in y and z, the wrapped cells each once, the bound in y taken to the
+// face through which the neighbour cell is adjacent ("Periodic search"); every other launch is shared: the
+// cell id and the order inside a cell are those of the open index (one index_cells for both, kmcf_pairwise.hip), which is
+// all the compaction reads.  d2 is the same bits from both ends of a pair, so a mutual choice is seen as one by b and c.
+//
 // Determinism: every device result is an integer sum or minimum; the order of the edge list is not, and the host sorts it
 // by key before use.  No thread waits for another; the search stops after CH_MAX_ROUNDS rounds (KMCF_ERR_STATE).
 #include <algorithm>
@@ -379,6 +385,145 @@ __global__ __launch_bounds__(KMCF_BLOCK) void ch_search_kernel(kmcf_cell_grid g,
     }
 }
 
+// Lower bound of the minimum-image |v_b - v| over the sites b of a periodic index's cell next to the cell of v, through
+// the face at f (lower: the face below v): the distance to that face, shortened by the relative 1e-9 of ch_face_dist with
+// the period in the scale -- the margin also covers the roundings of the cell rule and of fy * Ly in the distance.
+// (The margin and the rule of the gap's periodic search, kmcf_gap.hip; DESIGN 3.10, "Bound".)
+__device__ __forceinline__ double ch_face_dist_pbc(double v, double f, bool lower, double edge, double period)
+{
+    const double d = (lower ? v - f : f - v) - 1e-9 * (fabs(f) + fabs(v) + edge + period);
+    return d > 0.0 ? d : 0.0;
+}
+
+// a on a periodic index: ch_search_kernel under the minimum image in y and z (kmcf_min_image_dist's arithmetic, squared:
+// odd in the difference up to the squares, so both ends of a pair compute the same bits).  The list, the results and the
+// threshold rules are those of ch_search_kernel.  Cells as in gp_search_pbc_kernel and pairwise_pbc_kernel, each once: in
+// y the distinct cells of {cy-1, cy, cy+1} mod ncy, in z one or two runs of the compacted order; a candidate is met once
+// and has one distance, however many of its images lie within r_max.  Bound in y of a neighbour cell: ncy >= 3 -- the
+// cell below (cy-1 mod ncy) through the lower face of cy, the cell above through the upper face; ncy == 2 -- the other
+// cell is adjacent through both faces: the smaller of the two; own cell (all there is for ncy == 1): 0.  z is not pruned.
+// The x range, the number of y cells, the z runs and the thresholds depend on the member alone or are read by the
+// group's first lane and broadcast: the 16 lanes of a group never part in front of the shuffles; only the walk over a run
+// is per lane.
+template <bool FIRST>
+__global__ __launch_bounds__(KMCF_BLOCK) void ch_search_pbc_kernel(kmcf_cell_grid_pbc g, double edge_x,
+                                                                   const int *__restrict__ cell_start,
+                                                                   const int *__restrict__ lpos, const int *__restrict__ n_list,
+                                                                   const int *__restrict__ lsite, const int *__restrict__ lvcell,
+                                                                   const int *__restrict__ lcomp, const double *__restrict__ lx,
+                                                                   const double *__restrict__ ly, const double *__restrict__ lz,
+                                                                   double rmax2, const int *__restrict__ words, u64 *cbest,
+                                                                   u64 *direct, u64 *__restrict__ ld2, int *__restrict__ lj,
+                                                                   int *__restrict__ surf, int *flags)
+{
+    const int n = *n_list;
+    const int lane = threadIdx.x % CH_LPS;
+    const int rows = (n + CH_SPB - 1) / CH_SPB * CH_SPB;
+    const double inf = __longlong_as_double((long long)CH_INF);
+    const int ny = min(g.ncy, 3);               // y cells a member visits
+    const double edge_y = g.ly / (double)g.ncy;
+    for (int k = blockIdx.x * CH_SPB + threadIdx.x / CH_LPS; k < rows; k += gridDim.x * CH_SPB) {
+        const bool valid = k < n;
+        double bd = inf;                    // this lane's minimum (d2, partner)
+        int bb = CH_NO_SITE;
+        double dd = inf;                    // FIRST, L members: this lane's smallest d2 to an R member of the cell
+        int vc = -1, comp = -1, a = -1;
+        bool is_left = false;
+        if (valid) {
+            a = lsite[k];
+            vc = lvcell[k];
+            comp = lcomp[k];
+            const double xa = lx[k], ya = ly[k], za = lz[k];
+            const int cx = kmcf_cell_coord(xa, g.x0, g.inv_x, g.ncx), cy = kmcf_cell_coord(ya, g.y0, g.inv_y, g.ncy),
+                      cz = kmcf_cell_coord(za, g.z0, g.inv_z, g.ncz);
+            // z runs [lo0, hi0] and, if n_runs == 2, [lo1, hi1]
+            int n_runs = 1, lo0 = cz - 1, hi0 = cz + 1, lo1 = 0, hi1 = -1;
+            if (g.ncz <= 3) { lo0 = 0; hi0 = g.ncz - 1; }
+            else if (cz == 0) { lo0 = 0; hi0 = 1; lo1 = hi1 = g.ncz - 1; n_runs = 2; }
+            else if (cz == g.ncz - 1) { lo0 = 0; hi0 = 0; lo1 = g.ncz - 2; hi1 = g.ncz - 1; n_runs = 2; }
+            const int ay0 = g.ncy == 1 ? cy : cy - 1 + g.ncy;
+            // the faces of the member's cell in y
+            const double below = ch_face_dist_pbc(ya, g.y0 + (double)cy * edge_y, true, edge_y, g.ly);
+            const double above = ch_face_dist_pbc(ya, g.y0 + (double)(cy + 1) * edge_y, false, edge_y, g.ly);
+            double thr = rmax2;             // no pair with a larger d2 can be this member's or its component's result
+            double thr_dir = -1.0;          // ... or the cell's direct2 (L members of round 1 only)
+            int rrep = -1;
+            if (FIRST) {
+                const int *q = words + (size_t)CH_W_WORDS * vc;
+                is_left = comp == q[CH_W_LREP];
+                rrep = q[CH_W_RREP];
+                if (is_left) thr_dir = fmin(rmax2, __shfl(__longlong_as_double((long long)ch_load(direct + vc)), 0, CH_LPS));
+            } else {
+                // (the group's first lane's read for all of them: the loops below must not part the group's lanes)
+                const double seen = __shfl(__longlong_as_double((long long)ch_load(cbest + comp)), 0, CH_LPS);
+                if (seen < thr) thr = seen;
+            }
+            for (int ax = max(cx - 1, 0); ax <= min(cx + 1, g.ncx - 1); ++ax) {
+                const double fx = ax == cx ? 0.0 : ch_face_dist(xa, g.x0, edge_x, cx, ax);
+                for (int sy = 0; sy < ny; ++sy) {
+                    const int ay = (ay0 + sy) % g.ncy;
+                    const double fy = ay == cy ? 0.0 : (g.ncy == 2 ? fmin(below, above) : (sy == 0 ? below : above));
+                    const double bound = fx * fx + fy * fy;
+                    if (bound > thr && bound > thr_dir) continue;
+                    const int col = (ax * g.ncy + ay) * g.ncz;
+                    for (int run = 0; run < n_runs; ++run) {
+                        const int b = lpos[cell_start[col + (run ? lo1 : lo0)]];
+                        const int e = lpos[cell_start[col + (run ? hi1 : hi0) + 1]];
+                        for (int t = b + lane; t < e; t += CH_LPS) {
+                            if (lvcell[t] != vc) continue;
+                            const int ct = lcomp[t];
+                            if (ct == comp) continue;
+                            const double dx = xa - lx[t];
+                            double qy = (ya - ly[t]) / g.ly;
+                            qy -= round(qy);
+                            double qz = (za - lz[t]) / g.lz;
+                            qz -= round(qz);
+                            const double dy = qy * g.ly, dz = qz * g.lz;
+                            const double d2 = (dx * dx + dy * dy) + dz * dz;
+                            if (d2 <= rmax2) {
+                                const int j = lsite[t];
+                                if (d2 < bd || (d2 == bd && j < bb)) { bd = d2; bb = j; }
+                                if (FIRST && is_left && ct == rrep && d2 < dd) dd = d2;
+                            }
+                        }
+                    }
+                    double m = bd;
+#pragma unroll
+                    for (int off = CH_LPS / 2; off >= 1; off >>= 1) m = fmin(m, __shfl_xor(m, off, 64));
+                    if (m < thr) thr = m;
+                    if (FIRST && is_left) {
+                        double md = dd;
+#pragma unroll
+                        for (int off = CH_LPS / 2; off >= 1; off >>= 1) md = fmin(md, __shfl_xor(md, off, 64));
+                        if (md < thr_dir) thr_dir = md;
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int off = CH_LPS / 2; off >= 1; off >>= 1) {
+            const double od = __shfl_xor(bd, off, 64);
+            const int ob = __shfl_xor(bb, off, 64);
+            if (od < bd || (od == bd && ob < bb)) { bd = od; bb = ob; }
+            if (FIRST) dd = fmin(dd, __shfl_xor(dd, off, 64));
+        }
+        const bool found = valid && lane == 0 && bb != CH_NO_SITE;
+        if (valid && lane == 0) {
+            ld2[k] = (u64)__double_as_longlong(bd);
+            lj[k] = found ? bb : -1;
+            if (found) atomicMin(cbest + comp, (u64)__double_as_longlong(bd));
+            if (FIRST) {
+                surf[a] = found;
+                if (is_left && dd < inf) atomicMin(direct + vc, (u64)__double_as_longlong(dd));
+            }
+        }
+        if (FIRST) {
+            const u64 fm = __ballot(found);
+            if ((threadIdx.x & 63) == 0 && fm) atomicAdd(flags + CH_F_SURFACE, __popcll(fm));
+        }
+    }
+}
+
 // b: cbest[] is final (earlier launch); few members attain it
 __global__ __launch_bounds__(KMCF_BLOCK) void ch_pair_kernel(const int *__restrict__ n_list, const int *__restrict__ lsite,
                                                              const int *__restrict__ lcomp, const u64 *__restrict__ ld2,
@@ -492,7 +637,7 @@ int ch_workspace(kmcf_pairwise *p, size_t n_cells)
 // the argument checks both entry points share; p comes last: everything before it is checked without an index
 int ch_check_common(const char *what, const kmcf_pairwise *p, const double *d_x, const double *d_y, const double *d_z,
                     double r_max, const int *d_site_cell, int n_cells, const kmcf_chain_t *h_chains, const kmcf_hop_t *h_hops,
-                    int max_hops)
+                    int max_hops, bool periodic_ok)
 {
     KMCF_CHECK(d_x, KMCF_ERR_ARG, "%s: d_x is NULL", what);
     KMCF_CHECK(d_y, KMCF_ERR_ARG, "%s: d_y is NULL", what);
@@ -506,8 +651,8 @@ int ch_check_common(const char *what, const kmcf_pairwise *p, const double *d_x,
     KMCF_CHECK(!h_hops || max_hops > 0, KMCF_ERR_ARG, "%s: h_hops is set with max_hops = 0", what);
     KMCF_CHECK(h_hops || max_hops == 0, KMCF_ERR_ARG, "%s: h_hops is NULL with max_hops = %d", what, max_hops);
     KMCF_CHECK(p, KMCF_ERR_ARG, "%s: p is NULL", what);
-    KMCF_CHECK(!p->pbc, KMCF_ERR_ARG, "%s: the index is periodic (kmcf_compute_cutoff_list_pbc with pbc = 1) and the chain "
-               "search is non-periodic: build a non-periodic index", what);
+    KMCF_CHECK(periodic_ok || !p->pbc, KMCF_ERR_ARG, "%s: the index is periodic (kmcf_compute_cutoff_list_pbc with pbc = 1) and "
+               "this chain search is non-periodic: call %s_pbc for the minimum image, or build a non-periodic index", what, what);
     KMCF_CHECK(r_max <= p->cutoff, KMCF_ERR_ARG, "%s: r_max = %g exceeds the index's cutoff radius %g", what, r_max, p->cutoff);
     return KMCF_OK;
 }
@@ -553,7 +698,17 @@ int ch_search(const char *what, kmcf_pairwise *p, const double *d_x, const doubl
     int h[CH_F_WORDS];
     int edges_before = 0;
     for (int round = 1; round <= CH_MAX_ROUNDS; ++round) {
-        if (round == 1)
+        if (p->pbc && round == 1)
+            ch_search_pbc_kernel<true><<<search_grid, KMCF_BLOCK, 0, st>>>(p->grid_pbc(), p->cutoff, p->d_cell_start, w->d_lpos, n_list,
+                                                                          w->d_lsite, w->d_lvcell, w->d_lcomp, w->d_lx, w->d_ly,
+                                                                          w->d_lz, rmax2, w->d_words, w->d_cbest, w->d_direct,
+                                                                          w->d_ld2, w->d_lj, w->d_surf, w->d_flags);
+        else if (p->pbc)
+            ch_search_pbc_kernel<false><<<search_grid, KMCF_BLOCK, 0, st>>>(p->grid_pbc(), p->cutoff, p->d_cell_start, w->d_lpos, n_list,
+                                                                           w->d_lsite, w->d_lvcell, w->d_lcomp, w->d_lx, w->d_ly,
+                                                                           w->d_lz, rmax2, w->d_words, w->d_cbest, w->d_direct,
+                                                                           w->d_ld2, w->d_lj, w->d_surf, w->d_flags);
+        else if (round == 1)
             ch_search_kernel<true><<<search_grid, KMCF_BLOCK, 0, st>>>(p->grid(), p->d_cell_start, w->d_lpos, n_list, w->d_lsite,
                                                                       w->d_lvcell, w->d_lcomp, w->d_lx, w->d_ly, w->d_lz, rmax2,
                                                                       w->d_words, w->d_cbest, w->d_direct, w->d_ld2, w->d_lj,
@@ -702,17 +857,14 @@ int ch_finish(kmcf_pairwise *p, int n_cells, const ch_result &res, kmcf_chain_t 
     return KMCF_OK;
 }
 
-}  // namespace
-
-extern "C" int kmcf_site_set_chain(kmcf_pairwise *p, const double *d_x, const double *d_y, const double *d_z,
-                                   const int *d_site_side, const int *d_site_node, double r_max, const int *d_site_cell,
-                                   int n_cells, kmcf_chain_t *h_chains, kmcf_hop_t *h_hops, int max_hops,
-                                   kmcf_chain_stats_t *stats)
+// the body of kmcf_site_set_chain and kmcf_site_set_chain_pbc: they differ in the name and in whether a periodic index passes
+int ch_site_set_chain(const char *what, bool periodic_ok, kmcf_pairwise *p, const double *d_x, const double *d_y, const double *d_z,
+                      const int *d_site_side, const int *d_site_node, double r_max, const int *d_site_cell, int n_cells,
+                      kmcf_chain_t *h_chains, kmcf_hop_t *h_hops, int max_hops, kmcf_chain_stats_t *stats)
 {
-    const char *what = "kmcf_site_set_chain";
     KMCF_CHECK(d_site_side, KMCF_ERR_ARG, "%s: d_site_side is NULL", what);
     KMCF_CHECK(d_site_node, KMCF_ERR_ARG, "%s: d_site_node is NULL", what);
-    KMCF_TRY(ch_check_common(what, p, d_x, d_y, d_z, r_max, d_site_cell, n_cells, h_chains, h_hops, max_hops));
+    KMCF_TRY(ch_check_common(what, p, d_x, d_y, d_z, r_max, d_site_cell, n_cells, h_chains, h_hops, max_hops, periodic_ok));
     kmcf_comm *c = p->comm;
     KMCF_TRY(kmcf_enter(c));
     KMCF_TRY(ch_workspace(p, (size_t)n_cells));
@@ -722,13 +874,13 @@ extern "C" int kmcf_site_set_chain(kmcf_pairwise *p, const double *d_x, const do
     return ch_finish(p, n_cells, res, h_chains, h_hops, max_hops, nullptr, stats);
 }
 
-extern "C" int kmcf_filament_chain(kmcf_pairwise *p, int nn, const int *d_neigh_idx, const int *d_site_element,
-                                   const int *d_site_charge, const int *d_metals, int num_metals, const double *d_x,
-                                   const double *d_y, const double *d_z, int N_left_tot, int N_right_tot, double r_max,
-                                   const int *d_site_cell, int n_cells, kmcf_chain_t *h_chains, kmcf_hop_t *h_hops, int max_hops,
-                                   int *d_site_side, int *d_site_node, kmcf_chain_stats_t *stats)
+// the body of kmcf_filament_chain and kmcf_filament_chain_pbc
+int ch_filament_chain(const char *what, bool periodic_ok, kmcf_pairwise *p, int nn, const int *d_neigh_idx,
+                      const int *d_site_element, const int *d_site_charge, const int *d_metals, int num_metals, const double *d_x,
+                      const double *d_y, const double *d_z, int N_left_tot, int N_right_tot, double r_max, const int *d_site_cell,
+                      int n_cells, kmcf_chain_t *h_chains, kmcf_hop_t *h_hops, int max_hops, int *d_site_side, int *d_site_node,
+                      kmcf_chain_stats_t *stats)
 {
-    const char *what = "kmcf_filament_chain";
     KMCF_CHECK(d_neigh_idx, KMCF_ERR_ARG, "%s: d_neigh_idx is NULL", what);
     KMCF_CHECK(d_site_element, KMCF_ERR_ARG, "%s: d_site_element is NULL", what);
     KMCF_CHECK(d_site_charge, KMCF_ERR_ARG, "%s: d_site_charge is NULL", what);
@@ -737,7 +889,7 @@ extern "C" int kmcf_filament_chain(kmcf_pairwise *p, int nn, const int *d_neigh_
     KMCF_CHECK(num_metals == 0 || d_metals, KMCF_ERR_ARG, "%s: d_metals is NULL with num_metals = %d", what, num_metals);
     KMCF_CHECK(N_left_tot >= 0, KMCF_ERR_ARG, "%s: N_left_tot = %d is negative", what, N_left_tot);
     KMCF_CHECK(N_right_tot >= 0, KMCF_ERR_ARG, "%s: N_right_tot = %d is negative", what, N_right_tot);
-    KMCF_TRY(ch_check_common(what, p, d_x, d_y, d_z, r_max, d_site_cell, n_cells, h_chains, h_hops, max_hops));
+    KMCF_TRY(ch_check_common(what, p, d_x, d_y, d_z, r_max, d_site_cell, n_cells, h_chains, h_hops, max_hops, periodic_ok));
     const int N = p->N;
     KMCF_CHECK((int64_t)N_left_tot + N_right_tot <= N, KMCF_ERR_ARG, "%s: N_left_tot + N_right_tot = %lld exceeds N = %d", what,
                (long long)N_left_tot + N_right_tot, N);
@@ -757,4 +909,46 @@ extern "C" int kmcf_filament_chain(kmcf_pairwise *p, int nn, const int *d_neigh_
     ch_result res;
     KMCF_TRY(ch_search(what, p, d_x, d_y, d_z, side, node, r_max, d_site_cell, n_cells, &res));
     return ch_finish(p, n_cells, res, h_chains, h_hops, max_hops, c->ev_t1, stats);
+}
+
+}  // namespace
+
+extern "C" int kmcf_site_set_chain(kmcf_pairwise *p, const double *d_x, const double *d_y, const double *d_z,
+                                   const int *d_site_side, const int *d_site_node, double r_max, const int *d_site_cell,
+                                   int n_cells, kmcf_chain_t *h_chains, kmcf_hop_t *h_hops, int max_hops,
+                                   kmcf_chain_stats_t *stats)
+{
+    return ch_site_set_chain("kmcf_site_set_chain", false, p, d_x, d_y, d_z, d_site_side, d_site_node, r_max, d_site_cell, n_cells,
+                             h_chains, h_hops, max_hops, stats);
+}
+
+extern "C" int kmcf_site_set_chain_pbc(kmcf_pairwise *p, const double *d_x, const double *d_y, const double *d_z,
+                                       const int *d_site_side, const int *d_site_node, double r_max, const int *d_site_cell,
+                                       int n_cells, kmcf_chain_t *h_chains, kmcf_hop_t *h_hops, int max_hops,
+                                       kmcf_chain_stats_t *stats)
+{
+    return ch_site_set_chain("kmcf_site_set_chain_pbc", true, p, d_x, d_y, d_z, d_site_side, d_site_node, r_max, d_site_cell,
+                             n_cells, h_chains, h_hops, max_hops, stats);
+}
+
+extern "C" int kmcf_filament_chain(kmcf_pairwise *p, int nn, const int *d_neigh_idx, const int *d_site_element,
+                                   const int *d_site_charge, const int *d_metals, int num_metals, const double *d_x,
+                                   const double *d_y, const double *d_z, int N_left_tot, int N_right_tot, double r_max,
+                                   const int *d_site_cell, int n_cells, kmcf_chain_t *h_chains, kmcf_hop_t *h_hops, int max_hops,
+                                   int *d_site_side, int *d_site_node, kmcf_chain_stats_t *stats)
+{
+    return ch_filament_chain("kmcf_filament_chain", false, p, nn, d_neigh_idx, d_site_element, d_site_charge, d_metals, num_metals,
+                             d_x, d_y, d_z, N_left_tot, N_right_tot, r_max, d_site_cell, n_cells, h_chains, h_hops, max_hops,
+                             d_site_side, d_site_node, stats);
+}
+
+extern "C" int kmcf_filament_chain_pbc(kmcf_pairwise *p, int nn, const int *d_neigh_idx, const int *d_site_element,
+                                       const int *d_site_charge, const int *d_metals, int num_metals, const double *d_x,
+                                       const double *d_y, const double *d_z, int N_left_tot, int N_right_tot, double r_max,
+                                       const int *d_site_cell, int n_cells, kmcf_chain_t *h_chains, kmcf_hop_t *h_hops,
+                                       int max_hops, int *d_site_side, int *d_site_node, kmcf_chain_stats_t *stats)
+{
+    return ch_filament_chain("kmcf_filament_chain_pbc", true, p, nn, d_neigh_idx, d_site_element, d_site_charge, d_metals,
+                             num_metals, d_x, d_y, d_z, N_left_tot, N_right_tot, r_max, d_site_cell, n_cells, h_chains, h_hops,
+                             max_hops, d_site_side, d_site_node, stats);
 }

@@ -238,6 +238,10 @@ SIGNATURES = {
                                       C.c_int, C.POINTER(ChainStats)]),
     "kmcf_filament_chain": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P,
                                       C.c_int, C.POINTER(Chain), C.POINTER(Hop), C.c_int, _P, _P, C.POINTER(ChainStats)]),
+    "kmcf_site_set_chain_pbc": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_double, _P, C.c_int, C.POINTER(Chain), C.POINTER(Hop),
+                                          C.c_int, C.POINTER(ChainStats)]),
+    "kmcf_filament_chain_pbc": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P,
+                                          C.c_int, C.POINTER(Chain), C.POINTER(Hop), C.c_int, _P, _P, C.POINTER(ChainStats)]),
     "kmcf_neighbor_list":(C.c_int, [_P, _P, _P, _P, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _P]),
     "kmcf_neighbor_list_pbc": (C.c_int, [_P, _P, _P, _P, C.c_int, _DP, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _P]),
 }

@@ -748,31 +748,36 @@ def _chain_out(n_cells, max_hops):
     return chains, hops, (hops.ctypes.data_as(C.POINTER(_L.Hop)) if hops is not None else None)
 
 
-def site_set_chain(gpubuf, site_side, site_node, r_max, site_cell=None, n_cells=1, max_hops=0):
+def site_set_chain(gpubuf, site_side, site_node, r_max, site_cell=None, n_cells=1, max_hops=0, periodic=False):
     """kmcf_site_set_chain on the buffers' spatial index (gpubuf.cutoff_idx, compute_cutoff_list): per gap cell the chain
     of hops from the sites with side bit 0 to the sites with side bit 1 through the floating bodies of site_node whose
     largest hop is as small as any chain's (definitions: include/kmcfield.h).  site_side, site_node: int32 device tensors
-    of N entries (a node outside [0, N): none); site_cell as in site_set_gap.  Returns dict(chains: numpy structured array
-    CHAIN_DTYPE of n_cells records, hops: HOP_DTYPE array (n_cells, max_hops) or None with max_hops == 0, stats: dict)."""
+    of N entries (a node outside [0, N): none); site_cell as in site_set_gap.  periodic=True: kmcf_site_set_chain_pbc, which
+    takes the minimum image in y and z on a periodic index (compute_cutoff_list with pbc = 1) and is the plain call on any
+    other; the default refuses a periodic index.  Returns dict(chains: numpy structured array CHAIN_DTYPE of n_cells
+    records, hops: HOP_DTYPE array (n_cells, max_hops) or None with max_hops == 0, stats: dict)."""
     assert gpubuf.cutoff_idx is not None, "site_set_chain needs the spatial index: compute_cutoff_list first"
     for name, t in (("site_side", site_side), ("site_node", site_node)):
         assert t.dtype == torch.int32 and t.numel() == gpubuf.N_, name + ": N int32 entries"
     cell = _gap_cells(gpubuf, site_cell, n_cells)
     chains, hops, hp = _chain_out(n_cells, max_hops)
     st = _L.ChainStats()
-    _L.check(_L.load().kmcf_site_set_chain(gpubuf.cutoff_idx, _ptr(gpubuf.site_x), _ptr(gpubuf.site_y), _ptr(gpubuf.site_z),
-                                           _ptr(site_side), _ptr(site_node), float(r_max), _ptr(cell), int(n_cells),
-                                           chains.ctypes.data_as(C.POINTER(_L.Chain)), hp, int(max_hops), C.byref(st)),
-             "kmcf_site_set_chain")
+    name = "kmcf_site_set_chain_pbc" if periodic else "kmcf_site_set_chain"
+    _L.check(getattr(_L.load(), name)(gpubuf.cutoff_idx, _ptr(gpubuf.site_x), _ptr(gpubuf.site_y), _ptr(gpubuf.site_z),
+                                      _ptr(site_side), _ptr(site_node), float(r_max), _ptr(cell), int(n_cells),
+                                      chains.ctypes.data_as(C.POINTER(_L.Chain)), hp, int(max_hops), C.byref(st)), name)
     return dict(chains=chains, hops=hops, stats=st.as_dict())
 
 
 def filament_chain(kmc_comm, gpubuf, N_left_tot, N_right_tot, r_max, site_cell=None, n_cells=1, max_hops=0, sides=True,
-                   nodes=True):
+                   nodes=True, periodic=False):
     """kmcf_filament_chain: the stepping-stone chain between the matter attached to the left electrode and the matter
     attached to the right one through the floating conductive clusters, per gap cell (definitions: include/kmcfield.h).
-    Call it after update_charge_gpu and compute_cutoff_list, on the communicator the index was built with.  Returns
-    dict(chains, hops (or None), side / node: int32 device tensors of N entries or None, stats: dict)."""
+    Call it after update_charge_gpu and compute_cutoff_list, on the communicator the index was built with.
+    periodic=True: kmcf_filament_chain_pbc -- the minimum image in y and z on a periodic index (compute_cutoff_list with
+    pbc = 1; build the list with compute_neighbor_list(pbc=1) as well, so that a body that passes a face is one node), the
+    plain call on any other; the default refuses a periodic index.  Returns dict(chains, hops (or None), side / node:
+    int32 device tensors of N entries or None, stats: dict)."""
     N = gpubuf.N_
     assert gpubuf.cutoff_idx is not None, "filament_chain needs the spatial index: compute_cutoff_list first"
     assert gpubuf.neigh_idx is not None and gpubuf.neigh_idx.numel() == N * gpubuf.nn_, \
@@ -782,12 +787,13 @@ def filament_chain(kmc_comm, gpubuf, N_left_tot, N_right_tot, r_max, site_cell=N
     side = torch.empty(N, dtype=torch.int32, device=gpubuf.device) if sides else None
     node = torch.empty(N, dtype=torch.int32, device=gpubuf.device) if nodes else None
     st = _L.ChainStats()
-    _L.check(_L.load().kmcf_filament_chain(gpubuf.cutoff_idx, gpubuf.nn_, _ptr(gpubuf.neigh_idx), _ptr(gpubuf.site_element),
-                                           _ptr(gpubuf.site_charge), _ptr(gpubuf.metal_types), gpubuf.num_metal_types_,
-                                           _ptr(gpubuf.site_x), _ptr(gpubuf.site_y), _ptr(gpubuf.site_z), int(N_left_tot),
-                                           int(N_right_tot), float(r_max), _ptr(cell), int(n_cells),
-                                           chains.ctypes.data_as(C.POINTER(_L.Chain)), hp, int(max_hops), _ptr(side),
-                                           _ptr(node), C.byref(st)), "kmcf_filament_chain")
+    name = "kmcf_filament_chain_pbc" if periodic else "kmcf_filament_chain"
+    _L.check(getattr(_L.load(), name)(gpubuf.cutoff_idx, gpubuf.nn_, _ptr(gpubuf.neigh_idx), _ptr(gpubuf.site_element),
+                                      _ptr(gpubuf.site_charge), _ptr(gpubuf.metal_types), gpubuf.num_metal_types_,
+                                      _ptr(gpubuf.site_x), _ptr(gpubuf.site_y), _ptr(gpubuf.site_z), int(N_left_tot),
+                                      int(N_right_tot), float(r_max), _ptr(cell), int(n_cells),
+                                      chains.ctypes.data_as(C.POINTER(_L.Chain)), hp, int(max_hops), _ptr(side), _ptr(node),
+                                      C.byref(st)), name)
     return dict(chains=chains, hops=hops, side=side, node=node, stats=st.as_dict())
 
 

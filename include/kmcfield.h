@@ -732,7 +732,8 @@ typedef struct {
  * KMCF_ERR_ARG (before anything needs a device; kmcf_last_error names the argument): NULL coordinates, d_site_side,
  * d_site_node, h_chains or p; r_max not finite, <= 0, or larger than the index's cutoff radius; n_cells < 1, or NULL
  * d_site_cell with n_cells != 1; max_hops < 0, h_hops set with max_hops == 0 or NULL with max_hops > 0; a periodic index
- * (the periodic form is a later change).  KMCF_ERR_STATE: the search did not stop within 40 rounds. */
+ * (kmcf_site_set_chain_pbc / kmcf_filament_chain_pbc below take it; the message names that call).  KMCF_ERR_STATE: the
+ * search did not stop within 40 rounds. */
 int kmcf_site_set_chain(kmcf_pairwise *p, const double *d_x, const double *d_y, const double *d_z,
                         const int *d_site_side /* N */, const int *d_site_node /* N */, double r_max,
                         const int *d_site_cell /* N, or NULL */, int n_cells,
@@ -751,6 +752,46 @@ int kmcf_filament_chain(kmcf_pairwise *p, int nn, const int *d_neigh_idx, const 
                         kmcf_hop_t *h_hops /* n_cells*max_hops, or NULL */, int max_hops,
                         int *d_site_side /* N out, or NULL */, int *d_site_node /* N out, or NULL */,
                         kmcf_chain_stats_t *stats);
+
+/* The same two analyses under periodic y-z boundaries.  Parameter lists, outputs, argument checks and their order are
+ * those of kmcf_site_set_chain / kmcf_filament_chain (kmcf_last_error names the _pbc call); the one difference: a
+ * periodic index is accepted.
+ * On a non-periodic index (kmcf_compute_cutoff_list, or kmcf_compute_cutoff_list_pbc with pbc == 0) they launch the
+ * kernels of the plain calls and return their bytes.
+ * On a periodic index (kmcf_compute_cutoff_list_pbc with pbc == 1) the pair distance is the library's one minimum image,
+ * as in kmcf_site_set_gap_pbc, Ly and Lz being the periods the index was built with:
+ *     dx = x[a] - x[b]
+ *     fy = (y[a] - y[b]) / Ly;  fy -= round(fy);  dy = fy * Ly        (z likewise; round = C round, half away from zero)
+ *     d2 = (dx*dx + dy*dy) + dz*dz
+ * every operation rounded to double: no fused multiply-add, the division an IEEE division.  x is never periodic.
+ * Symmetry.  d2(a, b) and d2(b, a) are the same bits: division, round, subtraction and product are odd in the difference,
+ * and the squares remove the sign.  The two ends of a link therefore see one key, which the search relies on.
+ * One distance per pair.  Where a period is shorter than 2 r_max, a second image within r_max adds no pair, no link and
+ * no surface mark of its own: surface_sites counts sites.
+ * A vertex near its own image links to nothing: pairs inside one vertex are never links, through a face or not.
+ * Everything else is the contract above, unchanged: terminals, stones, homes, vertex cells; a pair counts iff
+ * d2 <= r_max*r_max; the link key (d2, min(a,b), max(a,b)); the chain as the L - R path of the minimum spanning forest;
+ * statuses, records, the orientation of the hops, length as the host's sum of sqrt(d2) in chain order; the stats; r_max is
+ * at most the index's cutoff radius; two calls on the same input return the same bytes.
+ * direct2 is bit-equal to gap2 of kmcf_site_set_gap_pbc on the same sides and index.
+ * kmcf_filament_chain_pbc derives sides and nodes from the list it is given: pass the list of kmcf_neighbor_list_pbc
+ * (pbc == 1, the same periods) so that a floating body that passes through a face is ONE node, and a stump of the filament
+ * beyond a face belongs to its electrode.  This is not checked (as with kmcf_filament_gap_pbc): an open list under a
+ * periodic distance gives open clusters -- bodies cut in two at the faces -- measured across the wrap.
+ * Cost on the periodic 5 nm cell: DESIGN 3.12, "Periodic search". */
+int kmcf_site_set_chain_pbc(kmcf_pairwise *p, const double *d_x, const double *d_y, const double *d_z,
+                            const int *d_site_side /* N */, const int *d_site_node /* N */, double r_max,
+                            const int *d_site_cell /* N, or NULL */, int n_cells,
+                            kmcf_chain_t *h_chains /* n_cells */, kmcf_hop_t *h_hops /* n_cells*max_hops, or NULL */,
+                            int max_hops, kmcf_chain_stats_t *stats /* or NULL */);
+int kmcf_filament_chain_pbc(kmcf_pairwise *p, int nn, const int *d_neigh_idx, const int *d_site_element,
+                            const int *d_site_charge, const int *d_metals, int num_metals,
+                            const double *d_x, const double *d_y, const double *d_z,
+                            int N_left_tot, int N_right_tot, double r_max,
+                            const int *d_site_cell, int n_cells, kmcf_chain_t *h_chains,
+                            kmcf_hop_t *h_hops /* n_cells*max_hops, or NULL */, int max_hops,
+                            int *d_site_side /* N out, or NULL */, int *d_site_node /* N out, or NULL */,
+                            kmcf_chain_stats_t *stats);
 
 /* ---------------------------------------------------------------------- */
 /* T path: current solve (Kirchhoff matrix with two virtual nodes + WKB       */

@@ -29,9 +29,10 @@ to R angstrom (at most 20, the cell edge of the spatial index), per cell of stru
 workloads.  The step line gains `gap <ms clusters>+<ms search> [<cell>: <gap> A (<site_left>-<site_right>) L <n_left> R
 <n_right> | <cell>: bridged (<n_both> sites) L .. R .. | <cell>: none L .. R ..]`; with --clusters a bridged cell also shows
 `constriction <sites>`: the smallest number of filament vacancies in a slice of 3.2 angstrom along x.  --chain R runs the
-tunnelling-chain analysis (kmcf_filament_chain) next to it: per cell the chain of hops from the left side to the right
+tunnelling-chain analysis (kmcf_filament_chain; on `5nm-periodic` kmcf_filament_chain_pbc: periodic clusters, minimum-image
+hops) next to it: per cell the chain of hops from the left side to the right
 side through the floating conductive clusters whose longest hop is as short as any chain's, hops of at most R angstrom
-(at most 20; not on `5nm-periodic`: the search is non-periodic).  The step line gains `chain <ms clusters>+<ms search>
+(at most 20).  The step line gains `chain <ms clusters>+<ms search>
 (<rounds> rounds, <surface sites> surface) [<cell>: <hops> hops, longest <hop_max> A (<from>-<to>), length <length> A,
 direct <sqrt(direct2)> A, <stones> stones | <cell>: bridged | <cell>: open, .. stones | <cell>: none]`; --chain-hops K also
 lists the first K hops of every chain as `<from>-<to> <hop> A`.
@@ -83,8 +84,6 @@ def main():
         ap.error("--gap %g: the search radius is > 0 and at most 20 (the cell edge of the spatial index)" % a.gap)
     if a.chain is not None and not 0.0 < a.chain <= 20.0:
         ap.error("--chain %g: the hop length is > 0 and at most 20 (the cell edge of the spatial index)" % a.chain)
-    if a.chain is not None and a.workload == "5nm-periodic":
-        ap.error("--chain: the chain search is non-periodic and refuses the periodic index of 5nm-periodic")
     if a.chain_hops < 0 or (a.chain_hops and a.chain is None):
         ap.error("--chain-hops K: K >= 0, with --chain")
     if a.rate_mode != "bg" and not a.current:
@@ -181,7 +180,7 @@ def main():
             clusters += " | gap %.3f+%.3f [%s]" % (gp["stats"]["ms_clusters"], gp["stats"]["ms_search"], " | ".join(cells))
         if a.chain is not None:
             ch = S.filament_chain(comm, buf, NL, NL, a.chain, site_cell=gap_cells, n_cells=n_gap_cells, max_hops=a.chain_hops,
-                                  sides=False, nodes=False)
+                                  sides=False, nodes=False, periodic=periodic)
             cells = []
             for c, r in enumerate(ch["chains"]):
                 if r["status"] == S.CHAIN_BRIDGED:
