@@ -45,6 +45,8 @@ struct kmcf_tstate {
     kmcf_matrix *T = nullptr;
     int N = 0, N_atom = 0, Nsub = 0, n_inj = 0, n_ext = 0, n_layers = 0;
     double nn_dist = 0.0;
+    int pbc = 0;                                   // 1: every distance of the state is the minimum image in y and z
+    double lattice[3] = {0.0, 0.0, 0.0};           // the caller's h_lattice (kmcf_initialize_sparsity_T_pbc, pbc == 1), else zeros
     std::vector<int> h_atom_site;
     std::vector<int> h_row_ptr, h_col;             // pattern of this rank, global columns, caller row order
     std::vector<int> h_inv_perm;                   // caller local row -> internal row
@@ -102,6 +104,25 @@ __device__ __forceinline__ double dist3(double x1, double y1, double z1, double 
     const double dx = x2 - x1, dy = y2 - y1, dz = z2 - z1;
     return sqrt(dx * dx + dy * dy + dz * dz);
 }
+
+// The distance of a pair of tunnel points, chosen at compile time: a kernel that measures a pair is instantiated once per
+// geometry and takes the functor by value.  dist_open is empty and calls dist3: the open instantiation is the code it was.
+// dist_min_image carries the periods of kmcf_initialize_sparsity_T_pbc and calls the library's one minimum image
+// (kmcf_internal.hpp); that expression is odd in every difference up to the squares, so d(i, j) and d(j, i) are the same
+// bits -- which the mirrored tiles and the bitmap, where each row measures the pair itself, rely on to agree.
+struct dist_open {
+    __device__ __forceinline__ double operator()(double x1, double y1, double z1, double x2, double y2, double z2) const
+    {
+        return dist3(x1, y1, z1, x2, y2, z2);
+    }
+};
+struct dist_min_image {
+    double ly, lz;
+    __device__ __forceinline__ double operator()(double x1, double y1, double z1, double x2, double y2, double z2) const
+    {
+        return kmcf_min_image_dist(x1, y1, z1, x2, y2, z2, ly, lz);
+    }
+};
 
 // ---------------------------------------------------------------- atoms
 __global__ __launch_bounds__(KMCF_BLOCK) void gather_coords_kernel(int n, const int *__restrict__ site, const double *__restrict__ sx,
@@ -273,10 +294,11 @@ __device__ __forceinline__ bool tunnel_pair(int info_i, int info_j, double cb_i,
 
 // One wave per local sub row: masks of its row (one ballot per 64 columns) and its entry count
 // (calc_nnz_per_row_tunnel + assemble_tunnel_col_indices, :212-372).
+template <typename DIST>
 __global__ __launch_bounds__(KMCF_BLOCK) void tunnel_mask_kernel(
     int n_loc, int s0, int n_glob, int n_groups, const int *__restrict__ tinfo, const double *__restrict__ tx,
     const double *__restrict__ ty, const double *__restrict__ tz, const double *__restrict__ tcb, double nn_dist, double tol,
-    unsigned long long *__restrict__ mask, int *__restrict__ rowcnt)
+    unsigned long long *__restrict__ mask, int *__restrict__ rowcnt, DIST dist)
 {
     const int lane = threadIdx.x & 63;
     const int wpb = KMCF_BLOCK / 64;
@@ -292,7 +314,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void tunnel_mask_kernel(
                 if (j == sg) take = true;                                           // :255-258 diagonal
                 else {
                     bool c2t;
-                    const double d = dist3(xi, yi, zi, tx[j], ty[j], tz[j]);
+                    const double d = dist(xi, yi, zi, tx[j], ty[j], tz[j]);
                     take = d > nn_dist && tunnel_pair(fi, tinfo[j], cbi, tcb[j], tol, &c2t);   // :261-284
                 }
             }
@@ -332,11 +354,12 @@ __device__ __forceinline__ double wkb_value(double dist_angstrom, double cb_i, d
 
 // One wave per local sub row: values of the set positions + the row's diagonal = -(sum of the others)
 // (populate_T_tunnel_dist2 + calc_diagonal_T_tunnel, :497-614, :669-689).
+template <typename DIST>
 __global__ __launch_bounds__(KMCF_BLOCK) void tunnel_value_kernel(
     int n_loc, int s0, int n_groups, const int *__restrict__ tinfo, const double *__restrict__ tx, const double *__restrict__ ty,
     const double *__restrict__ tz, const double *__restrict__ tcb, double nn_dist, double tol, double m_e, double V0,
     const unsigned long long *__restrict__ mask, const long long *__restrict__ voff, double *__restrict__ val,
-    double *__restrict__ tdiag)
+    double *__restrict__ tdiag, DIST dist)
 {
     const int lane = threadIdx.x & 63;
     const int wpb = KMCF_BLOCK / 64;
@@ -358,7 +381,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void tunnel_value_kernel(
                 else {
                     bool c2t;
                     tunnel_pair(fi, tinfo[j], cbi, tcb[j], tol, &c2t);
-                    const double v = wkb_value(dist3(xi, yi, zi, tx[j], ty[j], tz[j]), cbi, tcb[j], c2t, m_e, V0);
+                    const double v = wkb_value(dist(xi, yi, zi, tx[j], ty[j], tz[j]), cbi, tcb[j], c2t, m_e, V0);
                     val[pos] = v;
                     rowsum += v;
                 }
@@ -368,6 +391,38 @@ __global__ __launch_bounds__(KMCF_BLOCK) void tunnel_value_kernel(
         rowsum = kmcf_wave_sum64(rowsum);
         if (dpos >= 0) val[dpos] = -rowsum;                                // :685
         if (lane == 0) tdiag[s] = -rowsum;                                 // :680
+    }
+}
+
+// The row sums alone, by tunnel_value_kernel's walk and in its order of addition (lane = column of a mask word, one wave
+// sum per row), nothing stored but rowsum[s0 + s]: the tunnel diagonal of a PERIODIC state held as tiles.  A row's sum
+// then depends on the row alone -- not on the storage form, nor on how a group deals the tiles -- so every form and
+// every group size give the diagonal and the preconditioner of the one-rank bitmap, bit for bit.
+template <typename DIST>
+__global__ __launch_bounds__(KMCF_BLOCK) void tunnel_rowsum_kernel(
+    int n_loc, int s0, int n_groups, const int *__restrict__ tinfo, const double *__restrict__ tx, const double *__restrict__ ty,
+    const double *__restrict__ tz, const double *__restrict__ tcb, double tol, double m_e, double V0,
+    const unsigned long long *__restrict__ mask, double *__restrict__ rowsum_out, DIST dist)
+{
+    const int lane = threadIdx.x & 63;
+    const int wpb = KMCF_BLOCK / 64;
+    for (int s = blockIdx.x * wpb + (threadIdx.x >> 6); s < n_loc; s += gridDim.x * wpb) {
+        const int sg = s0 + s;
+        const double xi = tx[sg], yi = ty[sg], zi = tz[sg], cbi = tcb[sg];
+        const int fi = tinfo[sg];
+        double rowsum = 0.0;
+        for (int g = 0; g < n_groups; ++g) {
+            const unsigned long long mk = mask[(size_t)s * n_groups + g];
+            if (mk == 0ull) continue;                                      // wave-uniform
+            const int j = g * 64 + lane;
+            if (((mk >> lane) & 1ull) && j != sg) {
+                bool c2t;
+                tunnel_pair(fi, tinfo[j], cbi, tcb[j], tol, &c2t);
+                rowsum += wkb_value(dist(xi, yi, zi, tx[j], ty[j], tz[j]), cbi, tcb[j], c2t, m_e, V0);
+            }
+        }
+        rowsum = kmcf_wave_sum64(rowsum);
+        if (lane == 0) rowsum_out[sg] = rowsum;
     }
 }
 
@@ -614,10 +669,11 @@ constexpr int SYM_WAVE_DOUBLES = 64 * SYM_LD + 256;          // tile + four 64-v
 
 // Values of the upper tiles (populate_T_tunnel_dist2 on the pairs of the tile; 0 where the pattern has no entry, on
 // the diagonal -- set afterwards -- and past the last point).  A wave per strip, lane = column, rows one by one.
+template <typename DIST>
 __global__ __launch_bounds__(KMCF_BLOCK) void tunnel_dense_fill_kernel(
     int n_strips, const int4 *__restrict__ strips, int n_glob, const int *__restrict__ tinfo, const double *__restrict__ tx,
     const double *__restrict__ ty, const double *__restrict__ tz, const double *__restrict__ tcb, double nn_dist, double tol,
-    double m_e, double V0, double *__restrict__ tiles)
+    double m_e, double V0, double *__restrict__ tiles, DIST dist)
 {
     const int lane = threadIdx.x & 63;
     for (int s = blockIdx.x * 4 + (threadIdx.x >> 6); s < n_strips; s += gridDim.x * 4) {
@@ -634,7 +690,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void tunnel_dense_fill_kernel(
                 if (i < n_glob && jin && i != j) {
                     bool c2t;
                     const double cbi = tcb[i];
-                    const double d = dist3(tx[i], ty[i], tz[i], xj, yj, zj);
+                    const double d = dist(tx[i], ty[i], tz[i], xj, yj, zj);
                     if (d > nn_dist && tunnel_pair(tinfo[i], fj, cbi, cbj, tol, &c2t)) v = wkb_value(d, cbi, cbj, c2t, m_e, V0);
                 }
                 tile[r * 64 + lane] = v;
@@ -783,10 +839,11 @@ __global__ __launch_bounds__(KMCF_BLOCK) void symj_mask_kernel(int n_strips, con
 }
 
 // values in layer order (populate_T_tunnel_dist2 on the tile's entries; the diagonal entry 0 until symj_set_diag_kernel)
+template <typename DIST>
 __global__ __launch_bounds__(KMCF_BLOCK) void symj_fill_kernel(
     int n_strips, const int4 *__restrict__ strips, int n_glob, const int *__restrict__ tinfo, const double *__restrict__ tx,
     const double *__restrict__ ty, const double *__restrict__ tz, const double *__restrict__ tcb, double tol, double m_e, double V0,
-    const symj_u64 *__restrict__ jmask, const long long *__restrict__ jvoff, double *__restrict__ jval)
+    const symj_u64 *__restrict__ jmask, const long long *__restrict__ jvoff, double *__restrict__ jval, DIST dist)
 {
     const int lane = threadIdx.x & 63;
     const symj_u64 lt = lane ? (~0ull >> (64 - lane)) : 0ull;
@@ -811,7 +868,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void symj_fill_kernel(
                         bool c2t;
                         const double cbj = tcb[j];
                         tunnel_pair(fi, tinfo[j], cbi, cbj, tol, &c2t);
-                        v = wkb_value(dist3(xi, yi, zi, tx[j], ty[j], tz[j]), cbi, cbj, c2t, m_e, V0);
+                        v = wkb_value(dist(xi, yi, zi, tx[j], ty[j], tz[j]), cbi, cbj, c2t, m_e, V0);
                     }
                     jval[base + __popcll(b & lt)] = v;
                 }
@@ -1165,10 +1222,11 @@ __global__ __launch_bounds__(KMCF_BLOCK) void current_neighbour_kernel(int n_loc
 // Tunnel part: a wave per local row of the pair bitmap (tunnel_value_kernel's walk), lane = column of a mask word; the
 // conductance of every set pair is evaluated afresh (one symmetric expression per pair: the same value whatever
 // storage the solve uses), the row's sums go into the slots of its node (after the neighbour part, same stream).
+template <typename DIST>
 __global__ __launch_bounds__(KMCF_BLOCK) void current_tunnel_kernel(
     int n_loc, int s0, int n_groups, const int *__restrict__ tinfo, const double *__restrict__ tx, const double *__restrict__ ty,
     const double *__restrict__ tz, const double *__restrict__ tcb, double tol, double m_e, double V0,
-    const unsigned long long *__restrict__ mask, const int *__restrict__ tidx, const double *__restrict__ m, double *__restrict__ cm)
+    const unsigned long long *__restrict__ mask, const int *__restrict__ tidx, const double *__restrict__ m, double *__restrict__ cm, DIST dist)
 {
     const int lane = threadIdx.x & 63;
     const int wpb = KMCF_BLOCK / 64;
@@ -1187,7 +1245,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void current_tunnel_kernel(
                 if (j != sg) {
                     bool c2t;
                     tunnel_pair(fi, tinfo[j], cbi, tcb[j], tol, &c2t);
-                    const double gc = -wkb_value(dist3(xi, yi, zi, tx[j], ty[j], tz[j]), cbi, tcb[j], c2t, m_e, V0);
+                    const double gc = -wkb_value(dist(xi, yi, zi, tx[j], ty[j], tz[j]), cbi, tcb[j], c2t, m_e, V0);
                     const double i_rc = gc * (mr - m[tidx[j] + 2]);
                     a += fabs(i_rc);
                     b += i_rc;
@@ -1261,6 +1319,15 @@ int wave_row_grid(int ns)
 
 // blocks of a kernel that gives a wave to each strip of tiles
 int strip_grid(int n_strips) { return std::max(1, std::min((n_strips + 3) / 4, 8192)); }
+
+// f(the state's distance functor): where the geometry of a state picks the instantiation of a kernel that BOTH geometries
+// run.  (One kernel only a periodic state runs, tunnel_rowsum_kernel<dist_min_image>, is launched by symm_diagonal itself.)
+template <typename F>
+void with_dist(const kmcf_tstate *t, F f)
+{
+    if (t->pbc) f(dist_min_image{t->lattice[1], t->lattice[2]});
+    else f(dist_open{});
+}
 
 }  // namespace
 
@@ -1366,10 +1433,13 @@ static int init_gather_coords(kmcf_tstate *t, const double *d_site_x, const doub
 // src/initialize_sparsity_T.cu:62-72, 166-177; the diagonal comes with it: dist 0 < nn_dist)
 static int init_atom_pattern(kmcf_tstate *t, int a0, int a1, std::vector<int> *arp, std::vector<int> *acol)
 {
+    // Open: no lattice (the periods are never read).  Periodic: the wrapped grid where at least 3 cells of nn_dist fit
+    // each period and the atoms do not span one, else every pair is tested (host_cells::usable, kmcf_cells.hpp).
     host_cells hc;
-    const double lattice[3] = {1, 1, 1};
-    KMCF_TRY(build_cells(t->d_ax, t->d_ay, t->d_az, t->N_atom, lattice, 0, t->nn_dist, &hc));
-    const int rc = build_pattern(hc, t->d_ax, t->d_ay, t->d_az, lattice, 0, t->nn_dist, a0, a1 - a0, 0, t->N_atom - 1, arp, acol, t->comm->stream);
+    const double open_lattice[3] = {1, 1, 1};
+    const double *lattice = t->pbc ? t->lattice : open_lattice;
+    KMCF_TRY(build_cells(t->d_ax, t->d_ay, t->d_az, t->N_atom, lattice, t->pbc, t->nn_dist, &hc));
+    const int rc = build_pattern(hc, t->d_ax, t->d_ay, t->d_az, lattice, t->pbc, t->nn_dist, a0, a1 - a0, 0, t->N_atom - 1, arp, acol, t->comm->stream);
     hc.release();
     return rc;
 }
@@ -1445,7 +1515,12 @@ static int init_row_tables(kmcf_tstate *t, const t_host_coords &xyz)
             if (col[j] == node) { diag_pos[i] = m->h_row_ptr[i] + (j - rp[r]); break; }
         if (node >= 2) {
             const int a = node - 2, g = Na - 1;
-            const double dx = xyz.x[g] - xyz.x[a], dy = xyz.y[g] - xyz.y[a], dz = xyz.z[g] - xyz.z[a];
+            double dx = xyz.x[g] - xyz.x[a], dy = xyz.y[g] - xyz.y[a], dz = xyz.z[g] - xyz.z[a];
+            if (t->pbc) {      // kmcf_min_image_dist restated on the host, operation for operation (the squares remove dx's sign)
+                double fy = (xyz.y[g] - xyz.y[a]) / t->lattice[1], fz = (xyz.z[g] - xyz.z[a]) / t->lattice[2];
+                fy -= std::round(fy); fz -= std::round(fz);
+                dy = fy * t->lattice[1]; dz = fz * t->lattice[2];
+            }
             ground[i] = std::sqrt(dx * dx + dy * dy + dz * dz) < t->nn_dist ? 1 : 0;      // current_solver_gpu.cu:1115-1117
         }
     }
@@ -1496,10 +1571,11 @@ static int init_workspace(kmcf_tstate *t, const int *h_counts_T, const int *h_di
     return KMCF_OK;
 }
 
-extern "C" int kmcf_initialize_sparsity_T(kmcf_comm *c, const double *d_site_x, const double *d_site_y, const double *d_site_z,
-                                          const int *d_site_element, int N, double nn_dist, int num_source_inj,
-                                          int num_ground_ext, int num_layers_contact, const int *h_counts_T,
-                                          const int *h_displs_T, kmcf_tstate **out)
+// both entry points: h_lattice is read with pbc == 1 only (checked by the caller)
+static int initialize_sparsity_T(kmcf_comm *c, const double *d_site_x, const double *d_site_y, const double *d_site_z,
+                                 const int *d_site_element, int N, const double *h_lattice, int pbc, double nn_dist, int num_source_inj,
+                                 int num_ground_ext, int num_layers_contact, const int *h_counts_T,
+                                 const int *h_displs_T, kmcf_tstate **out)
 {
     KMCF_TRY(init_check_args(c, d_site_x, d_site_y, d_site_z, d_site_element, N, nn_dist, num_source_inj, num_ground_ext,
                              num_layers_contact, h_counts_T, h_displs_T, out));
@@ -1509,6 +1585,8 @@ extern "C" int kmcf_initialize_sparsity_T(kmcf_comm *c, const double *d_site_x, 
     struct guard_t { kmcf_tstate *t; ~guard_t() { if (t) kmcf_tstate_destroy(t); } } guard{t};      // (a half-built state)
     t->comm = c; t->N = N; t->n_inj = num_source_inj; t->n_ext = num_ground_ext; t->n_layers = num_layers_contact;
     t->nn_dist = nn_dist;
+    t->pbc = pbc;
+    if (pbc) memcpy(t->lattice, h_lattice, sizeof(t->lattice));
     KMCF_TRY(init_atom_set(t, d_site_element, h_counts_T));
     t_host_coords xyz;
     KMCF_TRY(init_gather_coords(t, d_site_x, d_site_y, d_site_z, &xyz));
@@ -1524,6 +1602,42 @@ extern "C" int kmcf_initialize_sparsity_T(kmcf_comm *c, const double *d_site_x, 
     KMCF_TRY(init_workspace(t, h_counts_T, h_displs_T));
     guard.t = nullptr;
     *out = t;
+    return KMCF_OK;
+}
+
+extern "C" int kmcf_initialize_sparsity_T(kmcf_comm *c, const double *d_site_x, const double *d_site_y, const double *d_site_z,
+                                          const int *d_site_element, int N, double nn_dist, int num_source_inj,
+                                          int num_ground_ext, int num_layers_contact, const int *h_counts_T,
+                                          const int *h_displs_T, kmcf_tstate **out)
+{
+    return initialize_sparsity_T(c, d_site_x, d_site_y, d_site_z, d_site_element, N, nullptr, 0, nn_dist, num_source_inj, num_ground_ext,
+                                 num_layers_contact, h_counts_T, h_displs_T, out);
+}
+
+extern "C" int kmcf_initialize_sparsity_T_pbc(kmcf_comm *c, const double *d_site_x, const double *d_site_y, const double *d_site_z,
+                                              const int *d_site_element, int N, const double *h_lattice, int pbc, double nn_dist,
+                                              int num_source_inj, int num_ground_ext, int num_layers_contact, const int *h_counts_T,
+                                              const int *h_displs_T, kmcf_tstate **out)
+{
+    const char *what = "kmcf_initialize_sparsity_T_pbc";
+    KMCF_CHECK(pbc == 0 || pbc == 1, KMCF_ERR_ARG, "%s: pbc = %d is neither 0 nor 1", what, pbc);
+    if (pbc) {
+        KMCF_CHECK(h_lattice, KMCF_ERR_ARG, "%s: h_lattice is NULL with pbc = 1", what);
+        KMCF_CHECK(std::isfinite(h_lattice[1]) && h_lattice[1] > 0, KMCF_ERR_ARG, "%s: the period in y, h_lattice[1] = %g, is not finite and > 0",
+                   what, h_lattice[1]);
+        KMCF_CHECK(std::isfinite(h_lattice[2]) && h_lattice[2] > 0, KMCF_ERR_ARG, "%s: the period in z, h_lattice[2] = %g, is not finite and > 0",
+                   what, h_lattice[2]);
+    }
+    return initialize_sparsity_T(c, d_site_x, d_site_y, d_site_z, d_site_element, N, h_lattice, pbc, nn_dist, num_source_inj, num_ground_ext,
+                                 num_layers_contact, h_counts_T, h_displs_T, out);
+}
+
+extern "C" int kmcf_tstate_periodic(const kmcf_tstate *t, int *pbc, double *h_lattice)
+{
+    KMCF_CHECK(t, KMCF_ERR_ARG, "kmcf_tstate_periodic: t is NULL");
+    KMCF_CHECK(pbc, KMCF_ERR_ARG, "kmcf_tstate_periodic: pbc is NULL");
+    *pbc = t->pbc;
+    if (h_lattice) memcpy(h_lattice, t->lattice, sizeof(t->lattice));
     return KMCF_OK;
 }
 
@@ -1683,8 +1797,10 @@ static int symm_fill_jagged(kmcf_tstate *t)
     KMCF_HIP(hipStreamSynchronize(st));
     sb.jnnz = t->h_pin->jnnz;
     KMCF_TRY(ensure(&sb.d_jval, &sb.cap_jval, (size_t)sb.jnnz + 64));
-    symj_fill_kernel<<<grid, KMCF_BLOCK, 0, st>>>(sb.n_strips, sb.d_strips, sb.n_glob, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz, t->d_tcb, p->tol, p->m_e,
-                                                 p->V0, sb.d_jmask, sb.d_jvoff, sb.d_jval);
+    with_dist(t, [&](auto dist) {
+        symj_fill_kernel<decltype(dist)><<<grid, KMCF_BLOCK, 0, st>>>(sb.n_strips, sb.d_strips, sb.n_glob, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz, t->d_tcb,
+                                                                      p->tol, p->m_e, p->V0, sb.d_jmask, sb.d_jvoff, sb.d_jval, dist);
+    });
     KMCF_HIP(hipGetLastError());
     return KMCF_OK;
 }
@@ -1693,22 +1809,40 @@ static int symm_fill_dense(kmcf_tstate *t)
 {
     kmcf_subop &sb = t->sub;
     const kmcf_current_params_t *p = &t->par;
-    tunnel_dense_fill_kernel<<<strip_grid(sb.n_strips), KMCF_BLOCK, 0, t->comm->stream>>>(sb.n_strips, sb.d_strips, sb.n_glob, t->d_tinfo, t->d_tx, t->d_ty,
-                                                                                          t->d_tz, t->d_tcb, t->nn_dist, p->tol, p->m_e, p->V0, sb.d_tiles);
+    with_dist(t, [&](auto dist) {
+        tunnel_dense_fill_kernel<decltype(dist)><<<strip_grid(sb.n_strips), KMCF_BLOCK, 0, t->comm->stream>>>(
+            sb.n_strips, sb.d_strips, sb.n_glob, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz, t->d_tcb, t->nn_dist, p->tol, p->m_e, p->V0, sb.d_tiles, dist);
+    });
     KMCF_HIP(hipGetLastError());
     return KMCF_OK;
 }
 
-// diagonal = -(row sums): one application to the vector of ones (the diagonal entries are still 0); spread: of ALL
-// points on every rank (a rank sets the diagonal of the diagonal tiles it holds)
+// diagonal = -(row sums) of the tile forms, of ALL points on every rank when the tiles are spread (a rank sets the diagonal
+// of the diagonal tiles it holds).  TWO algorithms, by the state's geometry:
+//   open state:     one application of the tiles to the vector of ones (the diagonal entries are still 0); a group adds the
+//                   ranks' partial sums in rank order, so the last bit of a sum depends on the deal.  The bytes
+//                   of this library's open path before periodic states existed: kept.
+//   periodic state: tunnel_rowsum_kernel over this rank's rows of the pair bitmap, a group all-gathering the rows' sums:
+//                   a second evaluation of every pair's WKB value (5 nm: 34 us), for a diagonal that is the one-rank
+//                   bitmap's in every form and under every deal.
 static int symm_diagonal(kmcf_tstate *t)
 {
     kmcf_subop &sb = t->sub;
     hipStream_t st = t->comm->stream;
     const int n_t = sb.n_glob, nb = sb.nb;
-    fill_kernel<<<kmcf_grid1d(64 * nb), KMCF_BLOCK, 0, st>>>(64 * nb, sb.d_xsub, 1.0);
-    KMCF_HIP(hipMemsetAsync(t->d_tdiag, 0, (size_t)n_t * sizeof(double), st));
-    KMCF_TRY((symm_apply<0, false>(t->comm, sb, n_t, 0, nullptr, nullptr, t->d_tdiag, nullptr, nullptr, nullptr, 0)));
+    if (t->pbc) {
+        const kmcf_current_params_t *p = &t->par;
+        if (sb.n_loc > 0)
+            tunnel_rowsum_kernel<dist_min_image><<<wave_row_grid(sb.n_loc), KMCF_BLOCK, 0, st>>>(
+                sb.n_loc, sb.row0, sb.n_groups, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz, t->d_tcb, p->tol, p->m_e, p->V0, sb.d_mask, t->d_tdiag,
+                dist_min_image{t->lattice[1], t->lattice[2]});
+        KMCF_HIP(hipGetLastError());
+        if (sb.spread) KMCF_TRY(kmcf_comm_allgatherv_double(t->comm, t->d_tdiag, sb.counts.data(), sb.displs.data()));
+    } else {
+        fill_kernel<<<kmcf_grid1d(64 * nb), KMCF_BLOCK, 0, st>>>(64 * nb, sb.d_xsub, 1.0);
+        KMCF_HIP(hipMemsetAsync(t->d_tdiag, 0, (size_t)n_t * sizeof(double), st));
+        KMCF_TRY((symm_apply<0, false>(t->comm, sb, n_t, 0, nullptr, nullptr, t->d_tdiag, nullptr, nullptr, nullptr, 0)));
+    }
     if (sb.jagged) symj_set_diag_kernel<<<std::max(1, (nb + 3) / 4), KMCF_BLOCK, 0, st>>>(n_t, nb, t->d_tdiag, t->d_tdiag, sb.d_jmask, sb.d_jvoff, sb.d_jval);
     else symm_set_diag_kernel<<<kmcf_grid1d(n_t), KMCF_BLOCK, 0, st>>>(n_t, nb, t->d_tdiag, t->d_tdiag, sb.d_tiles, sb.spread ? sb.d_tile_local : nullptr);
     KMCF_HIP(hipMemsetAsync(sb.d_xsub, 0, (size_t)64 * nb * sizeof(double), st));      // the pad behind the last point stays 0
@@ -1827,8 +1961,10 @@ static int asm_bitmap_pattern(kmcf_tstate *t)
     KMCF_CHECK((int64_t)n_t * KMCF_BLOCK <= (int64_t)INT32_MAX, KMCF_ERR_ARG,
                "tunnel block: %d tunnel points exceed the row-offset scan's range (256 rows of that many entries in an int)", n_t);
     sub_rows_kernel<<<kmcf_grid1d(ns), KMCF_BLOCK, 0, st>>>(ns, sb.row0, t->d_tidx, t->T->row0, t->d_inv_perm, sb.d_rows);
-    tunnel_mask_kernel<<<wave_row_grid(ns), KMCF_BLOCK, 0, st>>>(ns, sb.row0, n_t, sb.n_groups, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz, t->d_tcb,
-                                                                 t->nn_dist, t->par.tol, sb.d_mask, t->d_rowcnt);
+    with_dist(t, [&](auto dist) {
+        tunnel_mask_kernel<decltype(dist)><<<wave_row_grid(ns), KMCF_BLOCK, 0, st>>>(ns, sb.row0, n_t, sb.n_groups, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz,
+                                                                                     t->d_tcb, t->nn_dist, t->par.tol, sb.d_mask, t->d_rowcnt, dist);
+    });
     kmcf_scan_counts_kernel<long long><<<1, KMCF_BLOCK, 0, st>>>(ns, t->d_rowcnt, sb.d_voff, 0);
     KMCF_HIP(hipGetLastError());
     KMCF_HIP(hipMemcpyAsync(&t->h_pin->nnz, sb.d_voff + ns, sizeof(long long), hipMemcpyDeviceToHost, st));
@@ -1882,8 +2018,11 @@ static int asm_values(kmcf_tstate *t)
         KMCF_TRY(symm_setup(t));
     } else if (ns > 0) {
         KMCF_TRY(ensure(&sb.d_val, &sb.cap_val, (size_t)sb.nnz + 64));
-        tunnel_value_kernel<<<wave_row_grid(ns), KMCF_BLOCK, 0, t->comm->stream>>>(ns, sb.row0, sb.n_groups, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz, t->d_tcb,
-                                                                                   t->nn_dist, p->tol, p->m_e, p->V0, sb.d_mask, sb.d_voff, sb.d_val, t->d_tdiag);
+        with_dist(t, [&](auto dist) {
+            tunnel_value_kernel<decltype(dist)><<<wave_row_grid(ns), KMCF_BLOCK, 0, t->comm->stream>>>(
+                ns, sb.row0, sb.n_groups, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz, t->d_tcb, t->nn_dist, p->tol, p->m_e, p->V0, sb.d_mask, sb.d_voff, sb.d_val,
+                t->d_tdiag, dist);
+        });
         KMCF_HIP(hipGetLastError());
     }
     sb.grid = sb.spread ? (ns + KMCF_BLOCK - 1) / KMCF_BLOCK : sb.dense ? sb.nb : ns > 0 ? wave_row_grid(ns) : 0;
@@ -2056,8 +2195,11 @@ static int tunnel_rows_recomputed(const kmcf_tstate *t, double *h_val)
     double *d_v = nullptr, *d_dg = nullptr;
     KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&d_v), ((size_t)sb.nnz + 64) * sizeof(double)));
     if (hipMalloc(reinterpret_cast<void **>(&d_dg), ((size_t)ns + 1) * sizeof(double)) != hipSuccess) { hipFree(d_v); KMCF_HIP(hipErrorOutOfMemory); }
-    tunnel_value_kernel<<<wave_row_grid(ns), KMCF_BLOCK, 0, t->comm->stream>>>(ns, sb.row0, sb.n_groups, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz, t->d_tcb,
-                                                                               t->nn_dist, t->par.tol, t->par.m_e, t->par.V0, sb.d_mask, sb.d_voff, d_v, d_dg);
+    with_dist(t, [&](auto dist) {
+        tunnel_value_kernel<decltype(dist)><<<wave_row_grid(ns), KMCF_BLOCK, 0, t->comm->stream>>>(
+            ns, sb.row0, sb.n_groups, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz, t->d_tcb, t->nn_dist, t->par.tol, t->par.m_e, t->par.V0, sb.d_mask, sb.d_voff, d_v,
+            d_dg, dist);
+    });
     hipError_t e1 = hipGetLastError();
     if (e1 == hipSuccess) e1 = hipStreamSynchronize(t->comm->stream);
     if (e1 == hipSuccess) e1 = hipMemcpy(h_val, d_v, (size_t)sb.nnz * sizeof(double), hipMemcpyDeviceToHost);
@@ -2236,8 +2378,11 @@ extern "C" int kmcf_current_map(kmcf_tstate *t, const double *d_atom_virtual_pot
         KMCF_HIP(hipGetLastError());
     }
     if (sb.n_loc > 0) {
-        current_tunnel_kernel<<<wave_row_grid(sb.n_loc), KMCF_BLOCK, 0, st>>>(sb.n_loc, sb.row0, sb.n_groups, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz, t->d_tcb,
-                                                                              t->par.tol, t->par.m_e, t->par.V0, sb.d_mask, t->d_tidx, pot, t->d_cmap);
+        with_dist(t, [&](auto dist) {
+            current_tunnel_kernel<decltype(dist)><<<wave_row_grid(sb.n_loc), KMCF_BLOCK, 0, st>>>(
+                sb.n_loc, sb.row0, sb.n_groups, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz, t->d_tcb, t->par.tol, t->par.m_e, t->par.V0, sb.d_mask, t->d_tidx, pot,
+                t->d_cmap, dist);
+        });
         KMCF_HIP(hipGetLastError());
     }
     // every rank gets all nodes (as d_pdisp is gathered: the row partition, three doubles a row)

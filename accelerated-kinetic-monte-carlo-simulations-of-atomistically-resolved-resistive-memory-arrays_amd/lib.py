@@ -197,6 +197,9 @@ SIGNATURES = {
     "kmcf_poisson_gridless": (C.c_int, [_P, _P, _P, _P, _P, C.c_double, C.c_double, C.c_int, C.c_int, _P]),
     "kmcf_initialize_sparsity_T": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _IP, _IP,
                                              C.POINTER(_P)]),
+    "kmcf_initialize_sparsity_T_pbc": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, _DP, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int,
+                                                 _IP, _IP, C.POINTER(_P)]),
+    "kmcf_tstate_periodic": (C.c_int, [_P, _IP, _DP]),
     "kmcf_tstate_destroy": (C.c_int, [_P]),
     "kmcf_tstate_matrix": (_P, [_P]),
     "kmcf_tstate_info": (C.c_int, [_P, C.POINTER(TStateInfo)]),

@@ -291,10 +291,14 @@ def update_CB_edge_gpu_sparse(gpubuf, N, N_left_tot, N_right_tot, Vd, pbc, high_
     return st.as_dict()
 
 
-def initialize_sparsity_T(gpubuf, pbc, nn_dist, num_source_inj, num_ground_ext, num_layers_contact, kmc_comm):
+def initialize_sparsity_T(gpubuf, pbc, nn_dist, num_source_inj, num_ground_ext, num_layers_contact, kmc_comm, periodic=False):
     """initialize_sparsity_T (gpu_solvers.h:57; src/initialize_sparsity_T.cu:948-1154).  kmc_comm.counts_T must
     partition N_atom + 1 rows (src/kmc_main.cpp:165-171); pbc is accepted and, like the reference's T kernels,
-    not used (they call the non-periodic site_dist_gpu overload)."""
+    not used (they call the non-periodic site_dist_gpu overload).  periodic=True with pbc == 1:
+    kmcf_initialize_sparsity_T_pbc with the periods of gpubuf.lattice_host -- neighbour pattern, ground flag, tunnel
+    block and current map take the minimum image in y and z (include/kmcfield.h).  periodic=True with any other pbc
+    builds the OPEN state without a warning (a caller's pbc = 0 device has no periods to take): t_periodic(gpubuf) is how
+    to find out which state was built."""
     lib = _L.load()
     if gpubuf.T_distributed is not None:
         lib.kmcf_tstate_destroy(gpubuf.T_distributed)
@@ -302,10 +306,17 @@ def initialize_sparsity_T(gpubuf, pbc, nn_dist, num_source_inj, num_ground_ext, 
     h = C.c_void_p()
     cnt, cntp = _ia(kmc_comm.counts_T)
     dsp, dspp = _ia(kmc_comm.displs_T)
-    _L.check(lib.kmcf_initialize_sparsity_T(kmc_comm.handle, _ptr(gpubuf.site_x), _ptr(gpubuf.site_y), _ptr(gpubuf.site_z),
-                                            _ptr(gpubuf.site_element), gpubuf.N_, float(nn_dist), int(num_source_inj),
-                                            int(num_ground_ext), int(num_layers_contact), cntp, dspp, C.byref(h)),
-             "kmcf_initialize_sparsity_T")
+    if periodic and int(pbc) == 1:
+        lat, latp = _da(gpubuf.lattice_host)
+        _L.check(lib.kmcf_initialize_sparsity_T_pbc(kmc_comm.handle, _ptr(gpubuf.site_x), _ptr(gpubuf.site_y), _ptr(gpubuf.site_z),
+                                                    _ptr(gpubuf.site_element), gpubuf.N_, latp, 1, float(nn_dist),
+                                                    int(num_source_inj), int(num_ground_ext), int(num_layers_contact), cntp, dspp,
+                                                    C.byref(h)), "kmcf_initialize_sparsity_T_pbc")
+    else:
+        _L.check(lib.kmcf_initialize_sparsity_T(kmc_comm.handle, _ptr(gpubuf.site_x), _ptr(gpubuf.site_y), _ptr(gpubuf.site_z),
+                                                _ptr(gpubuf.site_element), gpubuf.N_, float(nn_dist), int(num_source_inj),
+                                                int(num_ground_ext), int(num_layers_contact), cntp, dspp, C.byref(h)),
+                 "kmcf_initialize_sparsity_T")
     gpubuf.T_distributed = h
     info = t_info(gpubuf)
     gpubuf.N_atom_ = info["N_atom"]
@@ -364,6 +375,14 @@ def current_map(gpubuf, potentials=None, tunnel=True, net=True):
     _L.check(_L.load().kmcf_current_map(gpubuf.T_distributed, _ptr(pot), _ptr(cur), _ptr(tun), _ptr(nt), C.byref(st)),
              "kmcf_current_map")
     return dict(current=cur, tunnel=tun, net=nt, stats=st.as_dict())
+
+
+def t_periodic(gpubuf):
+    """kmcf_tstate_periodic: (pbc, lattice) the T state was built with -- (0, zeros) for a state of the plain call."""
+    pbc, lat = C.c_int(-1), np.zeros(3)
+    _L.check(_L.load().kmcf_tstate_periodic(gpubuf.T_distributed, C.byref(pbc), lat.ctypes.data_as(C.POINTER(C.c_double))),
+             "kmcf_tstate_periodic")
+    return pbc.value, lat
 
 
 def t_info(gpubuf):

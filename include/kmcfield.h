@@ -806,12 +806,39 @@ typedef struct kmcf_tstate kmcf_tstate; /* gpubuf.T_distributed + T_p_distribute
  * events, which only turn O <-> V and d <-> Od) and builds the pattern of the neighbour matrix
  * over Nsub = N_atom + 1 nodes (0 = extraction, 1 = injection, 2.. = atoms, the last atom --
  * the ground node -- cut) for the rows [displs[rank], +counts[rank]) of counts_T / displs_T
- * (kmc_comm.counts_T).  Cell list instead of the O(n_loc * Nsub) scans; the distance is the
- * non-periodic one the reference's T kernels use whatever pbc says (src/gpu_solvers.h:280-285). */
+ * (kmc_comm.counts_T).  Cell list instead of the O(n_loc * Nsub) scans; the distance of THIS call is
+ * the non-periodic one the reference's T kernels use whatever pbc says (src/gpu_solvers.h:280-285);
+ * kmcf_initialize_sparsity_T_pbc (below) builds the state under periodic y-z boundaries. */
 int kmcf_initialize_sparsity_T(kmcf_comm *c, const double *d_site_x, const double *d_site_y,
                                const double *d_site_z, const int *d_site_element, int N, double nn_dist,
                                int num_source_inj, int num_ground_ext, int num_layers_contact,
                                const int *h_counts_T, const int *h_displs_T, kmcf_tstate **out);
+
+/* The same state under periodic boundaries in y and z.  pbc == 0 (h_lattice may be NULL): kmcf_initialize_sparsity_T --
+ * the same launches, and a state whose every later output is the same bytes.  pbc == 1: the periods Ly = h_lattice[1],
+ * Lz = h_lattice[2] are copied into the state, and every distance the state forms from then on is the library's ONE
+ * minimum image (the text above kmcf_compute_cutoff_list_pbc: x never periodic, the C round, only the nearest image --
+ * where a period is shorter than 2 nn_dist a second image adds nothing):
+ *   - the neighbour pattern (d < nn_dist): bonds through the y and z faces.  The wrapped cell grid of
+ *     kmcf_initialize_sparsity_K where at least 3 cells of nn_dist fit each period and the atoms do not span one; else
+ *     every pair is tested;
+ *   - the ground flag: the atoms within nn_dist of the last atom THROUGH a face carry +high_G on their diagonal too;
+ *   - the tunnel block of every later kmcf_t_assemble / kmcf_update_power_sparse: the pair rule d > nn_dist and the
+ *     distance inside the WKB value, in all three storage forms; and the fresh evaluation of kmcf_current_map.
+ * d(i, j) and d(j, i) are the same bits (division, round, subtraction and product are odd in the difference, the squares
+ * remove the sign), so the block stays exactly symmetric and its storage forms hold the same values.  Everything that
+ * reads stored values -- the split SpMV, I_macro, the dissipated power -- is periodic through what was stored; the
+ * exports below report the periodic system.  A rank group deals and gathers as before.  The tunnel diagonal of a
+ * periodic state is one sum per row of the pair bitmap in every storage form: diagonal and preconditioner are the same
+ * bytes as bitmap, tiles or jagged tiles, on one rank or dealt over a group (the open state's tile sums depend on the deal).
+ * KMCF_ERR_ARG, kmcf_last_error naming the axis, before anything needs a device: pbc outside 0 / 1; with pbc == 1 a NULL
+ * h_lattice or a period that is not finite or <= 0.  Otherwise the errors of kmcf_initialize_sparsity_T. */
+int kmcf_initialize_sparsity_T_pbc(kmcf_comm *c, const double *d_site_x, const double *d_site_y, const double *d_site_z,
+                                   const int *d_site_element, int N, const double *h_lattice /* 3, host */, int pbc,
+                                   double nn_dist, int num_source_inj, int num_ground_ext, int num_layers_contact,
+                                   const int *h_counts_T, const int *h_displs_T, kmcf_tstate **out);
+/* Inspection: *pbc and (h_lattice may be NULL) the three lattice values the state was built with (zeros if none). */
+int kmcf_tstate_periodic(const kmcf_tstate *t, int *pbc, double *h_lattice /* 3, may be NULL */);
 int kmcf_tstate_destroy(kmcf_tstate *t);
 kmcf_matrix *kmcf_tstate_matrix(kmcf_tstate *t);   /* gpubuf.T_distributed (neighbour part) */
 

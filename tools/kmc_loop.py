@@ -12,7 +12,9 @@ solve with heating (site_power), local heat solve (site_temperature); --rate-mod
 that field (kmcf_execute_kmc_step_thermal).  Workload `conducting`: the 4 x 4 crossbar with a vacancy filament of
 tests/test_gpu_conducting.py, whose current is a property of the device.  Workload `5nm-periodic`: the 5 nm example as the
 periodic cell it is (structure.periodic_5nm, pbc = 1 in y and z): neighbour list, K pattern, the spatial index of the pairwise
-term and the pair distance of the event rates all take the minimum image; the step line is the one of `5nm`.  --clusters runs the conductive cluster analysis
+term and the pair distance of the event rates all take the minimum image, and with --current so does the T state of the
+current solve (kmcf_initialize_sparsity_T_pbc: neighbour bonds and the ground flag through the faces, the tunnel block's
+pair rule and WKB distance, the current map); the step line is the one of `5nm`.  --clusters runs the conductive cluster analysis
 (kmcf_conductive_clusters) after the charge update of every step: whether a filament bridges the electrodes, without a
 current solve; the step line gains `clusters <ms> (<vacancy clusters> vac, largest <sites>, bridging <filaments>)`, the
 time in milliseconds of device time.  --current-map (with --current) runs the site-resolved current map (kmcf_current_map)
@@ -118,7 +120,7 @@ def main():
         # the atoms of the current solve are invariant under KMC events: one pattern per run (src/kmc_main.cpp:273)
         N_atom = int(((d["element"] != 0) & (d["element"] != 1)).sum())
         comm.counts_T, comm.displs_T = comm.partition(N_atom + 1, comm.size_T)
-        S.initialize_sparsity_T(buf, d["pbc"], d["nn_dist"], NL, NL, 10, comm)
+        S.initialize_sparsity_T(buf, d["pbc"], d["nn_dist"], NL, NL, 10, comm, periodic=periodic)
         q_e = 1.60217663e-19
         high_G_T, loop_G, G0 = 1e5 * d["high_G"], 1e7 * d["high_G"], 2 * 3.8612e-5 * 1e-5
         side = float(d["lattice"][1]) * 1e-10
