@@ -980,6 +980,10 @@ typedef struct {
  * step_time, or the steady state when step_time > 1e3 * delta_t (*h_steady = 1).
  * d_site_temperature: N doubles in/out.  Its interface slice is T_old and the start guess;
  * on return every rank holds the whole field (interface solved, contacts = background_temp).
+ * The contact slots are written, never read: whatever the caller left there is replaced.
+ * step_time == 0 assembles and solves nothing: the interface slice comes back as it was, the
+ * contacts are set to background_temp all the same, *h_steady = 0, stats are zero with
+ * converged = 1, and the state keeps the system it held.
  * *h_T_bg = mean over the interface sites.  h_T_bg, h_steady and stats may be NULL.
  * Runs on one rank and on rank groups; overwrites the K values of the state (the next
  * kmcf_k_assemble refills them) and never uses K's resident solve plan. */
