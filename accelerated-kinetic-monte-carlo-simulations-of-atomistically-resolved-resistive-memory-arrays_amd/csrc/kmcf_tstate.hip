@@ -24,6 +24,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 
 #include "kmcf_cells.hpp"
 #include "kmcf_internal.hpp"
@@ -83,6 +84,16 @@ struct kmcf_tstate {
     double *d_cmap = nullptr;                      // 3 (Nsub + 2): per node sum |I|, tunnel sum |I|, sum I, interleaved
     double *d_cmstat = nullptr, *h_cmstat = nullptr;   // 8 doubles on the device / pinned: the statistics
     std::vector<int> cm_counts, cm_displs;         // 3 x the matrix's row partition (the all-gather of d_cmap)
+    // kmcf_current_profile: scratch only, like the current map's
+    double *d_cprof = nullptr;                     // CP_STRIDE (Nsub + 2): the per-node sums (nullptr: too many atoms for int32 counts)
+    int *d_cpq = nullptr, *d_cpcell = nullptr;     // N_atom each: slab and cell of every atom
+    double *d_cpplanes = nullptr, *h_cpplanes = nullptr;   // 1024 planes on the device / pinned (staging of h_plane_x)
+    double *d_cpout = nullptr, *h_cpout = nullptr; // the profile + 8 statistics on the device / pinned; grown at the start of a call
+    size_t cap_cpout = 0;
+    double *d_cppart = nullptr;                    // the segments' slab sums of the binning; grown like d_cpout
+    size_t cap_cppart = 0;
+    std::vector<void *> cp_retired_dev, cp_retired_host;   // outgrown d_cpout / h_cpout: freed with the state, never inside a call
+    std::vector<int> cp_counts, cp_displs;         // CP_STRIDE x the row partition
 };
 
 namespace {
@@ -1302,6 +1313,292 @@ __global__ __launch_bounds__(KMCF_BLOCK) void current_stats_kernel(int n_rows_at
     }
 }
 
+// ---------------------------------------------------------------- current profile (kmcf_current_profile)
+// Per node CP_STRIDE doubles, interleaved so that one all-gather moves them:
+//   [0] / [1]  sum of I_as over the node's counted NEIGHBOUR pairs that leave its slab (q(s) != q(a)): those of its own
+//              cell / the rest        [2] / [3]  the same over its TUNNEL pairs
+//   [4 .. 6]   sum of I_as * d_as (twice J; zeros when no vector is asked for)        [7]  sum of I_as over ALL its pairs
+// The two virtual nodes have no position: only [7] is formed for them (the injected / extracted current).
+constexpr int CP_STRIDE = 8, CP_MAX = 1024;
+
+// d_as in y and z: plain differences on an open state, the library's minimum image (kmcf_min_image_dist's expression, of
+// s against a) on a periodic one; picked by the state's distance functor like the WKB distance itself
+__device__ __forceinline__ void pair_disp(const dist_open &, double ya, double za, double ys, double zs, double *dy, double *dz)
+{
+    *dy = ys - ya; *dz = zs - za;
+}
+__device__ __forceinline__ void pair_disp(const dist_min_image &d, double ya, double za, double ys, double zs, double *dy, double *dz)
+{
+    double fy = (ys - ya) / d.ly;
+    fy -= round(fy);
+    double fz = (zs - za) / d.lz;
+    fz -= round(fz);
+    *dy = fy * d.ly; *dz = fz * d.lz;
+}
+
+// q(a) = number of planes X_k <= x_a (binary search in LDS) and the cell of every atom: n_cells stands for "none"
+__global__ __launch_bounds__(KMCF_BLOCK) void profile_key_kernel(int n_atoms, const double *__restrict__ ax, const int *__restrict__ atom_site,
+                                                                 const int *__restrict__ site_cell, int n_cells,
+                                                                 const double *__restrict__ planes, int n_planes, int *__restrict__ q,
+                                                                 int *__restrict__ cell)
+{
+    __shared__ double X[CP_MAX];
+    for (int k = threadIdx.x; k < n_planes; k += KMCF_BLOCK) X[k] = planes[k];
+    __syncthreads();
+    for (int a = blockIdx.x * blockDim.x + threadIdx.x; a < n_atoms; a += gridDim.x * blockDim.x) {
+        const double x = ax[a];
+        int lo = 0, hi = n_planes;                                        // planes [0, lo) are <= x, planes [hi, n) are > x
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (X[mid] <= x) lo = mid + 1; else hi = mid;
+        }
+        q[a] = lo;
+        int c = 0;
+        if (site_cell) {
+            c = site_cell[atom_site[a]];
+            if (c < 0 || c >= n_cells) c = n_cells;
+        }
+        cell[a] = c;
+    }
+}
+
+// one counted pair a -> s carrying i_as into the sums of a
+template <bool VEC, typename DIST>
+__device__ __forceinline__ void profile_add_pair(double i_as, int a, int s, int qa, int ca, int n_cells, const int *__restrict__ q,
+                                                 const int *__restrict__ cell, const double *__restrict__ ax, const double *__restrict__ ay,
+                                                 const double *__restrict__ az, double xa, double ya, double za, const DIST &dist,
+                                                 double &same, double &rest, double &jx, double &jy, double &jz)
+{
+    if (q[s] != qa) {
+        if (ca < n_cells && cell[s] == ca) same += i_as; else rest += i_as;
+    }
+    if (VEC) {
+        double dy, dz;
+        pair_disp(dist, ya, za, ay[s], az[s], &dy, &dz);
+        jx += i_as * (ax[s] - xa); jy += i_as * dy; jz += i_as * dz;
+    }
+}
+
+// Neighbour part: current_neighbour_kernel's walk (LPR lanes per internal row, virtual rows included); sets all
+// CP_STRIDE values of the row's node.
+template <int LPR, bool VEC, typename DIST>
+__global__ __launch_bounds__(KMCF_BLOCK) void profile_neighbour_kernel(
+    int n_loc, const int *__restrict__ row_ptr, const int *__restrict__ col, const double *__restrict__ val, const int *__restrict__ diag_pos,
+    const int *__restrict__ col_node, const double *__restrict__ m, const int *__restrict__ q, const int *__restrict__ cell, int n_cells,
+    const double *__restrict__ ax, const double *__restrict__ ay, const double *__restrict__ az, double *__restrict__ pv, DIST dist)
+{
+    constexpr int RPB = KMCF_BLOCK / LPR;
+    const int lane = threadIdx.x % LPR;
+    const int groups = (n_loc + RPB - 1) / RPB;
+    for (int grp = blockIdx.x; grp < groups; grp += gridDim.x) {
+        const int r = grp * RPB + threadIdx.x / LPR;
+        const bool valid = r < n_loc;
+        double same = 0.0, rest = 0.0, jx = 0.0, jy = 0.0, jz = 0.0, net = 0.0;
+        int nr = 0;
+        if (valid) {
+            nr = col_node[r];
+            const double mr = m[nr];
+            const int dpos = diag_pos[r];
+            const int a = nr - 2;
+            int qa = 0, ca = 0;
+            double xa = 0.0, ya = 0.0, za = 0.0;
+            if (a >= 0) {
+                qa = q[a]; ca = cell[a];
+                if (VEC) { xa = ax[a]; ya = ay[a]; za = az[a]; }
+            }
+            for (int j = row_ptr[r] + lane; j < row_ptr[r + 1]; j += LPR) {
+                if (j == dpos) continue;
+                const int nc = col_node[col[j]];
+                if (nr < 2 && nc < 2) continue;                        // (0, 1) / (1, 0)
+                const double g = -val[j];
+                const double i_rc = g * (mr - m[nc]);
+                net += i_rc;
+                if (a >= 0 && nc >= 2) profile_add_pair<VEC>(i_rc, a, nc - 2, qa, ca, n_cells, q, cell, ax, ay, az, xa, ya, za, dist, same, rest, jx, jy, jz);
+            }
+        }
+#pragma unroll
+        for (int off = LPR / 2; off >= 1; off >>= 1) {
+            same += __shfl_xor(same, off, 64); rest += __shfl_xor(rest, off, 64); net += __shfl_xor(net, off, 64);
+            if (VEC) { jx += __shfl_xor(jx, off, 64); jy += __shfl_xor(jy, off, 64); jz += __shfl_xor(jz, off, 64); }
+        }
+        if (valid && lane == 0) {
+            double *v = pv + CP_STRIDE * (size_t)nr;
+            v[0] = same; v[1] = rest; v[2] = 0.0; v[3] = 0.0; v[4] = jx; v[5] = jy; v[6] = jz; v[7] = net;
+        }
+    }
+}
+
+// Tunnel part: current_tunnel_kernel's walk (a wave per local row of the pair bitmap, the conductance of every set pair
+// evaluated afresh); sets [2] / [3] and adds onto [4 .. 7] of the row's node (after the neighbour part, same stream).
+template <bool VEC, typename DIST>
+__global__ __launch_bounds__(KMCF_BLOCK) void profile_tunnel_kernel(
+    int n_loc, int s0, int n_groups, const int *__restrict__ tinfo, const double *__restrict__ tx, const double *__restrict__ ty,
+    const double *__restrict__ tz, const double *__restrict__ tcb, double tol, double m_e, double V0,
+    const unsigned long long *__restrict__ mask, const int *__restrict__ tidx, const double *__restrict__ m, const int *__restrict__ q,
+    const int *__restrict__ cell, int n_cells, double *__restrict__ pv, DIST dist)
+{
+    const int lane = threadIdx.x & 63;
+    const int wpb = KMCF_BLOCK / 64;
+    for (int s = blockIdx.x * wpb + (threadIdx.x >> 6); s < n_loc; s += gridDim.x * wpb) {
+        const int sg = s0 + s;
+        const double xi = tx[sg], yi = ty[sg], zi = tz[sg], cbi = tcb[sg];
+        const int fi = tinfo[sg];
+        const int a = tidx[sg];
+        const double mr = m[a + 2];
+        const int qa = q[a], ca = cell[a];
+        double same = 0.0, rest = 0.0, jx = 0.0, jy = 0.0, jz = 0.0, net = 0.0;
+        for (int g = 0; g < n_groups; ++g) {
+            const unsigned long long mk = mask[(size_t)s * n_groups + g];
+            if (mk == 0ull) continue;                                      // wave-uniform
+            if ((mk >> lane) & 1ull) {
+                const int j = g * 64 + lane;
+                if (j != sg) {
+                    bool c2t;
+                    tunnel_pair(fi, tinfo[j], cbi, tcb[j], tol, &c2t);
+                    const double gc = -wkb_value(dist(xi, yi, zi, tx[j], ty[j], tz[j]), cbi, tcb[j], c2t, m_e, V0);
+                    const int b = tidx[j];
+                    const double i_rc = gc * (mr - m[b + 2]);
+                    net += i_rc;
+                    // (the tunnel points' coordinates are the atoms': tx[j] == ax[tidx[j]], indexed by point here)
+                    if (q[b] != qa) {
+                        if (ca < n_cells && cell[b] == ca) same += i_rc; else rest += i_rc;
+                    }
+                    if (VEC) {
+                        double dy, dz;
+                        pair_disp(dist, yi, zi, ty[j], tz[j], &dy, &dz);
+                        jx += i_rc * (tx[j] - xi); jy += i_rc * dy; jz += i_rc * dz;
+                    }
+                }
+            }
+        }
+        same = kmcf_wave_sum64(same); rest = kmcf_wave_sum64(rest); net = kmcf_wave_sum64(net);
+        if (VEC) { jx = kmcf_wave_sum64(jx); jy = kmcf_wave_sum64(jy); jz = kmcf_wave_sum64(jz); }
+        if (lane == 0) {
+            double *v = pv + CP_STRIDE * ((size_t)a + 2);
+            v[2] = same; v[3] = rest; v[7] += net;
+            if (VEC) { v[4] += jx; v[5] += jy; v[6] += jz; }
+        }
+    }
+}
+
+// Binning, in two steps without atomics.  The atoms with a row are cut into n_seg segments of seg_len atoms (a multiple of
+// KMCF_BLOCK; both follow from the atom count and n_cells alone, so the order of every addition is fixed by the input).
+// profile_bin_kernel, block (g, c): the values of cell c (c == n_cells: the rest values of every atom) of segment g, summed
+// by slab into part[c][g][slab][t].  The atoms pass through LDS in chunks of KMCF_BLOCK; thread q % 256 owns slab q and adds
+// the chunk's atoms of its slabs in ascending atom order.  (An atom whose two values are zero is skipped: adding a zero
+// changes no bit of a sum that starts at +0.)
+__global__ __launch_bounds__(KMCF_BLOCK) void profile_bin_kernel(int n_rows_atoms, int seg_len, int n_planes, int n_cells,
+                                                                 const int *__restrict__ q, const int *__restrict__ cell,
+                                                                 const double *__restrict__ pv, double *__restrict__ part)
+{
+    __shared__ double bins[2 * (CP_MAX + 1)];
+    __shared__ double s0[KMCF_BLOCK], s1[KMCF_BLOCK];
+    __shared__ int sq[KMCF_BLOCK];
+    const int g = blockIdx.x, c = blockIdx.y, tid = threadIdx.x;
+    const bool is_rest = c == n_cells;
+    const int n_bins = 2 * (n_planes + 1);
+    for (int i = tid; i < n_bins; i += KMCF_BLOCK) bins[i] = 0.0;
+    const int a_end = min(n_rows_atoms, (g + 1) * seg_len);
+    for (int a0 = g * seg_len; a0 < a_end; a0 += KMCF_BLOCK) {
+        const int a = a0 + tid;
+        int myq = -1;
+        double v0 = 0.0, v1 = 0.0;
+        if (a < a_end && (is_rest || cell[a] == c)) {
+            const double *v = pv + CP_STRIDE * ((size_t)a + 2);
+            v0 = v[is_rest ? 1 : 0]; v1 = v[is_rest ? 3 : 2];
+            if (v0 != 0.0 || v1 != 0.0) myq = q[a];
+        }
+        if (!__syncthreads_or(myq >= 0)) continue;                        // (block-uniform; also the barrier before sq is rewritten)
+        sq[tid] = myq; s0[tid] = v0; s1[tid] = v1;
+        __syncthreads();
+#pragma unroll 4
+        for (int j = 0; j < KMCF_BLOCK; ++j) {
+            const int qq = sq[j];
+            if (qq >= 0 && (qq & (KMCF_BLOCK - 1)) == tid) { bins[2 * qq] += s0[j]; bins[2 * qq + 1] += s1[j]; }
+        }
+    }
+    __syncthreads();
+    double *out = part + ((size_t)c * gridDim.x + g) * n_bins;
+    for (int i = tid; i < n_bins; i += KMCF_BLOCK) out[i] = bins[i];
+}
+
+// profile_prefix_kernel, block c: the segments' sums of every slab added in ascending segment order, then
+// F[c][k][t] = sum over the slabs q <= k, one thread per kind.
+__global__ __launch_bounds__(KMCF_BLOCK) void profile_prefix_kernel(int n_seg, int n_planes, const double *__restrict__ part,
+                                                                    double *__restrict__ prof)
+{
+    __shared__ double bins[2 * (CP_MAX + 1)];
+    const int c = blockIdx.x, tid = threadIdx.x;
+    const int n_bins = 2 * (n_planes + 1);
+    for (int i = tid; i < n_bins; i += KMCF_BLOCK) {
+        double acc = 0.0;
+        for (int g = 0; g < n_seg; ++g) acc += part[((size_t)c * n_seg + g) * n_bins + i];
+        bins[i] = acc;
+    }
+    __syncthreads();
+    if (tid == 0 || tid == 64) {
+        const int t = tid >> 6;
+        double acc = 0.0;
+        for (int k = 0; k < n_planes; ++k) {
+            acc += bins[2 * k + t];
+            prof[((size_t)c * n_planes + k) * 2 + t] = acc;
+        }
+    }
+}
+
+// J to the site arrays (zero-filled before): half of the sums, atoms with a row only
+__global__ __launch_bounds__(KMCF_BLOCK) void profile_scatter_kernel(int n_rows_atoms, const int *__restrict__ atom_site,
+                                                                     const double *__restrict__ pv, double *__restrict__ site_jx,
+                                                                     double *__restrict__ site_jy, double *__restrict__ site_jz)
+{
+    for (int a = blockIdx.x * blockDim.x + threadIdx.x; a < n_rows_atoms; a += gridDim.x * blockDim.x) {
+        const int s = atom_site[a];
+        const double *v = pv + CP_STRIDE * ((size_t)a + 2);
+        site_jx[s] = 0.5 * v[4]; site_jy[s] = 0.5 * v[5]; site_jz[s] = 0.5 * v[6];
+    }
+}
+
+// One block.  total[k] = sum over c = 0 .. n_cells (ascending) of (F[c][k][0] + F[c][k][1]), thread k % 256; its smallest and
+// largest value with the lowest plane among equals; sum of jx like current_stats_kernel's sums.
+// out: [0] net[1], [1] -net[0], [2] flux_min, [3] flux_max, [4] sum_jx, [5] plane_min, [6] plane_max
+__global__ __launch_bounds__(KMCF_BLOCK) void profile_stats_kernel(int n_rows_atoms, int n_planes, int n_cells, const double *__restrict__ prof,
+                                                                   const double *__restrict__ pv, int vec, double *__restrict__ out)
+{
+    __shared__ double lds4[4];
+    __shared__ double tot[CP_MAX];
+    const double inf = __builtin_huge_val();
+    double mx = -inf, mn_neg = -inf;                                       // (minus the minimum: a maximum again)
+    for (int k = threadIdx.x; k < n_planes; k += KMCF_BLOCK) {
+        double s = 0.0;
+        for (int c = 0; c <= n_cells; ++c) {
+            const double *f = prof + ((size_t)c * n_planes + k) * 2;
+            s += f[0] + f[1];
+        }
+        tot[k] = s;
+        mx = fmax(mx, s); mn_neg = fmax(mn_neg, -s);
+    }
+    mx = kmcf_block_max(mx, lds4);                                         // (its barriers also publish tot)
+    mn_neg = kmcf_block_max(mn_neg, lds4);
+    double kmx = -2147483648.0, kmn = -2147483648.0;                       // (minus the plane)
+    for (int k = threadIdx.x; k < n_planes; k += KMCF_BLOCK) {
+        if (tot[k] == mx) kmx = fmax(kmx, -(double)k);
+        if (-tot[k] == mn_neg) kmn = fmax(kmn, -(double)k);
+    }
+    kmx = kmcf_block_max(kmx, lds4);
+    kmn = kmcf_block_max(kmn, lds4);
+    double sj = 0.0;
+    if (vec)
+        for (int a = threadIdx.x; a < n_rows_atoms; a += KMCF_BLOCK) sj += 0.5 * pv[CP_STRIDE * ((size_t)a + 2) + 4];
+    sj = kmcf_block_sum(sj, lds4);
+    if (threadIdx.x == 0) {
+        out[0] = pv[CP_STRIDE * 1 + 7];
+        out[1] = -pv[7];
+        out[2] = -mn_neg; out[3] = mx; out[4] = sj;
+        out[5] = kmn > -2147483648.0 ? -kmn : -1.0;                       // (-1: every total is a NaN)
+        out[6] = kmx > -2147483648.0 ? -kmx : -1.0;
+    }
+}
+
 // growth rule of the per-assembly buffers: a quarter more than needed, 64 elements at least
 template <typename T>
 int ensure(T **d, size_t *cap, size_t need)
@@ -1343,7 +1640,11 @@ extern "C" int kmcf_tstate_destroy(kmcf_tstate *t)
                            t->sub.d_rows, t->sub.d_mask, t->sub.d_voff, t->sub.d_val, t->sub.d_xsub, t->d_pdisp, t->d_scal, t->d_err,
                            t->sub.d_tiles, t->sub.d_strips, t->sub.d_strip_first, t->sub.d_rowpart, t->sub.d_colpart,
                            t->sub.d_jmask, t->sub.d_jvoff, t->sub.d_jval, t->sub.d_jcnt, t->sub.d_tile_local, t->sub.d_ypart, t->d_agree,
-                           t->d_cmap, t->d_cmstat});
+                           t->d_cmap, t->d_cmstat, t->d_cprof, t->d_cpq, t->d_cpcell, t->d_cpplanes, t->d_cpout, t->d_cppart});
+        for (void *p : t->cp_retired_dev) hipFree(p);
+        for (void *p : t->cp_retired_host) hipHostFree(p);
+        if (t->h_cpplanes) hipHostFree(t->h_cpplanes);
+        if (t->h_cpout) hipHostFree(t->h_cpout);
         if (t->h_pin) hipHostFree(t->h_pin);
         if (t->h_agree) hipHostFree(t->h_agree);
         if (t->h_cmstat) hipHostFree(t->h_cmstat);
@@ -1568,6 +1869,15 @@ static int init_workspace(kmcf_tstate *t, const int *h_counts_T, const int *h_di
     KMCF_TRY(pinned_zeroed(&t->h_cmstat, 8));
     t->cm_counts.resize((size_t)P); t->cm_displs.resize((size_t)P);
     for (int q = 0; q < P; ++q) { t->cm_counts[q] = 3 * h_counts_T[q]; t->cm_displs[q] = 3 * h_displs_T[q]; }
+    // scratch of kmcf_current_profile (the profile itself is sized by the call: grown at its very start)
+    if ((int64_t)CP_STRIDE * (Nsub + 2) < (int64_t)INT32_MAX) {
+        KMCF_TRY(kmcf_dev_alloc(&t->d_cprof, (size_t)CP_STRIDE * (Nsub + 2), true));
+        KMCF_TRY(kmcf_dev_alloc(&t->d_cpq, na, true)); KMCF_TRY(kmcf_dev_alloc(&t->d_cpcell, na, true));
+        KMCF_TRY(kmcf_dev_alloc(&t->d_cpplanes, (size_t)CP_MAX, true));
+        KMCF_TRY(pinned_zeroed(&t->h_cpplanes, (size_t)CP_MAX));
+        t->cp_counts.resize((size_t)P); t->cp_displs.resize((size_t)P);
+        for (int q = 0; q < P; ++q) { t->cp_counts[q] = CP_STRIDE * h_counts_T[q]; t->cp_displs[q] = CP_STRIDE * h_displs_T[q]; }
+    }
     return KMCF_OK;
 }
 
@@ -2407,6 +2717,119 @@ extern "C" int kmcf_current_map(kmcf_tstate *t, const double *d_atom_virtual_pot
         float ms = 0.f;
         KMCF_HIP(hipEventElapsedTime(&ms, c->ev_a0, c->ev_a1));
         stats->ms = ms;
+    }
+    return KMCF_OK;
+}
+
+// the device and pinned copies of the profile + statistics hold n doubles afterwards; an outgrown pair is kept until the
+// state goes (a free would wait for the device, where another rank of the group may already stand in its all-gather)
+static int profile_out_grow(kmcf_tstate *t, size_t n, size_t n_part)
+{
+    if (!t->d_cppart || n_part > t->cap_cppart) {
+        if (t->d_cppart) { t->cp_retired_dev.push_back(t->d_cppart); t->d_cppart = nullptr; }
+        t->cap_cppart = 0;
+        KMCF_TRY(kmcf_dev_alloc(&t->d_cppart, n_part, true));
+        t->cap_cppart = n_part;
+    }
+    if (t->d_cpout && n <= t->cap_cpout) return KMCF_OK;
+    if (t->d_cpout) { t->cp_retired_dev.push_back(t->d_cpout); t->d_cpout = nullptr; }
+    if (t->h_cpout) { t->cp_retired_host.push_back(t->h_cpout); t->h_cpout = nullptr; }
+    t->cap_cpout = 0;
+    KMCF_TRY(kmcf_dev_alloc(&t->d_cpout, n, true));
+    KMCF_TRY(pinned_zeroed(&t->h_cpout, n));
+    t->cap_cpout = n;
+    return KMCF_OK;
+}
+
+extern "C" int kmcf_current_profile(kmcf_tstate *t, const double *d_atom_virtual_potentials, const int *d_site_cell, int n_cells,
+                                    const double *h_plane_x, int n_planes, double *h_profile, double *d_site_jx, double *d_site_jy,
+                                    double *d_site_jz, kmcf_current_profile_stats_t *stats)
+{
+    KMCF_CHECK(t, KMCF_ERR_ARG, "kmcf_current_profile: null state (t)");
+    KMCF_CHECK(d_atom_virtual_potentials, KMCF_ERR_ARG, "kmcf_current_profile: null d_atom_virtual_potentials");
+    KMCF_CHECK(h_plane_x, KMCF_ERR_ARG, "kmcf_current_profile: null h_plane_x");
+    KMCF_CHECK(h_profile, KMCF_ERR_ARG, "kmcf_current_profile: null h_profile");
+    KMCF_CHECK(n_planes >= 1 && n_planes <= CP_MAX, KMCF_ERR_ARG, "kmcf_current_profile: n_planes = %d outside 1 ... %d", n_planes, CP_MAX);
+    KMCF_CHECK(n_cells >= 1 && n_cells <= CP_MAX, KMCF_ERR_ARG, "kmcf_current_profile: n_cells = %d outside 1 ... %d", n_cells, CP_MAX);
+    KMCF_CHECK(d_site_cell || n_cells == 1, KMCF_ERR_ARG, "kmcf_current_profile: d_site_cell is NULL with n_cells = %d", n_cells);
+    for (int k = 0; k < n_planes; ++k) {
+        KMCF_CHECK(std::isfinite(h_plane_x[k]), KMCF_ERR_ARG, "kmcf_current_profile: h_plane_x[%d] is not finite", k);
+        KMCF_CHECK(k == 0 || h_plane_x[k - 1] < h_plane_x[k], KMCF_ERR_ARG, "kmcf_current_profile: h_plane_x is not strictly ascending at [%d]", k);
+    }
+    const bool vec = d_site_jx && d_site_jy && d_site_jz;
+    KMCF_CHECK(vec || (!d_site_jx && !d_site_jy && !d_site_jz), KMCF_ERR_ARG,
+               "kmcf_current_profile: d_site_jx, d_site_jy, d_site_jz: pass all three or none");
+    KMCF_CHECK(t->assembled, KMCF_ERR_STATE, "kmcf_current_profile: call kmcf_t_assemble or kmcf_update_power_sparse first");
+    KMCF_CHECK(t->d_cprof, KMCF_ERR_STATE, "kmcf_current_profile: %d atoms exceed the int32 counts of the gather", t->N_atom);
+    kmcf_comm *c = t->comm;
+    kmcf_matrix *m = t->T;
+    KMCF_CHECK(c->connected, KMCF_ERR_COMM, "kmcf_current_profile: communicator not connected");
+    KMCF_TRY(kmcf_enter(c));
+    hipStream_t st = c->stream;
+    const kmcf_subop &sb = t->sub;
+    const int n_loc = m->n_loc, Na = t->N_atom, N = t->N;
+    const double *pot = d_atom_virtual_potentials;
+    const size_t n_prof = (size_t)(n_cells + 1) * n_planes * 2;
+    // the binning's segments: about 1024 blocks over the cells, a segment a multiple of KMCF_BLOCK atoms
+    const int n_rows_atoms = Na - 1;
+    const int seg_want = std::max(1, (1024 + n_cells) / (n_cells + 1));
+    const int seg_len = std::max(1, ((n_rows_atoms + seg_want - 1) / seg_want + KMCF_BLOCK - 1) / KMCF_BLOCK) * KMCF_BLOCK;
+    const int n_seg = std::max(1, (n_rows_atoms + seg_len - 1) / seg_len);
+    KMCF_TRY(profile_out_grow(t, n_prof + 8, (size_t)(n_cells + 1) * n_seg * 2 * (n_planes + 1)));      // (the only allocations, before the first kernel)
+    memcpy(t->h_cpplanes, h_plane_x, (size_t)n_planes * sizeof(double));
+    KMCF_HIP(hipEventRecord(c->ev_a0, st));
+    KMCF_HIP(hipMemcpyAsync(t->d_cpplanes, t->h_cpplanes, (size_t)n_planes * sizeof(double), hipMemcpyHostToDevice, st));
+    if (vec) {
+        KMCF_HIP(hipMemsetAsync(d_site_jx, 0, (size_t)N * sizeof(double), st));
+        KMCF_HIP(hipMemsetAsync(d_site_jy, 0, (size_t)N * sizeof(double), st));
+        KMCF_HIP(hipMemsetAsync(d_site_jz, 0, (size_t)N * sizeof(double), st));
+    }
+    profile_key_kernel<<<kmcf_grid1d(Na), KMCF_BLOCK, 0, st>>>(Na, t->d_ax, t->d_atom_site, d_site_cell, n_cells, t->d_cpplanes, n_planes, t->d_cpq,
+                                                              t->d_cpcell);
+    KMCF_HIP(hipGetLastError());
+    // this rank's rows: the neighbour part sets the values of a node, the tunnel part adds the row's pairs of the bitmap
+    auto walk = [&](auto dist, auto with_vec) {
+        constexpr bool VEC = decltype(with_vec)::value;
+        if (n_loc > 0)
+            profile_neighbour_kernel<16, VEC, decltype(dist)><<<kmcf_grid1d((int64_t)n_loc * 16), KMCF_BLOCK, 0, st>>>(
+                n_loc, m->d_row_ptr, m->d_col, m->d_val, t->d_diag_pos, t->d_col_node, pot, t->d_cpq, t->d_cpcell, n_cells, t->d_ax, t->d_ay, t->d_az,
+                t->d_cprof, dist);
+        if (sb.n_loc > 0)
+            profile_tunnel_kernel<VEC, decltype(dist)><<<wave_row_grid(sb.n_loc), KMCF_BLOCK, 0, st>>>(
+                sb.n_loc, sb.row0, sb.n_groups, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz, t->d_tcb, t->par.tol, t->par.m_e, t->par.V0, sb.d_mask, t->d_tidx, pot,
+                t->d_cpq, t->d_cpcell, n_cells, t->d_cprof, dist);
+    };
+    with_dist(t, [&](auto dist) {
+        if (vec) walk(dist, std::true_type{}); else walk(dist, std::false_type{});
+    });
+    KMCF_HIP(hipGetLastError());
+    KMCF_TRY(kmcf_comm_allgatherv_double(c, t->d_cprof, t->cp_counts.data(), t->cp_displs.data()));
+    KMCF_HIP(hipEventRecord(c->ev_a1, st));
+    profile_bin_kernel<<<dim3(n_seg, n_cells + 1), KMCF_BLOCK, 0, st>>>(n_rows_atoms, seg_len, n_planes, n_cells, t->d_cpq, t->d_cpcell, t->d_cprof,
+                                                                         t->d_cppart);
+    profile_prefix_kernel<<<n_cells + 1, KMCF_BLOCK, 0, st>>>(n_seg, n_planes, t->d_cppart, t->d_cpout);
+    if (vec) profile_scatter_kernel<<<kmcf_grid1d(Na - 1), KMCF_BLOCK, 0, st>>>(Na - 1, t->d_atom_site, t->d_cprof, d_site_jx, d_site_jy, d_site_jz);
+    profile_stats_kernel<<<1, KMCF_BLOCK, 0, st>>>(Na - 1, n_planes, n_cells, t->d_cpout, t->d_cprof, vec ? 1 : 0, t->d_cpout + n_prof);
+    KMCF_HIP(hipGetLastError());
+    KMCF_HIP(hipMemcpyAsync(t->h_cpout, t->d_cpout, (n_prof + 8) * sizeof(double), hipMemcpyDeviceToHost, st));
+    KMCF_HIP(hipEventRecord(c->ev_t1, st));
+    KMCF_HIP(hipStreamSynchronize(st));
+    KMCF_TRY(kmcf_p2p_check(c));
+    memcpy(h_profile, t->h_cpout, n_prof * sizeof(double));
+    if (stats) {
+        const double *h = t->h_cpout + n_prof;
+        stats->i_injection = h[0];
+        stats->i_extraction = h[1];
+        stats->flux_min = h[2];
+        stats->flux_max = h[3];
+        stats->sum_jx = h[4];
+        stats->plane_min = (int)h[5];
+        stats->plane_max = (int)h[6];
+        float ms = 0.f;
+        KMCF_HIP(hipEventElapsedTime(&ms, c->ev_a0, c->ev_a1));
+        stats->ms_pairs = ms;
+        KMCF_HIP(hipEventElapsedTime(&ms, c->ev_a1, c->ev_t1));
+        stats->ms_planes = ms;
     }
     return KMCF_OK;
 }

@@ -128,6 +128,16 @@ class CurrentMapStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class CurrentProfileStats(C.Structure):
+    """kmcf_current_profile_stats_t"""
+    _fields_ = [("i_injection", C.c_double), ("i_extraction", C.c_double), ("flux_min", C.c_double),
+                ("flux_max", C.c_double), ("sum_jx", C.c_double), ("plane_min", C.c_int), ("plane_max", C.c_int),
+                ("ms_pairs", C.c_float), ("ms_planes", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 _P = C.c_void_p          # device or opaque pointer
 _IP = C.POINTER(C.c_int)
 _DP = C.POINTER(C.c_double)
@@ -211,6 +221,7 @@ SIGNATURES = {
     "kmcf_update_power_sparse": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, _P, _P, C.POINTER(CurrentParams),
                                            C.POINTER(C.c_double), C.POINTER(SolveStats)]),
     "kmcf_current_map": (C.c_int, [_P, _P, _P, _P, _P, C.POINTER(CurrentMapStats)]),
+    "kmcf_current_profile": (C.c_int, [_P, _P, _P, C.c_int, _DP, C.c_int, _DP, _P, _P, _P, C.POINTER(CurrentProfileStats)]),
     "kmcf_update_temperature_global": (C.c_int, [_P, _P, _P, C.c_int, C.c_double, C.c_double, C.c_double,
                                                  C.c_double, C.c_double]),
     "kmcf_update_temperature_local": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_double,

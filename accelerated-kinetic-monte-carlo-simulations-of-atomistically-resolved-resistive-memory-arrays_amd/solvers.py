@@ -377,6 +377,27 @@ def current_map(gpubuf, potentials=None, tunnel=True, net=True):
     return dict(current=cur, tunnel=tun, net=nt, stats=st.as_dict())
 
 
+def current_profile(gpubuf, planes, site_cell=None, n_cells=1, potentials=None, vector=False):
+    """kmcf_current_profile: the current through x-planes per cell and kind, and the per-site current vector
+    (definitions: include/kmcfield.h).  planes: strictly ascending x values (host); site_cell: N ints on the device or
+    None (one cell).  Returns dict(profile: ndarray [n_cells + 1, n_planes, 2] -- the last cell index is the rest, the
+    last axis neighbour / tunnel pairs --, jx / jy / jz: N doubles per site on the device or None, stats)."""
+    pot = gpubuf.atom_virtual_potentials if potentials is None else potentials
+    assert pot is None or pot.numel() == gpubuf.N_atom_ + 2, "potentials: N_atom + 2 doubles"
+    assert site_cell is None or (site_cell.numel() == gpubuf.N_ and site_cell.dtype == torch.int32), "site_cell: N int32"
+    x = np.ascontiguousarray(planes, np.float64).reshape(-1)
+    n_cells = int(n_cells)
+    prof = np.zeros((max(n_cells, 0) + 1, len(x), 2))
+    f64 = dict(dtype=torch.float64, device=gpubuf.device)
+    jx, jy, jz = (torch.empty(gpubuf.N_, **f64) for _ in range(3)) if vector else (None, None, None)
+    st = _L.CurrentProfileStats()
+    dp = C.POINTER(C.c_double)
+    _L.check(_L.load().kmcf_current_profile(gpubuf.T_distributed, _ptr(pot), _ptr(site_cell), n_cells, x.ctypes.data_as(dp),
+                                            len(x), prof.ctypes.data_as(dp), _ptr(jx), _ptr(jy), _ptr(jz), C.byref(st)),
+             "kmcf_current_profile")
+    return dict(profile=prof, jx=jx, jy=jy, jz=jz, stats=st.as_dict())
+
+
 def t_periodic(gpubuf):
     """kmcf_tstate_periodic: (pbc, lattice) the T state was built with -- (0, zeros) for a state of the plain call."""
     pbc, lat = C.c_int(-1), np.zeros(3)

@@ -951,6 +951,58 @@ int kmcf_current_map(kmcf_tstate *t, const double *d_atom_virtual_potentials,
                      double *d_site_current /* N, required */, double *d_site_tunnel /* N or NULL */,
                      double *d_site_net /* N or NULL */, kmcf_current_map_stats_t *stats /* or NULL */);
 
+/* Current profile: which cell carries the current, where along x it tunnels, which way it flows.
+ * Nodes, potentials m, PAIR and I_rc = g (m[r] - m[c]) are exactly kmcf_current_map's.  A COUNTED
+ * pair is a PAIR whose two ends are both atoms (nodes >= 2): pairs with a virtual end have no
+ * position and are left out.  x_a, y_a, z_a are the coordinates of atom a the state holds.
+ * Planes: h_plane_x[0 .. n_planes) strictly ascending and finite; q(a) = number of planes with
+ * X_k <= x_a (an atom on a plane lies to its right).  A directed counted pair r -> s CROSSES
+ * PLANE k FORWARD iff q(r) <= k < q(s); every pair is stored from both ends, only its left end
+ * counts it, once, with its sign.  x is never periodic, so this holds under periodic y-z too.
+ * Cells: cell(a) = d_site_cell[atom_site[a]]; the pair (r, s) belongs to cell c when
+ * cell(r) == cell(s) == c and 0 <= c < n_cells, every other counted pair to the REST, stored as
+ * cell index n_cells.  d_site_cell == NULL requires n_cells == 1 and puts every site in cell 0
+ * (kmcf_site_set_gap's convention).
+ * Profile: F[c][k][t] = sum of I_rs over the counted pairs of cell c and kind t (0 neighbour
+ * pairs, 1 tunnel pairs) that cross plane k forward; h_profile[((c * n_planes) + k) * 2 + t],
+ * c in [0, n_cells]; positive = flow towards +x.  It is formed per node: with S_a the sum of I_as
+ * over a's counted pairs (of one kind and bucket) that end in another slab, q(s) != q(a),
+ * F[c][k][t] = sum of S_a over the atoms of cell c with q(a) <= k (the rest over all atoms): pairs
+ * with both ends left of the plane cancel, pairs inside one slab are never added.
+ * Current vector: J_a = 1/2 sum_s I_as * d_as over the counted pairs of atom a, both kinds; d_as
+ * is the displacement from a to s: dx = x_s - x_a, and dy, dz likewise on an open state; on a
+ * periodic state f = (y_s - y_a) / Ly, f -= round(f), dy = f * Ly and z likewise (the library's
+ * one minimum image).  Each term is (g * (m_r - m_s)) * d, every operation rounded.  Three
+ * optional site arrays, N doubles each, zero-filled, then written at atom_site[a] for the atoms
+ * with a row; pass all three or none.  Units: A * Angstrom.
+ * Statistics: TOTAL[k] = sum over c = 0 .. n_cells, in that order, of (F[c][k][0] + F[c][k][1]).
+ * Contract as for kmcf_current_map: reads the state as the last assembly left it, changes scratch
+ * only, never touches site_power, the matrix or a tunnel storage; walks the pair bitmap, so it
+ * does not depend on the storage the solve chose; two calls on the same input return the same
+ * bytes (no atomics on doubles, every sum in an order the input fixes).  A periodic state uses
+ * its distance functor for the WKB value and the minimum image for d_as.  On a rank group every
+ * rank calls it: each forms the sums of its own rows, the per-node values are all-gathered by the
+ * row partition, every rank returns the complete profile and site arrays.
+ * KMCF_ERR_ARG (before anything needs a device; kmcf_last_error names the argument): NULL t,
+ * potentials, h_plane_x or h_profile; n_planes or n_cells outside 1 ... 1024; NULL d_site_cell
+ * with n_cells != 1; planes not finite or not strictly ascending; only some of the three vector
+ * arrays set.  KMCF_ERR_STATE: nothing assembled yet.  KMCF_ERR_COMM: communicator not connected. */
+typedef struct {
+    double i_injection, i_extraction;   /* as kmcf_current_map_stats_t */
+    double flux_min, flux_max;          /* smallest / largest TOTAL forward current over the planes
+                                           (all cells + rest, both kinds) */
+    double sum_jx;                      /* sum over atoms of jx; 0 when no vector was asked for */
+    int    plane_min, plane_max;        /* the planes that hold them, lowest index among equals */
+    float  ms_pairs, ms_planes;         /* device time: pair walk + gather / everything behind; this rank */
+} kmcf_current_profile_stats_t;
+
+int kmcf_current_profile(kmcf_tstate *t, const double *d_atom_virtual_potentials,
+                         const int *d_site_cell /* N, or NULL */, int n_cells,
+                         const double *h_plane_x /* n_planes, host */, int n_planes,
+                         double *h_profile /* (n_cells + 1) * n_planes * 2, host, required */,
+                         double *d_site_jx, double *d_site_jy, double *d_site_jz /* N each, or all NULL */,
+                         kmcf_current_profile_stats_t *stats /* or NULL */);
+
 /* update_temperatureglobal_gpu (src/heat_solver_gpu.cu:53-70). */
 int kmcf_update_temperature_global(kmcf_comm *c, const double *d_site_power, double *d_T_bg, int N,
                                    double a_coeff, double b_coeff, double number_steps,

@@ -4,7 +4,7 @@ boundary (K) solve, pairwise term, sum/gather, KMC events -- with the per-module
 prints into output<size>_<rank>.txt ("Z - calculation time - ...").
 
     python tools/kmc_loop.py [--workload 5nm|5nm-periodic|40nm|conducting] [--steps 6] [--T 300] [--current] [--rate-mode bg|ekin|site]
-                             [--clusters] [--current-map] [--scheme all|half|third --select W,B] [--gap R]
+                             [--clusters] [--current-map] [--current-profile N] [--scheme all|half|third --select W,B] [--gap R]
                              [--chain R [--chain-hops K]]
 
 --current adds the electro-thermal stages after the potential and before the events: conduction-band edge, current
@@ -19,7 +19,11 @@ pair rule and WKB distance, the current map); the step line is the one of `5nm`.
 current solve; the step line gains `clusters <ms> (<vacancy clusters> vac, largest <sites>, bridging <filaments>)`, the
 time in milliseconds of device time.  --current-map (with --current) runs the site-resolved current map (kmcf_current_map)
 after the power update of every step: the step line gains `current map <ms> (tunnel share <sum_tunnel / sum_through>, max
-<max_through> at site <max_site>)`, the time again in milliseconds of device time.  --scheme all | half | third with --select W,B
+<max_through> at site <max_site>)`, the time again in milliseconds of device time.  --current-profile N (with --current) runs
+the current profile (kmcf_current_profile) next to it: N planes equally spaced strictly between the x of the left and the
+right contact blocks, cells from structure.crossbar_lines on the crossbar workloads (one cell otherwise).  Below the step line
+it prints, per cell and for the rest, the current through the middle plane, its tunnel share and the range of planes whose
+tunnel share exceeds one half, then `flux <flux_min> .. <flux_max> against I_macro <I_macro>` and the two device times.  --scheme all | half | third with --select W,B
 (the synthetic crossbars only) drives the array per line instead of with one scalar Vd: the contact slots of the potential
 array are filled once by structure.bias_scheme (selected word line -Vd/2, selected bit line +Vd/2, the others by the scheme),
 the boundary solve is kmcf_background_potential_sparse_contacts, and the step line gains `events per cell [c0 c1 ...]`: the
@@ -66,6 +70,8 @@ def main():
                     help="conductive cluster analysis after every charge update: vacancy clusters, the largest, bridging filaments")
     ap.add_argument("--current-map", action="store_true",
                     help="site-resolved current map after every power update (needs --current): tunnel share, the busiest site")
+    ap.add_argument("--current-profile", type=int, default=0, metavar="N",
+                    help="current through N x-planes between the contacts per crossbar cell and pair kind (needs --current)")
     ap.add_argument("--scheme", default=None, choices=["all", "half", "third"],
                     help="per-line bias of the crossbar (synthetic workloads): all cells selected | V/2 scheme | V/3 scheme")
     ap.add_argument("--select", default="0,0", help="W,B: the selected word line and bit line of --scheme")
@@ -82,6 +88,10 @@ def main():
         ap.error("--scheme needs a crossbar with lines: --workload 40nm or conducting")
     if a.current_map and not a.current:
         ap.error("--current-map needs --current (the map reads the potentials of the current solve)")
+    if a.current_profile and not a.current:
+        ap.error("--current-profile needs --current (the profile reads the potentials of the current solve)")
+    if not 0 <= a.current_profile <= 1024:
+        ap.error("--current-profile N: 1 ... 1024 planes")
     if a.gap is not None and not 0.0 < a.gap <= 20.0:
         ap.error("--gap %g: the search radius is > 0 and at most 20 (the cell edge of the spatial index)" % a.gap)
     if a.chain is not None and not 0.0 < a.chain <= 20.0:
@@ -135,6 +145,13 @@ def main():
             ap.error("--select %s: %s" % (a.select, str(e) or "W,B expected"))
         cell_of_site = km.structure.crossbar_lines(d)[2]
         buf.site_potential_boundary.copy_(torch.as_tensor(contacts))      # once: the solve reads the slots, never writes them
+    prof_cells, n_prof_cells, prof_planes = None, 1, None
+    if a.current_profile:
+        x_l, x_r = float(d["xyz"][:NL, 0].max()), float(d["xyz"][N - NL:, 0].min())       # the facing ends of the contact blocks
+        prof_planes = x_l + (x_r - x_l) * np.arange(1, a.current_profile + 1) / (a.current_profile + 1)
+        if a.workload not in ("5nm", "5nm-periodic"):
+            cells = km.structure.crossbar_lines(d)[2] if cell_of_site is None else cell_of_site
+            prof_cells, n_prof_cells = torch.as_tensor(np.ascontiguousarray(cells, np.int32), device="cuda"), int(cells.max()) + 1
     gap_cells, n_gap_cells, gap_bins = None, 1, None
     if a.gap is not None or a.chain is not None:
         if a.workload not in ("5nm", "5nm-periodic"):
@@ -219,6 +236,20 @@ def main():
                 cm = S.current_map(buf, tunnel=False, net=False)["stats"]
                 clusters += " | current map %.3f (tunnel share %.4f, max %.4e at site %d)" % (
                     cm["ms"], cm["sum_tunnel"] / cm["sum_through"] if cm["sum_through"] > 0 else 0.0, cm["max_through"], cm["max_site"])
+            profile_lines = []
+            if a.current_profile:
+                cp = S.current_profile(buf, prof_planes, site_cell=prof_cells, n_cells=n_prof_cells)
+                F, mid = cp["profile"], a.current_profile // 2
+                for c in range(n_prof_cells + 1):
+                    tot = F[c].sum(1)
+                    share = np.divide(F[c][:, 1], tot, out=np.zeros_like(tot), where=tot != 0)
+                    tun = np.flatnonzero(share > 0.5)
+                    profile_lines.append("  %-7s I(plane %d) %+.4e  tunnel share %.4f  tunnels at planes %s" % (
+                        "rest" if c == n_prof_cells else "cell %d" % c, mid, tot[mid], share[mid],
+                        "%d..%d (x %.2f..%.2f A, %d planes)" % (tun[0], tun[-1], prof_planes[tun[0]], prof_planes[tun[-1]], len(tun)) if len(tun) else "none"))
+                ps = cp["stats"]
+                profile_lines.append("  flux %.6e (plane %d) .. %.6e (plane %d) against I_macro %.6e | pairs %.3f ms, planes %.3f ms" % (
+                    ps["flux_min"], ps["plane_min"], ps["flux_max"], ps["plane_max"], imacro, ps["ms_pairs"], ps["ms_planes"]))
             th, ht = timed(lambda: S.update_temperature_local_gpu(buf, N, NL, NL, 1e-6, heat))      # steady state
             if a.rate_mode != "bg":
                 thermal = dict(site_temperature=buf.site_temperature, rate_mode=a.rate_mode)
@@ -256,6 +287,8 @@ def main():
                                                          st_t["iterations"], imacro, th, ht["stats"]["iterations"],
                                                          float(buf.site_temperature.max()), a.rate_mode, te, ev[1],
                                                          tc + tb + tp + tg + tcb + tpw + th + te, kmc_time, clusters), flush=True)
+            for line in profile_lines:
+                print(line, flush=True)
             continue
         print("step %d: charge %.6f | boundary %.6f (%d it) | pairwise %.6f | gather %.6f | events %.6f (%d ev) | "
               "superstep %.6f | KMC time %.5e%s" % (step + 1, tc, tb, st["iterations"], tp, tg, te, ev[1],
