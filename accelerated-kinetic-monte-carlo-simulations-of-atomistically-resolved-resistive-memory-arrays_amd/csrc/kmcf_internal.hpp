@@ -136,6 +136,8 @@ struct kmcf_comm {
     struct kmcf_event_cache *ev_cache = nullptr;
     // workspace of kmcf_conductive_clusters (kmcf_clusters.hip): buffers only, no result outlives a call
     struct kmcf_cluster_ws *cl_ws = nullptr;
+    // scratch of kmcf_site_gradient (kmcf_gradient.hip): buffers only
+    struct kmcf_gradient_ws *gr_ws = nullptr;
     // geometry of the event step's pair distance (kmcf_events_set_lattice): 1 = minimum image in y and z with these periods.
     // Plain values: kmcf_events_reset leaves them, they go with the communicator
     int ev_pbc = 0;
@@ -164,6 +166,7 @@ inline bool kmcf_trace(const kmcf_comm *c) { return kmcf_opt_set(c, KNOB_TRACE);
 uint32_t kmcf_group_knob_hash(const kmcf_comm *c, kmcf_knob_id k);
 void kmcf_event_cache_free(kmcf_comm *c);
 void kmcf_cluster_ws_free(kmcf_comm *c);
+void kmcf_gradient_ws_free(kmcf_comm *c);
 
 // clusters.hip: the cluster pass of kmcf_conductive_clusters (its arguments, already checked; kmcf_enter done) enqueued on
 // the compute stream, nothing waited for and nothing copied.  Hands back where the results lie on the device: the class

@@ -118,6 +118,22 @@ class ChainStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class GradientCell(C.Structure):
+    """kmcf_gradient_cell_t"""
+    _fields_ = [("n_sites", C.c_int), ("n_full", C.c_int), ("g_max", C.c_double), ("g_site", C.c_int),
+                ("drop_max", C.c_double), ("drop_from", C.c_int), ("drop_to", C.c_int)]
+
+
+class GradientStats(C.Structure):
+    """kmcf_gradient_stats_t"""
+    _fields_ = [("n_sites", C.c_int), ("n_full", C.c_int), ("n_degenerate", C.c_int), ("pairs", C.c_int64),
+                ("g_max", C.c_double), ("g_site", C.c_int), ("drop_max", C.c_double), ("drop_from", C.c_int),
+                ("drop_to", C.c_int), ("ms", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class CurrentMapStats(C.Structure):
     """kmcf_current_map_stats_t"""
     _fields_ = [("i_injection", C.c_double), ("i_extraction", C.c_double), ("sum_through", C.c_double),
@@ -256,6 +272,8 @@ SIGNATURES = {
                                           C.c_int, C.POINTER(ChainStats)]),
     "kmcf_filament_chain_pbc": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_double, _P,
                                           C.c_int, C.POINTER(Chain), C.POINTER(Hop), C.c_int, _P, _P, C.POINTER(ChainStats)]),
+    "kmcf_site_gradient": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _DP, C.c_int, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P,
+                                     _P, C.POINTER(GradientCell), C.POINTER(GradientStats)]),
     "kmcf_neighbor_list":(C.c_int, [_P, _P, _P, _P, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _P]),
     "kmcf_neighbor_list_pbc": (C.c_int, [_P, _P, _P, _P, C.c_int, _DP, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _P]),
 }

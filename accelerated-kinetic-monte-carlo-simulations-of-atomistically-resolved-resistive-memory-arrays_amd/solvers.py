@@ -837,6 +837,53 @@ def filament_chain(kmc_comm, gpubuf, N_left_tot, N_right_tot, r_max, site_cell=N
     return dict(chains=chains, hops=hops, side=side, node=node, stats=st.as_dict())
 
 
+GRADIENT_CELL_DTYPE = np.dtype([("n_sites", np.int32), ("n_full", np.int32), ("g_max", np.float64), ("g_site", np.int32),
+                                ("drop_max", np.float64), ("drop_from", np.int32), ("drop_to", np.int32)],
+                               align=True)                                     # kmcf_gradient_cell_t
+
+
+def site_gradient(kmc_comm, gpubuf, value, mask=None, site_cell=None, n_cells=1, periodic=False, nn=None):
+    """kmcf_site_gradient on the buffers' whole-device neighbour list: per site the least-squares gradient of `value` over
+    the counted pairs of its row and the largest bond drop, with the maxima per cell (definitions: include/kmcfield.h).
+    value: N doubles on the device; mask: int32 device tensor of N entries (0: the site is left out) or None; site_cell:
+    int32 tensor or array of N entries (values outside [0, n_cells): no cell), or None with n_cells == 1.  periodic=True:
+    the minimum image in y and z with the periods of gpubuf.lattice_host (build the list with compute_neighbor_list(pbc=1)
+    as well).  nn: slots per row of gpubuf.neigh_idx (default gpubuf.nn_).  Returns dict(gx, gy, gz, drop: N doubles,
+    drop_to, full: N int32, all on the device; cells: numpy structured array GRADIENT_CELL_DTYPE of n_cells records;
+    stats: dict)."""
+    N = gpubuf.N_
+    nn = gpubuf.nn_ if nn is None else int(nn)
+    assert gpubuf.neigh_idx is not None and gpubuf.neigh_idx.numel() == N * nn, \
+        "site_gradient needs the neighbour list of the whole device (N * nn entries)"
+    assert value.dtype == torch.float64 and value.numel() == N, "value: N doubles"
+    assert mask is None or (mask.dtype == torch.int32 and mask.numel() == N), "mask: N int32 entries"
+    cell = _gap_cells(gpubuf, site_cell, n_cells)
+    f64 = dict(dtype=torch.float64, device=gpubuf.device)
+    i32 = dict(dtype=torch.int32, device=gpubuf.device)
+    gx, gy, gz, drop = (torch.empty(N, **f64) for _ in range(4))
+    drop_to, full = torch.empty(N, **i32), torch.empty(N, **i32)
+    cells = np.zeros(int(n_cells), GRADIENT_CELL_DTYPE)
+    st = _L.GradientStats()
+    lat, latp = _da(gpubuf.lattice_host)
+    _L.check(_L.load().kmcf_site_gradient(kmc_comm.handle, N, nn, _ptr(gpubuf.neigh_idx), _ptr(gpubuf.site_x),
+                                          _ptr(gpubuf.site_y), _ptr(gpubuf.site_z), latp, 1 if periodic else 0, _ptr(value),
+                                          _ptr(mask), _ptr(cell), int(n_cells), _ptr(gx), _ptr(gy), _ptr(gz), _ptr(drop),
+                                          _ptr(drop_to), _ptr(full), cells.ctypes.data_as(C.POINTER(_L.GradientCell)),
+                                          C.byref(st)), "kmcf_site_gradient")
+    return dict(gx=gx, gy=gy, gz=gz, drop=drop, drop_to=drop_to, full=full, cells=cells, stats=st.as_dict())
+
+
+def field_map(kmc_comm, gpubuf, potential=None, mask=None, site_cell=None, n_cells=1, periodic=False, nn=None):
+    """The electric field at every site: site_gradient of the site potential the events read -- site_potential_boundary +
+    site_potential_charge (background_potential_gpu_sparse and poisson_gridless_gpu first), or `potential` (N doubles on
+    the device) -- and E = -g.  Returns site_gradient's dict with Ex, Ey, Ez (N doubles on the device) and `potential`
+    added; g_max in cells and stats is the largest |E|, drop the largest potential difference per length of a bond."""
+    pot = gpubuf.site_potential_boundary + gpubuf.site_potential_charge if potential is None else potential
+    out = site_gradient(kmc_comm, gpubuf, pot, mask=mask, site_cell=site_cell, n_cells=n_cells, periodic=periodic, nn=nn)
+    out.update(Ex=-out["gx"], Ey=-out["gy"], Ez=-out["gz"], potential=pot)
+    return out
+
+
 def k_assemble(gpubuf, Vd, high_G, low_G):
     lib = _L.load()
     _L.check(lib.kmcf_k_assemble(gpubuf.K_distributed, _ptr(gpubuf.site_element), _ptr(gpubuf.site_charge),

@@ -794,6 +794,72 @@ int kmcf_filament_chain_pbc(kmcf_pairwise *p, int nn, const int *d_neigh_idx, co
                             kmcf_chain_stats_t *stats);
 
 /* ---------------------------------------------------------------------- */
+/* Site gradient map: the local gradient of a site field (the potential the events read, the band edge, the site
+ * temperature) and the largest bond drop per site, with their maxima per cell and for the device.  The reference has no
+ * counterpart.
+ * IN: site i is in when d_site_mask is NULL or d_site_mask[i] != 0.
+ * COUNTED PAIRS of an in site i: the slots s = 0 ... nn-1 of row i of d_neigh_idx, in slot order, whose entry j meets all
+ * of: 0 <= j < N (anything else is padding, as for kmcf_conductive_clusters); j != i; j is in; |d_ij| > 0 (coincident
+ * sites -- the 5 nm example holds one such pair -- contribute nothing).  ONLY ROW i IS READ: a truncated, one-sided list
+ * gives one-sided pairs; an entry that occurs twice in the row counts twice.
+ * Displacement d_ij from i to j: open (pbc == 0) the plain difference (x_j - x_i, y_j - y_i, z_j - z_i); pbc == 1: x the
+ * plain difference, y and z the library's one minimum image, f = (y_j - y_i) / Ly, f -= round(f), dy = f * Ly (the C round;
+ * Ly = h_lattice[1], Lz = h_lattice[2]).  |d| = sqrt((dx dx + dy dy) + dz dz); u = d / |d| per component;
+ * q_ij = (value[j] - value[i]) / |d|.  Every operation is rounded on its own (no contraction).
+ * Gradient: M = sum u u^T (3 x 3 symmetric), b = sum u q, n_i = number of counted pairs.  The site is FULL iff n_i >= 3
+ * and det(M) >= 1e-9 * (n_i / 3)^3 (the trace of M is n_i, so det(M) / (n_i / 3)^3 lies in [0, 1]; a plane or a line of
+ * neighbours gives 0 up to rounding).  A full site gets g = M^-1 b -- the least-squares gradient of the pairs with weights
+ * 1 / |d|^2 -- as the closed-form symmetric inverse: the cofactors c00 = m11 m22 - m12 m12, c01 = m02 m12 - m01 m22,
+ * c02 = m01 m12 - m02 m11, c11 = m00 m22 - m02 m02, c12 = m01 m02 - m00 m12, c22 = m00 m11 - m01 m01,
+ * det = (m00 c00 + m01 c01) + m02 c02, g_x = ((c00 b0 + c01 b1) + c02 b2) / det and g_y, g_z alike.  A site that is not
+ * full gets g = 0 and full = 0.  |g| = sqrt((gx gx + gy gy) + gz gz).
+ * Drop: drop[i] = max over the counted pairs of |q_ij|, drop_to[i] = the j of the FIRST slot that attains it (a |q| that
+ * is not a number attains nothing); a site without such a pair gets 0 and -1.
+ * Sites that are not in get 0 / 0 / 0 / 0 / -1 / 0 in whichever of gx, gy, gz, drop, drop_to, full are given.
+ * Order of addition (fixed by the input): 16 lanes work on a site; lane l adds the terms of its slots l, l + 16, l + 32, ...
+ * in ascending order, starting from zero, and keeps its largest |q| (first slot among equals); then four butterfly steps
+ * t = 8, 4, 2, 1 in which every lane replaces each of its sums s by s + (the sum lane l xor t holds), and its largest |q|
+ * by the other lane's if that is larger, or equal with the lower slot.  Lane 0 solves.
+ * Cells: d_site_cell == NULL requires n_cells == 1 and puts every site in cell 0 (kmcf_site_set_gap's convention).  A site
+ * whose cell is outside [0, n_cells) gets its outputs and enters the whole-device statistics, but no cell record.
+ * Maxima (per cell in h_cells, over all in sites in stats): a value that is not finite enters no maximum; a site without
+ * a counted pair is no candidate for the largest drop; g_max / drop_max are the bits of a per-site output (a selection,
+ * not a sum); among equal |g| the smallest site id is g_site, among equal drops the smallest drop_from wins (drop_to is
+ * that site's drop_to); without a candidate the value is 0 and the ids are -1.
+ * n_degenerate: the in sites with n_i >= 3 that fail the determinant test; pairs: sum of n_i over the in sites.
+ * Two calls on the same input return the same bytes: no atomics on doubles, every sum in the order above; maxima, ties and
+ * counts are integer atomics.  pbc == 0: h_lattice is ignored, the bytes are the same whether it is NULL or set.
+ * Scope: a local operation on the whole-device list, like kmcf_conductive_clusters: no collectives; in a rank group every
+ * rank that wants the result calls it.  Scratch lives on the communicator.  The call synchronises once, at its end; ms
+ * is the device time of everything it enqueued (HIP events).
+ * KMCF_ERR_ARG (before anything needs a device; kmcf_last_error names the argument): NULL c, d_neigh_idx, d_x, d_y, d_z or
+ * d_value; N <= 0 or nn <= 0; pbc outside 0 / 1; with pbc == 1 a NULL h_lattice or a y or z period that is not finite or
+ * <= 0; n_cells outside 1 ... 1024; NULL d_site_cell with n_cells != 1; only some of d_gx / d_gy / d_gz set; no output
+ * requested at all.  KMCF_ERR_STATE: host-only communicator. */
+/* ---------------------------------------------------------------------- */
+typedef struct {            /* one per cell, 40 bytes */
+    int n_sites, n_full;    /* in sites of the cell; those with a full-rank gradient */
+    double g_max;  int g_site;               /* largest |g|; smallest site id among equals; -1 if none */
+    double drop_max; int drop_from, drop_to; /* largest drop; smallest drop_from among equals; -1/-1 if none */
+} kmcf_gradient_cell_t;
+typedef struct {
+    int n_sites, n_full, n_degenerate;  int64_t pairs;   /* counted pairs, all in sites */
+    double g_max; int g_site; double drop_max; int drop_from, drop_to;   /* over all in sites */
+    float ms;
+} kmcf_gradient_stats_t;
+
+int kmcf_site_gradient(kmcf_comm *c, int N, int nn, const int *d_neigh_idx /* N*nn */,
+                       const double *d_x, const double *d_y, const double *d_z,
+                       const double *h_lattice /* 3, host; may be NULL with pbc == 0 */, int pbc,
+                       const double *d_value /* N */, const int *d_site_mask /* N or NULL */,
+                       const int *d_site_cell /* N or NULL */, int n_cells,
+                       double *d_gx, double *d_gy, double *d_gz /* N each; all three or none */,
+                       double *d_site_drop /* N or NULL */, int *d_site_drop_to /* N or NULL */,
+                       int *d_site_full /* N or NULL */,
+                       kmcf_gradient_cell_t *h_cells /* n_cells, or NULL */,
+                       kmcf_gradient_stats_t *stats /* or NULL */);
+
+/* ---------------------------------------------------------------------- */
 /* T path: current solve (Kirchhoff matrix with two virtual nodes + WKB       */
 /* tunnelling sub-block), SURVEY 8 rows a14 / f3.  PARITY UNPINNED: no         */
 /* reference fixture exercises it (src/KMC_comm.h:243 disables it from main).  */

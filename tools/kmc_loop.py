@@ -5,7 +5,7 @@ prints into output<size>_<rank>.txt ("Z - calculation time - ...").
 
     python tools/kmc_loop.py [--workload 5nm|5nm-periodic|40nm|conducting] [--steps 6] [--T 300] [--current] [--rate-mode bg|ekin|site]
                              [--clusters] [--current-map] [--current-profile N] [--scheme all|half|third --select W,B] [--gap R]
-                             [--chain R [--chain-hops K]]
+                             [--chain R [--chain-hops K]] [--field-map]
 
 --current adds the electro-thermal stages after the potential and before the events: conduction-band edge, current
 solve with heating (site_power), local heat solve (site_temperature); --rate-mode ekin | site lets the event rates read
@@ -41,7 +41,12 @@ side through the floating conductive clusters whose longest hop is as short as a
 (at most 20).  The step line gains `chain <ms clusters>+<ms search>
 (<rounds> rounds, <surface sites> surface) [<cell>: <hops> hops, longest <hop_max> A (<from>-<to>), length <length> A,
 direct <sqrt(direct2)> A, <stones> stones | <cell>: bridged | <cell>: open, .. stones | <cell>: none]`; --chain-hops K also
-lists the first K hops of every chain as `<from>-<to> <hop> A`.
+lists the first K hops of every chain as `<from>-<to> <hop> A`.  --field-map runs the site gradient map
+(kmcf_site_gradient through solvers.field_map) on the potential the events read, after the sum / gather of every step: below
+the step line it prints, per cell of structure.crossbar_lines on the crossbar workloads (one cell otherwise), `field <cell>:
+|E| max <V/A> at site <site> = <ratio> x mean | drop <V/A> (<from>-<to>) | <full>/<sites> full` -- the mean field is
+|Vd| / (x extent of the interface) -- and the device time; with --current the same for the site temperature of the heat
+solve (`grad T`, K/A, no ratio).  On `5nm-periodic` the displacement is the minimum image.
 """
 import argparse
 import os
@@ -82,6 +87,9 @@ def main():
                     help="tunnelling-chain analysis after every charge update, hops of at most R angstrom (<= 20): the "
                          "stepping-stone chain between the electrode sides per crossbar cell, its longest hop and length")
     ap.add_argument("--chain-hops", type=int, default=0, metavar="K", help="with --chain: list the first K hops of every chain")
+    ap.add_argument("--field-map", action="store_true",
+                    help="site gradient map of the potential after every sum / gather: largest |E| and bond drop per crossbar "
+                         "cell, against the mean field; with --current also of the site temperature")
     a = ap.parse_args()
     periodic = a.workload == "5nm-periodic"
     if a.scheme and a.workload in ("5nm", "5nm-periodic"):
@@ -160,6 +168,29 @@ def main():
         if a.clusters and a.gap is not None:
             x_lo, x_hi = float(d["xyz"][:, 0].min()), float(d["xyz"][:, 0].max()) + 1e-6
             gap_bins = (int(np.ceil((x_hi - x_lo) / 3.2)), x_lo, x_hi)
+    field_cells, n_field_cells, mean_field = None, 1, 0.0
+    if a.field_map:
+        if a.workload not in ("5nm", "5nm-periodic"):
+            cells = km.structure.crossbar_lines(d)[2] if cell_of_site is None else cell_of_site
+            field_cells, n_field_cells = torch.as_tensor(np.ascontiguousarray(cells, np.int32), device="cuda"), int(cells.max()) + 1
+        x_if = d["xyz"][NL:N - NL, 0]
+        mean_field = abs(d["Vd"]) / float(x_if.max() - x_if.min())
+
+    def gradient_lines(what, unit, value, scale):
+        """the per-cell lines of one site field"""
+        fn = S.field_map if scale > 0 else S.site_gradient              # (|E| = |g|: the tables are the same)
+        gm = fn(comm, buf, value, site_cell=field_cells, n_cells=n_field_cells, periodic=periodic)
+        out = []
+        for c, r in enumerate(gm["cells"]):
+            ratio = " = %.2f x mean" % (r["g_max"] / scale) if scale > 0 else ""
+            out.append("  %s cell %d: max %.5e %s at site %d%s | drop %.5e %s (%d-%d) | %d/%d full" % (
+                what, c, r["g_max"], unit, r["g_site"], ratio, r["drop_max"], unit, r["drop_from"], r["drop_to"], r["n_full"],
+                r["n_sites"]))
+        st_g = gm["stats"]
+        out.append("  %s device: max %.5e %s at site %d | %d pairs, %d degenerate sites | %.3f ms" % (
+            what, st_g["g_max"], unit, st_g["g_site"], st_g["pairs"], st_g["n_degenerate"], st_g["ms"]))
+        return out
+
     comm.sync()
     print("init [s] %.3f  (sites %d)" % (time.perf_counter() - t0, N))
     kmc_time = 0.0
@@ -225,6 +256,8 @@ def main():
                                                                      d["low_G"], d["nn_dist"], len(d["metals"]), step))
         tp, _ = timed(lambda: S.poisson_gridless_gpu(buf, comm))
         tg, _ = timed(lambda: S.sum_and_gather_potential(buf, NL, comm))
+        # (site_potential_charge now holds boundary + charge: the potential the events read; |g| of it is |E|)
+        field_lines = gradient_lines("field |E|", "V/A", buf.site_potential_charge, mean_field) if a.field_map else []
         thermal = {}
         if a.current:
             tcb, st_cb = timed(lambda: S.update_CB_edge_gpu_sparse(buf, N, NL, NL, d["Vd"], d["pbc"], d["high_G"], d["low_G"],
@@ -251,6 +284,8 @@ def main():
                 profile_lines.append("  flux %.6e (plane %d) .. %.6e (plane %d) against I_macro %.6e | pairs %.3f ms, planes %.3f ms" % (
                     ps["flux_min"], ps["plane_min"], ps["flux_max"], ps["plane_max"], imacro, ps["ms_pairs"], ps["ms_planes"]))
             th, ht = timed(lambda: S.update_temperature_local_gpu(buf, N, NL, NL, 1e-6, heat))      # steady state
+            if a.field_map:
+                field_lines += gradient_lines("grad T", "K/A", buf.site_temperature, 0.0)
             if a.rate_mode != "bg":
                 thermal = dict(site_temperature=buf.site_temperature, rate_mode=a.rate_mode)
         te, ev = timed(lambda: S.execute_kmc_step_mpi(comm, N, comm.counts_events, comm.displs_events, 52, buf.neigh_idx,
@@ -287,12 +322,14 @@ def main():
                                                          st_t["iterations"], imacro, th, ht["stats"]["iterations"],
                                                          float(buf.site_temperature.max()), a.rate_mode, te, ev[1],
                                                          tc + tb + tp + tg + tcb + tpw + th + te, kmc_time, clusters), flush=True)
-            for line in profile_lines:
+            for line in profile_lines + field_lines:
                 print(line, flush=True)
             continue
         print("step %d: charge %.6f | boundary %.6f (%d it) | pairwise %.6f | gather %.6f | events %.6f (%d ev) | "
               "superstep %.6f | KMC time %.5e%s" % (step + 1, tc, tb, st["iterations"], tp, tg, te, ev[1],
                                                      tc + tb + tp + tg + te, kmc_time, clusters), flush=True)
+        for line in field_lines:
+            print(line, flush=True)
     buf.freeGPUmemory()
     comm.close()
 
