@@ -795,12 +795,13 @@ static int cgr_plan(kmcf_matrix *m)
     KMCF_HIP(hipHostMalloc(reinterpret_cast<void **>(&g->h_err), sizeof(int), hipHostMallocDefault));
     *g->h_err = 0;
     // granules never carry sequence number 0: everything starts cleared (the zones in the peer-to-peer window were
-    // cleared when the matrix was built, kmcf_p2p_matrix_alloc)
-    KMCF_HIP(hipMemset(g->d_zll, 0, 2 * g->zwords * sizeof(u64)));
-    KMCF_HIP(hipMemset(g->d_slot, 0, 2 * (size_t)g->nblocks * CGR_LINE * sizeof(u64)));
-    KMCF_HIP(hipMemset(g->d_gslot, 0, 2 * (size_t)g->ngroups * CGR_LINE * sizeof(u64)));
-    KMCF_HIP(hipMemset(g->d_seq, 0, sizeof(unsigned int)));
-    KMCF_HIP(hipMemset(g->d_err, 0, sizeof(int)));
+    // cleared when the matrix was built, kmcf_p2p_matrix_alloc).  On the compute stream, in front of the launch that reads
+    // them: a hipMemset runs on the null stream, which nothing orders the compute stream behind.
+    KMCF_HIP(hipMemsetAsync(g->d_zll, 0, 2 * g->zwords * sizeof(u64), c->stream));
+    KMCF_HIP(hipMemsetAsync(g->d_slot, 0, 2 * (size_t)g->nblocks * CGR_LINE * sizeof(u64), c->stream));
+    KMCF_HIP(hipMemsetAsync(g->d_gslot, 0, 2 * (size_t)g->ngroups * CGR_LINE * sizeof(u64), c->stream));
+    KMCF_HIP(hipMemsetAsync(g->d_seq, 0, sizeof(unsigned int), c->stream));
+    KMCF_HIP(hipMemsetAsync(g->d_err, 0, sizeof(int), c->stream));
     g->seq_bound = 0;
     return KMCF_OK;
 }

@@ -336,6 +336,20 @@ int kmcf_enter(kmcf_comm *c)
     return KMCF_OK;
 }
 
+// Set-up entry points (cell lists, patterns, neighbour lists: once per device) copy the caller's arrays to the host with
+// synchronous copies.  Those run on the null stream, which waits for no non-blocking stream -- and torch creates every
+// torch.cuda.Stream() non-blocking -- so the event of kmcf_enter, which orders the COMPUTE stream, does not order them: a
+// host copy read the coordinates as they were before the caller's queued kernels wrote them, while the pattern and list
+// kernels -- launched on kmcf_setup_stream(c), which IS the caller's stream (kmcf_internal.hpp), not on the compute
+// stream -- ran behind the caller's queue and read them afterwards (tests/test_gpu_stream_order.py).  These entry points wait for the
+// caller's stream on the host.  Not for per-step entry points: they keep kmcf_enter and its idle shortcut.
+int kmcf_enter_setup(kmcf_comm *c)
+{
+    KMCF_TRY(kmcf_enter(c));
+    KMCF_HIP(hipStreamSynchronize(c->caller_stream));
+    return KMCF_OK;
+}
+
 // ------------------------------------------------------------------ loopback transport (tests)
 namespace {
 

@@ -185,11 +185,17 @@ int kmcf_clusters_enqueue(kmcf_comm *c, int N, int nn, const int *d_neigh_idx, c
 
 // ---------------------------------------------------------------- device buffers and 1-D grids
 // n elements, zeroed on request.  The one place that calls hipMalloc for a typed buffer.
+// fill_stream: the stream the zero fill is queued on.  Without one the fill is a hipMemset, an operation on the legacy null
+// stream -- the caller's stream unless another was declared -- that does not wait on the host: the entry point then
+// returns with the fill on the caller's stream (hipStreamQuery there: not ready, tests/test_gpu_stream_order.py), and
+// nothing orders a non-blocking stream behind it.  With one (the communicator's compute stream) the fill is in order with
+// the kernels of that stream; a buffer that another stream touches first needs that stream synchronised by the caller.
 template <typename T>
-int kmcf_dev_alloc(T **d, size_t n, bool zero)
+int kmcf_dev_alloc(T **d, size_t n, bool zero, hipStream_t fill_stream = nullptr)
 {
     KMCF_HIP(hipMalloc(reinterpret_cast<void **>(d), n * sizeof(T)));
-    if (zero) KMCF_HIP(hipMemset(*d, 0, n * sizeof(T)));
+    if (zero && fill_stream) KMCF_HIP(hipMemsetAsync(*d, 0, n * sizeof(T), fill_stream));
+    else if (zero) KMCF_HIP(hipMemset(*d, 0, n * sizeof(T)));
     return KMCF_OK;
 }
 
@@ -681,6 +687,9 @@ int kmcf_jacobi_cg_workspace_absolute(kmcf_matrix *m, double tol, int max_iterat
 // the work the caller has queued so far (buffers filled by kernels or async copies still in flight on the
 // caller's stream are complete before any library kernel reads them).
 int kmcf_enter(kmcf_comm *c);
+// kmcf_enter for the set-up entry points that read the caller's arrays through synchronous host copies: also waits, on
+// the host, until the caller's stream has finished what was queued on it
+int kmcf_enter_setup(kmcf_comm *c);
 int kmcf_comm_allreduce_sum(kmcf_comm *c, double *d_buf, int count);
 // In-process groups on the peer-to-peer transport only (ranks = host threads sharing ONE GPU, a test device): the
 // members meet on the host before an exchange whose kernels wait for each other on the device.  A member that is

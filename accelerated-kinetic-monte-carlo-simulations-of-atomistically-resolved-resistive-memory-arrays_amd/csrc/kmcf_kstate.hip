@@ -427,7 +427,7 @@ extern "C" int kmcf_initialize_sparsity_K(kmcf_comm *c, const double *d_x, const
                "kmcf_initialize_sparsity_K: null argument");
     KMCF_CHECK(c->device >= 0, KMCF_ERR_STATE, "kmcf_initialize_sparsity_K: host-only communicator");
     KMCF_CHECK(N > 2 * N_contact && N_contact >= 0, KMCF_ERR_ARG, "kmcf_initialize_sparsity_K: N=%d, N_contact=%d", N, N_contact);
-    KMCF_TRY(kmcf_enter(c));
+    KMCF_TRY(kmcf_enter_setup(c));
     const int N_left = N_contact, N_right = N_contact;
     const int N_interface = N - (N_left + N_right);             // iterative_solvers_gpu.cu:271-273
     const int n_loc = h_counts[c->rank], disp = h_displs[c->rank];
@@ -878,7 +878,7 @@ static int neighbor_list_impl(const char *what, kmcf_comm *c, const double *d_x,
     KMCF_CHECK(c && d_x && d_y && d_z && d_neigh_idx, KMCF_ERR_ARG, "%s: null argument", what);
     KMCF_CHECK(c->device >= 0, KMCF_ERR_STATE, "%s: host-only communicator", what);
     KMCF_CHECK(nn > 0 && nn <= NL_CAP && count >= 0 && displ >= 0 && displ + count <= N, KMCF_ERR_ARG, "%s: bad sizes", what);
-    KMCF_TRY(kmcf_enter(c));
+    KMCF_TRY(kmcf_enter_setup(c));
     host_cells hc;
     const double open_lattice[3] = {1, 1, 1};
     const double *lattice = pbc ? h_lattice : open_lattice;

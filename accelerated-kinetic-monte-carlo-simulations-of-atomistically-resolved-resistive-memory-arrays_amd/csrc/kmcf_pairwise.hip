@@ -206,7 +206,7 @@ extern "C" int kmcf_compute_cutoff_list_pbc(kmcf_comm *c, const double *d_x, con
     KMCF_CHECK(std::isfinite(Ly) && Ly > 0, KMCF_ERR_ARG, "%s: the period in y, h_lattice[1] = %g, is not finite and > 0", what, Ly);
     KMCF_CHECK(std::isfinite(Lz) && Lz > 0, KMCF_ERR_ARG, "%s: the period in z, h_lattice[2] = %g, is not finite and > 0", what, Lz);
     KMCF_CHECK(c->device >= 0, KMCF_ERR_STATE, "%s: host-only communicator", what);
-    KMCF_TRY(kmcf_enter(c));
+    KMCF_TRY(kmcf_enter_setup(c));
     std::vector<double> x(N), y(N), z(N);
     KMCF_HIP(hipMemcpy(x.data(), d_x, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
     KMCF_HIP(hipMemcpy(y.data(), d_y, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
@@ -260,7 +260,7 @@ extern "C" int kmcf_compute_cutoff_list(kmcf_comm *c, const double *d_x, const d
 {
     KMCF_CHECK(c && d_x && d_y && d_z && out && N > 0 && cutoff_radius > 0, KMCF_ERR_ARG, "kmcf_compute_cutoff_list: bad argument");
     KMCF_CHECK(c->device >= 0, KMCF_ERR_STATE, "kmcf_compute_cutoff_list: host-only communicator");
-    KMCF_TRY(kmcf_enter(c));
+    KMCF_TRY(kmcf_enter_setup(c));
     std::vector<double> x(N), y(N), z(N);
     KMCF_HIP(hipMemcpy(x.data(), d_x, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
     KMCF_HIP(hipMemcpy(y.data(), d_y, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));

@@ -1691,9 +1691,10 @@ static int init_atom_set(kmcf_tstate *t, const int *d_site_element, const int *h
     KMCF_TRY(upload(&t->d_atom_site, t->h_atom_site));
     KMCF_TRY(upload(&t->d_site_is_atom, is_atom));
     const size_t na = (size_t)Na;      // (>= 4: no buffer below is empty; all of them start zeroed)
-    KMCF_TRY(kmcf_dev_alloc(&t->d_ax, na, true)); KMCF_TRY(kmcf_dev_alloc(&t->d_ay, na, true)); KMCF_TRY(kmcf_dev_alloc(&t->d_az, na, true));
-    KMCF_TRY(kmcf_dev_alloc(&t->d_acb, na, true)); KMCF_TRY(kmcf_dev_alloc(&t->d_ael, na, true)); KMCF_TRY(kmcf_dev_alloc(&t->d_ach, na, true));
-    KMCF_TRY(kmcf_dev_alloc(&t->d_acls, na, true));
+    KMCF_TRY(kmcf_dev_alloc(&t->d_ax, na, true, t->comm->stream)); KMCF_TRY(kmcf_dev_alloc(&t->d_ay, na, true, t->comm->stream)); KMCF_TRY(kmcf_dev_alloc(&t->d_az, na, true, t->comm->stream));
+    KMCF_TRY(kmcf_dev_alloc(&t->d_acb, na, true, t->comm->stream)); KMCF_TRY(kmcf_dev_alloc(&t->d_ael, na, true, t->comm->stream)); KMCF_TRY(kmcf_dev_alloc(&t->d_ach, na, true, t->comm->stream));
+    KMCF_TRY(kmcf_dev_alloc(&t->d_acls, na, true, t->comm->stream));
+    KMCF_HIP(hipStreamSynchronize(t->comm->stream));      // (the fills: the gather kernel, on the caller's stream, writes d_ax .. d_az next)
     return KMCF_OK;
 }
 
@@ -1847,37 +1848,38 @@ static int init_workspace(kmcf_tstate *t, const int *h_counts_T, const int *h_di
     const kmcf_matrix *m = t->T;
     const int n_loc = m->n_loc, Na = t->N_atom, Nsub = t->Nsub, P = t->comm->nranks;
     const size_t na = (size_t)Na, nl1 = (size_t)std::max(n_loc, 1);     // (a rank may hold no row)
-    KMCF_TRY(kmcf_dev_alloc(&t->d_cls_col, std::max<size_t>((size_t)n_loc + m->n_halo, 1), true));
-    KMCF_TRY(kmcf_dev_alloc(&t->d_diag, nl1, true)); KMCF_TRY(kmcf_dev_alloc(&t->d_diag_tot, nl1, true));
-    KMCF_TRY(kmcf_dev_alloc(&t->d_rhs, (size_t)n_loc + 2, true));
+    KMCF_TRY(kmcf_dev_alloc(&t->d_cls_col, std::max<size_t>((size_t)n_loc + m->n_halo, 1), true, t->comm->stream));
+    KMCF_TRY(kmcf_dev_alloc(&t->d_diag, nl1, true, t->comm->stream)); KMCF_TRY(kmcf_dev_alloc(&t->d_diag_tot, nl1, true, t->comm->stream));
+    KMCF_TRY(kmcf_dev_alloc(&t->d_rhs, (size_t)n_loc + 2, true, t->comm->stream));
     // tunnel workspace sized by the atom count
     const int nblk = (Na + KMCF_SCAN_TILE - 1) / KMCF_SCAN_TILE;
-    KMCF_TRY(kmcf_dev_alloc(&t->d_blk, (size_t)2 * nblk + 2, true));
-    KMCF_TRY(kmcf_dev_alloc(&t->d_tidx, na, true)); KMCF_TRY(kmcf_dev_alloc(&t->d_tinfo, na, true));
-    KMCF_TRY(kmcf_dev_alloc(&t->d_tx, na, true)); KMCF_TRY(kmcf_dev_alloc(&t->d_ty, na, true)); KMCF_TRY(kmcf_dev_alloc(&t->d_tz, na, true));
-    KMCF_TRY(kmcf_dev_alloc(&t->d_tcb, na, true));
-    KMCF_TRY(kmcf_dev_alloc(&t->d_pdisp, (size_t)Nsub + 2, true)); KMCF_TRY(kmcf_dev_alloc(&t->d_scal, 4, true));
-    KMCF_TRY(kmcf_dev_alloc(&t->d_err, 1, true));
+    KMCF_TRY(kmcf_dev_alloc(&t->d_blk, (size_t)2 * nblk + 2, true, t->comm->stream));
+    KMCF_TRY(kmcf_dev_alloc(&t->d_tidx, na, true, t->comm->stream)); KMCF_TRY(kmcf_dev_alloc(&t->d_tinfo, na, true, t->comm->stream));
+    KMCF_TRY(kmcf_dev_alloc(&t->d_tx, na, true, t->comm->stream)); KMCF_TRY(kmcf_dev_alloc(&t->d_ty, na, true, t->comm->stream)); KMCF_TRY(kmcf_dev_alloc(&t->d_tz, na, true, t->comm->stream));
+    KMCF_TRY(kmcf_dev_alloc(&t->d_tcb, na, true, t->comm->stream));
+    KMCF_TRY(kmcf_dev_alloc(&t->d_pdisp, (size_t)Nsub + 2, true, t->comm->stream)); KMCF_TRY(kmcf_dev_alloc(&t->d_scal, 4, true, t->comm->stream));
+    KMCF_TRY(kmcf_dev_alloc(&t->d_err, 1, true, t->comm->stream));
     KMCF_TRY(pinned_zeroed(&t->h_pin, 1));
-    KMCF_TRY(kmcf_dev_alloc(&t->d_agree, (size_t)2 * P, true));
+    KMCF_TRY(kmcf_dev_alloc(&t->d_agree, (size_t)2 * P, true, t->comm->stream));
     KMCF_TRY(pinned_zeroed(&t->h_agree, (size_t)(2 + 2 * P)));
     t->sub.counts.assign(P, 0);
     t->sub.displs.assign(P, 0);
     // scratch of kmcf_current_map (here, not at its first call: no allocation between the exchanges of a group)
     KMCF_CHECK((int64_t)3 * (Nsub + 2) < (int64_t)INT32_MAX, KMCF_ERR_ARG, "kmcf_initialize_sparsity_T: %d atoms exceed int32 indexing", Na);
-    KMCF_TRY(kmcf_dev_alloc(&t->d_cmap, (size_t)3 * (Nsub + 2), true)); KMCF_TRY(kmcf_dev_alloc(&t->d_cmstat, 8, true));
+    KMCF_TRY(kmcf_dev_alloc(&t->d_cmap, (size_t)3 * (Nsub + 2), true, t->comm->stream)); KMCF_TRY(kmcf_dev_alloc(&t->d_cmstat, 8, true, t->comm->stream));
     KMCF_TRY(pinned_zeroed(&t->h_cmstat, 8));
     t->cm_counts.resize((size_t)P); t->cm_displs.resize((size_t)P);
     for (int q = 0; q < P; ++q) { t->cm_counts[q] = 3 * h_counts_T[q]; t->cm_displs[q] = 3 * h_displs_T[q]; }
     // scratch of kmcf_current_profile (the profile itself is sized by the call: grown at its very start)
     if ((int64_t)CP_STRIDE * (Nsub + 2) < (int64_t)INT32_MAX) {
-        KMCF_TRY(kmcf_dev_alloc(&t->d_cprof, (size_t)CP_STRIDE * (Nsub + 2), true));
-        KMCF_TRY(kmcf_dev_alloc(&t->d_cpq, na, true)); KMCF_TRY(kmcf_dev_alloc(&t->d_cpcell, na, true));
-        KMCF_TRY(kmcf_dev_alloc(&t->d_cpplanes, (size_t)CP_MAX, true));
+        KMCF_TRY(kmcf_dev_alloc(&t->d_cprof, (size_t)CP_STRIDE * (Nsub + 2), true, t->comm->stream));
+        KMCF_TRY(kmcf_dev_alloc(&t->d_cpq, na, true, t->comm->stream)); KMCF_TRY(kmcf_dev_alloc(&t->d_cpcell, na, true, t->comm->stream));
+        KMCF_TRY(kmcf_dev_alloc(&t->d_cpplanes, (size_t)CP_MAX, true, t->comm->stream));
         KMCF_TRY(pinned_zeroed(&t->h_cpplanes, (size_t)CP_MAX));
         t->cp_counts.resize((size_t)P); t->cp_displs.resize((size_t)P);
         for (int q = 0; q < P; ++q) { t->cp_counts[q] = CP_STRIDE * h_counts_T[q]; t->cp_displs[q] = CP_STRIDE * h_displs_T[q]; }
     }
+    KMCF_HIP(hipStreamSynchronize(t->comm->stream));      // (the fills on the compute stream: done before any stream uses the workspace)
     return KMCF_OK;
 }
 
@@ -2728,14 +2730,14 @@ static int profile_out_grow(kmcf_tstate *t, size_t n, size_t n_part)
     if (!t->d_cppart || n_part > t->cap_cppart) {
         if (t->d_cppart) { t->cp_retired_dev.push_back(t->d_cppart); t->d_cppart = nullptr; }
         t->cap_cppart = 0;
-        KMCF_TRY(kmcf_dev_alloc(&t->d_cppart, n_part, true));
+        KMCF_TRY(kmcf_dev_alloc(&t->d_cppart, n_part, true, t->comm->stream));
         t->cap_cppart = n_part;
     }
     if (t->d_cpout && n <= t->cap_cpout) return KMCF_OK;
     if (t->d_cpout) { t->cp_retired_dev.push_back(t->d_cpout); t->d_cpout = nullptr; }
     if (t->h_cpout) { t->cp_retired_host.push_back(t->h_cpout); t->h_cpout = nullptr; }
     t->cap_cpout = 0;
-    KMCF_TRY(kmcf_dev_alloc(&t->d_cpout, n, true));
+    KMCF_TRY(kmcf_dev_alloc(&t->d_cpout, n, true, t->comm->stream));
     KMCF_TRY(pinned_zeroed(&t->h_cpout, n));
     t->cap_cpout = n;
     return KMCF_OK;
