@@ -272,6 +272,7 @@ extern "C" int kmcf_comm_destroy(kmcf_comm *c)
     kmcf_event_cache_free(c);
     kmcf_cluster_ws_free(c);
     kmcf_gradient_ws_free(c);
+    kmcf_census_ws_free(c);
     kmcf_p2p_destroy(c);
     if (c->nccl) g_rccl.CommDestroy(static_cast<ncclComm_t>(c->nccl));
     if (c->nccl_red) g_rccl.CommDestroy(static_cast<ncclComm_t>(c->nccl_red));

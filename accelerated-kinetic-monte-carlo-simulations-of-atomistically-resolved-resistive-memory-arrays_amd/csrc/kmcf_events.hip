@@ -1488,11 +1488,12 @@ extern "C" int kmcf_execute_kmc_step(kmcf_comm *c, int N, const int *h_count, co
 extern "C" int kmcf_events_reset(kmcf_comm *c)
 {
     KMCF_CHECK(c, KMCF_ERR_ARG, "kmcf_events_reset: null argument");
-    if (c->ev_cache && c->device >= 0) {
+    if ((c->ev_cache || c->cs_ws) && c->device >= 0) {
         KMCF_TRY(kmcf_enter(c));
         KMCF_HIP(hipStreamSynchronize(c->stream));              // (nothing of a step is in flight when its buffers go)
     }
     kmcf_event_cache_free(c);
+    kmcf_census_ws_free(c);                                     // (the census's own scratch: kmcf_census.hip)
     return KMCF_OK;
 }
 
@@ -1565,4 +1566,49 @@ extern "C" int kmcf_event_rates(kmcf_comm *c, int N, const int *h_count, const i
     KMCF_CHECK(bad_site == EV_NO_BAD_SITE, KMCF_ERR_ARG, "%s: the temperature of site %d is not finite or not > 0 (it owns an event)",
                what, bad_site);
     return KMCF_OK;
+}
+
+// kmcf_event_census: the checks and the list's arguments live here, next to the build kernel; the census itself is
+// kmcf_census_run (kmcf_census.hip), which gets the build as a callback that fills ITS scratch.
+extern "C" int kmcf_event_census(kmcf_comm *c, int N, const int *h_count, const int *h_displs, int nn, const int *d_neigh_idx,
+                                 const int *d_site_layer, double T_bg, double freq, double sigma, double k, const double *d_x,
+                                 const double *d_y, const double *d_z, const double *d_site_potential_charge,
+                                 const int *d_site_element, const int *d_site_charge, int num_layers, const double *h_E_gen,
+                                 const double *h_E_rec, const double *h_E_Vdiff, const double *h_E_Odiff,
+                                 const double *d_site_temperature, int rate_mode, const int *d_site_cell, int n_cells,
+                                 kmcf_census_bucket_t *h_table, int n_bins, int e_lo, int e_step, int64_t *h_spectrum,
+                                 double *d_row_rate, int *d_row_best, kmcf_census_stats_t *stats)
+{
+    const char *what = "kmcf_event_census";
+    KMCF_TRY(check_thermal_args(what, rate_mode, d_site_temperature, T_bg));
+    // (the argument checks of check_step_args once more: it turns a host-only communicator away before it looks at the sizes)
+    KMCF_CHECK(c && h_count && h_displs && d_neigh_idx && d_site_layer && d_x && d_y && d_z && d_site_potential_charge && d_site_element &&
+                   d_site_charge && h_E_gen && h_E_rec && h_E_Vdiff && h_E_Odiff, KMCF_ERR_ARG, "%s: null argument", what);
+    KMCF_CHECK(num_layers > 0 && num_layers <= MAX_LAYERS && nn > 0 && freq > 0, KMCF_ERR_ARG, "%s: bad sizes", what);
+    KMCF_CHECK(h_table, KMCF_ERR_ARG, "%s: h_table is NULL", what);
+    KMCF_CHECK(n_cells >= 1 && n_cells <= 1024, KMCF_ERR_ARG, "%s: n_cells = %d outside 1 ... 1024", what, n_cells);
+    KMCF_CHECK(d_site_cell || n_cells == 1, KMCF_ERR_ARG, "%s: d_site_cell is NULL with n_cells = %d (NULL needs n_cells == 1)", what, n_cells);
+    KMCF_CHECK(n_bins >= 0 && n_bins <= 256, KMCF_ERR_ARG, "%s: n_bins = %d outside 0 ... 256", what, n_bins);
+    KMCF_CHECK(n_bins == 0 || h_spectrum, KMCF_ERR_ARG, "%s: h_spectrum is NULL with n_bins = %d", what, n_bins);
+    KMCF_CHECK(n_bins == 0 || e_step >= 1, KMCF_ERR_ARG, "%s: e_step = %d is not >= 1", what, e_step);
+    KMCF_CHECK(n_bins > 0 || !h_spectrum, KMCF_ERR_ARG, "%s: h_spectrum is set with n_bins == 0", what);
+    const int count = h_count[c->rank], start_i = h_displs[c->rank];
+    KMCF_CHECK(count >= 0 && start_i >= 0 && (int64_t)start_i + count <= N, KMCF_ERR_ARG,
+               "%s: h_count / h_displs: rows [%d, +%d) do not lie in [0, N = %d)", what, start_i, count, N);
+    KMCF_CHECK((int64_t)count * nn < INT32_MAX, KMCF_ERR_ARG, "%s: count * nn = %lld event slots do not fit the int32 slot id", what,
+               (long long)count * nn);
+    ev_step_in in = {N, nn, d_neigh_idx, d_site_layer, T_bg, freq, sigma, k, d_x, d_y, d_z, d_site_potential_charge,
+                     d_site_element, d_site_charge, d_site_temperature, rate_mode, {}};
+    KMCF_TRY(check_step_args(what, c, h_count, h_displs, in, {num_layers, h_E_gen, h_E_rec, h_E_Vdiff, h_E_Odiff}, true));
+    KMCF_TRY(kmcf_enter(c));
+    struct build_ctx { const kmcf_comm *c; const ev_step_in *in; int count, start_i; } ctx = {c, &in, count, start_i};
+    kmcf_census_args a = {what, count, start_i, nn, num_layers, d_neigh_idx, d_site_layer, d_site_cell, n_cells, h_table, n_bins, e_lo, e_step,
+                          h_spectrum, d_row_rate, d_row_best, stats,
+                          [](void *p, unsigned char *d_type, double *d_prob, int *d_bad) {
+                              const build_ctx *b = static_cast<const build_ctx *>(p);
+                              launch_build_event_list(b->c, *b->in, b->count, b->start_i, d_type, d_prob,
+                                                      b->in->rate_mode != KMCF_RATE_T_BG ? d_bad : nullptr);
+                          },
+                          &ctx};
+    return kmcf_census_run(c, a);
 }

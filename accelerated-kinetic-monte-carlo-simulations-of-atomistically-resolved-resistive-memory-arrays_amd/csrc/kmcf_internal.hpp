@@ -138,6 +138,8 @@ struct kmcf_comm {
     struct kmcf_cluster_ws *cl_ws = nullptr;
     // scratch of kmcf_site_gradient (kmcf_gradient.hip): buffers only
     struct kmcf_gradient_ws *gr_ws = nullptr;
+    // scratch of kmcf_event_census (kmcf_census.hip): its own copy of the event list, the live slots, their keys
+    struct kmcf_census_ws *cs_ws = nullptr;
     // geometry of the event step's pair distance (kmcf_events_set_lattice): 1 = minimum image in y and z with these periods.
     // Plain values: kmcf_events_reset leaves them, they go with the communicator
     int ev_pbc = 0;
@@ -167,6 +169,26 @@ uint32_t kmcf_group_knob_hash(const kmcf_comm *c, kmcf_knob_id k);
 void kmcf_event_cache_free(kmcf_comm *c);
 void kmcf_cluster_ws_free(kmcf_comm *c);
 void kmcf_gradient_ws_free(kmcf_comm *c);
+void kmcf_census_ws_free(kmcf_comm *c);
+
+// census.hip: everything of kmcf_event_census behind its checks (arguments checked, kmcf_enter done).  build writes
+// the event list of the count rows from displ into the scratch it is handed (the build kernel of kmcf_events.hip, which
+// owns the entry point and the list's arguments); bad: the word of the thermal modes, preset to KMCF_NO_BAD_SITE.
+struct kmcf_census_args {
+    const char *what;
+    int count, displ, nn, num_layers;
+    const int *d_neigh_idx, *d_site_layer, *d_site_cell;
+    int n_cells;
+    kmcf_census_bucket_t *h_table;
+    int n_bins, e_lo, e_step;
+    int64_t *h_spectrum;
+    double *d_row_rate;
+    int *d_row_best;
+    kmcf_census_stats_t *stats;
+    void (*build)(void *ctx, unsigned char *d_type, double *d_prob, int *d_bad);
+    void *ctx;
+};
+int kmcf_census_run(kmcf_comm *c, const kmcf_census_args &a);
 
 // clusters.hip: the cluster pass of kmcf_conductive_clusters (its arguments, already checked; kmcf_enter done) enqueued on
 // the compute stream, nothing waited for and nothing copied.  Hands back where the results lie on the device: the class

@@ -154,6 +154,23 @@ class CurrentProfileStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class CensusBucket(C.Structure):
+    """kmcf_census_bucket_t"""
+    _fields_ = [("n_events", C.c_int64), ("rate_sum", C.c_double), ("rate_max", C.c_double), ("max_i", C.c_int),
+                ("max_j", C.c_int), ("n_zero", C.c_int), ("reserved", C.c_int)]
+
+
+class CensusStats(C.Structure):
+    """kmcf_census_stats_t"""
+    _fields_ = [("slots", C.c_int64), ("n_events", C.c_int64), ("n_zero", C.c_int64), ("n_nan", C.c_int64),
+                ("n_type", C.c_int64 * 4), ("rate_type", C.c_double * 4), ("rate_total", C.c_double),
+                ("dt_mean", C.c_double), ("rate_max", C.c_double), ("max_i", C.c_int), ("max_j", C.c_int),
+                ("max_type", C.c_int), ("rows_live", C.c_int), ("ms_build", C.c_float), ("ms_census", C.c_float)]
+
+    def as_dict(self):
+        return {k: (list(getattr(self, k)) if k in ("n_type", "rate_type") else getattr(self, k)) for k, _ in self._fields_}
+
+
 _P = C.c_void_p          # device or opaque pointer
 _IP = C.POINTER(C.c_int)
 _DP = C.POINTER(C.c_double)
@@ -256,6 +273,10 @@ SIGNATURES = {
     "kmcf_event_rates": (C.c_int, [_P, C.c_int, _IP, _IP, C.c_int, _P, _P, C.c_double, C.c_double, C.c_double,
                                    C.c_double, _P, _P, _P, _P, _P, _P, C.c_int, _DP, _DP, _DP, _DP, _P, C.c_int,
                                    C.POINTER(C.c_ubyte), _DP]),
+    "kmcf_event_census": (C.c_int, [_P, C.c_int, _IP, _IP, C.c_int, _P, _P, C.c_double, C.c_double, C.c_double,
+                                    C.c_double, _P, _P, _P, _P, _P, _P, C.c_int, _DP, _DP, _DP, _DP, _P, C.c_int,
+                                    _P, C.c_int, C.POINTER(CensusBucket), C.c_int, C.c_int, C.c_int,
+                                    C.POINTER(C.c_int64), _P, _P, C.POINTER(CensusStats)]),
     "kmcf_conductive_clusters": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, C.c_int, C.c_int, _P,
                                            C.POINTER(Cluster), C.c_int, C.POINTER(ClusterStats)]),
     "kmcf_site_set_gap": (C.c_int, [_P, _P, _P, _P, _P, C.c_double, _P, C.c_int, C.POINTER(Gap), C.POINTER(GapStats)]),

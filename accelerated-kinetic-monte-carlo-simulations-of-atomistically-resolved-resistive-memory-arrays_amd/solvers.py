@@ -677,6 +677,102 @@ def event_rates(kmc_comm, N, count, displs, nn, neigh_idx, site_layer, T_bg, fre
     return typ, prob
 
 
+CENSUS_DTYPE = np.dtype([("n_events", np.int64), ("rate_sum", np.float64), ("rate_max", np.float64), ("max_i", np.int32),
+                         ("max_j", np.int32), ("n_zero", np.int32), ("reserved", np.int32)])      # kmcf_census_bucket_t
+EVENT_NAMES = ("gen", "rec", "vdiff", "odiff")      # EVENTTYPE 0..3
+
+
+def event_census(kmc_comm, N, count, displs, nn, neigh_idx, site_layer, T_bg, freq, sigma, k, posx, posy, posz,
+                 site_potential_charge, site_element, site_charge, layers, site_temperature=None, rate_mode="bg",
+                 site_cell=None, n_cells=1, bins=(64, -128, 16), rows=False):
+    """kmcf_event_census: the event list of this rank's rows (the one event_rates returns) reduced on the device to rates
+    per cell, layer and event type; nothing executed, nothing drawn (definitions: include/kmcfield.h).  site_cell: int32
+    device tensor of N cell ids (outside [0, n_cells): the rest, cell index n_cells) or None with n_cells = 1.
+    bins = (n_bins, e_lo, e_step): the spectrum of the rates' binary exponents, None or n_bins = 0 for none.  rows: also
+    the sum and the best slot per row, as device tensors.
+    Returns dict(table: CENSUS_DTYPE array of shape (n_cells + 1, num_layers, 4), spectrum: int64 (4, n_bins) or None,
+    row_rate / row_best: float64 / int32 device tensors of count[rank] entries or None, stats: dict)."""
+    lib = _L.load()
+    cnt, cntp = _ia(count)
+    dsp, dspp = _ia(displs)
+    (eg, egp), (er, erp), (ev, evp), (eo, eop) = _layer_energies(layers)
+    n_rows = int(cnt[kmc_comm.rank_events])
+    n_bins, e_lo, e_step = (0, 0, 1) if bins is None else (int(b) for b in bins)
+    table = np.zeros((int(n_cells) + 1, len(layers), 4), CENSUS_DTYPE)
+    spectrum = np.zeros((4, n_bins), np.int64) if n_bins > 0 else None
+    row_rate = row_best = None
+    if rows:
+        dev = neigh_idx.device
+        row_rate = torch.empty(n_rows, dtype=torch.float64, device=dev)
+        row_best = torch.empty(n_rows, dtype=torch.int32, device=dev)
+    st = _L.CensusStats()
+    _L.check(lib.kmcf_event_census(kmc_comm.handle, int(N), cntp, dspp, int(nn), _ptr(neigh_idx), _ptr(site_layer),
+                                   float(T_bg), float(freq), float(sigma), float(k), _ptr(posx), _ptr(posy), _ptr(posz),
+                                   _ptr(site_potential_charge), _ptr(site_element), _ptr(site_charge), len(layers),
+                                   egp, erp, evp, eop, _ptr(site_temperature), _rate_mode(rate_mode),
+                                   _ptr(site_cell), int(n_cells), table.ctypes.data_as(C.POINTER(_L.CensusBucket)),
+                                   n_bins, e_lo, e_step,
+                                   spectrum.ctypes.data_as(C.POINTER(C.c_int64)) if spectrum is not None else None,
+                                   _ptr(row_rate), _ptr(row_best), C.byref(st)),
+             "kmcf_event_census")
+    return dict(table=table, spectrum=spectrum, row_rate=row_rate, row_best=row_best, stats=st.as_dict())
+
+
+def census_stats_from_table(table):
+    """The statistics kmcf_event_census forms from its table, by the header's formulas: integer sums, rate_type[t] over cell
+    ascending then layer ascending from 0.0, rate_total = ((r0 + r1) + r2) + r3, dt_mean (the overall maximum needs the
+    slots of the maxima and is not formed here)."""
+    n_type, rate_type = [0] * 4, [0.0] * 4
+    for t in range(4):
+        r = 0.0
+        for c in range(table.shape[0]):
+            for l in range(table.shape[1]):
+                r += float(table[c, l, t]["rate_sum"])
+        rate_type[t] = r
+        n_type[t] = int(table[:, :, t]["n_events"].sum())
+    total = ((rate_type[0] + rate_type[1]) + rate_type[2]) + rate_type[3]
+    return dict(n_type=n_type, rate_type=rate_type, n_events=int(table["n_events"].sum()), n_zero=int(table["n_zero"].sum()),
+                rate_total=total, dt_mean=float("inf") if total == 0 else 1 / total)
+
+
+def event_census_merge(results):
+    """The host combination of the censuses of a partitioned group's ranks (or of (count, displ) slices), in list order =
+    ascending rows: integers add, sums add in list order, a maximum goes to the larger rate and among equal rates stays
+    with the earlier result (its slot id is the smaller one).  Row outputs are concatenated.  Returns a result dict like
+    event_census; stats are formed from the merged table, ms_build / ms_census add up."""
+    results = list(results)
+    first = results[0]
+    table = first["table"].copy()
+    spectrum = None if first["spectrum"] is None else first["spectrum"].copy()
+    best = dict(rate_max=first["stats"]["rate_max"], max_i=first["stats"]["max_i"], max_j=first["stats"]["max_j"],
+                max_type=first["stats"]["max_type"])
+    for r in results[1:]:
+        t = r["table"]
+        table["n_events"] += t["n_events"]
+        table["n_zero"] += t["n_zero"]
+        table["rate_sum"] = table["rate_sum"] + t["rate_sum"]
+        take = (t["max_i"] >= 0) & ((table["max_i"] < 0) | (t["rate_max"] > table["rate_max"]))
+        for f in ("rate_max", "max_i", "max_j"):
+            table[f] = np.where(take, t[f], table[f])
+        if spectrum is not None:
+            spectrum += r["spectrum"]
+        s = r["stats"]
+        if s["max_i"] >= 0 and (best["max_i"] < 0 or s["rate_max"] > best["rate_max"]):
+            best = dict(rate_max=s["rate_max"], max_i=s["max_i"], max_j=s["max_j"], max_type=s["max_type"])
+    stats = census_stats_from_table(table)
+    stats.update(best)
+    for key in ("slots", "n_nan", "rows_live", "ms_build", "ms_census"):
+        stats[key] = sum(r["stats"][key] for r in results)
+
+    def cat(key):
+        parts = [r[key] for r in results]
+        if any(p is None for p in parts):
+            return None
+        return torch.cat(parts) if isinstance(parts[0], torch.Tensor) else np.concatenate(parts)
+
+    return dict(table=table, spectrum=spectrum, row_rate=cat("row_rate"), row_best=cat("row_best"), stats=stats)
+
+
 # K-state inspection helpers used by the parity tests --------------------------------
 
 CLUSTER_DTYPE = np.dtype([("root", np.int32), ("kind", np.int32), ("size", np.int32), ("touch", np.int32),

@@ -523,6 +523,78 @@ int kmcf_event_rates(kmcf_comm *c, int N, const int *h_count, const int *h_displ
                      const double *d_site_temperature, int rate_mode,
                      unsigned char *h_type, double *h_prob);
 
+/* Event rate census: the list kmcf_event_rates returns for this rank's rows [displs[rank], +count[rank]) in the given rate
+ * mode (the same build kernel, the same bits; it honours kmcf_events_set_lattice), reduced on the device to rates per cell,
+ * layer and event type.  Executes nothing, draws nothing; a local operation without collectives.  Arguments up to
+ * rate_mode: those of kmcf_event_rates.  Slot id = (i - displ) * nn + s.  An EVENT is a slot whose type is not NULL_EVENT
+ * (4); its rate is the list's event_prob.
+ * Bucket of an event (i, j, type): cell = d_site_cell[i] (the row's site), layer = d_site_layer[j] (the layer whose
+ * energy entered the rate); h_table[((cell * num_layers) + layer) * 4 + type].  A cell value outside [0, n_cells) goes to
+ * the REST, cell index n_cells (the convention of kmcf_current_profile).  d_site_cell == NULL (n_cells must be 1): every
+ * site in cell 0.  Layers must lie in [0, num_layers), as the step requires; an event whose layer does not is left out of
+ * the table, the spectrum, n_nan and with them every statistic except slots and rows_live (the row outputs keep it).
+ * Nothing is stored outside the table for any input.
+ * Per bucket: n_events and n_zero exact.  rate_sum: the sum of the bucket's rates that are not NaN, no atomics on doubles;
+ * ORDER OF ADDITION: the events of the list in ascending slot id are numbered p = 0 ... n - 1 and cut into S pieces of
+ * ceil(n / S) consecutive events, S = min(max(count * nn / 32768, 1), max(65536 / buckets, 1), 64).  Within a piece that
+ * starts at p0, thread t of 256 adds the bucket's events with (p - p0) % 256 == t in ascending p to an accumulator that
+ * starts at 0.0, then the xor butterfly inside each wavefront of 64 and (w0 + w1) + (w2 + w3); the pieces' sums are added
+ * in ascending order to an accumulator that starts at 0.0.  The input alone fixes it: two calls on the same input return
+ * the same bytes.  rate_max: the bits of one slot's rate, the largest that is not NaN; among equal rates the smallest slot
+ * id (a bucket whose events all have rate 0.0: 0.0 with the pair of its first slot).  A NaN rate enters n_events and
+ * stats->n_nan and nothing else.
+ * Spectrum (n_bins in 0..256; 0: none, h_spectrum NULL): for a normal rate P, e = ((bits of P >> 52) & 0x7ff) - 1023, bin
+ * floor((e - e_lo) / e_step) clamped into [0, n_bins - 1]; 0.0 and subnormals: bin 0; +infinity: the last bin; NaN: no
+ * bin.  h_spectrum[type * n_bins + bin]: exact counts over all cells.
+ * Row outputs (device, optional): d_row_rate[r] the sum of the non-NaN rates of row displ + r, in slot order by one
+ * accumulator from 0.0; d_row_best[r] the slot s of the row's largest rate, the first among equals, -1 when the row has
+ * no event whose rate is a number.  Rows without events: 0.0 and -1.
+ * stats (host, formed from the table): rate_type[t] = sum over cell ascending, then layer ascending, of rate_sum, from
+ * 0.0; rate_total = ((r0 + r1) + r2) + r3; dt_mean = 1 / rate_total (+infinity for 0); the maximum by the bucket rule.
+ * In a partitioned group every rank gets the census of its own rows; tables combine on the host (integers add, sums add
+ * in rank order, maxima by the rule above).
+ * Keeps scratch of its own on the communicator (15 bytes per slot: type, rate, the live slots and their keys), freed by
+ * kmcf_comm_destroy and dropped by kmcf_events_reset; reads and writes nothing of the event step's workspace.  Enters
+ * like every entry point (stream ordering contract) and synchronises once, at its end.  count[rank] == 0: KMCF_OK, table,
+ * spectrum and stats zeroed (the table's and the stats' site ids -1, as for any empty bucket), dt_mean +infinity.  A
+ * list without events is no error.
+ * KMCF_ERR_ARG before anything needs a device (kmcf_last_error names the argument): the checks of kmcf_event_rates,
+ * count * nn >= 2^31 - 1 (slot ids are int32, as in the step's gather), rows outside [0, N), NULL h_table, n_cells
+ * outside 1..1024, NULL d_site_cell with n_cells != 1, n_bins outside 0..256,
+ * n_bins > 0 with NULL h_spectrum or e_step < 1, h_spectrum with n_bins == 0.  KMCF_ERR_STATE: host-only communicator,
+ * after these.  KMCF_ERR_ARG at the final synchronisation: an unusable temperature in a thermal mode, message and
+ * verdict of kmcf_event_rates; the outputs are unspecified then. */
+typedef struct {            /* one per bucket, 40 bytes */
+    int64_t n_events;       /* non-null slots of the bucket                                   */
+    double  rate_sum;       /* sum of their rates                                             */
+    double  rate_max;       /* largest rate (0.0 when the bucket has no candidate)            */
+    int     max_i, max_j;   /* its slot's site pair, -1 / -1 when none                        */
+    int     n_zero;         /* events of the bucket whose rate is exactly 0.0                 */
+    int     reserved;
+} kmcf_census_bucket_t;
+
+typedef struct {
+    int64_t slots, n_events, n_zero, n_nan;    /* count * nn; non-null slots; rate == 0.0; rate is NaN */
+    int64_t n_type[4];  double rate_type[4];   /* per EVENTTYPE 0..3 */
+    double  rate_total, dt_mean;               /* dt_mean = 1 / rate_total, +infinity when rate_total == 0 */
+    double  rate_max;  int max_i, max_j, max_type;   /* over all buckets; -1 ids when none */
+    int     rows_live;                         /* rows with at least one non-null slot */
+    float   ms_build, ms_census;               /* device time (HIP events): the build kernel / everything behind it */
+} kmcf_census_stats_t;
+
+int kmcf_event_census(kmcf_comm *c, int N, const int *h_count, const int *h_displs, int nn,
+                      const int *d_neigh_idx, const int *d_site_layer, double T_bg, double freq,
+                      double sigma, double k, const double *d_x, const double *d_y, const double *d_z,
+                      const double *d_site_potential_charge, const int *d_site_element,
+                      const int *d_site_charge, int num_layers, const double *h_E_gen,
+                      const double *h_E_rec, const double *h_E_Vdiff, const double *h_E_Odiff,
+                      const double *d_site_temperature, int rate_mode,
+                      const int *d_site_cell /* N, or NULL */, int n_cells,
+                      kmcf_census_bucket_t *h_table /* (n_cells + 1) * num_layers * 4, required */,
+                      int n_bins, int e_lo, int e_step, int64_t *h_spectrum /* 4 * n_bins, or NULL with n_bins == 0 */,
+                      double *d_row_rate /* count[rank] doubles, or NULL */, int *d_row_best /* count[rank] ints, or NULL */,
+                      kmcf_census_stats_t *stats /* or NULL */);
+
 /* ---------------------------------------------------------------------- */
 /* Conductive clusters: the filament as a graph (no reference counterpart)   */
 /* ---------------------------------------------------------------------- */

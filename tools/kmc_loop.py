@@ -5,7 +5,7 @@ prints into output<size>_<rank>.txt ("Z - calculation time - ...").
 
     python tools/kmc_loop.py [--workload 5nm|5nm-periodic|40nm|conducting] [--steps 6] [--T 300] [--current] [--rate-mode bg|ekin|site]
                              [--clusters] [--current-map] [--current-profile N] [--scheme all|half|third --select W,B] [--gap R]
-                             [--chain R [--chain-hops K]] [--field-map]
+                             [--chain R [--chain-hops K]] [--field-map] [--event-census]
 
 --current adds the electro-thermal stages after the potential and before the events: conduction-band edge, current
 solve with heating (site_power), local heat solve (site_temperature); --rate-mode ekin | site lets the event rates read
@@ -46,7 +46,13 @@ lists the first K hops of every chain as `<from>-<to> <hop> A`.  --field-map run
 the step line it prints, per cell of structure.crossbar_lines on the crossbar workloads (one cell otherwise), `field <cell>:
 |E| max <V/A> at site <site> = <ratio> x mean | drop <V/A> (<from>-<to>) | <full>/<sites> full` -- the mean field is
 |Vd| / (x extent of the interface) -- and the device time; with --current the same for the site temperature of the heat
-solve (`grad T`, K/A, no ratio).  On `5nm-periodic` the displacement is the minimum image.
+solve (`grad T`, K/A, no ratio).  On `5nm-periodic` the displacement is the minimum image.  --event-census runs the event
+rate census (kmcf_event_census) before the event step of every superstep, in the step's rate mode: the forecast of the step
+from the rates of every possible event, nothing executed.  Cells from structure.crossbar_lines on the crossbar workloads (one
+cell otherwise).  Below the step line it prints, per cell and for the rest, `census cell <c>: rate <sum> (<share of the
+total>) | gen <..> rec <..> vdiff <..> odiff <..> | max <rate> (<i>-<j>, <type>)` -- with --scheme also `| realised <share of
+the step's events that fell into the cell>` next to the forecast share -- then `census device: rate_total <..> dt_mean <..> |
+rows_live <..> n_zero <..> | build <ms> census <ms>`, the two device times.
 """
 import argparse
 import os
@@ -87,6 +93,9 @@ def main():
                     help="tunnelling-chain analysis after every charge update, hops of at most R angstrom (<= 20): the "
                          "stepping-stone chain between the electrode sides per crossbar cell, its longest hop and length")
     ap.add_argument("--chain-hops", type=int, default=0, metavar="K", help="with --chain: list the first K hops of every chain")
+    ap.add_argument("--event-census", action="store_true",
+                    help="event rate census before every event step: rate per crossbar cell and event type, the fastest event, "
+                         "the mean residence time; with --scheme the realised share of the step's events next to the forecast")
     ap.add_argument("--field-map", action="store_true",
                     help="site gradient map of the potential after every sum / gather: largest |E| and bond drop per crossbar "
                          "cell, against the mean field; with --current also of the site temperature")
@@ -175,6 +184,37 @@ def main():
             field_cells, n_field_cells = torch.as_tensor(np.ascontiguousarray(cells, np.int32), device="cuda"), int(cells.max()) + 1
         x_if = d["xyz"][NL:N - NL, 0]
         mean_field = abs(d["Vd"]) / float(x_if.max() - x_if.min())
+
+    census_cells, n_census_cells = None, 1
+    if a.event_census and a.workload not in ("5nm", "5nm-periodic"):
+        cells = km.structure.crossbar_lines(d)[2] if cell_of_site is None else cell_of_site
+        census_cells, n_census_cells = torch.as_tensor(np.ascontiguousarray(cells, np.int32), device="cuda"), int(cells.max()) + 1
+
+    def census_lines(cs, log):
+        """the per-cell lines of one census; log: the step's (i, j, type) rows, for the realised shares of --scheme"""
+        t, st_c = cs["table"], cs["stats"]
+        realised = None
+        if a.scheme and len(log):
+            cells = cell_of_site[log[:, 0]]
+            cells = np.where((cells < 0) | (cells >= n_census_cells), n_census_cells, cells)
+            realised = np.bincount(cells, minlength=n_census_cells + 1) / len(log)
+        out = []
+        for c in range(n_census_cells + 1):
+            by_type = [sum(float(t[c, l, ty]["rate_sum"]) for l in range(t.shape[1])) for ty in range(4)]
+            rate = ((by_type[0] + by_type[1]) + by_type[2]) + by_type[3]
+            top, ty_top = t[c, 0, 0], 0
+            for l in range(t.shape[1]):
+                for ty in range(4):
+                    b = t[c, l, ty]
+                    if b["max_i"] >= 0 and (top["max_i"] < 0 or b["rate_max"] > top["rate_max"]):
+                        top, ty_top = b, ty
+            out.append("  census %s: rate %.5e (%.4f) | gen %.4e rec %.4e vdiff %.4e odiff %.4e | max %.5e (%d-%d, %s)%s" % (
+                "rest" if c == n_census_cells else "cell %d" % c, rate, rate / st_c["rate_total"] if st_c["rate_total"] > 0 else 0.0,
+                *by_type, top["rate_max"], top["max_i"], top["max_j"], S.EVENT_NAMES[ty_top] if top["max_i"] >= 0 else "none",
+                "" if realised is None else " | realised %.4f" % realised[c]))
+        out.append("  census device: rate_total %.6e dt_mean %.5e | rows_live %d n_zero %d | build %.3f ms census %.3f ms" % (
+            st_c["rate_total"], st_c["dt_mean"], st_c["rows_live"], st_c["n_zero"], st_c["ms_build"], st_c["ms_census"]))
+        return out
 
     def gradient_lines(what, unit, value, scale):
         """the per-cell lines of one site field"""
@@ -288,6 +328,11 @@ def main():
                 field_lines += gradient_lines("grad T", "K/A", buf.site_temperature, 0.0)
             if a.rate_mode != "bg":
                 thermal = dict(site_temperature=buf.site_temperature, rate_mode=a.rate_mode)
+        census = None
+        if a.event_census:
+            census = S.event_census(comm, N, comm.counts_events, comm.displs_events, 52, buf.neigh_idx, lay, a.T, freq, d["sigma"],
+                                    d["k"], buf.site_x, buf.site_y, buf.site_z, buf.site_potential_charge, buf.site_element,
+                                    buf.site_charge, layers, site_cell=census_cells, n_cells=n_census_cells, **thermal)
         te, ev = timed(lambda: S.execute_kmc_step_mpi(comm, N, comm.counts_events, comm.displs_events, 52, buf.neigh_idx,
                                                       lay, a.T, freq, d["sigma"], d["k"], buf.site_x, buf.site_y,
                                                       buf.site_z, buf.site_potential_charge, buf.site_element,
@@ -315,6 +360,8 @@ def main():
                             lru.popitem(last=False)
                 line += ", LRU-%d hit rate %.2f" % (cap, hits / len(st_))
             print(line, flush=True)
+        if census is not None:
+            field_lines = field_lines + census_lines(census, ev[2])
         if a.current:
             print("step %d: charge %.6f | boundary %.6f (%d it) | pairwise %.6f | gather %.6f | CB edge %.6f (%d it) | "
                   "power %.6f (%d it, I_macro %.4e) | heat %.6f (%d it, max T %.2f K) | events[%s] %.6f (%d ev) | "
