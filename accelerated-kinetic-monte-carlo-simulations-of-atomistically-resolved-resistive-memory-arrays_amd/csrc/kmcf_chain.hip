@@ -36,10 +36,12 @@
 // their exact (d2, smallest partner); the others never enter b.
 //
 // Periodic index (kmcf_site_set_chain_pbc / kmcf_filament_chain_pbc on an index of kmcf_compute_cutoff_list_pbc with pbc = 1):
-// step a is ch_search_pbc_kernel -- the minimum image in y and z, the wrapped cells each once, the bound in y taken to the
-// face through which the neighbour cell is adjacent ("Periodic search"); every other launch is shared: the
-// cell id and the order inside a cell are those of the open index (one index_cells for both, kmcf_pairwise.hip), which is
-// all the compaction reads.  d2 is the same bits from both ends of a pair, so a mutual choice is seen as one by b and c.
+// step a is ch_search_kernel on the periodic geometry (kmcf_cell_grid_pbc; the walk and the distance are those of
+// kmcf_cellwalk.hpp) -- the minimum image in y and z, the wrapped cells each once, the bound in y taken to the face through
+// which the neighbour cell is adjacent ("Periodic search"); a candidate is met once and has one distance,
+// however many of its images lie within r_max; z is not pruned.  Every other launch is shared: the cell id and the order
+// inside a cell are those of the open index (one index_cells for both, kmcf_pairwise.hip), which is all the compaction
+// reads.  d2 is the same bits from both ends of a pair, so a mutual choice is seen as one by b and c.
 //
 // Determinism: every device result is an integer sum or minimum; the order of the edge list is not, and the host sorts it
 // by key before use.  No thread waits for another; the search stops after CH_MAX_ROUNDS rounds (KMCF_ERR_STATE).
@@ -50,7 +52,7 @@
 #include <unordered_map>
 #include <vector>
 
-#include "kmcf_internal.hpp"
+#include "kmcf_cellwalk.hpp"
 
 static_assert(sizeof(kmcf_chain_t) == 64, "kmcf_chain_t is 64 bytes");
 static_assert(sizeof(kmcf_hop_t) == 16, "kmcf_hop_t is 16 bytes");
@@ -99,19 +101,10 @@ void kmcf_chain_ws_free(kmcf_pairwise *p)
 namespace {
 
 constexpr int CH_LPS = 16, CH_SPB = KMCF_BLOCK / CH_LPS;          // lanes per member, members per block
-constexpr u64 CH_INF = 0x7ff0000000000000ull;                    // bits of +infinity
-constexpr u64 CH_NO_PAIR = ~0ull;
 constexpr int CH_NO_SITE = 0x7fffffff;
 constexpr int CH_MAX_ROUNDS = 40;
 enum { CH_W_LEFT, CH_W_RIGHT, CH_W_BOTH, CH_W_STONES, CH_W_STONE_SITES, CH_W_LREP, CH_W_RREP, CH_W_WORDS = 8 };
 enum { CH_F_EDGES, CH_F_ERROR, CH_F_SURFACE, CH_F_OPEN0, CH_F_WORDS = CH_F_OPEN0 + CH_MAX_ROUNDS };
-
-// gap cell of a site, -1: none
-__device__ __forceinline__ int ch_cell(const int *__restrict__ site_cell, int n_cells, int i)
-{
-    const int c = site_cell ? site_cell[i] : 0;
-    return (unsigned)c < (unsigned)n_cells ? c : -1;
-}
 
 // both terminals and no site on both sides: the cell's vertices enter the search
 __device__ __forceinline__ bool ch_active(const int *__restrict__ words, int c)
@@ -119,8 +112,6 @@ __device__ __forceinline__ bool ch_active(const int *__restrict__ words, int c)
     const int *q = words + (size_t)CH_W_WORDS * c;
     return q[CH_W_LEFT] > 0 && q[CH_W_RIGHT] > 0 && q[CH_W_BOTH] == 0;
 }
-
-__device__ __forceinline__ u64 ch_load(const u64 *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // sides and nodes from the cluster pass: touch of the site's cluster; the label where that cluster floats
 __global__ __launch_bounds__(KMCF_BLOCK) void ch_side_node_kernel(int N, const unsigned char *__restrict__ cls,
@@ -144,15 +135,15 @@ __global__ __launch_bounds__(KMCF_BLOCK) void ch_clear_kernel(int N, size_t n_ce
     if (i < (size_t)N) {
         home[i] = CH_NO_SITE;
         root[i] = next[i] = (int)i;
-        cbest[i] = CH_INF;
-        cpair[i] = CH_NO_PAIR;
+        cbest[i] = KMCF_D2_INF;
+        cpair[i] = KMCF_NO_PAIR;
     }
     if (i < n_cells) {
         int *q = words + CH_W_WORDS * i;
 #pragma unroll
         for (int k = 0; k < CH_W_WORDS; ++k) q[k] = 0;
         q[CH_W_LREP] = q[CH_W_RREP] = CH_NO_SITE;
-        direct[i] = CH_INF;
+        direct[i] = KMCF_D2_INF;
     }
     if (blockIdx.x == 0 && threadIdx.x < CH_F_WORDS) flags[threadIdx.x] = 0;
 }
@@ -164,7 +155,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void ch_count_kernel(int N, const int *
     const int i = blockIdx.x * KMCF_BLOCK + threadIdx.x;
     const int lane = threadIdx.x & 63;
     const int s = i < N ? (side[i] & 3) : 0;
-    const int c = i < N ? ch_cell(site_cell, n_cells, i) : -1;
+    const int c = i < N ? kmcf_site_cell(site_cell, n_cells, i) : -1;
     if (i < N && s == 0 && c >= 0) {
         const int n = node[i];
         if ((unsigned)n < (unsigned)N) atomicMin(home + n, i);
@@ -198,13 +189,13 @@ __global__ __launch_bounds__(KMCF_BLOCK) void ch_vertex_kernel(int N, const int 
     const int i = blockIdx.x * KMCF_BLOCK + threadIdx.x;
     if (i >= N) return;
     const int s = side[i] & 3;
-    const int c = ch_cell(site_cell, n_cells, i);
+    const int c = kmcf_site_cell(site_cell, n_cells, i);
     int vert = -1, vc = -1;
     if (c >= 0 && s == 0) {
         const int n = node[i];
         if ((unsigned)n < (unsigned)N) {
             vert = home[n];
-            vc = ch_cell(site_cell, n_cells, vert);              // (the home is a stone site: it has a cell)
+            vc = kmcf_site_cell(site_cell, n_cells, vert);              // (the home is a stone site: it has a cell)
             int *q = words + (size_t)CH_W_WORDS * vc;
             atomicAdd(q + CH_W_STONE_SITES, 1);
             if (vert == i) atomicAdd(q + CH_W_STONES, 1);
@@ -271,21 +262,12 @@ __global__ __launch_bounds__(KMCF_BLOCK) void ch_scatter_kernel(int N, int nb, c
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x == KMCF_BLOCK - 1) lpos[N] = sum[nb];
 }
 
-// Lower bound of |v_b - v| over the sites b of index cell column `a` next to the column `c` of v (a = c - 1 or c + 1):
-// the distance to the face between them, shortened by far more than the cell rule can misplace a site (relative 1e-9).
-// (The margin and the rule of the gap search, kmcf_gap.hip.)
-__device__ __forceinline__ double ch_face_dist(double v, double v0, double edge, int c, int a)
-{
-    const double f = v0 + (double)(a > c ? c + 1 : c) * edge;
-    const double d = (a > c ? f - v : v - f) - 1e-9 * (fabs(f) + fabs(v) + edge);
-    return d > 0.0 ? d : 0.0;
-}
-
-// a: the search of one round over the list.  A group of CH_LPS lanes per member; the loop runs over whole blocks of
-// groups, and every loop bound and threshold is uniform over a group, so its lanes reach the shuffles together.
+// a: the search of one round over the list, on the open (GRID = kmcf_cell_grid) or the periodic index (kmcf_cell_grid_pbc).
+// A group of CH_LPS lanes per member; the loop runs over whole blocks of groups, and both thresholds are uniform over a
+// group, as the walk requires (kmcf_cellwalk.hpp), so its lanes reach the shuffles together.
 // FIRST: round 1 -- components are vertices, the surface marks, direct2.
-template <bool FIRST>
-__global__ __launch_bounds__(KMCF_BLOCK) void ch_search_kernel(kmcf_cell_grid g, const int *__restrict__ cell_start,
+template <bool FIRST, class GRID>
+__global__ __launch_bounds__(KMCF_BLOCK) void ch_search_kernel(GRID g, const int *__restrict__ cell_start,
                                                                const int *__restrict__ lpos, const int *__restrict__ n_list,
                                                                const int *__restrict__ lsite, const int *__restrict__ lvcell,
                                                                const int *__restrict__ lcomp, const double *__restrict__ lx,
@@ -297,7 +279,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void ch_search_kernel(kmcf_cell_grid g,
     const int n = *n_list;
     const int lane = threadIdx.x % CH_LPS;
     const int rows = (n + CH_SPB - 1) / CH_SPB * CH_SPB;
-    const double inf = __longlong_as_double((long long)CH_INF);
+    const double inf = __longlong_as_double((long long)KMCF_D2_INF);
     for (int k = blockIdx.x * CH_SPB + threadIdx.x / CH_LPS; k < rows; k += gridDim.x * CH_SPB) {
         const bool valid = k < n;
         double bd = inf;                    // this lane's minimum (d2, partner)
@@ -310,8 +292,6 @@ __global__ __launch_bounds__(KMCF_BLOCK) void ch_search_kernel(kmcf_cell_grid g,
             vc = lvcell[k];
             comp = lcomp[k];
             const double xa = lx[k], ya = ly[k], za = lz[k];
-            const int cx = kmcf_cell_coord(xa, g.x0, g.inv, g.ncx), cy = kmcf_cell_coord(ya, g.y0, g.inv, g.ncy),
-                      cz = kmcf_cell_coord(za, g.z0, g.inv, g.ncz);
             double thr = rmax2;             // no pair with a larger d2 can be this member's or its component's result
             double thr_dir = -1.0;          // ... or the cell's direct2 (L members of round 1 only)
             int rrep = -1;
@@ -319,35 +299,28 @@ __global__ __launch_bounds__(KMCF_BLOCK) void ch_search_kernel(kmcf_cell_grid g,
                 const int *q = words + (size_t)CH_W_WORDS * vc;
                 is_left = comp == q[CH_W_LREP];
                 rrep = q[CH_W_RREP];
-                if (is_left) thr_dir = fmin(rmax2, __shfl(__longlong_as_double((long long)ch_load(direct + vc)), 0, CH_LPS));
+                if (is_left) thr_dir = fmin(rmax2, __shfl(__longlong_as_double((long long)kmcf_load_relaxed(direct + vc)), 0, CH_LPS));
             } else {
-                // (the group's first lane's read for all of them: the loops below must not part the group's lanes)
-                const double seen = __shfl(__longlong_as_double((long long)ch_load(cbest + comp)), 0, CH_LPS);
+                // (the group's first lane's read for all of them: the walk must not part the group's lanes)
+                const double seen = __shfl(__longlong_as_double((long long)kmcf_load_relaxed(cbest + comp)), 0, CH_LPS);
                 if (seen < thr) thr = seen;
             }
-            for (int ax = max(cx - 1, 0); ax <= min(cx + 1, g.ncx - 1); ++ax) {
-                const double fx = ax == cx ? 0.0 : ch_face_dist(xa, g.x0, g.edge, cx, ax);
-                for (int ay = max(cy - 1, 0); ay <= min(cy + 1, g.ncy - 1); ++ay) {
-                    const double fy = ay == cy ? 0.0 : ch_face_dist(ya, g.y0, g.edge, cy, ay);
-                    const double bound = fx * fx + fy * fy;
-                    if (bound > thr && bound > thr_dir) continue;
-                    // cells (ax, ay, cz-1..cz+1) are contiguous in the cell order: one run
-                    const int c_lo = (ax * g.ncy + ay) * g.ncz + max(cz - 1, 0);
-                    const int c_hi = (ax * g.ncy + ay) * g.ncz + min(cz + 1, g.ncz - 1);
-                    const int b = lpos[cell_start[c_lo]], e = lpos[cell_start[c_hi + 1]];
-                    if (b == e) continue;
+            kmcf_walk_columns(
+                g, xa, ya, za, cell_start, lpos, [&](double bound) { return !(bound > thr && bound > thr_dir); },
+                [&](int b, int e) {
                     for (int t = b + lane; t < e; t += CH_LPS) {
                         if (lvcell[t] != vc) continue;
                         const int ct = lcomp[t];
                         if (ct == comp) continue;
-                        const double dx = xa - lx[t], dy = ya - ly[t], dz = za - lz[t];
-                        const double d2 = (dx * dx + dy * dy) + dz * dz;
+                        const double d2 = kmcf_walk_d2(g, xa, ya, za, lx[t], ly[t], lz[t]);
                         if (d2 <= rmax2) {
                             const int j = lsite[t];
                             if (d2 < bd || (d2 == bd && j < bb)) { bd = d2; bb = j; }
                             if (FIRST && is_left && ct == rrep && d2 < dd) dd = d2;
                         }
                     }
+                },
+                [&]() {
                     double m = bd;
 #pragma unroll
                     for (int off = CH_LPS / 2; off >= 1; off >>= 1) m = fmin(m, __shfl_xor(m, off, 64));
@@ -358,147 +331,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void ch_search_kernel(kmcf_cell_grid g,
                         for (int off = CH_LPS / 2; off >= 1; off >>= 1) md = fmin(md, __shfl_xor(md, off, 64));
                         if (md < thr_dir) thr_dir = md;
                     }
-                }
-            }
-        }
-#pragma unroll
-        for (int off = CH_LPS / 2; off >= 1; off >>= 1) {
-            const double od = __shfl_xor(bd, off, 64);
-            const int ob = __shfl_xor(bb, off, 64);
-            if (od < bd || (od == bd && ob < bb)) { bd = od; bb = ob; }
-            if (FIRST) dd = fmin(dd, __shfl_xor(dd, off, 64));
-        }
-        const bool found = valid && lane == 0 && bb != CH_NO_SITE;
-        if (valid && lane == 0) {
-            ld2[k] = (u64)__double_as_longlong(bd);
-            lj[k] = found ? bb : -1;
-            if (found) atomicMin(cbest + comp, (u64)__double_as_longlong(bd));
-            if (FIRST) {
-                surf[a] = found;
-                if (is_left && dd < inf) atomicMin(direct + vc, (u64)__double_as_longlong(dd));
-            }
-        }
-        if (FIRST) {
-            const u64 fm = __ballot(found);
-            if ((threadIdx.x & 63) == 0 && fm) atomicAdd(flags + CH_F_SURFACE, __popcll(fm));
-        }
-    }
-}
-
-// Lower bound of the minimum-image |v_b - v| over the sites b of a periodic index's cell next to the cell of v, through
-// the face at f (lower: the face below v): the distance to that face, shortened by the relative 1e-9 of ch_face_dist with
-// the period in the scale -- the margin also covers the roundings of the cell rule and of fy * Ly in the distance.
-// (The margin and the rule of the gap's periodic search, kmcf_gap.hip; DESIGN 3.10, "Bound".)
-__device__ __forceinline__ double ch_face_dist_pbc(double v, double f, bool lower, double edge, double period)
-{
-    const double d = (lower ? v - f : f - v) - 1e-9 * (fabs(f) + fabs(v) + edge + period);
-    return d > 0.0 ? d : 0.0;
-}
-
-// a on a periodic index: ch_search_kernel under the minimum image in y and z (kmcf_min_image_dist's arithmetic, squared:
-// odd in the difference up to the squares, so both ends of a pair compute the same bits).  The list, the results and the
-// threshold rules are those of ch_search_kernel.  Cells as in gp_search_pbc_kernel and pairwise_pbc_kernel, each once: in
-// y the distinct cells of {cy-1, cy, cy+1} mod ncy, in z one or two runs of the compacted order; a candidate is met once
-// and has one distance, however many of its images lie within r_max.  Bound in y of a neighbour cell: ncy >= 3 -- the
-// cell below (cy-1 mod ncy) through the lower face of cy, the cell above through the upper face; ncy == 2 -- the other
-// cell is adjacent through both faces: the smaller of the two; own cell (all there is for ncy == 1): 0.  z is not pruned.
-// The x range, the number of y cells, the z runs and the thresholds depend on the member alone or are read by the
-// group's first lane and broadcast: the 16 lanes of a group never part in front of the shuffles; only the walk over a run
-// is per lane.
-template <bool FIRST>
-__global__ __launch_bounds__(KMCF_BLOCK) void ch_search_pbc_kernel(kmcf_cell_grid_pbc g, double edge_x,
-                                                                   const int *__restrict__ cell_start,
-                                                                   const int *__restrict__ lpos, const int *__restrict__ n_list,
-                                                                   const int *__restrict__ lsite, const int *__restrict__ lvcell,
-                                                                   const int *__restrict__ lcomp, const double *__restrict__ lx,
-                                                                   const double *__restrict__ ly, const double *__restrict__ lz,
-                                                                   double rmax2, const int *__restrict__ words, u64 *cbest,
-                                                                   u64 *direct, u64 *__restrict__ ld2, int *__restrict__ lj,
-                                                                   int *__restrict__ surf, int *flags)
-{
-    const int n = *n_list;
-    const int lane = threadIdx.x % CH_LPS;
-    const int rows = (n + CH_SPB - 1) / CH_SPB * CH_SPB;
-    const double inf = __longlong_as_double((long long)CH_INF);
-    const int ny = min(g.ncy, 3);               // y cells a member visits
-    const double edge_y = g.ly / (double)g.ncy;
-    for (int k = blockIdx.x * CH_SPB + threadIdx.x / CH_LPS; k < rows; k += gridDim.x * CH_SPB) {
-        const bool valid = k < n;
-        double bd = inf;                    // this lane's minimum (d2, partner)
-        int bb = CH_NO_SITE;
-        double dd = inf;                    // FIRST, L members: this lane's smallest d2 to an R member of the cell
-        int vc = -1, comp = -1, a = -1;
-        bool is_left = false;
-        if (valid) {
-            a = lsite[k];
-            vc = lvcell[k];
-            comp = lcomp[k];
-            const double xa = lx[k], ya = ly[k], za = lz[k];
-            const int cx = kmcf_cell_coord(xa, g.x0, g.inv_x, g.ncx), cy = kmcf_cell_coord(ya, g.y0, g.inv_y, g.ncy),
-                      cz = kmcf_cell_coord(za, g.z0, g.inv_z, g.ncz);
-            // z runs [lo0, hi0] and, if n_runs == 2, [lo1, hi1]
-            int n_runs = 1, lo0 = cz - 1, hi0 = cz + 1, lo1 = 0, hi1 = -1;
-            if (g.ncz <= 3) { lo0 = 0; hi0 = g.ncz - 1; }
-            else if (cz == 0) { lo0 = 0; hi0 = 1; lo1 = hi1 = g.ncz - 1; n_runs = 2; }
-            else if (cz == g.ncz - 1) { lo0 = 0; hi0 = 0; lo1 = g.ncz - 2; hi1 = g.ncz - 1; n_runs = 2; }
-            const int ay0 = g.ncy == 1 ? cy : cy - 1 + g.ncy;
-            // the faces of the member's cell in y
-            const double below = ch_face_dist_pbc(ya, g.y0 + (double)cy * edge_y, true, edge_y, g.ly);
-            const double above = ch_face_dist_pbc(ya, g.y0 + (double)(cy + 1) * edge_y, false, edge_y, g.ly);
-            double thr = rmax2;             // no pair with a larger d2 can be this member's or its component's result
-            double thr_dir = -1.0;          // ... or the cell's direct2 (L members of round 1 only)
-            int rrep = -1;
-            if (FIRST) {
-                const int *q = words + (size_t)CH_W_WORDS * vc;
-                is_left = comp == q[CH_W_LREP];
-                rrep = q[CH_W_RREP];
-                if (is_left) thr_dir = fmin(rmax2, __shfl(__longlong_as_double((long long)ch_load(direct + vc)), 0, CH_LPS));
-            } else {
-                // (the group's first lane's read for all of them: the loops below must not part the group's lanes)
-                const double seen = __shfl(__longlong_as_double((long long)ch_load(cbest + comp)), 0, CH_LPS);
-                if (seen < thr) thr = seen;
-            }
-            for (int ax = max(cx - 1, 0); ax <= min(cx + 1, g.ncx - 1); ++ax) {
-                const double fx = ax == cx ? 0.0 : ch_face_dist(xa, g.x0, edge_x, cx, ax);
-                for (int sy = 0; sy < ny; ++sy) {
-                    const int ay = (ay0 + sy) % g.ncy;
-                    const double fy = ay == cy ? 0.0 : (g.ncy == 2 ? fmin(below, above) : (sy == 0 ? below : above));
-                    const double bound = fx * fx + fy * fy;
-                    if (bound > thr && bound > thr_dir) continue;
-                    const int col = (ax * g.ncy + ay) * g.ncz;
-                    for (int run = 0; run < n_runs; ++run) {
-                        const int b = lpos[cell_start[col + (run ? lo1 : lo0)]];
-                        const int e = lpos[cell_start[col + (run ? hi1 : hi0) + 1]];
-                        for (int t = b + lane; t < e; t += CH_LPS) {
-                            if (lvcell[t] != vc) continue;
-                            const int ct = lcomp[t];
-                            if (ct == comp) continue;
-                            const double dx = xa - lx[t];
-                            double qy = (ya - ly[t]) / g.ly;
-                            qy -= round(qy);
-                            double qz = (za - lz[t]) / g.lz;
-                            qz -= round(qz);
-                            const double dy = qy * g.ly, dz = qz * g.lz;
-                            const double d2 = (dx * dx + dy * dy) + dz * dz;
-                            if (d2 <= rmax2) {
-                                const int j = lsite[t];
-                                if (d2 < bd || (d2 == bd && j < bb)) { bd = d2; bb = j; }
-                                if (FIRST && is_left && ct == rrep && d2 < dd) dd = d2;
-                            }
-                        }
-                    }
-                    double m = bd;
-#pragma unroll
-                    for (int off = CH_LPS / 2; off >= 1; off >>= 1) m = fmin(m, __shfl_xor(m, off, 64));
-                    if (m < thr) thr = m;
-                    if (FIRST && is_left) {
-                        double md = dd;
-#pragma unroll
-                        for (int off = CH_LPS / 2; off >= 1; off >>= 1) md = fmin(md, __shfl_xor(md, off, 64));
-                        if (md < thr_dir) thr_dir = md;
-                    }
-                }
-            }
+                });
         }
 #pragma unroll
         for (int off = CH_LPS / 2; off >= 1; off >>= 1) {
@@ -546,8 +379,8 @@ __global__ __launch_bounds__(KMCF_BLOCK) void ch_hook_kernel(int N, const int *_
     const int v = blockIdx.x * KMCF_BLOCK + threadIdx.x;
     if (v >= N) return;
     int to = v;
-    const u64 pr = root[v] == v ? cpair[v] : CH_NO_PAIR;          // (a site that is no vertex has no pair)
-    if (pr != CH_NO_PAIR) {
+    const u64 pr = root[v] == v ? cpair[v] : KMCF_NO_PAIR;          // (a site that is no vertex has no pair)
+    if (pr != KMCF_NO_PAIR) {
         ch_edge e;
         e.d2 = cbest[v];
         e.a = (int)(pr >> 32);
@@ -581,8 +414,8 @@ __global__ __launch_bounds__(KMCF_BLOCK) void ch_jump_kernel(int N, const int *_
     }
     if (next[r] != r) atomicOr(flags + CH_F_ERROR, 2);
     root[v] = r;
-    cbest[v] = CH_INF;
-    cpair[v] = CH_NO_PAIR;
+    cbest[v] = KMCF_D2_INF;
+    cpair[v] = KMCF_NO_PAIR;
 }
 
 // e
@@ -695,29 +528,17 @@ int ch_search(const char *what, kmcf_pairwise *p, const double *d_x, const doubl
     ch_vertex_kernel<<<site_grid, KMCF_BLOCK, 0, st>>>(N, d_side, d_node, d_site_cell, n_cells, w->d_home, w->d_words, w->d_svert,
                                                       w->d_svcell);
     ch_compact(p, nullptr, d_x, d_y, d_z);
+    const auto search = [&](auto grid, bool first) {     // step a: the instantiation for the index and the round
+        const auto kernel = first ? ch_search_kernel<true, decltype(grid)> : ch_search_kernel<false, decltype(grid)>;
+        kernel<<<search_grid, KMCF_BLOCK, 0, st>>>(grid, p->d_cell_start, w->d_lpos, n_list, w->d_lsite, w->d_lvcell, w->d_lcomp,
+                                                  w->d_lx, w->d_ly, w->d_lz, rmax2, w->d_words, w->d_cbest, w->d_direct, w->d_ld2,
+                                                  w->d_lj, w->d_surf, w->d_flags);
+    };
     int h[CH_F_WORDS];
     int edges_before = 0;
     for (int round = 1; round <= CH_MAX_ROUNDS; ++round) {
-        if (p->pbc && round == 1)
-            ch_search_pbc_kernel<true><<<search_grid, KMCF_BLOCK, 0, st>>>(p->grid_pbc(), p->cutoff, p->d_cell_start, w->d_lpos, n_list,
-                                                                          w->d_lsite, w->d_lvcell, w->d_lcomp, w->d_lx, w->d_ly,
-                                                                          w->d_lz, rmax2, w->d_words, w->d_cbest, w->d_direct,
-                                                                          w->d_ld2, w->d_lj, w->d_surf, w->d_flags);
-        else if (p->pbc)
-            ch_search_pbc_kernel<false><<<search_grid, KMCF_BLOCK, 0, st>>>(p->grid_pbc(), p->cutoff, p->d_cell_start, w->d_lpos, n_list,
-                                                                           w->d_lsite, w->d_lvcell, w->d_lcomp, w->d_lx, w->d_ly,
-                                                                           w->d_lz, rmax2, w->d_words, w->d_cbest, w->d_direct,
-                                                                           w->d_ld2, w->d_lj, w->d_surf, w->d_flags);
-        else if (round == 1)
-            ch_search_kernel<true><<<search_grid, KMCF_BLOCK, 0, st>>>(p->grid(), p->d_cell_start, w->d_lpos, n_list, w->d_lsite,
-                                                                      w->d_lvcell, w->d_lcomp, w->d_lx, w->d_ly, w->d_lz, rmax2,
-                                                                      w->d_words, w->d_cbest, w->d_direct, w->d_ld2, w->d_lj,
-                                                                      w->d_surf, w->d_flags);
-        else
-            ch_search_kernel<false><<<search_grid, KMCF_BLOCK, 0, st>>>(p->grid(), p->d_cell_start, w->d_lpos, n_list, w->d_lsite,
-                                                                       w->d_lvcell, w->d_lcomp, w->d_lx, w->d_ly, w->d_lz, rmax2,
-                                                                       w->d_words, w->d_cbest, w->d_direct, w->d_ld2, w->d_lj,
-                                                                       w->d_surf, w->d_flags);
+        if (p->pbc) search(p->grid_pbc(), round == 1);
+        else search(p->grid(), round == 1);
         ch_pair_kernel<<<list_grid, KMCF_BLOCK, 0, st>>>(n_list, w->d_lsite, w->d_lcomp, w->d_ld2, w->d_lj, w->d_cbest, w->d_cpair);
         ch_hook_kernel<<<site_grid, KMCF_BLOCK, 0, st>>>(N, w->d_svert, w->d_root, w->d_cbest, w->d_cpair, w->d_next, w->d_edges,
                                                         w->d_flags);

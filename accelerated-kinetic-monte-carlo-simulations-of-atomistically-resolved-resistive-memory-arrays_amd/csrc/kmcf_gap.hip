@@ -10,9 +10,10 @@
 //   3-5  compact, per INDEX cell (the cells of kmcf_compute_cutoff_list), the B members with their coordinates and gap
 //        cell, and the A members: the tile compaction of kmcf_block.hpp (two sets in one pass), on scratch of this file's own
 //        (kmcf_poisson_gridless keeps its lists)
-//   6    search: 16 lanes per A site walk the contiguous runs of the 27 surrounding index cells (r_max <= cell edge),
-//        every lane keeps its lexicographic minimum (d2, b); the group's minimum is stored per A site and lowers the gap
-//        cell's best d2 with a 64-bit integer atomicMin on the bit pattern (non-negative doubles order as integers)
+//   6    search: 16 lanes per A site walk the contiguous runs of the 27 surrounding index cells (r_max <= cell edge;
+//        kmcf_walk_columns of kmcf_cellwalk.hpp), every lane keeps its lexicographic minimum (d2, b); the group's minimum is
+//        stored per A site and lowers the gap cell's best d2 with a 64-bit integer atomicMin on the bit pattern
+//        (non-negative doubles order as integers)
 //   7    among the A sites that attain their cell's d2, the smallest packed (a << 32 | b) wins (atomicMin again)
 //   8    the records; 9 (kmcf_filament_gap with a profile) the histogram
 //
@@ -24,15 +25,16 @@
 // whose stored minimum may be too large or missing -- never enter step 7.  The result does not depend on what was read.
 //
 // Periodic index (kmcf_site_set_gap_pbc / kmcf_filament_gap_pbc on an index of kmcf_compute_cutoff_list_pbc with pbc = 1):
-// step 6 is gp_search_pbc_kernel -- the minimum image in y and z, the wrapped cells each once, the bound in y taken to
-// the face through which the neighbour cell is adjacent ("Periodic search"); every other step is shared.
+// step 6 is gp_search_kernel on the periodic geometry (kmcf_cell_grid_pbc) -- the minimum image in y and z, the wrapped
+// cells each once, the bound in y taken to the face through which the neighbour cell is adjacent ("Periodic
+// search"); every other step, and everything in step 6 but the walk and the distance, is shared.
 //
 // Determinism: counts are integer adds, the minimum d2 and the packed pair are integer minima: every output is
 // independent of the execution order.  No thread waits for another.
 #include <cmath>
 #include <limits>
 
-#include "kmcf_internal.hpp"
+#include "kmcf_cellwalk.hpp"
 
 static_assert(sizeof(kmcf_gap_t) == 56, "kmcf_gap_t is 56 bytes");
 
@@ -69,17 +71,8 @@ namespace {
 
 typedef unsigned long long u64;
 constexpr int GP_LPS = 16, GP_SPB = KMCF_BLOCK / GP_LPS;          // lanes per A site, A sites per block
-constexpr u64 GP_INF = 0x7ff0000000000000ull;                    // bits of +infinity
-constexpr u64 GP_NO_PAIR = ~0ull;
 constexpr int GP_KIND_VACANCY = KMCF_CLUSTER_VACANCY;
 enum { GP_STAT_LEFT, GP_STAT_RIGHT, GP_STAT_BOTH, GP_STAT_BRIDGED, GP_STAT_OPEN, GP_STAT_NONE, GP_STAT_WORDS = 8 };
-
-// gap cell of a site, -1: none
-__device__ __forceinline__ int gp_cell(const int *__restrict__ site_cell, int n_cells, int i)
-{
-    const int c = site_cell ? site_cell[i] : 0;
-    return (unsigned)c < (unsigned)n_cells ? c : -1;
-}
 
 // the sides: touch word of the site's cluster, 0 for non-members
 __global__ __launch_bounds__(KMCF_BLOCK) void gp_side_kernel(int N, const unsigned char *__restrict__ cls,
@@ -96,8 +89,8 @@ __global__ __launch_bounds__(KMCF_BLOCK) void gp_clear_kernel(size_t n_cells, u6
 {
     const size_t c = (size_t)blockIdx.x * KMCF_BLOCK + threadIdx.x;
     if (c < n_cells) {
-        best[c] = GP_INF;
-        pair[c] = GP_NO_PAIR;
+        best[c] = KMCF_D2_INF;
+        pair[c] = KMCF_NO_PAIR;
         cnt[3 * c] = cnt[3 * c + 1] = cnt[3 * c + 2] = 0;
     }
     if (blockIdx.x == 0 && threadIdx.x < GP_STAT_WORDS) stats[threadIdx.x] = 0;
@@ -110,7 +103,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void gp_count_kernel(int N, const int *
     const int i = blockIdx.x * KMCF_BLOCK + threadIdx.x;
     const int lane = threadIdx.x & 63;
     const int s = i < N ? (side[i] & 3) : 0;
-    const int c = s ? gp_cell(site_cell, n_cells, i) : -1;
+    const int c = s ? kmcf_site_cell(site_cell, n_cells, i) : -1;
     const u64 d1 = __ballot(s & 1), d2 = __ballot(s & 2), d3 = __ballot(s == 3);
     if (lane == 0) {
         if (d1) atomicAdd(stats + GP_STAT_LEFT, __popcll(d1));
@@ -138,7 +131,7 @@ constexpr int GP_A = 1, GP_B = 2;
 __device__ __forceinline__ int gp_flags(const int *__restrict__ side, const int *__restrict__ site_cell, int n_cells, int i)
 {
     const int s = side[i] & 3;
-    return (s && gp_cell(site_cell, n_cells, i) >= 0) ? s : 0;
+    return (s && kmcf_site_cell(site_cell, n_cells, i) >= 0) ? s : 0;
 }
 
 // 3: per-tile counts of the A and of the B members (index-cell order): the A counts in sum[0, nb), the B counts in
@@ -182,7 +175,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void gp_scatter_kernel(int N, int nb, c
         bpos[t] = pb;
         if (!f[k]) continue;
         const int i = site[k];
-        const int c = gp_cell(site_cell, n_cells, i);
+        const int c = kmcf_site_cell(site_cell, n_cells, i);
         if (f[k] & GP_A) {
             alist[pa] = i;
             acell[pa] = c;
@@ -200,20 +193,11 @@ __global__ __launch_bounds__(KMCF_BLOCK) void gp_scatter_kernel(int N, int nb, c
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x == KMCF_BLOCK - 1) bpos[N] = sum[2 * nb + 1];
 }
 
-// Lower bound of |v_b - v| over the sites b of index cell column `a` next to the column `c` of v (a = c - 1 or c + 1):
-// the distance to the face between them, shortened by far more than the cell rule can misplace a site (relative 1e-9).
-__device__ __forceinline__ double gp_face_dist(double v, double v0, double edge, int c, int a)
-{
-    const double f = v0 + (double)(a > c ? c + 1 : c) * edge;
-    const double d = (a > c ? f - v : v - f) - 1e-9 * (fabs(f) + fabs(v) + edge);
-    return d > 0.0 ? d : 0.0;
-}
-
-__device__ __forceinline__ u64 gp_load(const u64 *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// 6: the search.  A group of GP_LPS lanes per A member; the loop runs over whole blocks of groups, so every lane of a wave
-// reaches the shuffles behind it.
-__global__ __launch_bounds__(KMCF_BLOCK) void gp_search_kernel(kmcf_cell_grid g, const int *__restrict__ cell_start,
+// 6: the search, on the open (GRID = kmcf_cell_grid) or the periodic index (kmcf_cell_grid_pbc: the minimum image in y and
+// z).  A group of GP_LPS lanes per A member; the loop runs over whole blocks of groups, so every lane of a wave reaches the
+// shuffles behind it.  The threshold is uniform over a group, as the walk requires (kmcf_cellwalk.hpp).
+template <class GRID>
+__global__ __launch_bounds__(KMCF_BLOCK) void gp_search_kernel(GRID g, const int *__restrict__ cell_start,
                                                                const int *__restrict__ bpos, const int *__restrict__ n_a,
                                                                const int *__restrict__ alist, const int *__restrict__ acell,
                                                                const int *__restrict__ bsite, const int *__restrict__ bcell,
@@ -226,7 +210,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void gp_search_kernel(kmcf_cell_grid g,
     const int nA = *n_a;
     const int lane = threadIdx.x % GP_LPS;
     const int rows = (nA + GP_SPB - 1) / GP_SPB * GP_SPB;
-    const double inf = __longlong_as_double((long long)GP_INF);
+    const double inf = __longlong_as_double((long long)KMCF_D2_INF);
     for (int k = blockIdx.x * GP_SPB + threadIdx.x / GP_LPS; k < rows; k += gridDim.x * GP_SPB) {
         const bool valid = k < nA;
         double bd = inf;                    // this lane's minimum (d2, b)
@@ -236,142 +220,28 @@ __global__ __launch_bounds__(KMCF_BLOCK) void gp_search_kernel(kmcf_cell_grid g,
             const int a = alist[k];
             ca = acell[k];
             const double xa = x[a], ya = y[a], za = z[a];
-            const int cx = kmcf_cell_coord(xa, g.x0, g.inv, g.ncx), cy = kmcf_cell_coord(ya, g.y0, g.inv, g.ncy),
-                      cz = kmcf_cell_coord(za, g.z0, g.inv, g.ncz);
             double thr = rmax2;             // no pair with a larger d2 can be the result (uniform over the group)
-            // (the group's first lane's read for all of them: the loops below must not part the group's lanes)
-            const double seen = __shfl(__longlong_as_double((long long)gp_load(best + ca)), 0, GP_LPS);
+            // (the group's first lane's read for all of them: the walk must not part the group's lanes)
+            const double seen = __shfl(__longlong_as_double((long long)kmcf_load_relaxed(best + ca)), 0, GP_LPS);
             if (seen < thr) thr = seen;
-            for (int ax = max(cx - 1, 0); ax <= min(cx + 1, g.ncx - 1); ++ax) {
-                const double lx = ax == cx ? 0.0 : gp_face_dist(xa, g.x0, g.edge, cx, ax);
-                for (int ay = max(cy - 1, 0); ay <= min(cy + 1, g.ncy - 1); ++ay) {
-                    const double ly = ay == cy ? 0.0 : gp_face_dist(ya, g.y0, g.edge, cy, ay);
-                    if (lx * lx + ly * ly > thr) continue;
-                    // cells (ax, ay, cz-1..cz+1) are contiguous in the cell order: one run
-                    const int c_lo = (ax * g.ncy + ay) * g.ncz + max(cz - 1, 0);
-                    const int c_hi = (ax * g.ncy + ay) * g.ncz + min(cz + 1, g.ncz - 1);
-                    const int b = bpos[cell_start[c_lo]], e = bpos[cell_start[c_hi + 1]];
-                    if (b == e) continue;
+            kmcf_walk_columns(
+                g, xa, ya, za, cell_start, bpos, [&](double bound) { return !(bound > thr); },
+                [&](int b, int e) {
                     for (int t = b + lane; t < e; t += GP_LPS) {
                         if (bcell[t] != ca) continue;
-                        const double dx = xa - bx[t], dy = ya - by[t], dz = za - bz[t];
-                        const double d2 = (dx * dx + dy * dy) + dz * dz;
+                        const double d2 = kmcf_walk_d2(g, xa, ya, za, bx[t], by[t], bz[t]);
                         if (d2 <= rmax2) {
                             const int j = bsite[t];                  // (j == a is a pair like any other)
                             if (d2 < bd || (d2 == bd && j < bb)) { bd = d2; bb = j; }
                         }
                     }
+                },
+                [&]() {
                     double m = bd;
 #pragma unroll
                     for (int off = GP_LPS / 2; off >= 1; off >>= 1) m = fmin(m, __shfl_xor(m, off, 64));
                     if (m < thr) thr = m;
-                }
-            }
-        }
-#pragma unroll
-        for (int off = GP_LPS / 2; off >= 1; off >>= 1) {
-            const double od = __shfl_xor(bd, off, 64);
-            const int ob = __shfl_xor(bb, off, 64);
-            if (od < bd || (od == bd && ob < bb)) { bd = od; bb = ob; }
-        }
-        if (valid && lane == 0) {
-            const bool found = bb != 0x7fffffff;
-            const u64 bits = (u64)__double_as_longlong(bd);
-            ad2[k] = bits;
-            ab[k] = found ? bb : -1;
-            if (found) atomicMin(best + ca, bits);
-        }
-    }
-}
-
-// Lower bound of the minimum-image |v_b - v| over the sites b of a periodic index's cell next to the cell of v, through
-// the face at f (lower: the face below v): the distance to that face, shortened by the relative 1e-9 of gp_face_dist, the
-// period included in the scale -- the margin also covers the roundings of the cell rule and of fy * Ly in the distance.
-__device__ __forceinline__ double gp_face_dist_pbc(double v, double f, bool lower, double edge, double period)
-{
-    const double d = (lower ? v - f : f - v) - 1e-9 * (fabs(f) + fabs(v) + edge + period);
-    return d > 0.0 ? d : 0.0;
-}
-
-// 6 on a periodic index: the search under the minimum image in y and z (kmcf_min_image_dist's arithmetic, squared).
-// Cells as in pairwise_pbc_kernel, each once: in y the distinct cells of {cy-1, cy, cy+1} mod ncy, in z the runs of the
-// compacted order.  All loop bounds and the pruning threshold depend on the member alone, so the 16 lanes of a group
-// never part in front of the shuffles; only the walk over a run is per lane.
-// Bound in y of a neighbour cell: ncy >= 3 -- the cell below (cy-1 mod ncy) is adjacent through the lower face of cy, the
-// cell above through the upper face, and the way round the period is at least one cell edge longer than either; ncy == 2
-// -- the other cell is adjacent through both faces: the smaller of the two; own cell (all there is for ncy == 1): 0.
-__global__ __launch_bounds__(KMCF_BLOCK) void gp_search_pbc_kernel(kmcf_cell_grid_pbc g, double edge_x,
-                                                                   const int *__restrict__ cell_start,
-                                                                   const int *__restrict__ bpos, const int *__restrict__ n_a,
-                                                                   const int *__restrict__ alist, const int *__restrict__ acell,
-                                                                   const int *__restrict__ bsite, const int *__restrict__ bcell,
-                                                                   const double *__restrict__ bx, const double *__restrict__ by,
-                                                                   const double *__restrict__ bz, const double *__restrict__ x,
-                                                                   const double *__restrict__ y, const double *__restrict__ z,
-                                                                   double rmax2, u64 *best, u64 *__restrict__ ad2,
-                                                                   int *__restrict__ ab)
-{
-    const int nA = *n_a;
-    const int lane = threadIdx.x % GP_LPS;
-    const int rows = (nA + GP_SPB - 1) / GP_SPB * GP_SPB;
-    const double inf = __longlong_as_double((long long)GP_INF);
-    const int ny = min(g.ncy, 3);               // y cells a member visits
-    const double edge_y = g.ly / (double)g.ncy;
-    for (int k = blockIdx.x * GP_SPB + threadIdx.x / GP_LPS; k < rows; k += gridDim.x * GP_SPB) {
-        const bool valid = k < nA;
-        double bd = inf;                    // this lane's minimum (d2, b)
-        int bb = 0x7fffffff;
-        int ca = -1;
-        if (valid) {
-            const int a = alist[k];
-            ca = acell[k];
-            const double xa = x[a], ya = y[a], za = z[a];
-            const int cx = kmcf_cell_coord(xa, g.x0, g.inv_x, g.ncx), cy = kmcf_cell_coord(ya, g.y0, g.inv_y, g.ncy),
-                      cz = kmcf_cell_coord(za, g.z0, g.inv_z, g.ncz);
-            // z runs [lo0, hi0] and, if n_runs == 2, [lo1, hi1]
-            int n_runs = 1, lo0 = cz - 1, hi0 = cz + 1, lo1 = 0, hi1 = -1;
-            if (g.ncz <= 3) { lo0 = 0; hi0 = g.ncz - 1; }
-            else if (cz == 0) { lo0 = 0; hi0 = 1; lo1 = hi1 = g.ncz - 1; n_runs = 2; }
-            else if (cz == g.ncz - 1) { lo0 = 0; hi0 = 0; lo1 = g.ncz - 2; hi1 = g.ncz - 1; n_runs = 2; }
-            const int ay0 = g.ncy == 1 ? cy : cy - 1 + g.ncy;
-            // the faces of the member's cell in y
-            const double below = gp_face_dist_pbc(ya, g.y0 + (double)cy * edge_y, true, edge_y, g.ly);
-            const double above = gp_face_dist_pbc(ya, g.y0 + (double)(cy + 1) * edge_y, false, edge_y, g.ly);
-            double thr = rmax2;             // no pair with a larger d2 can be the result (uniform over the group)
-            // (the group's first lane's read for all of them: the loops below must not part the group's lanes)
-            const double seen = __shfl(__longlong_as_double((long long)gp_load(best + ca)), 0, GP_LPS);
-            if (seen < thr) thr = seen;
-            for (int ax = max(cx - 1, 0); ax <= min(cx + 1, g.ncx - 1); ++ax) {
-                const double lx = ax == cx ? 0.0 : gp_face_dist(xa, g.x0, edge_x, cx, ax);
-                for (int sy = 0; sy < ny; ++sy) {
-                    const int ay = (ay0 + sy) % g.ncy;
-                    const double ly = ay == cy ? 0.0 : (g.ncy == 2 ? fmin(below, above) : (sy == 0 ? below : above));
-                    if (lx * lx + ly * ly > thr) continue;
-                    const int col = (ax * g.ncy + ay) * g.ncz;
-                    for (int run = 0; run < n_runs; ++run) {
-                        const int b = bpos[cell_start[col + (run ? lo1 : lo0)]];
-                        const int e = bpos[cell_start[col + (run ? hi1 : hi0) + 1]];
-                        for (int t = b + lane; t < e; t += GP_LPS) {
-                            if (bcell[t] != ca) continue;
-                            const double dx = xa - bx[t];
-                            double fy = (ya - by[t]) / g.ly;
-                            fy -= round(fy);
-                            double fz = (za - bz[t]) / g.lz;
-                            fz -= round(fz);
-                            const double dy = fy * g.ly, dz = fz * g.lz;
-                            const double d2 = (dx * dx + dy * dy) + dz * dz;
-                            if (d2 <= rmax2) {
-                                const int j = bsite[t];                  // (j == a is a pair like any other)
-                                if (d2 < bd || (d2 == bd && j < bb)) { bd = d2; bb = j; }
-                            }
-                        }
-                    }
-                    double m = bd;
-#pragma unroll
-                    for (int off = GP_LPS / 2; off >= 1; off >>= 1) m = fmin(m, __shfl_xor(m, off, 64));
-                    if (m < thr) thr = m;
-                }
-            }
+                });
         }
 #pragma unroll
         for (int off = GP_LPS / 2; off >= 1; off >>= 1) {
@@ -416,8 +286,8 @@ __global__ __launch_bounds__(KMCF_BLOCK) void gp_record_kernel(size_t n_cells, c
         const u64 pr = pair[c];
         r.n_left = cnt[3 * c]; r.n_right = cnt[3 * c + 1]; r.n_both = cnt[3 * c + 2];
         r.bridged = r.n_both > 0;
-        if (pr == GP_NO_PAIR) {
-            r.gap = r.gap2 = __longlong_as_double((long long)GP_INF);
+        if (pr == KMCF_NO_PAIR) {
+            r.gap = r.gap2 = __longlong_as_double((long long)KMCF_D2_INF);
             r.x_left = r.x_right = 0.0;
             r.site_left = r.site_right = -1;
         } else {
@@ -429,7 +299,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void gp_record_kernel(size_t n_cells, c
             r.x_right = x[r.site_right];
         }
         gaps[c] = r;
-        state = r.bridged ? 0 : (pr == GP_NO_PAIR ? 2 : 1);
+        state = r.bridged ? 0 : (pr == KMCF_NO_PAIR ? 2 : 1);
     }
     const u64 m0 = __ballot(state == 0), m1 = __ballot(state == 1), m2 = __ballot(state == 2);
     if ((threadIdx.x & 63) == 0) {
@@ -449,7 +319,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void gp_profile_kernel(int N, const uns
     if (i >= N || cls[i] != GP_KIND_VACANCY) return;
     const int s = side[i] & 3;
     if (!s) return;
-    const int c = gp_cell(site_cell, n_cells, i);
+    const int c = kmcf_site_cell(site_cell, n_cells, i);
     if (c < 0) return;
     const double t = (x[i] - x_lo) * inv_w;
     if (t >= 0.0 && t < (double)n_bins) atomicAdd(prof + ((size_t)c * n_bins + (int)t) * 3 + (s - 1), 1);
@@ -533,15 +403,13 @@ int gp_enqueue(kmcf_pairwise *p, const double *d_x, const double *d_y, const dou
     gp_scatter_kernel<<<nb, KMCF_BLOCK, 0, st>>>(N, nb, p->d_cell_order, d_side, d_site_cell, n_cells, d_x, d_y, d_z, w->d_sum,
                                                 w->d_bpos, w->d_alist, w->d_acell, w->d_bsite, w->d_bcell, w->d_bx, w->d_by,
                                                 w->d_bz);
-    if (p->pbc)
-        gp_search_pbc_kernel<<<(int)search_grid, KMCF_BLOCK, 0, st>>>(p->grid_pbc(), p->cutoff, p->d_cell_start, w->d_bpos, n_a,
-                                                                     w->d_alist, w->d_acell, w->d_bsite, w->d_bcell, w->d_bx,
-                                                                     w->d_by, w->d_bz, d_x, d_y, d_z, r_max * r_max, w->d_best,
-                                                                     w->d_ad2, w->d_ab);
-    else
-        gp_search_kernel<<<(int)search_grid, KMCF_BLOCK, 0, st>>>(p->grid(), p->d_cell_start, w->d_bpos, n_a, w->d_alist,
-                                                                 w->d_acell, w->d_bsite, w->d_bcell, w->d_bx, w->d_by, w->d_bz,
-                                                                 d_x, d_y, d_z, r_max * r_max, w->d_best, w->d_ad2, w->d_ab);
+    const auto search = [&](auto grid) {
+        gp_search_kernel<<<(int)search_grid, KMCF_BLOCK, 0, st>>>(grid, p->d_cell_start, w->d_bpos, n_a, w->d_alist, w->d_acell,
+                                                                 w->d_bsite, w->d_bcell, w->d_bx, w->d_by, w->d_bz, d_x, d_y, d_z,
+                                                                 r_max * r_max, w->d_best, w->d_ad2, w->d_ab);
+    };
+    if (p->pbc) search(p->grid_pbc());
+    else search(p->grid());
     gp_pair_kernel<<<(int)pair_grid, KMCF_BLOCK, 0, st>>>(n_a, w->d_alist, w->d_acell, w->d_ad2, w->d_ab, w->d_best, w->d_pair);
     gp_record_kernel<<<cell_grid, KMCF_BLOCK, 0, st>>>(nc, w->d_best, w->d_pair, w->d_cnt, d_x, w->d_gaps, w->d_stats);
     if (profile) {

@@ -85,12 +85,8 @@ struct disp_min_image {
                                                double &dy, double &dz) const
     {
         dx = xj - xi;
-        double fy = (yj - yi) / ly;
-        fy -= round(fy);
-        double fz = (zj - zi) / lz;
-        fz -= round(fz);
-        dy = fy * ly;
-        dz = fz * lz;
+        dy = kmcf_min_image(yj - yi, ly);
+        dz = kmcf_min_image(zj - zi, lz);
     }
 };
 
@@ -98,12 +94,6 @@ struct disp_min_image {
 __device__ __forceinline__ u64 gr_key(double v)
 {
     return (v >= 0.0 && v < __longlong_as_double(0x7ff0000000000000ll)) ? (u64)__double_as_longlong(v) + 1 : 0;
-}
-
-__device__ __forceinline__ int gr_cell(const int *__restrict__ site_cell, int n_cells, int i)
-{
-    const int c = site_cell ? site_cell[i] : 0;
-    return (unsigned)c < (unsigned)n_cells ? c : -1;
 }
 
 __device__ __forceinline__ void gr_raise(kmcf_gr_row *r, u64 gk, u64 dk, int ns, int nf)
@@ -219,7 +209,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void gr_walk_kernel(
                 const u64 gk = gr_key(gm), dk = bj >= 0 ? gr_key(drop) : 0;
                 a_gk[0] = max(a_gk[0], gk); a_dk[0] = max(a_dk[0], dk);
                 ++a_ns[0]; a_nf[0] += full; a_nd += (cnt >= 3 && !full); a_pairs += (u64)cnt;
-                const int c = gr_cell(site_cell, n_cells, i);
+                const int c = kmcf_site_cell(site_cell, n_cells, i);
                 if (c >= 0) {
                     if (c != a_cell) {
                         if (a_cell >= 0) gr_raise(rows + a_cell, a_gk[1], a_dk[1], a_ns[1], a_nf[1]);
@@ -269,10 +259,10 @@ __global__ __launch_bounds__(KMCF_BLOCK) void gr_walk_kernel(
 
 __device__ __forceinline__ void gr_pick_row(kmcf_gr_row *r, int i, u64 gk, u64 dk, int to)
 {
-    if (gk && gk == r->gkey && i < __hip_atomic_load(&r->gsite, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&r->gsite, i);
+    if (gk && gk == r->gkey && i < kmcf_load_relaxed(&r->gsite)) atomicMin(&r->gsite, i);
     if (dk && dk == r->dkey) {
         const u64 pr = ((u64)(unsigned)i << 32) | (unsigned)to;
-        if (pr < __hip_atomic_load(&r->dpair, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&r->dpair, pr);
+        if (pr < kmcf_load_relaxed(&r->dpair)) atomicMin(&r->dpair, pr);
     }
 }
 
@@ -287,7 +277,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void gr_pick_kernel(int N, const int *_
         const int to = dto[i];
         const u64 gk = gr_key(gm[i]), dk = to >= 0 ? gr_key(drop[i]) : 0;
         gr_pick_row(rows + n_cells, i, gk, dk, to);
-        const int c = gr_cell(site_cell, n_cells, i);
+        const int c = kmcf_site_cell(site_cell, n_cells, i);
         if (c >= 0) gr_pick_row(rows + c, i, gk, dk, to);
     }
 }

@@ -252,8 +252,9 @@ inline int kmcf_grid1d(int64_t n, int cap = 2048)
 
 // Spatial index of the sites (kmcf_pairwise.hip: kmcf_compute_cutoff_list): cells of edge `cutoff`, cell id
 // (cx * ncy + cy) * ncz + cz, so the cells (cx, cy, cz-1..cz+1) are one contiguous run of d_cell_order.
-// kmcf_cell_grid is what the kernels that walk it take (pairwise_kernel, gp_search_kernel): origin, inverse edge, edge,
-// cell counts; kmcf_cell_coord is the cell rule along one axis.
+// kmcf_cell_grid is what the kernels that walk it take (pairwise_kernel, gp_search_kernel, ch_search_kernel, through
+// kmcf_walk_columns of kmcf_cellwalk.hpp): origin, inverse edge, edge, cell counts; kmcf_cell_coord is the cell rule along
+// one axis.
 struct kmcf_cell_grid {
     double x0, y0, z0, inv, edge;
     int ncx, ncy, ncz;
@@ -268,8 +269,9 @@ __host__ __device__ inline int kmcf_cell_coord(double v, double v0, double inv, 
 // A periodic index (kmcf_compute_cutoff_list_pbc, pbc == 1) keeps x as above; in y and z its cells tile one period
 // [y0, y0 + Ly) exactly: ncy = max(1, floor(Ly / cutoff)) cells of width Ly / ncy >= cutoff, coordinate
 // kmcf_cell_coord(y, y0, ncy / Ly, ncy).  Same cell id, same order inside a cell: the compaction kernels are shared.
+// edge_x is the cell edge in x (the cutoff); the edges in y and z follow from the periods.
 struct kmcf_cell_grid_pbc {
-    double x0, y0, z0, inv_x, inv_y, inv_z, ly, lz;
+    double x0, y0, z0, inv_x, inv_y, inv_z, edge_x, ly, lz;
     int ncx, ncy, ncz;
 };
 
@@ -292,7 +294,7 @@ struct kmcf_pairwise {
     struct kmcf_gap_ws *gap_ws = nullptr;   // scratch of kmcf_site_set_gap / kmcf_filament_gap (kmcf_gap.hip): buffers only
     struct kmcf_chain_ws *chain_ws = nullptr;   // scratch of kmcf_site_set_chain / kmcf_filament_chain (kmcf_chain.hip): buffers only
     kmcf_cell_grid grid() const { return kmcf_cell_grid{x0, y0, z0, inv, cutoff, ncx, ncy, ncz}; }
-    kmcf_cell_grid_pbc grid_pbc() const { return kmcf_cell_grid_pbc{x0, y0, z0, inv, inv_y, inv_z, lattice[1], lattice[2], ncx, ncy, ncz}; }
+    kmcf_cell_grid_pbc grid_pbc() const { return kmcf_cell_grid_pbc{x0, y0, z0, inv, inv_y, inv_z, cutoff, lattice[1], lattice[2], ncx, ncy, ncz}; }
 };
 void kmcf_gap_ws_free(kmcf_pairwise *p);
 void kmcf_chain_ws_free(kmcf_pairwise *p);
@@ -793,18 +795,32 @@ inline hipStream_t kmcf_setup_stream(const kmcf_comm *c) { return c->caller_stre
 #if defined(__HIPCC__)
 // The reference's four-argument site_dist_gpu with pbc == 1 (src/gpu_solvers.h:287-319), operation for operation: x is
 // never periodic, y and z take the minimum image through round() -- the C round, half away from zero.  One distance for
-// the K pattern, the periodic neighbour list, the periodic pairwise term and the periodic event list.
+// the K pattern, the periodic neighbour list, the periodic pairwise term and the periodic event list.  kmcf_min_image is
+// the minimum image of a difference d along one periodic axis.
+__device__ __forceinline__ double kmcf_min_image(double d, double period)
+{
+    double f = d / period;
+    f -= round(f);
+    return f * period;
+}
 __device__ __forceinline__ double kmcf_min_image_dist(double x1, double y1, double z1, double x2, double y2, double z2,
                                                       double ly, double lz)
 {
     double dist_x = x1 - x2;
-    double fy = (y1 - y2) / ly;
-    fy -= round(fy);
-    double fz = (z1 - z2) / lz;
-    fz -= round(fz);
-    double dy = fy * ly, dz = fz * lz;
+    double dy = kmcf_min_image(y1 - y2, ly), dz = kmcf_min_image(z1 - z2, lz);
     return sqrt(dist_x * dist_x + dy * dy + dz * dz);
 }
+
+// gap cell of a site, -1: none (d_site_cell / n_cells of the analyses; no d_site_cell: one cell)
+__device__ __forceinline__ int kmcf_site_cell(const int *__restrict__ site_cell, int n_cells, int i)
+{
+    const int c = site_cell ? site_cell[i] : 0;
+    return (unsigned)c < (unsigned)n_cells ? c : -1;
+}
+
+// relaxed agent-scope load of a word that other blocks lower with atomics: whatever value it held at some time
+template <class T>
+__device__ __forceinline__ T kmcf_load_relaxed(const T *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 typedef unsigned int kmcf_u2 __attribute__((ext_vector_type(2)));
 template <int CTRL>

@@ -14,12 +14,13 @@
 // (v_solve_gpu, src/gpu_solvers.h:321-329), the same set the reference's list yields as long as charged
 // sites are V / Od (update_charge only ever charges those, potential_solver_gpu.cu:27-60).
 // kmcf_compute_cutoff_list_pbc builds the same index over one period in y and z; pairwise_pbc_kernel then takes the
-// minimum image.
+// minimum image.  Both kernels are one sum (pairwise_sum) over the walk of kmcf_cellwalk.hpp, which the gap
+// and chain searches share.
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
-#include "kmcf_internal.hpp"      // struct kmcf_pairwise
+#include "kmcf_cellwalk.hpp"      // the walk; kmcf_internal.hpp: struct kmcf_pairwise
 
 namespace {
 
@@ -57,12 +58,29 @@ __global__ __launch_bounds__(KMCF_BLOCK) void flag_scatter_kernel(int N, const i
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x == KMCF_BLOCK - 1) flag_pos[N] = block_sum[gridDim.x];
 }
 
-// calculate_pairwise_interaction_indexed (potential_solver_gpu.cu:1525-1564): potential[i] = sum, written not added
-__global__ __launch_bounds__(KMCF_BLOCK) void pairwise_kernel(
-    kmcf_cell_grid g, const int *__restrict__ cell_start, const int *__restrict__ flag_pos, const int *__restrict__ clist,
-    const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ z,
-    const int *__restrict__ charge, double sigma, double k, double cutoff, int count, int displ,
-    double *__restrict__ potential)
+// the reference's distance from site i to site j, operation for operation: open, and on a periodic index the minimum
+// image in y and z.  A pair has ONE distance: where a period is shorter than two cutoffs no second image is added.
+__device__ __forceinline__ double pairwise_dist(const kmcf_cell_grid &, double xi, double yi, double zi, double xj, double yj,
+                                                double zj)
+{
+    const double dx = xj - xi, dy = yj - yi, dz = zj - zi;
+    return sqrt(dx * dx + dy * dy + dz * dz);
+}
+__device__ __forceinline__ double pairwise_dist(const kmcf_cell_grid_pbc &g, double xi, double yi, double zi, double xj,
+                                                double yj, double zj)
+{
+    return kmcf_min_image_dist(xi, yi, zi, xj, yj, zj, g.ly, g.lz);
+}
+
+// calculate_pairwise_interaction_indexed (potential_solver_gpu.cu:1525-1564): potential[i] = sum, written not added, over
+// the charged j != i below the cutoff.  16 lanes per site take the runs of kmcf_walk_columns (kmcf_cellwalk.hpp: every
+// cell once, no column skipped) in its order; a lane adds its terms in the order it meets them.
+template <class GRID>
+__device__ __forceinline__ void pairwise_sum(const GRID &g, const int *__restrict__ cell_start, const int *__restrict__ flag_pos,
+                                             const int *__restrict__ clist, const double *__restrict__ x,
+                                             const double *__restrict__ y, const double *__restrict__ z,
+                                             const int *__restrict__ charge, double sigma, double k, double cutoff, int count,
+                                             int displ, double *__restrict__ potential)
 {
     constexpr int LPS = 16, SPB = KMCF_BLOCK / LPS;
     const double q = 1.60217663e-19;            // gpu_solvers.h:323
@@ -75,25 +93,20 @@ __global__ __launch_bounds__(KMCF_BLOCK) void pairwise_kernel(
         double acc = 0.0;
         if (valid) {
             const double xi = x[i], yi = y[i], zi = z[i];
-            const int cx = kmcf_cell_coord(xi, g.x0, g.inv, g.ncx), cy = kmcf_cell_coord(yi, g.y0, g.inv, g.ncy),
-                      cz = kmcf_cell_coord(zi, g.z0, g.inv, g.ncz);
-            for (int ax = max(cx - 1, 0); ax <= min(cx + 1, g.ncx - 1); ++ax)
-                for (int ay = max(cy - 1, 0); ay <= min(cy + 1, g.ncy - 1); ++ay) {
-                    // cells (ax, ay, az-1..az+1) are contiguous in the cell order: one run
-                    const int c_lo = (ax * g.ncy + ay) * g.ncz + max(cz - 1, 0);
-                    const int c_hi = (ax * g.ncy + ay) * g.ncz + min(cz + 1, g.ncz - 1);
-                    const int b = flag_pos[cell_start[c_lo]], e = flag_pos[cell_start[c_hi + 1]];
+            kmcf_walk_columns(
+                g, xi, yi, zi, cell_start, flag_pos, [](double) { return true; },
+                [&](int b, int e) {
                     for (int t = b + lane; t < e; t += LPS) {
                         const int j = clist[t];
                         if (j == i) continue;
-                        const double dx = x[j] - xi, dy = y[j] - yi, dz = z[j] - zi;
-                        const double dist = sqrt(dx * dx + dy * dy + dz * dz);
+                        const double dist = pairwise_dist(g, xi, yi, zi, x[j], y[j], z[j]);
                         if (dist < cutoff) {
                             const double r = 1e-10 * dist;                                    // :1554
                             acc += (double)charge[j] * erfc(r / (sigma * sqrt(2.0))) * k * q / r;  // gpu_solvers.h:325
                         }
                     }
-                }
+                },
+                []() {});
         }
 #pragma unroll
         for (int off = LPS / 2; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
@@ -101,60 +114,23 @@ __global__ __launch_bounds__(KMCF_BLOCK) void pairwise_kernel(
     }
 }
 
-// The same sum on a periodic index (kmcf_cell_grid_pbc): the charged j != i whose minimum-image distance (y and z,
-// kmcf_min_image_dist) is below the cutoff.  Every cell is visited once: in y the distinct cells of {cy-1, cy, cy+1} mod
-// ncy (one for ncy == 1, two for ncy == 2, else three); in z the cells {cz-1, cz, cz+1} mod ncz as runs of the compacted
-// list -- the whole column when ncz <= 3, [cz-1, cz+1] inside, and [0, hi] + [lo, ncz-1] when cz sits on a face.  All
-// bounds depend on the site alone, so they are the same for its 16 lanes; only the walk over a run is per lane.  A pair
-// has ONE distance, the minimum image: where a period is shorter than two cutoffs no second image is added.
+__global__ __launch_bounds__(KMCF_BLOCK) void pairwise_kernel(
+    kmcf_cell_grid g, const int *__restrict__ cell_start, const int *__restrict__ flag_pos, const int *__restrict__ clist,
+    const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ z,
+    const int *__restrict__ charge, double sigma, double k, double cutoff, int count, int displ,
+    double *__restrict__ potential)
+{
+    pairwise_sum(g, cell_start, flag_pos, clist, x, y, z, charge, sigma, k, cutoff, count, displ, potential);
+}
+
+// the same sum on a periodic index
 __global__ __launch_bounds__(KMCF_BLOCK) void pairwise_pbc_kernel(
     kmcf_cell_grid_pbc g, const int *__restrict__ cell_start, const int *__restrict__ flag_pos, const int *__restrict__ clist,
     const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ z,
     const int *__restrict__ charge, double sigma, double k, double cutoff, int count, int displ,
     double *__restrict__ potential)
 {
-    constexpr int LPS = 16, SPB = KMCF_BLOCK / LPS;
-    const double q = 1.60217663e-19;            // gpu_solvers.h:323
-    const int lane = threadIdx.x % LPS;
-    const int groups = (count + SPB - 1) / SPB;
-    const int ny = min(g.ncy, 3);               // y cells a site visits
-    for (int grp = blockIdx.x; grp < groups; grp += gridDim.x) {
-        const int idx = grp * SPB + threadIdx.x / LPS;
-        const bool valid = idx < count;
-        const int i = displ + idx;
-        double acc = 0.0;
-        if (valid) {
-            const double xi = x[i], yi = y[i], zi = z[i];
-            const int cx = kmcf_cell_coord(xi, g.x0, g.inv_x, g.ncx), cy = kmcf_cell_coord(yi, g.y0, g.inv_y, g.ncy),
-                      cz = kmcf_cell_coord(zi, g.z0, g.inv_z, g.ncz);
-            // z runs [lo0, hi0] and, if n_runs == 2, [lo1, hi1]
-            int n_runs = 1, lo0 = cz - 1, hi0 = cz + 1, lo1 = 0, hi1 = -1;
-            if (g.ncz <= 3) { lo0 = 0; hi0 = g.ncz - 1; }
-            else if (cz == 0) { lo0 = 0; hi0 = 1; lo1 = hi1 = g.ncz - 1; n_runs = 2; }
-            else if (cz == g.ncz - 1) { lo0 = 0; hi0 = 0; lo1 = g.ncz - 2; hi1 = g.ncz - 1; n_runs = 2; }
-            const int ay0 = g.ncy == 1 ? cy : cy - 1 + g.ncy;
-            for (int ax = max(cx - 1, 0); ax <= min(cx + 1, g.ncx - 1); ++ax)
-                for (int sy = 0; sy < ny; ++sy) {
-                    const int col = (ax * g.ncy + (ay0 + sy) % g.ncy) * g.ncz;
-                    for (int run = 0; run < n_runs; ++run) {
-                        const int b = flag_pos[cell_start[col + (run ? lo1 : lo0)]];
-                        const int e = flag_pos[cell_start[col + (run ? hi1 : hi0) + 1]];
-                        for (int t = b + lane; t < e; t += LPS) {
-                            const int j = clist[t];
-                            if (j == i) continue;
-                            const double dist = kmcf_min_image_dist(xi, yi, zi, x[j], y[j], z[j], g.ly, g.lz);
-                            if (dist < cutoff) {
-                                const double r = 1e-10 * dist;
-                                acc += (double)charge[j] * erfc(r / (sigma * sqrt(2.0))) * k * q / r;
-                            }
-                        }
-                    }
-                }
-        }
-#pragma unroll
-        for (int off = LPS / 2; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
-        if (valid && lane == 0) potential[i] = acc;
-    }
+    pairwise_sum(g, cell_start, flag_pos, clist, x, y, z, charge, sigma, k, cutoff, count, displ, potential);
 }
 
 // the sites in cell order and the buffers of the per-step compaction, from the host copy of the coordinates; coord(s)

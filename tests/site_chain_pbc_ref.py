@@ -1,4 +1,4 @@
-"""The restatement kmcf_site_set_chain_pbc and kmcf_filament_chain_pbc (csrc/kmcf_chain.hip, ch_search_pbc_kernel) are held
+"""The restatement kmcf_site_set_chain_pbc and kmcf_filament_chain_pbc (csrc/kmcf_chain.hip, the periodic ch_search_kernel) are held
 to: the contract of include/kmcfield.h in plain numpy, and the inputs the tests run it on.  No GPU.
 
 Vertices, Kruskal, the rounds of Boruvka, the tree walk and the record types are those of tests/site_chain_ref.py; the pair

@@ -1,4 +1,4 @@
-"""The restatement kmcf_site_set_gap_pbc and kmcf_filament_gap_pbc (csrc/kmcf_gap.hip, gp_search_pbc_kernel) are held to:
+"""The restatement kmcf_site_set_gap_pbc and kmcf_filament_gap_pbc (csrc/kmcf_gap.hip, the periodic gp_search_kernel) are held to:
 the contract of include/kmcfield.h in plain numpy, and the inputs the tests run it on.  No GPU.
 
 ALL pairs (a, b) of a gap cell, in blocks of A sites; the distance written out operation by operation --

@@ -1,4 +1,4 @@
-"""GPU: kmcf_site_set_chain_pbc and kmcf_filament_chain_pbc (csrc/kmcf_chain.hip, ch_search_pbc_kernel) against the
+"""GPU: kmcf_site_set_chain_pbc and kmcf_filament_chain_pbc (csrc/kmcf_chain.hip, the periodic ch_search_kernel) against the
 restatement of tests/site_chain_pbc_ref.py, in the sense of `_same` of tests/test_gpu_site_chain.py: array_equal on every
 integer, hop_max2, direct2, the hops and the input-decided stats (surface sites included); hop_max within 1 ulp, length
 within 2 n ulp; a second call the same bytes.  Random site sets on periodic indices of (1,1), (2,3), (3,4), (5,2) and (3,3)

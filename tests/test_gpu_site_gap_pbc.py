@@ -1,4 +1,4 @@
-"""GPU: kmcf_site_set_gap_pbc and kmcf_filament_gap_pbc (csrc/kmcf_gap.hip, gp_search_pbc_kernel) against the restatement of
+"""GPU: kmcf_site_set_gap_pbc and kmcf_filament_gap_pbc (csrc/kmcf_gap.hip, the periodic gp_search_kernel) against the restatement of
 tests/site_gap_pbc_ref.py: array_equal on every field of every record and on every integer of the stats; gap within 1 ulp of
 sqrt(gap2); a second call the same bytes.  Random site sets on periodic indices of (1,1), (2,3), (3,4), (5,2) and (3,3)
 cells in (y, z) at two radii; constructed sets on exact lattices (corner, rim, half a period, ties, two cells, second image,
