@@ -171,6 +171,15 @@ class CensusStats(C.Structure):
         return {k: (list(getattr(self, k)) if k in ("n_type", "rate_type") else getattr(self, k)) for k, _ in self._fields_}
 
 
+class PairStats(C.Structure):
+    """kmcf_pair_stats_t"""
+    _fields_ = [("n_pairs_total", C.c_uint64), ("n_members", C.c_int), ("n_probes", C.c_int), ("max_count", C.c_int),
+                ("max_count_site", C.c_int), ("ms", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 _P = C.c_void_p          # device or opaque pointer
 _IP = C.POINTER(C.c_int)
 _DP = C.POINTER(C.c_double)
@@ -295,6 +304,10 @@ SIGNATURES = {
                                           C.c_int, C.POINTER(Chain), C.POINTER(Hop), C.c_int, _P, _P, C.POINTER(ChainStats)]),
     "kmcf_site_gradient": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _DP, C.c_int, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P,
                                      _P, C.POINTER(GradientCell), C.POINTER(GradientStats)]),
+    "kmcf_pair_correlation": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_double, C.c_int, C.c_double, _P, C.c_int,
+                                        C.POINTER(C.c_uint64), _IP, _DP, _P, C.POINTER(PairStats)]),
+    "kmcf_defect_correlation": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_double, C.c_int, C.c_double, _P, C.c_int,
+                                          C.POINTER(C.c_uint64), _IP, _DP, _P, _P, C.POINTER(PairStats)]),
     "kmcf_neighbor_list":(C.c_int, [_P, _P, _P, _P, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _P]),
     "kmcf_neighbor_list_pbc": (C.c_int, [_P, _P, _P, _P, C.c_int, _DP, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _P]),
 }

@@ -980,6 +980,95 @@ def field_map(kmc_comm, gpubuf, potential=None, mask=None, site_cell=None, n_cel
     return out
 
 
+PC_MAX_CLASSES, PC_MAX_BINS = 4, 256           # KMCF_PC_MAX_CLASSES, KMCF_PC_MAX_BINS
+DEFECT_CLASSES = ("V0", "V+", "ion")           # the classes of kmcf_defect_correlation; 3: probe
+
+
+def _pair_out(n_classes, n_bins, n_cells, r_max, r_count, counts, gpubuf):
+    n_pairs = n_classes * (n_classes + 1) // 2
+    hist = np.zeros((int(n_cells) + 1, n_pairs, int(n_bins)), np.uint64)
+    members = np.zeros((int(n_cells) + 1, n_classes), np.int32)
+    edge2 = np.zeros(int(n_bins) + 1, np.float64)
+    cnt = torch.empty((gpubuf.N_, n_classes), dtype=torch.int32, device=gpubuf.device) if counts else None
+    return hist, members, edge2, cnt, float(r_max if r_count is None else r_count)
+
+
+def _pair_result(hist, members, edge2, r_max, n_bins, cnt, st, **more):
+    edges = float(r_max) * np.arange(int(n_bins) + 1, dtype=np.float64) / float(int(n_bins))
+    return dict(hist=hist, members=members, edge2=edge2, edges=edges, counts=cnt, stats=st.as_dict(), **more)
+
+
+def pair_correlation(gpubuf, site_class, n_classes, r_max, n_bins, r_count=None, site_cell=None, n_cells=1, counts=False):
+    """kmcf_pair_correlation on the buffers' spatial index (gpubuf.cutoff_idx, compute_cutoff_list; open or periodic: the
+    distance is the index's own): per bucket and class pair the histogram of the pair distances up to r_max, the members
+    per cell and class, and (counts=True) per centre the members of every class within r_count (default r_max)
+    (definitions: include/kmcfield.h).  site_class: int32 device tensor of N entries -- [0, n_classes) member, n_classes
+    probe, anything else no part; site_cell as in site_set_gap.  Returns dict(hist: uint64 (n_cells + 1, n_pairs, n_bins),
+    members: int32 (n_cells + 1, n_classes), edge2: the table of squared bin edges, edges: r_max * k / n_bins, counts:
+    int32 device tensor (N, n_classes) or None, stats: dict)."""
+    assert gpubuf.cutoff_idx is not None, "pair_correlation needs the spatial index: compute_cutoff_list first"
+    assert site_class.dtype == torch.int32 and site_class.numel() == gpubuf.N_, "site_class: N int32 entries"
+    assert 1 <= int(n_classes) <= PC_MAX_CLASSES and 1 <= int(n_bins) <= PC_MAX_BINS
+    cell = _gap_cells(gpubuf, site_cell, n_cells)
+    hist, members, edge2, cnt, r_count = _pair_out(int(n_classes), n_bins, n_cells, r_max, r_count, counts, gpubuf)
+    st = _L.PairStats()
+    _L.check(_L.load().kmcf_pair_correlation(gpubuf.cutoff_idx, _ptr(gpubuf.site_x), _ptr(gpubuf.site_y), _ptr(gpubuf.site_z),
+                                             _ptr(site_class), int(n_classes), float(r_max), int(n_bins), r_count, _ptr(cell),
+                                             int(n_cells), hist.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                             members.ctypes.data_as(C.POINTER(C.c_int)),
+                                             edge2.ctypes.data_as(C.POINTER(C.c_double)), _ptr(cnt), C.byref(st)),
+             "kmcf_pair_correlation")
+    return _pair_result(hist, members, edge2, r_max, n_bins, cnt, st)
+
+
+def defect_correlation(kmc_comm, gpubuf, r_max, n_bins, r_count=None, site_cell=None, n_cells=1, counts=False, probe_all=False,
+                       classes=False):
+    """kmcf_defect_correlation: pair_correlation with the three classes of DEFECT_CLASSES taken from gpubuf.site_element
+    and gpubuf.site_charge -- neutral vacancies, charged vacancies, oxygen ions; probe_all: every other site is a probe (a
+    centre of the counts), otherwise it takes no part.  Call it after update_charge_gpu and compute_cutoff_list, on the
+    communicator the index was built with.  classes=True: also returns the classes as formed (`site_class`, int32 device
+    tensor of N entries).  Returns pair_correlation's dict."""
+    assert gpubuf.cutoff_idx is not None, "defect_correlation needs the spatial index: compute_cutoff_list first"
+    cell = _gap_cells(gpubuf, site_cell, n_cells)
+    hist, members, edge2, cnt, r_count = _pair_out(3, n_bins, n_cells, r_max, r_count, counts, gpubuf)
+    cls = torch.empty(gpubuf.N_, dtype=torch.int32, device=gpubuf.device) if classes else None
+    st = _L.PairStats()
+    _L.check(_L.load().kmcf_defect_correlation(gpubuf.cutoff_idx, _ptr(gpubuf.site_x), _ptr(gpubuf.site_y), _ptr(gpubuf.site_z),
+                                               _ptr(gpubuf.site_element), _ptr(gpubuf.site_charge), 1 if probe_all else 0,
+                                               float(r_max), int(n_bins), r_count, _ptr(cell), int(n_cells),
+                                               hist.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                               members.ctypes.data_as(C.POINTER(C.c_int)),
+                                               edge2.ctypes.data_as(C.POINTER(C.c_double)), _ptr(cnt), _ptr(cls), C.byref(st)),
+             "kmcf_defect_correlation")
+    return _pair_result(hist, members, edge2, r_max, n_bins, cnt, st, site_class=cls)
+
+
+def pair_class_index(p, q, n_classes):
+    """index of the class pair {p, q} in the histogram's second axis"""
+    p, q = min(p, q), max(p, q)
+    return p * n_classes - p * (p - 1) // 2 + (q - p)
+
+
+def pair_rdf(result, volume):
+    """The pair distribution g(r) of a pair_correlation result against a random arrangement, host-only numpy: per cell
+    c < n_cells, class pair and bin, hist / (n_pq * shell_k / volume) with n_pq = N_p N_q for p != q and N_p (N_p - 1) / 2
+    for p == q (N_p: the cell's members of class p), shell_k = 4/3 pi (e[k+1]^3 - e[k]^3); nan where n_pq == 0.  volume:
+    a cell's volume (a number, or one per cell).  Returns float64 (n_cells, n_pairs, n_bins)."""
+    hist, members, e = np.asarray(result["hist"]), np.asarray(result["members"]), np.asarray(result["edges"], np.float64)
+    n_cells, n_classes = hist.shape[0] - 1, members.shape[1]
+    shell = 4.0 / 3.0 * np.pi * (e[1:] ** 3 - e[:-1] ** 3)
+    vol = np.broadcast_to(np.asarray(volume, np.float64), (n_cells,))
+    out = np.full((n_cells,) + hist.shape[1:], np.nan)
+    for c in range(n_cells):
+        for p in range(n_classes):
+            for q in range(p, n_classes):
+                n_pq = float(members[c, p]) * float(members[c, q]) if p != q else float(members[c, p]) * (float(members[c, p]) - 1.0) / 2.0
+                if n_pq > 0:
+                    k = pair_class_index(p, q, n_classes)
+                    out[c, k] = hist[c, k].astype(np.float64) / (n_pq * shell / vol[c])
+    return out
+
+
 def k_assemble(gpubuf, Vd, high_G, low_G):
     lib = _L.load()
     _L.check(lib.kmcf_k_assemble(gpubuf.K_distributed, _ptr(gpubuf.site_element), _ptr(gpubuf.site_charge),

@@ -932,6 +932,78 @@ int kmcf_site_gradient(kmcf_comm *c, int N, int nn, const int *d_neigh_idx /* N*
                        kmcf_gradient_stats_t *stats /* or NULL */);
 
 /* ---------------------------------------------------------------------- */
+/* Pair correlation: pair-distance histograms per class pair and cell, and    */
+/* counts of class members around every site (no reference counterpart)       */
+/* ---------------------------------------------------------------------- */
+/* How the defects are arranged: the vacancy-vacancy pair distribution (clustering, against a random arrangement), the
+ * ion-vacancy separation (recombination), the number of defects within a radius of every site (a density map).
+ * Classes: d_site_class[i] in [0, n_classes): site i is a MEMBER of that class.  d_site_class[i] == n_classes
+ * (KMCF_PC_PROBE relative to the call): site i is a PROBE -- a centre of the site counts only, never a partner, never in
+ * the histogram.  Any other value: the site takes no part.  1 <= n_classes <= KMCF_PC_MAX_CLASSES.
+ * Distance: the index's own.  On a non-periodic index (kmcf_compute_cutoff_list, or kmcf_compute_cutoff_list_pbc with
+ * pbc == 0), for the sites i and j
+ *     dx = x[i] - x[j], likewise dy, dz;  d2 = (dx*dx + dy*dy) + dz*dz
+ * and on an index of kmcf_compute_cutoff_list_pbc with pbc == 1 the library's minimum image, Ly and Lz the index's periods:
+ *     dx = x[i] - x[j]
+ *     fy = (y[i] - y[j]) / Ly;  fy -= round(fy);  dy = fy * Ly        (z likewise; round = C round, half away from zero)
+ *     d2 = (dx*dx + dy*dy) + dz*dz
+ * every operation rounded to double (no fused multiply-add, an IEEE division), as above kmcf_site_set_gap_pbc.  Both are
+ * even in the difference: d2 of (i, j) and of (j, i) are the same bits.  A pair has ONE distance, whatever number of its
+ * images lie within reach.  One call serves both kinds of index.
+ * Pair: an unordered {i, j}, i != j, both members, d2 <= r_max*r_max, that product formed in double.  It is counted once.
+ * Two different sites with equal coordinates are a pair with d2 = 0.
+ * Bins: e[k] = r_max * (double)k / (double)n_bins for k = 0 .. n_bins (multiply, then divide, each rounded to double),
+ * edge2[k] = e[k] * e[k], and edge2[n_bins] = r_max * r_max; formed on the host and returned in h_edge2.  A pair falls
+ * into bin k, the largest k < n_bins with edge2[k] <= d2: the TABLE defines the bin, not an expression in sqrt(d2).
+ * 1 <= n_bins <= KMCF_PC_MAX_BINS.
+ * Class pair of the classes p <= q: index p * n_classes - p * (p - 1) / 2 + (q - p); n_pairs = n_classes * (n_classes + 1) / 2.
+ * Bucket: from d_site_cell as in kmcf_site_set_gap (a value outside [0, n_cells): no valid cell; NULL requires
+ * n_cells == 1 and puts every site in cell 0).  Both sites in the same cell c: bucket c.  Both in valid, different
+ * cells: the rest bucket n_cells.  Either site without a valid cell: the pair enters no bucket.
+ * Outputs:
+ *   h_hist[(bucket * n_pairs + pair) * n_bins + k]   counts, n_cells + 1 buckets
+ *   h_members[bucket * n_classes + p]                members of class p per cell; bucket n_cells: those without a valid cell
+ *   d_site_count[i * n_classes + q]                  device, N * n_classes ints, or NULL: for every centre i (member or
+ *       probe) the members j != i of class q with d2 <= r_count*r_count, whatever their cells; the row of every other
+ *       site is written as zeros.  0 < r_count <= r_max.
+ *   stats    n_pairs_total: the sum of h_hist; n_members, n_probes; max_count: the largest sum of a centre's count row,
+ *       max_count_site: the smallest site id that attains it (-1 and 0 without a centre) -- formed with or without
+ *       d_site_count; ms: device time of everything the call enqueued (HIP events).
+ * Every output is a pure function of the input (integer accumulation only): two calls return the same bytes.
+ * Both calls are LOCAL operations on WHOLE-device arrays of the index's N sites, like kmcf_site_set_gap: no collectives,
+ * scratch on the index (freed by kmcf_pairwise_destroy), kmcf_poisson_gridless's lists and the gap and chain scratch
+ * untouched, one synchronisation per call.
+ * KMCF_ERR_ARG (before anything needs a device; kmcf_last_error names the argument): NULL coordinates, classes, h_hist,
+ * h_members or p; n_classes or n_bins out of range; r_max not finite, <= 0 or above the index's cutoff radius; r_count not
+ * finite, <= 0 or > r_max; n_cells < 1, or NULL d_site_cell with n_cells != 1; (n_cells + 1) * n_pairs * n_bins > 2^24. */
+#define KMCF_PC_MAX_CLASSES 4
+#define KMCF_PC_MAX_BINS 256
+typedef struct {
+    unsigned long long n_pairs_total;
+    int n_members, n_probes;
+    int max_count, max_count_site;
+    float ms;
+} kmcf_pair_stats_t;
+
+int kmcf_pair_correlation(kmcf_pairwise *p, const double *d_x, const double *d_y, const double *d_z,
+                          const int *d_site_class /* N */, int n_classes, double r_max, int n_bins, double r_count,
+                          const int *d_site_cell /* N, or NULL */, int n_cells,
+                          unsigned long long *h_hist /* (n_cells + 1) * n_pairs * n_bins */,
+                          int *h_members /* (n_cells + 1) * n_classes */, double *h_edge2 /* n_bins + 1, or NULL */,
+                          int *d_site_count /* N * n_classes, or NULL */, kmcf_pair_stats_t *stats /* or NULL */);
+
+/* kmcf_pair_correlation with n_classes = 3 and the classes taken from the device state: class 0 VACANCY (element 2)
+ * with charge 0, class 1 VACANCY with charge != 0, class 2 OXYGEN_DEFECT (element 1); every other site a probe when
+ * probe_all != 0, otherwise no part.  d_site_class: N ints out (the classes as formed), or NULL.
+ * KMCF_ERR_ARG as above, and NULL d_site_element or d_site_charge. */
+int kmcf_defect_correlation(kmcf_pairwise *p, const double *d_x, const double *d_y, const double *d_z,
+                            const int *d_site_element, const int *d_site_charge, int probe_all,
+                            double r_max, int n_bins, double r_count, const int *d_site_cell /* N, or NULL */, int n_cells,
+                            unsigned long long *h_hist, int *h_members, double *h_edge2 /* n_bins + 1, or NULL */,
+                            int *d_site_count /* N * 3, or NULL */, int *d_site_class /* N out, or NULL */,
+                            kmcf_pair_stats_t *stats /* or NULL */);
+
+/* ---------------------------------------------------------------------- */
 /* T path: current solve (Kirchhoff matrix with two virtual nodes + WKB       */
 /* tunnelling sub-block), SURVEY 8 rows a14 / f3.  PARITY UNPINNED: no         */
 /* reference fixture exercises it (src/KMC_comm.h:243 disables it from main).  */

@@ -5,7 +5,7 @@ prints into output<size>_<rank>.txt ("Z - calculation time - ...").
 
     python tools/kmc_loop.py [--workload 5nm|5nm-periodic|40nm|conducting] [--steps 6] [--T 300] [--current] [--rate-mode bg|ekin|site]
                              [--clusters] [--current-map] [--current-profile N] [--scheme all|half|third --select W,B] [--gap R]
-                             [--chain R [--chain-hops K]] [--field-map] [--event-census]
+                             [--chain R [--chain-hops K]] [--field-map] [--event-census] [--pair-correlation R [--pair-bins N]]
 
 --current adds the electro-thermal stages after the potential and before the events: conduction-band edge, current
 solve with heating (site_power), local heat solve (site_temperature); --rate-mode ekin | site lets the event rates read
@@ -52,7 +52,14 @@ from the rates of every possible event, nothing executed.  Cells from structure.
 cell otherwise).  Below the step line it prints, per cell and for the rest, `census cell <c>: rate <sum> (<share of the
 total>) | gen <..> rec <..> vdiff <..> odiff <..> | max <rate> (<i>-<j>, <type>)` -- with --scheme also `| realised <share of
 the step's events that fell into the cell>` next to the forecast share -- then `census device: rate_total <..> dt_mean <..> |
-rows_live <..> n_zero <..> | build <ms> census <ms>`, the two device times.
+rows_live <..> n_zero <..> | build <ms> census <ms>`, the two device times.  --pair-correlation R [--pair-bins N] runs the
+defect pair correlation (kmcf_defect_correlation; the distance is the spatial index's own, the minimum image on `5nm-periodic`)
+after the event step of every superstep, up to R angstrom (at most 20) in N bins (default 20), every other site a probe of the
+counts.  Cells from structure.crossbar_lines on the crossbar workloads (one cell otherwise).  Below the step line it prints,
+per cell and for the rest, `pairs cell <c>: V0 <n> V+ <n> ion <n> | V-V first <lo>-<hi> A peak <lo>-<hi> A (<pairs>) | V-ion
+first .. peak ..` -- V-V: the three vacancy-vacancy class pairs added, V-ion: the two vacancy-ion ones; first: the first
+non-empty bin, peak: the fullest one (the first among equals) -- then `pairs device: <pairs> pairs, <members> defects,
+<probes> probes | densest site <site> (<count> defects within R) | <ms> ms`.
 """
 import argparse
 import os
@@ -99,6 +106,10 @@ def main():
     ap.add_argument("--field-map", action="store_true",
                     help="site gradient map of the potential after every sum / gather: largest |E| and bond drop per crossbar "
                          "cell, against the mean field; with --current also of the site temperature")
+    ap.add_argument("--pair-correlation", type=float, default=None, metavar="R",
+                    help="defect pair correlation after every step, up to R angstrom (<= 20): defect counts per crossbar cell, "
+                         "first and fullest bin of the vacancy-vacancy and vacancy-ion distances, the densest site")
+    ap.add_argument("--pair-bins", type=int, default=20, metavar="N", help="with --pair-correlation: bins of the histograms (<= 256)")
     a = ap.parse_args()
     periodic = a.workload == "5nm-periodic"
     if a.scheme and a.workload in ("5nm", "5nm-periodic"):
@@ -113,6 +124,10 @@ def main():
         ap.error("--gap %g: the search radius is > 0 and at most 20 (the cell edge of the spatial index)" % a.gap)
     if a.chain is not None and not 0.0 < a.chain <= 20.0:
         ap.error("--chain %g: the hop length is > 0 and at most 20 (the cell edge of the spatial index)" % a.chain)
+    if a.pair_correlation is not None and not 0.0 < a.pair_correlation <= 20.0:
+        ap.error("--pair-correlation %g: the radius is > 0 and at most 20 (the cell edge of the spatial index)" % a.pair_correlation)
+    if not 1 <= a.pair_bins <= 256:
+        ap.error("--pair-bins N: 1 ... 256 bins")
     if a.chain_hops < 0 or (a.chain_hops and a.chain is None):
         ap.error("--chain-hops K: K >= 0, with --chain")
     if a.rate_mode != "bg" and not a.current:
@@ -189,6 +204,35 @@ def main():
     if a.event_census and a.workload not in ("5nm", "5nm-periodic"):
         cells = km.structure.crossbar_lines(d)[2] if cell_of_site is None else cell_of_site
         census_cells, n_census_cells = torch.as_tensor(np.ascontiguousarray(cells, np.int32), device="cuda"), int(cells.max()) + 1
+
+    pair_cells, n_pair_cells = None, 1
+    if a.pair_correlation is not None and a.workload not in ("5nm", "5nm-periodic"):
+        cells = km.structure.crossbar_lines(d)[2] if cell_of_site is None else cell_of_site
+        pair_cells, n_pair_cells = torch.as_tensor(np.ascontiguousarray(cells, np.int32), device="cuda"), int(cells.max()) + 1
+
+    def pair_lines():
+        """the per-cell lines of one defect pair correlation"""
+        pc = S.defect_correlation(comm, buf, a.pair_correlation, a.pair_bins, site_cell=pair_cells, n_cells=n_pair_cells,
+                                  probe_all=True)
+        e, h, m, st_p = pc["edges"], pc["hist"], pc["members"], pc["stats"]
+        ix = lambda p, q: S.pair_class_index(p, q, 3)
+
+        def summary(row):
+            nz = np.flatnonzero(row)
+            if not len(nz):
+                return "none"
+            k = int(np.argmax(row))
+            return "first %.2f-%.2f A peak %.2f-%.2f A (%d)" % (e[nz[0]], e[nz[0] + 1], e[k], e[k + 1], int(row[k]))
+        out = []
+        for c in range(n_pair_cells + 1):
+            vv = h[c, ix(0, 0)] + h[c, ix(0, 1)] + h[c, ix(1, 1)]
+            vi = h[c, ix(0, 2)] + h[c, ix(1, 2)]
+            out.append("  pairs %s: V0 %d V+ %d ion %d | V-V %s | V-ion %s" % (
+                "rest" if c == n_pair_cells else "cell %d" % c, m[c, 0], m[c, 1], m[c, 2], summary(vv), summary(vi)))
+        out.append("  pairs device: %d pairs, %d defects, %d probes | densest site %d (%d defects within %g A) | %.3f ms" % (
+            st_p["n_pairs_total"], st_p["n_members"], st_p["n_probes"], st_p["max_count_site"], st_p["max_count"], a.pair_correlation,
+            st_p["ms"]))
+        return out
 
     def census_lines(cs, log):
         """the per-cell lines of one census; log: the step's (i, j, type) rows, for the realised shares of --scheme"""
@@ -362,6 +406,8 @@ def main():
             print(line, flush=True)
         if census is not None:
             field_lines = field_lines + census_lines(census, ev[2])
+        if a.pair_correlation is not None:
+            field_lines = field_lines + pair_lines()
         if a.current:
             print("step %d: charge %.6f | boundary %.6f (%d it) | pairwise %.6f | gather %.6f | CB edge %.6f (%d it) | "
                   "power %.6f (%d it, I_macro %.4e) | heat %.6f (%d it, max T %.2f K) | events[%s] %.6f (%d ev) | "
