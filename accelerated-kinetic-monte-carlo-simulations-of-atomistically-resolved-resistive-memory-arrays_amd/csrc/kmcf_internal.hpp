@@ -294,12 +294,14 @@ struct kmcf_pairwise {
     struct kmcf_gap_ws *gap_ws = nullptr;   // scratch of kmcf_site_set_gap / kmcf_filament_gap (kmcf_gap.hip): buffers only
     struct kmcf_chain_ws *chain_ws = nullptr;   // scratch of kmcf_site_set_chain / kmcf_filament_chain (kmcf_chain.hip): buffers only
     struct kmcf_pc_ws *pc_ws = nullptr;   // scratch of kmcf_pair_correlation / kmcf_defect_correlation (kmcf_paircorr.hip): buffers only
+    struct kmcf_fs_ws *fs_ws = nullptr;   // scratch of kmcf_field_sample / kmcf_field_grid (kmcf_fieldsample.hip): buffers only
     kmcf_cell_grid grid() const { return kmcf_cell_grid{x0, y0, z0, inv, cutoff, ncx, ncy, ncz}; }
     kmcf_cell_grid_pbc grid_pbc() const { return kmcf_cell_grid_pbc{x0, y0, z0, inv, inv_y, inv_z, cutoff, lattice[1], lattice[2], ncx, ncy, ncz}; }
 };
 void kmcf_gap_ws_free(kmcf_pairwise *p);
 void kmcf_chain_ws_free(kmcf_pairwise *p);
 void kmcf_pc_ws_free(kmcf_pairwise *p);
+void kmcf_fs_ws_free(kmcf_pairwise *p);
 
 struct kmcf_subop;   // sub-block operator of the split T matrix (kmcf_tstate.hip)
 

@@ -271,6 +271,7 @@ extern "C" int kmcf_pairwise_destroy(kmcf_pairwise *p)
     kmcf_gap_ws_free(p);
     kmcf_chain_ws_free(p);
     kmcf_pc_ws_free(p);
+    kmcf_fs_ws_free(p);
     kmcf_dev_free_all({p->d_cell_order, p->d_cell_start, p->d_flag_pos, p->d_block_sum, p->d_clist});
     delete p;
     return KMCF_OK;

@@ -180,6 +180,15 @@ class PairStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class SampleStats(C.Structure):
+    """kmcf_sample_stats_t"""
+    _fields_ = [("n_points", C.c_int64), ("n_empty", C.c_int64), ("n_visits", C.c_int64), ("n_members", C.c_int),
+                ("max_count", C.c_int), ("max_count_point", C.c_int), ("ms", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 _P = C.c_void_p          # device or opaque pointer
 _IP = C.POINTER(C.c_int)
 _DP = C.POINTER(C.c_double)
@@ -308,6 +317,10 @@ SIGNATURES = {
                                         C.POINTER(C.c_uint64), _IP, _DP, _P, C.POINTER(PairStats)]),
     "kmcf_defect_correlation": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_double, C.c_int, C.c_double, _P, C.c_int,
                                           C.POINTER(C.c_uint64), _IP, _DP, _P, _P, C.POINTER(PairStats)]),
+    "kmcf_field_sample": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_double, C.c_int, C.c_double, _P, _P,
+                                    _P, _P, _P, C.POINTER(SampleStats)]),
+    "kmcf_field_grid": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, _P, _DP, _DP, _IP, C.c_double, C.c_int, C.c_double, _P, _P, _P, _P,
+                                  _P, C.POINTER(SampleStats)]),
     "kmcf_neighbor_list":(C.c_int, [_P, _P, _P, _P, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _P]),
     "kmcf_neighbor_list_pbc": (C.c_int, [_P, _P, _P, _P, C.c_int, _DP, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _P]),
 }

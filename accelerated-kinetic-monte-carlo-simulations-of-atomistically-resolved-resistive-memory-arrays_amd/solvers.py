@@ -183,6 +183,7 @@ class GPUBuffers:
         self.sigma, self.k = float(sigma), float(k)
         self.neigh_idx = None
         self.cutoff_idx = None         # kmcf_pairwise* (replaces cutoff_idx / cutoff_window)
+        self.cutoff_radius = None      # ... and the cutoff radius it was built with (compute_cutoff_list)
         self.K_distributed = None      # kmcf_kstate* (K_distributed + K_p_distributed + contact patterns)
         self.T_distributed = None      # kmcf_tstate* (T_distributed + T_p_distributed + atom_* arrays)
         self.site_CB_edge = None
@@ -199,7 +200,7 @@ class GPUBuffers:
             self.K_distributed = None
         if self.cutoff_idx is not None:
             _L.load().kmcf_pairwise_destroy(self.cutoff_idx)
-            self.cutoff_idx = None
+            self.cutoff_idx = self.cutoff_radius = None
 
 
 # --------------------------------------------------------------------------
@@ -493,12 +494,12 @@ def compute_cutoff_list(kmc_comm, gpubuf, cutoff_radius=20.0, pbc=0):
         _L.check(lib.kmcf_compute_cutoff_list_pbc(kmc_comm.handle, _ptr(gpubuf.site_x), _ptr(gpubuf.site_y), _ptr(gpubuf.site_z),
                                                   gpubuf.N_, float(cutoff_radius), latp, int(pbc), C.byref(h)),
                  "kmcf_compute_cutoff_list_pbc")
-        gpubuf.cutoff_idx = h
+        gpubuf.cutoff_idx, gpubuf.cutoff_radius = h, float(cutoff_radius)
         return
     _L.check(lib.kmcf_compute_cutoff_list(kmc_comm.handle, _ptr(gpubuf.site_x), _ptr(gpubuf.site_y),
                                           _ptr(gpubuf.site_z), gpubuf.N_, float(cutoff_radius), C.byref(h)),
              "kmcf_compute_cutoff_list")
-    gpubuf.cutoff_idx = h
+    gpubuf.cutoff_idx, gpubuf.cutoff_radius = h, float(cutoff_radius)
 
 
 def poisson_gridless_gpu(gpubuf, kmc_comm):
@@ -1067,6 +1068,113 @@ def pair_rdf(result, volume):
                     k = pair_class_index(p, q, n_classes)
                     out[c, k] = hist[c, k].astype(np.float64) / (n_pq * shell / vol[c])
     return out
+
+
+FS_MAX_FIELDS = 8                              # KMCF_FS_MAX_FIELDS
+
+
+def _fs_inputs(gpubuf, values, mask, radius):
+    """(values as a contiguous (n_fields, N) double tensor or None, n_fields, mask, radius) of field_sample / field_grid"""
+    assert gpubuf.cutoff_idx is not None, "field sampling needs the spatial index: compute_cutoff_list first"
+    N = gpubuf.N_
+    if values is not None:
+        if not torch.is_tensor(values):
+            values = torch.as_tensor(np.ascontiguousarray(values, dtype=np.float64), device=gpubuf.device)
+        values = values.reshape(-1, N).contiguous()
+        assert values.dtype == torch.float64 and 1 <= values.shape[0] <= FS_MAX_FIELDS, "values: 1 ... 8 rows of N doubles"
+    if mask is not None:
+        if not torch.is_tensor(mask):
+            mask = torch.as_tensor(np.ascontiguousarray(mask, dtype=np.int32), device=gpubuf.device)
+        assert mask.dtype == torch.int32 and mask.numel() == N, "mask: N int32 entries"
+    if radius is None:
+        assert getattr(gpubuf, "cutoff_radius", None) is not None, \
+            "radius=None takes the index's cutoff radius, which compute_cutoff_list records: pass radius= for an index attached otherwise"
+        radius = gpubuf.cutoff_radius
+    radius = float(radius)
+    return values, 0 if values is None else int(values.shape[0]), mask, radius
+
+
+def _fs_outputs(gpubuf, n_fields, n):
+    dev = gpubuf.device
+    return (torch.empty((n_fields, n), dtype=torch.float64, device=dev) if n_fields else None,
+            torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
+            torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.float64, device=dev))
+
+
+def field_sample(gpubuf, points, values=None, mask=None, radius=None, normalize=True, fill=float("nan")):
+    """kmcf_field_sample on the buffers' spatial index (gpubuf.cutoff_idx, compute_cutoff_list; open or periodic: the
+    distance is the index's own): the site fields `values` ((n_fields, N) or (N,) doubles, tensor or array; None: no field)
+    at the points ((n_points, 3) doubles, tensor or array), gathered from the sites with mask != 0 (all with mask None)
+    within `radius` (default: the index's cutoff) with the weight (1 - d2 / radius^2)^2 (definitions: include/kmcfield.h).
+    normalize: the weighted mean, `fill` where no weight was met; otherwise the raw weighted sum (sample_density).
+    Returns dict(out: (n_fields, n_points) doubles or None, wsum, count (int32), nearest (int32 site id, -1 none),
+    nearest_d2, stats: dict), the arrays on the device."""
+    values, n_fields, mask, radius = _fs_inputs(gpubuf, values, mask, radius)
+    if not torch.is_tensor(points):
+        points = torch.as_tensor(np.ascontiguousarray(points, dtype=np.float64), device=gpubuf.device)
+    assert points.dtype == torch.float64 and points.dim() == 2 and points.shape[1] == 3, "points: (n_points, 3) doubles"
+    n = int(points.shape[0])
+    px, py, pz = (points[:, k].contiguous() for k in range(3))
+    out, wsum, count, nearest, nd2 = _fs_outputs(gpubuf, n_fields, n)
+    st = _L.SampleStats()
+    nz = lambda t: _ptr(t) if n else None
+    _L.check(_L.load().kmcf_field_sample(gpubuf.cutoff_idx, _ptr(gpubuf.site_x), _ptr(gpubuf.site_y), _ptr(gpubuf.site_z), _ptr(mask),
+                                         n_fields, _ptr(values), n, nz(px), nz(py), nz(pz), radius, 1 if normalize else 0,
+                                         float(fill), _ptr(out), _ptr(wsum), _ptr(count), _ptr(nearest), _ptr(nd2), C.byref(st)),
+             "kmcf_field_sample")
+    return dict(out=out, wsum=wsum, count=count, nearest=nearest, nearest_d2=nd2, radius=radius, stats=st.as_dict())
+
+
+def field_grid(gpubuf, origin, spacing, dims, values=None, mask=None, radius=None, normalize=True, fill=float("nan"), labels=None):
+    """kmcf_field_grid: field_sample on the points origin + (i, j, k) * spacing of a grid of dims = (nx, ny, nz) voxels
+    (spacing: three numbers or one).  Returns field_sample's dict with the arrays shaped (n_fields, nx, ny, nz) and
+    (nx, ny, nz), and origin, spacing, dims; labels (an int32 site array: element, cluster label, cell id): also
+    `labels` = labels[nearest], -1 where a voxel has no site within radius."""
+    values, n_fields, mask, radius = _fs_inputs(gpubuf, values, mask, radius)
+    o = np.ascontiguousarray(np.broadcast_to(np.asarray(origin, np.float64), (3,)))
+    h = np.ascontiguousarray(np.broadcast_to(np.asarray(spacing, np.float64), (3,)))
+    d = np.ascontiguousarray(np.asarray(dims, np.int32).reshape(3))
+    n = int(np.prod(d.astype(np.int64)))
+    assert (d >= 1).all() and n < 2 ** 31, "dims: three counts >= 1 with a product below 2^31"
+    out, wsum, count, nearest, nd2 = _fs_outputs(gpubuf, n_fields, n)
+    st = _L.SampleStats()
+    _L.check(_L.load().kmcf_field_grid(gpubuf.cutoff_idx, _ptr(gpubuf.site_x), _ptr(gpubuf.site_y), _ptr(gpubuf.site_z), _ptr(mask),
+                                       n_fields, _ptr(values), o.ctypes.data_as(C.POINTER(C.c_double)),
+                                       h.ctypes.data_as(C.POINTER(C.c_double)), d.ctypes.data_as(C.POINTER(C.c_int)), radius,
+                                       1 if normalize else 0, float(fill), _ptr(out), _ptr(wsum), _ptr(count), _ptr(nearest),
+                                       _ptr(nd2), C.byref(st)), "kmcf_field_grid")
+    shape = tuple(int(v) for v in d)
+    res = dict(out=out.reshape((n_fields,) + shape) if n_fields else None, wsum=wsum.reshape(shape), count=count.reshape(shape),
+               nearest=nearest.reshape(shape), nearest_d2=nd2.reshape(shape), radius=radius, origin=o, spacing=h, dims=shape,
+               stats=st.as_dict())
+    if labels is not None:
+        if not torch.is_tensor(labels):
+            labels = torch.as_tensor(np.ascontiguousarray(labels, dtype=np.int32), device=gpubuf.device)
+        assert labels.dtype == torch.int32 and labels.numel() == gpubuf.N_, "labels: N int32 entries"
+        near = res["nearest"].long()
+        res["labels"] = torch.where(near >= 0, labels.reshape(-1)[near.clamp(min=0)], torch.full_like(res["nearest"], -1))
+    return res
+
+
+def field_slice(gpubuf, axis, position, spacing, **kw):
+    """field_grid on a one-voxel-thick grid across the sites' bounding box: the plane `axis` (0, 1, 2 or "x", "y", "z") =
+    position, voxels of `spacing` along the other two axes, from the box's lower corner to its upper one."""
+    axis = "xyz".index(axis) if isinstance(axis, str) else int(axis)
+    xyz = (gpubuf.site_x, gpubuf.site_y, gpubuf.site_z)
+    lo = np.array([float(t.min()) for t in xyz])
+    hi = np.array([float(t.max()) for t in xyz])
+    h = float(spacing)
+    dims = np.floor((hi - lo) / h).astype(np.int64) + 1
+    lo[axis], dims[axis] = float(position), 1
+    return field_grid(gpubuf, lo, h, dims, **kw)
+
+
+def sample_density(result, radius=None):
+    """The number density (per volume of the coordinates' unit) of a raw sum -- field_sample / field_grid with
+    normalize=False on a 0 / 1 field: out * 105 / (32 pi radius^3), the inverse of the weight's volume integral.  Host-only
+    arithmetic on whatever array type `out` is; radius defaults to the result's own."""
+    r = float(result["radius"] if radius is None else radius)
+    return result["out"] * (105.0 / (32.0 * np.pi * r ** 3))
 
 
 def k_assemble(gpubuf, Vd, high_G, low_G):

@@ -1004,6 +1004,89 @@ int kmcf_defect_correlation(kmcf_pairwise *p, const double *d_x, const double *d
                             kmcf_pair_stats_t *stats /* or NULL */);
 
 /* ---------------------------------------------------------------------- */
+/* Field sampling: site fields on sample points and regular grids             */
+/* (no reference counterpart)                                                  */
+/* ---------------------------------------------------------------------- */
+/* The value of site quantities at points that are not sites: a potential cut, a temperature map, a vacancy density per
+ * voxel, the material of a voxel.  Every point s gathers the MEMBERS within `radius` through the index's cell walk.
+ * Members: site j is a member when d_site_mask is NULL or d_site_mask[j] != 0.
+ * Distance: the index's own, the arithmetic stated above kmcf_pair_correlation with the point in the place of site i --
+ * the plain difference on an open index, the minimum image in y and z on an index of kmcf_compute_cutoff_list_pbc with
+ * pbc == 1 -- formed from the point's coordinates AS GIVEN.  Member j is within reach when d2 <= r2 = radius * radius,
+ * that product formed in double.
+ * Weight: u = d2 / r2;  t = 1.0 - u;  w = t * t  (an IEEE division, no fused multiply-add, no sqrt, no table): 1 on the
+ * member, 0 on the rim.
+ * Per point s:
+ *   d_count[s]       members within reach.
+ *   d_nearest[s]     the member within reach with the smallest (bits of d2, site id), -1 with none; d2 >= 0, so the bit
+ *                    order is the value order, and a tie in d2 goes to the smaller id.
+ *   d_nearest_d2[s]  its d2, +infinity with none.
+ *   d_wsum[s]        the sum of w.
+ *   d_out[f * n_points + s]   acc_f = the sum of w * v_f[j], v_f = d_values + f * N  (normalize == 0), or acc_f / wsum,
+ *                    and `fill` where wsum == 0.0 -- no member within reach, or members on the rim only (normalize == 1: the
+ *                    mean of an intensive field).  A number density is the raw sum of a 0 / 1 field times
+ *                    105 / (32 pi radius^3), the inverse of the weight's volume integral.
+ * Values are not checked: a NaN or an infinity in v_f[j] enters, by the IEEE rules (0 * NaN = NaN on the rim), the
+ * points member j is within reach of, in field f, and nothing else.  `fill` may be anything, a NaN included.
+ * Order of addition (wsum and every acc_f; fixed by the input alone, no atomics on doubles).  The members are laid out in
+ * the order of the index's cells, ascending site id inside a cell.  A point walks the index cell columns (ax, ay) around
+ * its own cell -- ax ascending, then ay in the walk's order: ascending on an open index, (cy - 1, cy, cy + 1) mod ncy on a
+ * periodic one -- and in a column the one or two contiguous runs of members in ascending cell order; the candidates of a
+ * point are numbered 0, 1, ... along that walk.  Sixteen partial sums start at 0.0; candidate number q of a RUN (q counted
+ * from the run's start) that is within reach is added to partial q % 16, in walk order; candidates out of reach add
+ * nothing.  The partials are then combined by a butterfly: for off = 8, 4, 2, 1 every partial l becomes
+ * partial[l] + partial[l ^ off]; the result is partial 0.  Two calls return the same bytes; a NULL mask and a mask of all
+ * ones return the same bytes.
+ * A point need not lie inside the sites' bounding box: the cell rule clamps it into a boundary cell, which only widens
+ * the candidate set.  On a periodic index the sites all lie inside one period [y0, y0 + Ly) by construction of the index;
+ * a point is wrapped into that period -- y - floor((y - y0) / Ly) * Ly -- ONLY to find its cell and the walk's bounds, and a
+ * wrapped value that rounds onto or past a face is clamped like a site there.  The wrap never enters d2.
+ * kmcf_field_grid samples the points (ox + i*hx, oy + j*hy, oz + k*hz), each coordinate one multiplication and one
+ * addition rounded to double, point index (i*ny + j)*nz + k (z fastest), and returns the bytes of kmcf_field_sample on
+ * those points.
+ * stats: n_points; n_empty: points with count 0; n_visits: the sum of count; n_members: sites that passed the mask;
+ * max_count, max_count_point: the largest count and the smallest point index that attains it (0 and -1 with no point);
+ * ms: device time of everything the call enqueued (HIP events).
+ * 0 < radius <= the index's cutoff radius (the reach of the 27-cell walk).  n_points == 0: KMCF_OK, nothing is written,
+ * the stats are zero.  Both calls are LOCAL operations on WHOLE-device arrays of the index's N sites, like
+ * kmcf_site_set_gap: no collectives, scratch on the index (freed by kmcf_pairwise_destroy; it holds nothing a later call
+ * reads), the scratch of the other analyses untouched, one synchronisation per call.
+ * KMCF_ERR_ARG before anything needs a device (kmcf_last_error names the argument and the call; p is checked last): NULL
+ * d_x, d_y or d_z; n_fields outside 0 .. KMCF_FS_MAX_FIELDS; d_values or d_out NULL with n_fields > 0 (an array of no
+ * element, d_out with n_points == 0, may be NULL) or non-NULL with n_fields == 0; n_points < 0; NULL d_px, d_py or d_pz
+ * with n_points > 0; for the grid a NULL h_origin, h_spacing or h_dims, a spacing that is not finite or <= 0, a dim < 1, a
+ * product of the dims >= 2^31, an origin that is not finite; radius not finite, <= 0 or above the index's cutoff radius;
+ * normalize neither 0 nor 1; every output and stats NULL; p NULL.
+ * KMCF_ERR_ARG at the call's synchronisation, the message naming the first such point: a point coordinate that is not
+ * finite; on a periodic index a point further than 1000 periods from the index's origin in y or z (the factor keeps the
+ * rounding of the wrap near 2e-13 of a period, far inside the margin of the walk's bounds).  The outputs are then
+ * unspecified. */
+#define KMCF_FS_MAX_FIELDS 8
+typedef struct {
+    long long n_points, n_empty, n_visits;
+    int n_members;
+    int max_count, max_count_point;
+    float ms;
+} kmcf_sample_stats_t;
+
+int kmcf_field_sample(kmcf_pairwise *p, const double *d_x, const double *d_y, const double *d_z,
+                      const int *d_site_mask /* N or NULL */,
+                      int n_fields, const double *d_values /* n_fields * N, field-major; NULL iff n_fields == 0 */,
+                      int n_points, const double *d_px, const double *d_py, const double *d_pz,
+                      double radius, int normalize, double fill,
+                      double *d_out /* n_fields * n_points, field-major; NULL iff n_fields == 0 */,
+                      double *d_wsum /* n_points or NULL */, int *d_count /* n_points or NULL */,
+                      int *d_nearest /* n_points or NULL */, double *d_nearest_d2 /* n_points or NULL */,
+                      kmcf_sample_stats_t *stats /* or NULL */);
+
+int kmcf_field_grid(kmcf_pairwise *p, const double *d_x, const double *d_y, const double *d_z,
+                    const int *d_site_mask /* N or NULL */, int n_fields, const double *d_values,
+                    const double *h_origin /* 3 */, const double *h_spacing /* 3, > 0 */, const int *h_dims /* 3, >= 1 */,
+                    double radius, int normalize, double fill,
+                    double *d_out /* n_fields * nx*ny*nz */, double *d_wsum, int *d_count, int *d_nearest,
+                    double *d_nearest_d2, kmcf_sample_stats_t *stats /* or NULL */);
+
+/* ---------------------------------------------------------------------- */
 /* T path: current solve (Kirchhoff matrix with two virtual nodes + WKB       */
 /* tunnelling sub-block), SURVEY 8 rows a14 / f3.  PARITY UNPINNED: no         */
 /* reference fixture exercises it (src/KMC_comm.h:243 disables it from main).  */

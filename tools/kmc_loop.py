@@ -59,7 +59,14 @@ counts.  Cells from structure.crossbar_lines on the crossbar workloads (one cell
 per cell and for the rest, `pairs cell <c>: V0 <n> V+ <n> ion <n> | V-V first <lo>-<hi> A peak <lo>-<hi> A (<pairs>) | V-ion
 first .. peak ..` -- V-V: the three vacancy-vacancy class pairs added, V-ion: the two vacancy-ion ones; first: the first
 non-empty bin, peak: the fullest one (the first among equals) -- then `pairs device: <pairs> pairs, <members> defects,
-<probes> probes | densest site <site> (<count> defects within R) | <ms> ms`.
+<probes> probes | densest site <site> (<count> defects within R) | <ms> ms`.  --field-grid H [--field-grid-radius R] samples,
+after the last step, site fields on a grid of spacing H angstrom (kmcf_field_grid through solvers.field_grid; radius R, at
+most and by default 20) over the bounding box of every cell of structure.crossbar_lines on the crossbar workloads (one cell
+otherwise): the potential the events read as a weighted mean, the neutral vacancies as a number density
+(solvers.sample_density) and the element of the nearest site.  Per cell it prints `field grid cell <c>: <nx> x <ny> x <nz>
+voxels of H A, radius R A | <visits> visits, <empty> empty | potential <min> .. <max> V | densest voxel (<i>, <j>, <k>)
+<density> V0/A^3 (<n> neutral vacancies within reach) | <ms> ms + <ms> ms`; nothing is written unless --field-grid-out
+FILE.npz names a file (potential, vacancy_density, element, count, origin, spacing; `_cell<c>` appended with several cells).
 """
 import argparse
 import os
@@ -110,8 +117,21 @@ def main():
                     help="defect pair correlation after every step, up to R angstrom (<= 20): defect counts per crossbar cell, "
                          "first and fullest bin of the vacancy-vacancy and vacancy-ion distances, the densest site")
     ap.add_argument("--pair-bins", type=int, default=20, metavar="N", help="with --pair-correlation: bins of the histograms (<= 256)")
+    ap.add_argument("--field-grid", type=float, default=None, metavar="H",
+                    help="after the last step: the potential the events read, the neutral-vacancy density and the element of "
+                         "the nearest site on a grid of spacing H angstrom over every crossbar cell's box")
+    ap.add_argument("--field-grid-radius", type=float, default=None, metavar="R",
+                    help="with --field-grid: the sampling radius in angstrom (at most and by default the cell edge of the spatial index)")
+    ap.add_argument("--field-grid-out", default=None, metavar="FILE.npz",
+                    help="with --field-grid: write the grids (potential, vacancy_density, element, count, origin, spacing per cell)")
     a = ap.parse_args()
     periodic = a.workload == "5nm-periodic"
+    if a.field_grid is not None and not (np.isfinite(a.field_grid) and a.field_grid > 0.0):
+        ap.error("--field-grid %g: the spacing is > 0" % a.field_grid)
+    if a.field_grid_radius is not None and (a.field_grid is None or not a.field_grid_radius > 0.0):
+        ap.error("--field-grid-radius R: R > 0, with --field-grid")
+    if a.field_grid_out is not None and a.field_grid is None:
+        ap.error("--field-grid-out needs --field-grid")
     if a.scheme and a.workload in ("5nm", "5nm-periodic"):
         ap.error("--scheme needs a crossbar with lines: --workload 40nm or conducting")
     if a.current_map and not a.current:
@@ -150,6 +170,8 @@ def main():
     pbc = 1 if periodic else 0                # (the other workloads keep the reference GPU path's open list and pairwise term)
     S.compute_neighbor_list(comm, buf, d["nn_dist"], 52, pbc=pbc)
     S.compute_cutoff_list(comm, buf, 20.0, pbc=pbc)
+    if a.field_grid_radius is not None and a.field_grid_radius > buf.cutoff_radius:
+        ap.error("--field-grid-radius %g: at most %g, the cell edge of the spatial index" % (a.field_grid_radius, buf.cutoff_radius))
     S.events_set_lattice(comm, d["lattice"], pbc)
     S.initialize_sparsity_K(buf, d["pbc"], d["nn_dist"], NL, comm)
     layers = km.structure.LAYERS
@@ -423,6 +445,41 @@ def main():
                                                      tc + tb + tp + tg + te, kmc_time, clusters), flush=True)
         for line in field_lines:
             print(line, flush=True)
+    if a.field_grid is not None:
+        # (site_potential_charge: boundary + charge as of the last step's sum / gather -- the potential its events read)
+        h, radius = a.field_grid, buf.cutoff_radius if a.field_grid_radius is None else a.field_grid_radius
+        if a.workload in ("5nm", "5nm-periodic"):
+            cells = np.zeros(N, np.int32)
+        else:
+            cells = km.structure.crossbar_lines(d)[2] if cell_of_site is None else cell_of_site
+        neutral = ((buf.site_element == km.structure.VACANCY) & (buf.site_charge == 0)).to(torch.int32)
+        ones = torch.ones(1, N, dtype=torch.float64, device="cuda")
+        saved = {}
+        for c in range(int(cells.max()) + 1):
+            box = d["xyz"][cells == c]
+            lo, hi = box.min(0), box.max(0)
+            dims = np.floor((hi - lo) / h).astype(np.int64) + 1
+            pot = S.field_grid(buf, lo, h, dims, buf.site_potential_charge, radius=radius, labels=buf.site_element)
+            vac = S.field_grid(buf, lo, h, dims, ones, mask=neutral, radius=radius, normalize=False)
+            dens = S.sample_density(vac)[0]
+            v = pot["out"][0]
+            seen = ~torch.isnan(v)
+            k = int(torch.argmax(dens))
+            ijk = np.unravel_index(k, tuple(int(n) for n in dims))
+            st_f = pot["stats"]
+            print("  field grid cell %d: %d x %d x %d voxels of %g A, radius %g A | %d visits, %d empty | potential %s V | "
+                  "densest voxel (%d, %d, %d) %.4e V0/A^3 (%d neutral vacancies within reach) | %.3f ms + %.3f ms" % (
+                      c, dims[0], dims[1], dims[2], h, radius, st_f["n_visits"], st_f["n_empty"],
+                      "%.6f .. %.6f" % (float(v[seen].min()), float(v[seen].max())) if bool(seen.any()) else "none",
+                      ijk[0], ijk[1], ijk[2], float(dens.reshape(-1)[k]), int(vac["count"].reshape(-1)[k]), st_f["ms"],
+                      vac["stats"]["ms"]), flush=True)
+            if a.field_grid_out is not None:
+                tag = "" if int(cells.max()) == 0 else "_cell%d" % c
+                saved.update({"potential" + tag: v.cpu().numpy(), "vacancy_density" + tag: dens.cpu().numpy(),
+                              "element" + tag: pot["labels"].cpu().numpy(), "count" + tag: pot["count"].cpu().numpy(),
+                              "origin" + tag: lo, "spacing" + tag: np.float64(h)})
+        if a.field_grid_out is not None:
+            np.savez(a.field_grid_out, **saved)
     buf.freeGPUmemory()
     comm.close()
 
