@@ -1,8 +1,9 @@
 // The walk over the spatial index of kmcf_compute_cutoff_list(_pbc) that the pairwise term (kmcf_pairwise.hip), the gap
-// search (kmcf_gap.hip) and the chain search (kmcf_chain.hip) share.  Device only.
+// search (kmcf_gap.hip), the chain search (kmcf_chain.hip), the pair correlation (kmcf_paircorr.hip) and the field
+// sampling (kmcf_fieldsample.hip) share.  Device only.  The list it walks is built by kmcf_cellmembers.hpp.
 //
-// A group of 16 lanes serves one member (a site).  kmcf_walk_columns enumerates the columns (ax, ay) of the 27 index
-// cells around the member; the cells of a column that the member reaches are one or two contiguous runs [b, e) of a list
+// A group of 16 lanes serves one member (a site) or sample point.  kmcf_walk_columns enumerates the columns (ax, ay) of
+// the 27 index cells around it; the cells of a column that it reaches are one or two contiguous runs [b, e) of a list
 // compacted in cell order (pos[] holds, per slot of the cell order, the list position).  Per column, in this order:
 //   keep(bound)  bound = lx*lx + ly*ly, a lower bound of the squared (x, y) distance to every site of the column;
 //                false: the column is skipped (z is not pruned)
@@ -14,7 +15,7 @@
 // depend on the member alone too or be read by the group's first lane and broadcast: the 16 lanes of a group then take
 // every branch of the walk together and reach every __shfl_xor in end() together.  Only the stride over a run is per lane.
 #pragma once
-#include "kmcf_internal.hpp"
+#include "kmcf_cellmembers.hpp"
 
 constexpr unsigned long long KMCF_D2_INF = 0x7ff0000000000000ull;      // bits of +infinity: no d2 seen
 constexpr unsigned long long KMCF_NO_PAIR = ~0ull;                     // a packed pair: none

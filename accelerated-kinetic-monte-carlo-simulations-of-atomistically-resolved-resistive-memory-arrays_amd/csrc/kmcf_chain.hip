@@ -11,7 +11,8 @@
 //   2    counts of the sides per gap cell, smallest L / R site per cell, home per node        [integer atomicAdd / atomicMin]
 //   3    vertex and vertex cell per site; stones and stone sites per cell; members = sites of the vertices of cells with
 //        both terminals and no site on both sides (NONE and BRIDGED cells drop out)
-//   4-6  compact the members per INDEX cell with coordinates, vertex cell, vertex and component (kmcf_block.hpp)
+//   4-6  compact the members per INDEX cell with coordinates, vertex cell, vertex and component: the shared compaction of
+//        kmcf_cellmembers.hpp (ch_rule, ch_emit)
 //   round r = 1, 2, ... (Boruvka):
 //     a  search: 16 lanes per member walk the runs of the 27 surrounding index cells over the candidates of the same vertex
 //        cell and another component; the group's minimum (d2, smallest partner) is stored per member and lowers the
@@ -74,10 +75,8 @@ struct kmcf_chain_ws {
     int *d_surf = nullptr;                       // per site: found a partner in round 1
     int *d_root = nullptr, *d_next = nullptr;    // per vertex: component root; the hook of this round
     u64 *d_cbest = nullptr, *d_cpair = nullptr;  // per component root: bits of the smallest d2, packed pair
-    int *d_sum = nullptr;                        // tiles + 1: tile counts / offsets; the list's length in d_sum[tiles]
-    int *d_lpos = nullptr;                       // N + 1: exclusive scan of the list flags in index-cell order
-    int *d_lsite = nullptr, *d_lvcell = nullptr, *d_lvert = nullptr, *d_lcomp = nullptr;   // the list (index-cell order)
-    double *d_lx = nullptr, *d_ly = nullptr, *d_lz = nullptr;
+    kmcf_members l;                              // the list (index-cell order) with coordinates; its length in d_sum[tiles]
+    int *d_lvcell = nullptr, *d_lvert = nullptr, *d_lcomp = nullptr;   // ... vertex cell, vertex and component
     u64 *d_ld2 = nullptr;                        // per list member: bits of its smallest d2
     int *d_lj = nullptr;                         // ... and the partner (-1: none)
     ch_edge *d_edges = nullptr;                  // N
@@ -91,9 +90,10 @@ void kmcf_chain_ws_free(kmcf_pairwise *p)
 {
     if (!p || !p->chain_ws) return;
     kmcf_chain_ws *w = p->chain_ws;
+    kmcf_members_free(&w->l);
     kmcf_dev_free_all({w->d_side, w->d_node, w->d_home, w->d_svert, w->d_svcell, w->d_surf, w->d_root, w->d_next, w->d_cbest,
-                       w->d_cpair, w->d_sum, w->d_lpos, w->d_lsite, w->d_lvcell, w->d_lvert, w->d_lcomp, w->d_lx, w->d_ly, w->d_lz,
-                       w->d_ld2, w->d_lj, w->d_edges, w->d_flags, w->d_words, w->d_direct});
+                       w->d_cpair, w->d_lvcell, w->d_lvert, w->d_lcomp, w->d_ld2, w->d_lj, w->d_edges, w->d_flags, w->d_words,
+                       w->d_direct});
     delete w;
     p->chain_ws = nullptr;
 }
@@ -210,57 +210,25 @@ __global__ __launch_bounds__(KMCF_BLOCK) void ch_vertex_kernel(int N, const int 
     svcell[i] = vc;
 }
 
-// 4: per-tile counts of the list flags.  surf == nullptr: the members; else: the surface members
-__device__ __forceinline__ int ch_flag(const int *__restrict__ svert, const int *__restrict__ surf, int i)
-{
-    return svert[i] >= 0 && (!surf || surf[i]);
-}
-
-__global__ __launch_bounds__(KMCF_BLOCK) void ch_flag_count_kernel(int N, const int *__restrict__ cell_order,
-                                                                   const int *__restrict__ svert, const int *__restrict__ surf,
-                                                                   int *__restrict__ sum)
-{
-    __shared__ int lds[4];
-    int f[KMCF_SCAN_ITEMS];
-    kmcf_tile_flags(N, f, [&](int t) { return ch_flag(svert, surf, cell_order[t]); });
-    const int n = kmcf_tile_count(f, lds);
-    if (threadIdx.x == 0) sum[blockIdx.x] = n;
-}
-
-// 6: positions of the flags (every slot of the cell order: the runs of the search start at cell boundaries) and the list
-__global__ __launch_bounds__(KMCF_BLOCK) void ch_scatter_kernel(int N, int nb, const int *__restrict__ cell_order,
-                                                                const int *__restrict__ svert, const int *__restrict__ surf,
-                                                                const int *__restrict__ svcell, const int *__restrict__ root,
-                                                                const double *__restrict__ x, const double *__restrict__ y,
-                                                                const double *__restrict__ z, const int *__restrict__ sum,
-                                                                int *__restrict__ lpos, int *__restrict__ lsite,
-                                                                int *__restrict__ lvcell, int *__restrict__ lvert,
-                                                                int *__restrict__ lcomp, double *__restrict__ lx,
-                                                                double *__restrict__ ly, double *__restrict__ lz)
-{
-    __shared__ int lds[4];
-    const int t0 = kmcf_tile_item0();
-    int f[KMCF_SCAN_ITEMS], site[KMCF_SCAN_ITEMS];
-    kmcf_tile_flags(N, f, [&](int t) { return ch_flag(svert, surf, site[t - t0] = cell_order[t]); });
-    int pos = kmcf_tile_pos(f, sum[blockIdx.x], lds);
-#pragma unroll
-    for (int k = 0; k < KMCF_SCAN_ITEMS; ++k) {
-        const int t = t0 + k;
-        if (t >= N) break;
-        lpos[t] = pos;
-        if (!f[k]) continue;
-        const int i = site[k], v = svert[i];
-        lsite[pos] = i;
-        lvcell[pos] = svcell[i];
-        lvert[pos] = v;
-        lcomp[pos] = root[v];
-        lx[pos] = x[i];
-        ly[pos] = y[i];
-        lz[pos] = z[i];
-        ++pos;
+// 4-6, the list.  surf == nullptr: the members; else: the surface members.  With coordinates, vertex cell, vertex, component
+struct ch_rule {
+    const int *svert, *surf;
+    __device__ __forceinline__ int operator()(int i) const { return svert[i] >= 0 && (!surf || surf[i]); }
+};
+struct ch_emit {
+    const int *svert, *svcell, *root;
+    const double *x, *y, *z;
+    kmcf_members l;
+    int *lvcell, *lvert, *lcomp;
+    __device__ __forceinline__ void operator()(int, int q, int i, int) const
+    {
+        const int v = svert[i];
+        kmcf_member_put(l, q, i, x, y, z);
+        lvcell[q] = svcell[i];
+        lvert[q] = v;
+        lcomp[q] = root[v];
     }
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == KMCF_BLOCK - 1) lpos[N] = sum[nb];
-}
+};
 
 // a: the search of one round over the list, on the open (GRID = kmcf_cell_grid) or the periodic index (kmcf_cell_grid_pbc).
 // A group of CH_LPS lanes per member; the loop runs over whole blocks of groups, and both thresholds are uniform over a
@@ -445,15 +413,13 @@ int ch_workspace(kmcf_pairwise *p, size_t n_cells)
 {
     if (!p->chain_ws) {
         kmcf_chain_ws *w = p->chain_ws = new kmcf_chain_ws();
-        const size_t n = (size_t)p->N, nb = (n + KMCF_SCAN_TILE - 1) / KMCF_SCAN_TILE;
+        const size_t n = (size_t)p->N;
         w->N = p->N;
+        KMCF_TRY(kmcf_members_alloc(&w->l, p->N, 1, true));
         for (int **q : {&w->d_side, &w->d_node, &w->d_home, &w->d_svert, &w->d_svcell, &w->d_surf, &w->d_root, &w->d_next,
-                        &w->d_lsite, &w->d_lvcell, &w->d_lvert, &w->d_lcomp, &w->d_lj})
+                        &w->d_lvcell, &w->d_lvert, &w->d_lcomp, &w->d_lj})
             KMCF_TRY(kmcf_dev_alloc(q, n, false));
         for (u64 **q : {&w->d_cbest, &w->d_cpair, &w->d_ld2}) KMCF_TRY(kmcf_dev_alloc(q, n, false));
-        for (double **q : {&w->d_lx, &w->d_ly, &w->d_lz}) KMCF_TRY(kmcf_dev_alloc(q, n, false));
-        KMCF_TRY(kmcf_dev_alloc(&w->d_lpos, n + 1, false));
-        KMCF_TRY(kmcf_dev_alloc(&w->d_sum, nb + 1, false));
         KMCF_TRY(kmcf_dev_alloc(&w->d_edges, n, false));
         KMCF_TRY(kmcf_dev_alloc(&w->d_flags, (size_t)CH_F_WORDS, false));
     }
@@ -472,35 +438,22 @@ int ch_check_common(const char *what, const kmcf_pairwise *p, const double *d_x,
                     double r_max, const int *d_site_cell, int n_cells, const kmcf_chain_t *h_chains, const kmcf_hop_t *h_hops,
                     int max_hops, bool periodic_ok)
 {
-    KMCF_CHECK(d_x, KMCF_ERR_ARG, "%s: d_x is NULL", what);
-    KMCF_CHECK(d_y, KMCF_ERR_ARG, "%s: d_y is NULL", what);
-    KMCF_CHECK(d_z, KMCF_ERR_ARG, "%s: d_z is NULL", what);
+    KMCF_TRY(kmcf_check_coords(what, d_x, d_y, d_z));
     KMCF_CHECK(h_chains, KMCF_ERR_ARG, "%s: h_chains is NULL", what);
-    KMCF_CHECK(std::isfinite(r_max), KMCF_ERR_ARG, "%s: r_max is not finite", what);
-    KMCF_CHECK(r_max > 0.0, KMCF_ERR_ARG, "%s: r_max = %g is not > 0", what, r_max);
-    KMCF_CHECK(n_cells >= 1, KMCF_ERR_ARG, "%s: n_cells = %d is not >= 1", what, n_cells);
-    KMCF_CHECK(d_site_cell || n_cells == 1, KMCF_ERR_ARG, "%s: d_site_cell is NULL with n_cells = %d", what, n_cells);
+    KMCF_TRY(kmcf_check_radius(what, "r_max", r_max));
+    KMCF_TRY(kmcf_check_cells(what, d_site_cell, n_cells));
     KMCF_CHECK(max_hops >= 0, KMCF_ERR_ARG, "%s: max_hops = %d is negative", what, max_hops);
     KMCF_CHECK(!h_hops || max_hops > 0, KMCF_ERR_ARG, "%s: h_hops is set with max_hops = 0", what);
     KMCF_CHECK(h_hops || max_hops == 0, KMCF_ERR_ARG, "%s: h_hops is NULL with max_hops = %d", what, max_hops);
-    KMCF_CHECK(p, KMCF_ERR_ARG, "%s: p is NULL", what);
-    KMCF_CHECK(periodic_ok || !p->pbc, KMCF_ERR_ARG, "%s: the index is periodic (kmcf_compute_cutoff_list_pbc with pbc = 1) and "
-               "this chain search is non-periodic: call %s_pbc for the minimum image, or build a non-periodic index", what, what);
-    KMCF_CHECK(r_max <= p->cutoff, KMCF_ERR_ARG, "%s: r_max = %g exceeds the index's cutoff radius %g", what, r_max, p->cutoff);
-    return KMCF_OK;
+    return kmcf_check_index(what, p, "r_max", r_max, periodic_ok ? nullptr : "chain");
 }
 
-// steps 4-6: the list of the members (surf == nullptr) or of the surface members
+// steps 4-6 (kmcf_cellmembers.hpp): the list of the members (surf == nullptr) or of the surface members
 void ch_compact(kmcf_pairwise *p, const int *surf, const double *d_x, const double *d_y, const double *d_z)
 {
     kmcf_chain_ws *w = p->chain_ws;
-    hipStream_t st = p->comm->stream;
-    const int N = p->N, nb = (N + KMCF_SCAN_TILE - 1) / KMCF_SCAN_TILE;
-    ch_flag_count_kernel<<<nb, KMCF_BLOCK, 0, st>>>(N, p->d_cell_order, w->d_svert, surf, w->d_sum);
-    kmcf_scan_counts_kernel<int><<<1, KMCF_BLOCK, 0, st>>>(nb, w->d_sum, w->d_sum, nb + 1);
-    ch_scatter_kernel<<<nb, KMCF_BLOCK, 0, st>>>(N, nb, p->d_cell_order, w->d_svert, surf, w->d_svcell, w->d_root, d_x, d_y, d_z,
-                                                w->d_sum, w->d_lpos, w->d_lsite, w->d_lvcell, w->d_lvert, w->d_lcomp, w->d_lx,
-                                                w->d_ly, w->d_lz);
+    kmcf_members_enqueue<1>(p, w->l, ch_rule{w->d_svert, surf},
+                            ch_emit{w->d_svert, w->d_svcell, w->d_root, d_x, d_y, d_z, w->l, w->d_lvcell, w->d_lvert, w->d_lcomp});
 }
 
 struct ch_result {
@@ -513,11 +466,11 @@ int ch_search(const char *what, kmcf_pairwise *p, const double *d_x, const doubl
 {
     kmcf_chain_ws *w = p->chain_ws;
     hipStream_t st = p->comm->stream;
-    const int N = p->N, nb = (N + KMCF_SCAN_TILE - 1) / KMCF_SCAN_TILE;
+    const int N = p->N;
     const int site_grid = (N + KMCF_BLOCK - 1) / KMCF_BLOCK;
     const size_t nc = (size_t)n_cells;
     const int cell_grid = (int)((nc + KMCF_BLOCK - 1) / KMCF_BLOCK);
-    const int *n_list = w->d_sum + nb;
+    const int *n_list = w->l.d_sum + kmcf_member_tiles(N);
     const int search_grid = (int)std::min<int64_t>(8192, ((int64_t)N + CH_SPB - 1) / CH_SPB);   // the kernel strides
     const int list_grid = std::min(site_grid, 2048);
     const double rmax2 = r_max * r_max;
@@ -530,16 +483,15 @@ int ch_search(const char *what, kmcf_pairwise *p, const double *d_x, const doubl
     ch_compact(p, nullptr, d_x, d_y, d_z);
     const auto search = [&](auto grid, bool first) {     // step a: the instantiation for the index and the round
         const auto kernel = first ? ch_search_kernel<true, decltype(grid)> : ch_search_kernel<false, decltype(grid)>;
-        kernel<<<search_grid, KMCF_BLOCK, 0, st>>>(grid, p->d_cell_start, w->d_lpos, n_list, w->d_lsite, w->d_lvcell, w->d_lcomp,
-                                                  w->d_lx, w->d_ly, w->d_lz, rmax2, w->d_words, w->d_cbest, w->d_direct, w->d_ld2,
-                                                  w->d_lj, w->d_surf, w->d_flags);
+        kernel<<<search_grid, KMCF_BLOCK, 0, st>>>(grid, p->d_cell_start, w->l.d_pos, n_list, w->l.d_site, w->d_lvcell, w->d_lcomp,
+                                                  w->l.d_x, w->l.d_y, w->l.d_z, rmax2, w->d_words, w->d_cbest, w->d_direct,
+                                                  w->d_ld2, w->d_lj, w->d_surf, w->d_flags);
     };
     int h[CH_F_WORDS];
     int edges_before = 0;
     for (int round = 1; round <= CH_MAX_ROUNDS; ++round) {
-        if (p->pbc) search(p->grid_pbc(), round == 1);
-        else search(p->grid(), round == 1);
-        ch_pair_kernel<<<list_grid, KMCF_BLOCK, 0, st>>>(n_list, w->d_lsite, w->d_lcomp, w->d_ld2, w->d_lj, w->d_cbest, w->d_cpair);
+        p->with_grid([&](auto grid) { search(grid, round == 1); });
+        ch_pair_kernel<<<list_grid, KMCF_BLOCK, 0, st>>>(n_list, w->l.d_site, w->d_lcomp, w->d_ld2, w->d_lj, w->d_cbest, w->d_cpair);
         ch_hook_kernel<<<site_grid, KMCF_BLOCK, 0, st>>>(N, w->d_svert, w->d_root, w->d_cbest, w->d_cpair, w->d_next, w->d_edges,
                                                         w->d_flags);
         ch_jump_kernel<<<site_grid, KMCF_BLOCK, 0, st>>>(N, w->d_next, w->d_root, w->d_cbest, w->d_cpair, w->d_flags);

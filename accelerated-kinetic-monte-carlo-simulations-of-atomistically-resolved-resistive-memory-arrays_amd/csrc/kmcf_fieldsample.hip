@@ -5,8 +5,9 @@
 //
 // Launches, all on the compute stream:
 //   0    hipMemsetAsync of the stat words (empty points, visits, packed maximum) and of the two bad-point words
-//   1-3  compact the members (mask) in INDEX cell order with site id, coordinates and the n_fields value rows: the tile
-//        compaction of kmcf_block.hpp on scratch of this file's own; a run of the walk is then a contiguous stream
+//   1-3  compact the members (mask) in INDEX cell order with site id, coordinates and the n_fields value rows: the shared
+//        compaction of kmcf_cellmembers.hpp (fs_rule, fs_emit) on scratch of this file's own; a run of the walk is then a
+//        contiguous stream
 //   4    walk: 16 lanes per point stride over the contiguous runs of the 27 surrounding index cells (radius <= cell edge;
 //        kmcf_walk_columns of kmcf_cellwalk.hpp); count, nearest, wsum and the accumulators of the fields in registers,
 //        reduced over the group by shuffles; lane 0 writes
@@ -21,10 +22,7 @@
 static_assert(sizeof(kmcf_sample_stats_t) == 40, "kmcf_sample_stats_t is 40 bytes");
 
 struct kmcf_fs_ws {
-    int *d_mpos = nullptr;                       // N + 1: exclusive scan of the member flags in index-cell order
-    int *d_sum = nullptr;                        // tiles + 1: tile counts / offsets of the member flags
-    int *d_msite = nullptr;                      // members (index-cell order): site ...
-    double *d_mx = nullptr, *d_my = nullptr, *d_mz = nullptr;         // ... coordinates ...
+    kmcf_members m;                              // members (index-cell order) with coordinates ...
     double *d_mval = nullptr;                    // ... and value rows, field-major with stride N
     size_t cap_mval = 0;
     unsigned long long *d_stat = nullptr;        // FS_STAT_WORDS words: empty points, visits, packed maximum, bad points
@@ -34,7 +32,8 @@ void kmcf_fs_ws_free(kmcf_pairwise *p)
 {
     if (!p || !p->fs_ws) return;
     kmcf_fs_ws *w = p->fs_ws;
-    kmcf_dev_free_all({w->d_mpos, w->d_sum, w->d_msite, w->d_mx, w->d_my, w->d_mz, w->d_mval, w->d_stat});
+    kmcf_members_free(&w->m);
+    kmcf_dev_free_all({w->d_mval, w->d_stat});
     delete w;
     p->fs_ws = nullptr;
 }
@@ -77,51 +76,23 @@ __device__ __forceinline__ bool fs_walk_pos(const kmcf_cell_grid_pbc &g, double 
     return true;
 }
 
-__device__ __forceinline__ int fs_member(const int *__restrict__ mask, int i) { return mask ? mask[i] != 0 : 1; }
-
-// 1: per-tile counts of the members (index-cell order).  2 is kmcf_scan_counts_kernel, in place
-__global__ __launch_bounds__(KMCF_BLOCK) void fs_flag_count_kernel(int N, const int *__restrict__ cell_order,
-                                                                   const int *__restrict__ mask, int *__restrict__ sum)
-{
-    __shared__ int lds[4];
-    int f[KMCF_SCAN_ITEMS];
-    kmcf_tile_flags(N, f, [&](int t) { return fs_member(mask, cell_order[t]); });
-    const int tm = kmcf_tile_count(f, lds);
-    if (threadIdx.x == 0) sum[blockIdx.x] = tm;
-}
-
-// 3: positions of the member flags (every slot of the cell order: the runs of the walk start at cell boundaries) and the
-// members with site id, coordinates and value rows
-__global__ __launch_bounds__(KMCF_BLOCK) void fs_scatter_kernel(int N, int nb, const int *__restrict__ cell_order,
-                                                                const int *__restrict__ mask, const double *__restrict__ x,
-                                                                const double *__restrict__ y, const double *__restrict__ z,
-                                                                int n_fields, const double *__restrict__ values,
-                                                                const int *__restrict__ sum, int *__restrict__ mpos,
-                                                                int *__restrict__ msite, double *__restrict__ mx,
-                                                                double *__restrict__ my, double *__restrict__ mz,
-                                                                double *__restrict__ mval)
-{
-    __shared__ int lds[4];
-    const int t0 = kmcf_tile_item0();
-    int f[KMCF_SCAN_ITEMS], site[KMCF_SCAN_ITEMS];
-    kmcf_tile_flags(N, f, [&](int t) { return fs_member(mask, site[t - t0] = cell_order[t]); });
-    int pm = kmcf_tile_pos(f, sum[blockIdx.x], lds);
-#pragma unroll
-    for (int k = 0; k < KMCF_SCAN_ITEMS; ++k) {
-        const int t = t0 + k;
-        if (t >= N) break;
-        mpos[t] = pm;
-        if (!f[k]) continue;
-        const int i = site[k];
-        msite[pm] = i;
-        mx[pm] = x[i];
-        my[pm] = y[i];
-        mz[pm] = z[i];
-        for (int q = 0; q < n_fields; ++q) mval[(size_t)q * N + pm] = values[(size_t)q * N + i];
-        ++pm;
+// 1-3, the list: the members (mask; none: every site) with site id, coordinates and value rows
+struct fs_rule {
+    const int *mask;
+    __device__ __forceinline__ int operator()(int i) const { return mask ? mask[i] != 0 : 1; }
+};
+struct fs_emit {
+    const double *x, *y, *z;
+    int N, n_fields;
+    const double *values;
+    kmcf_members m;
+    double *mval;
+    __device__ __forceinline__ void operator()(int, int q, int i, int) const
+    {
+        kmcf_member_put(m, q, i, x, y, z);
+        for (int k = 0; k < n_fields; ++k) mval[(size_t)k * N + q] = values[(size_t)k * N + i];
     }
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == KMCF_BLOCK - 1) mpos[N] = sum[nb];
-}
+};
 
 // 4: the walk, on the open (GRID = kmcf_cell_grid) or the periodic index (kmcf_cell_grid_pbc: the minimum image in y and
 // z).  Block b serves the points [b * FS_PASSES * FS_SPB, (b + 1) * FS_PASSES * FS_SPB), FS_SPB per pass, a group of FS_LPS
@@ -235,13 +206,7 @@ int fs_workspace(kmcf_pairwise *p, int n_fields)
 {
     if (!p->fs_ws) {
         kmcf_fs_ws *w = p->fs_ws = new kmcf_fs_ws();
-        const size_t n = (size_t)p->N, nb = (n + KMCF_SCAN_TILE - 1) / KMCF_SCAN_TILE;
-        KMCF_TRY(kmcf_dev_alloc(&w->d_mpos, n + 1, false));
-        KMCF_TRY(kmcf_dev_alloc(&w->d_sum, nb + 1, false));
-        KMCF_TRY(kmcf_dev_alloc(&w->d_msite, n, false));
-        KMCF_TRY(kmcf_dev_alloc(&w->d_mx, n, false));
-        KMCF_TRY(kmcf_dev_alloc(&w->d_my, n, false));
-        KMCF_TRY(kmcf_dev_alloc(&w->d_mz, n, false));
+        KMCF_TRY(kmcf_members_alloc(&w->m, p->N, 1, true));
         KMCF_TRY(kmcf_dev_alloc(&w->d_stat, (size_t)FS_STAT_WORDS, false));
     }
     kmcf_fs_ws *w = p->fs_ws;
@@ -270,9 +235,7 @@ struct fs_call {
 int fs_check_sites(const fs_call &a, bool need_out)
 {
     const char *what = a.what;
-    KMCF_CHECK(a.d_x, KMCF_ERR_ARG, "%s: d_x is NULL", what);
-    KMCF_CHECK(a.d_y, KMCF_ERR_ARG, "%s: d_y is NULL", what);
-    KMCF_CHECK(a.d_z, KMCF_ERR_ARG, "%s: d_z is NULL", what);
+    KMCF_TRY(kmcf_check_coords(what, a.d_x, a.d_y, a.d_z));
     KMCF_CHECK(a.n_fields >= 0 && a.n_fields <= FS_MAX_FIELDS, KMCF_ERR_ARG, "%s: n_fields = %d is outside 0 ... %d", what, a.n_fields,
                FS_MAX_FIELDS);
     KMCF_CHECK(a.n_fields == 0 || a.d_values, KMCF_ERR_ARG, "%s: d_values is NULL with n_fields = %d", what, a.n_fields);
@@ -285,14 +248,11 @@ int fs_check_sites(const fs_call &a, bool need_out)
 int fs_check_rest(const fs_call &a, const kmcf_pairwise *p)
 {
     const char *what = a.what;
-    KMCF_CHECK(std::isfinite(a.radius), KMCF_ERR_ARG, "%s: radius is not finite", what);
-    KMCF_CHECK(a.radius > 0.0, KMCF_ERR_ARG, "%s: radius = %g is not > 0", what, a.radius);
+    KMCF_TRY(kmcf_check_radius(what, "radius", a.radius));
     KMCF_CHECK(a.normalize == 0 || a.normalize == 1, KMCF_ERR_ARG, "%s: normalize = %d is neither 0 nor 1", what, a.normalize);
     KMCF_CHECK(a.d_out || a.d_wsum || a.d_count || a.d_nearest || a.d_nearest_d2 || a.stats, KMCF_ERR_ARG,
                "%s: every output is NULL and stats is NULL: nothing to compute", what);
-    KMCF_CHECK(p, KMCF_ERR_ARG, "%s: p is NULL", what);
-    KMCF_CHECK(a.radius <= p->cutoff, KMCF_ERR_ARG, "%s: radius = %g exceeds the index's cutoff radius %g", what, a.radius, p->cutoff);
-    return KMCF_OK;
+    return kmcf_check_index(what, p, "radius", a.radius, nullptr);
 }
 
 template <class GRID, class POINTS>
@@ -304,8 +264,8 @@ void fs_launch_walk(const GRID &g, const POINTS &pts, kmcf_pairwise *p, const fs
     const double r2 = a.radius * a.radius;
     const auto go = [&](auto nf) {
         fs_walk_kernel<GRID, decltype(nf)::value, POINTS><<<grid, KMCF_BLOCK, 0, p->comm->stream>>>(
-            g, pts, a.n_points, p->d_cell_start, w->d_mpos, w->d_msite, w->d_mx, w->d_my, w->d_mz, w->d_mval, p->N, a.n_fields, r2,
-            a.normalize, a.fill, a.d_out, a.d_wsum, a.d_count, a.d_nearest, a.d_nearest_d2, w->d_stat);
+            g, pts, a.n_points, p->d_cell_start, w->m.d_pos, w->m.d_site, w->m.d_x, w->m.d_y, w->m.d_z, w->d_mval, p->N, a.n_fields,
+            r2, a.normalize, a.fill, a.d_out, a.d_wsum, a.d_count, a.d_nearest, a.d_nearest_d2, w->d_stat);
     };
     if (a.n_fields == 0) go(std::integral_constant<int, 0>());
     else if (a.n_fields == 1) go(std::integral_constant<int, 1>());
@@ -326,22 +286,16 @@ int fs_run(kmcf_pairwise *p, const fs_call &a, const POINTS &pts)
     KMCF_TRY(fs_workspace(p, a.n_fields));
     kmcf_fs_ws *w = p->fs_ws;
     hipStream_t st = c->stream;
-    const int N = p->N;
-    const int nb = (N + KMCF_SCAN_TILE - 1) / KMCF_SCAN_TILE;
     KMCF_HIP(hipEventRecord(c->ev_t0, st));
     KMCF_HIP(hipMemsetAsync(w->d_stat, 0, FS_BAD * sizeof(u64), st));
     KMCF_HIP(hipMemsetAsync(w->d_stat + FS_BAD, FS_NO_POINT & 0xff, sizeof(u64), st));
-    fs_flag_count_kernel<<<nb, KMCF_BLOCK, 0, st>>>(N, p->d_cell_order, a.d_site_mask, w->d_sum);
-    kmcf_scan_counts_kernel<int><<<1, KMCF_BLOCK, 0, st>>>(nb, w->d_sum, w->d_sum, nb + 1);
-    fs_scatter_kernel<<<nb, KMCF_BLOCK, 0, st>>>(N, nb, p->d_cell_order, a.d_site_mask, a.d_x, a.d_y, a.d_z, a.n_fields, a.d_values,
-                                                w->d_sum, w->d_mpos, w->d_msite, w->d_mx, w->d_my, w->d_mz, w->d_mval);
-    if (p->pbc) fs_launch_walk(p->grid_pbc(), pts, p, a);
-    else fs_launch_walk(p->grid(), pts, p, a);
+    kmcf_members_enqueue<1>(p, w->m, fs_rule{a.d_site_mask}, fs_emit{a.d_x, a.d_y, a.d_z, p->N, a.n_fields, a.d_values, w->m, w->d_mval});
+    p->with_grid([&](auto g) { fs_launch_walk(g, pts, p, a); });
     KMCF_HIP(hipGetLastError());
     // the copies, the call's one synchronisation, and what the host forms
     int *h = c->h_pinned;
     KMCF_HIP(hipMemcpyAsync(h, w->d_stat, FS_STAT_WORDS * sizeof(u64), hipMemcpyDeviceToHost, st));
-    KMCF_HIP(hipMemcpyAsync(h + 2 * FS_STAT_WORDS, w->d_sum + nb, sizeof(int), hipMemcpyDeviceToHost, st));   // members
+    KMCF_HIP(hipMemcpyAsync(h + 2 * FS_STAT_WORDS, w->m.d_sum + kmcf_member_tiles(p->N), sizeof(int), hipMemcpyDeviceToHost, st));   // members
     KMCF_HIP(hipEventRecord(c->ev_call1, st));
     KMCF_HIP(hipStreamSynchronize(st));
     const auto word = [&](int k) { return ((u64)(unsigned)h[2 * k + 1] << 32) | (unsigned)h[2 * k]; };

@@ -8,8 +8,8 @@
 //   1    clear the per-cell words
 //   2    counts of the sides per gap cell and for the device                       [integer atomics, one set per wave and cell]
 //   3-5  compact, per INDEX cell (the cells of kmcf_compute_cutoff_list), the B members with their coordinates and gap
-//        cell, and the A members: the tile compaction of kmcf_block.hpp (two sets in one pass), on scratch of this file's own
-//        (kmcf_poisson_gridless keeps its lists)
+//        cell, and the A members: the shared compaction of kmcf_cellmembers.hpp (two sets in one pass; gp_rule, gp_emit),
+//        on scratch of this file's own (kmcf_poisson_gridless keeps its lists)
 //   6    search: 16 lanes per A site walk the contiguous runs of the 27 surrounding index cells (r_max <= cell edge;
 //        kmcf_walk_columns of kmcf_cellwalk.hpp), every lane keeps its lexicographic minimum (d2, b); the group's minimum is
 //        stored per A site and lowers the gap cell's best d2 with a 64-bit integer atomicMin on the bit pattern
@@ -41,11 +41,9 @@ static_assert(sizeof(kmcf_gap_t) == 56, "kmcf_gap_t is 56 bytes");
 struct kmcf_gap_ws {
     int N = 0;                                   // the index's N: the per-site arrays hold that many
     int *d_side = nullptr;                       // side per site (kmcf_filament_gap without d_site_side)
-    int *d_bpos = nullptr;                       // N + 1: exclusive scan of the B flags in index-cell order
-    int *d_sum = nullptr;                        // 2 x (tiles + 1): tile counts / offsets of the A and of the B flags
+    kmcf_members b;                              // B members with coordinates; d_sum: the A and the B flags
+    int *d_bcell = nullptr;                      // ... and their gap cells
     int *d_alist = nullptr, *d_acell = nullptr;  // A members (index-cell order) and their gap cells
-    int *d_bsite = nullptr, *d_bcell = nullptr;  // B members (index-cell order), their gap cells ...
-    double *d_bx = nullptr, *d_by = nullptr, *d_bz = nullptr;   // ... and coordinates
     unsigned long long *d_ad2 = nullptr;         // per A member: bits of its smallest d2 (+inf: none seen)
     int *d_ab = nullptr;                         // ... and the b that gives it (-1: none)
     int *d_stats = nullptr;                      // GP_STAT_* words
@@ -61,8 +59,9 @@ void kmcf_gap_ws_free(kmcf_pairwise *p)
 {
     if (!p || !p->gap_ws) return;
     kmcf_gap_ws *w = p->gap_ws;
-    kmcf_dev_free_all({w->d_side, w->d_bpos, w->d_sum, w->d_alist, w->d_acell, w->d_bsite, w->d_bcell, w->d_bx, w->d_by, w->d_bz,
-                       w->d_ad2, w->d_ab, w->d_stats, w->d_best, w->d_pair, w->d_cnt, w->d_gaps, w->d_prof});
+    kmcf_members_free(&w->b);
+    kmcf_dev_free_all({w->d_side, w->d_alist, w->d_acell, w->d_bcell, w->d_ad2, w->d_ab, w->d_stats, w->d_best, w->d_pair, w->d_cnt,
+                       w->d_gaps, w->d_prof});
     delete w;
     p->gap_ws = nullptr;
 }
@@ -126,72 +125,35 @@ __global__ __launch_bounds__(KMCF_BLOCK) void gp_count_kernel(int N, const int *
     }
 }
 
-// members of the search: side bits (A = 1, B = 2) of a site that lies in a gap cell
-constexpr int GP_A = 1, GP_B = 2;
-__device__ __forceinline__ int gp_flags(const int *__restrict__ side, const int *__restrict__ site_cell, int n_cells, int i)
-{
-    const int s = side[i] & 3;
-    return (s && kmcf_site_cell(site_cell, n_cells, i) >= 0) ? s : 0;
-}
-
-// 3: per-tile counts of the A and of the B members (index-cell order): the A counts in sum[0, nb), the B counts in
-// sum[nb + 1, 2 nb + 1).  4 is kmcf_scan_counts_kernel on the two arrays, in place: totals in sum[nb] and sum[2 nb + 1]
-__global__ __launch_bounds__(KMCF_BLOCK) void gp_flag_count_kernel(int N, int nb, const int *__restrict__ cell_order,
-                                                                   const int *__restrict__ side, const int *__restrict__ site_cell,
-                                                                   int n_cells, int *__restrict__ sum)
-{
-    __shared__ int lds[4];
-    int f[KMCF_SCAN_ITEMS];
-    kmcf_tile_flags(N, f, [&](int t) { return gp_flags(side, site_cell, n_cells, cell_order[t]); });
-    const int ta = kmcf_tile_count(f, lds, GP_A), tb = kmcf_tile_count(f, lds, GP_B);
-    if (threadIdx.x == 0) {
-        sum[blockIdx.x] = ta;
-        sum[nb + 1 + blockIdx.x] = tb;
+// 3-5, the members of the search: side bits (set 0: A, set 1: B, the walked one) of a site that lies in a gap cell; the
+// B members with coordinates and gap cell, the A members with gap cell
+struct gp_rule {
+    const int *side, *site_cell;
+    int n_cells;
+    __device__ __forceinline__ int operator()(int i) const
+    {
+        const int s = side[i] & 3;
+        return (s && kmcf_site_cell(site_cell, n_cells, i) >= 0) ? s : 0;
     }
-}
-
-// 5: positions of the B flags (every slot of the cell order: the runs of the search start at cell boundaries), the B
-// members with coordinates and gap cell, the A members with gap cell
-__global__ __launch_bounds__(KMCF_BLOCK) void gp_scatter_kernel(int N, int nb, const int *__restrict__ cell_order,
-                                                                const int *__restrict__ side, const int *__restrict__ site_cell,
-                                                                int n_cells, const double *__restrict__ x,
-                                                                const double *__restrict__ y, const double *__restrict__ z,
-                                                                const int *__restrict__ sum, int *__restrict__ bpos,
-                                                                int *__restrict__ alist, int *__restrict__ acell,
-                                                                int *__restrict__ bsite, int *__restrict__ bcell,
-                                                                double *__restrict__ bx, double *__restrict__ by,
-                                                                double *__restrict__ bz)
-{
-    __shared__ int lds[4];
-    const int t0 = kmcf_tile_item0();
-    int f[KMCF_SCAN_ITEMS], site[KMCF_SCAN_ITEMS];
-    kmcf_tile_flags(N, f, [&](int t) { return gp_flags(side, site_cell, n_cells, site[t - t0] = cell_order[t]); });
-    int pa = kmcf_tile_pos(f, sum[blockIdx.x], lds, GP_A);
-    int pb = kmcf_tile_pos(f, sum[nb + 1 + blockIdx.x], lds, GP_B);
-#pragma unroll
-    for (int k = 0; k < KMCF_SCAN_ITEMS; ++k) {
-        const int t = t0 + k;
-        if (t >= N) break;
-        bpos[t] = pb;
-        if (!f[k]) continue;
-        const int i = site[k];
+};
+struct gp_emit {
+    const int *site_cell;
+    int n_cells;
+    const double *x, *y, *z;
+    kmcf_members b;
+    int *bcell, *alist, *acell;
+    __device__ __forceinline__ void operator()(int set, int q, int i, int) const
+    {
         const int c = kmcf_site_cell(site_cell, n_cells, i);
-        if (f[k] & GP_A) {
-            alist[pa] = i;
-            acell[pa] = c;
-            ++pa;
-        }
-        if (f[k] & GP_B) {
-            bsite[pb] = i;
-            bcell[pb] = c;
-            bx[pb] = x[i];
-            by[pb] = y[i];
-            bz[pb] = z[i];
-            ++pb;
+        if (set == 0) {
+            alist[q] = i;
+            acell[q] = c;
+        } else {
+            kmcf_member_put(b, q, i, x, y, z);
+            bcell[q] = c;
         }
     }
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == KMCF_BLOCK - 1) bpos[N] = sum[2 * nb + 1];
-}
+};
 
 // 6: the search, on the open (GRID = kmcf_cell_grid) or the periodic index (kmcf_cell_grid_pbc: the minimum image in y and
 // z).  A group of GP_LPS lanes per A member; the loop runs over whole blocks of groups, so every lane of a wave reaches the
@@ -330,18 +292,13 @@ int gp_workspace(kmcf_pairwise *p, size_t n_cells, size_t prof_words)
 {
     if (!p->gap_ws) {
         kmcf_gap_ws *w = p->gap_ws = new kmcf_gap_ws();
-        const size_t n = (size_t)p->N, nb = (n + KMCF_SCAN_TILE - 1) / KMCF_SCAN_TILE;
+        const size_t n = (size_t)p->N;
         w->N = p->N;
+        KMCF_TRY(kmcf_members_alloc(&w->b, p->N, 2, true));
         KMCF_TRY(kmcf_dev_alloc(&w->d_side, n, false));
-        KMCF_TRY(kmcf_dev_alloc(&w->d_bpos, n + 1, false));
-        KMCF_TRY(kmcf_dev_alloc(&w->d_sum, 2 * (nb + 1), false));
         KMCF_TRY(kmcf_dev_alloc(&w->d_alist, n, false));
         KMCF_TRY(kmcf_dev_alloc(&w->d_acell, n, false));
-        KMCF_TRY(kmcf_dev_alloc(&w->d_bsite, n, false));
         KMCF_TRY(kmcf_dev_alloc(&w->d_bcell, n, false));
-        KMCF_TRY(kmcf_dev_alloc(&w->d_bx, n, false));
-        KMCF_TRY(kmcf_dev_alloc(&w->d_by, n, false));
-        KMCF_TRY(kmcf_dev_alloc(&w->d_bz, n, false));
         KMCF_TRY(kmcf_dev_alloc(&w->d_ad2, n, false));
         KMCF_TRY(kmcf_dev_alloc(&w->d_ab, n, false));
         KMCF_TRY(kmcf_dev_alloc(&w->d_stats, (size_t)GP_STAT_WORDS, false));
@@ -363,19 +320,11 @@ int gp_workspace(kmcf_pairwise *p, size_t n_cells, size_t prof_words)
 int gp_check_common(const char *what, const kmcf_pairwise *p, const double *d_x, const double *d_y, const double *d_z,
                     double r_max, const int *d_site_cell, int n_cells, const kmcf_gap_t *h_gaps, bool periodic_ok)
 {
-    KMCF_CHECK(d_x, KMCF_ERR_ARG, "%s: d_x is NULL", what);
-    KMCF_CHECK(d_y, KMCF_ERR_ARG, "%s: d_y is NULL", what);
-    KMCF_CHECK(d_z, KMCF_ERR_ARG, "%s: d_z is NULL", what);
+    KMCF_TRY(kmcf_check_coords(what, d_x, d_y, d_z));
     KMCF_CHECK(h_gaps, KMCF_ERR_ARG, "%s: h_gaps is NULL", what);
-    KMCF_CHECK(std::isfinite(r_max), KMCF_ERR_ARG, "%s: r_max is not finite", what);
-    KMCF_CHECK(r_max > 0.0, KMCF_ERR_ARG, "%s: r_max = %g is not > 0", what, r_max);
-    KMCF_CHECK(n_cells >= 1, KMCF_ERR_ARG, "%s: n_cells = %d is not >= 1", what, n_cells);
-    KMCF_CHECK(d_site_cell || n_cells == 1, KMCF_ERR_ARG, "%s: d_site_cell is NULL with n_cells = %d", what, n_cells);
-    KMCF_CHECK(p, KMCF_ERR_ARG, "%s: p is NULL", what);
-    KMCF_CHECK(periodic_ok || !p->pbc, KMCF_ERR_ARG, "%s: the index is periodic (kmcf_compute_cutoff_list_pbc with pbc = 1) and "
-               "this gap search is non-periodic: call %s_pbc for the minimum image, or build a non-periodic index", what, what);
-    KMCF_CHECK(r_max <= p->cutoff, KMCF_ERR_ARG, "%s: r_max = %g exceeds the index's cutoff radius %g", what, r_max, p->cutoff);
-    return KMCF_OK;
+    KMCF_TRY(kmcf_check_radius(what, "r_max", r_max));
+    KMCF_TRY(kmcf_check_cells(what, d_site_cell, n_cells));
+    return kmcf_check_index(what, p, "r_max", r_max, periodic_ok ? nullptr : "gap");
 }
 
 // steps 1-8 (and 9 with cls and a profile) enqueued behind whatever produced d_side
@@ -386,11 +335,10 @@ int gp_enqueue(kmcf_pairwise *p, const double *d_x, const double *d_y, const dou
     kmcf_gap_ws *w = p->gap_ws;
     hipStream_t st = p->comm->stream;
     const int N = p->N;
-    const int nb = (N + KMCF_SCAN_TILE - 1) / KMCF_SCAN_TILE;
     const int site_grid = (N + KMCF_BLOCK - 1) / KMCF_BLOCK;
     const size_t nc = (size_t)n_cells;
     const int cell_grid = (int)((nc + KMCF_BLOCK - 1) / KMCF_BLOCK);
-    const int *n_a = w->d_sum + nb;
+    const int *n_a = w->b.d_sum + kmcf_member_tiles(N);
     int64_t search_grid = ((int64_t)N + GP_SPB - 1) / GP_SPB;      // an upper bound: the kernel strides over the A members
     if (search_grid > 8192) search_grid = 8192;
     int64_t pair_grid = site_grid;
@@ -398,18 +346,13 @@ int gp_enqueue(kmcf_pairwise *p, const double *d_x, const double *d_y, const dou
 
     gp_clear_kernel<<<cell_grid, KMCF_BLOCK, 0, st>>>(nc, w->d_best, w->d_pair, w->d_cnt, w->d_stats);
     gp_count_kernel<<<site_grid, KMCF_BLOCK, 0, st>>>(N, d_side, d_site_cell, n_cells, w->d_cnt, w->d_stats);
-    gp_flag_count_kernel<<<nb, KMCF_BLOCK, 0, st>>>(N, nb, p->d_cell_order, d_side, d_site_cell, n_cells, w->d_sum);
-    kmcf_scan_counts_kernel<int><<<2, KMCF_BLOCK, 0, st>>>(nb, w->d_sum, w->d_sum, nb + 1);
-    gp_scatter_kernel<<<nb, KMCF_BLOCK, 0, st>>>(N, nb, p->d_cell_order, d_side, d_site_cell, n_cells, d_x, d_y, d_z, w->d_sum,
-                                                w->d_bpos, w->d_alist, w->d_acell, w->d_bsite, w->d_bcell, w->d_bx, w->d_by,
-                                                w->d_bz);
-    const auto search = [&](auto grid) {
-        gp_search_kernel<<<(int)search_grid, KMCF_BLOCK, 0, st>>>(grid, p->d_cell_start, w->d_bpos, n_a, w->d_alist, w->d_acell,
-                                                                 w->d_bsite, w->d_bcell, w->d_bx, w->d_by, w->d_bz, d_x, d_y, d_z,
-                                                                 r_max * r_max, w->d_best, w->d_ad2, w->d_ab);
-    };
-    if (p->pbc) search(p->grid_pbc());
-    else search(p->grid());
+    kmcf_members_enqueue<2>(p, w->b, gp_rule{d_side, d_site_cell, n_cells},
+                            gp_emit{d_site_cell, n_cells, d_x, d_y, d_z, w->b, w->d_bcell, w->d_alist, w->d_acell});
+    p->with_grid([&](auto grid) {
+        gp_search_kernel<<<(int)search_grid, KMCF_BLOCK, 0, st>>>(grid, p->d_cell_start, w->b.d_pos, n_a, w->d_alist, w->d_acell,
+                                                                 w->b.d_site, w->d_bcell, w->b.d_x, w->b.d_y, w->b.d_z, d_x, d_y,
+                                                                 d_z, r_max * r_max, w->d_best, w->d_ad2, w->d_ab);
+    });
     gp_pair_kernel<<<(int)pair_grid, KMCF_BLOCK, 0, st>>>(n_a, w->d_alist, w->d_acell, w->d_ad2, w->d_ab, w->d_best, w->d_pair);
     gp_record_kernel<<<cell_grid, KMCF_BLOCK, 0, st>>>(nc, w->d_best, w->d_pair, w->d_cnt, d_x, w->d_gaps, w->d_stats);
     if (profile) {

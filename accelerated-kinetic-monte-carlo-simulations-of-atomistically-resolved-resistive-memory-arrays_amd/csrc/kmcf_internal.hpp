@@ -275,6 +275,15 @@ struct kmcf_cell_grid_pbc {
     int ncx, ncy, ncz;
 };
 
+// The list a pass walks (kmcf_walk_columns): the members of its walked set compacted in index-cell order, built by the
+// shared compaction of kmcf_cellmembers.hpp, which also allocates and frees it.  Every pass owns one: nothing is shared.
+struct kmcf_members {
+    int *d_pos = nullptr;          // N + 1: list position of every slot of the cell order (exclusive scan of the flags)
+    int *d_sum = nullptr;          // sets x (tiles + 1): tile counts / offsets per set; a set's total in its last word
+    int *d_site = nullptr;         // N: the members' sites ...
+    double *d_x = nullptr, *d_y = nullptr, *d_z = nullptr;     // ... and coordinates (passes that keep them)
+};
+
 struct kmcf_pairwise {
     kmcf_comm *comm = nullptr;
     int N = 0;
@@ -287,16 +296,20 @@ struct kmcf_pairwise {
     int ncell = 1;
     int *d_cell_order = nullptr;   // sites sorted by cell (ascending site id inside a cell), N
     int *d_cell_start = nullptr;   // ncell + 1 offsets into d_cell_order
-    int *d_flag_pos = nullptr;     // N + 1: exclusive scan of the charged flags (cell order)
-    int *d_block_sum = nullptr;    // scan scratch
-    int *d_clist = nullptr;        // compacted charged sites (cell order), N
-    int n_blocks = 0;
+    kmcf_members charged;          // kmcf_poisson_gridless: the charged sites (no coordinates), kept across other calls
     struct kmcf_gap_ws *gap_ws = nullptr;   // scratch of kmcf_site_set_gap / kmcf_filament_gap (kmcf_gap.hip): buffers only
     struct kmcf_chain_ws *chain_ws = nullptr;   // scratch of kmcf_site_set_chain / kmcf_filament_chain (kmcf_chain.hip): buffers only
     struct kmcf_pc_ws *pc_ws = nullptr;   // scratch of kmcf_pair_correlation / kmcf_defect_correlation (kmcf_paircorr.hip): buffers only
     struct kmcf_fs_ws *fs_ws = nullptr;   // scratch of kmcf_field_sample / kmcf_field_grid (kmcf_fieldsample.hip): buffers only
     kmcf_cell_grid grid() const { return kmcf_cell_grid{x0, y0, z0, inv, cutoff, ncx, ncy, ncz}; }
     kmcf_cell_grid_pbc grid_pbc() const { return kmcf_cell_grid_pbc{x0, y0, z0, inv, inv_y, inv_z, cutoff, lattice[1], lattice[2], ncx, ncy, ncz}; }
+    // f(the index's geometry): what picks the open or the periodic instantiation of a kernel that walks the index
+    template <class F>
+    void with_grid(F f) const
+    {
+        if (pbc) f(grid_pbc());
+        else f(grid());
+    }
 };
 void kmcf_gap_ws_free(kmcf_pairwise *p);
 void kmcf_chain_ws_free(kmcf_pairwise *p);

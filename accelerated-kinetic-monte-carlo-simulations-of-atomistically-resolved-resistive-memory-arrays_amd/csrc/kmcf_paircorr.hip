@@ -8,8 +8,8 @@
 //   0    hipMemsetAsync of the histogram, the member counts, the packed maximum and (if asked for) the count rows
 //   1    members per bucket and class                                  [integer atomics, one per wave and (bucket, class)]
 //   2-4  compact, per INDEX cell (the cells of kmcf_compute_cutoff_list), the centres (members and probes) with class and
-//        bucket cell, and the members with site id, class, bucket cell and coordinates: the tile compaction of
-//        kmcf_block.hpp, two sets in one pass, on scratch of this file's own
+//        bucket cell, and the members with site id, class, bucket cell and coordinates: the shared compaction of
+//        kmcf_cellmembers.hpp (pc_rule, pc_emit), two sets in one pass, on scratch of this file's own
 //   5    walk: 16 lanes per centre stride over the contiguous runs of the 27 surrounding index cells (r_max <= cell edge;
 //        kmcf_walk_columns of kmcf_cellwalk.hpp); the counts of a centre's row in registers, reduced over the group by
 //        shuffles; the histogram in LDS for the bucket of the block's first centre, in global memory for the others
@@ -31,11 +31,9 @@ static_assert(sizeof(kmcf_pair_stats_t) == 32, "kmcf_pair_stats_t is 32 bytes");
 
 struct kmcf_pc_ws {
     int *d_class = nullptr;                      // class per site (kmcf_defect_correlation without d_site_class)
-    int *d_mpos = nullptr;                       // N + 1: exclusive scan of the member flags in index-cell order
-    int *d_sum = nullptr;                        // 2 x (tiles + 1): tile counts / offsets of the centre and of the member flags
+    kmcf_members m;                              // members (index-cell order) with coordinates; d_sum: the centre and the member flags
+    int *d_mcls = nullptr, *d_mcell = nullptr;   // ... their class and bucket cell
     int *d_csite = nullptr, *d_ccls = nullptr, *d_ccell = nullptr;    // centres (index-cell order): site, class, bucket cell
-    int *d_msite = nullptr, *d_mcls = nullptr, *d_mcell = nullptr;    // members (index-cell order): site, class, bucket cell ...
-    double *d_mx = nullptr, *d_my = nullptr, *d_mz = nullptr;         // ... and coordinates
     unsigned long long *d_max = nullptr;         // packed (largest row sum << 32 | ~site); 0: no centre
     size_t cap_hist = 0, cap_members = 0;
     unsigned long long *d_hist = nullptr;
@@ -46,8 +44,8 @@ void kmcf_pc_ws_free(kmcf_pairwise *p)
 {
     if (!p || !p->pc_ws) return;
     kmcf_pc_ws *w = p->pc_ws;
-    kmcf_dev_free_all({w->d_class, w->d_mpos, w->d_sum, w->d_csite, w->d_ccls, w->d_ccell, w->d_msite, w->d_mcls, w->d_mcell,
-                       w->d_mx, w->d_my, w->d_mz, w->d_max, w->d_hist, w->d_members});
+    kmcf_members_free(&w->m);
+    kmcf_dev_free_all({w->d_class, w->d_csite, w->d_ccls, w->d_ccell, w->d_mcls, w->d_mcell, w->d_max, w->d_hist, w->d_members});
     delete w;
     p->pc_ws = nullptr;
 }
@@ -62,7 +60,6 @@ constexpr int PC_MAX_PAIRS = PC_MAX_CLS * (PC_MAX_CLS + 1) / 2;
 constexpr int PC_LDS_WORDS = PC_MAX_PAIRS * PC_MAX_BINS;          // 2560 32-bit counters: 10 KB
 constexpr int64_t PC_MAX_HIST = (int64_t)1 << 24;
 constexpr int EL_OXYGEN_DEFECT = 1, EL_VACANCY = 2;               // src/utils.h:37-44
-constexpr int PC_C = 1, PC_M = 2;                                 // flag bits: centre, member
 
 struct pc_edges { double e2[PC_MAX_BINS + 1]; };                  // the table, handed to the walk as a kernel argument
 
@@ -79,11 +76,37 @@ __global__ __launch_bounds__(KMCF_BLOCK) void pc_class_kernel(int N, const int *
     cls[i] = c;
 }
 
-// centre / member flags of a site
-__device__ __forceinline__ int pc_flags(int cl, int n_classes)
-{
-    return (unsigned)cl < (unsigned)n_classes ? (PC_C | PC_M) : (cl == n_classes ? PC_C : 0);
-}
+// 2-4, the lists: set 0 the centres (members and probes) with class and bucket cell, set 1 (the walked one) the members
+// with class, bucket cell and coordinates.  A centre's class rides in the flag word above the two set bits
+struct pc_rule {
+    const int *site_class;
+    int n_classes;
+    __device__ __forceinline__ int operator()(int i) const
+    {
+        const int cl = site_class[i];
+        return (unsigned)cl < (unsigned)n_classes ? (cl << 2 | 3) : (cl == n_classes ? (cl << 2 | 1) : 0);
+    }
+};
+struct pc_emit {
+    const int *site_cell;
+    int n_cells;
+    const double *x, *y, *z;
+    kmcf_members m;
+    int *mcls, *mcell, *csite, *ccls, *ccell;
+    __device__ __forceinline__ void operator()(int set, int q, int i, int word) const
+    {
+        const int c = kmcf_site_cell(site_cell, n_cells, i);
+        if (set == 0) {
+            csite[q] = i;
+            ccls[q] = word >> 2;
+            ccell[q] = c;
+        } else {
+            kmcf_member_put(m, q, i, x, y, z);
+            mcls[q] = word >> 2;
+            mcell[q] = c;
+        }
+    }
+};
 
 // 1: a wave adds once per (bucket, class) it meets
 __global__ __launch_bounds__(KMCF_BLOCK) void pc_members_kernel(int N, const int *__restrict__ site_class, int n_classes,
@@ -108,66 +131,6 @@ __global__ __launch_bounds__(KMCF_BLOCK) void pc_members_kernel(int N, const int
         if (lane == leader) atomicAdd(members + lk, __popcll(m));
         if (mine) todo = false;
     }
-}
-
-// 2: per-tile counts of the centres and of the members (index-cell order): the centre counts in sum[0, nb), the member
-// counts in sum[nb + 1, 2 nb + 1).  3 is kmcf_scan_counts_kernel on the two arrays, in place
-__global__ __launch_bounds__(KMCF_BLOCK) void pc_flag_count_kernel(int N, int nb, const int *__restrict__ cell_order,
-                                                                   const int *__restrict__ site_class, int n_classes,
-                                                                   int *__restrict__ sum)
-{
-    __shared__ int lds[4];
-    int f[KMCF_SCAN_ITEMS];
-    kmcf_tile_flags(N, f, [&](int t) { return pc_flags(site_class[cell_order[t]], n_classes); });
-    const int tc = kmcf_tile_count(f, lds, PC_C), tm = kmcf_tile_count(f, lds, PC_M);
-    if (threadIdx.x == 0) {
-        sum[blockIdx.x] = tc;
-        sum[nb + 1 + blockIdx.x] = tm;
-    }
-}
-
-// 4: positions of the member flags (every slot of the cell order: the runs of the walk start at cell boundaries), the
-// members with class, bucket cell and coordinates, the centres with class and bucket cell
-__global__ __launch_bounds__(KMCF_BLOCK) void pc_scatter_kernel(int N, int nb, const int *__restrict__ cell_order,
-                                                                const int *__restrict__ site_class, int n_classes,
-                                                                const int *__restrict__ site_cell, int n_cells,
-                                                                const double *__restrict__ x, const double *__restrict__ y,
-                                                                const double *__restrict__ z, const int *__restrict__ sum,
-                                                                int *__restrict__ mpos, int *__restrict__ csite,
-                                                                int *__restrict__ ccls, int *__restrict__ ccell,
-                                                                int *__restrict__ msite, int *__restrict__ mcls,
-                                                                int *__restrict__ mcell, double *__restrict__ mx,
-                                                                double *__restrict__ my, double *__restrict__ mz)
-{
-    __shared__ int lds[4];
-    const int t0 = kmcf_tile_item0();
-    int f[KMCF_SCAN_ITEMS], site[KMCF_SCAN_ITEMS], cls[KMCF_SCAN_ITEMS];
-    kmcf_tile_flags(N, f, [&](int t) { return pc_flags(cls[t - t0] = site_class[site[t - t0] = cell_order[t]], n_classes); });
-    int pc = kmcf_tile_pos(f, sum[blockIdx.x], lds, PC_C);
-    int pm = kmcf_tile_pos(f, sum[nb + 1 + blockIdx.x], lds, PC_M);
-#pragma unroll
-    for (int k = 0; k < KMCF_SCAN_ITEMS; ++k) {
-        const int t = t0 + k;
-        if (t >= N) break;
-        mpos[t] = pm;
-        if (!f[k]) continue;
-        const int i = site[k];
-        const int c = kmcf_site_cell(site_cell, n_cells, i);
-        csite[pc] = i;
-        ccls[pc] = cls[k];
-        ccell[pc] = c;
-        ++pc;
-        if (f[k] & PC_M) {
-            msite[pm] = i;
-            mcls[pm] = cls[k];
-            mcell[pm] = c;
-            mx[pm] = x[i];
-            my[pm] = y[i];
-            mz[pm] = z[i];
-            ++pm;
-        }
-    }
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == KMCF_BLOCK - 1) mpos[N] = sum[2 * nb + 1];
 }
 
 // 5: the walk, on the open (GRID = kmcf_cell_grid) or the periodic index (kmcf_cell_grid_pbc: the minimum image in y and
@@ -276,19 +239,9 @@ int pc_workspace(kmcf_pairwise *p, size_t hist_words, size_t member_words)
 {
     if (!p->pc_ws) {
         kmcf_pc_ws *w = p->pc_ws = new kmcf_pc_ws();
-        const size_t n = (size_t)p->N, nb = (n + KMCF_SCAN_TILE - 1) / KMCF_SCAN_TILE;
-        KMCF_TRY(kmcf_dev_alloc(&w->d_class, n, false));
-        KMCF_TRY(kmcf_dev_alloc(&w->d_mpos, n + 1, false));
-        KMCF_TRY(kmcf_dev_alloc(&w->d_sum, 2 * (nb + 1), false));
-        KMCF_TRY(kmcf_dev_alloc(&w->d_csite, n, false));
-        KMCF_TRY(kmcf_dev_alloc(&w->d_ccls, n, false));
-        KMCF_TRY(kmcf_dev_alloc(&w->d_ccell, n, false));
-        KMCF_TRY(kmcf_dev_alloc(&w->d_msite, n, false));
-        KMCF_TRY(kmcf_dev_alloc(&w->d_mcls, n, false));
-        KMCF_TRY(kmcf_dev_alloc(&w->d_mcell, n, false));
-        KMCF_TRY(kmcf_dev_alloc(&w->d_mx, n, false));
-        KMCF_TRY(kmcf_dev_alloc(&w->d_my, n, false));
-        KMCF_TRY(kmcf_dev_alloc(&w->d_mz, n, false));
+        const size_t n = (size_t)p->N;
+        KMCF_TRY(kmcf_members_alloc(&w->m, p->N, 2, true));
+        for (int **q : {&w->d_class, &w->d_csite, &w->d_ccls, &w->d_ccell, &w->d_mcls, &w->d_mcell}) KMCF_TRY(kmcf_dev_alloc(q, n, false));
         KMCF_TRY(kmcf_dev_alloc(&w->d_max, (size_t)1, false));
     }
     kmcf_pc_ws *w = p->pc_ws;
@@ -302,27 +255,20 @@ int pc_check_common(const char *what, const kmcf_pairwise *p, const double *d_x,
                     int n_classes, double r_max, int n_bins, double r_count, const int *d_site_cell, int n_cells,
                     const u64 *h_hist, const int *h_members)
 {
-    KMCF_CHECK(d_x, KMCF_ERR_ARG, "%s: d_x is NULL", what);
-    KMCF_CHECK(d_y, KMCF_ERR_ARG, "%s: d_y is NULL", what);
-    KMCF_CHECK(d_z, KMCF_ERR_ARG, "%s: d_z is NULL", what);
+    KMCF_TRY(kmcf_check_coords(what, d_x, d_y, d_z));
     KMCF_CHECK(h_hist, KMCF_ERR_ARG, "%s: h_hist is NULL", what);
     KMCF_CHECK(h_members, KMCF_ERR_ARG, "%s: h_members is NULL", what);
     KMCF_CHECK(n_classes >= 1 && n_classes <= PC_MAX_CLS, KMCF_ERR_ARG, "%s: n_classes = %d is outside 1 ... %d", what, n_classes,
                PC_MAX_CLS);
     KMCF_CHECK(n_bins >= 1 && n_bins <= PC_MAX_BINS, KMCF_ERR_ARG, "%s: n_bins = %d is outside 1 ... %d", what, n_bins, PC_MAX_BINS);
-    KMCF_CHECK(std::isfinite(r_max), KMCF_ERR_ARG, "%s: r_max is not finite", what);
-    KMCF_CHECK(r_max > 0.0, KMCF_ERR_ARG, "%s: r_max = %g is not > 0", what, r_max);
-    KMCF_CHECK(std::isfinite(r_count), KMCF_ERR_ARG, "%s: r_count is not finite", what);
-    KMCF_CHECK(r_count > 0.0, KMCF_ERR_ARG, "%s: r_count = %g is not > 0", what, r_count);
+    KMCF_TRY(kmcf_check_radius(what, "r_max", r_max));
+    KMCF_TRY(kmcf_check_radius(what, "r_count", r_count));
     KMCF_CHECK(r_count <= r_max, KMCF_ERR_ARG, "%s: r_count = %g exceeds r_max = %g", what, r_count, r_max);
-    KMCF_CHECK(n_cells >= 1, KMCF_ERR_ARG, "%s: n_cells = %d is not >= 1", what, n_cells);
-    KMCF_CHECK(d_site_cell || n_cells == 1, KMCF_ERR_ARG, "%s: d_site_cell is NULL with n_cells = %d", what, n_cells);
+    KMCF_TRY(kmcf_check_cells(what, d_site_cell, n_cells));
     const int64_t words = ((int64_t)n_cells + 1) * (n_classes * (n_classes + 1) / 2) * n_bins;
     KMCF_CHECK(words <= PC_MAX_HIST, KMCF_ERR_ARG, "%s: (n_cells + 1) * n_pairs * n_bins = %lld exceeds 2^24: fewer cells or n_bins",
                what, (long long)words);
-    KMCF_CHECK(p, KMCF_ERR_ARG, "%s: p is NULL", what);
-    KMCF_CHECK(r_max <= p->cutoff, KMCF_ERR_ARG, "%s: r_max = %g exceeds the index's cutoff radius %g", what, r_max, p->cutoff);
-    return KMCF_OK;
+    return kmcf_check_index(what, p, "r_max", r_max, nullptr);
 }
 
 struct pc_call {
@@ -346,7 +292,6 @@ int pc_enqueue(kmcf_pairwise *p, const pc_call &a, const int *d_site_class, cons
     kmcf_pc_ws *w = p->pc_ws;
     hipStream_t st = p->comm->stream;
     const int N = p->N;
-    const int nb = (N + KMCF_SCAN_TILE - 1) / KMCF_SCAN_TILE;
     const int site_grid = (N + KMCF_BLOCK - 1) / KMCF_BLOCK;
     const size_t hist_words = ((size_t)a.n_cells + 1) * (size_t)(a.n_classes * (a.n_classes + 1) / 2) * (size_t)a.n_bins;
     const size_t member_words = ((size_t)a.n_cells + 1) * (size_t)a.n_classes;
@@ -361,20 +306,17 @@ int pc_enqueue(kmcf_pairwise *p, const pc_call &a, const int *d_site_class, cons
     KMCF_HIP(hipMemsetAsync(w->d_max, 0, sizeof(u64), st));
     if (a.d_site_count) KMCF_HIP(hipMemsetAsync(a.d_site_count, 0, (size_t)N * a.n_classes * sizeof(int), st));
     pc_members_kernel<<<site_grid, KMCF_BLOCK, 0, st>>>(N, d_site_class, a.n_classes, a.d_site_cell, a.n_cells, w->d_members);
-    pc_flag_count_kernel<<<nb, KMCF_BLOCK, 0, st>>>(N, nb, p->d_cell_order, d_site_class, a.n_classes, w->d_sum);
-    kmcf_scan_counts_kernel<int><<<2, KMCF_BLOCK, 0, st>>>(nb, w->d_sum, w->d_sum, nb + 1);
-    pc_scatter_kernel<<<nb, KMCF_BLOCK, 0, st>>>(N, nb, p->d_cell_order, d_site_class, a.n_classes, a.d_site_cell, a.n_cells, a.d_x,
-                                                a.d_y, a.d_z, w->d_sum, w->d_mpos, w->d_csite, w->d_ccls, w->d_ccell, w->d_msite,
-                                                w->d_mcls, w->d_mcell, w->d_mx, w->d_my, w->d_mz);
-    const auto walk = [&](auto grid) {
-        pc_walk_kernel<<<walk_grid, KMCF_BLOCK, 0, st>>>(grid, p->d_cell_start, w->d_mpos, w->d_sum + nb, w->d_csite, w->d_ccls,
-                                                        w->d_ccell, w->d_msite, w->d_mcls, w->d_mcell, w->d_mx, w->d_my, w->d_mz,
-                                                        a.d_x, a.d_y, a.d_z, a.n_classes, a.n_bins, a.n_cells, a.r_max * a.r_max,
-                                                        a.r_count * a.r_count, (double)a.n_bins / a.r_max, edges, passes, lds,
-                                                        w->d_hist, a.d_site_count, w->d_max);
-    };
-    if (p->pbc) walk(p->grid_pbc());
-    else walk(p->grid());
+    kmcf_members_enqueue<2>(p, w->m, pc_rule{d_site_class, a.n_classes},
+                            pc_emit{a.d_site_cell, a.n_cells, a.d_x, a.d_y, a.d_z, w->m, w->d_mcls, w->d_mcell, w->d_csite, w->d_ccls,
+                                    w->d_ccell});
+    p->with_grid([&](auto grid) {
+        pc_walk_kernel<<<walk_grid, KMCF_BLOCK, 0, st>>>(grid, p->d_cell_start, w->m.d_pos, w->m.d_sum + kmcf_member_tiles(N),
+                                                        w->d_csite, w->d_ccls, w->d_ccell, w->m.d_site, w->d_mcls, w->d_mcell,
+                                                        w->m.d_x, w->m.d_y, w->m.d_z, a.d_x, a.d_y, a.d_z, a.n_classes, a.n_bins,
+                                                        a.n_cells, a.r_max * a.r_max, a.r_count * a.r_count,
+                                                        (double)a.n_bins / a.r_max, edges, passes, lds, w->d_hist, a.d_site_count,
+                                                        w->d_max);
+    });
     KMCF_HIP(hipGetLastError());
     return KMCF_OK;
 }
@@ -386,14 +328,14 @@ int pc_finish(kmcf_pairwise *p, const pc_call &a, const pc_edges &edges)
     kmcf_pc_ws *w = p->pc_ws;
     hipStream_t st = c->stream;
     int *h = c->h_pinned;
-    const int nb = (p->N + KMCF_SCAN_TILE - 1) / KMCF_SCAN_TILE;
+    const int nb = kmcf_member_tiles(p->N);
     const size_t hist_words = ((size_t)a.n_cells + 1) * (size_t)(a.n_classes * (a.n_classes + 1) / 2) * (size_t)a.n_bins;
     const size_t member_words = ((size_t)a.n_cells + 1) * (size_t)a.n_classes;
     KMCF_HIP(hipMemcpyAsync(a.h_hist, w->d_hist, hist_words * sizeof(u64), hipMemcpyDeviceToHost, st));
     KMCF_HIP(hipMemcpyAsync(a.h_members, w->d_members, member_words * sizeof(int), hipMemcpyDeviceToHost, st));
     KMCF_HIP(hipMemcpyAsync(h, w->d_max, sizeof(u64), hipMemcpyDeviceToHost, st));
-    KMCF_HIP(hipMemcpyAsync(h + 2, w->d_sum + nb, sizeof(int), hipMemcpyDeviceToHost, st));             // centres
-    KMCF_HIP(hipMemcpyAsync(h + 3, w->d_sum + 2 * nb + 1, sizeof(int), hipMemcpyDeviceToHost, st));     // members
+    KMCF_HIP(hipMemcpyAsync(h + 2, w->m.d_sum + nb, sizeof(int), hipMemcpyDeviceToHost, st));           // centres
+    KMCF_HIP(hipMemcpyAsync(h + 3, w->m.d_sum + 2 * nb + 1, sizeof(int), hipMemcpyDeviceToHost, st));   // members
     KMCF_HIP(hipEventRecord(c->ev_call1, st));
     KMCF_HIP(hipStreamSynchronize(st));
     if (a.h_edge2)

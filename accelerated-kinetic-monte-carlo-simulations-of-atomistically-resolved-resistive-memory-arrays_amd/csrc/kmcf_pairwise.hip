@@ -7,56 +7,32 @@
 // ints: ~0.6 GB at 5 nm) and walks the whole list every step, skipping the uncharged ones.  Only a few
 // percent of those sites carry a charge, so here the structure is inverted:
 //   init:      sites sorted by 20 A cell (positions never change)            -> kmcf_pairwise
-//   each step: flags of the charged sites in cell order -> exclusive scan -> compacted charged list per
-//              cell (deterministic, all on the device), then 16 lanes per site sum the charged sites of
-//              the 27 surrounding cells.
+//   each step: the charged sites compacted in cell order (the shared compaction of kmcf_cellmembers.hpp:
+//              deterministic, all on the device), then 16 lanes per site sum the charged sites of the 27
+//              surrounding cells.
 // Result per site = sum over charged j != i with dist < cutoff of  q_j erfc(r/(sigma sqrt 2)) k q / r
 // (v_solve_gpu, src/gpu_solvers.h:321-329), the same set the reference's list yields as long as charged
 // sites are V / Od (update_charge only ever charges those, potential_solver_gpu.cu:27-60).
 // kmcf_compute_cutoff_list_pbc builds the same index over one period in y and z; pairwise_pbc_kernel then takes the
-// minimum image.  Both kernels are one sum (pairwise_sum) over the walk of kmcf_cellwalk.hpp, which the gap
-// and chain searches share.
+// minimum image.  Both kernels are one sum (pairwise_sum) over the walk of kmcf_cellwalk.hpp, which the
+// analysis passes share.
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
-#include "kmcf_cellwalk.hpp"      // the walk; kmcf_internal.hpp: struct kmcf_pairwise
+#include "kmcf_cellwalk.hpp"      // the walk and, through kmcf_cellmembers.hpp, its list; kmcf_internal.hpp: struct kmcf_pairwise
 
 namespace {
 
-// phase 1: per-tile counts of charged sites (cell order); phase 2 is kmcf_scan_counts_kernel, in place
-__global__ __launch_bounds__(KMCF_BLOCK) void flag_count_kernel(int N, const int *__restrict__ cell_order,
-                                                                const int *__restrict__ charge, int *__restrict__ block_sum)
-{
-    __shared__ int lds[4];
-    int f[KMCF_SCAN_ITEMS];
-    kmcf_tile_flags(N, f, [&](int t) { return charge[cell_order[t]] != 0; });
-    const int total = kmcf_tile_count(f, lds);
-    if (threadIdx.x == 0) block_sum[blockIdx.x] = total;
-}
-
-// phase 3: positions + compaction
-__global__ __launch_bounds__(KMCF_BLOCK) void flag_scatter_kernel(int N, const int *__restrict__ cell_order,
-                                                                  const int *__restrict__ charge,
-                                                                  const int *__restrict__ block_sum,
-                                                                  int *__restrict__ flag_pos, int *__restrict__ clist)
-{
-    __shared__ int lds[4];
-    const int t0 = kmcf_tile_item0();
-    int f[KMCF_SCAN_ITEMS], site[KMCF_SCAN_ITEMS];
-    kmcf_tile_flags(N, f, [&](int t) { return charge[site[t - t0] = cell_order[t]] != 0; });
-    int pos = kmcf_tile_pos(f, block_sum[blockIdx.x], lds);
-#pragma unroll
-    for (int i = 0; i < KMCF_SCAN_ITEMS; ++i) {
-        const int t = t0 + i;
-        if (t < N) {
-            flag_pos[t] = pos;
-            if (f[i]) clist[pos] = site[i];
-            pos += f[i];
-        }
-    }
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == KMCF_BLOCK - 1) flag_pos[N] = block_sum[gridDim.x];
-}
+// the members of the per-step compaction (kmcf_cellmembers.hpp): the charged sites, by site id
+struct pw_rule {
+    const int *charge;
+    __device__ __forceinline__ int operator()(int i) const { return charge[i] != 0; }
+};
+struct pw_emit {
+    int *clist;
+    __device__ __forceinline__ void operator()(int, int q, int i, int) const { clist[q] = i; }
+};
 
 // the reference's distance from site i to site j, operation for operation: open, and on a periodic index the minimum
 // image in y and z.  A pair has ONE distance: where a period is shorter than two cutoffs no second image is added.
@@ -133,6 +109,9 @@ __global__ __launch_bounds__(KMCF_BLOCK) void pairwise_pbc_kernel(
     pairwise_sum(g, cell_start, flag_pos, clist, x, y, z, charge, sigma, k, cutoff, count, displ, potential);
 }
 
+inline auto pairwise_kernel_of(const kmcf_cell_grid &) { return pairwise_kernel; }
+inline auto pairwise_kernel_of(const kmcf_cell_grid_pbc &) { return pairwise_pbc_kernel; }
+
 // the sites in cell order and the buffers of the per-step compaction, from the host copy of the coordinates; coord(s)
 // is the cell id of site s
 template <class F>
@@ -147,12 +126,9 @@ int index_cells(kmcf_pairwise *p, F cell_of_site)
     for (int cc = 0; cc < p->ncell; ++cc) start[cc + 1] += start[cc];
     std::vector<int> fill(start.begin(), start.end() - 1);
     for (int s = 0; s < N; ++s) order[fill[cid[s]]++] = s;
-    p->n_blocks = (N + KMCF_SCAN_TILE - 1) / KMCF_SCAN_TILE;
     KMCF_TRY(kmcf_dev_alloc(&p->d_cell_order, (size_t)N, false));
     KMCF_TRY(kmcf_dev_alloc(&p->d_cell_start, (size_t)p->ncell + 1, false));
-    KMCF_TRY(kmcf_dev_alloc(&p->d_flag_pos, (size_t)N + 1, false));
-    KMCF_TRY(kmcf_dev_alloc(&p->d_block_sum, (size_t)p->n_blocks + 1, false));
-    KMCF_TRY(kmcf_dev_alloc(&p->d_clist, (size_t)N, false));
+    KMCF_TRY(kmcf_members_alloc(&p->charged, N, 1, false));
     KMCF_HIP(hipMemcpy(p->d_cell_order, order.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice));
     KMCF_HIP(hipMemcpy(p->d_cell_start, start.data(), start.size() * sizeof(int), hipMemcpyHostToDevice));
     return KMCF_OK;
@@ -160,7 +136,8 @@ int index_cells(kmcf_pairwise *p, F cell_of_site)
 
 void pairwise_release(kmcf_pairwise *p)
 {
-    kmcf_dev_free_all({p->d_cell_order, p->d_cell_start, p->d_flag_pos, p->d_block_sum, p->d_clist});
+    kmcf_dev_free_all({p->d_cell_order, p->d_cell_start});
+    kmcf_members_free(&p->charged);
     delete p;
 }
 
@@ -272,7 +249,8 @@ extern "C" int kmcf_pairwise_destroy(kmcf_pairwise *p)
     kmcf_chain_ws_free(p);
     kmcf_pc_ws_free(p);
     kmcf_fs_ws_free(p);
-    kmcf_dev_free_all({p->d_cell_order, p->d_cell_start, p->d_flag_pos, p->d_block_sum, p->d_clist});
+    kmcf_dev_free_all({p->d_cell_order, p->d_cell_start});
+    kmcf_members_free(&p->charged);
     delete p;
     return KMCF_OK;
 }
@@ -287,22 +265,16 @@ extern "C" int kmcf_poisson_gridless(kmcf_pairwise *p, const double *d_x, const 
     kmcf_comm *c = p->comm;
     KMCF_TRY(kmcf_enter(c));
     hipStream_t st = c->stream;
-    flag_count_kernel<<<p->n_blocks, KMCF_BLOCK, 0, st>>>(p->N, p->d_cell_order, d_site_charge, p->d_block_sum);
-    kmcf_scan_counts_kernel<int><<<1, KMCF_BLOCK, 0, st>>>(p->n_blocks, p->d_block_sum, p->d_block_sum, 0);
-    flag_scatter_kernel<<<p->n_blocks, KMCF_BLOCK, 0, st>>>(p->N, p->d_cell_order, d_site_charge, p->d_block_sum,
-                                                          p->d_flag_pos, p->d_clist);
+    kmcf_members_enqueue<1>(p, p->charged, pw_rule{d_site_charge}, pw_emit{p->charged.d_site});
     KMCF_HIP(hipGetLastError());
     if (count > 0) {
         int64_t grid = ((int64_t)count * 16 + KMCF_BLOCK - 1) / KMCF_BLOCK;
         if (grid > 8192) grid = 8192;
-        if (p->pbc)
-            pairwise_pbc_kernel<<<(int)grid, KMCF_BLOCK, 0, st>>>(p->grid_pbc(), p->d_cell_start, p->d_flag_pos, p->d_clist, d_x, d_y,
-                                                                 d_z, d_site_charge, sigma, k, p->cutoff, count, displ,
-                                                                 d_site_potential_charge);
-        else
-            pairwise_kernel<<<(int)grid, KMCF_BLOCK, 0, st>>>(p->grid(), p->d_cell_start, p->d_flag_pos, p->d_clist, d_x, d_y, d_z,
-                                                             d_site_charge, sigma, k, p->cutoff, count, displ,
-                                                             d_site_potential_charge);
+        p->with_grid([&](auto g) {
+            pairwise_kernel_of(g)<<<(int)grid, KMCF_BLOCK, 0, st>>>(g, p->d_cell_start, p->charged.d_pos, p->charged.d_site, d_x, d_y,
+                                                                   d_z, d_site_charge, sigma, k, p->cutoff, count, displ,
+                                                                   d_site_potential_charge);
+        });
         KMCF_HIP(hipGetLastError());
     }
     KMCF_HIP(hipStreamSynchronize(st));

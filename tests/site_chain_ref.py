@@ -465,10 +465,34 @@ def _large():
                 r_max=SK.CUTOFF, cutoff=SK.CUTOFF, max_hops=4, hops=hops)
 
 
+def _tile_edge(N):
+    """SK.tile_edge_sites(N) (N = 2047, 2048, 2049: a scan tile one item short, exactly full, one item over), one gap cell, a
+    random quarter of the sites each L, R, stone (50 nodes), none, and r_max = 0.5 A: no two lattice sites are that close
+    (4 - 0.6 A).  The stone s is the site at the LAST position of the index's cell order; the two sites before it become an
+    L site l at 0.4 A from s in x and an R site r at 0.4 A from s in y, both towards the lower corner, 0.57 A apart: the only
+    links are l - s and s - r, the only chain is l - s - r, and it is lost if the last item of the scan is."""
+    xyz, order = SK.tile_edge_sites(N)
+    xyz = xyz.copy()
+    l, r, s = (int(v) for v in order[-3:])
+    xyz[l] = xyz[s] - np.array([0.4, 0.0, 0.0])
+    xyz[r] = xyz[s] - np.array([0.0, 0.4, 0.0])
+    assert GR.index_positions(dict(xyz=xyz, cutoff=SK.CUTOFF))[s] == N - 1     # (of the final coordinates)
+    rng = np.random.default_rng(280 + N)
+    kind = rng.choice(4, N)                                                    # none, L, R, stone
+    side = np.where(kind == 3, 0, kind).astype(np.int32)
+    node = np.where(kind == 3, rng.integers(0, 50, N), -1).astype(np.int32)
+    side[[l, s, r]] = [1, 0, 2]
+    node[[l, s, r]] = [-1, 200, -1]
+    hops = [(l, s, float(d2_exact(xyz, l, s))), (s, r, float(d2_exact(xyz, s, r)))]
+    return dict(name="tile_edge@%d" % N, xyz=xyz, side=side, node=node, cell=None, n_cells=1, r_max=0.5, cutoff=SK.CUTOFF,
+                max_hops=4, hops=hops)
+
+
 BUILDERS = {"ladder": _ladder, "detour": _detour, "rim": lambda: _rim(5.0),
             "rim_below": lambda: _rim(float(np.nextafter(5.0, 0.0))), "ties": _ties, "straddle": _straddle,
             "home": lambda: _home(False), "home_flipped": lambda: _home(True), "multi_site": _multi_site, "zigzag": _zigzag,
-            "statuses": _statuses, "mixed": _mixed, "large": _large}
+            "statuses": _statuses, "mixed": _mixed, "large": _large,
+            **{"tile_edge@%d" % n: (lambda n=n: _tile_edge(n)) for n in SK.TILE_EDGE_SIZES}}
 _cache = {}
 
 

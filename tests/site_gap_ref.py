@@ -292,6 +292,22 @@ def _large_two():
                 cutoff=SK.CUTOFF, pairs=[(a0, b0, float(d2_exact(xyz, a0, b0))), (a1, b1, float(d2_exact(xyz, a1, b1)))])
 
 
+def _tile_edge(N):
+    """SK.tile_edge_sites(N) (N = 2047, 2048, 2049: a scan tile one item short, exactly full, one item over), one gap cell, a
+    random third of the sites each A, B, none.  The B site b is the one at the LAST position of the index's cell order; the A
+    site a at the position before it is moved to 0.35 A from b, towards the lower corner, closer than two lattice sites can be
+    (4 - 0.6 A): pair = (a, b, d2) is the answer by construction, and it is lost if the last item of the scan is."""
+    xyz, order = SK.tile_edge_sites(N)
+    xyz = xyz.copy()
+    a, b = int(order[-2]), int(order[-1])
+    xyz[a] = xyz[b] - 0.2
+    c = dict(name="tile_edge@%d" % N, xyz=xyz, cell=None, n_cells=1, r_max=SK.CUTOFF, cutoff=SK.CUTOFF)
+    assert index_positions(c)[b] == N - 1                                      # (of the final coordinates)
+    side = np.random.default_rng(270 + N).integers(0, 3, N).astype(np.int32)
+    side[a], side[b] = 1, 2
+    return dict(c, side=side, pair=(a, b, float(d2_exact(xyz, a, b))))
+
+
 def device_search(c, carry=True, later_write_stays=True):
     """The compaction and search of csrc/kmcf_gap.hip restated step by step on the index's cell order -- per-tile counts of
     the A and B flags, their exclusive scan in passes of 256 tiles, the scatter into the member lists, the walk of the
@@ -355,7 +371,7 @@ def device_search(c, carry=True, later_write_stays=True):
 
 BUILDERS = {"planes": _planes, "straddle": _straddle, "rim": lambda: _rim(5.0),
             "rim_below": lambda: _rim(float(np.nextafter(5.0, 0.0))), "mixed": _mixed, "dense": _dense, "large": _large,
-            "large_two": _large_two}
+            "large_two": _large_two, **{"tile_edge@%d" % n: (lambda n=n: _tile_edge(n)) for n in SK.TILE_EDGE_SIZES}}
 _cache = {}
 
 

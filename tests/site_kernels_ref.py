@@ -97,8 +97,26 @@ def _lattice(nx, ny, nz, a=4.0):
     return g.astype(np.float64) * a, g
 
 
+TILE_EDGE_SIZES = (SCAN_TILE - 1, SCAN_TILE, SCAN_TILE + 1)       # a scan tile one item short, exactly full, one item over
+TILE_EDGE = tuple("tile_edge@%d" % n for n in TILE_EDGE_SIZES)
+
+
+@functools.lru_cache(maxsize=None)
+def tile_edge_sites(N):
+    """(xyz, order) of the cases at the edge of a scan tile, shared by the pairwise, gap and chain tests: N sites drawn from
+    a 13 x 13 x 13 lattice of 4 A, jittered by 0.3 A, ids shuffled -- 3 x 3 x 3 cells of CUTOFF, a dozen sites or more in the
+    last one.  order = cell_order(xyz)[0]: order[-1] is the site at the LAST position of the cell order, the item whose
+    list position comes out of every count before it and whose run ends at the list's total.  Read-only."""
+    rng = np.random.default_rng(4000 + N)
+    g, _ = _lattice(13, 13, 13)
+    xyz = g[rng.choice(len(g), N, replace=False)] + rng.uniform(-0.3, 0.3, (N, 3))
+    order, nc = cell_order(xyz)
+    assert nc == (3, 3, 3)
+    return _ro(xyz, order)
+
+
 PAIRWISE_CASES = ("thin", "thin_uncharged", "one_cell", "one_site", "seventeen", "cube", "lattice_cutoffs", "large",
-                  "large_tail")
+                  "large_tail") + TILE_EDGE
 ON_LATTICE = ("thin", "thin_uncharged", "lattice_cutoffs")
 LARGE = ("large", "large_tail")
 
@@ -154,6 +172,11 @@ def pairwise_case(name):
             tail = cell_order(xyz)[0][-3000:]
             charge[tail] = np.where(np.arange(3000) % 3 == 0, -2, 2)
         slices = [(0, N)]
+    elif name in TILE_EDGE:                          # one charged site: the one at the last position of the cell order
+        xyz, order = tile_edge_sites(int(name.split("@")[1]))
+        charge = np.zeros(len(xyz), np.int32)
+        charge[order[-1]] = 2
+        slices = [(0, len(xyz))]
     else:
         raise KeyError(name)
     _ro(xyz, charge)

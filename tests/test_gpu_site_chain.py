@@ -102,7 +102,7 @@ class _Index:
 
 
 CASES = ["ladder", "detour", "rim", "rim_below", "ties", "straddle", "home", "home_flipped", "multi_site", "zigzag", "statuses",
-         "mixed", "large"]
+         "mixed", "large", "tile_edge@2047", "tile_edge@2048", "tile_edge@2049"]
 
 
 @pytest.mark.parametrize("name", CASES)

@@ -70,7 +70,8 @@ class _Index:
         self.km.lib.load().kmcf_pairwise_destroy(self.handle)
 
 
-@pytest.mark.parametrize("name", ["planes", "straddle", "rim", "rim_below", "mixed", "dense", "large", "large_two"])
+@pytest.mark.parametrize("name", ["planes", "straddle", "rim", "rim_below", "mixed", "dense", "large", "large_two",
+                                  "tile_edge@2047", "tile_edge@2048", "tile_edge@2049"])
 def test_site_sets_match_the_restatement(km, comm, name):
     ix = _Index(km, comm, GR.case(name))
     try:

@@ -5,7 +5,8 @@ tests/site_kernels_ref.py (tests/test_site_kernels_ref.py pins the references an
     site's own sum of absolute terms (the project's 1e-12 of test_gpu_parity.py, no longer against the device-wide
     maximum), exactly 0.0 where no charged site lies within the cutoff, the sentinel outside the requested slice.
     Devices thinner than a cutoff, a single cell, full / empty / barely begun scan tiles, pairs AT the cutoff, sites on
-    cell faces, slices, and 263 scan tiles (the carry across passes of 256 tiles, once with every earlier tile empty).
+    cell faces, slices, 263 scan tiles (the carry across passes of 256 tiles, once with every earlier tile empty), and
+    the only charged site as the last item of the scan with 2047, 2048 and 2049 sites (tile_edge@N).
   * charge rule (kmcf_update_charge): hand-written neighbour rows, equal to charge_ref on the whole vector.
   * K / CB-edge value assembly: two synthetic devices x pbc 0 / 1 x both rules x both kernels (tiles, row-wise):
     off-diagonals bit-equal to k_values_ref, vectors and diagonal entries rtol 1e-14 (test_k_assembly_matches_oracle's
@@ -54,7 +55,8 @@ def _f64(torch, a):
 # ------------------------------------------------------------------------------------------------ pairwise term
 PAIRWISE_RUNS = {"thin": ("thin", "thin_uncharged"), "one_cell": ("one_cell",), "one_site": ("one_site",),
                  "seventeen": ("seventeen",), "cube": ("cube",), "lattice_cutoffs": ("lattice_cutoffs",),
-                 "large": ("large", "large_tail")}           # (one cutoff list per run: the sites are the same)
+                 "large": ("large", "large_tail"),           # (one cutoff list per run: the sites are the same)
+                 **{name: (name,) for name in R.TILE_EDGE}}  # the only charged site: the last item of the compaction's scan
 
 
 @pytest.mark.parametrize("run", sorted(PAIRWISE_RUNS))

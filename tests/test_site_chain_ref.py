@@ -12,7 +12,8 @@ def _paths(name):
     return c, r, known
 
 
-@pytest.mark.parametrize("name", ["ladder", "detour", "rim", "rim_below", "straddle", "home", "home_flipped", "large"])
+@pytest.mark.parametrize("name", ["ladder", "detour", "rim", "rim_below", "straddle", "home", "home_flipped", "large",
+                                  "tile_edge@2047", "tile_edge@2048", "tile_edge@2049"])
 def test_known_chains(name):
     c, r, known = _paths(name)
     assert len(known) == c["n_cells"]
@@ -130,6 +131,27 @@ def test_large_members_sit_at_both_ends_of_the_scan():
     between = (pos >= T) & (pos < 256 * T)
     assert between.sum() <= 3                                                   # (planted sites that moved into a later index cell)
     assert R.reference("large")["stats"]["surface_sites"] > 1000
+
+
+@pytest.mark.parametrize("N", R.SK.TILE_EDGE_SIZES)
+def test_tile_edge_chain_needs_the_last_item_of_the_scan(N):
+    c, ref = R.case("tile_edge@%d" % N), R.reference("tile_edge@%d" % N)
+    (l, s, d_ls), (s2, r, d_sr) = c["hops"]
+    assert len(c["xyz"]) == N and N in (R.SK.SCAN_TILE - 1, R.SK.SCAN_TILE, R.SK.SCAN_TILE + 1) and s == s2
+    assert R.GR.index_positions(c)[s] == N - 1 and c["node"][s] == 200 and (c["node"] == 200).sum() == 1
+    assert (c["side"][l], c["side"][s], c["side"][r]) == (1, 0, 2)
+    assert d_ls <= 0.25 and d_sr <= 0.25 and R.d2_exact(c["xyz"], l, r) > 0.25
+    # no two other sites come near: the lattice leaves 4 - 0.6 A between any two
+    others = np.setdiff1d(np.arange(N), [l, r])
+    assert R.cKDTree(c["xyz"][others]).query(c["xyz"][others], k=2)[0][:, 1].min() >= 3.4
+    for kind in (c["side"] == 1, c["side"] == 2, c["node"] >= 0):
+        assert kind.sum() >= 400
+    rec = ref["chains"][0]
+    assert rec["status"] == R.CHAINED and rec["n_hops"] == 2 and np.isinf(rec["direct2"])
+    assert ref["stats"]["surface_sites"] == 3
+    # ... and without the stone at the last position there is no chain
+    lost = R.site_set_chain(c["xyz"], c["side"], np.where(np.arange(N) == s, -1, c["node"]), c["r_max"], max_hops=4)
+    assert lost["chains"][0]["status"] == R.OPEN
 
 
 def test_boruvka_with_the_early_stop_returns_kruskals_hops():

@@ -253,6 +253,30 @@ def test_large_two_has_a_record_that_depends_on_the_carry_of_the_scan():
         assert (broken[0] != want[0]) if later else (broken[1] != want[1])   # the cell whose members were overwritten
 
 
+@pytest.mark.parametrize("N", GR.SK.TILE_EDGE_SIZES)
+def test_tile_edge_answer_hangs_on_the_last_item_of_the_scan(N):
+    c = GR.case("tile_edge@%d" % N)
+    T = GR.SK.SCAN_TILE
+    pos = GR.index_positions(c)
+    a, b, d2 = c["pair"]
+    assert len(c["xyz"]) == N and N in (T - 1, T, T + 1) and c["cutoff"] == c["r_max"] == 20.0
+    assert pos[b] == N - 1 and c["side"][b] == 2 and c["side"][a] == 1
+    assert 0.1199 < d2 < 0.1201 and d2 == GR.d2_exact(c["xyz"], a, b)
+    # no two other sites come near that: the lattice leaves 4 - 0.6 A between any two, and a lies 0.35 A from one
+    others = np.setdiff1d(np.arange(N), [a])
+    assert GR.cKDTree(c["xyz"][others]).query(c["xyz"][others], k=2)[0][:, 1].min() >= 3.4
+    for bit in (1, 2):
+        assert ((c["side"] & bit) != 0).sum() >= 500
+    gaps, stats = GR.reference(c["name"])
+    g = gaps[0]
+    assert (g["site_left"], g["site_right"], g["gap2"]) == (a, b, d2) and stats["cells_open"] == 1 and stats["n_both"] == 0
+    assert GR.device_search(c) == [(a, b, d2)]
+    # ... and without the last item the answer is another pair, farther apart
+    lost = dict(c, side=np.where(np.arange(N) == b, 0, c["side"]))
+    (a2, b2, d22), = GR.device_search(lost)
+    assert b2 != b and d22 > 9.0
+
+
 # ---- struct layout and argument errors ---------------------------------------------------------------------------------------
 
 def test_python_struct_layout(km):

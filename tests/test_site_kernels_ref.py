@@ -188,8 +188,14 @@ def test_pairwise_input_meets_its_conditions(name):
             assert int((charge != 0).sum()) == 3000 and pos[charge != 0].min() == N - 3000
             assert per_tile[:-2].sum() == 0 and per_tile[256:].sum() == 3000
             assert np.array_equal(xyz, R.pairwise_case("large")["xyz"])
+    if name in R.TILE_EDGE:
+        # the one charged site is the last item of the scan: of a tile one short, of a full tile, alone in a second tile;
+        # every term of the result is its term
+        assert N in R.TILE_EDGE_SIZES and nc == (3, 3, 3) and np.flatnonzero(flags).tolist() == [N - 1]
+        assert per_tile.tolist() == ([1] if N <= R.SCAN_TILE else [0, 1])
+        assert n.max() == 1 and (n > 0).sum() >= 100 and n[order[-1]] == 0
     # the zero pattern of the result is part of the bar: sites without a term exist wherever the case can have them
-    if name in ("large", "large_tail", "one_site", "seventeen", "thin_uncharged"):
+    if name in ("large", "large_tail", "one_site", "seventeen", "thin_uncharged") + R.TILE_EDGE:
         assert (n == 0).any()
 
 
