@@ -21,6 +21,13 @@
 //   sub-block, unpack_add (dist_iterative/dist_spmv_split_sparse.cpp:5-78)
 //                                                             -> pack, all-gather, neighbour SpMV, one bitmap kernel
 //       (wave per row, coalesced value stream, x_sub from L2) adding into Ap and into the p.Ap partials.
+//
+// Shared device pieces (every kernel outside the solve's own -- sub_spmv, sub_symm, sub_symj and their helpers -- is built
+// from them):
+//   t_points, t_wkb, pair_value   the tunnel points and WKB parameters by value; THE value of one tunnel pair
+//   neighbour_walk<LPR>           LPR lanes per internal row of T over the row's off-diagonal entries, butterfly, lane-0 finish
+//   bitmap_rows, bitmap_row       a wave per local row of the pair bitmap; (column, packed offset) of every set position
+//   profile_add_pair              one counted pair into the sums of the current profile, neighbour and tunnel part alike
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -119,8 +126,7 @@ __device__ __forceinline__ double dist3(double x1, double y1, double z1, double 
 // The distance of a pair of tunnel points, chosen at compile time: a kernel that measures a pair is instantiated once per
 // geometry and takes the functor by value.  dist_open is empty and calls dist3: the open instantiation is the code it was.
 // dist_min_image carries the periods of kmcf_initialize_sparsity_T_pbc and calls the library's one minimum image
-// (kmcf_internal.hpp); that expression is odd in every difference up to the squares, so d(i, j) and d(j, i) are the same
-// bits -- which the mirrored tiles and the bitmap, where each row measures the pair itself, rely on to agree.
+// (kmcf_internal.hpp).  (Why d(i, j) and d(j, i) must be the same bits: at pair_value, the one place that measures a pair.)
 struct dist_open {
     __device__ __forceinline__ double operator()(double x1, double y1, double z1, double x2, double y2, double z2) const
     {
@@ -182,6 +188,38 @@ __global__ __launch_bounds__(KMCF_BLOCK) void t_cls_col_kernel(int n_cols, const
     }
 }
 
+// ---------------------------------------------------------------- the walk of the neighbour rows of T
+// LPR lanes per internal row r, a block taking whole groups of KMCF_BLOCK / LPR rows (grid: kmcf_grid1d(n_loc * LPR)).  Per
+// row: start(r) loads what the row needs and says whether its entries are walked at all; entry(j, acc) for the positions j
+// of row_ptr[r] .. row_ptr[r + 1] but the diagonal's, lane l taking l, l + LPR, ... in ascending order and adding into its
+// NACC accumulators; an xor butterfly over the row's lanes; finish(r, dpos, acc) on the row's lane 0.  The kernels keep
+// what start found for entry and finish in locals of their own.
+template <int LPR, typename ACC, int NACC, typename START, typename ENTRY, typename FINISH>
+__device__ __forceinline__ void neighbour_walk(int n_loc, const int *__restrict__ row_ptr, const int *__restrict__ diag_pos, START start,
+                                               ENTRY entry, FINISH finish)
+{
+    constexpr int RPB = KMCF_BLOCK / LPR;
+    const int lane = threadIdx.x % LPR;
+    const int groups = (n_loc + RPB - 1) / RPB;
+    for (int grp = blockIdx.x; grp < groups; grp += gridDim.x) {
+        const int r = grp * RPB + threadIdx.x / LPR;
+        const bool valid = r < n_loc;
+        ACC acc[NACC] = {};
+        int dpos = -1;
+        if (valid && start(r)) {
+            dpos = diag_pos[r];
+            for (int j = row_ptr[r] + lane; j < row_ptr[r + 1]; j += LPR)
+                if (j != dpos) entry(j, acc);
+        }
+#pragma unroll
+        for (int off = LPR / 2; off >= 1; off >>= 1) {
+#pragma unroll
+            for (int k = 0; k < NACC; ++k) acc[k] += __shfl_xor(acc[k], off, 64);
+        }
+        if (valid && lane == 0) finish(r, dpos, acc);
+    }
+}
+
 // ---------------------------------------------------------------- neighbour values
 // populate_T_dist (src/current_solver_gpu.cu:1051-1247) + calc_diagonal_T + insert_diag_T (:1279-1321), one
 // pass, LPR lanes per row.  Entry rule by the classes of row and column node:
@@ -200,48 +238,37 @@ __global__ __launch_bounds__(KMCF_BLOCK) void t_assemble_kernel(
     double *__restrict__ diagv, int n_coded)
 {
     constexpr int SLOT_MASK = (1 << KMCF_SLOT_BITS) - 1;
-    constexpr int RPB = KMCF_BLOCK / LPR;
-    const int lane = threadIdx.x % LPR;
-    const int groups = (n_loc + RPB - 1) / RPB;
-    for (int grp = blockIdx.x; grp < groups; grp += gridDim.x) {
-        const int r = grp * RPB + threadIdx.x / LPR;
-        const bool valid = r < n_loc;
-        int n_high = 0, n_low = 0, n_loop = 0, dpos = -1;
-        unsigned char ci = 0;
-        if (valid) {
-            ci = cls_col[r];
-            dpos = diag_pos[r];
-            const bool coded = idx16 && r < n_coded;
-            for (int j = row_ptr[r] + lane; j < row_ptr[r + 1]; j += LPR) {
-                if (j == dpos) continue;
-                const unsigned char cj = cls_col[col[j]];
-                int code;
-                if (ci & 0x80) code = (cj & 0x80) ? CODE_LOOP : CODE_HIGH;
-                else if (cj & 0x80) code = CODE_HIGH;
-                else code = (ci & cj & 3) ? CODE_HIGH : CODE_LOW;
-                val[j] = code == CODE_HIGH ? -high_G : (code == CODE_LOW ? -low_G : -loop_G);
-                if (coded) idx16[j] = (unsigned short)((idx16[j] & SLOT_MASK) | (code << KMCF_SLOT_BITS));
-                n_high += code == CODE_HIGH; n_low += code == CODE_LOW; n_loop += code == CODE_LOOP;
-            }
-        }
-#pragma unroll
-        for (int off = LPR / 2; off >= 1; off >>= 1) {
-            n_high += __shfl_xor(n_high, off, 64); n_low += __shfl_xor(n_low, off, 64); n_loop += __shfl_xor(n_loop, off, 64);
-        }
-        if (valid && lane == 0) {
+    unsigned char ci = 0;
+    bool coded = false;
+    neighbour_walk<LPR, int, 3>(
+        n_loc, row_ptr, diag_pos,
+        [&](int r) { ci = cls_col[r]; coded = idx16 && r < n_coded; return true; },
+        [&](int j, int *n /* entries of value code CODE_HIGH, CODE_LOW, CODE_LOOP */) {
+            // (read here, not where they are chosen: a choice among three captured references becomes ONE load at an index
+            // into the closure, which then cannot leave memory -- 32 bytes of scratch a lane)
+            const double g_high = -high_G, g_low = -low_G, g_loop = -loop_G;
+            const unsigned char cj = cls_col[col[j]];
+            int code;
+            if (ci & 0x80) code = (cj & 0x80) ? CODE_LOOP : CODE_HIGH;
+            else if (cj & 0x80) code = CODE_HIGH;
+            else code = (ci & cj & 3) ? CODE_HIGH : CODE_LOW;
+            val[j] = code == CODE_HIGH ? g_high : (code == CODE_LOW ? g_low : g_loop);
+            if (coded) idx16[j] = (unsigned short)((idx16[j] & SLOT_MASK) | (code << KMCF_SLOT_BITS));
+            n[CODE_HIGH] += code == CODE_HIGH; n[CODE_LOW] += code == CODE_LOW; n[CODE_LOOP] += code == CODE_LOOP;
+        },
+        [&](int r, int dpos, const int *n) {
             double d0 = 0.0;
             if (ci == 0x80) d0 = high_G;
             else if (!(ci & 0x80) && ground[r]) d0 = high_G;
-            const double off = (double)n_high * high_G + (double)n_low * low_G + (double)n_loop * loop_G;
+            const double off = (double)n[CODE_HIGH] * high_G + (double)n[CODE_LOW] * low_G + (double)n[CODE_LOOP] * loop_G;
             const double d = d0 + off;
             if (dpos >= 0) {
                 val[dpos] = d;
-                if (idx16 && r < n_coded) idx16[dpos] = (unsigned short)((idx16[dpos] & SLOT_MASK) | (KMCF_CODE_DIAG << KMCF_SLOT_BITS));
+                if (coded) idx16[dpos] = (unsigned short)((idx16[dpos] & SLOT_MASK) | (KMCF_CODE_DIAG << KMCF_SLOT_BITS));
             }
             if (diagv && r < n_coded) diagv[r] = dpos >= 0 ? d : 0.0;
             diag_out[r] = d;
-        }
-    }
+        });
 }
 
 // ---------------------------------------------------------------- tunnel points
@@ -303,20 +330,26 @@ __device__ __forceinline__ bool tunnel_pair(int info_i, int info_j, double cb_i,
     return (t2t || ct || cc) && (fabs(cb_i - cb_j) > tol);
 }
 
+// The tunnel points and the WKB parameters of a state as the kernels take them: by value (points_of / wkb_of fill them;
+// a kernel reads the members it needs).  t_point: one point's five values in registers.
+struct t_points { const int *info; const double *x, *y, *z, *cb; };
+struct t_wkb { double nn_dist, tol, m_e, V0; };
+struct t_point { int info; double x, y, z, cb; };
+
+__device__ __forceinline__ t_point load_point(const t_points &P, int i) { return {P.info[i], P.x[i], P.y[i], P.z[i], P.cb[i]}; }
+
 // One wave per local sub row: masks of its row (one ballot per 64 columns) and its entry count
 // (calc_nnz_per_row_tunnel + assemble_tunnel_col_indices, :212-372).
 template <typename DIST>
-__global__ __launch_bounds__(KMCF_BLOCK) void tunnel_mask_kernel(
-    int n_loc, int s0, int n_glob, int n_groups, const int *__restrict__ tinfo, const double *__restrict__ tx,
-    const double *__restrict__ ty, const double *__restrict__ tz, const double *__restrict__ tcb, double nn_dist, double tol,
-    unsigned long long *__restrict__ mask, int *__restrict__ rowcnt, DIST dist)
+__global__ __launch_bounds__(KMCF_BLOCK) void tunnel_mask_kernel(int n_loc, int s0, int n_glob, int n_groups, t_points P, t_wkb w,
+                                                                 unsigned long long *__restrict__ mask, int *__restrict__ rowcnt, DIST dist)
 {
     const int lane = threadIdx.x & 63;
     const int wpb = KMCF_BLOCK / 64;
     for (int s = blockIdx.x * wpb + (threadIdx.x >> 6); s < n_loc; s += gridDim.x * wpb) {
         const int sg = s0 + s;
-        const double xi = tx[sg], yi = ty[sg], zi = tz[sg], cbi = tcb[sg];
-        const int fi = tinfo[sg];
+        const double xi = P.x[sg], yi = P.y[sg], zi = P.z[sg], cbi = P.cb[sg];
+        const int fi = P.info[sg];
         int cnt = 0;
         for (int g = 0; g < n_groups; ++g) {
             const int j = g * 64 + lane;
@@ -325,8 +358,8 @@ __global__ __launch_bounds__(KMCF_BLOCK) void tunnel_mask_kernel(
                 if (j == sg) take = true;                                           // :255-258 diagonal
                 else {
                     bool c2t;
-                    const double d = dist(xi, yi, zi, tx[j], ty[j], tz[j]);
-                    take = d > nn_dist && tunnel_pair(fi, tinfo[j], cbi, tcb[j], tol, &c2t);   // :261-284
+                    const double d = dist(xi, yi, zi, P.x[j], P.y[j], P.z[j]);
+                    take = d > w.nn_dist && tunnel_pair(fi, P.info[j], cbi, P.cb[j], w.tol, &c2t);   // :261-284
                 }
             }
             const unsigned long long mk = __ballot(take);
@@ -363,78 +396,89 @@ __device__ __forceinline__ double wkb_value(double dist_angstrom, double cb_i, d
     return 0.0;      // E2 == 0: written by neither branch there (uninitialised memory, :881)
 }
 
-// One wave per local sub row: values of the set positions + the row's diagonal = -(sum of the others)
-// (populate_T_tunnel_dist2 + calc_diagonal_T_tunnel, :497-614, :669-689).
-template <typename DIST>
-__global__ __launch_bounds__(KMCF_BLOCK) void tunnel_value_kernel(
-    int n_loc, int s0, int n_groups, const int *__restrict__ tinfo, const double *__restrict__ tx, const double *__restrict__ ty,
-    const double *__restrict__ tz, const double *__restrict__ tcb, double nn_dist, double tol, double m_e, double V0,
-    const unsigned long long *__restrict__ mask, const long long *__restrict__ voff, double *__restrict__ val,
-    double *__restrict__ tdiag, DIST dist)
+// THE value of the tunnel pair (a, b), a the row's point: every kernel that needs one calls this, so the storage forms,
+// the current map and the current profile hold the same bits because they run the same expression.  The mirrored tiles,
+// and the bitmap where each row measures the pair itself, also need v(a, b) == v(b, a): DIST's expression (dist3, the
+// library's minimum image) is odd in every difference up to the squares, so d(a, b) and d(b, a) are the same bits.
+// IN_PATTERN: for a fill that finds the pattern itself -- 0.0 unless the pair is an entry (the rule of tunnel_mask_kernel).
+template <bool IN_PATTERN, typename DIST>
+__device__ __forceinline__ double pair_value(const t_point &a, const t_point &b, const t_wkb &w, const DIST &dist)
+{
+    bool c2t;
+    const bool rule = tunnel_pair(a.info, b.info, a.cb, b.cb, w.tol, &c2t);
+    const double d = dist(a.x, a.y, a.z, b.x, b.y, b.z);
+    if (IN_PATTERN && !(d > w.nn_dist && rule)) return 0.0;
+    return wkb_value(d, a.cb, b.cb, c2t, w.m_e, w.V0);
+}
+
+// ---------------------------------------------------------------- the walk of the rows of the pair bitmap
+// One wave per local row s (grid: wave_row_grid(n_loc)): row(s).  Inside it bitmap_row(the row's mask words, n_groups,
+// off, body) calls body(j, pos) on the lane of every set column j = 64 g + lane, mask words in ascending order, all-zero
+// words skipped wave-uniformly; pos = off + the set positions before j: with off = voff[s] the entry's place in the packed
+// value stream (a body that ignores pos passes 0, and the offset arithmetic folds away).  A kernel is then: load the row's
+// data, walk with a lambda, kmcf_wave_sum64 per accumulator, write on lane 0.  (sub_spmv_kernel keeps its own unrolled walk.)
+template <typename ROW>
+__device__ __forceinline__ void bitmap_rows(int n_loc, ROW row)
+{
+    constexpr int wpb = KMCF_BLOCK / 64;
+    for (int s = blockIdx.x * wpb + (threadIdx.x >> 6); s < n_loc; s += gridDim.x * wpb) row(s);
+}
+
+template <typename BODY>
+__device__ __forceinline__ void bitmap_row(const unsigned long long *__restrict__ mrow, int n_groups, long long off, BODY body)
 {
     const int lane = threadIdx.x & 63;
-    const int wpb = KMCF_BLOCK / 64;
     const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-    for (int s = blockIdx.x * wpb + (threadIdx.x >> 6); s < n_loc; s += gridDim.x * wpb) {
-        const int sg = s0 + s;
-        const double xi = tx[sg], yi = ty[sg], zi = tz[sg], cbi = tcb[sg];
-        const int fi = tinfo[sg];
-        long long off = voff[s];
-        long long dpos = -1;
-        double rowsum = 0.0;
-        for (int g = 0; g < n_groups; ++g) {
-            const unsigned long long mk = mask[(size_t)s * n_groups + g];
-            if (mk == 0ull) continue;                                      // wave-uniform
-            if ((mk >> lane) & 1ull) {
-                const int j = g * 64 + lane;
-                const long long pos = off + __popcll(mk & lt);
-                if (j == sg) dpos = pos;
-                else {
-                    bool c2t;
-                    tunnel_pair(fi, tinfo[j], cbi, tcb[j], tol, &c2t);
-                    const double v = wkb_value(dist(xi, yi, zi, tx[j], ty[j], tz[j]), cbi, tcb[j], c2t, m_e, V0);
-                    val[pos] = v;
-                    rowsum += v;
-                }
-            }
-            off += __popcll(mk);
-        }
-        rowsum = kmcf_wave_sum64(rowsum);
-        if (dpos >= 0) val[dpos] = -rowsum;                                // :685
-        if (lane == 0) tdiag[s] = -rowsum;                                 // :680
+    for (int g = 0; g < n_groups; ++g) {
+        const unsigned long long mk = mrow[g];
+        if (mk == 0ull) continue;                                          // wave-uniform
+        if ((mk >> lane) & 1ull) body(g * 64 + lane, off + __popcll(mk & lt));
+        off += __popcll(mk);
     }
 }
 
-// The row sums alone, by tunnel_value_kernel's walk and in its order of addition (lane = column of a mask word, one wave
-// sum per row), nothing stored but rowsum[s0 + s]: the tunnel diagonal of a PERIODIC state held as tiles.  A row's sum
-// then depends on the row alone -- not on the storage form, nor on how a group deals the tiles -- so every form and
-// every group size give the diagonal and the preconditioner of the one-rank bitmap, bit for bit.
+// Values of the set positions + the row's diagonal = -(sum of the others)
+// (populate_T_tunnel_dist2 + calc_diagonal_T_tunnel, :497-614, :669-689).
 template <typename DIST>
-__global__ __launch_bounds__(KMCF_BLOCK) void tunnel_rowsum_kernel(
-    int n_loc, int s0, int n_groups, const int *__restrict__ tinfo, const double *__restrict__ tx, const double *__restrict__ ty,
-    const double *__restrict__ tz, const double *__restrict__ tcb, double tol, double m_e, double V0,
-    const unsigned long long *__restrict__ mask, double *__restrict__ rowsum_out, DIST dist)
+__global__ __launch_bounds__(KMCF_BLOCK) void tunnel_value_kernel(int n_loc, int s0, int n_groups, t_points P, t_wkb w,
+                                                                  const unsigned long long *__restrict__ mask, const long long *__restrict__ voff,
+                                                                  double *__restrict__ val, double *__restrict__ tdiag, DIST dist)
 {
-    const int lane = threadIdx.x & 63;
-    const int wpb = KMCF_BLOCK / 64;
-    for (int s = blockIdx.x * wpb + (threadIdx.x >> 6); s < n_loc; s += gridDim.x * wpb) {
+    bitmap_rows(n_loc, [&](int s) {
         const int sg = s0 + s;
-        const double xi = tx[sg], yi = ty[sg], zi = tz[sg], cbi = tcb[sg];
-        const int fi = tinfo[sg];
+        const t_point pi = load_point(P, sg);
+        long long dpos = -1;
         double rowsum = 0.0;
-        for (int g = 0; g < n_groups; ++g) {
-            const unsigned long long mk = mask[(size_t)s * n_groups + g];
-            if (mk == 0ull) continue;                                      // wave-uniform
-            const int j = g * 64 + lane;
-            if (((mk >> lane) & 1ull) && j != sg) {
-                bool c2t;
-                tunnel_pair(fi, tinfo[j], cbi, tcb[j], tol, &c2t);
-                rowsum += wkb_value(dist(xi, yi, zi, tx[j], ty[j], tz[j]), cbi, tcb[j], c2t, m_e, V0);
-            }
-        }
+        bitmap_row(mask + (size_t)s * n_groups, n_groups, voff[s], [&](int j, long long pos) {
+            if (j == sg) { dpos = pos; return; }
+            const double v = pair_value<false>(pi, load_point(P, j), w, dist);
+            val[pos] = v;
+            rowsum += v;
+        });
         rowsum = kmcf_wave_sum64(rowsum);
-        if (lane == 0) rowsum_out[sg] = rowsum;
-    }
+        if (dpos >= 0) val[dpos] = -rowsum;                                // :685
+        if ((threadIdx.x & 63) == 0) tdiag[s] = -rowsum;                   // :680
+    });
+}
+
+// The row sums alone, in tunnel_value_kernel's order of addition, nothing stored but rowsum[s0 + s]: the tunnel diagonal
+// of a PERIODIC state held as tiles.  A row's sum then depends on the row alone -- not on the storage form, nor on how a
+// group deals the tiles -- so every form and every group size give the diagonal and the preconditioner of the one-rank
+// bitmap, bit for bit.
+template <typename DIST>
+__global__ __launch_bounds__(KMCF_BLOCK) void tunnel_rowsum_kernel(int n_loc, int s0, int n_groups, t_points P, t_wkb w,
+                                                                   const unsigned long long *__restrict__ mask, double *__restrict__ rowsum_out, DIST dist)
+{
+    bitmap_rows(n_loc, [&](int s) {
+        const int sg = s0 + s;
+        const t_point pi = load_point(P, sg);
+        double rowsum = 0.0;
+        bitmap_row(mask + (size_t)s * n_groups, n_groups, 0, [&](int j, long long) {
+            if (j != sg) rowsum += pair_value<false>(pi, load_point(P, j), w, dist);
+        });
+        rowsum = kmcf_wave_sum64(rowsum);
+        if ((threadIdx.x & 63) == 0) rowsum_out[sg] = rowsum;
+    });
 }
 
 // assemble_preconditioner + invert_diag (src/current_solver_gpu.cu:1323-1338), rhs (:1627-1632)
@@ -590,66 +634,45 @@ __global__ __launch_bounds__(KMCF_BLOCK) void power_neighbour_kernel(int n_loc, 
                                                                      const int *__restrict__ col_node, const double *__restrict__ m,
                                                                      double Vd, double *__restrict__ psum, double *__restrict__ isum)
 {
-    constexpr int RPB = KMCF_BLOCK / LPR;
-    const int lane = threadIdx.x % LPR;
-    const int groups = (n_loc + RPB - 1) / RPB;
-    for (int grp = blockIdx.x; grp < groups; grp += gridDim.x) {
-        const int r = grp * RPB + threadIdx.x / LPR;
-        const bool valid = r < n_loc;
-        double a = 0.0, b = 0.0;
-        if (valid) {
+    double mr = 0.0;
+    neighbour_walk<LPR, double, 2>(
+        n_loc, row_ptr, diag_pos,
+        [&](int r) {
             const int nr = col_node[r];
-            if (nr >= 2) {
-                const double mr = m[nr];
-                const int dpos = diag_pos[r];
-                for (int j = row_ptr[r] + lane; j < row_ptr[r + 1]; j += LPR) {
-                    if (j == dpos) continue;
-                    const int nc = col_node[col[j]];
-                    if (nc < 2) continue;
-                    const double mc = m[nc];
-                    const double ig = ineg_of(val[j], mr, mc, Vd);
-                    a += ig * mc;
-                    b += ig;
-                }
-            }
-        }
-#pragma unroll
-        for (int off = LPR / 2; off >= 1; off >>= 1) { a += __shfl_xor(a, off, 64); b += __shfl_xor(b, off, 64); }
-        if (valid && lane == 0) { psum[r] = a; isum[r] = b; }
-    }
+            if (nr >= 2) mr = m[nr];
+            return nr >= 2;
+        },
+        [&](int j, double *ab) {
+            const int nc = col_node[col[j]];
+            if (nc < 2) return;
+            const double mc = m[nc];
+            const double ig = ineg_of(val[j], mr, mc, Vd);
+            ab[0] += ig * mc;
+            ab[1] += ig;
+        },
+        [&](int r, int, const double *ab) { psum[r] = ab[0]; isum[r] = ab[1]; });
 }
 
-// tunnel part, added into the same per-row sums (a wave per local sub row)
+// tunnel part, added into the same per-row sums: the stored values of the bitmap's rows
 __global__ __launch_bounds__(KMCF_BLOCK) void power_tunnel_kernel(
     int n_loc, int s0, int n_groups, const unsigned long long *__restrict__ mask, const long long *__restrict__ voff,
     const double *__restrict__ val, const int *__restrict__ tidx, const int *__restrict__ rows, const double *__restrict__ m,
     double Vd, double *__restrict__ psum, double *__restrict__ isum)
 {
-    const int lane = threadIdx.x & 63;
-    const int wpb = KMCF_BLOCK / 64;
-    const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-    for (int s = blockIdx.x * wpb + (threadIdx.x >> 6); s < n_loc; s += gridDim.x * wpb) {
+    bitmap_rows(n_loc, [&](int s) {
         const int sg = s0 + s;
         const double mr = m[tidx[sg] + 2];
-        long long off = voff[s];
         double a = 0.0, b = 0.0;
-        for (int g = 0; g < n_groups; ++g) {
-            const unsigned long long mk = mask[(size_t)s * n_groups + g];
-            if (mk == 0ull) continue;
-            if ((mk >> lane) & 1ull) {
-                const int j = g * 64 + lane;
-                if (j != sg) {
-                    const double mc = m[tidx[j] + 2];
-                    const double ig = ineg_of(val[off + __popcll(mk & lt)], mr, mc, Vd);
-                    a += ig * mc;
-                    b += ig;
-                }
-            }
-            off += __popcll(mk);
-        }
+        bitmap_row(mask + (size_t)s * n_groups, n_groups, voff[s], [&](int j, long long pos) {
+            if (j == sg) return;
+            const double mc = m[tidx[j] + 2];
+            const double ig = ineg_of(val[pos], mr, mc, Vd);
+            a += ig * mc;
+            b += ig;
+        });
         a = kmcf_wave_sum64(a); b = kmcf_wave_sum64(b);
-        if (lane == 0) { psum[rows[s]] += a; isum[rows[s]] += b; }
-    }
+        if ((threadIdx.x & 63) == 0) { psum[rows[s]] += a; isum[rows[s]] += b; }
+    });
 }
 
 // P[r] into the row-partitioned pdisp (global row order)
@@ -681,10 +704,8 @@ constexpr int SYM_WAVE_DOUBLES = 64 * SYM_LD + 256;          // tile + four 64-v
 // Values of the upper tiles (populate_T_tunnel_dist2 on the pairs of the tile; 0 where the pattern has no entry, on
 // the diagonal -- set afterwards -- and past the last point).  A wave per strip, lane = column, rows one by one.
 template <typename DIST>
-__global__ __launch_bounds__(KMCF_BLOCK) void tunnel_dense_fill_kernel(
-    int n_strips, const int4 *__restrict__ strips, int n_glob, const int *__restrict__ tinfo, const double *__restrict__ tx,
-    const double *__restrict__ ty, const double *__restrict__ tz, const double *__restrict__ tcb, double nn_dist, double tol,
-    double m_e, double V0, double *__restrict__ tiles, DIST dist)
+__global__ __launch_bounds__(KMCF_BLOCK) void tunnel_dense_fill_kernel(int n_strips, const int4 *__restrict__ strips, int n_glob, t_points P,
+                                                                       t_wkb w, double *__restrict__ tiles, DIST dist)
 {
     const int lane = threadIdx.x & 63;
     for (int s = blockIdx.x * 4 + (threadIdx.x >> 6); s < n_strips; s += gridDim.x * 4) {
@@ -692,18 +713,12 @@ __global__ __launch_bounds__(KMCF_BLOCK) void tunnel_dense_fill_kernel(
         for (int q = 0; q < st.z; ++q) {
             const int J = st.y + q, j = 64 * J + lane;
             const bool jin = j < n_glob;
-            const double xj = jin ? tx[j] : 0.0, yj = jin ? ty[j] : 0.0, zj = jin ? tz[j] : 0.0, cbj = jin ? tcb[j] : 0.0;
-            const int fj = jin ? tinfo[j] : 0;
+            const t_point pj = jin ? load_point(P, j) : t_point{};
             double *tile = tiles + ((size_t)st.w + q) * 4096;
             for (int r = 0; r < 64; ++r) {
                 const int i = 64 * st.x + r;
                 double v = 0.0;
-                if (i < n_glob && jin && i != j) {
-                    bool c2t;
-                    const double cbi = tcb[i];
-                    const double d = dist(tx[i], ty[i], tz[i], xj, yj, zj);
-                    if (d > nn_dist && tunnel_pair(tinfo[i], fj, cbi, cbj, tol, &c2t)) v = wkb_value(d, cbi, cbj, c2t, m_e, V0);
-                }
+                if (i < n_glob && jin && i != j) v = pair_value<true>(load_point(P, i), pj, w, dist);
                 tile[r * 64 + lane] = v;
             }
         }
@@ -851,19 +866,16 @@ __global__ __launch_bounds__(KMCF_BLOCK) void symj_mask_kernel(int n_strips, con
 
 // values in layer order (populate_T_tunnel_dist2 on the tile's entries; the diagonal entry 0 until symj_set_diag_kernel)
 template <typename DIST>
-__global__ __launch_bounds__(KMCF_BLOCK) void symj_fill_kernel(
-    int n_strips, const int4 *__restrict__ strips, int n_glob, const int *__restrict__ tinfo, const double *__restrict__ tx,
-    const double *__restrict__ ty, const double *__restrict__ tz, const double *__restrict__ tcb, double tol, double m_e, double V0,
-    const symj_u64 *__restrict__ jmask, const long long *__restrict__ jvoff, double *__restrict__ jval, DIST dist)
+__global__ __launch_bounds__(KMCF_BLOCK) void symj_fill_kernel(int n_strips, const int4 *__restrict__ strips, int n_glob, t_points P, t_wkb w,
+                                                               const symj_u64 *__restrict__ jmask, const long long *__restrict__ jvoff,
+                                                               double *__restrict__ jval, DIST dist)
 {
     const int lane = threadIdx.x & 63;
     const symj_u64 lt = lane ? (~0ull >> (64 - lane)) : 0ull;
     for (int s = blockIdx.x * 4 + (threadIdx.x >> 6); s < n_strips; s += gridDim.x * 4) {
         const int4 st = strips[s];
         const int i = 64 * st.x + lane;
-        const bool iin = i < n_glob;
-        const double xi = iin ? tx[i] : 0.0, yi = iin ? ty[i] : 0.0, zi = iin ? tz[i] : 0.0, cbi = iin ? tcb[i] : 0.0;
-        const int fi = iin ? tinfo[i] : 0;
+        const t_point pi = i < n_glob ? load_point(P, i) : t_point{};
         for (int q = 0; q < st.z; ++q) {
             const size_t t = (size_t)st.w + q;
             symj_u64 m = jmask[t * 64 + lane];
@@ -874,14 +886,7 @@ __global__ __launch_bounds__(KMCF_BLOCK) void symj_fill_kernel(
                 if (m) {
                     const int j = 64 * (st.y + q) + __builtin_ctzll(m);
                     m &= m - 1;
-                    double v = 0.0;
-                    if (j != i) {
-                        bool c2t;
-                        const double cbj = tcb[j];
-                        tunnel_pair(fi, tinfo[j], cbi, cbj, tol, &c2t);
-                        v = wkb_value(dist(xi, yi, zi, tx[j], ty[j], tz[j]), cbi, cbj, c2t, m_e, V0);
-                    }
-                    jval[base + __popcll(b & lt)] = v;
+                    jval[base + __popcll(b & lt)] = j != i ? pair_value<false>(pi, load_point(P, j), w, dist) : 0.0;
                 }
                 base += __popcll(b);
             }
@@ -1195,77 +1200,52 @@ __global__ __launch_bounds__(KMCF_BLOCK) void gather_tunnel_pot_kernel(int n_glo
 // Per node r of the T matrix three sums over the stored off-diagonals (r, c) of its row, I_rc = g (m_r - m_c) with
 // g = -A_rc: sum |I_rc|, the same over tunnel pairs only, and sum I_rc; kept interleaved in cm[3 node + 0 / 1 / 2] so that
 // one all-gather moves them.  The virtual-virtual entry (0, 1) / (1, 0) -- the loop_G driver -- is no pair.
-// Neighbour part: LPR lanes per internal row (power_neighbour_kernel's walk), virtual rows included; sets all three.
+// Neighbour part (neighbour_walk, virtual rows included): sets all three.
 template <int LPR>
 __global__ __launch_bounds__(KMCF_BLOCK) void current_neighbour_kernel(int n_loc, const int *__restrict__ row_ptr, const int *__restrict__ col,
                                                                        const double *__restrict__ val, const int *__restrict__ diag_pos,
                                                                        const int *__restrict__ col_node, const double *__restrict__ m,
                                                                        double *__restrict__ cm)
 {
-    constexpr int RPB = KMCF_BLOCK / LPR;
-    const int lane = threadIdx.x % LPR;
-    const int groups = (n_loc + RPB - 1) / RPB;
-    for (int grp = blockIdx.x; grp < groups; grp += gridDim.x) {
-        const int r = grp * RPB + threadIdx.x / LPR;
-        const bool valid = r < n_loc;
-        double a = 0.0, b = 0.0;
-        int nr = 0;
-        if (valid) {
-            nr = col_node[r];
-            const double mr = m[nr];
-            const int dpos = diag_pos[r];
-            for (int j = row_ptr[r] + lane; j < row_ptr[r + 1]; j += LPR) {
-                if (j == dpos) continue;
-                const int nc = col_node[col[j]];
-                if (nr < 2 && nc < 2) continue;                        // (0, 1) / (1, 0)
-                const double g = -val[j];
-                const double i_rc = g * (mr - m[nc]);
-                a += fabs(i_rc);
-                b += i_rc;
-            }
-        }
-#pragma unroll
-        for (int off = LPR / 2; off >= 1; off >>= 1) { a += __shfl_xor(a, off, 64); b += __shfl_xor(b, off, 64); }
-        if (valid && lane == 0) { cm[3 * (size_t)nr] = a; cm[3 * (size_t)nr + 1] = 0.0; cm[3 * (size_t)nr + 2] = b; }
-    }
+    int nr = 0;
+    double mr = 0.0;
+    neighbour_walk<LPR, double, 2>(
+        n_loc, row_ptr, diag_pos,
+        [&](int r) { nr = col_node[r]; mr = m[nr]; return true; },
+        [&](int j, double *ab) {
+            const int nc = col_node[col[j]];
+            if (nr < 2 && nc < 2) return;                              // (0, 1) / (1, 0)
+            const double g = -val[j];
+            const double i_rc = g * (mr - m[nc]);
+            ab[0] += fabs(i_rc);
+            ab[1] += i_rc;
+        },
+        [&](int, int, const double *ab) { cm[3 * (size_t)nr] = ab[0]; cm[3 * (size_t)nr + 1] = 0.0; cm[3 * (size_t)nr + 2] = ab[1]; });
 }
 
-// Tunnel part: a wave per local row of the pair bitmap (tunnel_value_kernel's walk), lane = column of a mask word; the
-// conductance of every set pair is evaluated afresh (one symmetric expression per pair: the same value whatever
-// storage the solve uses), the row's sums go into the slots of its node (after the neighbour part, same stream).
+// Tunnel part (the bitmap's rows): the conductance of every set pair is evaluated afresh -- pair_value: the same value
+// whatever storage the solve uses --, the row's sums go into the slots of its node (after the neighbour part, same stream).
 template <typename DIST>
-__global__ __launch_bounds__(KMCF_BLOCK) void current_tunnel_kernel(
-    int n_loc, int s0, int n_groups, const int *__restrict__ tinfo, const double *__restrict__ tx, const double *__restrict__ ty,
-    const double *__restrict__ tz, const double *__restrict__ tcb, double tol, double m_e, double V0,
-    const unsigned long long *__restrict__ mask, const int *__restrict__ tidx, const double *__restrict__ m, double *__restrict__ cm, DIST dist)
+__global__ __launch_bounds__(KMCF_BLOCK) void current_tunnel_kernel(int n_loc, int s0, int n_groups, t_points P, t_wkb w,
+                                                                    const unsigned long long *__restrict__ mask, const int *__restrict__ tidx,
+                                                                    const double *__restrict__ m, double *__restrict__ cm, DIST dist)
 {
-    const int lane = threadIdx.x & 63;
-    const int wpb = KMCF_BLOCK / 64;
-    for (int s = blockIdx.x * wpb + (threadIdx.x >> 6); s < n_loc; s += gridDim.x * wpb) {
+    bitmap_rows(n_loc, [&](int s) {
         const int sg = s0 + s;
-        const double xi = tx[sg], yi = ty[sg], zi = tz[sg], cbi = tcb[sg];
-        const int fi = tinfo[sg];
+        const t_point pi = load_point(P, sg);
         const int node = tidx[sg] + 2;
         const double mr = m[node];
         double a = 0.0, b = 0.0;
-        for (int g = 0; g < n_groups; ++g) {
-            const unsigned long long mk = mask[(size_t)s * n_groups + g];
-            if (mk == 0ull) continue;                                      // wave-uniform
-            if ((mk >> lane) & 1ull) {
-                const int j = g * 64 + lane;
-                if (j != sg) {
-                    bool c2t;
-                    tunnel_pair(fi, tinfo[j], cbi, tcb[j], tol, &c2t);
-                    const double gc = -wkb_value(dist(xi, yi, zi, tx[j], ty[j], tz[j]), cbi, tcb[j], c2t, m_e, V0);
-                    const double i_rc = gc * (mr - m[tidx[j] + 2]);
-                    a += fabs(i_rc);
-                    b += i_rc;
-                }
-            }
-        }
+        bitmap_row(mask + (size_t)s * n_groups, n_groups, 0, [&](int j, long long) {
+            if (j == sg) return;
+            const double gc = -pair_value<false>(pi, load_point(P, j), w, dist);
+            const double i_rc = gc * (mr - m[tidx[j] + 2]);
+            a += fabs(i_rc);
+            b += i_rc;
+        });
         a = kmcf_wave_sum64(a); b = kmcf_wave_sum64(b);
-        if (lane == 0) { cm[3 * (size_t)node] += a; cm[3 * (size_t)node + 1] = a; cm[3 * (size_t)node + 2] += b; }
-    }
+        if ((threadIdx.x & 63) == 0) { cm[3 * (size_t)node] += a; cm[3 * (size_t)node + 1] = a; cm[3 * (size_t)node + 2] += b; }
+    });
 }
 
 // site arrays (zero-filled before): through = half of sum |I|, tunnel likewise, net; atoms with a row only
@@ -1362,123 +1342,98 @@ __global__ __launch_bounds__(KMCF_BLOCK) void profile_key_kernel(int n_atoms, co
     }
 }
 
-// one counted pair a -> s carrying i_as into the sums of a
+// The slab and cell of every atom, as the pair kernels take them
+struct cp_keys { const int *q, *cell; int n_cells; };
+
+// The sums of one row while its pairs are walked: CP_SAME / CP_REST / CP_NET, and with VEC the three of the vector behind
+// them -- without it they do not exist, so nothing shuffles or adds them.
+constexpr int CP_SAME = 0, CP_REST = 1, CP_NET = 2, CP_JX = 3;
+
+// One counted pair a -> s carrying i_as into the sums of a.  s is the other ATOM; its coordinates are cx / cy / cz[cs]: the
+// atoms' arrays at s (neighbour part) or the tunnel points' at the point's index (tunnel part; tx[j] == ax[tidx[j]]).
 template <bool VEC, typename DIST>
-__device__ __forceinline__ void profile_add_pair(double i_as, int a, int s, int qa, int ca, int n_cells, const int *__restrict__ q,
-                                                 const int *__restrict__ cell, const double *__restrict__ ax, const double *__restrict__ ay,
-                                                 const double *__restrict__ az, double xa, double ya, double za, const DIST &dist,
-                                                 double &same, double &rest, double &jx, double &jy, double &jz)
+__device__ __forceinline__ void profile_add_pair(double i_as, int s, int cs, int qa, int ca, const cp_keys &K, const double *__restrict__ cx,
+                                                 const double *__restrict__ cy, const double *__restrict__ cz, double xa, double ya, double za,
+                                                 const DIST &dist, double *sums)
 {
-    if (q[s] != qa) {
-        if (ca < n_cells && cell[s] == ca) same += i_as; else rest += i_as;
+    if (K.q[s] != qa) {
+        if (ca < K.n_cells && K.cell[s] == ca) sums[CP_SAME] += i_as; else sums[CP_REST] += i_as;
     }
-    if (VEC) {
+    if constexpr (VEC) {
         double dy, dz;
-        pair_disp(dist, ya, za, ay[s], az[s], &dy, &dz);
-        jx += i_as * (ax[s] - xa); jy += i_as * dy; jz += i_as * dz;
+        pair_disp(dist, ya, za, cy[cs], cz[cs], &dy, &dz);
+        sums[CP_JX] += i_as * (cx[cs] - xa); sums[CP_JX + 1] += i_as * dy; sums[CP_JX + 2] += i_as * dz;
     }
 }
 
-// Neighbour part: current_neighbour_kernel's walk (LPR lanes per internal row, virtual rows included); sets all
-// CP_STRIDE values of the row's node.
+// Neighbour part (neighbour_walk, virtual rows included); sets all CP_STRIDE values of the row's node.
 template <int LPR, bool VEC, typename DIST>
 __global__ __launch_bounds__(KMCF_BLOCK) void profile_neighbour_kernel(
     int n_loc, const int *__restrict__ row_ptr, const int *__restrict__ col, const double *__restrict__ val, const int *__restrict__ diag_pos,
-    const int *__restrict__ col_node, const double *__restrict__ m, const int *__restrict__ q, const int *__restrict__ cell, int n_cells,
-    const double *__restrict__ ax, const double *__restrict__ ay, const double *__restrict__ az, double *__restrict__ pv, DIST dist)
+    const int *__restrict__ col_node, const double *__restrict__ m, cp_keys K, const double *__restrict__ ax, const double *__restrict__ ay,
+    const double *__restrict__ az, double *__restrict__ pv, DIST dist)
 {
-    constexpr int RPB = KMCF_BLOCK / LPR;
-    const int lane = threadIdx.x % LPR;
-    const int groups = (n_loc + RPB - 1) / RPB;
-    for (int grp = blockIdx.x; grp < groups; grp += gridDim.x) {
-        const int r = grp * RPB + threadIdx.x / LPR;
-        const bool valid = r < n_loc;
-        double same = 0.0, rest = 0.0, jx = 0.0, jy = 0.0, jz = 0.0, net = 0.0;
-        int nr = 0;
-        if (valid) {
+    int nr = 0, qa = 0, ca = 0;
+    double mr = 0.0, xa = 0.0, ya = 0.0, za = 0.0;
+    neighbour_walk<LPR, double, VEC ? 6 : 3>(
+        n_loc, row_ptr, diag_pos,
+        [&](int r) {
             nr = col_node[r];
-            const double mr = m[nr];
-            const int dpos = diag_pos[r];
+            mr = m[nr];
             const int a = nr - 2;
-            int qa = 0, ca = 0;
-            double xa = 0.0, ya = 0.0, za = 0.0;
             if (a >= 0) {
-                qa = q[a]; ca = cell[a];
+                qa = K.q[a]; ca = K.cell[a];
                 if (VEC) { xa = ax[a]; ya = ay[a]; za = az[a]; }
             }
-            for (int j = row_ptr[r] + lane; j < row_ptr[r + 1]; j += LPR) {
-                if (j == dpos) continue;
-                const int nc = col_node[col[j]];
-                if (nr < 2 && nc < 2) continue;                        // (0, 1) / (1, 0)
-                const double g = -val[j];
-                const double i_rc = g * (mr - m[nc]);
-                net += i_rc;
-                if (a >= 0 && nc >= 2) profile_add_pair<VEC>(i_rc, a, nc - 2, qa, ca, n_cells, q, cell, ax, ay, az, xa, ya, za, dist, same, rest, jx, jy, jz);
-            }
-        }
-#pragma unroll
-        for (int off = LPR / 2; off >= 1; off >>= 1) {
-            same += __shfl_xor(same, off, 64); rest += __shfl_xor(rest, off, 64); net += __shfl_xor(net, off, 64);
-            if (VEC) { jx += __shfl_xor(jx, off, 64); jy += __shfl_xor(jy, off, 64); jz += __shfl_xor(jz, off, 64); }
-        }
-        if (valid && lane == 0) {
+            return true;
+        },
+        [&](int j, double *sums) {
+            const int nc = col_node[col[j]];
+            if (nr < 2 && nc < 2) return;                              // (0, 1) / (1, 0)
+            const double g = -val[j];
+            const double i_rc = g * (mr - m[nc]);
+            sums[CP_NET] += i_rc;
+            if (nr >= 2 && nc >= 2) profile_add_pair<VEC>(i_rc, nc - 2, nc - 2, qa, ca, K, ax, ay, az, xa, ya, za, dist, sums);
+        },
+        [&](int, int, const double *sums) {
             double *v = pv + CP_STRIDE * (size_t)nr;
-            v[0] = same; v[1] = rest; v[2] = 0.0; v[3] = 0.0; v[4] = jx; v[5] = jy; v[6] = jz; v[7] = net;
-        }
-    }
+            v[0] = sums[CP_SAME]; v[1] = sums[CP_REST]; v[2] = 0.0; v[3] = 0.0; v[7] = sums[CP_NET];
+            if constexpr (VEC) { v[4] = sums[CP_JX]; v[5] = sums[CP_JX + 1]; v[6] = sums[CP_JX + 2]; }
+            else v[4] = v[5] = v[6] = 0.0;
+        });
 }
 
-// Tunnel part: current_tunnel_kernel's walk (a wave per local row of the pair bitmap, the conductance of every set pair
-// evaluated afresh); sets [2] / [3] and adds onto [4 .. 7] of the row's node (after the neighbour part, same stream).
+// Tunnel part (the bitmap's rows, every set pair's conductance by pair_value); sets [2] / [3] and adds onto [4 .. 7] of the
+// row's node (after the neighbour part, same stream).
 template <bool VEC, typename DIST>
-__global__ __launch_bounds__(KMCF_BLOCK) void profile_tunnel_kernel(
-    int n_loc, int s0, int n_groups, const int *__restrict__ tinfo, const double *__restrict__ tx, const double *__restrict__ ty,
-    const double *__restrict__ tz, const double *__restrict__ tcb, double tol, double m_e, double V0,
-    const unsigned long long *__restrict__ mask, const int *__restrict__ tidx, const double *__restrict__ m, const int *__restrict__ q,
-    const int *__restrict__ cell, int n_cells, double *__restrict__ pv, DIST dist)
+__global__ __launch_bounds__(KMCF_BLOCK) void profile_tunnel_kernel(int n_loc, int s0, int n_groups, t_points P, t_wkb w,
+                                                                    const unsigned long long *__restrict__ mask, const int *__restrict__ tidx,
+                                                                    const double *__restrict__ m, cp_keys K, double *__restrict__ pv, DIST dist)
 {
-    const int lane = threadIdx.x & 63;
-    const int wpb = KMCF_BLOCK / 64;
-    for (int s = blockIdx.x * wpb + (threadIdx.x >> 6); s < n_loc; s += gridDim.x * wpb) {
+    bitmap_rows(n_loc, [&](int s) {
         const int sg = s0 + s;
-        const double xi = tx[sg], yi = ty[sg], zi = tz[sg], cbi = tcb[sg];
-        const int fi = tinfo[sg];
+        const t_point pi = load_point(P, sg);
         const int a = tidx[sg];
         const double mr = m[a + 2];
-        const int qa = q[a], ca = cell[a];
-        double same = 0.0, rest = 0.0, jx = 0.0, jy = 0.0, jz = 0.0, net = 0.0;
-        for (int g = 0; g < n_groups; ++g) {
-            const unsigned long long mk = mask[(size_t)s * n_groups + g];
-            if (mk == 0ull) continue;                                      // wave-uniform
-            if ((mk >> lane) & 1ull) {
-                const int j = g * 64 + lane;
-                if (j != sg) {
-                    bool c2t;
-                    tunnel_pair(fi, tinfo[j], cbi, tcb[j], tol, &c2t);
-                    const double gc = -wkb_value(dist(xi, yi, zi, tx[j], ty[j], tz[j]), cbi, tcb[j], c2t, m_e, V0);
-                    const int b = tidx[j];
-                    const double i_rc = gc * (mr - m[b + 2]);
-                    net += i_rc;
-                    // (the tunnel points' coordinates are the atoms': tx[j] == ax[tidx[j]], indexed by point here)
-                    if (q[b] != qa) {
-                        if (ca < n_cells && cell[b] == ca) same += i_rc; else rest += i_rc;
-                    }
-                    if (VEC) {
-                        double dy, dz;
-                        pair_disp(dist, yi, zi, ty[j], tz[j], &dy, &dz);
-                        jx += i_rc * (tx[j] - xi); jy += i_rc * dy; jz += i_rc * dz;
-                    }
-                }
-            }
-        }
-        same = kmcf_wave_sum64(same); rest = kmcf_wave_sum64(rest); net = kmcf_wave_sum64(net);
-        if (VEC) { jx = kmcf_wave_sum64(jx); jy = kmcf_wave_sum64(jy); jz = kmcf_wave_sum64(jz); }
-        if (lane == 0) {
+        const int qa = K.q[a], ca = K.cell[a];
+        constexpr int NS = VEC ? 6 : 3;
+        double sums[NS] = {};
+        bitmap_row(mask + (size_t)s * n_groups, n_groups, 0, [&](int j, long long) {
+            if (j == sg) return;
+            const double gc = -pair_value<false>(pi, load_point(P, j), w, dist);
+            const int b = tidx[j];
+            const double i_rc = gc * (mr - m[b + 2]);
+            sums[CP_NET] += i_rc;
+            profile_add_pair<VEC>(i_rc, b, j, qa, ca, K, P.x, P.y, P.z, pi.x, pi.y, pi.z, dist, sums);
+        });
+#pragma unroll
+        for (int k = 0; k < NS; ++k) sums[k] = kmcf_wave_sum64(sums[k]);
+        if ((threadIdx.x & 63) == 0) {
             double *v = pv + CP_STRIDE * ((size_t)a + 2);
-            v[2] = same; v[3] = rest; v[7] += net;
-            if (VEC) { v[4] += jx; v[5] += jy; v[6] += jz; }
+            v[2] = sums[CP_SAME]; v[3] = sums[CP_REST]; v[7] += sums[CP_NET];
+            if constexpr (VEC) { v[4] += sums[CP_JX]; v[5] += sums[CP_JX + 1]; v[6] += sums[CP_JX + 2]; }
         }
-    }
+    });
 }
 
 // Binning, in two steps without atomics.  The atoms with a row are cut into n_seg segments of seg_len atoms (a multiple of
@@ -1619,6 +1574,9 @@ int strip_grid(int n_strips) { return std::max(1, std::min((n_strips + 3) / 4, 8
 
 // f(the state's distance functor): where the geometry of a state picks the instantiation of a kernel that BOTH geometries
 // run.  (One kernel only a periodic state runs, tunnel_rowsum_kernel<dist_min_image>, is launched by symm_diagonal itself.)
+t_points points_of(const kmcf_tstate *t) { return {t->d_tinfo, t->d_tx, t->d_ty, t->d_tz, t->d_tcb}; }
+t_wkb wkb_of(const kmcf_tstate *t) { return {t->nn_dist, t->par.tol, t->par.m_e, t->par.V0}; }
+
 template <typename F>
 void with_dist(const kmcf_tstate *t, F f)
 {
@@ -2096,7 +2054,6 @@ static int symm_fill_jagged(kmcf_tstate *t)
 {
     kmcf_subop &sb = t->sub;
     hipStream_t st = t->comm->stream;
-    const kmcf_current_params_t *p = &t->par;
     const int grid = strip_grid(sb.n_strips);
     KMCF_TRY(ensure(&sb.d_jmask, &sb.cap_jmask, (size_t)sb.n_tiles * 64));
     KMCF_TRY(ensure(&sb.d_jcnt, &sb.cap_jcnt, (size_t)sb.n_tiles + 1));
@@ -2110,8 +2067,8 @@ static int symm_fill_jagged(kmcf_tstate *t)
     sb.jnnz = t->h_pin->jnnz;
     KMCF_TRY(ensure(&sb.d_jval, &sb.cap_jval, (size_t)sb.jnnz + 64));
     with_dist(t, [&](auto dist) {
-        symj_fill_kernel<decltype(dist)><<<grid, KMCF_BLOCK, 0, st>>>(sb.n_strips, sb.d_strips, sb.n_glob, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz, t->d_tcb,
-                                                                      p->tol, p->m_e, p->V0, sb.d_jmask, sb.d_jvoff, sb.d_jval, dist);
+        symj_fill_kernel<decltype(dist)><<<grid, KMCF_BLOCK, 0, st>>>(sb.n_strips, sb.d_strips, sb.n_glob, points_of(t), wkb_of(t), sb.d_jmask, sb.d_jvoff,
+                                                                      sb.d_jval, dist);
     });
     KMCF_HIP(hipGetLastError());
     return KMCF_OK;
@@ -2120,10 +2077,9 @@ static int symm_fill_jagged(kmcf_tstate *t)
 static int symm_fill_dense(kmcf_tstate *t)
 {
     kmcf_subop &sb = t->sub;
-    const kmcf_current_params_t *p = &t->par;
     with_dist(t, [&](auto dist) {
-        tunnel_dense_fill_kernel<decltype(dist)><<<strip_grid(sb.n_strips), KMCF_BLOCK, 0, t->comm->stream>>>(
-            sb.n_strips, sb.d_strips, sb.n_glob, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz, t->d_tcb, t->nn_dist, p->tol, p->m_e, p->V0, sb.d_tiles, dist);
+        tunnel_dense_fill_kernel<decltype(dist)><<<strip_grid(sb.n_strips), KMCF_BLOCK, 0, t->comm->stream>>>(sb.n_strips, sb.d_strips, sb.n_glob, points_of(t),
+                                                                                                             wkb_of(t), sb.d_tiles, dist);
     });
     KMCF_HIP(hipGetLastError());
     return KMCF_OK;
@@ -2143,11 +2099,9 @@ static int symm_diagonal(kmcf_tstate *t)
     hipStream_t st = t->comm->stream;
     const int n_t = sb.n_glob, nb = sb.nb;
     if (t->pbc) {
-        const kmcf_current_params_t *p = &t->par;
         if (sb.n_loc > 0)
             tunnel_rowsum_kernel<dist_min_image><<<wave_row_grid(sb.n_loc), KMCF_BLOCK, 0, st>>>(
-                sb.n_loc, sb.row0, sb.n_groups, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz, t->d_tcb, p->tol, p->m_e, p->V0, sb.d_mask, t->d_tdiag,
-                dist_min_image{t->lattice[1], t->lattice[2]});
+                sb.n_loc, sb.row0, sb.n_groups, points_of(t), wkb_of(t), sb.d_mask, t->d_tdiag, dist_min_image{t->lattice[1], t->lattice[2]});
         KMCF_HIP(hipGetLastError());
         if (sb.spread) KMCF_TRY(kmcf_comm_allgatherv_double(t->comm, t->d_tdiag, sb.counts.data(), sb.displs.data()));
     } else {
@@ -2274,8 +2228,8 @@ static int asm_bitmap_pattern(kmcf_tstate *t)
                "tunnel block: %d tunnel points exceed the row-offset scan's range (256 rows of that many entries in an int)", n_t);
     sub_rows_kernel<<<kmcf_grid1d(ns), KMCF_BLOCK, 0, st>>>(ns, sb.row0, t->d_tidx, t->T->row0, t->d_inv_perm, sb.d_rows);
     with_dist(t, [&](auto dist) {
-        tunnel_mask_kernel<decltype(dist)><<<wave_row_grid(ns), KMCF_BLOCK, 0, st>>>(ns, sb.row0, n_t, sb.n_groups, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz,
-                                                                                     t->d_tcb, t->nn_dist, t->par.tol, sb.d_mask, t->d_rowcnt, dist);
+        tunnel_mask_kernel<decltype(dist)><<<wave_row_grid(ns), KMCF_BLOCK, 0, st>>>(ns, sb.row0, n_t, sb.n_groups, points_of(t), wkb_of(t), sb.d_mask,
+                                                                                     t->d_rowcnt, dist);
     });
     kmcf_scan_counts_kernel<long long><<<1, KMCF_BLOCK, 0, st>>>(ns, t->d_rowcnt, sb.d_voff, 0);
     KMCF_HIP(hipGetLastError());
@@ -2324,16 +2278,14 @@ static int asm_choose_storage(kmcf_tstate *t)
 static int asm_values(kmcf_tstate *t)
 {
     kmcf_subop &sb = t->sub;
-    const kmcf_current_params_t *p = &t->par;
     const int ns = sb.n_loc;
     if (sb.dense) {
         KMCF_TRY(symm_setup(t));
     } else if (ns > 0) {
         KMCF_TRY(ensure(&sb.d_val, &sb.cap_val, (size_t)sb.nnz + 64));
         with_dist(t, [&](auto dist) {
-            tunnel_value_kernel<decltype(dist)><<<wave_row_grid(ns), KMCF_BLOCK, 0, t->comm->stream>>>(
-                ns, sb.row0, sb.n_groups, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz, t->d_tcb, t->nn_dist, p->tol, p->m_e, p->V0, sb.d_mask, sb.d_voff, sb.d_val,
-                t->d_tdiag, dist);
+            tunnel_value_kernel<decltype(dist)><<<wave_row_grid(ns), KMCF_BLOCK, 0, t->comm->stream>>>(ns, sb.row0, sb.n_groups, points_of(t), wkb_of(t),
+                                                                                                       sb.d_mask, sb.d_voff, sb.d_val, t->d_tdiag, dist);
         });
         KMCF_HIP(hipGetLastError());
     }
@@ -2508,9 +2460,8 @@ static int tunnel_rows_recomputed(const kmcf_tstate *t, double *h_val)
     KMCF_HIP(hipMalloc(reinterpret_cast<void **>(&d_v), ((size_t)sb.nnz + 64) * sizeof(double)));
     if (hipMalloc(reinterpret_cast<void **>(&d_dg), ((size_t)ns + 1) * sizeof(double)) != hipSuccess) { hipFree(d_v); KMCF_HIP(hipErrorOutOfMemory); }
     with_dist(t, [&](auto dist) {
-        tunnel_value_kernel<decltype(dist)><<<wave_row_grid(ns), KMCF_BLOCK, 0, t->comm->stream>>>(
-            ns, sb.row0, sb.n_groups, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz, t->d_tcb, t->nn_dist, t->par.tol, t->par.m_e, t->par.V0, sb.d_mask, sb.d_voff, d_v,
-            d_dg, dist);
+        tunnel_value_kernel<decltype(dist)><<<wave_row_grid(ns), KMCF_BLOCK, 0, t->comm->stream>>>(ns, sb.row0, sb.n_groups, points_of(t), wkb_of(t),
+                                                                                                   sb.d_mask, sb.d_voff, d_v, d_dg, dist);
     });
     hipError_t e1 = hipGetLastError();
     if (e1 == hipSuccess) e1 = hipStreamSynchronize(t->comm->stream);
@@ -2691,9 +2642,8 @@ extern "C" int kmcf_current_map(kmcf_tstate *t, const double *d_atom_virtual_pot
     }
     if (sb.n_loc > 0) {
         with_dist(t, [&](auto dist) {
-            current_tunnel_kernel<decltype(dist)><<<wave_row_grid(sb.n_loc), KMCF_BLOCK, 0, st>>>(
-                sb.n_loc, sb.row0, sb.n_groups, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz, t->d_tcb, t->par.tol, t->par.m_e, t->par.V0, sb.d_mask, t->d_tidx, pot,
-                t->d_cmap, dist);
+            current_tunnel_kernel<decltype(dist)><<<wave_row_grid(sb.n_loc), KMCF_BLOCK, 0, st>>>(sb.n_loc, sb.row0, sb.n_groups, points_of(t), wkb_of(t),
+                                                                                                  sb.d_mask, t->d_tidx, pot, t->d_cmap, dist);
         });
         KMCF_HIP(hipGetLastError());
     }
@@ -2790,16 +2740,15 @@ extern "C" int kmcf_current_profile(kmcf_tstate *t, const double *d_atom_virtual
                                                               t->d_cpcell);
     KMCF_HIP(hipGetLastError());
     // this rank's rows: the neighbour part sets the values of a node, the tunnel part adds the row's pairs of the bitmap
+    const cp_keys keys{t->d_cpq, t->d_cpcell, n_cells};
     auto walk = [&](auto dist, auto with_vec) {
         constexpr bool VEC = decltype(with_vec)::value;
         if (n_loc > 0)
             profile_neighbour_kernel<16, VEC, decltype(dist)><<<kmcf_grid1d((int64_t)n_loc * 16), KMCF_BLOCK, 0, st>>>(
-                n_loc, m->d_row_ptr, m->d_col, m->d_val, t->d_diag_pos, t->d_col_node, pot, t->d_cpq, t->d_cpcell, n_cells, t->d_ax, t->d_ay, t->d_az,
-                t->d_cprof, dist);
+                n_loc, m->d_row_ptr, m->d_col, m->d_val, t->d_diag_pos, t->d_col_node, pot, keys, t->d_ax, t->d_ay, t->d_az, t->d_cprof, dist);
         if (sb.n_loc > 0)
             profile_tunnel_kernel<VEC, decltype(dist)><<<wave_row_grid(sb.n_loc), KMCF_BLOCK, 0, st>>>(
-                sb.n_loc, sb.row0, sb.n_groups, t->d_tinfo, t->d_tx, t->d_ty, t->d_tz, t->d_tcb, t->par.tol, t->par.m_e, t->par.V0, sb.d_mask, t->d_tidx, pot,
-                t->d_cpq, t->d_cpcell, n_cells, t->d_cprof, dist);
+                sb.n_loc, sb.row0, sb.n_groups, points_of(t), wkb_of(t), sb.d_mask, t->d_tidx, pot, keys, t->d_cprof, dist);
     };
     with_dist(t, [&](auto dist) {
         if (vec) walk(dist, std::true_type{}); else walk(dist, std::false_type{});
